@@ -1,17 +1,21 @@
 #!/usr/bin/env python3
 """Headline benchmark: BN254 pairings/s (+ G1/G2 scalar-mults/s) at batch 2^20 per MI355X  (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 One step = one pass of the hot path over one batch: B independent bn254.Pair calls (Miller-loop kernels +
 final-exponentiation kernel) on synthetic random points P_i=[k("P",i)]g1, Q_i=[k("Q",i)]g2,
 inputs and outputs resident in HBM.  Each rank owns its own batch of B pairs (weak scaling, no data-path
-collective: SURVEY.md §8e); value = pairs all ranks processed / max-over-ranks time.  Every rank bit-compares a
-sample of its own outputs with the oracle and the run fails if any rank disagrees.
+collective: SURVEY.md §8e); value = pairs all ranks processed / max-over-ranks time.
 
-Extra objects on the JSON line:
+A plain run only sets up, warms up, times the K steps and prints the headline line.  --dump-outputs DIR then writes a
+fixed, seeded sample of rank 0's GT values from the last timed step (the bytes a caller of the path receives, one float32
+per byte, exact) as DIR/pair_gt.npy, and the batch indices of its rows as DIR/pair_gt_index.npy: the inputs are the same
+from run to run, so two builds can be compared output for output.  --full adds everything below: every rank bit-compares
+a sample of its own outputs with the oracle and the run fails if any rank disagrees, and these objects join the line
+(--no-secondary, --no-configs, --no-cpu and --no-scalar-mul trim them):
   roofline     the single kernel with the largest time per step (rocprofv3 agrees: profiles/) against the VALU integer-MAC
                roofline: algorithmic MACs per launch (nominal Fp-mul x 136 MAC x pairs) / its mean duration
                from HIP events on the launch stream (gpbc_profile_begin / _end bracket every launch).  peak = measured
@@ -54,6 +58,18 @@ NOMINAL_FP_MUL = {"k_miller_lines": 2000, "k_miller_accumulate": 5000, "k_final_
 EXECUTED_MAD = {}                         # filled from profiles/executed_mads.json (tests/test_device_math_bounds.py writes it: exact counts of the device code)
 PEAK_TMAC_PER_S = 34.9                    # measured: v_mad_u64_u32, 8 waves/SIMD (profiles/r01_microbench_valu.txt)
 HBM_PEAK_GBS = 8000.0
+DUMP_ROWS = 32768                         # --dump-outputs: at most this many GT values (x 384 bytes x float32 = 48 MiB)
+
+
+def dump_outputs(out_dir, gt):
+    """--dump-outputs: the last timed step's GT values, a fixed seeded sample of rows when the batch has more than DUMP_ROWS, as
+    out_dir/pair_gt.npy (rows x 384, one float32 per byte of gnark's in-memory struct: exact) + out_dir/pair_gt_index.npy (float64)."""
+    n = gt.shape[0]
+    idx = np.arange(n) if n <= DUMP_ROWS else np.sort(np.random.default_rng(wl.SEED).choice(n, DUMP_ROWS, replace=False))
+    rows = gt[torch.from_numpy(idx).to(gt.device)].cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "pair_gt.npy"), rows.astype(np.float32))
+    np.save(os.path.join(out_dir, "pair_gt_index.npy"), idx.astype(np.float64))
 
 
 def usable_cpus():
@@ -124,12 +140,17 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--batch", type=int, default=1 << 20, help="pairs per GPU per step (metric: 2^20)")
-    ap.add_argument("--no-secondary", action="store_true", help="headline line only (scalar-mult rates, extras and config legs skipped)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the BASELINE config 2-4 legs")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline (profiling runs)")
-    ap.add_argument("--no-scalar-mul", action="store_true", help="skip the G1/G2 scalar-mult half of the metric (roofline.scalar_mul)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write a fixed sample of the last timed step's GT values to DIR (rank 0)")
+    ap.add_argument("--full", action="store_true", help="also the oracle check, per-kernel roofline, scalar-mult rates, extras, "
+                                                         "config legs, PCIe / latency / CPU baselines (trimmed by the --no-* options)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the extras and config legs")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the BASELINE config 2-4 legs")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline (profiling runs)")
+    ap.add_argument("--no-scalar-mul", action="store_true", help="with --full: skip the G1/G2 scalar-mult half of the metric (roofline.scalar_mul)")
     ap.add_argument("--config-scale", type=int, default=1, help="divide the config-leg sizes by this (quick runs; 1 = BASELINE sizes)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -230,12 +251,43 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
-    _lib.check(lib.gpbc_profile_begin(stream))           # HIP events around every kernel of the timed steps, on their stream
+    if args.full:
+        _lib.check(lib.gpbc_profile_begin(stream))       # HIP events around every kernel of the timed steps, on their stream
     t0 = time.perf_counter()
     for s in range(args.steps):
         step()
     barrier()
-    dt = time.perf_counter() - t0
+    dt = max_over_ranks(time.perf_counter() - t0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gt)
+
+    value = world * B * args.steps / dt
+    result = {
+        "metric": "BN254 pairings/s at batch 2^20 per GPU (+ G1/G2 scalar-mults/s at the same batch in roofline.scalar_mul)",
+        "value": value, "unit": "pairings/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "int64", "data": "synthetic",
+        "config": {"workload": "configs[1]: batch of %d independent bn254.Pair on random (G1,G2) points per GPU" % B,
+                   "batch_per_gpu": B, "sharding": "independent index ranges per rank, no data-path collective",
+                   "arithmetic": "254-bit Montgomery integers as 9 signed 29-bit limbs (int32), 32x32+64-bit MACs into int64 columns"},
+    }
+    if rehearsal:
+        result["config"]["rehearsal"] = ("NOT A MEASUREMENT: %d ranks share one GPU (GPBC_BENCH_REHEARSAL), torch.distributed on gloo, " % world) + \
+            ("library communicator over the rccl TEST DOUBLE of tests/stub_rccl" if rehearsal_stub else "no library communicator")
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(result))
+        if use_dist:
+            dist.barrier()
+            try:
+                bn254.comm_destroy()
+            except Exception:                             # noqa: BLE001
+                pass
+            dist.destroy_process_group()
+
+    if not args.full:
+        return finish()
     names = ctypes.create_string_buffer(32 * 16)
     ms = (ctypes.c_double * 16)()
     cnt = (ctypes.c_int * 16)()
@@ -245,7 +297,6 @@ def main():
     for i in range(nk.value):
         nm = names.raw[32 * i:32 * i + 32].split(b"\0")[0].decode()
         kern[nm] = {"ms_per_step": ms[i] / args.steps, "launches_per_step": cnt[i] / args.steps, "ms_per_launch": ms[i] / cnt[i]}
-    dt = max_over_ranks(dt)
     # the roofline's denominator and the shader clock, measured in this process right after the timed steps (rank 0's device)
     probe = (ctypes.c_double * 4)()
     _lib.check(lib.gpbc_valu_probe(probe))
@@ -264,22 +315,8 @@ def main():
     if not all_ranks_true(sample_ok):
         raise SystemExit("PARITY FAILURE: rank %d: GPU pairings differ from the oracle on its sample" % rank if not sample_ok
                          else "PARITY FAILURE on another rank")
-
-    value = world * B * args.steps / dt
-    result = {
-        "metric": "BN254 pairings/s at batch 2^20 per GPU (+ G1/G2 scalar-mults/s at the same batch in roofline.scalar_mul)",
-        "value": value, "unit": "pairings/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "int64", "data": "synthetic",
-        "config": {"workload": "configs[1]: batch of %d independent bn254.Pair on random (G1,G2) points per GPU; every rank "
-                               "bit-compares %d of its outputs with the oracle (in-repo restatement: parity with gnark-crypto "
-                               "itself is unpinned, tests/test_gnark_vectors.py)" % (B, len(si)),
-                   "batch_per_gpu": B, "sharding": "independent index ranges per rank, no data-path collective",
-                   "arithmetic": "254-bit Montgomery integers as 9 signed 29-bit limbs (int32), 32x32+64-bit MACs into int64 columns"},
-    }
-    if rehearsal:
-        result["config"]["rehearsal"] = ("NOT A MEASUREMENT: %d ranks share one GPU (GPBC_BENCH_REHEARSAL), torch.distributed on gloo, " % world) + \
-            ("library communicator over the rccl TEST DOUBLE of tests/stub_rccl" if rehearsal_stub else "no library communicator")
+    result["config"]["workload"] += ("; every rank bit-compares %d of its outputs with the oracle (in-repo restatement: parity with "
+                                     "gnark-crypto itself is unpinned, tests/test_gnark_vectors.py)" % len(si))
     # ---- roofline, VALU integer-MAC bound: the single kernel with the largest time per step
     frac = lambda fpmul, t_ms: fpmul * MAC_PER_FP_MUL * B / (t_ms * 1e-3) / 1e12 / PEAK_TMAC_PER_S
     # VALU instructions per wave of the same kernels from the last committed PMC pass (tools/pmc_run.sh -> profiles/pmc_counters.json):
@@ -646,15 +683,7 @@ def main():
             raise
         except Exception as exc:                          # noqa: BLE001
             result["concurrent_calls"] = {"error": repr(exc)}
-    if rank == 0:
-        print(json.dumps(result))
-    if use_dist:
-        dist.barrier()
-        try:
-            bn254.comm_destroy()
-        except Exception:                                 # noqa: BLE001
-            pass
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -655,7 +655,7 @@ def test_two_process_ranks_over_the_test_double(eng, tmp_path):
     # test runner is one of them; the 8-rank arithmetic runs in one process above.
     for ranks, batch, scale, port in ((2, "16384", "64", "29531"), (4, "16387", "61", "29533")):
         out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1", "--master-port", port,
-                              os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "1", "--warmup", "1", "--batch", batch, "--config-scale", scale, "--no-cpu"],
+                              os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "1", "--warmup", "1", "--batch", batch, "--config-scale", scale, "--full", "--no-cpu"],
                              capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
         assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
         line = json.loads(out.stdout.strip().splitlines()[-1])
