@@ -129,6 +129,16 @@ static inline unsigned grid_for(size_t n) { return (unsigned)((n + BLOCK - 1) / 
 int check_launch(const char *what);
 void profile_mark(const char *kernel_name, hipStream_t st);   // bench.py's per-kernel timing (gpbc_profile_begin / _end); a no-op otherwise
 int sync_default();
+// Every kernel launch of the library: launch on `stream`, check it, and mark the stream for the per-kernel timing under the kernel's
+// own name; evaluates to the status.  GPBC_LAUNCH_AS names the kernel explicitly (a template whose arguments hold a comma, passed in
+// parentheses).
+#define GPBC_LAUNCH_AS(name, kernel, grid, block, stream, ...) ([&]() {   \
+        kernel<<<(grid), (block), 0, (stream)>>>(__VA_ARGS__);          \
+        const int rc_ = check_launch(name);                             \
+        if (rc_ == GPBC_OK) profile_mark(name, (stream));               \
+        return rc_;                                                     \
+    }())
+#define GPBC_LAUNCH(kernel, grid, block, stream, ...) GPBC_LAUNCH_AS(#kernel, kernel, grid, block, stream, __VA_ARGS__)
 
 // RAII device buffer for the host-pointer entry points
 // Device blocks of the host-pointer entries.  hipMalloc / hipFree per call cost 0.1-0.2 ms on a good day and, now and then, 10 ms and
@@ -230,31 +240,62 @@ struct CallLane {
     bool busy = false;
     int reserve(size_t pin_need, size_t dev_need);  // grow-only; called by the batch runner before it writes anything
 };
-struct SmallCall {
-    const void *in[3] = {nullptr, nullptr, nullptr};   // caller's input columns (meaning per kind)
-    bool in_one[3] = {false, false, false};            // column holds ONE element for all units (a shared base)
-    void *out[2] = {nullptr, nullptr};
-    size_t units = 0;                                  // pairs / points / GT elements
+// A host-pointer call of n units: its columns and, for the combined route, what the combiner needs besides.
+struct HostCall {
+    const void *in[3] = {nullptr, nullptr, nullptr};   // input columns (meaning per entry); null = none
+    size_t in_bytes[3] = {0, 0, 0};                    // bytes per unit, or of the whole column with in_one
+    bool in_one[3] = {false, false, false};            // column holds ONE element for all units (a shared base, the fixed-Q list)
+    void *out[2] = {nullptr, nullptr};                 // output columns; null = not wanted
+    size_t out_bytes[2] = {0, 0};                      // bytes per unit
+    int n_in = 0, n_out = 0;
+    static constexpr size_t UNITS_N = ~(size_t)0;
+    size_t units = UNITS_N;                            // what the combiner's cap counts: pairs / points / terms (UNITS_N: the n of the call)
+    bool in_place = false;                             // output column 0 lives in the device copy of input column 0 (same bytes per unit)
     const uint64_t *seg = nullptr;                     // CALL_PAIRS: the call's own segment table (segs + 1 entries); null = one pair per segment
-    size_t segs = 0;                                   //   (CALL_HASH_*: seg = the call's message offsets, units + 1 entries)
+                                                       //   (CALL_HASH_*: seg = the call's message offsets, units + 1 entries)
     // Calls of one kind share a launch only if their keys are equal byte for byte: the domain-separation tag of a hash (a kernel
     // argument), the table handle of a fixed-base sum.  No key: every call of the kind combines.
     const void *key = nullptr;
     size_t key_len = 0;
+    HostCall &input(const void *p, size_t bytes, bool one = false) { in[n_in] = p; in_bytes[n_in] = bytes; in_one[n_in++] = one; return *this; }
+    HostCall &output(void *p, size_t bytes) { out[n_out] = p; out_bytes[n_out++] = bytes; return *this; }
+};
+struct SmallCall : HostCall {
+    size_t segs = 0;                                   // the call's n: segments / points / GT elements / sums / messages
     int rc = GPBC_OK;
     char err[512] = "";
     bool taken = false, done = false;
     std::condition_variable cv;
 };
-using SmallBatchFn = int (*)(CallLane &lane, SmallCall *const *calls, size_t n_calls);
+using SmallBatchFn = int (*)(SmallKind kind, CallLane &lane, SmallCall *const *calls, size_t n_calls);
 // Runs `c` through the combiner of the calling thread's current device; returns the call's status with gpbc_last_error() set.
 int small_call(SmallKind kind, SmallCall &c, SmallBatchFn run);
+// The batch runner of the elementwise kinds: the calls' rows of every input column one after the other in the lane's pinned block (a
+// column of one element repeated per row), the outputs behind them; `launch` gets the device (and host) addresses of the columns and the rows,
+// reserves the lane's device block for itself and enqueues on lane.stream; the runner waits for that stream and hands out the slices.
+using RowsLaunch = std::function<int(const uint8_t *const *in, const uint8_t *const *in_host, uint8_t *const *out, size_t rows)>;
+int small_rows_run(CallLane &lane, SmallCall *const *calls, size_t n_calls, const RowsLaunch &launch);
 // The same lanes for small calls that are NOT combined (wire formats, hash to curve, fixed-base sums: one call = one launch): the caller
 // takes a free lane (waits for one), stages through its pinned block, launches on its stream, waits for that stream alone — off the null
 // stream and without the device-wide synchronisation a DevBuf costs when it is freed, so such a call neither waits for the batches of
 // other threads nor makes them wait.  body runs on the calling thread with the lane's buffers reserved by itself (lane.reserve).
 int with_call_lane(const std::function<int(CallLane &)> &body);
 constexpr size_t LANE_CALL_MAX_UNITS = 16384;       // elements per such call (the quad-of-lanes kernels' range); larger calls keep the bulk path
+// Host-pointer calls on the current device: host_call binds it and takes the first route that applies — the combined small call
+// (small_call of `kind` with `run`, 0 < units <= small_max), a call lane of its own (0 < units <= lane_max), pipelined chunks
+// (n >= 2 * pipe_chunk; per-unit columns travel chunk by chunk) or device blocks (DevBuf: upload, body on stream 0, sync_default,
+// download).  The body gets the device copies of the columns (null where the host column is null) and `tmp`, tmp_bytes of device
+// memory of its own (lane and device-block routes).  host_call_sharded cuts [0, n) with run_sharded (min_units), slices the
+// per-unit columns and runs host_call on every part; whole columns travel unsliced.
+struct HostRoute {
+    SmallKind kind = CALL_KINDS;
+    SmallBatchFn run = nullptr;
+    size_t small_max = 0, lane_max = 0, pipe_chunk = 0, tmp_bytes = 0;
+};
+struct DevCols { const uint8_t *in[3]; uint8_t *out[2]; uint8_t *tmp; };
+using HostCallBody = std::function<int(const DevCols &d, size_t n, hipStream_t st)>;
+int host_call(size_t n, const HostCall &c, const HostRoute &r, const HostCallBody &body);
+int host_call_sharded(size_t n, size_t min_units, const HostCall &c, const HostRoute &r, const HostCallBody &body);
 void free_call_lanes();
 
 #endif

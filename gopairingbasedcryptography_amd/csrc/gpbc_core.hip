@@ -186,7 +186,7 @@ int small_call(SmallKind kind, SmallCall &c, SmallBatchFn run) {
         int rc = GPBC_OK;
         if (!lane->stream && hipStreamCreateWithFlags(&lane->stream, hipStreamNonBlocking) != hipSuccess) rc = fail(GPBC_ERR_HIP, "hipStreamCreateWithFlags failed for a call lane");
         if (rc == GPBC_OK) {
-            try { rc = run(*lane, batch.data(), batch.size()); }
+            try { rc = run(kind, *lane, batch.data(), batch.size()); }
             catch (const std::exception &e) { rc = fail(GPBC_ERR_INTERNAL, "small-call batch: %s", e.what()); }      // (allocation failure of a host table: no exception may cross the C ABI)
         }
         if (rc != GPBC_OK && lane->stream) (void)hipStreamSynchronize(lane->stream);      // nothing of a failed batch may still be running when the lane is reused
@@ -248,6 +248,35 @@ int with_call_lane(const std::function<int(CallLane &)> &body) {
     }
     return rc;
 }
+int small_rows_run(CallLane &lane, SmallCall *const *calls, size_t nc, const RowsLaunch &launch) {
+    const HostCall &h = *calls[0];                               // (the calls of a batch share one kind and key: their column widths agree)
+    size_t N = 0, off[5], total = 0;
+    for (size_t c = 0; c < nc; c++) N += calls[c]->segs;
+    for (int i = 0; i < 5; i++) { off[i] = total; total += Scratch::padded(N * (i < 3 ? h.in_bytes[i] : h.out_bytes[i - 3])); }
+    TRY(lane.reserve(total, 0));
+    size_t n0 = 0;
+    for (size_t c = 0; c < nc; c++) {
+        const SmallCall &r = *calls[c];
+        for (int i = 0; i < 3; i++) {
+            const size_t w = h.in_bytes[i];
+            if (r.in_one[i]) for (size_t j = 0; j < r.segs; j++) memcpy(lane.pin + off[i] + (n0 + j) * w, r.in[i], w);
+            else if (w) memcpy(lane.pin + off[i] + n0 * w, r.in[i], r.segs * w);
+        }
+        n0 += r.segs;
+    }
+    const uint8_t *in[3] = {lane.d_pin + off[0], lane.d_pin + off[1], lane.d_pin + off[2]};
+    const uint8_t *in_host[3] = {lane.pin + off[0], lane.pin + off[1], lane.pin + off[2]};
+    uint8_t *out[2] = {lane.d_pin + off[3], lane.d_pin + off[4]};
+    TRY(launch(in, in_host, out, N));
+    HIP_TRY(hipStreamSynchronize(lane.stream));
+    n0 = 0;
+    for (size_t c = 0; c < nc; c++) {
+        for (int i = 0; i < 2; i++)
+            if (calls[c]->out[i]) memcpy(calls[c]->out[i], lane.pin + off[3 + i] + n0 * h.out_bytes[i], calls[c]->segs * h.out_bytes[i]);
+        n0 += calls[c]->segs;
+    }
+    return GPBC_OK;
+}
 void free_call_lanes() {
     int keep = -1;
     (void)hipGetDevice(&keep);
@@ -263,6 +292,87 @@ void free_call_lanes() {
         }
     }
     if (keep >= 0) (void)hipSetDevice(keep);
+}
+
+// ---- host-pointer calls (gpbc_common.hpp: host_call)
+static size_t in_col_bytes(const HostCall &c, int i, size_t n) { return c.in_one[i] ? c.in_bytes[i] : n * c.in_bytes[i]; }
+int host_call(size_t n, const HostCall &c, const HostRoute &r, const HostCallBody &body) {
+    TRY(bind_device());
+    const size_t units = c.units == HostCall::UNITS_N ? n : c.units;
+    if (r.run && units && units <= r.small_max) {
+        SmallCall s;
+        static_cast<HostCall &>(s) = c;
+        s.units = units; s.segs = n;
+        return small_call(r.kind, s, r.run);
+    }
+    if (units && units <= r.lane_max)
+        return with_call_lane([&](CallLane &l) {
+            size_t off[5], total = 0;
+            for (int i = 0; i < 5; i++) { off[i] = total; total += Scratch::padded(i < 3 ? in_col_bytes(c, i, n) : n * c.out_bytes[i - 3]); }
+            TRY(l.reserve(total, r.tmp_bytes));
+            if (c.in_place) off[3] = off[0];
+            DevCols d{};
+            for (int i = 0; i < 3; i++) if (c.in[i]) { if (in_col_bytes(c, i, n)) memcpy(l.pin + off[i], c.in[i], in_col_bytes(c, i, n)); d.in[i] = l.d_pin + off[i]; }
+            for (int i = 0; i < 2; i++) if (c.out[i]) d.out[i] = l.d_pin + off[3 + i];
+            d.tmp = l.dev;
+            TRY(body(d, n, l.stream));
+            HIP_TRY(hipStreamSynchronize(l.stream));
+            for (int i = 0; i < 2; i++) if (c.out[i]) memcpy(c.out[i], l.pin + off[3 + i], n * c.out_bytes[i]);
+            return (int)GPBC_OK;
+        });
+    const bool pipe = r.pipe_chunk && n >= 2 * r.pipe_chunk;
+    DevBuf din[3], dout[2], dtmp;
+    DevCols d{};
+    for (int i = 0; i < 3; i++) {
+        if (!c.in[i]) continue;
+        TRY(pipe && !c.in_one[i] ? din[i].alloc(n * c.in_bytes[i]) : din[i].upload(c.in[i], in_col_bytes(c, i, n)));
+        d.in[i] = din[i].u8();
+    }
+    for (int i = 0; i < 2; i++) {
+        if (!c.out[i]) continue;
+        if (i == 0 && c.in_place) { d.out[0] = din[0].u8(); continue; }
+        TRY(dout[i].alloc(n * c.out_bytes[i]));
+        d.out[i] = dout[i].u8();
+    }
+    if (r.tmp_bytes) { TRY(dtmp.alloc(r.tmp_bytes)); d.tmp = dtmp.u8(); }
+    if (!pipe) {
+        TRY(body(d, n, nullptr));
+        TRY(sync_default());
+        for (int i = 0; i < 2; i++) if (c.out[i]) TRY((i == 0 && c.in_place ? din[0] : dout[i]).download(c.out[i], n * c.out_bytes[i]));
+        return GPBC_OK;
+    }
+    // upload / kernels / download of neighbouring chunks overlap on the slot's two streams (pipelined_chunks)
+    auto at = [&](size_t off) {
+        DevCols s = d;
+        for (int i = 0; i < 3; i++) if (s.in[i] && !c.in_one[i]) s.in[i] += off * c.in_bytes[i];
+        for (int i = 0; i < 2; i++) if (s.out[i]) s.out[i] += off * c.out_bytes[i];
+        return s;
+    };
+    const int rc = pipelined_chunks(n, r.pipe_chunk,
+        [&](size_t off, size_t m, hipStream_t st) {
+            const DevCols s = at(off);
+            for (int i = 0; i < 3; i++)
+                if (c.in[i] && !c.in_one[i])
+                    HIP_TRY(hipMemcpyAsync((void *)s.in[i], (const uint8_t *)c.in[i] + off * c.in_bytes[i], m * c.in_bytes[i], hipMemcpyHostToDevice, st));
+            return (int)GPBC_OK;
+        },
+        [&](size_t off, size_t m, hipStream_t st) { return body(at(off), m, st); },
+        [&](size_t off, size_t m, hipStream_t st) {
+            const DevCols s = at(off);
+            for (int i = 0; i < 2; i++)
+                if (c.out[i]) HIP_TRY(hipMemcpyAsync((uint8_t *)c.out[i] + off * c.out_bytes[i], s.out[i], m * c.out_bytes[i], hipMemcpyDeviceToHost, st));
+            return (int)GPBC_OK;
+        });
+    if (rc != GPBC_OK) (void)hipDeviceSynchronize();          // nothing may still use the buffers when they are freed
+    return rc;
+}
+int host_call_sharded(size_t n, size_t min_units, const HostCall &c, const HostRoute &r, const HostCallBody &body) {
+    return run_sharded(n, min_units, [&](size_t lo, size_t hi) {
+        HostCall s = c;
+        for (int i = 0; i < 3; i++) if (s.in[i] && !s.in_one[i]) s.in[i] = (const uint8_t *)s.in[i] + lo * s.in_bytes[i];
+        for (int i = 0; i < 2; i++) if (s.out[i]) s.out[i] = (uint8_t *)s.out[i] + lo * s.out_bytes[i];
+        return host_call(hi - lo, s, r, body);
+    });
 }
 
 // ---- internal workspace, one grow-only buffer per (bound device slot, stream)
@@ -439,8 +549,8 @@ int comm_allgather(const void *d_send, size_t bytes, void *d_recv, hipStream_t s
     return GPBC_OK;
 }
 
-// ---- per-kernel timing for bench.py (HIP events on the launch stream).  Entries call profile_mark(name, stream) right
-// after a launch; with profiling on, that records an event, and the time between consecutive marks of a stream is the
+// ---- per-kernel timing for bench.py (HIP events on the launch stream).  Every launch (GPBC_LAUNCH) marks its stream under
+// the kernel's name; with profiling on, that records an event, and the time between consecutive marks of a stream is the
 // duration of the kernel that ended at the later one (the stream is kept busy, so there are no gaps to speak of).
 struct ProfMark { char name[32]; hipEvent_t ev; };
 static std::mutex g_prof_mu;
@@ -673,15 +783,13 @@ int gpbc_valu_probe(double *out4) {
     HIP_TRY(hipMemset(d.p, 0, 3 * sizeof(uint64_t)));
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    k_valu_probe<<<ncu * waves_per_simd, 256>>>((uint64_t *)d.p, 16, 3u, 5u);        // warm-up (clocks, code object)
+    int rc = GPBC_LAUNCH(k_valu_probe, ncu * waves_per_simd, 256, nullptr, (uint64_t *)d.p, 16, 3u, 5u);      // warm-up (clocks, code object)
     float best = 1e30f;
     uint64_t h[3] = {0, 0, 0}, hb[3] = {0, 0, 0};
-    int rc = check_launch("k_valu_probe");
     for (int rep = 0; rep < 3 && rc == GPBC_OK; rep++) {
         float ms = 0;
         if (hipEventRecord(e0, nullptr) != hipSuccess) rc = fail(GPBC_ERR_HIP, "hipEventRecord failed");
-        k_valu_probe<<<ncu * waves_per_simd, 256>>>((uint64_t *)d.p, iters, 3u, 5u);
-        if (rc == GPBC_OK) rc = check_launch("k_valu_probe");
+        if (rc == GPBC_OK) rc = GPBC_LAUNCH(k_valu_probe, ncu * waves_per_simd, 256, nullptr, (uint64_t *)d.p, iters, 3u, 5u);
         if (rc == GPBC_OK && (hipEventRecord(e1, nullptr) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess)) rc = fail(GPBC_ERR_HIP, "timing of the probe failed");
         if (rc == GPBC_OK) rc = d.download(h, sizeof h);
         if (rc == GPBC_OK && ms < best) { best = ms; memcpy(hb, h, sizeof h); }
@@ -704,8 +812,7 @@ int gpbc_fp_mul_batch(const void *a, const void *b, size_t n, void *out) {
     TRY(bind_device());
     DevBuf dA, dB, dO;
     TRY(dA.upload(a, n * 32)); TRY(dB.upload(b, n * 32)); TRY(dO.alloc(n * 32));
-    k_fp_mul<<<grid_for(n), BLOCK>>>(dA.u8(), dB.u8(), dO.u8(), n);
-    TRY(check_launch("k_fp_mul"));
+    TRY(GPBC_LAUNCH(k_fp_mul, grid_for(n), BLOCK, nullptr, dA.u8(), dB.u8(), dO.u8(), n));
     TRY(sync_default());
     return dO.download(out, n * 32);
 }

@@ -215,17 +215,13 @@ static int shared_base_mul_dev(bool g2, const void *d_base, const void *d_scalar
         int32_t *tabws = nullptr;
         rc = stream_workspace(st, (size_t)FB_ENTRIES * tab_bytes, &tabws);
         if (rc == GPBC_OK) {
-            if (g2) k_g2_fb_build<<<grid_for(FB_ENTRIES), BLOCK, 0, st>>>((const uint8_t *)d_base, 1, table, base_inf, tabws, 0, FB_ENTRIES);
-            else k_g1_fb_build<<<grid_for(FB_ENTRIES), BLOCK, 0, st>>>((const uint8_t *)d_base, 1, table, base_inf, tabws, 0, FB_ENTRIES);
-            rc = check_launch("k_fb_build");
-            profile_mark(g2 ? "k_g2_fb_build" : "k_g1_fb_build", st);
+            if (g2) rc = GPBC_LAUNCH(k_g2_fb_build, grid_for(FB_ENTRIES), BLOCK, st, (const uint8_t *)d_base, 1, table, base_inf, tabws, 0, FB_ENTRIES);
+            else rc = GPBC_LAUNCH(k_g1_fb_build, grid_for(FB_ENTRIES), BLOCK, st, (const uint8_t *)d_base, 1, table, base_inf, tabws, 0, FB_ENTRIES);
         }
     }
     if (rc == GPBC_OK) {
-        if (g2) k_g2_fb_msm<<<grid_for(n), BLOCK, 0, st>>>(table, base_inf, 1, (const uint8_t *)d_scalars, n, 1, 1, (uint8_t *)d_out);
-        else k_g1_fb_msm<<<grid_for(n), BLOCK, 0, st>>>(table, base_inf, 1, (const uint8_t *)d_scalars, n, 1, 1, (uint8_t *)d_out);
-        rc = check_launch("k_fb_msm");
-        profile_mark(g2 ? "k_g2_fb_msm" : "k_g1_fb_msm", st);
+        if (g2) rc = GPBC_LAUNCH(k_g2_fb_msm, grid_for(n), BLOCK, st, table, base_inf, 1, (const uint8_t *)d_scalars, n, 1, 1, (uint8_t *)d_out);
+        else rc = GPBC_LAUNCH(k_g1_fb_msm, grid_for(n), BLOCK, st, table, base_inf, 1, (const uint8_t *)d_scalars, n, 1, 1, (uint8_t *)d_out);
     }
     return rc;
 }
@@ -253,23 +249,11 @@ static int scalar_mul_dev(bool g2, const void *d_bases, size_t nbase, const void
         const size_t m = n - off < chunk ? n - off : chunk;
         const uint8_t *b = (const uint8_t *)d_bases + (shared ? 0 : off * pt), *k = (const uint8_t *)d_scalars + off * GPBC_SCALAR_BYTES;
         uint8_t *o = (uint8_t *)d_out + off * pt;
-        if (g2 && n <= SMUL_OCT_MAX) {
-            k_g2_scalar_mul_oct<<<grid_for(8 * m), BLOCK, 0, st>>>(b, shared, k, o, m, tabws);
-            TRY(check_launch("k_g2_scalar_mul_oct"));
-            profile_mark("k_g2_scalar_mul_oct", st);
-            continue;
-        }
-        if (n <= SMUL_QUAD_MAX) {
-            if (g2) k_g2_scalar_mul_quad<<<grid_for(4 * m), BLOCK, 0, st>>>(b, shared, k, o, m, tabws);
-            else k_g1_scalar_mul_quad<<<grid_for(4 * m), BLOCK, 0, st>>>(b, shared, k, o, m, tabws);
-            TRY(check_launch(g2 ? "k_g2_scalar_mul_quad" : "k_g1_scalar_mul_quad"));
-            profile_mark(g2 ? "k_g2_scalar_mul_quad" : "k_g1_scalar_mul_quad", st);
-            continue;
-        }
-        if (g2) k_g2_scalar_mul<<<grid_for(m), BLOCK, 0, st>>>(b, shared, k, o, m, tabws);
-        else k_g1_scalar_mul<<<grid_for(m), BLOCK, 0, st>>>(b, shared, k, o, m, tabws);
-        TRY(check_launch(g2 ? "k_g2_scalar_mul" : "k_g1_scalar_mul"));
-        profile_mark(g2 ? "k_g2_scalar_mul" : "k_g1_scalar_mul", st);
+        if (g2 && n <= SMUL_OCT_MAX) TRY(GPBC_LAUNCH(k_g2_scalar_mul_oct, grid_for(8 * m), BLOCK, st, b, shared, k, o, m, tabws));
+        else if (g2 && n <= SMUL_QUAD_MAX) TRY(GPBC_LAUNCH(k_g2_scalar_mul_quad, grid_for(4 * m), BLOCK, st, b, shared, k, o, m, tabws));
+        else if (n <= SMUL_QUAD_MAX) TRY(GPBC_LAUNCH(k_g1_scalar_mul_quad, grid_for(4 * m), BLOCK, st, b, shared, k, o, m, tabws));
+        else if (g2) TRY(GPBC_LAUNCH(k_g2_scalar_mul, grid_for(m), BLOCK, st, b, shared, k, o, m, tabws));
+        else TRY(GPBC_LAUNCH(k_g1_scalar_mul, grid_for(m), BLOCK, st, b, shared, k, o, m, tabws));
     }
     return GPBC_OK;
 }
@@ -295,10 +279,8 @@ static int sum_dev(bool g2, const void *d_pts, size_t n, void *d_out, void *d_ws
     for (;;) {
         size_t n_out = (n_in + SUM_FANIN - 1) / SUM_FANIN;
         uint8_t *out = n_out == 1 ? (uint8_t *)d_out : ws;
-        if (g2) k_g2_sum_level<<<grid_for(n_out), BLOCK, 0, (hipStream_t)stream>>>(in, n_in, out, n_out);
-        else k_g1_sum_level<<<grid_for(n_out), BLOCK, 0, (hipStream_t)stream>>>(in, n_in, out, n_out);
-        TRY(check_launch("k_sum_level"));
-        profile_mark(g2 ? "k_g2_sum_level" : "k_g1_sum_level", (hipStream_t)stream);
+        if (g2) TRY(GPBC_LAUNCH(k_g2_sum_level, grid_for(n_out), BLOCK, (hipStream_t)stream, in, n_in, out, n_out));
+        else TRY(GPBC_LAUNCH(k_g1_sum_level, grid_for(n_out), BLOCK, (hipStream_t)stream, in, n_in, out, n_out));
         if (n_out == 1) break;
         in = out; ws += n_out * pt; n_in = n_out;
     }
@@ -311,91 +293,32 @@ constexpr size_t SMUL_PIPE_CHUNK = 131072;
 // Small calls (gpbc_common.hpp "Small host-pointer calls"): every waiting ScalarMultiplication of one group in one launch of the
 // quad-of-lanes kernel on a call lane — bases and scalars read from the lane's pinned block, results written into it, the GLV
 // tables in the lane's device block.  A call with one base for all its scalars gets that base repeated per scalar.
-static int small_mul_run(bool G2, CallLane &lane, SmallCall *const *calls, size_t nc) {
-    const size_t pt = G2 ? GPBC_G2_BYTES : GPBC_G1_BYTES;
-    const size_t tab_bytes = sizeof(int32_t) * (G2 ? (size_t)glv_table_dwords<F2>() : (size_t)glv_table_dwords<Fe>());
-    size_t N = 0;
-    for (size_t c = 0; c < nc; c++) N += calls[c]->units;
-    const size_t oB = 0, oS = Scratch::padded(N * pt), oO = oS + Scratch::padded(N * GPBC_SCALAR_BYTES), total = oO + Scratch::padded(N * pt);
-    TRY(lane.reserve(total, N * tab_bytes));
-    size_t n0 = 0;
-    for (size_t c = 0; c < nc; c++) {
-        const SmallCall &r = *calls[c];
-        if (r.in_one[0]) for (size_t i = 0; i < r.units; i++) memcpy(lane.pin + oB + (n0 + i) * pt, r.in[0], pt);
-        else memcpy(lane.pin + oB + n0 * pt, r.in[0], r.units * pt);
-        memcpy(lane.pin + oS + n0 * GPBC_SCALAR_BYTES, r.in[1], r.units * GPBC_SCALAR_BYTES);
-        n0 += r.units;
-    }
-    if (G2) k_g2_scalar_mul_oct<<<grid_for(8 * N), BLOCK, 0, lane.stream>>>(lane.d_pin + oB, 0, lane.d_pin + oS, lane.d_pin + oO, N, (int32_t *)lane.dev);   // N <= 2 048 = SMUL_OCT_MAX
-    else k_g1_scalar_mul_quad<<<grid_for(4 * N), BLOCK, 0, lane.stream>>>(lane.d_pin + oB, 0, lane.d_pin + oS, lane.d_pin + oO, N, (int32_t *)lane.dev);
-    TRY(check_launch(G2 ? "k_g2_scalar_mul_quad" : "k_g1_scalar_mul_quad"));
-    profile_mark(G2 ? "k_g2_scalar_mul_quad" : "k_g1_scalar_mul_quad", lane.stream);
-    HIP_TRY(hipStreamSynchronize(lane.stream));
-    n0 = 0;
-    for (size_t c = 0; c < nc; c++) { memcpy(calls[c]->out[0], lane.pin + oO + n0 * pt, calls[c]->units * pt); n0 += calls[c]->units; }
-    return GPBC_OK;
+static int small_mul_run(SmallKind kind, CallLane &lane, SmallCall *const *calls, size_t nc) {
+    const bool g2 = kind == CALL_G2_MUL;
+    const size_t tab_bytes = sizeof(int32_t) * (g2 ? (size_t)glv_table_dwords<F2>() : (size_t)glv_table_dwords<Fe>());
+    return small_rows_run(lane, calls, nc, [&](const uint8_t *const *in, const uint8_t *const *, uint8_t *const *out, size_t N) {
+        TRY(lane.reserve(0, N * tab_bytes));
+        if (g2) return GPBC_LAUNCH(k_g2_scalar_mul_oct, grid_for(8 * N), BLOCK, lane.stream, in[0], 0, in[1], out[0], N, (int32_t *)lane.dev);   // N <= 2 048 = SMUL_OCT_MAX
+        return GPBC_LAUNCH(k_g1_scalar_mul_quad, grid_for(4 * N), BLOCK, lane.stream, in[0], 0, in[1], out[0], N, (int32_t *)lane.dev);
+    });
 }
-static int small_g1_mul_run(CallLane &l, SmallCall *const *c, size_t n) { return small_mul_run(false, l, c, n); }
-static int small_g2_mul_run(CallLane &l, SmallCall *const *c, size_t n) { return small_mul_run(true, l, c, n); }
-static int scalar_mul_one(bool g2, const void *bases, size_t nbase, const void *scalars, size_t n, void *out) {
-    TRY(bind_device());
-    size_t pt = g2 ? GPBC_G2_BYTES : GPBC_G1_BYTES;
-    if (n <= SMALL_CALL_MAX_UNITS) {
-        SmallCall c;
-        c.in[0] = bases; c.in_one[0] = nbase == 1 && n != 1; c.in[1] = scalars; c.out[0] = out; c.units = n;
-        return g2 ? small_call(CALL_G2_MUL, c, small_g2_mul_run) : small_call(CALL_G1_MUL, c, small_g1_mul_run);
-    }
-    if (nbase == n && n >= 2 * SMUL_PIPE_CHUNK) {
-        // one base per scalar, large batch: transfers of neighbouring chunks overlap the kernels (pipelined_chunks)
-        DevBuf dB, dS, dO;
-        TRY(dB.alloc(n * pt)); TRY(dS.alloc(n * GPBC_SCALAR_BYTES)); TRY(dO.alloc(n * pt));
-        int rc = pipelined_chunks(n, SMUL_PIPE_CHUNK,
-            [&](size_t off, size_t m, hipStream_t st) {
-                HIP_TRY(hipMemcpyAsync(dB.u8() + off * pt, (const uint8_t *)bases + off * pt, m * pt, hipMemcpyHostToDevice, st));
-                HIP_TRY(hipMemcpyAsync(dS.u8() + off * GPBC_SCALAR_BYTES, (const uint8_t *)scalars + off * GPBC_SCALAR_BYTES, m * GPBC_SCALAR_BYTES, hipMemcpyHostToDevice, st));
-                return (int)GPBC_OK;
-            },
-            [&](size_t off, size_t m, hipStream_t st) { return scalar_mul_dev(g2, dB.u8() + off * pt, m, dS.u8() + off * GPBC_SCALAR_BYTES, m, dO.u8() + off * pt, st); },
-            [&](size_t off, size_t m, hipStream_t st) {
-                HIP_TRY(hipMemcpyAsync((uint8_t *)out + off * pt, dO.u8() + off * pt, m * pt, hipMemcpyDeviceToHost, st));
-                return (int)GPBC_OK;
-            });
-        if (rc != GPBC_OK) { (void)hipDeviceSynchronize(); return rc; }
-        return GPBC_OK;
-    }
-    DevBuf dB, dS, dO;
-    TRY(dB.upload(bases, nbase * pt)); TRY(dS.upload(scalars, n * GPBC_SCALAR_BYTES)); TRY(dO.alloc(n * pt));
-    TRY(scalar_mul_dev(g2, dB.p, nbase, dS.p, n, dO.p, nullptr));
-    TRY(sync_default());
-    return dO.download(out, n * pt);
-}
-// host-pointer entries shard [0, n) over the bound devices (run_sharded, gpbc_core.hip)
+// host-pointer entries shard [0, n) over the bound devices (run_sharded, gpbc_core.hip); one base per scalar and a large batch:
+// transfers of neighbouring chunks overlap the kernels (pipelined_chunks)
 constexpr size_t SMUL_SHARD_MIN = 4096;
 static int scalar_mul_host(bool g2, const void *bases, size_t nbase, const void *scalars, size_t n, void *out) {
     if (!n) return GPBC_OK;
     if (!bases || !scalars || !out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
     if (nbase != 1 && nbase != n) return fail(GPBC_ERR_INVALID_ARG, "nbase must be 1 or n");
     const size_t pt = g2 ? GPBC_G2_BYTES : GPBC_G1_BYTES;
-    return run_sharded(n, SMUL_SHARD_MIN, [=](size_t lo, size_t hi) {
-        const bool shared = nbase == 1 && n != 1;
-        return scalar_mul_one(g2, (const uint8_t *)bases + (shared ? 0 : lo * pt), shared ? 1 : hi - lo, (const uint8_t *)scalars + lo * GPBC_SCALAR_BYTES,
-                              hi - lo, (uint8_t *)out + lo * pt);
-    });
+    const bool shared = nbase == 1 && n != 1;
+    return host_call_sharded(n, SMUL_SHARD_MIN, HostCall().input(bases, pt, shared).input(scalars, GPBC_SCALAR_BYTES).output(out, pt),
+                             HostRoute{g2 ? CALL_G2_MUL : CALL_G1_MUL, small_mul_run, SMALL_CALL_MAX_UNITS, 0, shared ? 0 : SMUL_PIPE_CHUNK},
+                             [=](const DevCols &d, size_t m, hipStream_t st) { return scalar_mul_dev(g2, d.in[0], shared ? 1 : m, d.in[1], m, d.out[0], st); });
 }
 int gpbc_g1_scalar_mul_batch(const void *b, size_t nb, const void *s, size_t n, void *o) { return scalar_mul_host(false, b, nb, s, n, o); }
 int gpbc_g2_scalar_mul_batch(const void *b, size_t nb, const void *s, size_t n, void *o) { return scalar_mul_host(true, b, nb, s, n, o); }
 
-static int sum_one(bool g2, const void *pts, size_t n, void *out) {
-    TRY(bind_device());
-    size_t pt = g2 ? GPBC_G2_BYTES : GPBC_G1_BYTES;
-    DevBuf dP, dO, dW;
-    TRY(dP.upload(pts, n * pt)); TRY(dO.alloc(pt));
-    size_t wsb = gpbc_sum_workspace_bytes(n, g2);
-    TRY(dW.alloc(wsb));
-    TRY(sum_dev(g2, dP.p, n, dO.p, dW.p, wsb, nullptr));
-    TRY(sync_default());
-    return dO.download(out, pt);
-}
+static int sum_host(bool g2, const void *pts, size_t n, void *out);
 // Partial sums of the shards of a host-pointer call: every shard leaves one point in the host array `parts` and the calling
 // thread's device adds them up.  No collective here — the data of a host-pointer call is on the host anyway; RCCL carries the
 // partial sums only where they are device-resident per rank (gpbc_g1/g2_scalar_mul_sum_dev).
@@ -417,12 +340,17 @@ static int sharded_point_sum(bool g2, size_t n, size_t min_units, const std::fun
         return dp.download(parts.data() + (size_t)idx * pt, pt);
     }));
     if (used.load() == 1) { memcpy(out, parts.data() + (size_t)(before > 0 && before < nd ? before : 0) * pt, pt); return GPBC_OK; }
-    return sum_one(g2, parts.data(), (size_t)nd, out);
+    return sum_host(g2, parts.data(), (size_t)nd, out);
 }
 static int sum_host(bool g2, const void *pts, size_t n, void *out) {
     if (!out || (n && !pts)) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
     const size_t pt = g2 ? GPBC_G2_BYTES : GPBC_G1_BYTES;
-    if (device_count_initialised() <= 1 || n < 2 * 65536) return sum_one(g2, pts, n, out);
+    if (device_count_initialised() <= 1 || n < 2 * 65536) {
+        // one call of ONE unit: the points are a whole column, the sum its one output
+        const size_t wsb = gpbc_sum_workspace_bytes(n, g2);
+        return host_call(1, HostCall().input(pts, n * pt, true).output(out, pt), HostRoute{CALL_KINDS, nullptr, 0, 0, 0, wsb},
+                         [=](const DevCols &d, size_t, hipStream_t st) { return sum_dev(g2, d.in[0], n, d.out[0], d.tmp, wsb, st); });
+    }
     return sharded_point_sum(g2, n, 65536, [=](size_t lo, size_t hi, uint8_t *d_out) {
         DevBuf dP, dW;
         TRY(dP.upload((const uint8_t *)pts + lo * pt, (hi - lo) * pt));
@@ -525,10 +453,8 @@ int gpbc_fixed_base_create_dev(int is_g2, const void *d_bases, size_t nbase, voi
         rc = stream_workspace(st, chunk * tab_bytes, &tabws);
         for (size_t off = 0; rc == GPBC_OK && off < total; off += chunk) {
             const size_t m = total - off < chunk ? total - off : chunk;
-            if (is_g2) k_g2_fb_build<<<grid_for(m), BLOCK, 0, st>>>((const uint8_t *)d_bases, nbase, h->table, h->base_inf, tabws, off, m);
-            else k_g1_fb_build<<<grid_for(m), BLOCK, 0, st>>>((const uint8_t *)d_bases, nbase, h->table, h->base_inf, tabws, off, m);
-            rc = check_launch("k_fb_build");
-            profile_mark(is_g2 ? "k_g2_fb_build" : "k_g1_fb_build", st);
+            if (is_g2) rc = GPBC_LAUNCH(k_g2_fb_build, grid_for(m), BLOCK, st, (const uint8_t *)d_bases, nbase, h->table, h->base_inf, tabws, off, m);
+            else rc = GPBC_LAUNCH(k_g1_fb_build, grid_for(m), BLOCK, st, (const uint8_t *)d_bases, nbase, h->table, h->base_inf, tabws, off, m);
         }
     }
     if (rc != GPBC_OK) { (void)hipFree(h->table); (void)hipFree(h->base_inf); delete h; return rc; }
@@ -586,13 +512,11 @@ int gpbc_fixed_base_msm_dev(const gpbc_fixed_base *h, const void *d_scalars, siz
     const size_t pt = h->is_g2 ? GPBC_G2_BYTES : GPBC_G1_BYTES;
     uint8_t *partial = n_chunks > 1 ? (uint8_t *)d_workspace : (uint8_t *)d_out;
     const size_t lanes = n_msm * n_chunks;
-    if (lanes <= FB_QUAD_MAX) {
-        if (h->is_g2) k_g2_fb_msm_quad<<<grid_for(4 * lanes), BLOCK, 0, st>>>(h->table, h->base_inf, h->nbase, (const uint8_t *)d_scalars, n_msm, C, n_chunks, partial);
-        else k_g1_fb_msm_quad<<<grid_for(4 * lanes), BLOCK, 0, st>>>(h->table, h->base_inf, h->nbase, (const uint8_t *)d_scalars, n_msm, C, n_chunks, partial);
-    } else if (h->is_g2) k_g2_fb_msm<<<grid_for(lanes), BLOCK, 0, st>>>(h->table, h->base_inf, h->nbase, (const uint8_t *)d_scalars, n_msm, C, n_chunks, partial);
-    else k_g1_fb_msm<<<grid_for(lanes), BLOCK, 0, st>>>(h->table, h->base_inf, h->nbase, (const uint8_t *)d_scalars, n_msm, C, n_chunks, partial);
-    TRY(check_launch("k_fb_msm"));
-    profile_mark(h->is_g2 ? "k_g2_fb_msm" : "k_g1_fb_msm", st);
+    const uint8_t *sc = (const uint8_t *)d_scalars;
+    if (lanes <= FB_QUAD_MAX && h->is_g2) TRY(GPBC_LAUNCH(k_g2_fb_msm_quad, grid_for(4 * lanes), BLOCK, st, h->table, h->base_inf, h->nbase, sc, n_msm, C, n_chunks, partial));
+    else if (lanes <= FB_QUAD_MAX) TRY(GPBC_LAUNCH(k_g1_fb_msm_quad, grid_for(4 * lanes), BLOCK, st, h->table, h->base_inf, h->nbase, sc, n_msm, C, n_chunks, partial));
+    else if (h->is_g2) TRY(GPBC_LAUNCH(k_g2_fb_msm, grid_for(lanes), BLOCK, st, h->table, h->base_inf, h->nbase, sc, n_msm, C, n_chunks, partial));
+    else TRY(GPBC_LAUNCH(k_g1_fb_msm, grid_for(lanes), BLOCK, st, h->table, h->base_inf, h->nbase, sc, n_msm, C, n_chunks, partial));
     // partials are chunk-major (partial[c * n_msm + m]); the strided sum kernel with n_out = c' * n_msm adds, for every m,
     // the chunks c' + i * c'' — so each launch divides the number of chunks by 16 until one row per sum is left
     const uint8_t *in = partial;
@@ -600,10 +524,8 @@ int gpbc_fixed_base_msm_dev(const gpbc_fixed_base *h, const void *d_scalars, siz
     for (size_t c = n_chunks; c > 1;) {
         const size_t c2 = (c + 15) / 16;
         uint8_t *out = c2 == 1 ? (uint8_t *)d_out : ws;
-        if (h->is_g2) k_g2_sum_level<<<grid_for(c2 * n_msm), BLOCK, 0, st>>>(in, c * n_msm, out, c2 * n_msm);
-        else k_g1_sum_level<<<grid_for(c2 * n_msm), BLOCK, 0, st>>>(in, c * n_msm, out, c2 * n_msm);
-        TRY(check_launch("k_sum_level"));
-        profile_mark(h->is_g2 ? "k_g2_sum_level" : "k_g1_sum_level", st);
+        if (h->is_g2) TRY(GPBC_LAUNCH(k_g2_sum_level, grid_for(c2 * n_msm), BLOCK, st, in, c * n_msm, out, c2 * n_msm));
+        else TRY(GPBC_LAUNCH(k_g1_sum_level, grid_for(c2 * n_msm), BLOCK, st, in, c * n_msm, out, c2 * n_msm));
         in = out; ws += c2 * n_msm * pt; c = c2;
     }
     return GPBC_OK;
@@ -611,49 +533,24 @@ int gpbc_fixed_base_msm_dev(const gpbc_fixed_base *h, const void *d_scalars, siz
 // Small fixed-base sums (ScalarMultiplicationBase as the reference calls it: one scalar against the generator table,
 // cpabe/bsw07/bsw07_cpabe.go:69, signature/bls01_signature/bls_signature.go:45) COMBINED per table: key = the handle, in[0] = the
 // call's scalars (segs rows of nbase each), in[1] = the handle, units = scalars (the batch cap counts terms).
-static int small_fixed_base_run(CallLane &lane, SmallCall *const *calls, size_t nc) {
-    const gpbc_fixed_base *h = (const gpbc_fixed_base *)calls[0]->in[1];
-    const size_t pt = h->is_g2 ? GPBC_G2_BYTES : GPBC_G1_BYTES, row = h->nbase * GPBC_SCALAR_BYTES;
-    size_t M = 0;
-    for (size_t c = 0; c < nc; c++) M += calls[c]->segs;
-    const size_t o_out = Scratch::padded(M * row), wsb = gpbc_fixed_base_msm_workspace_bytes(h, M);
-    TRY(lane.reserve(o_out + Scratch::padded(M * pt), wsb));
-    size_t m0 = 0;
-    for (size_t c = 0; c < nc; c++) { memcpy(lane.pin + m0 * row, calls[c]->in[0], calls[c]->segs * row); m0 += calls[c]->segs; }
-    TRY(gpbc_fixed_base_msm_dev(h, lane.d_pin, M, lane.d_pin + o_out, lane.dev, wsb, lane.stream));
-    HIP_TRY(hipStreamSynchronize(lane.stream));
-    m0 = 0;
-    for (size_t c = 0; c < nc; c++) { memcpy(calls[c]->out[0], lane.pin + o_out + m0 * pt, calls[c]->segs * pt); m0 += calls[c]->segs; }
-    return GPBC_OK;
+static int small_fixed_base_run(SmallKind, CallLane &lane, SmallCall *const *calls, size_t nc) {
+    const gpbc_fixed_base *h = *(const gpbc_fixed_base *const *)calls[0]->key;
+    return small_rows_run(lane, calls, nc, [&](const uint8_t *const *in, const uint8_t *const *, uint8_t *const *out, size_t M) {
+        const size_t wsb = gpbc_fixed_base_msm_workspace_bytes(h, M);
+        TRY(lane.reserve(0, wsb));
+        return gpbc_fixed_base_msm_dev(h, in[0], M, out[0], lane.dev, wsb, lane.stream);
+    });
 }
 int gpbc_fixed_base_msm(const gpbc_fixed_base *h, const void *scalars, size_t n_msm, void *out) {
     if (!h) return fail(GPBC_ERR_INVALID_ARG, "null table handle");
     if (!n_msm) return GPBC_OK;
     if (!scalars || !out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    TRY(bind_device());
-    const size_t pt = h->is_g2 ? GPBC_G2_BYTES : GPBC_G1_BYTES;
-    if (n_msm * h->nbase <= SMALL_CALL_MAX_UNITS) {
-        SmallCall c;
-        c.in[0] = scalars; c.in[1] = h; c.out[0] = out; c.units = n_msm * h->nbase; c.segs = n_msm; c.key = &h; c.key_len = sizeof h;
-        return small_call(CALL_FIXED_BASE, c, small_fixed_base_run);
-    }
-    if (n_msm * h->nbase <= LANE_CALL_MAX_UNITS)      // larger, still small: one launch on a call lane of its own, gpbc_common.hpp
-        return with_call_lane([&](CallLane &l) {
-            const size_t sb = n_msm * h->nbase * GPBC_SCALAR_BYTES, o_out = Scratch::padded(sb), wsb = gpbc_fixed_base_msm_workspace_bytes(h, n_msm);
-            TRY(l.reserve(o_out + Scratch::padded(n_msm * pt), wsb));
-            memcpy(l.pin, scalars, sb);
-            TRY(gpbc_fixed_base_msm_dev(h, l.d_pin, n_msm, l.d_pin + o_out, l.dev, wsb, l.stream));
-            HIP_TRY(hipStreamSynchronize(l.stream));
-            memcpy(out, l.pin + o_out, n_msm * pt);
-            return (int)GPBC_OK;
-        });
-    DevBuf dS, dO, dW;
-    TRY(dS.upload(scalars, n_msm * h->nbase * GPBC_SCALAR_BYTES)); TRY(dO.alloc(n_msm * pt));
+    // rows of nbase scalars; the combiner and the lane (larger, still small: one launch on a call lane of its own) count terms
+    HostCall c = HostCall().input(scalars, h->nbase * GPBC_SCALAR_BYTES).output(out, h->is_g2 ? GPBC_G2_BYTES : GPBC_G1_BYTES);
+    c.units = n_msm * h->nbase; c.key = &h; c.key_len = sizeof h;
     const size_t wsb = gpbc_fixed_base_msm_workspace_bytes(h, n_msm);
-    TRY(dW.alloc(wsb));
-    TRY(gpbc_fixed_base_msm_dev(h, dS.p, n_msm, dO.p, dW.p, wsb, nullptr));
-    TRY(sync_default());
-    return dO.download(out, n_msm * pt);
+    return host_call(n_msm, c, HostRoute{CALL_FIXED_BASE, small_fixed_base_run, SMALL_CALL_MAX_UNITS, LANE_CALL_MAX_UNITS, 0, wsb},
+                     [=](const DevCols &d, size_t m, hipStream_t st) { return gpbc_fixed_base_msm_dev(h, d.in[0], m, d.out[0], d.tmp, wsb, st); });
 }
 
 }  // extern "C"

@@ -267,9 +267,9 @@ template <class F> static int msm_run(const uint8_t *d_bases, const uint8_t *d_s
     const size_t n_tiles = (p.M + SCAN_TILE - 1) / SCAN_TILE;
     const size_t gpw = ((size_t)1 << p.c) / MSM_GROUP;
     int rc = GPBC_OK;
-    auto step = [&](const char *name) { if (rc == GPBC_OK) { rc = check_launch(name); profile_mark(name, st); } };
+#define MSM_NAME(k) (G2 ? #k "<F2>" : #k "<Fe>")                       // (the profile keeps G1 and G2 apart)
     if (hipMemsetAsync(counts, 0, p.M * 4, st) != hipSuccess) rc = fail(GPBC_ERR_HIP, "hipMemsetAsync failed");
-    if (rc == GPBC_OK) { k_msm_keys<F, false><<<grid_for(n), BLOCK, 0, st>>>(d_bases, d_scalars, n, p.c, p.W, counts, nullptr, nullptr); step(G2 ? "k_msm_count_g2" : "k_msm_count_g1"); }
+    if (rc == GPBC_OK) rc = GPBC_LAUNCH_AS(G2 ? "k_msm_keys<F2, false>" : "k_msm_keys<Fe, false>", (k_msm_keys<F, false>), grid_for(n), BLOCK, st, d_bases, d_scalars, n, p.c, p.W, counts, nullptr, nullptr);
     // Skewed scalars (all rho equal, small integers, one repeated value): a window's terms land in ONE bucket, and the lane that owns
     // it would run n dependent additions — seconds.  The histogram says so before any point is touched: when the longest bucket is far
     // above the mean the caller takes the per-term path (n independent scalar multiplications + the sum tree: milliseconds).  Costs
@@ -281,7 +281,7 @@ template <class F> static int msm_run(const uint8_t *d_bases, const uint8_t *d_s
         // partial top window is spread over its sub-buckets (k_msm_keys), so the same bound holds for it
         static_assert(sizeof(uint32_t) * 32 <= 256, "per-window maxima live in the `total` slot");
         if (rc == GPBC_OK && hipMemsetAsync(total, 0, 4 * (size_t)p.W, st) != hipSuccess) rc = fail(GPBC_ERR_HIP, "hipMemsetAsync failed");
-        if (rc == GPBC_OK) { k_msm_max_count<<<(unsigned)((p.M + SCAN_BLOCK - 1) / SCAN_BLOCK), SCAN_BLOCK, 0, st>>>(counts, p.M, p.c, total); step("k_msm_max_count"); }
+        if (rc == GPBC_OK) rc = GPBC_LAUNCH(k_msm_max_count, (unsigned)((p.M + SCAN_BLOCK - 1) / SCAN_BLOCK), SCAN_BLOCK, st, counts, p.M, p.c, total);
         if (rc == GPBC_OK && (hipMemcpyAsync(pin, total, 4 * (size_t)p.W, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) rc = fail(GPBC_ERR_HIP, "read-back of the longest buckets failed");
         if (rc == GPBC_OK) {
             uint32_t longest = 0;
@@ -290,31 +290,31 @@ template <class F> static int msm_run(const uint8_t *d_bases, const uint8_t *d_s
             g_msm_bucket_runs.fetch_add(1);
         }
     }
-    if (rc == GPBC_OK) { k_scan_tiles<<<(unsigned)n_tiles, SCAN_BLOCK, 0, st>>>(counts, offsets, tiles, p.M); step("k_scan_tiles"); }
-    if (rc == GPBC_OK) { k_scan_tops<<<1, SCAN_BLOCK, 0, st>>>(tiles, n_tiles, total); step("k_scan_tops"); }
-    if (rc == GPBC_OK) { k_scan_add<<<(unsigned)n_tiles, SCAN_BLOCK, 0, st>>>(offsets, tiles, p.M, total); step("k_scan_add"); }
+    if (rc == GPBC_OK) rc = GPBC_LAUNCH(k_scan_tiles, (unsigned)n_tiles, SCAN_BLOCK, st, counts, offsets, tiles, p.M);
+    if (rc == GPBC_OK) rc = GPBC_LAUNCH(k_scan_tops, 1, SCAN_BLOCK, st, tiles, n_tiles, total);
+    if (rc == GPBC_OK) rc = GPBC_LAUNCH(k_scan_add, (unsigned)n_tiles, SCAN_BLOCK, st, offsets, tiles, p.M, total);
     if (rc == GPBC_OK && hipMemsetAsync(counts, 0, p.M * 4, st) != hipSuccess) rc = fail(GPBC_ERR_HIP, "hipMemsetAsync failed");
-    if (rc == GPBC_OK) { k_msm_keys<F, true><<<grid_for(n), BLOCK, 0, st>>>(d_bases, d_scalars, n, p.c, p.W, counts, offsets, idx); step(G2 ? "k_msm_scatter_g2" : "k_msm_scatter_g1"); }
-    if (rc == GPBC_OK) { k_msm_bases<F><<<grid_for(n), BLOCK, 0, st>>>(d_bases, n, base_rows); step(G2 ? "k_msm_bases_g2" : "k_msm_bases_g1"); }
+    if (rc == GPBC_OK) rc = GPBC_LAUNCH_AS(G2 ? "k_msm_keys<F2, true>" : "k_msm_keys<Fe, true>", (k_msm_keys<F, true>), grid_for(n), BLOCK, st, d_bases, d_scalars, n, p.c, p.W, counts, offsets, idx);
+    if (rc == GPBC_OK) rc = GPBC_LAUNCH_AS(MSM_NAME(k_msm_bases), k_msm_bases<F>, grid_for(n), BLOCK, st, d_bases, n, base_rows);
     // buckets by size (the tile-sum scratch of the first scan is free again: hist_tiles <= n_tiles of the key scan for c = 16; a
     // separate region keeps it simple)
-    if (rc == GPBC_OK) { k_size_hist<<<(unsigned)p.n_size_blocks, SCAN_BLOCK, 0, st>>>(offsets, p.M, p.c, hist, p.n_size_blocks); step("k_size_hist"); }
-    if (rc == GPBC_OK) { k_scan_tiles<<<(unsigned)hist_tiles, SCAN_BLOCK, 0, st>>>(hist, hist_scanned, tiles, hist_len); step("k_scan_tiles"); }
-    if (rc == GPBC_OK) { k_scan_tops<<<1, SCAN_BLOCK, 0, st>>>(tiles, hist_tiles, total); step("k_scan_tops"); }
-    if (rc == GPBC_OK) { k_scan_add<<<(unsigned)hist_tiles, SCAN_BLOCK, 0, st>>>(hist_scanned, tiles, hist_len, total); step("k_scan_add"); }
-    if (rc == GPBC_OK) { k_size_scatter<<<(unsigned)p.n_size_blocks, SCAN_BLOCK, 0, st>>>(offsets, p.M, p.c, hist_scanned, p.n_size_blocks, perm); step("k_size_scatter"); }
-    if (rc == GPBC_OK) { k_msm_buckets<F><<<grid_for(p.M), BLOCK, 0, st>>>(base_rows, offsets, idx, perm, p.c, p.M, buckets); step(G2 ? "k_msm_buckets_g2" : "k_msm_buckets_g1"); }
-    if (rc == GPBC_OK) { k_msm_groups<F><<<grid_for(p.n_groups), BLOCK, 0, st>>>(buckets, p.c, p.W, p.n_groups, groups); step(G2 ? "k_msm_groups_g2" : "k_msm_groups_g1"); }
+    if (rc == GPBC_OK) rc = GPBC_LAUNCH(k_size_hist, (unsigned)p.n_size_blocks, SCAN_BLOCK, st, offsets, p.M, p.c, hist, p.n_size_blocks);
+    if (rc == GPBC_OK) rc = GPBC_LAUNCH(k_scan_tiles, (unsigned)hist_tiles, SCAN_BLOCK, st, hist, hist_scanned, tiles, hist_len);
+    if (rc == GPBC_OK) rc = GPBC_LAUNCH(k_scan_tops, 1, SCAN_BLOCK, st, tiles, hist_tiles, total);
+    if (rc == GPBC_OK) rc = GPBC_LAUNCH(k_scan_add, (unsigned)hist_tiles, SCAN_BLOCK, st, hist_scanned, tiles, hist_len, total);
+    if (rc == GPBC_OK) rc = GPBC_LAUNCH(k_size_scatter, (unsigned)p.n_size_blocks, SCAN_BLOCK, st, offsets, p.M, p.c, hist_scanned, p.n_size_blocks, perm);
+    if (rc == GPBC_OK) rc = GPBC_LAUNCH_AS(MSM_NAME(k_msm_buckets), k_msm_buckets<F>, grid_for(p.M), BLOCK, st, base_rows, offsets, idx, perm, p.c, p.M, buckets);
+    if (rc == GPBC_OK) rc = GPBC_LAUNCH_AS(MSM_NAME(k_msm_groups), k_msm_groups<F>, grid_for(p.n_groups), BLOCK, st, buckets, p.c, p.W, p.n_groups, groups);
     // tree over the groups of every window: rows are window-major, so segments of `fan` consecutive rows never cross a window
     int32_t *src = groups, *dst = tmp;
     for (size_t per_window = gpw; rc == GPBC_OK && per_window > 1;) {
         const size_t fan = per_window >= MSM_FAN ? MSM_FAN : per_window, next = per_window / fan;
-        k_msm_rows_sum<F><<<grid_for((size_t)p.W * next), BLOCK, 0, st>>>(src, (size_t)p.W * next, fan, dst);
-        step(G2 ? "k_msm_rows_sum_g2" : "k_msm_rows_sum_g1");
+        rc = GPBC_LAUNCH_AS(MSM_NAME(k_msm_rows_sum), k_msm_rows_sum<F>, grid_for((size_t)p.W * next), BLOCK, st, src, (size_t)p.W * next, fan, dst);
         int32_t *t = src; src = dst; dst = t;
         per_window = next;
     }
-    if (rc == GPBC_OK) { k_msm_finish<F><<<1, BLOCK, 0, st>>>(src, p.c, p.W, d_out); step(G2 ? "k_msm_finish_g2" : "k_msm_finish_g1"); }
+    if (rc == GPBC_OK) rc = GPBC_LAUNCH_AS(MSM_NAME(k_msm_finish), k_msm_finish<F>, 1, BLOCK, st, src, p.c, p.W, d_out);
+#undef MSM_NAME
     return rc;
 }
 

@@ -670,10 +670,7 @@ int gpbc_miller_loop_dev(const void *dP, const void *dQ, size_t n, void *d_f_out
     hipStream_t st = (hipStream_t)stream;
     size_t chunk = n < MILLER_CHUNK ? n : MILLER_CHUNK;
     if (n <= g_wide_max.load()) {
-        k_miller_wide<<<(unsigned)n, WIDE_MILLER_THREADS, 0, st>>>((const uint8_t *)dP, (const uint8_t *)dQ, (uint8_t *)d_f_out, n, 0);
-        TRY(check_launch("k_miller_wide"));
-        profile_mark("k_miller_wide", st);
-        return GPBC_OK;
+        return GPBC_LAUNCH(k_miller_wide, (unsigned)n, WIDE_MILLER_THREADS, st, (const uint8_t *)dP, (const uint8_t *)dQ, (uint8_t *)d_f_out, n, 0);
     }
     if (n <= PIPELINED_MAX_PAIRS && g_pipelined.load()) {
         Scratch flags;                                            // level 2: callers may hold levels 0 and 1 on this stream
@@ -684,11 +681,8 @@ int gpbc_miller_loop_dev(const void *dP, const void *dQ, size_t n, void *d_f_out
         TRY(lines_workspace(st, n, &lines));
         HIP_TRY(hipMemsetAsync(progress, 0, n * sizeof(uint32_t), st));
         const unsigned n_line_blocks = grid_for(n);
-        k_miller_pipelined<<<n_line_blocks + grid_for(2 * n), BLOCK, 0, st>>>((const uint8_t *)dP, (const uint8_t *)dQ, lines, progress, (uint8_t *)d_f_out, n, n, n_line_blocks,
-                                                                                       g_pipelined.load() == 2 ? 0u : PIPELINED_SPIN_LIMIT);
-        TRY(check_launch("k_miller_pipelined"));
-        profile_mark("k_miller_pipelined", st);
-        return GPBC_OK;
+        return GPBC_LAUNCH(k_miller_pipelined, n_line_blocks + grid_for(2 * n), BLOCK, st, (const uint8_t *)dP, (const uint8_t *)dQ, lines, progress, (uint8_t *)d_f_out, n, n,
+                           n_line_blocks, g_pipelined.load() == 2 ? 0u : PIPELINED_SPIN_LIMIT);
     }
     std::lock_guard<std::mutex> seq(g_ws_seq_mu);
     int32_t *lines = nullptr;
@@ -696,12 +690,8 @@ int gpbc_miller_loop_dev(const void *dP, const void *dQ, size_t n, void *d_f_out
     for (size_t off = 0; off < n; off += chunk) {
         size_t m = n - off < chunk ? n - off : chunk;
         const uint8_t *p = (const uint8_t *)dP + off * GPBC_G1_BYTES, *q = (const uint8_t *)dQ + off * GPBC_G2_BYTES;
-        k_miller_lines<<<grid_for(m), BLOCK, 0, st>>>(p, q, lines, m, chunk);
-        TRY(check_launch("k_miller_lines"));
-        profile_mark("k_miller_lines", st);
-        k_miller_accumulate<<<grid_for(2 * m), BLOCK, 0, st>>>(p, q, lines, (uint8_t *)d_f_out + off * GPBC_GT_BYTES, m, chunk);
-        TRY(check_launch("k_miller_accumulate"));
-        profile_mark("k_miller_accumulate", st);
+        TRY(GPBC_LAUNCH(k_miller_lines, grid_for(m), BLOCK, st, p, q, lines, m, chunk));
+        TRY(GPBC_LAUNCH(k_miller_accumulate, grid_for(2 * m), BLOCK, st, p, q, lines, (uint8_t *)d_f_out + off * GPBC_GT_BYTES, m, chunk));
     }
     return GPBC_OK;
 }
@@ -711,14 +701,9 @@ int gpbc_final_exp_dev(const void *d_f, size_t n, void *d_gt_out, void *stream) 
     TRY(bind_device());
     // (two rounds of the chip still beat the lane-pair kernel's 2.6 ms floor: 3 072 / 4 096 values 1.38 / 1.75 ms; 6 144: 2.54 — even.
     // The Miller loop's switch-over stays at one round: its wavefront form holds 768 pairings at a time.)
-    if (n <= 2 * g_wide_max.load()) {
-        k_final_exp_wide<<<(unsigned)n, wide_threads(n), 0, (hipStream_t)stream>>>((const uint8_t *)d_f, (uint8_t *)d_gt_out, n);
-        profile_mark("k_final_exp_wide", (hipStream_t)stream);
-        return check_launch("k_final_exp_wide");
-    }
-    k_final_exp<<<grid_for(2 * n), BLOCK, 0, (hipStream_t)stream>>>((const uint8_t *)d_f, (uint8_t *)d_gt_out, n);
-    profile_mark("k_final_exp", (hipStream_t)stream);
-    return check_launch("k_final_exp");
+    if (n <= 2 * g_wide_max.load())
+        return GPBC_LAUNCH(k_final_exp_wide, (unsigned)n, wide_threads(n), (hipStream_t)stream, (const uint8_t *)d_f, (uint8_t *)d_gt_out, n);
+    return GPBC_LAUNCH(k_final_exp, grid_for(2 * n), BLOCK, (hipStream_t)stream, (const uint8_t *)d_f, (uint8_t *)d_gt_out, n);
 }
 int gpbc_pair_batch_dev(const void *dP, const void *dQ, size_t n, void *d_gt_out, void *stream) {
     if (!n) return fail(GPBC_ERR_INVALID_ARG, "invalid inputs sizes");
@@ -737,9 +722,7 @@ static int segment_fold_passes(uint8_t *vals, const uint64_t *d_seg_off, size_t 
     while (fold < 4096 && (size_t)fold * 8 < avg) fold *= 8;
     uint64_t limit = 0;
     for (;; fold /= 8) {
-        k_segment_fold<<<grid_for(2 * k * fold), BLOCK, 0, st>>>(vals, d_seg_off, uniform_len, k, n_vals, fold, limit);
-        TRY(check_launch("k_segment_fold"));
-        profile_mark("k_segment_fold", st);
+        TRY(GPBC_LAUNCH(k_segment_fold, grid_for(2 * k * fold), BLOCK, st, vals, d_seg_off, uniform_len, k, n_vals, fold, limit));
         limit = fold;
         if (fold == 8) break;
     }
@@ -749,15 +732,8 @@ static int segment_fold_passes(uint8_t *vals, const uint64_t *d_seg_off, size_t 
 // latency path, after the Miller loop: the values of each segment (table, or equal runs of `uniform_len`) multiplied and exponentiated
 static int segments_wide(uint8_t *vals, const uint64_t *d_seg_off, size_t uniform_len, size_t k, size_t n_vals, uint8_t *d_gt_out, uint64_t *d_echo, hipStream_t st, uint8_t *d_ok = nullptr) {
     const unsigned fold = n_vals >= 128 * k ? 16u : n_vals >= 32 * k ? 8u : 0u;
-    if (fold) {
-        k_segment_fold_wide<<<(unsigned)(k * fold), wide_threads(k * fold), 0, st>>>(vals, d_seg_off, uniform_len, k, n_vals, fold);
-        TRY(check_launch("k_segment_fold_wide"));
-        profile_mark("k_segment_fold_wide", st);
-    }
-    k_segment_final_exp_wide<<<(unsigned)k, wide_threads(k), 0, st>>>(vals, d_seg_off, uniform_len, d_gt_out, k, n_vals, d_echo, fold, d_ok);
-    TRY(check_launch("k_segment_final_exp_wide"));
-    profile_mark("k_segment_final_exp_wide", st);
-    return GPBC_OK;
+    if (fold) TRY(GPBC_LAUNCH(k_segment_fold_wide, (unsigned)(k * fold), wide_threads(k * fold), st, vals, d_seg_off, uniform_len, k, n_vals, fold));
+    return GPBC_LAUNCH(k_segment_final_exp_wide, (unsigned)k, wide_threads(k), st, vals, d_seg_off, uniform_len, d_gt_out, k, n_vals, d_echo, fold, d_ok);
 }
 static int multi_pair_dev_echo(const void *dP, const void *dQ, const uint64_t *d_seg_off, size_t n_pairs, size_t k,
                                void *d_gt_out, void *d_workspace, size_t workspace_bytes, uint64_t *d_echo, void *stream) {
@@ -772,9 +748,7 @@ static int multi_pair_dev_echo(const void *dP, const void *dQ, const uint64_t *d
     }
     uint64_t limit = 0;
     TRY(segment_fold_passes((uint8_t *)d_workspace, d_seg_off, 0, k, n_pairs, (hipStream_t)stream, &limit));
-    k_segment_product<<<grid_for(k), BLOCK, 0, (hipStream_t)stream>>>((const uint8_t *)d_workspace, d_seg_off, (uint8_t *)d_gt_out, k, n_pairs, nullptr, d_echo, limit);
-    TRY(check_launch("k_segment_product"));
-    profile_mark("k_segment_product", (hipStream_t)stream);
+    TRY(GPBC_LAUNCH(k_segment_product, grid_for(k), BLOCK, (hipStream_t)stream, (const uint8_t *)d_workspace, d_seg_off, (uint8_t *)d_gt_out, k, n_pairs, nullptr, d_echo, limit));
     return gpbc_final_exp_dev(d_gt_out, k, d_gt_out, stream);
 }
 int gpbc_multi_pair_dev(const void *dP, const void *dQ, const uint64_t *d_seg_off, size_t n_pairs, size_t k,
@@ -789,8 +763,7 @@ int gpbc_check_segments_dev(const uint64_t *d_seg_off, size_t n_pairs, size_t k,
     DevBuf dFlag;
     TRY(dFlag.alloc(sizeof(int)));
     HIP_TRY(hipMemsetAsync(dFlag.p, 0, sizeof(int), st));
-    k_check_segments<<<grid_for(k + 1), BLOCK, 0, st>>>(d_seg_off, k, n_pairs, (int *)dFlag.p);
-    TRY(check_launch("k_check_segments"));
+    TRY(GPBC_LAUNCH(k_check_segments, grid_for(k + 1), BLOCK, st, d_seg_off, k, n_pairs, (int *)dFlag.p));
     int flag = 0;
     HIP_TRY(hipMemcpyAsync(&flag, dFlag.p, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -806,12 +779,7 @@ int gpbc_gt_exp_batch_dev(const void *d_x, const void *d_k, size_t n, void *d_ou
     hipStream_t st = (hipStream_t)stream;
     // one round of the chip holds 2 048 wavefronts (1.1 ms per round when full), the lane-pair kernel needs 3.6 ms whatever the size
     // below 65 536: measured 2 048 / 4 096 / 8 192 elements 1.09 / 2.45 / 4.23 ms against 3.6 — two rounds is where the wavefront form stops winning
-    if (n <= 2 * g_wide_max.load()) {
-        k_gt_exp_wide<<<(unsigned)n, wide_threads(n), 0, st>>>((const uint8_t *)d_x, (const uint8_t *)d_k, (uint8_t *)d_out, n);
-        TRY(check_launch("k_gt_exp_wide"));
-        profile_mark("k_gt_exp_wide", st);
-        return GPBC_OK;
-    }
+    if (n <= 2 * g_wide_max.load()) return GPBC_LAUNCH(k_gt_exp_wide, (unsigned)n, wide_threads(n), st, (const uint8_t *)d_x, (const uint8_t *)d_k, (uint8_t *)d_out, n);
     constexpr size_t CHUNK = 131072;                       // elements per launch: 1 GB of window tables (4 KB per lane)
     const size_t chunk = n < CHUNK ? n : CHUNK;
     std::lock_guard<std::mutex> seq(g_ws_seq_mu);
@@ -819,10 +787,8 @@ int gpbc_gt_exp_batch_dev(const void *d_x, const void *d_k, size_t n, void *d_ou
     TRY(stream_workspace(st, 2 * chunk * GT_EXP_TAB_DWORDS * sizeof(int32_t), &tabws));
     for (size_t off = 0; off < n; off += chunk) {
         const size_t m = n - off < chunk ? n - off : chunk;
-        k_gt_exp<<<grid_for(2 * m), BLOCK, 0, st>>>((const uint8_t *)d_x + off * GPBC_GT_BYTES, (const uint8_t *)d_k + off * GPBC_SCALAR_BYTES,
-                                                    (uint8_t *)d_out + off * GPBC_GT_BYTES, m, tabws);
-        TRY(check_launch("k_gt_exp"));
-        profile_mark("k_gt_exp", st);
+        TRY(GPBC_LAUNCH(k_gt_exp, grid_for(2 * m), BLOCK, st, (const uint8_t *)d_x + off * GPBC_GT_BYTES, (const uint8_t *)d_k + off * GPBC_SCALAR_BYTES,
+                        (uint8_t *)d_out + off * GPBC_GT_BYTES, m, tabws));
     }
     return GPBC_OK;
 }
@@ -830,9 +796,7 @@ static int gt_binary_dev(int op, const void *a, const void *b, size_t n, void *o
     if (!n) return GPBC_OK;
     if (!a || (op != 2 && !b) || !out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
     TRY(bind_device());
-    k_gt_binary<<<grid_for(n), BLOCK, 0, (hipStream_t)stream>>>((const uint8_t *)a, (const uint8_t *)b, (uint8_t *)out, n, op);
-    profile_mark("k_gt_binary", (hipStream_t)stream);
-    return check_launch("k_gt_binary");
+    return GPBC_LAUNCH(k_gt_binary, grid_for(n), BLOCK, (hipStream_t)stream, (const uint8_t *)a, (const uint8_t *)b, (uint8_t *)out, n, op);
 }
 int gpbc_gt_mul_batch_dev(const void *a, const void *b, size_t n, void *o, void *s) { return gt_binary_dev(0, a, b, n, o, s); }
 int gpbc_gt_div_batch_dev(const void *a, const void *b, size_t n, void *o, void *s) { return gt_binary_dev(1, a, b, n, o, s); }
@@ -841,35 +805,19 @@ int gpbc_gt_inverse_batch_dev(const void *a, size_t n, void *o, void *s) { retur
 // Host-pointer entries: [0, n) is split over the bound devices (run_sharded, gpbc_core.hip); each shard uploads, computes and
 // downloads on its own device from its own host thread.
 constexpr size_t SHARD_MIN_UNITS = 4096;
-static int miller_loop_one(const void *P, const void *Q, size_t n, void *f_out) {
-    TRY(bind_device());
-    DevBuf dP, dQ, dF;
-    TRY(dP.upload(P, n * GPBC_G1_BYTES)); TRY(dQ.upload(Q, n * GPBC_G2_BYTES)); TRY(dF.alloc(n * GPBC_GT_BYTES));
-    TRY(gpbc_miller_loop_dev(dP.p, dQ.p, n, dF.p, nullptr));
-    TRY(sync_default());
-    return dF.download(f_out, n * GPBC_GT_BYTES);
-}
 int gpbc_miller_loop(const void *P, const void *Q, size_t n, void *f_out) {
     if (!n) return GPBC_OK;
     if (!P || !Q || !f_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    return run_sharded(n, SHARD_MIN_UNITS, [=](size_t lo, size_t hi) {
-        return miller_loop_one((const uint8_t *)P + lo * GPBC_G1_BYTES, (const uint8_t *)Q + lo * GPBC_G2_BYTES, hi - lo, (uint8_t *)f_out + lo * GPBC_GT_BYTES);
-    });
-}
-static int final_exp_one(const void *f, size_t n, void *gt_out) {
-    TRY(bind_device());
-    DevBuf dF;
-    TRY(dF.upload(f, n * GPBC_GT_BYTES));
-    TRY(gpbc_final_exp_dev(dF.p, n, dF.p, nullptr));
-    TRY(sync_default());
-    return dF.download(gt_out, n * GPBC_GT_BYTES);
+    return host_call_sharded(n, SHARD_MIN_UNITS, HostCall().input(P, GPBC_G1_BYTES).input(Q, GPBC_G2_BYTES).output(f_out, GPBC_GT_BYTES), HostRoute(),
+                             [](const DevCols &d, size_t m, hipStream_t st) { return gpbc_miller_loop_dev(d.in[0], d.in[1], m, d.out[0], st); });
 }
 int gpbc_final_exp(const void *f, size_t n, void *gt_out) {
     if (!n) return GPBC_OK;
     if (!f || !gt_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    return run_sharded(n, SHARD_MIN_UNITS, [=](size_t lo, size_t hi) {
-        return final_exp_one((const uint8_t *)f + lo * GPBC_GT_BYTES, hi - lo, (uint8_t *)gt_out + lo * GPBC_GT_BYTES);
-    });
+    HostCall c = HostCall().input(f, GPBC_GT_BYTES).output(gt_out, GPBC_GT_BYTES);
+    c.in_place = true;                                                     // each lane rewrites its own 384 B
+    return host_call_sharded(n, SHARD_MIN_UNITS, c, HostRoute(),
+                             [](const DevCols &d, size_t m, hipStream_t st) { return gpbc_final_exp_dev(d.in[0], m, d.out[0], st); });
 }
 // ---- small calls (gpbc_common.hpp "Small host-pointer calls"): every waiting Pair / PairingCheck / multi-pairing of the latency
 // path in ONE launch pair on a call lane.  The batch is a multi-pairing over the concatenated pairs with the concatenated segment
@@ -877,7 +825,7 @@ int gpbc_final_exp(const void *f, size_t n, void *gt_out) {
 // k_segment_final_exp_wide writes the GT values, the PairingCheck flags and the echo of the table straight into it.
 static std::atomic<int> g_fault_table{0};
 static int verify_echo(const uint64_t *echo, const uint64_t *seg_off, size_t k);
-static int small_pairs_run(CallLane &lane, SmallCall *const *calls, size_t nc) {
+static int small_pairs_run(SmallKind, CallLane &lane, SmallCall *const *calls, size_t nc) {
     size_t N = 0, K = 0;
     for (size_t c = 0; c < nc; c++) { N += calls[c]->units; K += calls[c]->segs; }
     const size_t oP = 0, oQ = oP + Scratch::padded(N * GPBC_G1_BYTES), oSeg = oQ + Scratch::padded(N * GPBC_G2_BYTES), oEcho = oSeg + Scratch::padded((K + 1) * sizeof(uint64_t)),
@@ -897,9 +845,7 @@ static int small_pairs_run(CallLane &lane, SmallCall *const *calls, size_t nc) {
     memcpy(pin_seg, table.data(), (K + 1) * sizeof(uint64_t));
     if (g_fault_table.exchange(0)) pin_seg[K] = pin_seg[K - 1];  // test knob: the device sees a last segment that is empty
     memset(h_echo, 0xff, 2 * K * sizeof(uint64_t));
-    k_miller_wide<<<(unsigned)N, WIDE_MILLER_THREADS, 0, lane.stream>>>(lane.d_pin + oP, lane.d_pin + oQ, lane.dev, N, 0);
-    TRY(check_launch("k_miller_wide"));
-    profile_mark("k_miller_wide", lane.stream);
+    TRY(GPBC_LAUNCH(k_miller_wide, (unsigned)N, WIDE_MILLER_THREADS, lane.stream, lane.d_pin + oP, lane.d_pin + oQ, lane.dev, N, 0));
     TRY(segments_wide(lane.dev, (const uint64_t *)(lane.d_pin + oSeg), 0, K, N, lane.d_pin + oGt, (uint64_t *)(lane.d_pin + oEcho), lane.stream, lane.d_pin + oOk));
     HIP_TRY(hipStreamSynchronize(lane.stream));
     k0 = 0;
@@ -920,84 +866,28 @@ static int small_pairs_run(CallLane &lane, SmallCall *const *calls, size_t nc) {
     return GPBC_OK;
 }
 // GT.Exp / Mul / Div / Inverse one call at a time (access/tree/access_tree_node.go:114,123,156-157): elementwise batches on a lane
-static int small_gt_run(int OP, CallLane &lane, SmallCall *const *calls, size_t nc) {     // OP 0 mul, 1 div, 2 inverse, 3 exp
-    size_t N = 0;
-    for (size_t c = 0; c < nc; c++) N += calls[c]->units;
-    const size_t b_unit = OP == 3 ? GPBC_SCALAR_BYTES : OP == 2 ? 0 : GPBC_GT_BYTES;
-    const size_t oA = 0, oB = Scratch::padded(N * GPBC_GT_BYTES), oO = oB + Scratch::padded(N * b_unit), total = oO + Scratch::padded(N * GPBC_GT_BYTES);
-    TRY(lane.reserve(total, OP == 3 ? 0 : 2 * N * GPBC_GT_BYTES));
-    size_t n0 = 0;
-    for (size_t c = 0; c < nc; c++) {
-        const SmallCall &r = *calls[c];
-        memcpy(lane.pin + oA + n0 * GPBC_GT_BYTES, r.in[0], r.units * GPBC_GT_BYTES);
-        if (b_unit) memcpy(lane.pin + oB + n0 * b_unit, r.in[1], r.units * b_unit);
-        n0 += r.units;
-    }
-    if (OP == 3) {
-        k_gt_exp_wide<<<(unsigned)N, wide_threads(N), 0, lane.stream>>>(lane.d_pin + oA, lane.d_pin + oB, lane.d_pin + oO, N);
-        TRY(check_launch("k_gt_exp_wide"));
-        profile_mark("k_gt_exp_wide", lane.stream);
-    } else {
+static int small_gt_run(SmallKind kind, CallLane &lane, SmallCall *const *calls, size_t nc) {
+    return small_rows_run(lane, calls, nc, [&](const uint8_t *const *in, const uint8_t *const *in_host, uint8_t *const *out, size_t N) {
+        if (kind == CALL_GT_EXP) return GPBC_LAUNCH(k_gt_exp_wide, (unsigned)N, wide_threads(N), lane.stream, in[0], in[1], out[0], N);
         // one lane per element walks its 384 + 384 bytes many times: operands into device memory first
-        HIP_TRY(hipMemcpyAsync(lane.dev, lane.pin + oA, N * GPBC_GT_BYTES, hipMemcpyHostToDevice, lane.stream));
-        if (b_unit) HIP_TRY(hipMemcpyAsync(lane.dev + N * GPBC_GT_BYTES, lane.pin + oB, N * GPBC_GT_BYTES, hipMemcpyHostToDevice, lane.stream));
-        k_gt_binary<<<grid_for(N), BLOCK, 0, lane.stream>>>(lane.dev, lane.dev + N * GPBC_GT_BYTES, lane.d_pin + oO, N, OP);
-        TRY(check_launch("k_gt_binary"));
-        profile_mark("k_gt_binary", lane.stream);
-    }
-    HIP_TRY(hipStreamSynchronize(lane.stream));
-    n0 = 0;
-    for (size_t c = 0; c < nc; c++) { memcpy(calls[c]->out[0], lane.pin + oO + n0 * GPBC_GT_BYTES, calls[c]->units * GPBC_GT_BYTES); n0 += calls[c]->units; }
-    return GPBC_OK;
+        TRY(lane.reserve(0, 2 * N * GPBC_GT_BYTES));
+        HIP_TRY(hipMemcpyAsync(lane.dev, in_host[0], N * GPBC_GT_BYTES, hipMemcpyHostToDevice, lane.stream));
+        if (kind != CALL_GT_INV) HIP_TRY(hipMemcpyAsync(lane.dev + N * GPBC_GT_BYTES, in_host[1], N * GPBC_GT_BYTES, hipMemcpyHostToDevice, lane.stream));
+        return GPBC_LAUNCH(k_gt_binary, grid_for(N), BLOCK, lane.stream, lane.dev, lane.dev + N * GPBC_GT_BYTES, out[0], N, (int)(kind - CALL_GT_MUL));
+    });
 }
-static int small_gt_mul_run(CallLane &l, SmallCall *const *c, size_t n) { return small_gt_run(0, l, c, n); }
-static int small_gt_div_run(CallLane &l, SmallCall *const *c, size_t n) { return small_gt_run(1, l, c, n); }
-static int small_gt_inv_run(CallLane &l, SmallCall *const *c, size_t n) { return small_gt_run(2, l, c, n); }
-static int small_gt_exp_run(CallLane &l, SmallCall *const *c, size_t n) { return small_gt_run(3, l, c, n); }
-static bool small_call_ok(size_t units) { const size_t lim = g_wide_max.load(); return units && units <= lim && units <= SMALL_CALL_MAX_UNITS; }
+// the largest call of the latency path that goes through the combiner (0 with the latency path switched off)
+static size_t small_limit() { const size_t lim = g_wide_max.load(); return lim < SMALL_CALL_MAX_UNITS ? lim : SMALL_CALL_MAX_UNITS; }
 
 constexpr size_t PIPE_CHUNK = 131072;          // pairs per pipelined chunk: 2.5 GB of lines per stream
-static int pair_batch_one(const void *P, const void *Q, size_t n, void *gt_out) {
-    TRY(bind_device());
-    if (n >= 2 * PIPE_CHUNK) {
-        // upload / kernels / download of neighbouring chunks overlap on the slot's two streams (pipelined_chunks)
-        DevBuf dP, dQ, dG;
-        TRY(dP.alloc(n * GPBC_G1_BYTES)); TRY(dQ.alloc(n * GPBC_G2_BYTES)); TRY(dG.alloc(n * GPBC_GT_BYTES));
-        int rc = pipelined_chunks(n, PIPE_CHUNK,
-            [&](size_t off, size_t m, hipStream_t st) {
-                HIP_TRY(hipMemcpyAsync(dP.u8() + off * GPBC_G1_BYTES, (const uint8_t *)P + off * GPBC_G1_BYTES, m * GPBC_G1_BYTES, hipMemcpyHostToDevice, st));
-                HIP_TRY(hipMemcpyAsync(dQ.u8() + off * GPBC_G2_BYTES, (const uint8_t *)Q + off * GPBC_G2_BYTES, m * GPBC_G2_BYTES, hipMemcpyHostToDevice, st));
-                return (int)GPBC_OK;
-            },
-            [&](size_t off, size_t m, hipStream_t st) {
-                return gpbc_pair_batch_dev(dP.u8() + off * GPBC_G1_BYTES, dQ.u8() + off * GPBC_G2_BYTES, m, dG.u8() + off * GPBC_GT_BYTES, st);
-            },
-            [&](size_t off, size_t m, hipStream_t st) {
-                HIP_TRY(hipMemcpyAsync((uint8_t *)gt_out + off * GPBC_GT_BYTES, dG.u8() + off * GPBC_GT_BYTES, m * GPBC_GT_BYTES, hipMemcpyDeviceToHost, st));
-                return (int)GPBC_OK;
-            });
-        if (rc != GPBC_OK) { (void)hipDeviceSynchronize(); return rc; }     // nothing may still use the buffers when they are freed
-        return GPBC_OK;
-    }
-    if (small_call_ok(n)) {
-        // a latency call (bn254.Pair as the reference makes it): through the device's call lanes, combined with whatever other
-        // threads are asking for at the same moment
-        SmallCall c;
-        c.in[0] = P; c.in[1] = Q; c.out[0] = gt_out; c.units = n; c.segs = n;
-        return small_call(CALL_PAIRS, c, small_pairs_run);
-    }
-    DevBuf dP, dQ, dG;
-    TRY(dP.upload(P, n * GPBC_G1_BYTES)); TRY(dQ.upload(Q, n * GPBC_G2_BYTES)); TRY(dG.alloc(n * GPBC_GT_BYTES));
-    TRY(gpbc_pair_batch_dev(dP.p, dQ.p, n, dG.p, nullptr));
-    TRY(sync_default());
-    return dG.download(gt_out, n * GPBC_GT_BYTES);
-}
 int gpbc_pair_batch(const void *P, const void *Q, size_t n, void *gt_out) {
     if (!n) return fail(GPBC_ERR_INVALID_ARG, "invalid inputs sizes");
     if (!P || !Q || !gt_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    return run_sharded(n, SHARD_MIN_UNITS, [=](size_t lo, size_t hi) {
-        return pair_batch_one((const uint8_t *)P + lo * GPBC_G1_BYTES, (const uint8_t *)Q + lo * GPBC_G2_BYTES, hi - lo, (uint8_t *)gt_out + lo * GPBC_GT_BYTES);
-    });
+    // a latency call (bn254.Pair as the reference makes it) goes through the device's call lanes, combined with whatever other threads
+    // are asking for at the same moment; a large one overlaps upload / kernels / download of neighbouring chunks
+    return host_call_sharded(n, SHARD_MIN_UNITS, HostCall().input(P, GPBC_G1_BYTES).input(Q, GPBC_G2_BYTES).output(gt_out, GPBC_GT_BYTES),
+                             HostRoute{CALL_PAIRS, small_pairs_run, small_limit(), 0, PIPE_CHUNK},
+                             [](const DevCols &d, size_t m, hipStream_t st) { return gpbc_pair_batch_dev(d.in[0], d.in[1], m, d.out[0], st); });
 }
 static int check_segments(const uint64_t *seg_off, size_t k, size_t *n_pairs) {
     if (!seg_off) return fail(GPBC_ERR_INVALID_ARG, "null segment table");
@@ -1113,25 +1003,15 @@ static int multi_pair_core(const uint8_t *dP, const uint8_t *dQ, const uint64_t 
             int32_t *lines = nullptr;
             TRY(lines_workspace(st, n_slots, &lines));
             const uint64_t *co = dChunkOff + cb;
-            k_miller_lines_chunks<<<grid_for(n_slots), BLOCK, 0, st>>>(dP, dQ, lines, co, g, n_slots, dSeenLines + 2 * cb);
-            TRY(check_launch("k_miller_lines_chunks"));
-            profile_mark("k_miller_lines_chunks", st);
-            k_miller_accumulate_chunks<<<grid_for(2 * g), BLOCK, 0, st>>>(dP, dQ, lines, co, dPart + cb * GPBC_GT_BYTES, g, n_slots, dSeenLines + 2 * cb, dSeen + 2 * cb);
-            TRY(check_launch("k_miller_accumulate_chunks"));
-            profile_mark("k_miller_accumulate_chunks", st);
+            TRY(GPBC_LAUNCH(k_miller_lines_chunks, grid_for(n_slots), BLOCK, st, dP, dQ, lines, co, g, n_slots, dSeenLines + 2 * cb));
+            TRY(GPBC_LAUNCH(k_miller_accumulate_chunks, grid_for(2 * g), BLOCK, st, dP, dQ, lines, co, dPart + cb * GPBC_GT_BYTES, g, n_slots, dSeenLines + 2 * cb, dSeen + 2 * cb));
         }
         uint64_t limit = 0;
         TRY(segment_fold_passes(dPart, dSegChunk, 0, k, n_chunks, st, &limit));
-        k_segment_product<<<grid_for(k), BLOCK, 0, st>>>(dPart, dSegChunk, dG, k, n_chunks, dSeen, dEcho, limit);
-        TRY(check_launch("k_segment_product (segments)"));
-        profile_mark("k_segment_product", st);
+        TRY(GPBC_LAUNCH(k_segment_product, grid_for(k), BLOCK, st, dPart, dSegChunk, dG, k, n_chunks, dSeen, dEcho, limit));
         TRY(gpbc_final_exp_dev(dG, k, dG, st));
     }
-    if (dOk) {
-        k_gt_is_one<<<grid_for(k), BLOCK, 0, st>>>(dG, dOk, k);
-        TRY(check_launch("k_gt_is_one"));
-        profile_mark("k_gt_is_one", st);
-    }
+    if (dOk) TRY(GPBC_LAUNCH(k_gt_is_one, grid_for(k), BLOCK, st, dG, dOk, k));
     HIP_TRY(hipMemcpyAsync(h_echo, dEcho, echo_bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     rc = verify_echo(h_echo, seg_off, k);
@@ -1154,9 +1034,7 @@ int gpbc_multi_pair_fixed_q_dev(const void *dP, const void *dQ, size_t m, size_t
         Scratch tmp;
         TRY(tmp.open(st, 0, Scratch::padded(m * k * GPBC_GT_BYTES)));
         uint8_t *vals = tmp.take(m * k * GPBC_GT_BYTES);
-        k_miller_wide<<<(unsigned)(m * k), WIDE_MILLER_THREADS, 0, st>>>((const uint8_t *)dP, (const uint8_t *)dQ, vals, m * k, m);
-        TRY(check_launch("k_miller_wide"));
-        profile_mark("k_miller_wide", st);
+        TRY(GPBC_LAUNCH(k_miller_wide, (unsigned)(m * k), WIDE_MILLER_THREADS, st, (const uint8_t *)dP, (const uint8_t *)dQ, vals, m * k, m));
         return segments_wide(vals, nullptr, m, k, m * k, (uint8_t *)d_gt_out, nullptr, st);
     }
     // Chunks of the Q list per lane pair: n_c equal chunks of L = ceil(m / n_c) <= FIXED_Q_CHUNK pairs.  One lane pair costs about
@@ -1184,42 +1062,24 @@ int gpbc_multi_pair_fixed_q_dev(const void *dP, const void *dQ, size_t m, size_t
         int32_t *dLines = tmp.take<int32_t>(m * LINE_BYTES_PER_PAIR), *dQ34 = tmp.take<int32_t>(q34_bytes), *dPint = tmp.take<int32_t>(pint_bytes);
         uint8_t *dPart = tmp.take(part_bytes);
         HIP_TRY(hipMemsetAsync(dLines, 0, m * LINE_BYTES_PER_PAIR, st));           // rows of points at infinity are never written, but are scaled
-        if (m <= g_wide_max.load() && g_wide_max.load() > 0) k_q_lines_wide<<<(unsigned)m, BLOCK, 0, st>>>((const uint8_t *)dQ, dLines, m);
-        else k_q_lines<<<grid_for(m), BLOCK, 0, st>>>((const uint8_t *)dQ, dLines, m);
-        TRY(check_launch("k_q_lines"));
-        profile_mark("k_q_lines", st);
-        k_q_lines_scale<<<grid_for(m * MILLER_LINES), BLOCK, 0, st>>>(dLines, dQ34, m);
-        TRY(check_launch("k_q_lines_scale"));
-        profile_mark("k_q_lines_scale", st);
-        k_g1_line_point<<<grid_for((m * k + LINE_POINT_GROUP - 1) / LINE_POINT_GROUP), BLOCK, 0, st>>>((const uint8_t *)dP, dPint, m * k);
-        TRY(check_launch("k_g1_line_point"));
-        profile_mark("k_g1_line_point", st);
-        k_miller_accumulate_fixed_q<<<grid_for(2 * n_c * k), BLOCK, 0, st>>>(dPint, (const uint8_t *)dQ, dQ34, dPart, m, k, L, n_c);
-        TRY(check_launch("k_miller_accumulate_fixed_q"));
-        profile_mark("k_miller_accumulate_fixed_q", st);
+        if (m <= g_wide_max.load() && g_wide_max.load() > 0) TRY(GPBC_LAUNCH(k_q_lines_wide, (unsigned)m, BLOCK, st, (const uint8_t *)dQ, dLines, m));
+        else TRY(GPBC_LAUNCH(k_q_lines, grid_for(m), BLOCK, st, (const uint8_t *)dQ, dLines, m));
+        TRY(GPBC_LAUNCH(k_q_lines_scale, grid_for(m * MILLER_LINES), BLOCK, st, dLines, dQ34, m));
+        TRY(GPBC_LAUNCH(k_g1_line_point, grid_for((m * k + LINE_POINT_GROUP - 1) / LINE_POINT_GROUP), BLOCK, st, (const uint8_t *)dP, dPint, m * k));
+        TRY(GPBC_LAUNCH(k_miller_accumulate_fixed_q, grid_for(2 * n_c * k), BLOCK, st, dPint, (const uint8_t *)dQ, dQ34, dPart, m, k, L, n_c));
         uint64_t limit = 0;
         TRY(segment_fold_passes(dPart, nullptr, n_c, k, n_c * k, st, &limit));
-        k_chunk_product<<<grid_for(k), BLOCK, 0, st>>>(dPart, (uint8_t *)d_gt_out, k, n_c, limit);      // ciphertext j owns chunk values [j n_c, (j+1) n_c)
-        TRY(check_launch("k_chunk_product"));
-        profile_mark("k_chunk_product", st);
+        TRY(GPBC_LAUNCH(k_chunk_product, grid_for(k), BLOCK, st, dPart, (uint8_t *)d_gt_out, k, n_c, limit));      // ciphertext j owns chunk values [j n_c, (j+1) n_c)
     }
     return gpbc_final_exp_dev(d_gt_out, k, d_gt_out, st);
-}
-static int multi_pair_fixed_q_one(const void *P, const void *Q, size_t m, size_t k, void *gt_out) {
-    TRY(bind_device());
-    DevBuf dP, dQ, dG;
-    TRY(dP.upload(P, m * k * GPBC_G1_BYTES)); TRY(dQ.upload(Q, m * GPBC_G2_BYTES)); TRY(dG.alloc(k * GPBC_GT_BYTES));
-    TRY(gpbc_multi_pair_fixed_q_dev(dP.p, dQ.p, m, k, dG.p, nullptr));
-    return dG.download(gt_out, k * GPBC_GT_BYTES);
 }
 int gpbc_multi_pair_fixed_q(const void *P, const void *Q, size_t m, size_t k, void *gt_out) {
     if (!k || !m) return fail(GPBC_ERR_INVALID_ARG, "invalid inputs sizes");
     if (!P || !Q || !gt_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
     // segments are the independent units; every device computes the lines of the shared Q list for itself
     const size_t min_seg = (SHARD_MIN_UNITS + m - 1) / m;
-    return run_sharded(k, min_seg, [=](size_t lo, size_t hi) {
-        return multi_pair_fixed_q_one((const uint8_t *)P + lo * m * GPBC_G1_BYTES, Q, m, hi - lo, (uint8_t *)gt_out + lo * GPBC_GT_BYTES);
-    });
+    return host_call_sharded(k, min_seg, HostCall().input(P, m * GPBC_G1_BYTES).input(Q, m * GPBC_G2_BYTES, true).output(gt_out, GPBC_GT_BYTES), HostRoute(),
+                             [m](const DevCols &d, size_t n, hipStream_t st) { return gpbc_multi_pair_fixed_q_dev(d.in[0], d.in[1], m, n, d.out[0], st); });
 }
 int gpbc_multi_pair_hostseg_dev(const void *dP, const void *dQ, const uint64_t *seg_off, size_t k, void *d_gt_out, void *stream) {
     if (!k) return fail(GPBC_ERR_INVALID_ARG, "invalid inputs sizes");
@@ -1229,37 +1089,30 @@ int gpbc_multi_pair_hostseg_dev(const void *dP, const void *dQ, const uint64_t *
     TRY(bind_device());
     return multi_pair_core((const uint8_t *)dP, (const uint8_t *)dQ, seg_off, k, n_pairs, (uint8_t *)d_gt_out, nullptr, (hipStream_t)stream);
 }
-static int multi_pair_host_one(const void *P, const void *Q, const uint64_t *seg_off, size_t k, size_t n_pairs, void *gt_out, uint8_t *ok_out) {
-    TRY(bind_device());
-    if (small_call_ok(n_pairs) && small_call_ok(k) && g_multi_chunk.load() <= 0) {
-        // a latency call (Pair / PairingCheck as the reference makes them): through the call lanes (small_pairs_run)
-        SmallCall c;
-        c.in[0] = P; c.in[1] = Q; c.out[0] = gt_out; c.out[1] = ok_out; c.units = n_pairs; c.seg = seg_off; c.segs = k;
-        return small_call(CALL_PAIRS, c, small_pairs_run);
-    }
-    DevBuf dP, dQ, dG, dOk;
-    TRY(dP.upload(P, n_pairs * GPBC_G1_BYTES)); TRY(dQ.upload(Q, n_pairs * GPBC_G2_BYTES));
-    TRY(dG.alloc(k * GPBC_GT_BYTES));
-    if (ok_out) TRY(dOk.alloc(k));
-    TRY(multi_pair_core(dP.u8(), dQ.u8(), seg_off, k, n_pairs, dG.u8(), ok_out ? dOk.u8() : nullptr, nullptr));
-    if (gt_out) TRY(dG.download(gt_out, k * GPBC_GT_BYTES));
-    if (ok_out) TRY(dOk.download(ok_out, k));
-    return GPBC_OK;
-}
 static int multi_pair_host(const void *P, const void *Q, const uint64_t *seg_off, size_t k, void *gt_out, uint8_t *ok_out) {
     if (!k) return fail(GPBC_ERR_INVALID_ARG, "invalid inputs sizes");
     size_t n_pairs = 0;
     TRY(check_segments(seg_off, k, &n_pairs));
     if ((n_pairs && (!P || !Q)) || (!gt_out && !ok_out)) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    // one run of segments: a latency call (Pair / PairingCheck as the reference makes them) through the call lanes (small_pairs_run),
+    // a larger one by multi_pair_core; the GT values of a PairingCheck land in the body's temporary block
+    auto run = [=](const void *p, const void *q, const uint64_t *seg, size_t ks, size_t np, void *gt, uint8_t *ok) {
+        HostCall c = HostCall().input(p, np * GPBC_G1_BYTES, true).input(q, np * GPBC_G2_BYTES, true).output(gt, GPBC_GT_BYTES).output(ok, 1);
+        c.units = np; c.seg = seg;
+        const HostRoute r{CALL_PAIRS, small_pairs_run, ks <= small_limit() && g_multi_chunk.load() <= 0 ? small_limit() : 0, 0, 0, gt ? 0 : ks * GPBC_GT_BYTES};
+        return host_call(ks, c, r, [=](const DevCols &d, size_t, hipStream_t st) {
+            return multi_pair_core(d.in[0], d.in[1], seg, ks, np, d.out[0] ? d.out[0] : d.tmp, d.out[1], st);
+        });
+    };
     // segments are the independent units: a shard is a run of whole segments with its table rebased to zero
     const size_t avg = n_pairs / k ? n_pairs / k : 1;
     return run_sharded(k, (SHARD_MIN_UNITS + avg - 1) / avg, [=](size_t lo, size_t hi) {
-        if (lo == 0 && hi == k) return multi_pair_host_one(P, Q, seg_off, k, n_pairs, gt_out, ok_out);
+        if (lo == 0 && hi == k) return run(P, Q, seg_off, k, n_pairs, gt_out, ok_out);
         std::vector<uint64_t> sub(hi - lo + 1);
         const uint64_t base = seg_off[lo];
         for (size_t j = lo; j <= hi; j++) sub[j - lo] = seg_off[j] - base;
-        return multi_pair_host_one((const uint8_t *)P + base * GPBC_G1_BYTES, (const uint8_t *)Q + base * GPBC_G2_BYTES, sub.data(), hi - lo,
-                                   (size_t)sub.back(), gt_out ? (uint8_t *)gt_out + lo * GPBC_GT_BYTES : nullptr, ok_out ? ok_out + lo : nullptr);
+        return run((const uint8_t *)P + base * GPBC_G1_BYTES, (const uint8_t *)Q + base * GPBC_G2_BYTES, sub.data(), hi - lo,
+                   (size_t)sub.back(), gt_out ? (uint8_t *)gt_out + lo * GPBC_GT_BYTES : nullptr, ok_out ? ok_out + lo : nullptr);
     });
 }
 int gpbc_multi_pair(const void *P, const void *Q, const uint64_t *seg_off, size_t k, void *gt_out) {
@@ -1270,47 +1123,20 @@ int gpbc_pairing_check(const void *P, const void *Q, const uint64_t *seg_off, si
     if (!ok_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
     return multi_pair_host(P, Q, seg_off, k, nullptr, ok_out);
 }
-static int gt_exp_one(const void *x, const void *k, size_t n, void *out) {
-    TRY(bind_device());
-    if (small_call_ok(n)) {
-        SmallCall c;
-        c.in[0] = x; c.in[1] = k; c.out[0] = out; c.units = n;
-        return small_call(CALL_GT_EXP, c, small_gt_exp_run);
-    }
-    DevBuf dX, dK, dO;
-    TRY(dX.upload(x, n * GPBC_GT_BYTES)); TRY(dK.upload(k, n * GPBC_SCALAR_BYTES)); TRY(dO.alloc(n * GPBC_GT_BYTES));
-    TRY(gpbc_gt_exp_batch_dev(dX.p, dK.p, n, dO.p, nullptr));
-    TRY(sync_default());
-    return dO.download(out, n * GPBC_GT_BYTES);
-}
 int gpbc_gt_exp_batch(const void *x, const void *k, size_t n, void *out) {
     if (!n) return GPBC_OK;
     if (!x || !k || !out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    return run_sharded(n, SHARD_MIN_UNITS, [=](size_t lo, size_t hi) {
-        return gt_exp_one((const uint8_t *)x + lo * GPBC_GT_BYTES, (const uint8_t *)k + lo * GPBC_SCALAR_BYTES, hi - lo, (uint8_t *)out + lo * GPBC_GT_BYTES);
-    });
-}
-static int gt_binary_one(int op, const void *a, const void *b, size_t n, void *out) {
-    TRY(bind_device());
-    if (small_call_ok(n)) {
-        SmallCall c;
-        c.in[0] = a; c.in[1] = b; c.out[0] = out; c.units = n;
-        return op == 0 ? small_call(CALL_GT_MUL, c, small_gt_mul_run) : op == 1 ? small_call(CALL_GT_DIV, c, small_gt_div_run) : small_call(CALL_GT_INV, c, small_gt_inv_run);
-    }
-    DevBuf dA, dB, dO;
-    TRY(dA.upload(a, n * GPBC_GT_BYTES));
-    if (op != 2) TRY(dB.upload(b, n * GPBC_GT_BYTES));
-    TRY(dO.alloc(n * GPBC_GT_BYTES));
-    TRY(gt_binary_dev(op, dA.p, dB.p, n, dO.p, nullptr));
-    TRY(sync_default());
-    return dO.download(out, n * GPBC_GT_BYTES);
+    return host_call_sharded(n, SHARD_MIN_UNITS, HostCall().input(x, GPBC_GT_BYTES).input(k, GPBC_SCALAR_BYTES).output(out, GPBC_GT_BYTES),
+                             HostRoute{CALL_GT_EXP, small_gt_run, small_limit()},
+                             [](const DevCols &d, size_t m, hipStream_t st) { return gpbc_gt_exp_batch_dev(d.in[0], d.in[1], m, d.out[0], st); });
 }
 static int gt_binary_host(int op, const void *a, const void *b, size_t n, void *out) {
     if (!n) return GPBC_OK;
     if (!a || (op != 2 && !b) || !out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    return run_sharded(n, 4 * SHARD_MIN_UNITS, [=](size_t lo, size_t hi) {
-        return gt_binary_one(op, (const uint8_t *)a + lo * GPBC_GT_BYTES, b ? (const uint8_t *)b + lo * GPBC_GT_BYTES : nullptr, hi - lo, (uint8_t *)out + lo * GPBC_GT_BYTES);
-    });
+    HostCall c = HostCall().input(a, GPBC_GT_BYTES);
+    if (op != 2) c.input(b, GPBC_GT_BYTES);
+    return host_call_sharded(n, 4 * SHARD_MIN_UNITS, c.output(out, GPBC_GT_BYTES), HostRoute{(SmallKind)(CALL_GT_MUL + op), small_gt_run, small_limit()},
+                             [op](const DevCols &d, size_t m, hipStream_t st) { return gt_binary_dev(op, d.in[0], d.in[1], m, d.out[0], st); });
 }
 int gpbc_gt_mul_batch(const void *a, const void *b, size_t n, void *o) { return gt_binary_host(0, a, b, n, o); }
 int gpbc_gt_div_batch(const void *a, const void *b, size_t n, void *o) { return gt_binary_host(1, a, b, n, o); }

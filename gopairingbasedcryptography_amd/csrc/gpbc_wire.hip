@@ -299,10 +299,9 @@ static int marshal_dev(int kind, const void *d_in, size_t n, int compressed, voi
     if (d_in == d_out) return fail(GPBC_ERR_INVALID_ARG, "marshal cannot run in place");
     TRY(bind_device());
     hipStream_t st = (hipStream_t)stream;
-    if (kind == 0) k_g1_encode<<<grid_for(n), BLOCK, 0, st>>>((const uint8_t *)d_in, (uint8_t *)d_out, n, compressed);
-    else if (kind == 1) k_g2_encode<<<grid_for(n), BLOCK, 0, st>>>((const uint8_t *)d_in, (uint8_t *)d_out, n, compressed);
-    else k_gt_encode<<<grid_for(n), BLOCK, 0, st>>>((const uint8_t *)d_in, (uint8_t *)d_out, n);
-    return check_launch("wire encode");
+    if (kind == 0) return GPBC_LAUNCH(k_g1_encode, grid_for(n), BLOCK, st, (const uint8_t *)d_in, (uint8_t *)d_out, n, compressed);
+    if (kind == 1) return GPBC_LAUNCH(k_g2_encode, grid_for(n), BLOCK, st, (const uint8_t *)d_in, (uint8_t *)d_out, n, compressed);
+    return GPBC_LAUNCH(k_gt_encode, grid_for(n), BLOCK, st, (const uint8_t *)d_in, (uint8_t *)d_out, n);
 }
 static int unmarshal_dev(int kind, const void *d_in, size_t elem_bytes, size_t n, void *d_out, uint8_t *d_ok, void *stream) {
     if (kind == 0 && elem_bytes != GPBC_G1_COMPRESSED_BYTES && elem_bytes != GPBC_G1_RAW_BYTES)
@@ -314,69 +313,30 @@ static int unmarshal_dev(int kind, const void *d_in, size_t elem_bytes, size_t n
     if (d_in == d_out) return fail(GPBC_ERR_INVALID_ARG, "unmarshal cannot run in place");
     TRY(bind_device());
     hipStream_t st = (hipStream_t)stream;
-    if (kind == 0) k_g1_decode<<<grid_for(n), BLOCK, 0, st>>>((const uint8_t *)d_in, (int)elem_bytes, (uint8_t *)d_out, d_ok, n);
-    else if (kind == 1 && n <= WIRE_OCT_MAX) k_g2_decode_oct<<<grid_for(8 * n), BLOCK, 0, st>>>((const uint8_t *)d_in, (int)elem_bytes, (uint8_t *)d_out, d_ok, n);
-    else if (kind == 1 && n <= WIRE_QUAD_MAX) k_g2_decode_quad<<<grid_for(4 * n), BLOCK, 0, st>>>((const uint8_t *)d_in, (int)elem_bytes, (uint8_t *)d_out, d_ok, n);
-    else if (kind == 1) k_g2_decode<<<grid_for(n), BLOCK, 0, st>>>((const uint8_t *)d_in, (int)elem_bytes, (uint8_t *)d_out, d_ok, n);
-    else k_gt_decode<<<grid_for(n), BLOCK, 0, st>>>((const uint8_t *)d_in, (uint8_t *)d_out, d_ok, n);
-    return check_launch("wire decode");
+    const uint8_t *in = (const uint8_t *)d_in;
+    if (kind == 0) return GPBC_LAUNCH(k_g1_decode, grid_for(n), BLOCK, st, in, (int)elem_bytes, (uint8_t *)d_out, d_ok, n);
+    if (kind == 1 && n <= WIRE_OCT_MAX) return GPBC_LAUNCH(k_g2_decode_oct, grid_for(8 * n), BLOCK, st, in, (int)elem_bytes, (uint8_t *)d_out, d_ok, n);
+    if (kind == 1 && n <= WIRE_QUAD_MAX) return GPBC_LAUNCH(k_g2_decode_quad, grid_for(4 * n), BLOCK, st, in, (int)elem_bytes, (uint8_t *)d_out, d_ok, n);
+    if (kind == 1) return GPBC_LAUNCH(k_g2_decode, grid_for(n), BLOCK, st, in, (int)elem_bytes, (uint8_t *)d_out, d_ok, n);
+    return GPBC_LAUNCH(k_gt_decode, grid_for(n), BLOCK, st, in, (uint8_t *)d_out, d_ok, n);
 }
-static int marshal_one(int kind, const void *in, size_t n, int compressed, void *out) {
-    TRY(bind_device());
-    if (n <= LANE_CALL_MAX_UNITS)      // a small call: through a call lane (pinned block in and out, the lane's stream), gpbc_common.hpp
-        return with_call_lane([&](CallLane &l) {
-            const size_t ib = n * wire_mem_bytes(kind), ob = n * wire_enc_bytes(kind, compressed), o_out = Scratch::padded(ib);
-            TRY(l.reserve(o_out + Scratch::padded(ob), 0));
-            memcpy(l.pin, in, ib);
-            TRY(marshal_dev(kind, l.d_pin, n, compressed, l.d_pin + o_out, l.stream));
-            HIP_TRY(hipStreamSynchronize(l.stream));
-            memcpy(out, l.pin + o_out, ob);
-            return (int)GPBC_OK;
-        });
-    DevBuf dI, dO;
-    TRY(dI.upload(in, n * wire_mem_bytes(kind))); TRY(dO.alloc(n * wire_enc_bytes(kind, compressed)));
-    TRY(marshal_dev(kind, dI.p, n, compressed, dO.p, nullptr));
-    TRY(sync_default());
-    return dO.download(out, n * wire_enc_bytes(kind, compressed));
-}
-// host-pointer entries shard [0, n) over the bound devices (run_sharded, gpbc_core.hip)
+// host-pointer entries shard [0, n) over the bound devices (run_sharded, gpbc_core.hip); a small call goes through a call lane (pinned
+// block in and out, the lane's stream), gpbc_common.hpp
 constexpr size_t WIRE_SHARD_MIN = 65536;
 static int marshal_host(int kind, const void *in, size_t n, int compressed, void *out) {
     if (!n) return GPBC_OK;
     if (!in || !out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    const size_t mb = wire_mem_bytes(kind), eb = wire_enc_bytes(kind, compressed);
-    return run_sharded(n, WIRE_SHARD_MIN, [=](size_t lo, size_t hi) {
-        return marshal_one(kind, (const uint8_t *)in + lo * mb, hi - lo, compressed, (uint8_t *)out + lo * eb);
-    });
-}
-static int unmarshal_one(int kind, const void *in, size_t elem_bytes, size_t n, void *out, uint8_t *ok) {
-    if (n && n <= LANE_CALL_MAX_UNITS)
-        return with_call_lane([&](CallLane &l) {
-            const size_t ib = n * elem_bytes, ob = n * wire_mem_bytes(kind), o_out = Scratch::padded(ib), o_ok = o_out + Scratch::padded(ob);
-            TRY(l.reserve(o_ok + Scratch::padded(n), 0));
-            memcpy(l.pin, in, ib);
-            TRY(unmarshal_dev(kind, l.d_pin, elem_bytes, n, l.d_pin + o_out, l.d_pin + o_ok, l.stream));
-            HIP_TRY(hipStreamSynchronize(l.stream));
-            memcpy(out, l.pin + o_out, ob); memcpy(ok, l.pin + o_ok, n);
-            return (int)GPBC_OK;
-        });
-    DevBuf dI, dO, dK;
-    if (n) {
-        TRY(bind_device());
-        TRY(dI.upload(in, n * elem_bytes)); TRY(dO.alloc(n * wire_mem_bytes(kind))); TRY(dK.alloc(n));
-    }
-    TRY(unmarshal_dev(kind, dI.p, elem_bytes, n, dO.p, dK.u8(), nullptr));
-    if (!n) return GPBC_OK;
-    TRY(sync_default());
-    TRY(dO.download(out, n * wire_mem_bytes(kind)));
-    return dK.download(ok, n);
+    return host_call_sharded(n, WIRE_SHARD_MIN, HostCall().input(in, wire_mem_bytes(kind)).output(out, wire_enc_bytes(kind, compressed)),
+                             HostRoute{CALL_KINDS, nullptr, 0, LANE_CALL_MAX_UNITS},
+                             [=](const DevCols &d, size_t m, hipStream_t st) { return marshal_dev(kind, d.in[0], m, compressed, d.out[0], st); });
 }
 static int unmarshal_host(int kind, const void *in, size_t elem_bytes, size_t n, void *out, uint8_t *ok) {
-    if (n && (!in || !out || !ok)) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    const size_t mb = wire_mem_bytes(kind);
-    return run_sharded(n, kind == 1 ? 8192 : WIRE_SHARD_MIN, [=](size_t lo, size_t hi) {      // G2 decoding carries the subgroup check
-        return unmarshal_one(kind, n ? (const uint8_t *)in + lo * elem_bytes : nullptr, elem_bytes, hi - lo, n ? (uint8_t *)out + lo * mb : nullptr, n ? ok + lo : nullptr);
-    });
+    if (!n) return unmarshal_dev(kind, nullptr, elem_bytes, 0, nullptr, nullptr, nullptr);      // (still rejects a bad elem_bytes)
+    if (!in || !out || !ok) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    const size_t min_units = kind == 1 ? 8192 : WIRE_SHARD_MIN;                 // G2 decoding carries the subgroup check
+    return host_call_sharded(n, min_units, HostCall().input(in, elem_bytes).output(out, wire_mem_bytes(kind)).output(ok, 1),
+                             HostRoute{CALL_KINDS, nullptr, 0, LANE_CALL_MAX_UNITS},
+                             [=](const DevCols &d, size_t m, hipStream_t st) { return unmarshal_dev(kind, d.in[0], elem_bytes, m, d.out[0], d.out[1], st); });
 }
 int gpbc_g1_marshal_batch(const void *p, size_t n, int c, void *o) { return marshal_host(0, p, n, c != 0, o); }
 int gpbc_g2_marshal_batch(const void *p, size_t n, int c, void *o) { return marshal_host(1, p, n, c != 0, o); }
@@ -396,43 +356,20 @@ static int map_fields_dev(bool g2, const void *d_u, size_t n, void *d_out, void 
     if (!n) return GPBC_OK;
     if (!d_u || !d_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
     TRY(bind_device());
-    if (g2 && n <= H2C_OCT_MAX) {
-        k_g2_map_fields_oct<<<grid_for(8 * n), BLOCK, 0, (hipStream_t)stream>>>((const uint8_t *)d_u, (uint8_t *)d_out, n);
-        return check_launch("k_g2_map_fields_oct");
-    }
-    if (n <= H2C_QUAD_MAX) {
-        if (g2) k_g2_map_fields_quad<<<grid_for(4 * n), BLOCK, 0, (hipStream_t)stream>>>((const uint8_t *)d_u, (uint8_t *)d_out, n);
-        else k_g1_map_fields_quad<<<grid_for(4 * n), BLOCK, 0, (hipStream_t)stream>>>((const uint8_t *)d_u, (uint8_t *)d_out, n);
-        return check_launch(g2 ? "k_g2_map_fields_quad" : "k_g1_map_fields_quad");
-    }
-    if (g2) k_g2_map_fields<<<grid_for(n), BLOCK, 0, (hipStream_t)stream>>>((const uint8_t *)d_u, (uint8_t *)d_out, n);
-    else k_g1_map_fields<<<grid_for(n), BLOCK, 0, (hipStream_t)stream>>>((const uint8_t *)d_u, (uint8_t *)d_out, n);
-    return check_launch(g2 ? "k_g2_map_fields" : "k_g1_map_fields");
-}
-static int map_fields_one(bool g2, const void *u, size_t n, void *out) {
-    TRY(bind_device());
-    size_t pt = g2 ? GPBC_G2_BYTES : GPBC_G1_BYTES;               // two field elements occupy as many bytes as one point
-    if (n <= LANE_CALL_MAX_UNITS)
-        return with_call_lane([&](CallLane &l) {
-            const size_t o_out = Scratch::padded(n * pt);
-            TRY(l.reserve(2 * o_out, 0));
-            memcpy(l.pin, u, n * pt);
-            TRY(map_fields_dev(g2, l.d_pin, n, l.d_pin + o_out, l.stream));
-            HIP_TRY(hipStreamSynchronize(l.stream));
-            memcpy(out, l.pin + o_out, n * pt);
-            return (int)GPBC_OK;
-        });
-    DevBuf dU, dO;
-    TRY(dU.upload(u, n * pt)); TRY(dO.alloc(n * pt));
-    TRY(map_fields_dev(g2, dU.p, n, dO.p, nullptr));
-    TRY(sync_default());
-    return dO.download(out, n * pt);
+    const hipStream_t st = (hipStream_t)stream;
+    const uint8_t *u = (const uint8_t *)d_u;
+    if (g2 && n <= H2C_OCT_MAX) return GPBC_LAUNCH(k_g2_map_fields_oct, grid_for(8 * n), BLOCK, st, u, (uint8_t *)d_out, n);
+    if (g2 && n <= H2C_QUAD_MAX) return GPBC_LAUNCH(k_g2_map_fields_quad, grid_for(4 * n), BLOCK, st, u, (uint8_t *)d_out, n);
+    if (n <= H2C_QUAD_MAX) return GPBC_LAUNCH(k_g1_map_fields_quad, grid_for(4 * n), BLOCK, st, u, (uint8_t *)d_out, n);
+    if (g2) return GPBC_LAUNCH(k_g2_map_fields, grid_for(n), BLOCK, st, u, (uint8_t *)d_out, n);
+    return GPBC_LAUNCH(k_g1_map_fields, grid_for(n), BLOCK, st, u, (uint8_t *)d_out, n);
 }
 static int map_fields_host(bool g2, const void *u, size_t n, void *out) {
     if (!n) return GPBC_OK;
     if (!u || !out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    const size_t pt = g2 ? GPBC_G2_BYTES : GPBC_G1_BYTES;
-    return run_sharded(n, 8192, [=](size_t lo, size_t hi) { return map_fields_one(g2, (const uint8_t *)u + lo * pt, hi - lo, (uint8_t *)out + lo * pt); });
+    const size_t pt = g2 ? GPBC_G2_BYTES : GPBC_G1_BYTES;               // two field elements occupy as many bytes as one point
+    return host_call_sharded(n, 8192, HostCall().input(u, pt).output(out, pt), HostRoute{CALL_KINDS, nullptr, 0, LANE_CALL_MAX_UNITS},
+                             [=](const DevCols &d, size_t m, hipStream_t st) { return map_fields_dev(g2, d.in[0], m, d.out[0], st); });
 }
 int gpbc_g1_map_to_curve_batch(const void *u, size_t n, void *o) { return map_fields_host(false, u, n, o); }
 int gpbc_g2_map_to_curve_batch(const void *u, size_t n, void *o) { return map_fields_host(true, u, n, o); }
@@ -455,23 +392,21 @@ static int hash_dev(int what, const void *d_msgs, const uint64_t *d_off, size_t 
     const uint8_t *m = (const uint8_t *)d_msgs;
     uint8_t *o = (uint8_t *)d_out;
     switch (what) {
-        case 0: if (n <= H2C_QUAD_MAX) k_g1_hash_quad<<<grid_for(4 * n), BLOCK, 0, st>>>(m, d_off, msgs_bytes, n, d, o);
-                else k_g1_hash<<<grid_for(n), BLOCK, 0, st>>>(m, d_off, msgs_bytes, n, d, o);
-                break;
-        case 1: if (n <= H2C_OCT_MAX) k_g2_hash_oct<<<grid_for(8 * n), BLOCK, 0, st>>>(m, d_off, msgs_bytes, n, d, o);
-                else if (n <= H2C_QUAD_MAX) k_g2_hash_quad<<<grid_for(4 * n), BLOCK, 0, st>>>(m, d_off, msgs_bytes, n, d, o);
-                else k_g2_hash<<<grid_for(n), BLOCK, 0, st>>>(m, d_off, msgs_bytes, n, d, o);
-                break;
-        case 2: k_hash_to_field<2><<<grid_for(n), BLOCK, 0, st>>>(m, d_off, msgs_bytes, n, d, o); break;
-        case 4: k_hash_to_field<4><<<grid_for(n), BLOCK, 0, st>>>(m, d_off, msgs_bytes, n, d, o); break;
+        case 0: if (n <= H2C_QUAD_MAX) return GPBC_LAUNCH(k_g1_hash_quad, grid_for(4 * n), BLOCK, st, m, d_off, msgs_bytes, n, d, o);
+                return GPBC_LAUNCH(k_g1_hash, grid_for(n), BLOCK, st, m, d_off, msgs_bytes, n, d, o);
+        case 1: if (n <= H2C_OCT_MAX) return GPBC_LAUNCH(k_g2_hash_oct, grid_for(8 * n), BLOCK, st, m, d_off, msgs_bytes, n, d, o);
+                if (n <= H2C_QUAD_MAX) return GPBC_LAUNCH(k_g2_hash_quad, grid_for(4 * n), BLOCK, st, m, d_off, msgs_bytes, n, d, o);
+                return GPBC_LAUNCH(k_g2_hash, grid_for(n), BLOCK, st, m, d_off, msgs_bytes, n, d, o);
+        case 2: return GPBC_LAUNCH(k_hash_to_field<2>, grid_for(n), BLOCK, st, m, d_off, msgs_bytes, n, d, o);
+        case 4: return GPBC_LAUNCH(k_hash_to_field<4>, grid_for(n), BLOCK, st, m, d_off, msgs_bytes, n, d, o);
         default: return fail(GPBC_ERR_INVALID_ARG, "count must be 2 or 4");
     }
-    return check_launch("k_hash");
 }
 // Small calls of HashToG1 / HashToG2 (every BLS Sign and Verify starts with one: signature/bls01_signature/bls_signature.go:58-63,75-79) are
 // COMBINED like the pairings (gpbc_common.hpp "Small host-pointer calls"): requests with the same domain-separation tag — the key —
 // share one launch; in[0] = the call's message bytes, seg = its offsets (rebased to 0), units = messages.
-static int small_hash_run(int what, CallLane &lane, SmallCall *const *calls, size_t nc) {
+static int small_hash_run(SmallKind kind, CallLane &lane, SmallCall *const *calls, size_t nc) {
+    const int what = kind == CALL_HASH_G2 ? 1 : 0;
     size_t N = 0, B = 0;
     for (size_t c = 0; c < nc; c++) { N += calls[c]->units; B += (size_t)calls[c]->seg[calls[c]->units]; }
     const size_t ob = hash_out_bytes(what), o_off = Scratch::padded(B), o_out = o_off + Scratch::padded((N + 1) * sizeof(uint64_t));
@@ -492,42 +427,26 @@ static int small_hash_run(int what, CallLane &lane, SmallCall *const *calls, siz
     for (size_t c = 0; c < nc; c++) { memcpy(calls[c]->out[0], lane.pin + o_out + n0 * ob, calls[c]->units * ob); n0 += calls[c]->units; }
     return GPBC_OK;
 }
-static int small_hash_g1_run(CallLane &l, SmallCall *const *c, size_t n) { return small_hash_run(0, l, c, n); }
-static int small_hash_g2_run(CallLane &l, SmallCall *const *c, size_t n) { return small_hash_run(1, l, c, n); }
-static int hash_one(int what, const uint8_t *msgs, const uint64_t *off, size_t n, const void *dst, size_t dst_len, uint8_t *out) {
-    TRY(bind_device());
-    const uint64_t base = off[0], bytes = off[n] - base;
-    std::vector<uint64_t> rel(n + 1);
-    for (size_t i = 0; i <= n; i++) rel[i] = off[i] - base;
-    if ((what == 0 || what == 1) && n <= SMALL_CALL_MAX_UNITS && bytes <= ((size_t)1 << 20) && dst_len <= 255) {
-        SmallCall c;
-        c.in[0] = msgs + base; c.seg = rel.data(); c.units = n; c.out[0] = out; c.key = dst; c.key_len = dst_len;
-        return what == 0 ? small_call(CALL_HASH_G1, c, small_hash_g1_run) : small_call(CALL_HASH_G2, c, small_hash_g2_run);
-    }
-    if (n <= LANE_CALL_MAX_UNITS && bytes <= ((size_t)64 << 20))
-        return with_call_lane([&](CallLane &l) {
-            const size_t ob = n * hash_out_bytes(what), o_off = Scratch::padded(bytes), o_out = o_off + Scratch::padded((n + 1) * sizeof(uint64_t));
-            TRY(l.reserve(o_out + Scratch::padded(ob), 0));
-            if (bytes) memcpy(l.pin, msgs + base, bytes);
-            memcpy(l.pin + o_off, rel.data(), (n + 1) * sizeof(uint64_t));
-            TRY(hash_dev(what, l.d_pin, (const uint64_t *)(l.d_pin + o_off), bytes, n, dst, dst_len, l.d_pin + o_out, l.stream));
-            HIP_TRY(hipStreamSynchronize(l.stream));
-            memcpy(out, l.pin + o_out, ob);
-            return (int)GPBC_OK;
-        });
-    DevBuf dM, dOff, dO;
-    TRY(dM.upload(msgs + base, bytes)); TRY(dOff.upload(rel.data(), (n + 1) * sizeof(uint64_t))); TRY(dO.alloc(n * hash_out_bytes(what)));
-    TRY(hash_dev(what, dM.p, (const uint64_t *)dOff.p, bytes, n, dst, dst_len, dO.p, nullptr));
-    TRY(sync_default());
-    return dO.download(out, n * hash_out_bytes(what));
-}
 static int hash_host(int what, const void *msgs, const uint64_t *off, size_t n, const void *dst, size_t dst_len, void *out) {
     if (!n) return GPBC_OK;
     if (!off || !out || (dst_len && !dst)) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
     for (size_t i = 0; i < n; i++) if (off[i + 1] < off[i]) return fail(GPBC_ERR_INVALID_ARG, "message offsets must not decrease");
     if (off[n] > off[0] && !msgs) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
     const size_t ob = hash_out_bytes(what);
-    return run_sharded(n, 8192, [=](size_t lo, size_t hi) { return hash_one(what, (const uint8_t *)msgs, off + lo, hi - lo, dst, dst_len, (uint8_t *)out + lo * ob); });
+    return run_sharded(n, 8192, [=](size_t lo, size_t hi) {
+        // a shard's messages and its offsets rebased to them, both whole columns; combined calls up to 1 MiB of messages, a lane up to 64 MiB
+        const size_t m = hi - lo;
+        const uint64_t base = off[lo], bytes = off[hi] - base;
+        std::vector<uint64_t> rel(m + 1);
+        for (size_t i = 0; i <= m; i++) rel[i] = off[lo + i] - base;
+        HostCall c = HostCall().input((const uint8_t *)msgs + base, bytes, true).input(rel.data(), (m + 1) * sizeof(uint64_t), true).output((uint8_t *)out + lo * ob, ob);
+        c.seg = rel.data(); c.key = dst; c.key_len = dst_len;
+        const bool combined = (what == 0 || what == 1) && bytes <= ((size_t)1 << 20) && dst_len <= 255;
+        const HostRoute r{what == 1 ? CALL_HASH_G2 : CALL_HASH_G1, small_hash_run, combined ? SMALL_CALL_MAX_UNITS : 0, bytes <= ((size_t)64 << 20) ? LANE_CALL_MAX_UNITS : 0};
+        return host_call(m, c, r, [&](const DevCols &d, size_t, hipStream_t st) {
+            return hash_dev(what, d.in[0], (const uint64_t *)d.in[1], bytes, m, dst, dst_len, d.out[0], st);
+        });
+    });
 }
 int gpbc_hash_to_g1(const void *m, const uint64_t *off, size_t n, const void *dst, size_t dl, void *o) { return hash_host(0, m, off, n, dst, dl, o); }
 int gpbc_hash_to_g2(const void *m, const uint64_t *off, size_t n, const void *dst, size_t dl, void *o) { return hash_host(1, m, off, n, dst, dl, o); }

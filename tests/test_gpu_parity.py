@@ -1111,3 +1111,82 @@ def test_bucket_msm_against_scalar_multiplications(eng, oracle):
                 assert (got_s == want_s).all(), (n, w, name)
                 assert dt < 1.0, (n, w, name, dt)
                 assert (msm(B.cpu().numpy(), Ks) == want_s).all(), (n, w, name, "host entry")
+
+
+def test_profile_labels_are_kernel_names(eng, synth):
+    """Every launch marks its stream under the launched kernel's own name (GPBC_LAUNCH, csrc/gpbc_common.hpp), so the
+    per-kernel timing of gpbc_profile_end bills each kernel to itself: a small and a large call of every host-entry family
+    report only kernels defined in csrc/, and a one-point G2 scalar multiplication reports the octet kernel it runs."""
+    import ctypes
+    import glob
+    import os
+    import re
+    from gopairingbasedcryptography_amd import _lib
+    lib = _lib.load()
+    src = "".join(open(f).read() for f in glob.glob(os.path.join(os.path.dirname(_lib.__file__), "csrc", "*.hip*")))
+    defined = set(re.findall(r"(?:__global__|GPBC_KERNEL\w*) [^;{#]*?\b(k_\w+)\(", src))
+
+    def profiled(fn):
+        _lib.check(lib.gpbc_profile_begin(None))
+        fn()
+        names, ms, cnt, nk = ctypes.create_string_buffer(32 * 64), (ctypes.c_double * 64)(), (ctypes.c_int * 64)(), ctypes.c_int(0)
+        _lib.check(lib.gpbc_profile_end(names, ms, cnt, 64, ctypes.byref(nk)))
+        return [names.raw[32 * i:32 * i + 32].split(b"\0")[0].decode() for i in range(nk.value)]
+
+    P, Q = synth
+    g1, g2 = eng.generators()
+    big = 3000                                                   # above every combined / latency limit, below the pipelined one
+    Pb, Qb = np.tile(P, (100, 1))[:6 * big], np.tile(Q, (100, 1))[:6 * big]
+    GT = np.tile(eng.pair_batch(P[:8], Q[:8]), (625, 1))
+    K = np.random.default_rng(7).integers(0, 256, 32 * 6 * big, dtype=np.uint8)
+
+    def every_family():
+        for n in (1, big):
+            seg = np.arange(0, 2 * n + 1, 2, dtype=np.uint64)
+            eng.pair_batch(Pb[:n], Qb[:n])
+            eng.final_exp(eng.miller_loop(Pb[:n], Qb[:n]))
+            eng.multi_pair(Pb[:2 * n], Qb[:2 * n], seg), eng.pairing_check_batch(Pb[:2 * n], Qb[:2 * n], seg)
+            eng.multi_pair_fixed_q(Pb[:4 * (n // 2 + 1)], Qb[:4])
+            eng.g1_scalar_mul(Pb[:n], K[:32 * n]), eng.g2_scalar_mul(Qb[:n], K[:32 * n])
+            eng.g1_scalar_mul(g1, K[:32 * 6 * n]), eng.g2_scalar_mul(g2, K[:32 * 6 * n])
+            eng.g1_scalar_mul_base(K[:32 * n]), eng.g2_scalar_mul_base(K[:32 * n])
+            eng.FixedBase(g1).mul(K[:32 * 6 * n])
+            eng.g1_sum(Pb[:n]), eng.g2_sum(Qb[:n])
+            eng.g1_scalar_mul_sum(Pb[:6 * n], K[:32 * 6 * n])
+            m = 5000 if n > 1 else 1                             # (GT.Exp's lane-pair kernel starts above two rounds of the chip)
+            eng.gt_exp(GT[:m], K[:32 * m])
+            eng.gt_mul(GT[:n], GT[:n]), eng.gt_div(GT[:n], GT[:n]), eng.gt_inverse(GT[:n])
+            for m in (n, 6 * n):
+                eng.g1_unmarshal(eng.g1_marshal(Pb[:m], compressed=True), elem_bytes=32)
+                eng.g2_unmarshal(eng.g2_marshal(Qb[:m], compressed=True), elem_bytes=64)
+                eng.gt_unmarshal(eng.gt_marshal(np.tile(GT, (4, 1))[:m]))
+                eng.map_to_g1(np.zeros((m, 64), dtype=np.uint8)), eng.map_to_g2(np.zeros((m, 128), dtype=np.uint8))
+                msgs = [b"m%d" % i for i in range(m)]
+                eng.hash_to_g1(msgs, b"DST"), eng.hash_to_g2(msgs, b"DST"), eng.hash_to_field(msgs, b"DST", 4)
+            eng.fp_mul(np.zeros(32 * n, dtype=np.uint8), np.zeros(32 * n, dtype=np.uint8))
+
+    names = profiled(every_family)
+    assert "(begin)" not in names and len(names) >= 30, names
+    assert not [nm for nm in names if nm.split("<")[0] not in defined], (names, sorted(defined))
+    assert profiled(lambda: eng.g2_scalar_mul(g2, K[:32])) == ["k_g2_scalar_mul_oct"]
+
+
+def test_multi_pair_with_every_segment_empty(eng):
+    """A multi-pairing or PairingCheck over segments that hold no pair at all (k = 1 and k = 3, no points): every product is GT's
+    one and every check true, through the Python wrappers and through the raw ABI with null point pointers.  (Such a call has no
+    pairs for the combined latency route and must take the device-block route.)"""
+    import ctypes
+    from gopairingbasedcryptography_amd import _lib
+    lib = _lib.load()
+    g1, g2 = eng.generators()
+    one = eng.pair_batch(np.zeros(64, dtype=np.uint8), g2)[0]
+    none_p, none_q = np.zeros((0, 64), dtype=np.uint8), np.zeros((0, 128), dtype=np.uint8)
+    for k in (1, 3):
+        seg = np.zeros(k + 1, dtype=np.uint64)
+        assert (eng.multi_pair(none_p, none_q, seg) == one).all(), k
+        assert eng.pairing_check_batch(none_p, none_q, seg).all(), k
+        out, ok = np.zeros((k, 384), dtype=np.uint8), np.zeros(k, dtype=np.uint8)
+        vp, sz = ctypes.c_void_p, ctypes.c_size_t(k)
+        _lib.check(lib.gpbc_multi_pair(None, None, vp(seg.ctypes.data), sz, vp(out.ctypes.data)))
+        _lib.check(lib.gpbc_pairing_check(None, None, vp(seg.ctypes.data), sz, vp(ok.ctypes.data)))
+        assert (out == one).all() and ok.all(), k

@@ -1,6 +1,6 @@
 // Diagnostic for the round-2 silent accept (profiles/r02_pool_bisect.txt): which operation of
 //     block = hipMallocAsync(st); hipMemcpyAsync(block, small host table, H2D, st); kernel<<<st>>>(block); hipFreeAsync(block, st); sync
-// is not ordered the way the multi-pairing assumed?  Every variant repeats the call shape of multi_pair_host_one (plain
+// is not ordered the way the multi-pairing assumed?  Every variant repeats the call shape of the multi-pairing host entry (plain
 // hipMalloc / hipMemcpy / hipFree of the point buffers around it) eight times with a different 16-byte table each time; the kernel
 // echoes the table it read and the host compares.  One process, one run; prints one line per variant.
 // build: hipcc -O3 --offload-arch=gfx950 tools/pool_order_probe.hip -o tools/pool_order_probe
