@@ -8,6 +8,7 @@ signature/bls01_signature/bls_signature.go:45,63,81 and cpabe/bsw07/bsw07_cpabe.
     (*G1Affine).ScalarMultiplication(a, s) / ...Base(s)           -> g1_scalar_mul(a, s) / g1_scalar_mul_base(s)
     (*G2Affine).ScalarMultiplication(a, s) / ...Base(s)           -> g2_scalar_mul(a, s) / g2_scalar_mul_base(s)
     (*GT).Exp / Mul / Div / Inverse                               -> gt_exp / gt_mul / gt_div / gt_inverse
+    (*G1Affine).Add / Sub / Double, n at a time (and G2)          -> g1_add / g1_sub / g1_double (g2_...)
     bn254.Generators()                                            -> generators()
 
 plus the batched forms the engine adds (pair_batch, multi_pair, pairing_check_batch).  Points and GT
@@ -373,6 +374,86 @@ def g1_scalar_mul(bases, scalars, out=None):
 def g2_scalar_mul(bases, scalars, out=None):
     lib = _lib.load()
     return _scalar_mul(G2_BYTES, lib.gpbc_g2_scalar_mul_batch, lib.gpbc_g2_scalar_mul_batch_dev, bases, scalars, out)
+
+
+# --------------------------------------------------------------------------------------- elementwise group law
+def _group_op(width, host_fn, dev_fn, a, b, out):
+    """out[i] = a[i] OP b[j] (b is None: doubling); j = i for one b per a, j = 0 for a single b.  Shapes are checked before any C
+    call; `out` may be `a`, or `b` when it holds one point per element (gnark's p.Add(p, q))."""
+    dbl = b is None
+    if _is_torch(a):
+        if a.numel() % width or (not dbl and (not _is_torch(b) or b.numel() % width)):
+            raise ValueError("points must be CUDA tensors of whole %d-byte rows" % width)
+        n = a.numel() // width
+        nb = n if dbl else b.numel() // width
+        if nb not in (1, n):
+            raise ValueError("need one b or one b per a (got %d for %d)" % (nb, n))
+        _ensure_init()
+        out = _tnew(a, n, width) if out is None else out
+        if n == 0:
+            return out
+        specs = [(a, n * width, "a"), (out, n * width, "out")] + ([] if dbl else [(b, nb * width, "b")])
+        _tchk(a, *specs)
+        if dbl:
+            _lib.check(dev_fn(_tptr(a), _sz(n), _tptr(out), _torch_stream()))
+        else:
+            _lib.check(dev_fn(_tptr(a), _tptr(b), _sz(nb), _sz(n), _tptr(out), _torch_stream()))
+        return out
+    if not dbl and _is_torch(b):
+        raise ValueError("a and b must both be CUDA tensors (or both host buffers)")
+    a = _np(a, width)
+    n = a.size // width
+    if not dbl:
+        b = _np(b, width)
+        nb = b.size // width
+        if nb not in (1, n):
+            raise ValueError("need one b or one b per a (got %d for %d)" % (nb, n))
+    if out is None:
+        out = np.empty((n, width), dtype=np.uint8)
+    elif not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"] and out.size == n * width):
+        raise ValueError("out must be a writable contiguous uint8 array of %d bytes" % (n * width))
+    if n == 0:
+        return out
+    _ensure_init()
+    if dbl:
+        _lib.check(host_fn(_ptr(a), _sz(n), _ptr(out)))
+    else:
+        _lib.check(host_fn(_ptr(a), _ptr(b), _sz(nb), _sz(n), _ptr(out)))
+    return out
+
+
+def g1_add(a, b, out=None):
+    """out[i] = a[i] + b[i] (or + b[0] for a single b): G1Affine.Add, batched.  A single Add is cheaper in gnark on the host."""
+    lib = _lib.load()
+    return _group_op(G1_BYTES, lib.gpbc_g1_add_batch, lib.gpbc_g1_add_batch_dev, a, b, out)
+
+
+def g1_sub(a, b, out=None):
+    """out[i] = a[i] - b[i] (or - b[0]): G1Affine.Sub, batched."""
+    lib = _lib.load()
+    return _group_op(G1_BYTES, lib.gpbc_g1_sub_batch, lib.gpbc_g1_sub_batch_dev, a, b, out)
+
+
+def g1_double(a, out=None):
+    """out[i] = 2 a[i]: G1Affine.Double, batched."""
+    lib = _lib.load()
+    return _group_op(G1_BYTES, lib.gpbc_g1_double_batch, lib.gpbc_g1_double_batch_dev, a, None, out)
+
+
+def g2_add(a, b, out=None):
+    """out[i] = a[i] + b[i] (or + b[0]): G2Affine.Add, batched (e.g. [H(m_i)]g2 + pk)."""
+    lib = _lib.load()
+    return _group_op(G2_BYTES, lib.gpbc_g2_add_batch, lib.gpbc_g2_add_batch_dev, a, b, out)
+
+
+def g2_sub(a, b, out=None):
+    lib = _lib.load()
+    return _group_op(G2_BYTES, lib.gpbc_g2_sub_batch, lib.gpbc_g2_sub_batch_dev, a, b, out)
+
+
+def g2_double(a, out=None):
+    lib = _lib.load()
+    return _group_op(G2_BYTES, lib.gpbc_g2_double_batch, lib.gpbc_g2_double_batch_dev, a, None, out)
 
 
 _gen_tables = {}

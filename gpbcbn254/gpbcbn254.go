@@ -293,6 +293,105 @@ func G2ScalarMultiplicationBatch(bases []bn254.G2Affine, s []fr.Element) ([]bn25
 	return out, status(rc)
 }
 
+// G1AddBatch: out[i] = a[i] + b[i] (or + b[0] when len(b) == 1) — loops of (*bn254.G1Affine).Add between batched steps
+// (dabe/lw11_dabe.go:100,157, cpabe/waters11/waters11_cpabe.go:226, bibe/afp25_bibe/afp25_bibe.go:216,252, ...).  out may be a
+// (or b when len(b) == len(a)); nil allocates.  A single Add or Neg stays with gnark: it costs less on the host than a launch.
+func G1AddBatch(out, a, b []bn254.G1Affine) ([]bn254.G1Affine, error) {
+	return g1GroupOp(false, out, a, b)
+}
+
+// G1SubBatch: out[i] = a[i] - b[i] (or - b[0]) — (*bn254.G1Affine).Sub.
+func G1SubBatch(out, a, b []bn254.G1Affine) ([]bn254.G1Affine, error) {
+	return g1GroupOp(true, out, a, b)
+}
+
+// G1DoubleBatch: out[i] = 2 a[i] — (*bn254.G1Affine).Double.
+func G1DoubleBatch(out, a []bn254.G1Affine) ([]bn254.G1Affine, error) {
+	defer pin()()
+	if len(a) == 0 {
+		return out, nil
+	}
+	if out == nil {
+		out = make([]bn254.G1Affine, len(a))
+	}
+	if len(out) != len(a) {
+		return nil, errSizes
+	}
+	rc := C.gpbc_g1_double_batch(unsafe.Pointer(unsafe.SliceData(a)), C.size_t(len(a)), unsafe.Pointer(unsafe.SliceData(out)))
+	return out, status(rc)
+}
+
+// G2AddBatch: out[i] = a[i] + b[i] (or + b[0]) — (*bn254.G2Affine).Add: BSW07 key components D_j = [r]g2 + [r_j]H(j)
+// (cpabe/bsw07/bsw07_cpabe.go:104,119), ZSS04 verification [H(m)]g2 + pk (signature/zss04_signature/zss04_signature.go:327).
+func G2AddBatch(out, a, b []bn254.G2Affine) ([]bn254.G2Affine, error) {
+	return g2GroupOp(false, out, a, b)
+}
+
+// G2SubBatch: out[i] = a[i] - b[i] (or - b[0]) — (*bn254.G2Affine).Sub.
+func G2SubBatch(out, a, b []bn254.G2Affine) ([]bn254.G2Affine, error) {
+	return g2GroupOp(true, out, a, b)
+}
+
+// G2DoubleBatch: out[i] = 2 a[i] — (*bn254.G2Affine).Double.
+func G2DoubleBatch(out, a []bn254.G2Affine) ([]bn254.G2Affine, error) {
+	defer pin()()
+	if len(a) == 0 {
+		return out, nil
+	}
+	if out == nil {
+		out = make([]bn254.G2Affine, len(a))
+	}
+	if len(out) != len(a) {
+		return nil, errSizes
+	}
+	rc := C.gpbc_g2_double_batch(unsafe.Pointer(unsafe.SliceData(a)), C.size_t(len(a)), unsafe.Pointer(unsafe.SliceData(out)))
+	return out, status(rc)
+}
+
+// g1GroupOp: Add (sub == false) or Sub over the batch (cgo cannot take a C function as a value, hence the flag)
+func g1GroupOp(sub bool, out, a, b []bn254.G1Affine) ([]bn254.G1Affine, error) {
+	defer pin()()
+	if len(a) == 0 {
+		return out, nil
+	}
+	if out == nil {
+		out = make([]bn254.G1Affine, len(a))
+	}
+	if (len(b) != 1 && len(b) != len(a)) || len(out) != len(a) {
+		return nil, errSizes
+	}
+	pa, pb, po := unsafe.Pointer(unsafe.SliceData(a)), unsafe.Pointer(unsafe.SliceData(b)), unsafe.Pointer(unsafe.SliceData(out))
+	var rc C.int
+	if sub {
+		rc = C.gpbc_g1_sub_batch(pa, pb, C.size_t(len(b)), C.size_t(len(a)), po)
+	} else {
+		rc = C.gpbc_g1_add_batch(pa, pb, C.size_t(len(b)), C.size_t(len(a)), po)
+	}
+	return out, status(rc)
+}
+
+// g2GroupOp: Add (sub == false) or Sub over the batch (cgo cannot take a C function as a value, hence the flag)
+func g2GroupOp(sub bool, out, a, b []bn254.G2Affine) ([]bn254.G2Affine, error) {
+	defer pin()()
+	if len(a) == 0 {
+		return out, nil
+	}
+	if out == nil {
+		out = make([]bn254.G2Affine, len(a))
+	}
+	if (len(b) != 1 && len(b) != len(a)) || len(out) != len(a) {
+		return nil, errSizes
+	}
+	pa, pb, po := unsafe.Pointer(unsafe.SliceData(a)), unsafe.Pointer(unsafe.SliceData(b)), unsafe.Pointer(unsafe.SliceData(out))
+	var rc C.int
+	if sub {
+		rc = C.gpbc_g2_sub_batch(pa, pb, C.size_t(len(b)), C.size_t(len(a)), po)
+	} else {
+		rc = C.gpbc_g2_add_batch(pa, pb, C.size_t(len(b)), C.size_t(len(a)), po)
+	}
+	return out, status(rc)
+}
+
 // G1ScalarMulSum = sum_i [s[i]] bases[i]: the verifier's side of BLS aggregate verification with random linear
 // combination (a loop of ScalarMultiplication + Add in the reference's style, gka/agka09/asbb.go:193-220), sharded over
 // all bound GPUs with the partial sums combined inside the library.

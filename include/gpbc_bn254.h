@@ -192,6 +192,31 @@ size_t gpbc_sum_workspace_bytes(size_t n, int is_g2);
 int gpbc_g1_sum_dev(const void *d_pts, size_t n, void *d_out, void *d_workspace, size_t workspace_bytes, void *stream);
 int gpbc_g2_sum_dev(const void *d_pts, size_t n, void *d_out, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---- elementwise group law -----------------------------------------------------------------------
+ * (*G1Affine|*G2Affine).Add(a, b) / Sub(a, b) / Double(a), n times, between device-resident steps of a scheme: key generation
+ * (cpabe/bsw07/bsw07_cpabe.go:104,119 D_j = [r]g2 + [r_j]H(j); dabe/lw11_dabe.go:100; fibe/sw05_fibe_large_universe.go:179;
+ * ibe/gentry06_ibe/gentry06_ibe.go:161), encryption (cpabe/waters11/waters11_cpabe.go:226; bibe/afp25_bibe/afp25_bibe.go:216,252;
+ * dabe/lw11_dabe.go:157; bibe/gwww25_bibe/gwww25_bibe.go:143,147), verification (signature/zss04_signature/zss04_signature.go:327
+ * [H(m)]g2 + pk; signature/bb04_signature/bb04_signature.go:277-278).
+ *   out[i] = a[i] + b[j],  a[i] - b[j],  2 a[i]      j = i when nb == n, j = 0 when nb == 1 (one b for every a, e.g. a public key)
+ * gnark's semantics: the all-zero point is infinity, P + inf = P, P + P doubles, P + (-P) = inf (all zero); outputs canonical,
+ * bit-identical to gnark.  Inputs are taken to be on the curve, as gnark does.  out may be a, or b when nb == n (gnark's
+ * p.Add(p, q)); any other overlap is undefined.  n == 0 is a no-op.  Elements share field inversions in groups (affine formulas,
+ * Montgomery's trick), so a batch costs a few products per element; a single Add / Neg stays with gnark on the host (a launch
+ * costs more than it). */
+int gpbc_g1_add_batch(const void *a, const void *b, size_t nb, size_t n, void *out);
+int gpbc_g1_sub_batch(const void *a, const void *b, size_t nb, size_t n, void *out);
+int gpbc_g1_double_batch(const void *a, size_t n, void *out);
+int gpbc_g2_add_batch(const void *a, const void *b, size_t nb, size_t n, void *out);
+int gpbc_g2_sub_batch(const void *a, const void *b, size_t nb, size_t n, void *out);
+int gpbc_g2_double_batch(const void *a, size_t n, void *out);
+int gpbc_g1_add_batch_dev(const void *d_a, const void *d_b, size_t nb, size_t n, void *d_out, void *stream);
+int gpbc_g1_sub_batch_dev(const void *d_a, const void *d_b, size_t nb, size_t n, void *d_out, void *stream);
+int gpbc_g1_double_batch_dev(const void *d_a, size_t n, void *d_out, void *stream);
+int gpbc_g2_add_batch_dev(const void *d_a, const void *d_b, size_t nb, size_t n, void *d_out, void *stream);
+int gpbc_g2_sub_batch_dev(const void *d_a, const void *d_b, size_t nb, size_t n, void *d_out, void *stream);
+int gpbc_g2_double_batch_dev(const void *d_a, size_t n, void *d_out, void *stream);
+
 /* sum_i [s_i] P_i — the verifier's side of BLS aggregate verification with random linear combination (BASELINE config 3:
  * A = sum rho_i pk_i in G1, B = sum rho_i sigma_i in G2; signature/bls01_signature/bls_signature.go:71-89 verifies one,
  * gka/agka09/asbb_test.go:203-238 has the aggregate shape).  nbase == n.

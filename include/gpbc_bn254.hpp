@@ -205,6 +205,30 @@ inline std::vector<G2Affine> G2ScalarMultiplicationBatch(const std::vector<G2Aff
     check(gpbc_g2_scalar_mul_batch(bases.data(), bases.size(), s.data(), s.size(), out.data()));
     return out;
 }
+// out[i] = a[i] + b[i] / a[i] - b[i] / 2 a[i]: batched G1Affine.Add / Sub / Double (and G2); b holds a.size() points or one point
+// for all (a public key added to every [H(m_i)]g2).  A single Add or Neg is cheaper in place on the host (G1Affine::Neg above).
+namespace detail {
+template <class P, class Fn> inline std::vector<P> group_op(const std::vector<P> &a, const std::vector<P> &b, Fn fn) {
+    if (b.size() != 1 && b.size() != a.size()) throw std::invalid_argument("need one b or one b per a");
+    std::vector<P> out(a.size());
+    check(fn(a.data(), b.data(), b.size(), a.size(), out.data()));
+    return out;
+}
+}  // namespace detail
+inline std::vector<G1Affine> G1AddBatch(const std::vector<G1Affine> &a, const std::vector<G1Affine> &b) { return detail::group_op(a, b, gpbc_g1_add_batch); }
+inline std::vector<G1Affine> G1SubBatch(const std::vector<G1Affine> &a, const std::vector<G1Affine> &b) { return detail::group_op(a, b, gpbc_g1_sub_batch); }
+inline std::vector<G1Affine> G1DoubleBatch(const std::vector<G1Affine> &a) {
+    std::vector<G1Affine> out(a.size());
+    check(gpbc_g1_double_batch(a.data(), a.size(), out.data()));
+    return out;
+}
+inline std::vector<G2Affine> G2AddBatch(const std::vector<G2Affine> &a, const std::vector<G2Affine> &b) { return detail::group_op(a, b, gpbc_g2_add_batch); }
+inline std::vector<G2Affine> G2SubBatch(const std::vector<G2Affine> &a, const std::vector<G2Affine> &b) { return detail::group_op(a, b, gpbc_g2_sub_batch); }
+inline std::vector<G2Affine> G2DoubleBatch(const std::vector<G2Affine> &a) {
+    std::vector<G2Affine> out(a.size());
+    check(gpbc_g2_double_batch(a.data(), a.size(), out.data()));
+    return out;
+}
 // k products against ONE list of G2 points (a decryption key against k ciphertexts): out[j] = Pair(P[j*m .. (j+1)*m), Q);
 // the Miller lines of Q are computed once (gnark: PrecomputeLines / MillerLoopFixedQ)
 inline std::vector<GT> PairFixedQ(const std::vector<G1Affine> &P, const std::vector<G2Affine> &Q) {

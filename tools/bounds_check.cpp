@@ -1,4 +1,4 @@
-// Host build of the DEVICE arithmetic (csrc/fe29.hip.hpp, tower29.hip.hpp, curve29.hip.hpp, pairing29.hip.hpp) with -DGPBC_BOUNDS:
+// Host build of the DEVICE arithmetic (csrc/fe29.hip.hpp, tower29.hip.hpp, curve29.hip.hpp, pairing29.hip.hpp, group29.hip.hpp ...) with -DGPBC_BOUNDS:
 // every field element carries data-independent magnitude bounds and every product asserts that its int64 column
 // accumulators cannot overflow (abort() on violation).  This is a verification harness for tests/ only — it is
 // never loaded by the product path (which has no CPU fallback).
@@ -16,6 +16,7 @@
 #include "../gopairingbasedcryptography_amd/csrc/wire29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/h2c29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/msm29.hip.hpp"
+#include "../gopairingbasedcryptography_amd/csrc/group29.hip.hpp"
 #include <condition_variable>
 #include <mutex>
 #include <thread>
@@ -127,6 +128,17 @@ struct WideHost {
         pending.clear(); pending_half.clear();
     }
 };
+// elementwise group law exactly as k_g1_add .. k_g2_dbl (csrc/gpbc_group.hip) run it: the same lane function of group29.hip.hpp with
+// the same grouping (lane t owns elements t, t + T, ... with T = ceil(n / k)); op 0 ADD, 1 SUB, 2 DBL; nb = 1 broadcasts B[0].
+// k = 0 takes the kernels' K (GROUP_K_G1 / GROUP_K_G2).  No cross-lane step: every lane runs on its own, one after the other.
+template <class F, int K> static void group_host(int op, const uint8_t *A, const uint8_t *B, size_t nb, size_t n, uint8_t *out) {
+    const size_t T = (n + K - 1) / K, step = nb == n && op != GROUP_DBL ? GroupPt<F>::BYTES : 0;
+    for (size_t t = 0; t < T; t++) {
+        if (op == GROUP_ADD) group_op_lane<F, K, GROUP_ADD>(A, B, step, out, n, t, T);
+        else if (op == GROUP_SUB) group_op_lane<F, K, GROUP_SUB>(A, B, step, out, n, t, T);
+        else group_op_lane<F, K, GROUP_DBL>(A, A, 0, out, n, t, T);
+    }
+}
 extern "C" {
 
 // one pairing per "wavefront": Miller loop and final exponentiation of the latency form (k_miller_wide / k_final_exp_wide)
@@ -433,6 +445,24 @@ void hc_g1_fb_msm(const uint8_t *B, size_t nbase, const uint8_t *K, size_t n_msm
         fe_store(out + 64 * m, a.x); fe_store(out + 64 * m + 32, a.y);
     }
 }
+int hc_group_op(int is_g2, int op, const uint8_t *A, const uint8_t *B, size_t nb, size_t n, uint8_t *out, int k) {
+    if (op < 0 || op > 2 || (op != GROUP_DBL && nb != 1 && nb != n)) return -1;
+    if (k == 0) k = is_g2 ? GROUP_K_G2 : GROUP_K_G1;
+    switch (k * 2 + (is_g2 ? 1 : 0)) {
+        case 2: group_host<Fe, 1>(op, A, B, nb, n, out); break;
+        case 3: group_host<F2, 1>(op, A, B, nb, n, out); break;
+        case 8: group_host<Fe, 4>(op, A, B, nb, n, out); break;
+        case 9: group_host<F2, 4>(op, A, B, nb, n, out); break;
+        case 12: group_host<Fe, 6>(op, A, B, nb, n, out); break;
+        case 13: group_host<F2, 6>(op, A, B, nb, n, out); break;
+        case 16: group_host<Fe, 8>(op, A, B, nb, n, out); break;
+        case 17: group_host<F2, 8>(op, A, B, nb, n, out); break;
+        default: return -1;
+    }
+    stats_flush();
+    return 0;
+}
+int hc_group_k(int is_g2) { return is_g2 ? GROUP_K_G2 : GROUP_K_G1; }
 void hc_msm(int g2, const uint8_t *B, const uint8_t *K, size_t n, int c, uint8_t *out) {
     if (!g2) msm_host<Fe>(B, K, n, c, out, 64,
                           [](const uint8_t *p) { return AffP<Fe>{fe_load(p), fe_load(p + 32), bytes_all_zero(p, 16)}; },
