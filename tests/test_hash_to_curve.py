@@ -1,6 +1,6 @@
 """Hash to curve on the CPU: RFC 9380's published expand_message_xmd vectors, the oracle against the
 committed fixture, the host-side hashing of the product mirror (hash_to.py — plain hashlib, no GPU needed) against the
-oracle, and the DEVICE code of csrc/h2c29.hip.hpp compiled for the host under the bounds harness against the fixture."""
+oracle, and the DEVICE code of csrc/h2c29.hip.hpp compiled for the host under the bounds harness against the fixture and the map corpus of tests/wire_cases.py."""
 import ctypes
 import os
 import subprocess
@@ -74,7 +74,7 @@ def test_host_hashing_of_the_mirror_matches_oracle():
 def _map(hc, g2, rows):
     w = 128 if g2 else 64
     u = np.frombuffer(b"".join(rows), dtype=np.uint8).copy()
-    out = np.zeros((len(rows), w), dtype=np.uint8)
+    out = np.full((len(rows), w), 0xAA, dtype=np.uint8)
     hc.hc_map_fields(int(g2), vp(u), ctypes.c_size_t(len(rows)), vp(out))
     return out
 
@@ -90,3 +90,15 @@ def test_device_code_under_bounds_matches_fixture(hc):
     out = _map(hc, True, [f2(c["u"][0]) + f2(c["u"][1]) for c in cases])
     for i, c in enumerate(cases):
         assert out[i].tobytes().hex() == c["point"], ("g2", i)
+
+
+def test_edge_corpus_maps_as_the_oracle_says(hc):
+    """The map corpus of tests/wire_cases.py through the device code: the fixture's rows, equal and opposite elements, zero, p - 1, the
+    exceptional u, and for G2 elements that drive the map onto an x1 with g(x1) in Fp — the real-root and imaginary-root branches of
+    f2_sqrt's "a lies in Fp" case, the latter also sgn0's "a0 is zero" case — bit for bit against the big-integer oracle."""
+    import wire_cases as wc
+    for g2 in (False, True):
+        corpus = wc.map_cases(g2)
+        out = _map(hc, g2, [c.data for c in corpus.cases])
+        ok = np.ones(len(corpus), dtype=np.uint8)
+        assert not wc.mismatches(corpus, np.arange(len(corpus)), out, ok, corpus.rows, ok), g2

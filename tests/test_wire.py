@@ -1,6 +1,7 @@
 """Wire formats on the CPU: the big-integer oracle against the committed fixture, structural facts of
 the published gnark encoding, and the DEVICE code of csrc/wire29.hip.hpp compiled for the host under the bounds harness
-(tools/bounds_check.cpp) against the same fixture.  The GPU parity tests are in test_gpu_parity.py."""
+(tools/bounds_check.cpp) against the same fixture and against the edge corpus of tests/wire_cases.py.  The GPU parity tests are in
+test_gpu_parity.py, the corpus through every kernel form in test_decode_forms_gpu.py."""
 import ctypes
 import os
 import subprocess
@@ -74,7 +75,7 @@ def test_published_structure():
 
 
 def _encode(hc, kind, mem, n, compressed, width):
-    out = np.zeros((n, width), dtype=np.uint8)
+    out = np.full((n, width), 0xAA, dtype=np.uint8)
     mem = mem.copy()
     hc.hc_wire_encode(kind, vp(mem), ctypes.c_size_t(n), int(compressed), vp(out))
     return out
@@ -166,3 +167,78 @@ def test_g2_subgroup_test_agrees_with_the_definition(hc):
         assert ok.tolist() == want, comp
         for i, p in enumerate(pts):
             assert dec[i].tobytes() == o.g2_to_bytes(p if want[i] else None)
+
+
+# ---------------------------------------------------------------------------------------- the edge corpus (tests/wire_cases.py)
+def _corpus_kinds():
+    import wire_cases as wc
+    yield from ((0, 64, wc.decode_cases("g1", 32)), (0, 64, wc.decode_cases("g1", 64)), (1, 128, wc.decode_cases("g2", 64)),
+                (1, 128, wc.decode_cases("g2", 128)), (2, 384, wc.gt_decode_cases()))
+
+
+def test_edge_corpus_meets_its_class_minimums():
+    """Every class of the corpus holds at least the number of cases it promises with the outcome it promises (the builders assert that),
+    and a third or more of every slot set is refused."""
+    import wire_cases as wc
+    for kind, mem_w, corpus in _corpus_kinds():
+        assert corpus.rows.shape == (len(corpus), mem_w) and set(corpus.ok.tolist()) == {0, 1}
+        assert 3 * int((corpus.ok == 0).sum()) >= len(corpus), (kind, corpus.data.shape)
+        assert not corpus.rows[corpus.ok == 0].any()
+    lo, hi = wc.lex_boundary_points()
+    half = (o.P - 1) // 2
+    assert len(lo) >= 2 and len(hi) >= 2 and all(0 <= half - y < 1 << 32 for _, y in lo) and all(0 < y - half < 1 << 32 for _, y in hi)
+    kinds = [k for _, _, k in wc.twist_points_y2_in_fp()]
+    assert len(kinds) >= 8 and kinds.count("real") >= 2 and kinds.count("imag") >= 2
+    for name, v, canon in wc.word_boundary_values():
+        assert o.gt_unmarshal(bytes(352) + v.to_bytes(32, "big"))[1] == canon, name
+
+
+def test_edge_corpus_decodes_as_the_oracle_says(hc):
+    """The whole decode corpus through the device code: off-subgroup points of every construction, non-canonical coordinates in every
+    slot, values that differ from p in one chosen 32-bit word, y next to (p - 1) / 2, twist points whose y^2 lies in Fp, stray bits
+    under the infinity flag.  ok is exactly 0 or 1 and equals the oracle's; every row equals the oracle's, all zero where refused."""
+    import wire_cases as wc
+    for kind, mem_w, corpus in _corpus_kinds():
+        slot = corpus.data.shape[1]
+        dec, ok = _decode(hc, kind, corpus.data.reshape(-1), slot, len(corpus), mem_w)
+        assert set(ok.tolist()) <= {0, 1}, (kind, slot)
+        assert not wc.mismatches(corpus, np.arange(len(corpus)), dec, ok, corpus.rows, corpus.ok), (kind, slot)
+
+
+def test_edge_corpus_encodes_as_the_oracle_says(hc):
+    """Accepted points of the corpus, the G1 points with y next to (p - 1) / 2 and the twist points whose y has a zero half, through
+    both forms of marshal (the flag of the compressed form is f2_lex_largest's a1 == 0 and a0 == 0 paths on the latter)."""
+    import wire_cases as wc
+    for kind, key in ((0, "g1"), (1, "g2")):
+        for comp in (False, True):
+            corpus = wc.marshal_cases(key, comp)
+            enc = _encode(hc, kind, corpus.data.reshape(-1), len(corpus), comp, corpus.rows.shape[1])
+            ok = np.ones(len(corpus), dtype=np.uint8)
+            assert not wc.mismatches(corpus, np.arange(len(corpus)), enc, ok, corpus.rows, ok), (key, comp)
+
+
+def test_square_roots_branch_by_branch(hc):
+    """fe_sqrt and f2_sqrt on their own: a root squares to its argument; the root of an element of Fp is real where that element is a
+    square in Fp and purely imaginary where it is not (the "a lies in Fp" branch of f2_sqrt); non-squares report ok = 0."""
+    import wire_cases as wc
+    fp_sq, fp_non, f2_real, f2_sq, f2_non = wc.sqrt_cases()
+
+    def run(fn, vals, w, enc):
+        a = np.frombuffer(b"".join(enc(v) for v in vals), dtype=np.uint8).copy()
+        out, ok = np.full((len(vals), w), 0xAA, dtype=np.uint8), np.full(len(vals), 7, dtype=np.uint8)
+        fn(vp(a), ctypes.c_size_t(len(vals)), vp(out), vp(ok))
+        return out, ok
+
+    out, ok = run(hc.hc_fe_sqrt, fp_sq + fp_non, 32, o.fp_to_mont_bytes)
+    assert ok.tolist() == [1] * len(fp_sq) + [0] * len(fp_non)
+    for i, a in enumerate(fp_sq):
+        assert o.fp_from_mont_bytes(out[i].tobytes()) ** 2 % o.P == a, i
+    vals = [(a, 0) for a, _ in f2_real] + f2_sq + f2_non
+    out, ok = run(hc.hc_f2_sqrt, vals, 64, o.f2_to_bytes)
+    assert ok.tolist() == [1] * (len(f2_real) + len(f2_sq)) + [0] * len(f2_non)
+    for i, a in enumerate(vals[:len(f2_real) + len(f2_sq)]):
+        r = o.f2_from_bytes(out[i].tobytes())
+        assert o.f2_sqr(r) == a, i
+        if i < len(f2_real):
+            assert r[0 if f2_real[i][1] == "imag" else 1] == 0, (i, f2_real[i][1])
+            assert (pow(a[0], (o.P - 1) // 2, o.P) in (0, 1)) == (f2_real[i][1] == "real"), i

@@ -394,6 +394,13 @@ void hc_wire_decode(int kind, const uint8_t *in, int elem_bytes, size_t n, uint8
         else ok[i] = gt_wire_decode(out + 384 * i, in + 384 * i);
     }
 }
+// the square roots of csrc/wire29.hip.hpp on their own (gnark fp.Element / E2 in and out): out = the value returned, ok = whether it is a root
+void hc_fe_sqrt(const uint8_t *A, size_t n, uint8_t *out, uint8_t *ok) {
+    for (size_t i = 0; i < n; i++) { bool good; fe_store(out + 32 * i, fe_sqrt(fe_load(A + 32 * i), good)); ok[i] = good ? 1 : 0; }
+}
+void hc_f2_sqrt(const uint8_t *A, size_t n, uint8_t *out, uint8_t *ok) {
+    for (size_t i = 0; i < n; i++) { bool good; f2_store(out + 64 * i, f2_sqrt(f2_load(A + 64 * i), good)); ok[i] = good ? 1 : 0; }
+}
 // hash to curve, group part (csrc/h2c29.hip.hpp): U = n x 2 field elements (gnark fp.Element / E2), out = n affine points
 void hc_map_fields(int g2, const uint8_t *U, size_t n, uint8_t *out) {
     for (size_t i = 0; i < n; i++) {
