@@ -33,6 +33,9 @@ EXPORTS = [
     "gpbc_fixed_base_msm", "gpbc_fixed_base_msm_workspace_bytes", "gpbc_fixed_base_msm_dev", "gpbc_fixed_base_destroy",
     "gpbc_g1_add_batch", "gpbc_g1_sub_batch", "gpbc_g1_double_batch", "gpbc_g2_add_batch", "gpbc_g2_sub_batch", "gpbc_g2_double_batch",
     "gpbc_g1_add_batch_dev", "gpbc_g1_sub_batch_dev", "gpbc_g1_double_batch_dev", "gpbc_g2_add_batch_dev", "gpbc_g2_sub_batch_dev", "gpbc_g2_double_batch_dev",
+    "gpbc_fr_add_batch", "gpbc_fr_sub_batch", "gpbc_fr_mul_batch", "gpbc_fr_neg_batch", "gpbc_fr_inverse_batch", "gpbc_fr_from_mont_batch", "gpbc_fr_to_mont_batch",
+    "gpbc_fr_add_batch_dev", "gpbc_fr_sub_batch_dev", "gpbc_fr_mul_batch_dev", "gpbc_fr_neg_batch_dev", "gpbc_fr_inverse_batch_dev", "gpbc_fr_from_mont_batch_dev",
+    "gpbc_fr_to_mont_batch_dev", "gpbc_fr_poly_from_roots", "gpbc_fr_poly_quotients", "gpbc_fr_poly_from_roots_dev", "gpbc_fr_poly_quotients_dev",
 ]
 
 _lib = None

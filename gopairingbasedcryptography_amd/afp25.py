@@ -115,3 +115,98 @@ def decrypt_batch_arrays(engine, D, pi, sk, C1, C2):
                   np.asarray(sk, dtype=np.uint8).reshape(n, 64)], axis=1)
     X = engine.multi_pair(P, np.asarray(C1, dtype=np.uint8).reshape(3 * n, 128), np.arange(0, 3 * n + 1, 3))
     return engine.gt_div(np.asarray(C2, dtype=np.uint8).reshape(n, 384), X)
+
+
+# ----------------------------------------------------------------------------------------------- from identities and SRS
+# The same decryption with the scalar work on the device (engine.fr_poly_from_roots / fr_poly_quotients, csrc/gpbc_fr.hip): a batch's
+# f(X) is one workgroup, every quotient f(X) / (X - id) one lane, and the coefficient rows go straight from the kernel that makes them
+# into the fixed-base MSM over the SRS table (srs_table: g1, [tau]_1 ... [tau^B]_1) as its scalars.  With CUDA tensors nothing but
+# the identities going in and the messages coming out crosses PCIe.  The functions above stay as the host statement of the same
+# computation; tests compare the two bit for bit.
+QUOTIENT_SCRATCH_BYTES = 256 << 20      # bound on the quotient rows held at once (k x B x (B + 1) x 32 bytes in all: 2.2 GB at 1024 x 256)
+
+
+def _is_torch(x):
+    return type(x).__module__.startswith("torch")
+
+
+def _identity_rows(engine, table, ids):
+    """ids -> (flat scalar rows, k, B) with B = table.nbase - 1: [k][B] Python integers (host rows; the reference's rule that an
+    identity occurs exactly once in its batch, afp25_bibe.go:371-381, is checked here), or k*B scalar rows as a uint8 array / CUDA
+    tensor (taken as they are: keeping a batch's identities distinct is then the caller's business)."""
+    B = table.nbase - 1
+    if B < 1:
+        raise ValueError("the SRS table needs at least two bases (g1 and [tau]_1)")
+    if _is_torch(ids) or isinstance(ids, np.ndarray) and ids.dtype == np.uint8:
+        flat = ids.reshape(-1)
+        n = (flat.numel() if _is_torch(ids) else flat.size) // 32
+        if n * 32 != (flat.numel() if _is_torch(ids) else flat.size) or n == 0 or n % B:
+            raise ValueError("ids must hold a whole number of batches of B = %d identities (32 bytes each)" % B)
+        return flat, n // B, B
+    rows = [[int(x) for x in r] for r in ids]
+    if not rows or any(len(r) != B for r in rows):
+        raise ValueError("ids must hold a whole number of batches of B = %d identities" % B)
+    for r in rows:
+        if len({x % R_ORDER for x in r}) != B:
+            raise ValueError("identity not found in identity list")          # duplicated in its batch: the reference removes more than one
+    return engine.fr_to_bytes([x for r in rows for x in r]), len(rows), B
+
+
+def digests(engine, table, ids):
+    """D_j = [f_j(tau)]_1, f_j(X) = prod_i (X - ids[j][i]), for k batches (Digest, afp25_bibe.go:293-305): [k, 64].
+    One kernel expands all f_j, one fixed-base MSM row per batch commits to them."""
+    rows, k, B = _identity_rows(engine, table, ids)
+    return table.msm(engine.fr_poly_from_roots(rows, B).reshape(-1))
+
+
+def opening_proofs(engine, table, ids, coeffs=None):
+    """pi[j*B + i] = [f_j(tau) / (tau - ids[j][i])]_1 for every identity of every batch: [k*B, 64].  coeffs: the f_j as
+    fr_poly_from_roots gives them (computed here when None).  The quotient rows (B + 1 scalars each) are made chunk by chunk of
+    whole batches in ONE scratch buffer of at most QUOTIENT_SCRATCH_BYTES and consumed by the MSM before the next chunk overwrites
+    them.  An identity that is not a root of its batch's polynomial raises ValueError, as quotient_by_root does."""
+    rows, k, B = _identity_rows(engine, table, ids)
+    stride = table.nbase
+    if coeffs is None:
+        coeffs = engine.fr_poly_from_roots(rows, B)
+    coeffs = coeffs.reshape(-1)
+    per_batch = B * stride * 32
+    chunk = min(k, max(1, QUOTIENT_SCRATCH_BYTES // per_batch))
+    if _is_torch(rows):
+        import torch
+        scratch = torch.empty(chunk * per_batch, dtype=torch.uint8, device=rows.device)
+        okbuf = torch.empty(chunk * B, dtype=torch.uint8, device=rows.device)
+        pi = torch.empty((k * B, 64), dtype=torch.uint8, device=rows.device)
+    else:
+        scratch, okbuf = np.empty(chunk * per_batch, dtype=np.uint8), np.empty(chunk * B, dtype=np.uint8)
+        pi = np.empty((k * B, 64), dtype=np.uint8)
+    for lo in range(0, k, chunk):
+        m = min(chunk, k - lo)
+        q, ok = engine.fr_poly_quotients(coeffs[lo * (B + 1) * 32:(lo + m) * (B + 1) * 32], rows[lo * B * 32:(lo + m) * B * 32], B, stride,
+                                         out=scratch[:m * per_batch], ok=okbuf[:m * B])
+        pi[lo * B:(lo + m) * B] = table.msm(q)
+        if not bool(ok.all()):
+            raise ValueError("identity not found in identity list")
+    return pi
+
+
+def decrypt_batches(engine, table, ids, sk, C1, C2, D=None):
+    """Decrypt k batches of B items from their identities and the SRS table: digests (unless D is given), opening proofs, then
+    decrypt_batch_arrays.  ids: as _identity_rows takes them; sk, D: [k, 64] (one per batch) or [k*B, 64] (one per item);
+    C1: [k*B, 3, 128]; C2: [k*B, 384].  Returns the messages [k*B, 384]."""
+    rows, k, B = _identity_rows(engine, table, ids)
+    coeffs = engine.fr_poly_from_roots(rows, B)
+    if D is None:
+        D = table.msm(coeffs.reshape(-1))
+    pi = opening_proofs(engine, table, rows, coeffs=coeffs)
+    n = k * B
+
+    def per_item(x, name):
+        size = x.numel() if _is_torch(x) else np.asarray(x).size
+        if size == n * 64:
+            return x.reshape(n, 64)
+        if size != k * 64:
+            raise ValueError("%s must hold one point per batch (%d) or per item (%d)" % (name, k, n))
+        if _is_torch(x):
+            return x.reshape(k, 1, 64).expand(k, B, 64).reshape(n, 64)
+        return np.repeat(np.asarray(x, dtype=np.uint8).reshape(k, 64), B, axis=0)
+    return decrypt_batch_arrays(engine, per_item(D, "D"), pi, per_item(sk, "sk"), C1, C2)

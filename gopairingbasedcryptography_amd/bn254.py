@@ -151,21 +151,27 @@ def _tptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
-def _tchk(first, *specs):
-    """Validate the HBM-resident arguments of one call before their raw pointers cross the C ABI: every (tensor, bytes,
-    name) must be a contiguous uint8 CUDA tensor of exactly `bytes` bytes on the device of `first`; that device must be one
-    of the bound ones and becomes the calling thread's current device.  A wrong size here would be an out-of-bounds device
-    access inside a kernel, so it is a ValueError on the host instead."""
-    dev = first.device
+def _tchk_static(first, *specs):
+    """The part of _tchk that needs no bound device — dtype, contiguity, size, one device, CUDA — for wrappers that check their
+    arguments before the engine is initialised."""
     for t, nbytes, name in specs:
         if not _is_torch(t) or t.dtype.__str__() != "torch.uint8" or not t.is_contiguous():
             raise ValueError("%s must be a contiguous uint8 CUDA tensor" % name)
         if t.numel() != nbytes:
             raise ValueError("%s holds %d bytes, expected %d" % (name, t.numel(), nbytes))
-        if t.device != dev:
-            raise ValueError("%s is on %s, expected %s" % (name, t.device, dev))
+        if t.device != first.device:
+            raise ValueError("%s is on %s, expected %s" % (name, t.device, first.device))
     if not first.is_cuda:
         raise ValueError("device buffers must be CUDA tensors (host data goes in as numpy arrays)")
+
+
+def _tchk(first, *specs):
+    """Validate the HBM-resident arguments of one call before their raw pointers cross the C ABI: every (tensor, bytes,
+    name) must be a contiguous uint8 CUDA tensor of exactly `bytes` bytes on the device of `first`; that device must be one
+    of the bound ones and becomes the calling thread's current device.  A wrong size here would be an out-of-bounds device
+    access inside a kernel, so it is a ValueError on the host instead."""
+    _tchk_static(first, *specs)
+    dev = first.device
     idx = dev.index if dev.index is not None else 0
     if _slots is None or idx not in _slots:
         raise ValueError("device %s is not bound: call bn254.init() with it" % dev)
@@ -454,6 +460,207 @@ def g2_sub(a, b, out=None):
 def g2_double(a, out=None):
     lib = _lib.load()
     return _group_op(G2_BYTES, lib.gpbc_g2_double_batch, lib.gpbc_g2_double_batch_dev, a, None, out)
+
+
+# --------------------------------------------------------------------------------------- scalar field Fr
+# fr.Element arithmetic on the scalar format (32-byte little-endian plain integers): inputs are any value < 2^256 and act as their
+# residue mod r, outputs are canonical — ready to be the `scalars` of g1_scalar_mul, FixedBase.msm and gt_exp without leaving HBM.
+FR_POLY_MAX_B = 1024
+
+
+def fr_to_bytes(values):
+    """ints in [0, 2^256) (NOT reduced: the device does that) or a uint8 buffer -> the scalar rows as a flat uint8 array."""
+    if isinstance(values, np.ndarray):
+        if values.dtype != np.uint8:
+            raise ValueError("scalar buffers must be uint8 (got %s)" % values.dtype)
+        a = np.ascontiguousarray(values).reshape(-1)
+    elif isinstance(values, (bytes, bytearray)):
+        a = np.frombuffer(bytes(values), dtype=np.uint8)
+    else:
+        if isinstance(values, int):
+            values = [values]
+        vals = [int(v) for v in values]
+        if any(v < 0 or v >> 256 for v in vals):
+            raise ValueError("scalars must lie in [0, 2^256)")
+        a = np.frombuffer(b"".join(v.to_bytes(32, "little") for v in vals), dtype=np.uint8)
+    if a.size % SCALAR_BYTES:
+        raise ValueError("buffer length %d is not a multiple of %d" % (a.size, SCALAR_BYTES))
+    return a
+
+
+def fr_to_ints(rows):
+    """scalar rows (numpy, or a CUDA tensor: copied to the host) -> Python ints"""
+    if _is_torch(rows):
+        rows = rows.cpu().numpy()
+    b = np.ascontiguousarray(rows, dtype=np.uint8).reshape(-1, SCALAR_BYTES)
+    return [int.from_bytes(r.tobytes(), "little") for r in b]
+
+
+def _host_out(out, nbytes, shape):
+    if out is None:
+        return np.empty(shape, dtype=np.uint8)
+    if not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"] and out.size == nbytes):
+        raise ValueError("out must be a writable contiguous uint8 array of %d bytes" % nbytes)
+    return out
+
+
+def _fr_op(name, a, b, out, binary):
+    """out[i] = a[i] OP b[j] (j = i, or 0 for a single b); unary when not `binary`.  Everything is checked before any C call."""
+    lib = _lib.load()
+    host_fn, dev_fn = getattr(lib, "gpbc_fr_%s_batch" % name), getattr(lib, "gpbc_fr_%s_batch_dev" % name)
+    if _is_torch(a) or (binary and _is_torch(b)):
+        if not _is_torch(a) or (binary and not _is_torch(b)):
+            raise ValueError("a and b must both be CUDA tensors (or both host buffers)")
+        if a.numel() % SCALAR_BYTES or (binary and b.numel() % SCALAR_BYTES):
+            raise ValueError("scalars must be CUDA tensors of whole %d-byte rows" % SCALAR_BYTES)
+        n = a.numel() // SCALAR_BYTES
+        nb = b.numel() // SCALAR_BYTES if binary else n
+        if nb not in (1, n):
+            raise ValueError("need one b or one b per a (got %d for %d)" % (nb, n))
+        specs = [(a, n * SCALAR_BYTES, "a")] + ([(b, nb * SCALAR_BYTES, "b")] if binary else [])
+        if out is not None:
+            specs.append((out, n * SCALAR_BYTES, "out"))
+        _tchk_static(a, *specs)
+        _ensure_init()
+        out = _tnew(a, n, SCALAR_BYTES) if out is None else out
+        if n == 0:
+            return out
+        _tchk(a, *specs)
+        if binary:
+            _lib.check(dev_fn(_tptr(a), _tptr(b), _sz(nb), _sz(n), _tptr(out), _torch_stream()))
+        else:
+            _lib.check(dev_fn(_tptr(a), _sz(n), _tptr(out), _torch_stream()))
+        return out
+    a = fr_to_bytes(a)
+    n = a.size // SCALAR_BYTES
+    if binary:
+        b = fr_to_bytes(b)
+        nb = b.size // SCALAR_BYTES
+        if nb not in (1, n):
+            raise ValueError("need one b or one b per a (got %d for %d)" % (nb, n))
+    out = _host_out(out, n * SCALAR_BYTES, (n, SCALAR_BYTES))
+    if n == 0:
+        return out
+    _ensure_init()
+    if binary:
+        _lib.check(host_fn(_ptr(a), _ptr(b), _sz(nb), _sz(n), _ptr(out)))
+    else:
+        _lib.check(host_fn(_ptr(a), _sz(n), _ptr(out)))
+    return out
+
+
+def fr_add(a, b, out=None):
+    """out[i] = a[i] + b[i] mod r (or + b[0] for a single b): fr.Element.Add, batched."""
+    return _fr_op("add", a, b, out, True)
+
+
+def fr_sub(a, b, out=None):
+    return _fr_op("sub", a, b, out, True)
+
+
+def fr_mul(a, b, out=None):
+    return _fr_op("mul", a, b, out, True)
+
+
+def fr_neg(a, out=None):
+    return _fr_op("neg", a, None, out, False)
+
+
+def fr_inverse(a, out=None):
+    """fr.Element.Inverse, batched: 1 / a[i] mod r, and 0 where a[i] is 0 mod r."""
+    return _fr_op("inverse", a, None, out, False)
+
+
+def fr_from_mont(a, out=None):
+    """fr.Element in-memory words (4 x uint64, x 2^256 mod r) -> the scalar format."""
+    return _fr_op("from_mont", a, None, out, False)
+
+
+def fr_to_mont(a, out=None):
+    """the scalar format -> canonical fr.Element in-memory words."""
+    return _fr_op("to_mont", a, None, out, False)
+
+
+def _fr_poly_shape(nscalars, per_poly, what):
+    if per_poly < 1 or nscalars % per_poly:
+        raise ValueError("%s: %d scalars are not a whole number of rows of %d" % (what, nscalars, per_poly))
+    return nscalars // per_poly
+
+
+def fr_poly_from_roots(roots, B=None, out=None):
+    """k polynomials prod_{i<B} (X - roots[j][i]), coefficients constant term first: [k, B + 1, 32] (computePolynomialCoeffs).
+    roots: [k][B] Python ints, or k x B scalar rows as a uint8 array / CUDA tensor together with B."""
+    lib = _lib.load()
+    if not _is_torch(roots) and not isinstance(roots, (np.ndarray, bytes, bytearray)):
+        rows = [list(r) for r in roots]
+        B = len(rows[0]) if rows and B is None else B
+        if any(len(r) != B for r in rows):
+            raise ValueError("every polynomial needs B = %s roots" % B)
+        roots = [v for r in rows for v in r]
+    if B is None or not 1 <= int(B) <= FR_POLY_MAX_B:
+        raise ValueError("B must be in 1 .. %d (got %s)" % (FR_POLY_MAX_B, B))
+    B = int(B)
+    if _is_torch(roots):
+        k = _fr_poly_shape(roots.numel() // SCALAR_BYTES if roots.numel() % SCALAR_BYTES == 0 else -1, B, "roots")
+        specs = [(roots, k * B * SCALAR_BYTES, "roots")] + ([(out, k * (B + 1) * SCALAR_BYTES, "out")] if out is not None else [])
+        _tchk_static(roots, *specs)
+        _ensure_init()
+        if out is None:
+            import torch
+            out = torch.empty((k, B + 1, SCALAR_BYTES), dtype=torch.uint8, device=roots.device)
+        if k:
+            _tchk(roots, *specs)
+            _lib.check(lib.gpbc_fr_poly_from_roots_dev(_tptr(roots), _sz(B), _sz(k), _tptr(out), _torch_stream()))
+        return out
+    r = fr_to_bytes(roots)
+    k = _fr_poly_shape(r.size // SCALAR_BYTES, B, "roots")
+    out = _host_out(out, k * (B + 1) * SCALAR_BYTES, (k, B + 1, SCALAR_BYTES))
+    if k:
+        _ensure_init()
+        _lib.check(lib.gpbc_fr_poly_from_roots(_ptr(r), _sz(B), _sz(k), _ptr(out)))
+    return out
+
+
+def fr_poly_quotients(coeffs, points, B, stride=None, out=None, ok=None):
+    """Row j*B + i of the result: the B coefficients of coeffs[j](X) / (X - points[j][i]) followed by stride - B zeros (stride
+    defaults to B); ok[j*B + i] = 1 iff the division is exact, otherwise the row is all zero.  coeffs: k x (B + 1) scalars,
+    points: k x B (ints, uint8 arrays or CUDA tensors).  Returns (q [k*B, stride, 32], ok [k*B])."""
+    lib = _lib.load()
+    if not isinstance(B, int) or not 1 <= B <= FR_POLY_MAX_B:
+        raise ValueError("B must be in 1 .. %d (got %s)" % (FR_POLY_MAX_B, B))
+    stride = B if stride is None else int(stride)
+    if stride < B or stride > 1 << 24:                       # the C entries refuse the same range: sizes and row offsets stay far from overflow
+        raise ValueError("stride must be in B .. 2^24 (got stride = %d, B = %d)" % (stride, B))
+    if _is_torch(coeffs) or _is_torch(points):
+        if not (_is_torch(coeffs) and _is_torch(points)):
+            raise ValueError("coeffs and points must both be CUDA tensors (or both host buffers)")
+        k = _fr_poly_shape(points.numel() // SCALAR_BYTES if points.numel() % SCALAR_BYTES == 0 else -1, B, "points")
+        specs = [(coeffs, k * (B + 1) * SCALAR_BYTES, "coeffs"), (points, k * B * SCALAR_BYTES, "points")]
+        if out is not None:
+            specs.append((out, k * B * stride * SCALAR_BYTES, "out"))
+        if ok is not None:
+            specs.append((ok, k * B, "ok"))
+        _tchk_static(coeffs, *specs)
+        _ensure_init()
+        import torch
+        if out is None:
+            out = torch.empty((k * B, stride, SCALAR_BYTES), dtype=torch.uint8, device=coeffs.device)
+        if ok is None:
+            ok = torch.empty((k * B,), dtype=torch.uint8, device=coeffs.device)
+        if k:
+            _tchk(coeffs, *specs)
+            _lib.check(lib.gpbc_fr_poly_quotients_dev(_tptr(coeffs), _tptr(points), _sz(B), _sz(k), _sz(stride), _tptr(out), _tptr(ok), _torch_stream()))
+        return out, ok
+    c, p = fr_to_bytes(coeffs), fr_to_bytes(points)
+    k = _fr_poly_shape(p.size // SCALAR_BYTES, B, "points")
+    if c.size != k * (B + 1) * SCALAR_BYTES:
+        raise ValueError("coeffs holds %d bytes, expected %d" % (c.size, k * (B + 1) * SCALAR_BYTES))
+    out = _host_out(out, k * B * stride * SCALAR_BYTES, (k * B, stride, SCALAR_BYTES))
+    ok = _host_out(ok, k * B, (k * B,))
+    if k:
+        _ensure_init()
+        _lib.check(lib.gpbc_fr_poly_quotients(_ptr(c), _ptr(p), _sz(B), _sz(k), _sz(stride), _ptr(out), _ptr(ok)))
+    return out, ok
 
 
 _gen_tables = {}

@@ -1,0 +1,234 @@
+// libgpbc_bn254.so, unit 7 of 7: the scalar field Fr on the device (csrc/fr29.hip.hpp) — elementwise add / sub / mul / neg /
+// inverse and the fr.Element conversions on the ABI's scalar format, and the two polynomial kernels of the AFP25 / GWWW25 opening
+// proofs — with their C-ABI entries (include/gpbc_bn254.h, "scalar field").  gfx950 only.
+#include "gpbc_common.hpp"
+#include "fr29.hip.hpp"
+
+// ------------------------------------------------------------------------------------------------ elementwise
+// one element per lane (no __restrict__: out may be a, or b)
+template <int OP> __device__ __forceinline__ void fr_op_kernel(const uint8_t *a, const uint8_t *b, size_t b_step, uint8_t *out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    fr_op_lane<OP>(a + 32 * i, b + i * b_step, out + 32 * i);
+}
+GPBC_KERNEL_G1 k_fr_add(const uint8_t *a, const uint8_t *b, size_t b_step, uint8_t *out, size_t n) { fr_op_kernel<FR_ADD>(a, b, b_step, out, n); }
+GPBC_KERNEL_G1 k_fr_sub(const uint8_t *a, const uint8_t *b, size_t b_step, uint8_t *out, size_t n) { fr_op_kernel<FR_SUB>(a, b, b_step, out, n); }
+GPBC_KERNEL_G1 k_fr_mul(const uint8_t *a, const uint8_t *b, size_t b_step, uint8_t *out, size_t n) { fr_op_kernel<FR_MUL>(a, b, b_step, out, n); }
+GPBC_KERNEL_G1 k_fr_neg(const uint8_t *a, const uint8_t *b, size_t b_step, uint8_t *out, size_t n) { fr_op_kernel<FR_NEG>(a, b, b_step, out, n); }
+GPBC_KERNEL_G1 k_fr_from_mont(const uint8_t *a, const uint8_t *b, size_t b_step, uint8_t *out, size_t n) { fr_op_kernel<FR_FROM_MONT>(a, b, b_step, out, n); }
+GPBC_KERNEL_G1 k_fr_to_mont(const uint8_t *a, const uint8_t *b, size_t b_step, uint8_t *out, size_t n) { fr_op_kernel<FR_TO_MONT>(a, b, b_step, out, n); }
+// FR_INV_K elements per lane share one inversion
+GPBC_KERNEL_G1 k_fr_inverse(const uint8_t *a, uint8_t *out, size_t n) {
+    const size_t T = (n + FR_INV_K - 1) / FR_INV_K, t = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (t >= T) return;
+    fr_inverse_lane<FR_INV_K>(a, out, n, t, T);
+}
+
+// ------------------------------------------------------------------------------------------------ polynomials
+__device__ __forceinline__ Fr lds_get(const int32_t *p) {
+    Fr x;
+#pragma unroll
+    for (int i = 0; i < NL; i++) x.l.v[i] = p[i];
+    return x;
+}
+__device__ __forceinline__ void lds_put(int32_t *p, const Fr &x) {
+#pragma unroll
+    for (int i = 0; i < NL; i++) p[i] = x.l.v[i];
+}
+
+// prod_{i<B} (X - roots[j][i]): one workgroup per polynomial, the coefficients in LDS (nine limbs each, an odd pitch: no bank
+// conflicts), thread t owns the coefficients t, t + 256, ...  One step per root: every coefficient up to the new degree is read
+// with its lower neighbour, a barrier, written, a barrier; coefficients past the current degree are not touched.  The roots are
+// converted 64 at a time by the first wave.
+constexpr int FR_ROOTS_BLOCK = 256, FR_ROOTS_OWN = (FR_POLY_MAX_B + FR_ROOTS_BLOCK) / FR_ROOTS_BLOCK;     // 5 coefficients per thread at B = 1024
+__global__ void __launch_bounds__(FR_ROOTS_BLOCK) k_fr_poly_from_roots(const uint8_t *__restrict__ roots, uint32_t B, uint8_t *__restrict__ coeffs_out) {
+    __shared__ int32_t cs[(FR_POLY_MAX_B + 1) * NL];
+    __shared__ int32_t rs[64 * NL];
+    const uint32_t tid = threadIdx.x;
+    const uint8_t *rt = roots + (size_t)blockIdx.x * B * 32;
+    uint8_t *out = coeffs_out + (size_t)blockIdx.x * (B + 1) * 32;
+    for (uint32_t i = tid; i <= B; i += FR_ROOTS_BLOCK) lds_put(cs + i * NL, i ? fr_zero() : fr_plain_one());
+    for (uint32_t s = 0; s < B; s++) {
+        if ((s & 63) == 0) {
+            if (tid < 64 && s + tid < B) lds_put(rs + tid * NL, fr_poly_neg_root(rt + 32 * (size_t)(s + tid)));
+            __syncthreads();
+        }
+        const Fr nr = lds_get(rs + (s & 63) * NL);
+        Fr nw[FR_ROOTS_OWN];
+#pragma unroll
+        for (int m = 0; m < FR_ROOTS_OWN; m++) {
+            const uint32_t i = tid + m * FR_ROOTS_BLOCK;
+            if (i <= s + 1) nw[m] = fr_poly_root_step(i ? lds_get(cs + (i - 1) * NL) : fr_zero(), lds_get(cs + i * NL), nr);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int m = 0; m < FR_ROOTS_OWN; m++) {
+            const uint32_t i = tid + m * FR_ROOTS_BLOCK;
+            if (i <= s + 1) lds_put(cs + i * NL, nw[m]);
+        }
+        __syncthreads();
+    }
+    for (uint32_t i = tid; i <= B; i += FR_ROOTS_BLOCK) fr_poly_store(out + 32 * (size_t)i, lds_get(cs + i * NL));
+}
+
+// coeffs[j](X) / (X - points[j][i]): one lane per (polynomial, point), one wave per workgroup, 64 points of ONE polynomial per wave.
+// f's coefficients wait in LDS in canonical limbs (every lane of the wave reads the same address: a broadcast); a lane walks from
+// the top coefficient down, one product per step.  The quotient's coefficients are canonical as they fall out of the step, but a
+// lane's row is stride x 32 bytes away from its neighbour's, so they are staged: FR_Q_STEPS steps fill a tile of 64 rows x 256 bytes
+// in LDS, which the wave then writes out row by row, 64 lanes = 256 contiguous bytes.  After the last step the remainder decides
+// ok; then the wave zeroes the padding columns [B, stride) of its rows and, whole, the rows whose division was not exact.
+// Two instances: LDS for B <= 256 (26 KB: six workgroups per CU) and for B <= 1024 (53 KB: two).
+constexpr int FR_Q_STEPS = 8, FR_Q_PITCH = FR_Q_STEPS * 8 + 1, FR_Q_SMALL_B = 256;
+template <int MAXB> __device__ __forceinline__ void fr_poly_quotients_kernel(const uint8_t *__restrict__ coeffs, const uint8_t *__restrict__ points, uint32_t B, uint32_t blocks_per_poly,
+                                                                              size_t stride, uint8_t *__restrict__ q_out, uint8_t *__restrict__ ok_out) {
+    __shared__ int32_t cs[(MAXB + 1) * NL];
+    __shared__ uint32_t tile[BLOCK * FR_Q_PITCH];
+    __shared__ uint32_t oks[BLOCK];
+    const uint32_t lane = threadIdx.x, j = blockIdx.x / blocks_per_poly, first = (blockIdx.x % blocks_per_poly) * BLOCK;
+    const uint32_t pi = first + lane, rows = B - first < BLOCK ? B - first : BLOCK;
+    const bool valid = pi < B;
+    const uint8_t *f = coeffs + (size_t)j * (B + 1) * 32;
+    for (uint32_t i = lane; i <= B; i += BLOCK) lds_put(cs + i * NL, fr_poly_coeff_in(f + 32 * (size_t)i));
+    const Fr point = valid ? fr_poly_point(points + ((size_t)j * B + pi) * 32) : fr_zero();
+    __syncthreads();
+    uint32_t *q = reinterpret_cast<uint32_t *>(q_out) + ((size_t)j * B + first) * stride * 8;      // row 0 of this wave
+    Fr carry = fr_zero();
+    for (int g = (int)((B - 1) / FR_Q_STEPS); g >= 0; g--) {
+        const uint32_t c_lo = (uint32_t)g * FR_Q_STEPS, ncols = B - c_lo < FR_Q_STEPS ? B - c_lo : FR_Q_STEPS;
+        for (int c = (int)ncols - 1; c >= 0; c--) {
+            carry = fr_poly_horner_step(carry, lds_get(cs + (c_lo + c + 1) * NL), point);      // quotient coefficient c_lo + c
+            uint32_t w[8];
+            fr_words(w, carry);
+#pragma unroll
+            for (int k = 0; k < 8; k++) tile[lane * FR_Q_PITCH + c * 8 + k] = w[k];
+        }
+        __syncthreads();
+        if (ncols == FR_Q_STEPS) {
+            for (uint32_t row = 0; row < rows; row++) q[((size_t)row * stride + c_lo) * 8 + lane] = tile[row * FR_Q_PITCH + lane];
+        } else {
+            const uint32_t run = ncols * 8;
+            for (uint32_t idx = lane; idx < rows * run; idx += BLOCK) {
+                const uint32_t row = idx / run, w = idx % run;
+                q[((size_t)row * stride + c_lo) * 8 + w] = tile[row * FR_Q_PITCH + w];
+            }
+        }
+        __syncthreads();
+    }
+    const bool ok = valid && fr_limbs_zero(fr_poly_horner_step(carry, lds_get(cs), point));
+    oks[lane] = ok ? 1u : 0u;
+    if (valid) ok_out[(size_t)j * B + pi] = ok ? 1 : 0;
+    __syncthreads();                                            // also: the rows are written before they are zeroed
+    for (uint32_t row = 0; row < rows; row++)
+        for (size_t w = (oks[row] ? (size_t)B * 8 : 0) + lane; w < stride * 8; w += BLOCK) q[(size_t)row * stride * 8 + w] = 0;
+}
+__global__ void __launch_bounds__(BLOCK) k_fr_poly_quotients(const uint8_t *__restrict__ coeffs, const uint8_t *__restrict__ points, uint32_t B, uint32_t blocks_per_poly, size_t stride,
+                                                             uint8_t *__restrict__ q_out, uint8_t *__restrict__ ok_out) {
+    fr_poly_quotients_kernel<FR_Q_SMALL_B>(coeffs, points, B, blocks_per_poly, stride, q_out, ok_out);
+}
+__global__ void __launch_bounds__(BLOCK) k_fr_poly_quotients_long(const uint8_t *__restrict__ coeffs, const uint8_t *__restrict__ points, uint32_t B, uint32_t blocks_per_poly, size_t stride,
+                                                                  uint8_t *__restrict__ q_out, uint8_t *__restrict__ ok_out) {
+    fr_poly_quotients_kernel<FR_POLY_MAX_B>(coeffs, points, B, blocks_per_poly, stride, q_out, ok_out);
+}
+
+extern "C" {
+
+// ------------------------------------------------------------------------------------------------ elementwise entries
+static int fr_dev(int op, const void *d_a, const void *d_b, size_t nb, size_t n, void *d_out, void *stream) {
+    const bool binary = op == FR_ADD || op == FR_SUB || op == FR_MUL;
+    if (!n) return GPBC_OK;
+    if (!d_a || !d_out || (binary && !d_b)) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    if (binary && nb != 1 && nb != n) return fail(GPBC_ERR_INVALID_ARG, "nb must be 1 or n (got nb = %zu, n = %zu)", nb, n);
+    TRY(bind_device());
+    const hipStream_t st = (hipStream_t)stream;
+    const uint8_t *a = (const uint8_t *)d_a, *b = binary ? (const uint8_t *)d_b : a;
+    uint8_t *o = (uint8_t *)d_out;
+    const size_t step = binary && nb == n ? GPBC_SCALAR_BYTES : 0;
+    const unsigned grid = grid_for(n);
+    switch (op) {
+        case FR_ADD: return GPBC_LAUNCH(k_fr_add, grid, BLOCK, st, a, b, step, o, n);
+        case FR_SUB: return GPBC_LAUNCH(k_fr_sub, grid, BLOCK, st, a, b, step, o, n);
+        case FR_MUL: return GPBC_LAUNCH(k_fr_mul, grid, BLOCK, st, a, b, step, o, n);
+        case FR_NEG: return GPBC_LAUNCH(k_fr_neg, grid, BLOCK, st, a, b, step, o, n);
+        case FR_FROM_MONT: return GPBC_LAUNCH(k_fr_from_mont, grid, BLOCK, st, a, b, step, o, n);
+        case FR_TO_MONT: return GPBC_LAUNCH(k_fr_to_mont, grid, BLOCK, st, a, b, step, o, n);
+        default: return GPBC_LAUNCH(k_fr_inverse, grid_for((n + FR_INV_K - 1) / FR_INV_K), BLOCK, st, a, o, n);
+    }
+}
+// Host-pointer entries: sharded over the bound devices and routed like the group law's (a call lane of its own up to
+// LANE_CALL_MAX_UNITS elements, device blocks above).  Not combined: one Fr operation costs nanoseconds on a host core.
+constexpr int FR_INVERSE = FR_OPS;
+constexpr size_t FR_SHARD_MIN = 4 * 4096;
+static int fr_host(int op, const void *a, const void *b, size_t nb, size_t n, void *out) {
+    const bool binary = op == FR_ADD || op == FR_SUB || op == FR_MUL;
+    if (!n) return GPBC_OK;
+    if (!a || !out || (binary && !b)) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    if (binary && nb != 1 && nb != n) return fail(GPBC_ERR_INVALID_ARG, "nb must be 1 or n (got nb = %zu, n = %zu)", nb, n);
+    const bool one = binary && nb == 1;
+    HostCall c = HostCall().input(a, GPBC_SCALAR_BYTES);
+    if (binary) c.input(b, GPBC_SCALAR_BYTES, one);
+    return host_call_sharded(n, FR_SHARD_MIN, c.output(out, GPBC_SCALAR_BYTES), HostRoute{CALL_KINDS, nullptr, 0, LANE_CALL_MAX_UNITS},
+                             [=](const DevCols &d, size_t m, hipStream_t st) { return fr_dev(op, d.in[0], d.in[1], one ? 1 : m, m, d.out[0], st); });
+}
+int gpbc_fr_add_batch(const void *a, const void *b, size_t nb, size_t n, void *o) { return fr_host(FR_ADD, a, b, nb, n, o); }
+int gpbc_fr_sub_batch(const void *a, const void *b, size_t nb, size_t n, void *o) { return fr_host(FR_SUB, a, b, nb, n, o); }
+int gpbc_fr_mul_batch(const void *a, const void *b, size_t nb, size_t n, void *o) { return fr_host(FR_MUL, a, b, nb, n, o); }
+int gpbc_fr_neg_batch(const void *a, size_t n, void *o) { return fr_host(FR_NEG, a, nullptr, n, n, o); }
+int gpbc_fr_inverse_batch(const void *a, size_t n, void *o) { return fr_host(FR_INVERSE, a, nullptr, n, n, o); }
+int gpbc_fr_from_mont_batch(const void *a, size_t n, void *o) { return fr_host(FR_FROM_MONT, a, nullptr, n, n, o); }
+int gpbc_fr_to_mont_batch(const void *a, size_t n, void *o) { return fr_host(FR_TO_MONT, a, nullptr, n, n, o); }
+int gpbc_fr_add_batch_dev(const void *a, const void *b, size_t nb, size_t n, void *o, void *st) { return fr_dev(FR_ADD, a, b, nb, n, o, st); }
+int gpbc_fr_sub_batch_dev(const void *a, const void *b, size_t nb, size_t n, void *o, void *st) { return fr_dev(FR_SUB, a, b, nb, n, o, st); }
+int gpbc_fr_mul_batch_dev(const void *a, const void *b, size_t nb, size_t n, void *o, void *st) { return fr_dev(FR_MUL, a, b, nb, n, o, st); }
+int gpbc_fr_neg_batch_dev(const void *a, size_t n, void *o, void *st) { return fr_dev(FR_NEG, a, nullptr, n, n, o, st); }
+int gpbc_fr_inverse_batch_dev(const void *a, size_t n, void *o, void *st) { return fr_dev(FR_INVERSE, a, nullptr, n, n, o, st); }
+int gpbc_fr_from_mont_batch_dev(const void *a, size_t n, void *o, void *st) { return fr_dev(FR_FROM_MONT, a, nullptr, n, n, o, st); }
+int gpbc_fr_to_mont_batch_dev(const void *a, size_t n, void *o, void *st) { return fr_dev(FR_TO_MONT, a, nullptr, n, n, o, st); }
+
+// ------------------------------------------------------------------------------------------------ polynomial entries
+static int poly_args(size_t B, size_t k, size_t stride, bool quotients) {
+    if (B < 1 || B > (size_t)FR_POLY_MAX_B) return fail(GPBC_ERR_INVALID_ARG, "B must be in 1 .. %d (got %zu)", FR_POLY_MAX_B, B);
+    if (quotients && stride < B) return fail(GPBC_ERR_INVALID_ARG, "stride must be at least B (got stride = %zu, B = %zu)", stride, B);
+    if (quotients && stride > ((size_t)1 << 24)) return fail(GPBC_ERR_INVALID_ARG, "stride too large (%zu)", stride);
+    const size_t blocks = quotients ? (B + BLOCK - 1) / BLOCK : 1;
+    if (k > (size_t)0x7fffffff / blocks) return fail(GPBC_ERR_INVALID_ARG, "too many polynomials for one call (%zu)", k);
+    return GPBC_OK;
+}
+int gpbc_fr_poly_from_roots_dev(const void *d_roots, size_t B, size_t k, void *d_coeffs_out, void *stream) {
+    TRY(poly_args(B, k, 0, false));
+    if (!k) return GPBC_OK;
+    if (!d_roots || !d_coeffs_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    TRY(bind_device());
+    return GPBC_LAUNCH(k_fr_poly_from_roots, (unsigned)k, FR_ROOTS_BLOCK, (hipStream_t)stream, (const uint8_t *)d_roots, (uint32_t)B, (uint8_t *)d_coeffs_out);
+}
+int gpbc_fr_poly_quotients_dev(const void *d_coeffs, const void *d_points, size_t B, size_t k, size_t stride, void *d_q_out, uint8_t *d_ok_out, void *stream) {
+    TRY(poly_args(B, k, stride, true));
+    if (!k) return GPBC_OK;
+    if (!d_coeffs || !d_points || !d_q_out || !d_ok_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    TRY(bind_device());
+    const uint32_t blocks = (uint32_t)((B + BLOCK - 1) / BLOCK);
+    if (B <= (size_t)FR_Q_SMALL_B)
+        return GPBC_LAUNCH(k_fr_poly_quotients, (unsigned)(k * blocks), BLOCK, (hipStream_t)stream, (const uint8_t *)d_coeffs, (const uint8_t *)d_points, (uint32_t)B, blocks,
+                           stride, (uint8_t *)d_q_out, d_ok_out);
+    return GPBC_LAUNCH(k_fr_poly_quotients_long, (unsigned)(k * blocks), BLOCK, (hipStream_t)stream, (const uint8_t *)d_coeffs, (const uint8_t *)d_points, (uint32_t)B, blocks,
+                       stride, (uint8_t *)d_q_out, d_ok_out);
+}
+// Host-pointer forms: the unit is a polynomial; a shard needs about 2^16 coefficient steps to pay for its thread and transfers.
+static size_t poly_shard_min(size_t B) { const size_t m = ((size_t)1 << 16) / (B * B); return m ? m : 1; }
+int gpbc_fr_poly_from_roots(const void *roots, size_t B, size_t k, void *coeffs_out) {
+    TRY(poly_args(B, k, 0, false));
+    if (!k) return GPBC_OK;
+    if (!roots || !coeffs_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    return host_call_sharded(k, poly_shard_min(B), HostCall().input(roots, B * GPBC_SCALAR_BYTES).output(coeffs_out, (B + 1) * GPBC_SCALAR_BYTES), HostRoute{},
+                             [=](const DevCols &d, size_t m, hipStream_t st) { return gpbc_fr_poly_from_roots_dev(d.in[0], B, m, d.out[0], st); });
+}
+int gpbc_fr_poly_quotients(const void *coeffs, const void *points, size_t B, size_t k, size_t stride, void *q_out, uint8_t *ok_out) {
+    TRY(poly_args(B, k, stride, true));
+    if (!k) return GPBC_OK;
+    if (!coeffs || !points || !q_out || !ok_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    return host_call_sharded(k, poly_shard_min(B),
+                             HostCall().input(coeffs, (B + 1) * GPBC_SCALAR_BYTES).input(points, B * GPBC_SCALAR_BYTES).output(q_out, B * stride * GPBC_SCALAR_BYTES).output(ok_out, B),
+                             HostRoute{},
+                             [=](const DevCols &d, size_t m, hipStream_t st) { return gpbc_fr_poly_quotients_dev(d.in[0], d.in[1], B, m, stride, d.out[0], d.out[1], st); });
+}
+
+}  // extern "C"

@@ -348,6 +348,144 @@ func G2DoubleBatch(out, a []bn254.G2Affine) ([]bn254.G2Affine, error) {
 	return out, status(rc)
 }
 
+// Scalar-field batches: []fr.Element in, []fr.Element out.  Go holds an fr.Element as four Montgomery words (R = 2^256); the engine
+// computes on the ABI's scalar format, so a batch goes through gpbc_fr_from_mont_batch once on the way in and gpbc_fr_to_mont_batch
+// once on the way out — on the device, inside the same call sequence; no BigInt round trip per element.
+const (
+	frAdd = iota
+	frSub
+	frMul
+	frNeg
+	frInverse
+)
+
+// frPlain: the elements' words -> plain 32-byte scalars (what every `scalars` argument of the engine takes)
+func frPlain(s []fr.Element) ([][32]byte, error) {
+	k := make([][32]byte, len(s))
+	if len(s) == 0 {
+		return k, nil
+	}
+	rc := C.gpbc_fr_from_mont_batch(unsafe.Pointer(unsafe.SliceData(s)), C.size_t(len(s)), unsafe.Pointer(unsafe.SliceData(k)))
+	return k, status(rc)
+}
+
+// frElements: plain scalars -> fr.Element words, into out
+func frElements(k [][32]byte, out []fr.Element) error {
+	if len(k) == 0 {
+		return nil
+	}
+	return status(C.gpbc_fr_to_mont_batch(unsafe.Pointer(unsafe.SliceData(k)), C.size_t(len(k)), unsafe.Pointer(unsafe.SliceData(out))))
+}
+
+func frOp(op int, out, a, b []fr.Element) ([]fr.Element, error) {
+	defer pin()()
+	if len(a) == 0 {
+		return out, nil
+	}
+	if out == nil {
+		out = make([]fr.Element, len(a))
+	}
+	binary := op == frAdd || op == frSub || op == frMul
+	if len(out) != len(a) || (binary && len(b) != 1 && len(b) != len(a)) {
+		return nil, errSizes
+	}
+	ka, err := frPlain(a)
+	if err != nil {
+		return nil, err
+	}
+	pa, n := unsafe.Pointer(unsafe.SliceData(ka)), C.size_t(len(a))
+	var rc C.int
+	if binary {
+		kb, err := frPlain(b)
+		if err != nil {
+			return nil, err
+		}
+		pb, nb := unsafe.Pointer(unsafe.SliceData(kb)), C.size_t(len(b))
+		switch op {
+		case frAdd:
+			rc = C.gpbc_fr_add_batch(pa, pb, nb, n, pa)
+		case frSub:
+			rc = C.gpbc_fr_sub_batch(pa, pb, nb, n, pa)
+		default:
+			rc = C.gpbc_fr_mul_batch(pa, pb, nb, n, pa)
+		}
+	} else if op == frNeg {
+		rc = C.gpbc_fr_neg_batch(pa, n, pa)
+	} else {
+		rc = C.gpbc_fr_inverse_batch(pa, n, pa)
+	}
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	return out, frElements(ka, out)
+}
+
+// FrAddBatch / FrSubBatch / FrMulBatch: out[i] = a[i] OP b[i] (or b[0] when len(b) == 1) — loops of fr.Element.Add / Sub / Mul.
+// out may be a or b; nil allocates.  A single operation stays with gnark: it costs nanoseconds on the host.
+func FrAddBatch(out, a, b []fr.Element) ([]fr.Element, error) { return frOp(frAdd, out, a, b) }
+func FrSubBatch(out, a, b []fr.Element) ([]fr.Element, error) { return frOp(frSub, out, a, b) }
+func FrMulBatch(out, a, b []fr.Element) ([]fr.Element, error) { return frOp(frMul, out, a, b) }
+
+// FrNegBatch: out[i] = -a[i].
+func FrNegBatch(out, a []fr.Element) ([]fr.Element, error) { return frOp(frNeg, out, a, nil) }
+
+// FrInverseBatch: out[i] = 1 / a[i], 0 for 0 as fr.Element.Inverse — the exponents 1 / (H(m) + x) of ZSS04 / BB04 signing
+// (signature/zss04_signature/zss04_signature.go:249-252, signature/bb04_signature/bb04_signature.go:233) for a batch of messages.
+func FrInverseBatch(out, a []fr.Element) ([]fr.Element, error) { return frOp(frInverse, out, a, nil) }
+
+// FrPolyFromRoots: k polynomials prod_i (X - roots[j*B + i]), k x (B + 1) coefficients, constant term first —
+// computePolynomialCoeffs (bibe/afp25_bibe/afp25_bibe_utils.go:14-43) for k batches at once.
+func FrPolyFromRoots(roots []fr.Element, B int) ([]fr.Element, error) {
+	defer pin()()
+	if B < 1 || len(roots) == 0 || len(roots)%B != 0 {
+		return nil, errSizes
+	}
+	k := len(roots) / B
+	kr, err := frPlain(roots)
+	if err != nil {
+		return nil, err
+	}
+	kc := make([][32]byte, k*(B+1))
+	rc := C.gpbc_fr_poly_from_roots(unsafe.Pointer(unsafe.SliceData(kr)), C.size_t(B), C.size_t(k), unsafe.Pointer(unsafe.SliceData(kc)))
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	out := make([]fr.Element, len(kc))
+	return out, frElements(kc, out)
+}
+
+// FrPolyQuotients: row j*B + i of the result holds the B coefficients of coeffs[j](X) / (X - points[j*B + i]) and stride - B zeros;
+// ok[j*B + i] is false (and the row zero) where the point is not a root — the "identity not found" of the reference's Decrypt
+// (bibe/afp25_bibe/afp25_bibe.go:369-418).
+func FrPolyQuotients(coeffs, points []fr.Element, B, stride int) ([]fr.Element, []bool, error) {
+	defer pin()()
+	if B < 1 || stride < B || len(points) == 0 || len(points)%B != 0 || len(coeffs) != len(points)/B*(B+1) {
+		return nil, nil, errSizes
+	}
+	k := len(points) / B
+	kc, err := frPlain(coeffs)
+	if err != nil {
+		return nil, nil, err
+	}
+	kp, err := frPlain(points)
+	if err != nil {
+		return nil, nil, err
+	}
+	kq := make([][32]byte, len(points)*stride)
+	okb := make([]byte, len(points))
+	rc := C.gpbc_fr_poly_quotients(unsafe.Pointer(unsafe.SliceData(kc)), unsafe.Pointer(unsafe.SliceData(kp)), C.size_t(B), C.size_t(k), C.size_t(stride),
+		unsafe.Pointer(unsafe.SliceData(kq)), (*C.uint8_t)(unsafe.SliceData(okb)))
+	if err := status(rc); err != nil {
+		return nil, nil, err
+	}
+	out := make([]fr.Element, len(kq))
+	ok := make([]bool, len(okb))
+	for i, b := range okb {
+		ok[i] = b != 0
+	}
+	return out, ok, frElements(kq, out)
+}
+
 // g1GroupOp: Add (sub == false) or Sub over the batch (cgo cannot take a C function as a value, hence the flag)
 func g1GroupOp(sub bool, out, a, b []bn254.G1Affine) ([]bn254.G1Affine, error) {
 	defer pin()()

@@ -324,6 +324,50 @@ int gpbc_hash_to_g1_dev(const void *d_msgs, const uint64_t *d_msg_off, size_t ms
 int gpbc_hash_to_g2_dev(const void *d_msgs, const uint64_t *d_msg_off, size_t msgs_bytes, size_t n, const void *dst, size_t dst_len, void *d_out, void *stream);
 int gpbc_hash_to_field_dev(const void *d_msgs, const uint64_t *d_msg_off, size_t msgs_bytes, size_t n, const void *dst, size_t dst_len, int count, void *d_out, void *stream);
 
+/* ---- scalar field ------------------------------------------------------------------------------
+ * fr.Element arithmetic (integers modulo the group order r) where the reference does it once per item of a batch, so that the
+ * scalars the entries above consume never have to be made on the host: the quotient polynomials of the batched-IBE opening proofs
+ * (bibe/afp25_bibe/afp25_bibe_utils.go:14-55 under afp25_bibe.go:369-418; bibe/gwww25_bibe/gwww25_bibe_utils.go:9 under
+ * gwww25_bibe.go:170,224), the exponent 1 / (H(m) + x) of a short signature (signature/zss04_signature/zss04_signature.go:249-252,
+ * signature/bb04_signature/bb04_signature.go:233) and of key extraction (ibe/gentry06_ibe/gentry06_ibe.go:151,
+ * ibe/bb04_sibe/bb04_sibe.go:143).
+ * An element is the ABI's one scalar format (above): inputs are any value < 2^256 and act as their residue, outputs are canonical
+ * in [0, r) — directly usable as the `scalars` of gpbc_*_scalar_mul_batch_dev, gpbc_fixed_base_msm_dev and gpbc_gt_exp_batch_dev.
+ * Go slices of fr.Element (4 x uint64, Montgomery R = 2^256) go through the from_mont / to_mont pair.
+ *   out[i] = a[i] + b[j],  a[i] - b[j],  a[i] b[j]     j = i when nb == n, j = 0 when nb == 1;   -a[i];   1 / a[i]
+ * inverse is gnark's Inverse: an element that is 0 modulo r gives 0 (elements share one field inversion in groups of 8 by
+ * Montgomery's trick; such an element does not spoil its neighbours).  out may be a, or b when nb == n.  n == 0 is a no-op.
+ * Not combined across calling threads: one Fr operation costs nanoseconds on a host core and stays there. */
+int gpbc_fr_add_batch(const void *a, const void *b, size_t nb, size_t n, void *out);
+int gpbc_fr_sub_batch(const void *a, const void *b, size_t nb, size_t n, void *out);
+int gpbc_fr_mul_batch(const void *a, const void *b, size_t nb, size_t n, void *out);
+int gpbc_fr_neg_batch(const void *a, size_t n, void *out);
+int gpbc_fr_inverse_batch(const void *a, size_t n, void *out);
+int gpbc_fr_from_mont_batch(const void *a, size_t n, void *out);      /* fr.Element words (x 2^256 mod r) -> scalar format */
+int gpbc_fr_to_mont_batch(const void *a, size_t n, void *out);        /* scalar format -> canonical fr.Element words */
+int gpbc_fr_add_batch_dev(const void *d_a, const void *d_b, size_t nb, size_t n, void *d_out, void *stream);
+int gpbc_fr_sub_batch_dev(const void *d_a, const void *d_b, size_t nb, size_t n, void *d_out, void *stream);
+int gpbc_fr_mul_batch_dev(const void *d_a, const void *d_b, size_t nb, size_t n, void *d_out, void *stream);
+int gpbc_fr_neg_batch_dev(const void *d_a, size_t n, void *d_out, void *stream);
+int gpbc_fr_inverse_batch_dev(const void *d_a, size_t n, void *d_out, void *stream);
+int gpbc_fr_from_mont_batch_dev(const void *d_a, size_t n, void *d_out, void *stream);
+int gpbc_fr_to_mont_batch_dev(const void *d_a, size_t n, void *d_out, void *stream);
+/* k independent polynomials per call (one per AFP25 batch), coefficients constant term first, 1 <= B <= 1024.
+ * from_roots (computePolynomialCoeffs): coeffs_out[j][0..B] = coefficients of prod_{i<B} (X - roots[j][i]); roots: k x B scalars,
+ *   coeffs_out: k x (B + 1).
+ * quotients: row j*B + i of q_out, `stride` >= B scalars: the B coefficients of coeffs[j](X) / (X - points[j][i]), then
+ *   stride - B zeros, so that a row is one row of a gpbc_fixed_base_msm_dev call over a table of `stride` bases (g1, [tau]g1 ...
+ *   [tau^B]g1: stride = B + 1).  ok_out[j*B + i] = 1 iff the division is exact (the point is a root of coeffs[j]); where it is not,
+ *   ok = 0 and the row is all zero, as the unmarshal entries do: a wrong opening can never be committed to by accident.  A repeated
+ *   root still divides exactly; the reference's "exactly one identity removed" rule (afp25_bibe.go:371-381) is the caller's.
+ *   coeffs: k x (B + 1), points: k x B, q_out: k x B x stride scalars, ok_out: k x B bytes.  Not in place.
+ * B outside 1 .. 1024, stride < B or stride > 2^24 (sizes and row offsets stay far from overflow) is GPBC_ERR_INVALID_ARG; k == 0 is a
+ * no-op. */
+int gpbc_fr_poly_from_roots(const void *roots, size_t B, size_t k, void *coeffs_out);
+int gpbc_fr_poly_quotients(const void *coeffs, const void *points, size_t B, size_t k, size_t stride, void *q_out, uint8_t *ok_out);
+int gpbc_fr_poly_from_roots_dev(const void *d_roots, size_t B, size_t k, void *d_coeffs_out, void *stream);
+int gpbc_fr_poly_quotients_dev(const void *d_coeffs, const void *d_points, size_t B, size_t k, size_t stride, void *d_q_out, uint8_t *d_ok_out, void *stream);
+
 /* ---- per-kernel timing (measurement, bench.py) ---------------------------------------------------
  * Between begin and end every kernel launch of the pairing / scalar-multiplication entries made on `stream` is bracketed by
  * HIP events on that stream; end synchronises and returns, per kernel name (32-byte zero-padded rows), the summed duration

@@ -229,6 +229,45 @@ inline std::vector<G2Affine> G2DoubleBatch(const std::vector<G2Affine> &a) {
     check(gpbc_g2_double_batch(a.data(), a.size(), out.data()));
     return out;
 }
+// fr.Element arithmetic on scalars, n at a time (gpbc_bn254.h "scalar field"): out[i] = a[i] + b[i] / - / * (b of one scalar: the same b
+// for every a), -a[i], 1 / a[i] (0 for 0, gnark's Inverse).  Inputs act as their residue modulo r, outputs are canonical.
+namespace detail {
+template <class Fn> inline std::vector<Scalar> fr_binary(const std::vector<Scalar> &a, const std::vector<Scalar> &b, Fn fn) {
+    if (b.size() != 1 && b.size() != a.size()) throw std::invalid_argument("need one b or one b per a");
+    std::vector<Scalar> out(a.size());
+    check(fn(a.data(), b.data(), b.size(), a.size(), out.data()));
+    return out;
+}
+template <class Fn> inline std::vector<Scalar> fr_unary(const std::vector<Scalar> &a, Fn fn) {
+    std::vector<Scalar> out(a.size());
+    check(fn(a.data(), a.size(), out.data()));
+    return out;
+}
+}  // namespace detail
+inline std::vector<Scalar> FrAddBatch(const std::vector<Scalar> &a, const std::vector<Scalar> &b) { return detail::fr_binary(a, b, gpbc_fr_add_batch); }
+inline std::vector<Scalar> FrSubBatch(const std::vector<Scalar> &a, const std::vector<Scalar> &b) { return detail::fr_binary(a, b, gpbc_fr_sub_batch); }
+inline std::vector<Scalar> FrMulBatch(const std::vector<Scalar> &a, const std::vector<Scalar> &b) { return detail::fr_binary(a, b, gpbc_fr_mul_batch); }
+inline std::vector<Scalar> FrNegBatch(const std::vector<Scalar> &a) { return detail::fr_unary(a, gpbc_fr_neg_batch); }
+inline std::vector<Scalar> FrInverseBatch(const std::vector<Scalar> &a) { return detail::fr_unary(a, gpbc_fr_inverse_batch); }
+// fr.Element's in-memory words (Montgomery, R = 2^256) <-> Scalar
+inline std::vector<Scalar> FrFromMontBatch(const std::vector<Scalar> &a) { return detail::fr_unary(a, gpbc_fr_from_mont_batch); }
+inline std::vector<Scalar> FrToMontBatch(const std::vector<Scalar> &a) { return detail::fr_unary(a, gpbc_fr_to_mont_batch); }
+// k polynomials prod_i (X - roots[j*B + i]) of B roots each: k x (B + 1) coefficients, constant term first (computePolynomialCoeffs)
+inline std::vector<Scalar> FrPolyFromRoots(const std::vector<Scalar> &roots, size_t B) {
+    if (B < 1 || roots.size() % B) throw std::invalid_argument("need B roots per polynomial");
+    std::vector<Scalar> out(roots.size() / B * (B + 1));
+    check(gpbc_fr_poly_from_roots(roots.data(), B, roots.size() / B, out.data()));
+    return out;
+}
+// row j*B + i: the B coefficients of coeffs[j](X) / (X - points[j*B + i]) and stride - B zeros; ok[j*B + i] = 0 (and a zero row) where the
+// division leaves a remainder.  A row is one row of G1FixedBase::Msm over stride bases.
+inline std::vector<Scalar> FrPolyQuotients(const std::vector<Scalar> &coeffs, const std::vector<Scalar> &points, size_t B, size_t stride, std::vector<uint8_t> &ok) {
+    if (B < 1 || stride < B || points.size() % B || coeffs.size() != points.size() / B * (B + 1)) throw std::invalid_argument("invalid inputs sizes");
+    std::vector<Scalar> out(points.size() * stride);
+    ok.assign(points.size(), 0);
+    check(gpbc_fr_poly_quotients(coeffs.data(), points.data(), B, points.size() / B, stride, out.data(), ok.data()));
+    return out;
+}
 // k products against ONE list of G2 points (a decryption key against k ciphertexts): out[j] = Pair(P[j*m .. (j+1)*m), Q);
 // the Miller lines of Q are computed once (gnark: PrecomputeLines / MillerLoopFixedQ)
 inline std::vector<GT> PairFixedQ(const std::vector<G1Affine> &P, const std::vector<G2Affine> &Q) {

@@ -17,6 +17,7 @@
 #include "../gopairingbasedcryptography_amd/csrc/h2c29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/msm29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/group29.hip.hpp"
+#include "../gopairingbasedcryptography_amd/csrc/fr29.hip.hpp"
 #include <condition_variable>
 #include <mutex>
 #include <thread>
@@ -138,6 +139,11 @@ template <class F, int K> static void group_host(int op, const uint8_t *A, const
         else if (op == GROUP_SUB) group_op_lane<F, K, GROUP_SUB>(A, B, step, out, n, t, T);
         else group_op_lane<F, K, GROUP_DBL>(A, A, 0, out, n, t, T);
     }
+}
+// the inversion kernel's lanes (hc_fr_op), k elements each
+template <int K> static void fr_inverse_host(const uint8_t *A, size_t n, uint8_t *out) {
+    const size_t T = (n + K - 1) / K;
+    for (size_t t = 0; t < T; t++) fr_inverse_lane<K>(A, out, n, t, T);
 }
 extern "C" {
 
@@ -477,6 +483,73 @@ void hc_msm(int g2, const uint8_t *B, const uint8_t *K, size_t n, int c, uint8_t
     else msm_host<F2>(B, K, n, c, out, 128,
                       [](const uint8_t *p) { return AffP<F2>{f2_load(p), f2_load(p + 64), bytes_all_zero(p, 32)}; },
                       [](uint8_t *p, const AffP<F2> &r) { f2_store(p, r.x); f2_store(p + 64, r.y); });
+}
+// The scalar field (csrc/fr29.hip.hpp) exactly as the kernels of csrc/gpbc_fr.hip run it.  op: FrOp, or FR_OPS = the inversion, whose
+// lanes own k elements each (k = 0: the kernel's FR_INV_K) at t, t + T, ... with T = ceil(n / k)
+int hc_fr_op(int op, const uint8_t *A, const uint8_t *B, size_t nb, size_t n, uint8_t *out, int k) {
+    if (op < 0 || op > FR_OPS || (op <= FR_MUL && nb != 1 && nb != n)) return -1;
+    const size_t step = nb == n ? 32 : 0;
+    if (op == FR_OPS) {
+        switch (k ? k : FR_INV_K) {
+            case 1: fr_inverse_host<1>(A, n, out); break;
+            case 4: fr_inverse_host<4>(A, n, out); break;
+            case 8: fr_inverse_host<8>(A, n, out); break;
+            default: return -1;
+        }
+    } else {
+        for (size_t i = 0; i < n; i++) {
+            const uint8_t *a = A + 32 * i, *b = op <= FR_MUL ? B + i * step : a;
+            switch (op) {
+                case FR_ADD: fr_op_lane<FR_ADD>(a, b, out + 32 * i); break;
+                case FR_SUB: fr_op_lane<FR_SUB>(a, b, out + 32 * i); break;
+                case FR_MUL: fr_op_lane<FR_MUL>(a, b, out + 32 * i); break;
+                case FR_NEG: fr_op_lane<FR_NEG>(a, b, out + 32 * i); break;
+                case FR_FROM_MONT: fr_op_lane<FR_FROM_MONT>(a, b, out + 32 * i); break;
+                default: fr_op_lane<FR_TO_MONT>(a, b, out + 32 * i); break;
+            }
+        }
+    }
+    stats_flush();
+    return 0;
+}
+int hc_fr_inv_k(void) { return FR_INV_K; }
+// k_fr_poly_from_roots: per root, every coefficient up to the new degree from itself and its lower neighbour (all read, then all written)
+int hc_fr_poly_from_roots(const uint8_t *roots, size_t B, size_t k, uint8_t *coeffs_out) {
+    if (B < 1 || B > (size_t)FR_POLY_MAX_B) return -1;
+    std::vector<Fr> cs(B + 1), nw(B + 1);
+    for (size_t j = 0; j < k; j++) {
+        for (size_t i = 0; i <= B; i++) cs[i] = i ? fr_zero() : fr_plain_one();
+        for (size_t s = 0; s < B; s++) {
+            const Fr nr = fr_poly_neg_root(roots + (j * B + s) * 32);
+            for (size_t i = 0; i <= s + 1; i++) nw[i] = fr_poly_root_step(i ? cs[i - 1] : fr_zero(), cs[i], nr);
+            for (size_t i = 0; i <= s + 1; i++) cs[i] = nw[i];
+        }
+        for (size_t i = 0; i <= B; i++) fr_poly_store(coeffs_out + (j * (B + 1) + i) * 32, cs[i]);
+    }
+    stats_flush();
+    return 0;
+}
+// k_fr_poly_quotients: one walk from the top coefficient down per (polynomial, point); rows of `stride` scalars
+int hc_fr_poly_quotients(const uint8_t *coeffs, const uint8_t *points, size_t B, size_t k, size_t stride, uint8_t *q_out, uint8_t *ok_out) {
+    if (B < 1 || B > (size_t)FR_POLY_MAX_B || stride < B) return -1;
+    std::vector<Fr> cs(B + 1);
+    for (size_t j = 0; j < k; j++) {
+        for (size_t i = 0; i <= B; i++) cs[i] = fr_poly_coeff_in(coeffs + (j * (B + 1) + i) * 32);
+        for (size_t pi = 0; pi < B; pi++) {
+            const Fr point = fr_poly_point(points + (j * B + pi) * 32);
+            uint8_t *row = q_out + (j * B + pi) * stride * 32;
+            Fr carry = fr_zero();
+            for (size_t c = B; c-- > 0;) {
+                carry = fr_poly_horner_step(carry, cs[c + 1], point);
+                fr_store_canonical(row + 32 * c, carry);
+            }
+            const bool ok = fr_limbs_zero(fr_poly_horner_step(carry, cs[0], point));
+            ok_out[j * B + pi] = ok ? 1 : 0;
+            memset(row + (ok ? B * 32 : 0), 0, (stride - (ok ? B : 0)) * 32);
+        }
+    }
+    stats_flush();
+    return 0;
 }
 // worst-case figures since process start: [max |int64 column|, max limb bound, max value bound (units of p),
 // #products (fe_mul + fe_mul2), #norms, #fe_mul2, #reduces]  (out must hold 7 doubles)

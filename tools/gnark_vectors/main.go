@@ -114,6 +114,29 @@ func main() {
 	one.SetOne()
 	out["fr_one_raw"] = hex.EncodeToString(unsafe.Slice((*byte)(unsafe.Pointer(&one)), 32))
 
+	// fr.Element arithmetic in gnark's own words (Montgomery, R = 2^256) on neighbouring scalars of the list above: what the
+	// gpbc_fr_* entries compute between gpbc_fr_from_mont_batch and gpbc_fr_to_mont_batch (tests/test_fr.py reads "fr")
+	rawFr := func(x *fr.Element) string { return hex.EncodeToString(unsafe.Slice((*byte)(unsafe.Pointer(x)), 32)) }
+	var frs []map[string]string
+	for i := 0; i+1 < len(ks); i++ {
+		ka, _ := new(big.Int).SetString(ks[i], 10)
+		kb, _ := new(big.Int).SetString(ks[i+1], 10)
+		var a, b, sum, diff, mul, neg, inv fr.Element
+		a.SetBigInt(ka)
+		b.SetBigInt(kb)
+		sum.Add(&a, &b)
+		diff.Sub(&a, &b)
+		mul.Mul(&a, &b)
+		neg.Neg(&a)
+		inv.Inverse(&a)
+		frs = append(frs, map[string]string{"a": ks[i], "b": ks[i+1], "a_raw": rawFr(&a), "b_raw": rawFr(&b), "add_raw": rawFr(&sum),
+			"sub_raw": rawFr(&diff), "mul_raw": rawFr(&mul), "neg_raw": rawFr(&neg), "inverse_raw": rawFr(&inv)})
+	}
+	out["fr"] = frs
+	var zero, zeroInv fr.Element
+	zeroInv.Inverse(&zero)
+	out["fr_inverse_of_zero_raw"] = rawFr(&zeroInv)
+
 	enc := json.NewEncoder(os.Stdout)
 	enc.SetIndent("", " ")
 	if err := enc.Encode(out); err != nil {
