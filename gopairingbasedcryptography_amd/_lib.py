@@ -19,7 +19,7 @@ EXPORTS = [
     "gpbc_g1_scalar_mul_batch", "gpbc_g1_scalar_mul_batch_dev", "gpbc_g2_scalar_mul_batch",
     "gpbc_g2_scalar_mul_batch_dev", "gpbc_g1_sum", "gpbc_g2_sum", "gpbc_sum_workspace_bytes",
     "gpbc_g1_sum_dev", "gpbc_g2_sum_dev",
-    "gpbc_gt_exp_batch", "gpbc_gt_exp_batch_dev", "gpbc_gt_mul_batch", "gpbc_gt_div_batch",
+    "gpbc_gt_exp_batch", "gpbc_gt_exp_batch_dev", "gpbc_gt_multi_exp", "gpbc_gt_multi_exp_workspace_bytes", "gpbc_gt_multi_exp_dev", "gpbc_gt_mul_batch", "gpbc_gt_div_batch",
     "gpbc_gt_inverse_batch", "gpbc_gt_mul_batch_dev", "gpbc_gt_div_batch_dev", "gpbc_gt_inverse_batch_dev",
     "gpbc_fp_mul_batch", "gpbc_profile_begin", "gpbc_profile_end",
     "gpbc_g1_marshal_batch", "gpbc_g2_marshal_batch", "gpbc_gt_marshal_batch",
@@ -63,6 +63,8 @@ def load():
         lib.gpbc_last_error.restype = ctypes.c_char_p
         lib.gpbc_multi_pair_workspace_bytes.restype = ctypes.c_size_t
         lib.gpbc_multi_pair_workspace_bytes.argtypes = [ctypes.c_size_t, ctypes.c_size_t]
+        lib.gpbc_gt_multi_exp_workspace_bytes.restype = ctypes.c_size_t
+        lib.gpbc_gt_multi_exp_workspace_bytes.argtypes = [ctypes.c_size_t, ctypes.c_size_t]
         lib.gpbc_sum_workspace_bytes.restype = ctypes.c_size_t
         lib.gpbc_sum_workspace_bytes.argtypes = [ctypes.c_size_t, ctypes.c_int]
         lib.gpbc_fixed_base_table_bytes.restype = ctypes.c_size_t

@@ -835,6 +835,100 @@ def gt_exp(x, k, out=None):
     return out
 
 
+def gt_multi_exp(x, k, seg_off, out=None, workspace=None):
+    """out[s] = prod_{i in [seg_off[s], seg_off[s+1])} x[i]^k[i]: the `res.Mul(res, tmp.Exp(c, w))` loops of the reference as one call,
+    every factor with GT.Exp's semantics (256-bit exponents as they are, any Fp12 base), the squarings shared by four factors.
+    k: one exponent per element, or ONE list of m exponents when every segment has exactly m elements (the weights of a policy
+    against many ciphertexts), or None for the plain product; Python ints must be in [0, 2^256).  numpy arrays in, numpy array out;
+    CUDA tensors in (seg_off a host sequence, or an int64 / uint64 CUDA tensor that is then validated on the device), CUDA tensor
+    out, enqueued on the current torch stream.  Arguments are checked before the engine is touched."""
+    dev = _is_torch(x)
+    if isinstance(k, int):
+        k = [k]
+    if isinstance(k, (list, tuple)):
+        if any(not 0 <= int(e) < (1 << 256) for e in k):
+            raise ValueError("exponents must be in [0, 2^256): invert the base for a negative one")
+        k = np.frombuffer(b"".join(int(e).to_bytes(32, "little") for e in k), dtype=np.uint8)
+    if not dev and (_is_torch(k) or _is_torch(seg_off) or _is_torch(out)):
+        raise ValueError("x is a host buffer: k, seg_off and out must be host buffers too")
+    dev_table = dev and _is_torch(seg_off)
+    if dev:
+        import torch
+        if x.dtype != torch.uint8 or x.numel() % GT_BYTES:
+            raise ValueError("x must hold whole GT elements as uint8")
+        n = x.numel() // GT_BYTES
+        if dev_table:
+            if seg_off.dtype not in (torch.int64, torch.uint64) or not seg_off.is_cuda or not seg_off.is_contiguous() or seg_off.device != x.device:
+                raise ValueError("a device segment table must be a contiguous int64 / uint64 CUDA tensor on the elements' device")
+            n_seg = seg_off.numel() - 1
+    else:
+        x = _np(x, GT_BYTES)
+        n = x.size // GT_BYTES
+    if not dev_table:
+        seg = np.ascontiguousarray(seg_off, dtype=np.uint64).reshape(-1)
+        n_seg = seg.size - 1
+        if n_seg < 1 or int(seg[0]) != 0 or int(seg[-1]) != n or (np.diff(seg.astype(np.int64)) < 0).any():
+            raise ValueError("seg_off must have n_seg + 1 >= 2 non-decreasing entries from 0 to the number of elements")
+    if n_seg < 1:
+        raise ValueError("invalid inputs sizes")
+    nk = 0
+    if k is not None:
+        if not _is_torch(k):
+            k = _np(k, SCALAR_BYTES)
+        elif k.dtype.__str__() != "torch.uint8" or k.numel() % SCALAR_BYTES:
+            raise ValueError("k must hold whole 32-byte exponents as uint8")
+        nk = (k.numel() if _is_torch(k) else k.size) // SCALAR_BYTES
+        if nk != n:
+            if nk > n or nk * n_seg != n:
+                raise ValueError("k must hold one exponent per element, or one list for segments of equal length (nk = %d, n = %d, n_seg = %d)" % (nk, n, n_seg))
+            if not dev_table and (np.diff(seg.astype(np.int64)) != nk).any():
+                raise ValueError("a shared exponent list of %d needs segments of exactly %d elements" % (nk, nk))
+    if dev:
+        if out is not None and (not _is_torch(out) or out.numel() != n_seg * GT_BYTES):
+            raise ValueError("out must be a CUDA tensor of %d bytes" % (n_seg * GT_BYTES))
+        _tchk_static(x, (x, n * GT_BYTES, "x"))
+    elif out is not None and not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.size == n_seg * GT_BYTES and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"]):
+        raise ValueError("out must be a writable contiguous uint8 array of %d bytes" % (n_seg * GT_BYTES))
+    _ensure_init()
+    lib = _lib.load()
+    if not dev:
+        out = np.empty((n_seg, GT_BYTES), dtype=np.uint8) if out is None else out
+        _lib.check(lib.gpbc_gt_multi_exp(_ptr(x), _ptr(k) if k is not None else None, _sz(nk), _ptr(seg), _sz(n_seg), _ptr(out)))
+        return out
+    _tchk(x, (x, n * GT_BYTES, "x"))                             # binds the device before anything is put on it
+    if k is not None and not _is_torch(k):
+        k = torch.from_numpy(k.copy()).to(x.device)
+    if dev_table:
+        if lib.gpbc_check_segments_dev(ctypes.c_void_p(seg_off.data_ptr()), _sz(n), _sz(n_seg), _torch_stream()) < 0:
+            raise ValueError("invalid inputs sizes: " + lib.gpbc_last_error().decode())
+        if nk != n and k is not None and bool((seg_off.view(torch.int64).diff() != nk).any()):
+            raise ValueError("a shared exponent list of %d needs segments of exactly %d elements" % (nk, nk))
+    else:
+        seg_off = torch.from_numpy(seg.astype(np.int64)).to(x.device)
+    out = _tnew(x, n_seg, GT_BYTES) if out is None else out
+    wsb = lib.gpbc_gt_multi_exp_workspace_bytes(n, n_seg)
+    if workspace is None:
+        workspace = torch.empty(max(wsb, 1), dtype=torch.uint8, device=x.device)
+    if workspace.numel() < wsb:
+        raise ValueError("workspace holds %d bytes, needs %d" % (workspace.numel(), wsb))
+    specs = [(x, n * GT_BYTES, "x"), (out, n_seg * GT_BYTES, "out"), (workspace, workspace.numel(), "workspace")]
+    if k is not None:
+        specs.append((k, nk * SCALAR_BYTES, "k"))
+    _tchk(x, *specs)
+    _lib.check(lib.gpbc_gt_multi_exp_dev(_tptr(x), _tptr(k) if k is not None else None, _sz(nk), ctypes.c_void_p(seg_off.data_ptr()), _sz(n), _sz(n_seg),
+                                         _tptr(out), _tptr(workspace), _sz(workspace.numel()), _torch_stream()))
+    return out
+
+
+def gt_prod(x, seg_off=None):
+    """Products in GT without exponents: out[s] = prod x[seg_off[s]:seg_off[s+1]] (the GT sibling of g1_sum — the chain of GT.Mul in
+    `AggregatePublicKeys`); without seg_off the product of all of x as ONE element."""
+    if seg_off is None:
+        n = (x.numel() if _is_torch(x) else _np(x, GT_BYTES).size) // GT_BYTES
+        return gt_multi_exp(x, None, [0, n])[0]
+    return gt_multi_exp(x, None, seg_off)
+
+
 def _gt_binary(host_fn, dev_fn, a, b):
     _ensure_init()
     if _is_torch(a):

@@ -1,0 +1,88 @@
+// Segmented multi-exponentiation in GT on a lane pair: out = prod_i x_i^{k_i} over a run of factors, with GT.Exp's semantics per
+// factor (f12p_exp256: 256-bit plain exponents, any Fp12 base, fixed 4-bit windows left to right) and ONE squaring chain for
+// GT_MEXP_GROUP factors (Straus interleaving): the factors are taken four at a time, each with its 16-row window table, and a
+// window costs 4 squarings + 4 table products for the four of them — 63 + 77.25 x 2.34 = 244 squaring-equivalents per factor
+// where f12p_exp256 spends 252 + 77 x 2.34 = 432.  The tables of ONE group are the whole workspace of a lane (GT_MEXP_TAB_DWORDS
+// int32, 16 KB), whatever the length of the run: the next group overwrites them.
+// The same file cuts the work (gt_mexp_pieces / gt_mexp_piece_range): the kernels (csrc/gpbc_gtmexp.hip) and the host interval
+// harness (tools/bounds_check.cpp, hc_gt_multi_exp_pair) run one plan.
+#ifndef GPBC_GTMEXP29_HIP_HPP
+#define GPBC_GTMEXP29_HIP_HPP
+#include "pairing29_pair.hip.hpp"
+
+namespace gpbc {
+
+constexpr int GT_MEXP_GROUP = 4;                                             // factors that share a squaring chain
+constexpr int GT_MEXP_TAB_DWORDS = GT_MEXP_GROUP * GT_EXP_TAB_DWORDS;        // per lane: 4 tables x 16 rows x 256 bytes
+constexpr size_t GT_MEXP_FILL = 65536;                                       // lane pairs that fill the chip: 256 CUs x 4 SIMDs x 2 waves x 32 pairs
+constexpr size_t GT_MEXP_PROD_MIN = 8;                                       // a product-only piece has at least this many factors on average
+
+// Pieces per segment, from the sizes alone (the segment table may live in device memory): enough pieces to fill the chip, but none
+// shorter on average than one group of factors (with exponents) or GT_MEXP_PROD_MIN factors (product only).  1 = no cut: a lane
+// pair per segment writes the result itself.  n_seg x J <= GT_MEXP_FILL + n_seg whatever the segment lengths are.
+GPBC_INLINE size_t gt_mexp_pieces(size_t n, size_t n_seg, bool has_k) {
+    if (!n_seg) return 1;
+    const size_t by_len = (n / n_seg) / (has_k ? (size_t)GT_MEXP_GROUP : GT_MEXP_PROD_MIN);
+    const size_t by_fill = (GT_MEXP_FILL + n_seg - 1) / n_seg;
+    const size_t j = by_len < by_fill ? by_len : by_fill;
+    return j ? j : 1;
+}
+// Factors [a, b) of piece j of J of the segment [lo, hi): the J pieces tile the segment, their lengths differ by at most one.
+GPBC_INLINE void gt_mexp_piece_range(size_t lo, size_t hi, size_t j, size_t J, size_t &a, size_t &b) {
+    const size_t len = hi - lo;
+    a = lo + (size_t)((uint64_t)len * j / J);                               // len < 2^47, J <= 2^16 + 1: no overflow
+    b = lo + (size_t)((uint64_t)len * (j + 1) / J);
+}
+
+// prod_{i < cnt} base(i)^{k_i}, digit(i, w) = window w (0 = lowest) of k_i.  Every lane of the wavefront must call it (x.all); the
+// trip counts are the wavefront's longest, pairs with fewer factors ride along on one = row 0 of a table that holds nothing else.
+template <class X, class Base, class Digit>
+GPBC_INLINE F6 f12p_multi_exp(const X &x, size_t cnt, Base base, Digit digit, int32_t *tab) {
+    F6 acc = f12p_one(x);
+    for (size_t g0 = 0; !x.all(g0 >= cnt); g0 += GT_MEXP_GROUP) {
+        const int nf = g0 >= cnt ? 0 : cnt - g0 < (size_t)GT_MEXP_GROUP ? (int)(cnt - g0) : GT_MEXP_GROUP;
+        int nfw = 1;
+        while (nfw < GT_MEXP_GROUP && !x.all(nf <= nfw)) nfw++;
+        bool cyc = true;
+#pragma unroll 1
+        for (int j = 0; j < nfw; j++) {
+            int32_t *t = tab + j * GT_EXP_TAB_DWORDS;
+            F6 cur = f12p_one(x);
+            f6_row_store(t, cur);
+            if (j < nf) {                                                   // (pairs diverge here at most; nothing below asks the wavefront)
+                const F6 b = base(g0 + j);
+                cyc = cyc && f12p_is_cyclotomic(x, b);
+                cur = b;
+                f6_row_store(t + GT_EXP_ROW_DWORDS, cur);
+#pragma unroll 1
+                for (int i = 2; i < 16; i++) { cur = f12p_mul(x, cur, b); f6_row_store(t + i * GT_EXP_ROW_DWORDS, cur); }
+            }
+        }
+        // f12p_exp256's rule, per group: Granger-Scott squarings when every base of the wavefront's groups is cyclotomic
+        cyc = x.all(cyc);
+        auto row = [&](int j, int w) { return f6_row_load(tab + j * GT_EXP_TAB_DWORDS + (j < nf ? digit(g0 + j, w) : 0) * GT_EXP_ROW_DWORDS); };
+        F6 r = row(0, 63);
+#pragma unroll 1
+        for (int j = 1; j < nfw; j++) r = f12p_mul(x, r, row(j, 63));
+#pragma unroll 1
+        for (int w = 62; w >= 0; w--) {
+            if (cyc) { bool flipped = false; r = f12p_cyclo_sqr_run(x, r, 4, flipped); }
+            else for (int s = 0; s < 4; s++) r = f6_reduce(f12p_sqr(x, r));
+#pragma unroll 1
+            for (int j = 0; j < nfw; j++) r = f12p_mul(x, r, row(j, w));    // several products in a row, no squaring between
+        }
+        if (g0 == 0) acc = r;
+        else f12p_mul_to(x, acc, acc, r);
+    }
+    return acc;
+}
+// prod_{i < cnt} base(i): no exponents, no squarings, no tables
+template <class X, class Base> GPBC_INLINE F6 f12p_product(const X &x, size_t cnt, Base base) {
+    F6 acc = f12p_one(x);
+    for (size_t i = 0; !x.all(i >= cnt); i++)
+        if (i < cnt) acc = f12p_mul(x, acc, base(i));
+    return acc;
+}
+
+}  // namespace gpbc
+#endif

@@ -1,0 +1,111 @@
+"""Host-side planner for batched LW11 decentralised ABE decryption (Lewko-Waters 2011; dabe/lw11_dabe.go:176-203): one user key,
+one LSSS policy, a batch of ciphertexts under that policy.
+
+What is computed.  With the rows x whose attribute rho(x) the user holds and weights w_x such that sum_x w_x M_x = (1, 0, ..., 0),
+
+    M = c0 / prod_x ( c1x * e(H(GID), c3x) / e(K_rho(x),GID, c2x) ) ^ w_x
+
+because c1x e(H, c3x) / e(K, c2x) = e(g1, g2)^lambda_x e(H, g2)^omega_x, and the shares recombine to sum w_x lambda_x = s,
+sum w_x omega_x = 0.  Two of the three factors fold into the key, once per (key, policy): e(H, c3x)^w = e([w]H, c3x) and
+e(K, c2x)^-w = e([-w]K, c2x) exactly as Fp12 elements, so per ciphertext
+
+    E = Pair([A_x..., B_x...], [c3x..., c2x...]),  A_x = [w_x] H(GID),  B_x = [-w_x] K_rho(x),GID     one multi-pairing segment of 2k pairs
+    F = prod_x c1x ^ w_x                                                                             one GT multi-exponentiation
+    M = c0 / (E * F)
+
+c1x is ciphertext data in GT: it cannot be folded into a key or in front of a pairing, which is why this scheme needs a product of
+powers of varying GT bases per ciphertext (engine.gt_multi_exp with ONE exponent list for all ciphertexts).
+
+The reference's loop is not that formula: it raises the RUNNING product to the weight at every row, ((1 * t_0)^w * t_1)^w' ...,
+and it indexes the compacted weight slice by the matrix row number (lw11_dabe.go:191-195; SURVEY.md's notes on Waters11 / DABE
+record both).  The two agree when every weight is 1 — the solution that Lewko-Waters matrices of AND / OR formulas have — and this
+planner follows the scheme, not the loop, just as bsw07.py drops the reference's debug pairing.
+
+Host orchestration only, engine-agnostic (every function takes the engine: `bn254`, or a stand-in with the same function names):
+the elimination is per policy, microseconds in Python integers, and stays on the host."""
+import numpy as np
+
+R_ORDER = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+
+
+def reconstruction_weights(matrix, rho, attributes):
+    """(rows, weights): the rows x with rho[x] in `attributes` that carry a non-zero weight, and w_x in [1, r) with
+    sum_x w_x matrix[x] = (1, 0, ..., 0) modulo r; None when the attribute set does not satisfy the policy
+    (FindLinearCombinationWeight, access/lsss/lewko_waters_lsss_matrix.go:167-221).  Gauss-Jordan elimination on the transposed
+    sub-matrix; unknowns without a pivot (redundant rows) get weight 0 and are dropped."""
+    attrs = set(attributes)
+    sat = [x for x in range(len(rho)) if rho[x] in attrs]
+    if not sat:
+        return None
+    cols = len(matrix[0])
+    m = len(sat)
+    aug = [[int(matrix[x][j]) % R_ORDER for x in sat] + [1 if j == 0 else 0] for j in range(cols)]     # cols equations, m unknowns
+    pivots, row = [], 0
+    for col in range(m):
+        p = next((i for i in range(row, cols) if aug[i][col]), None)
+        if p is None:
+            continue
+        aug[row], aug[p] = aug[p], aug[row]
+        inv = pow(aug[row][col], -1, R_ORDER)
+        aug[row] = [v * inv % R_ORDER for v in aug[row]]
+        for i in range(cols):
+            if i != row and aug[i][col]:
+                f = aug[i][col]
+                aug[i] = [(a - f * b) % R_ORDER for a, b in zip(aug[i], aug[row])]
+        pivots.append(col)
+        row += 1
+        if row == cols:
+            break
+    if any(aug[i][m] for i in range(row, cols)):                 # 0 = non-zero: the target is not in the span
+        return None
+    w = [0] * m
+    for i, col in enumerate(pivots):
+        w[col] = aug[i][m]
+    rows = [sat[i] for i in range(m) if w[i]]
+    weights = [w[i] for i in range(m) if w[i]]
+    for j in range(cols):                                          # the defining identity, checked on what is returned
+        assert sum(wx * int(matrix[x][j]) for x, wx in zip(rows, weights)) % R_ORDER == (1 if j == 0 else 0)
+    return rows, weights
+
+
+def fold_key(engine, rows, weights, h_gid, k_by_rho):
+    """Once per (key, policy): A_x = [w_x] H(GID) and B_x = [-w_x] K_rho(x),GID for the used rows.
+    h_gid: the 64-byte H(GID); k_by_rho[x]: the 64-byte key component of row x's attribute (a mapping or a sequence indexed by the
+    matrix row).  Returns (rows, weights, A [k, 64], B [k, 64])."""
+    if len(rows) != len(weights) or not rows:
+        raise ValueError("one weight per used row, at least one row")
+    h = np.asarray(h_gid, dtype=np.uint8).reshape(64)
+    kb = np.stack([np.asarray(k_by_rho[x], dtype=np.uint8).reshape(64) for x in rows])
+    A = engine.g1_scalar_mul(np.stack([h] * len(rows)), [int(w) % R_ORDER for w in weights])
+    B = engine.g1_scalar_mul(kb, [(-int(w)) % R_ORDER for w in weights])
+    return list(rows), [int(w) % R_ORDER for w in weights], np.asarray(A).reshape(-1, 64), np.asarray(B).reshape(-1, 64)
+
+
+def decrypt_batch(engine, folded, c0, c1, c2, c3):
+    """The n messages of n ciphertexts under one folded (key, policy): c0 [n, 384]; c1 [n, R, 384], c2, c3 [n, R, 128] with all R
+    rows of the policy per ciphertext (the used rows are picked here).  numpy in, numpy out; CUDA tensors in, CUDA tensor out, with
+    only the folded key, the weights and a segment table going to the device.  Three engine calls besides the row selection:
+    multi_pair (n segments of 2k pairs, one final exponentiation each), gt_multi_exp with the shared weight list, and
+    gt_mul + gt_div."""
+    rows, weights, A, B = folded
+    k = len(rows)
+    P_seg = np.concatenate([A, B]).reshape(2 * k, 64)
+    if type(c0).__module__.startswith("torch"):
+        import torch
+        n = c0.numel() // 384
+        R = c1.numel() // (n * 384)
+        idx = torch.as_tensor(rows, dtype=torch.long, device=c0.device)
+        g1 = c1.reshape(n, R, 384).index_select(1, idx).contiguous()
+        Q = torch.cat([c3.reshape(n, R, 128).index_select(1, idx), c2.reshape(n, R, 128).index_select(1, idx)], dim=1).contiguous()
+        P = torch.from_numpy(np.ascontiguousarray(P_seg)).to(c0.device).repeat(n, 1).contiguous()
+        E = engine.multi_pair(P.reshape(-1), Q.reshape(-1), np.arange(0, 2 * k * n + 1, 2 * k, dtype=np.uint64))
+        F = engine.gt_multi_exp(g1.reshape(-1), weights, np.arange(0, k * n + 1, k, dtype=np.uint64))
+        return engine.gt_div(c0.reshape(n, 384).contiguous(), engine.gt_mul(E, F))
+    c0 = np.asarray(c0, dtype=np.uint8).reshape(-1, 384)
+    n = c0.shape[0]
+    g1 = np.ascontiguousarray(np.asarray(c1, dtype=np.uint8).reshape(n, -1, 384)[:, rows, :])
+    Q = np.concatenate([np.asarray(c3, dtype=np.uint8).reshape(n, -1, 128)[:, rows, :], np.asarray(c2, dtype=np.uint8).reshape(n, -1, 128)[:, rows, :]], axis=1)
+    P = np.tile(P_seg, (n, 1))
+    E = engine.multi_pair(P.reshape(-1), np.ascontiguousarray(Q).reshape(-1), np.arange(0, 2 * k * n + 1, 2 * k, dtype=np.uint64))
+    F = engine.gt_multi_exp(g1.reshape(-1), weights, np.arange(0, k * n + 1, k, dtype=np.uint64))
+    return engine.gt_div(c0, engine.gt_mul(E, F))

@@ -614,6 +614,78 @@ func GTExp(z *bn254.GT, x bn254.GT, k *big.Int) *bn254.GT {
 	return z
 }
 
+// GTMultiExp: z = prod_i xs[i]^ks[i] in ONE call — the loop `res.Mul(res, tmp.Exp(c, w))` of dabe/lw11_dabe.go:180-196 and of the
+// threshold gates (access/tree/access_tree_node.go:123,156) with the squarings shared among the factors.  Exponents as in GTExp:
+// any big.Int, not reduced; a negative one inverts its base first; one wider than 256 bits contributes one factor per 256-bit
+// digit, x^k = prod_j (x^(2^(256 j)))^(k_j).  No factors: one.
+func GTMultiExp(z *bn254.GT, xs []bn254.GT, ks []*big.Int) (*bn254.GT, error) {
+	defer pin()()
+	if len(xs) != len(ks) {
+		return z, errSizes
+	}
+	mask := new(big.Int).Sub(new(big.Int).Lsh(big.NewInt(1), 256), big.NewInt(1))
+	var two255, two [32]byte
+	two255[31] = 0x80
+	two[0] = 2
+	bases := make([]bn254.GT, 0, len(xs))
+	exps := make([]byte, 0, 32*len(xs))
+	for i := range xs {
+		var abs big.Int
+		abs.Abs(ks[i])
+		base := xs[i]
+		if ks[i].Sign() < 0 {
+			var inv bn254.GT
+			must(C.gpbc_gt_inverse_batch(unsafe.Pointer(&xs[i]), 1, unsafe.Pointer(&inv)))
+			base = inv
+		}
+		for {
+			var digit big.Int
+			digit.And(&abs, mask)
+			var e [32]byte
+			b := digit.Bytes() // at most 32 bytes
+			for j := range b {
+				e[len(b)-1-j] = b[j]
+			}
+			bases = append(bases, base)
+			exps = append(exps, e[:]...)
+			abs.Rsh(&abs, 256)
+			if abs.Sign() == 0 {
+				break
+			}
+			h := gtExp256(&base, &two255) // base^(2^256) = (base^(2^255))^2
+			base = gtExp256(&h, &two)
+		}
+	}
+	var out bn254.GT
+	out.SetOne()
+	if len(bases) > 0 {
+		seg := [2]C.uint64_t{0, C.uint64_t(len(bases))}
+		rc := C.gpbc_gt_multi_exp(unsafe.Pointer(unsafe.SliceData(bases)), unsafe.Pointer(unsafe.SliceData(exps)), C.size_t(len(bases)), &seg[0], 1, unsafe.Pointer(&out))
+		if err := status(rc); err != nil {
+			return z, err
+		}
+	}
+	*z = out
+	return z, nil
+}
+
+// GTProd: z = prod_i xs[i], the chain `aggregateA.Mul(&aggregateA, &pk.A)` of gka/agka09/asbb.go:193-207 as one call (the GT
+// sibling of G1Sum).  No factors: one.
+func GTProd(z *bn254.GT, xs []bn254.GT) (*bn254.GT, error) {
+	defer pin()()
+	var out bn254.GT
+	out.SetOne()
+	if len(xs) > 0 {
+		seg := [2]C.uint64_t{0, C.uint64_t(len(xs))}
+		rc := C.gpbc_gt_multi_exp(unsafe.Pointer(unsafe.SliceData(xs)), nil, 0, &seg[0], 1, unsafe.Pointer(&out))
+		if err := status(rc); err != nil {
+			return z, err
+		}
+	}
+	*z = out
+	return z, nil
+}
+
 // GTMul, GTDiv, GTInverse replace new(bn254.GT).Mul(x, y) / Div(x, y) / Inverse(x) with gnark's signatures
 // (access/tree/access_tree_node.go:114,157; cpabe/bsw07/bsw07_cpabe.go:189-190): z may alias an operand.
 func GTMul(z, x, y *bn254.GT) *bn254.GT {

@@ -247,6 +247,24 @@ int gpbc_gt_inverse_batch(const void *a, size_t n, void *out);
 int gpbc_gt_mul_batch_dev(const void *d_a, const void *d_b, size_t n, void *d_out, void *stream);
 int gpbc_gt_div_batch_dev(const void *d_a, const void *d_b, size_t n, void *d_out, void *stream);
 int gpbc_gt_inverse_batch_dev(const void *d_a, size_t n, void *d_out, void *stream);
+/* Reductions in GT: out[s] = prod over i in [seg_off[s], seg_off[s+1]) of x[i]^k[i], each factor with (*GT).Exp's semantics (256-bit plain
+ * exponents, not reduced; any Fp12 base), one squaring chain shared by four factors — the `res.Mul(res, tmp.Exp(c, w))` loops of
+ * dabe/lw11_dabe.go:180-196 and access/tree/access_tree_node.go:123,156.  Results are canonical: the bytes of gpbc_gt_exp_batch
+ * folded with gpbc_gt_mul_batch.  An empty segment and exponent 0 give one.
+ *   k: nk == n exponents, one per element; or nk == n / n_seg, ONE list for all segments, each of exactly nk elements (the weights of
+ *   one policy against many ciphertexts); or k == NULL with nk == 0: the plain product, no squarings at all — the chain of
+ *   `aggregateA.Mul(&aggregateA, &pk.A)` in gka/agka09/asbb.go:193-207, the GT sibling of gpbc_g1_sum.
+ * seg_off as for gpbc_multi_pair: n_seg + 1 non-decreasing entries from 0 to n; the host entry validates it (and that a shared list
+ * fits every segment), the _dev entry clamps every offset to n and ends a segment after nk factors of a shared list, so a malformed
+ * table gives wrong products but never an out-of-bounds access — gpbc_check_segments_dev validates a device table, and that every
+ * segment has nk elements is the caller's promise there.  out (n_seg elements) must not overlap x.  Anything else is
+ * GPBC_ERR_INVALID_ARG before any launch.  Workspace: gpbc_gt_multi_exp_workspace_bytes(n, n_seg) =
+ * min(P, 65536) x 32 KiB of window tables + at most 432 x P bytes of piece values, P = n_seg x J <= 65536 + n_seg pieces with J from n
+ * and n_seg alone: bounded whatever the segment lengths are.  Stream-ordered, not synchronised. */
+int gpbc_gt_multi_exp(const void *x, const void *k, size_t nk, const uint64_t *seg_off, size_t n_seg, void *out);
+size_t gpbc_gt_multi_exp_workspace_bytes(size_t n, size_t n_seg);
+int gpbc_gt_multi_exp_dev(const void *d_x, const void *d_k, size_t nk, const uint64_t *d_seg_off, size_t n, size_t n_seg,
+                          void *d_out, void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* ---- fixed-base tables and multi-scalar multiplication -----------------------------------------
  * Sums  out[m] = sum_j [s[m][j]] base_j  over a FIXED set of bases: (*G1Affine).ScalarMultiplicationBase (nbase == 1, the

@@ -149,6 +149,24 @@ inline const GeneratorTables &generator_tables() { static const GeneratorTables 
 inline G1Affine &G1Affine::ScalarMultiplicationBase(const Scalar &s) { check(gpbc_fixed_base_msm(detail::generator_tables().g1, s.le.data(), 1, this)); return *this; }
 inline G2Affine &G2Affine::ScalarMultiplicationBase(const Scalar &s) { check(gpbc_fixed_base_msm(detail::generator_tables().g2, s.le.data(), 1, this)); return *this; }
 
+// prod_i x[i]^k[i] in one call (the Exp + Mul loops of dabe/lw11_dabe.go:180-196, access/tree/access_tree_node.go:123,156) and the
+// plain product (gka/agka09/asbb.go:193-207); no factors give one.
+inline GT GTMultiExp(const std::vector<GT> &x, const std::vector<Scalar> &k) {
+    if (x.size() != k.size()) throw std::invalid_argument("invalid inputs sizes");
+    std::vector<uint8_t> e(32 * k.size());
+    for (size_t i = 0; i < k.size(); i++) std::memcpy(e.data() + 32 * i, k[i].le.data(), 32);
+    const uint64_t seg[2] = {0, x.size()};
+    GT z;
+    check(gpbc_gt_multi_exp(x.data(), e.data(), k.size(), seg, 1, &z));
+    return z;
+}
+inline GT GTProd(const std::vector<GT> &x) {
+    const uint64_t seg[2] = {0, x.size()};
+    GT z;
+    check(gpbc_gt_multi_exp(x.data(), nullptr, 0, seg, 1, &z));
+    return z;
+}
+
 // bn254.Pair: product of pairings, one final exponentiation.  gnark's error: "invalid inputs sizes".
 inline GT Pair(const std::vector<G1Affine> &P, const std::vector<G2Affine> &Q) {
     if (P.empty() || P.size() != Q.size()) throw std::invalid_argument("invalid inputs sizes");

@@ -1,0 +1,132 @@
+"""LW11 decentralised ABE batched decryption through the host planner gopairingbasedcryptography_amd/lw11.py, on the oracle engine
+(the same flow runs on the GPU engine in test_lw11_gpu.py): the reconstruction weights by their defining identity in Python
+integers, then small instances made by lw11_fixture.py from known secrets — decrypt_batch returns the messages; for an AND / OR
+policy it is bit-identical to the reference's loop written out with oracle calls; for a matrix whose weights are not 0 / 1 it
+returns the messages too."""
+import numpy as np
+import pytest
+
+import bn254_py as o
+import gt_multi_exp_cases as gc
+from lw11_fixture import Instance, and_chain_policy, and_or_policy, threshold_policy
+from gopairingbasedcryptography_amd import lw11
+
+
+class OracleEngine:
+    def __init__(self, oracle):
+        self.o = oracle
+
+    def _k(self, ks):
+        if isinstance(ks, (list, tuple)):
+            return np.frombuffer(b"".join(o.scalar_to_bytes(int(k) % o.R) for k in ks), dtype=np.uint8)
+        return ks
+
+    def pair_batch(self, P, Q): return self.o.pair_batch(P, Q)
+    def multi_pair(self, P, Q, off): return self.o.multi_pair(P, Q, off, threads=4)
+    def g1_scalar_mul(self, b, k): return self.o.g1_scalar_mul(b, self._k(k))
+    def g2_scalar_mul(self, b, k): return self.o.g2_scalar_mul(b, self._k(k))
+    def gt_mul(self, a, b): return self.o.gt_mul(a, b)
+    def gt_div(self, a, b): return self.o.gt_div(a, b)
+    def gt_exp(self, x, k): return self.o.gt_exp(x, self._k(k))
+
+    def gt_multi_exp(self, x, k, seg):
+        x = np.asarray(x, dtype=np.uint8).reshape(-1, 384)
+        seg = [int(v) for v in seg]
+        return gc.expect(self.o, x, k, seg, k is not None and len(k) != len(x))
+
+
+def check_identity(matrix, rows, weights):
+    for j in range(len(matrix[0])):
+        assert sum(w * matrix[x][j] for x, w in zip(rows, weights)) % o.R == (1 if j == 0 else 0)
+    assert all(0 < w < o.R for w in weights)
+
+
+def test_weights_a_and_b_or_c():
+    m, rho = [[1, 1], [0, -1], [1, 0]], ["A", "B", "C"]               # (A and B) or C
+    assert lw11.reconstruction_weights(m, rho, {"A", "B"}) == ([0, 1], [1, 1])
+    assert lw11.reconstruction_weights(m, rho, {"C"}) == ([2], [1])
+    assert lw11.reconstruction_weights(m, rho, {"A"}) is None and lw11.reconstruction_weights(m, rho, {"B"}) is None
+    assert lw11.reconstruction_weights(m, rho, {"Z"}) is None and lw11.reconstruction_weights(m, rho, set()) is None
+    rows, w = lw11.reconstruction_weights(m, rho, {"A", "B", "C"})     # redundant rows: any solution, zero weights dropped
+    check_identity(m, rows, w)
+    assert len(rows) < 3
+
+
+def test_weights_and_chain_of_three():
+    m, rho = and_chain_policy(3)
+    assert m == [[1, 1, 0], [0, -1, 1], [0, 0, -1]]
+    assert lw11.reconstruction_weights(m, rho, set(rho)) == ([0, 1, 2], [1, 1, 1])
+    for missing in rho:
+        assert lw11.reconstruction_weights(m, rho, set(rho) - {missing}) is None
+
+
+def test_weights_redundant_rows_and_repeated_attributes():
+    m, rho = and_or_policy()                                            # (11 and 22) or (33 and 44)
+    rows, w = lw11.reconstruction_weights(m, rho, {11, 22, 33, 44})
+    check_identity(m, rows, w)
+    assert lw11.reconstruction_weights(m, rho, {11, 22, 44}) == ([0, 1], [1, 1])
+    assert lw11.reconstruction_weights(m, rho, {11, 33, 44}) == ([2, 3], [1, 1])
+    assert lw11.reconstruction_weights(m, rho, {11, 44}) is None
+    m2, rho2 = [[1, 1], [0, -1], [1, 1], [2, 0]], [5, 6, 5, 7]        # attribute 5 labels two equal rows; row 3 alone needs weight 1 / 2
+    rows, w = lw11.reconstruction_weights(m2, rho2, {5, 6})
+    check_identity(m2, rows, w)
+    assert lw11.reconstruction_weights(m2, rho2, {7}) == ([3], [pow(2, -1, o.R)])
+
+
+def test_weights_that_are_not_zero_or_one():
+    """2 of 3 as Shamir rows (1, x): rows 1 and 3 give the Lagrange coefficients 3 / 2 and -1 / 2 — the only solution"""
+    m, rho = threshold_policy(2, 3)
+    assert m == [[1, 1], [1, 2], [1, 3]]
+    rows, w = lw11.reconstruction_weights(m, rho, {rho[0], rho[2]})
+    half = pow(2, -1, o.R)
+    assert rows == [0, 2] and w == [3 * half % o.R, (-half) % o.R]
+    check_identity(m, rows, w)
+    assert lw11.reconstruction_weights(m, rho, {rho[1]}) is None
+
+
+def test_and_or_policy_matches_the_reference_loop(oracle):
+    """3 ciphertexts, 4 rows, (11 and 22) or (33 and 44), key for 11, 22, 44: the messages come back and every one is bit-identical
+    to the reference's loop (running product raised at every row, weights indexed by row number) — all weights are 1 there"""
+    eng = OracleEngine(oracle)
+    m, rho = and_or_policy()
+    inst = Instance(eng, m, rho, [11, 22, 44, 99], n_ct=3)
+    rows, w = lw11.reconstruction_weights(m, rho, inst.user_attrs)
+    assert (rows, w) == ([0, 1], [1, 1])
+    folded = lw11.fold_key(eng, rows, w, inst.h_gid, inst.k_by_row)
+    out = lw11.decrypt_batch(eng, folded, inst.c0, inst.c1, inst.c2, inst.c3)
+    assert out.shape == (3, 384)
+    for t in range(3):
+        assert (out[t] == inst.msgs[t]).all()
+        assert (out[t] == inst.row_by_row_decrypt(oracle, t, rows, w, running=True)).all()
+        assert (out[t] == inst.row_by_row_decrypt(oracle, t, rows, w, running=False)).all()
+    # the other branch of the OR with another key: rows 2 and 3
+    inst2 = Instance(eng, m, rho, [33, 44], n_ct=2, tag="b")
+    rows2, w2 = lw11.reconstruction_weights(m, rho, inst2.user_attrs)
+    assert rows2 == [2, 3]
+    out2 = lw11.decrypt_batch(eng, lw11.fold_key(eng, rows2, w2, inst2.h_gid, inst2.k_by_row), inst2.c0, inst2.c1, inst2.c2, inst2.c3)
+    assert (out2 == inst2.msgs).all()
+
+
+def test_weights_other_than_one_return_the_message(oracle):
+    """3 of 4 as Shamir rows, key for rows 0, 1, 3: Lagrange weights.  decrypt_batch returns the messages, and so does the row by
+    row evaluation of the scheme.  (The reference's loop as written does not: it raises the running product at every row and
+    reads wSlice[x] at the row number, which for rows [0, 1, 3] is out of the compacted slice's range.  Stated, not asserted.)"""
+    eng = OracleEngine(oracle)
+    m, rho = threshold_policy(3, 4)
+    inst = Instance(eng, m, rho, [rho[0], rho[1], rho[3]], n_ct=3, tag="t")
+    rows, w = lw11.reconstruction_weights(m, rho, inst.user_attrs)
+    assert rows == [0, 1, 3] and all(x not in (0, 1) for x in w)
+    folded = lw11.fold_key(eng, rows, w, inst.h_gid, inst.k_by_row)
+    out = lw11.decrypt_batch(eng, folded, inst.c0, inst.c1, inst.c2, inst.c3)
+    assert (out == inst.msgs).all()
+    assert (inst.row_by_row_decrypt(oracle, 1, rows, w, running=False) == inst.msgs[1]).all()
+    # a key that misses the threshold cannot be folded at all
+    assert lw11.reconstruction_weights(m, rho, {rho[0], rho[3]}) is None
+
+
+def test_fold_key_arguments(oracle):
+    eng = OracleEngine(oracle)
+    with pytest.raises(ValueError):
+        lw11.fold_key(eng, [0, 1], [1], np.zeros(64, np.uint8), {0: np.zeros(64, np.uint8), 1: np.zeros(64, np.uint8)})
+    with pytest.raises(ValueError):
+        lw11.fold_key(eng, [], [], np.zeros(64, np.uint8), {})

@@ -18,6 +18,7 @@
 #include "../gopairingbasedcryptography_amd/csrc/msm29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/group29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/fr29.hip.hpp"
+#include "../gopairingbasedcryptography_amd/csrc/gtmexp29.hip.hpp"
 #include <condition_variable>
 #include <mutex>
 #include <thread>
@@ -383,6 +384,43 @@ void hc_gt_exp_pair(const uint8_t *A, const uint8_t *K, size_t n, uint8_t *out) 
         std::thread t1(lane, true);
         lane(false);
         t1.join();
+    }
+}
+// segmented GT multi-exponentiation exactly as gpbc_gt_multi_exp_dev (csrc/gpbc_gtmexp.hip) runs it: the same plan (gt_mexp_pieces per
+// level, gt_mexp_piece_range per piece), the same lane functions (f12p_multi_exp, f12p_product for K = null and for the folds), one
+// piece per lane pair.  out[s] = prod_{i in [seg_off[s], seg_off[s+1])} A[i]^K[i]; nk = n, or one list of nk exponents for all segments
+void hc_gt_multi_exp_pair(const uint8_t *A, const uint8_t *K, size_t nk, const uint64_t *seg_off, size_t n, size_t n_seg, uint8_t *out) {
+    std::vector<uint8_t> val[2];
+    const uint8_t *x = A;
+    const bool shared = K && nk != n;
+    size_t cur_n = n, m = 0;                               // m: uniform segment length of the fold levels (seg_off = null there)
+    for (int level = 0;; level++) {
+        const size_t J = gt_mexp_pieces(cur_n, n_seg, K != nullptr), pieces = n_seg * J;
+        uint8_t *dst = out;
+        if (J > 1) { val[level & 1].assign(pieces * 384, 0); dst = val[level & 1].data(); }
+        for (size_t P = 0; P < pieces; P++) {
+            const size_t s = P / J;
+            size_t lo = seg_off ? (size_t)seg_off[s] : s * m, hi = seg_off ? (size_t)seg_off[s + 1] : lo + m, a, b;
+            gt_mexp_piece_range(lo, hi, P % J, J, a, b);
+            PairRendezvous rv;
+            auto lane = [&](bool odd) {
+                PairHost px{odd, &rv};
+                const size_t half = odd ? 192 : 0, k0 = shared ? lo : 0;
+                auto base = [&](size_t i) { return f6_load(x + (a + i) * 384 + half); };
+                F6 r;
+                if (K) {
+                    alignas(16) static thread_local int32_t tab[GT_MEXP_TAB_DWORDS];
+                    r = f12p_multi_exp(px, b - a, base, [&](size_t i, int w) { uint32_t d; memcpy(&d, K + 32 * (a + i - k0) + 4 * (w >> 3), 4); return (int)((d >> (4 * (w & 7))) & 15); }, tab);
+                } else r = f12p_product(px, b - a, base);
+                f6_store(dst + P * 384 + half, r);
+                stats_flush();
+            };
+            std::thread t1(lane, true);
+            lane(false);
+            t1.join();
+        }
+        if (J == 1) return;
+        x = dst; K = nullptr; seg_off = nullptr; m = J; cur_n = pieces;
     }
 }
 // wire formats (csrc/wire29.hip.hpp): kind 0 G1, 1 G2, 2 GT; the same per-element functions the kernels call
