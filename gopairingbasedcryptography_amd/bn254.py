@@ -663,6 +663,80 @@ def fr_poly_quotients(coeffs, points, B, stride=None, out=None, ok=None):
     return out, ok
 
 
+def _fr_rows_arg(v, per_row, what):
+    """(buffer, rows, per_row) of a set / node argument: nested Python ints [rows][per_row] (per_row may then be None), or scalar
+    rows as a uint8 array / bytes / CUDA tensor together with per_row"""
+    if not _is_torch(v) and not isinstance(v, (np.ndarray, bytes, bytearray)):
+        rows = [list(r) for r in v]
+        per_row = len(rows[0]) if rows and per_row is None else per_row
+        if any(len(r) != per_row for r in rows):
+            raise ValueError("%s: every row needs %s scalars" % (what, per_row))
+        v = [s for r in rows for s in r]
+    if not isinstance(per_row, (int, np.integer)) or isinstance(per_row, bool) or not 1 <= int(per_row) <= FR_POLY_MAX_B:
+        raise ValueError("%s: the row length must be in 1 .. %d (got %s)" % (what, FR_POLY_MAX_B, per_row))
+    per_row = int(per_row)
+    if _is_torch(v):
+        return v, _fr_poly_shape(v.numel() // SCALAR_BYTES if v.numel() % SCALAR_BYTES == 0 else -1, per_row, what), per_row
+    buf = fr_to_bytes(v)
+    return buf, _fr_poly_shape(buf.size // SCALAR_BYTES, per_row, what), per_row
+
+
+def fr_lagrange_basis(set, B=None, nodes=None, m=None, x=None, out=None):
+    """out[j][t] = prod over the elements s of set[j] with s != nodes[j][t] (mod r) of (x[j] - s) / (nodes[j][t] - s), for k rows:
+    utils.ComputeLagrangeBasis with a node set per item (include/gpbc_bn254.h).  set: [rows][B] Python ints, or rows x B scalar
+    rows (uint8 array / CUDA tensor) with B; nodes likewise with m, None = the set's own elements (m = B); x: scalars, None = 0.
+    set and nodes have one row (shared by all) or k; x has one value or k; k is the largest of the three counts.  A set element
+    equal to the node modulo r is skipped, so the result is total; a repeated element counts once per occurrence.
+    Returns [k, m, 32] canonical scalars of the kind that went in (numpy, or a CUDA tensor)."""
+    lib = _lib.load()
+    s, ns, B = _fr_rows_arg(set, B, "set")
+    args = [s]
+    if nodes is None:
+        if m is not None and int(m) != B:
+            raise ValueError("without nodes m must equal B (got m = %s, B = %d)" % (m, B))
+        nd, nn, m = None, ns, B
+    else:
+        nd, nn, m = _fr_rows_arg(nodes, m, "nodes")
+        args.append(nd)
+    if x is None:
+        xs, nx = None, 0
+    else:
+        xs = x if _is_torch(x) else fr_to_bytes(x)
+        args.append(xs)
+        nx = (xs.numel() if _is_torch(xs) else xs.size)
+        if nx % SCALAR_BYTES:
+            raise ValueError("x must hold whole %d-byte scalars" % SCALAR_BYTES)
+        nx //= SCALAR_BYTES
+    dev = [_is_torch(a) for a in args]
+    if any(dev) and not all(dev):
+        raise ValueError("set, nodes and x must all be CUDA tensors (or all host buffers)")
+    k = max(ns, nn, nx)
+    if ns not in (1, k) or nn not in (1, k) or (xs is not None and nx not in (1, k)):
+        raise ValueError("set, nodes and x need one row or one row per output row (got %d, %d, %d)" % (ns, nn, nx))
+    if k > (1 << 29) - 1:
+        raise ValueError("too many rows for one call (%d)" % k)
+    null = ctypes.c_void_p(None)
+    if dev[0]:
+        specs = [(s, ns * B * SCALAR_BYTES, "set")] + ([(nd, nn * m * SCALAR_BYTES, "nodes")] if nd is not None else []) + \
+                ([(xs, nx * SCALAR_BYTES, "x")] if xs is not None else []) + ([(out, k * m * SCALAR_BYTES, "out")] if out is not None else [])
+        _tchk_static(s, *specs)
+        _ensure_init()
+        if out is None:
+            import torch
+            out = torch.empty((k, m, SCALAR_BYTES), dtype=torch.uint8, device=s.device)
+        if k:
+            _tchk(s, *specs)
+            _lib.check(lib.gpbc_fr_lagrange_basis_dev(_tptr(s), _sz(ns), _sz(B), _tptr(nd) if nd is not None else null, _sz(nn), _sz(m),
+                                                      _tptr(xs) if xs is not None else null, _sz(nx), _sz(k), _tptr(out), _torch_stream()))
+        return out
+    out = _host_out(out, k * m * SCALAR_BYTES, (k, m, SCALAR_BYTES))
+    if k:
+        _ensure_init()
+        _lib.check(lib.gpbc_fr_lagrange_basis(_ptr(s), _sz(ns), _sz(B), _ptr(nd) if nd is not None else null, _sz(nn), _sz(m),
+                                              _ptr(xs) if xs is not None else null, _sz(nx), _sz(k), _ptr(out)))
+    return out
+
+
 _gen_tables = {}
 
 

@@ -359,5 +359,104 @@ GPBC_INLINE Fr fr_poly_point(const uint8_t *p) { return fr_to_internal(fr_load_r
 // written, and after the last step (i = 0) the remainder f(point)
 GPBC_INLINE Fr fr_poly_horner_step(const Fr &carry, const Fr &c_i, const Fr &point) { return fr_canonical<1, 3>(fr_add(c_i, fr_mul(carry, point))); }
 
+// ------------------------------------------------------------------------------------------------ Lagrange basis
+// out[t] = prod over the set elements s != node_t (by value modulo r) of (x - s) / (node_t - s): utils.ComputeLagrangeBasis of the
+// reference as fibe/sw05_fibe_common.go:316 and fibe/sw05_fibe_large_universe.go:277,318 call it, once per element of a set that
+// differs from item to item.  Set elements, nodes and x are made canonical ONCE (fr_lagrange_in, when the set is staged and when a
+// lane loads its node), so "s equals the node" is a limb comparison and a factor is the carry-free difference of two canonical
+// values.  A skipped factor multiplies both products by the chain's 1 (2^261), which keeps every lane of a wave on one path.
+// Numerator and denominator start at 2^261 and take the same number c of plain factors, so both are (true value) x 2^(261 (1 - c))
+// and the power cancels in the quotient: no factor is ever converted.
+// A lane owns G outputs of ONE row (nodes gi, gi + gpr, ..., gpr = ceil(m / G): neighbouring lanes read and write neighbouring
+// scalars) and inverts the product of their G denominators once.  With D_g, N_g the products of output g:
+//   P_g = P_(g-1) D_g / 2^261,  W_g = N_g P_(g-1) / 2^261  (P_0 = D_0, W_0 = N_0),  I_(G-1) = 2^261 / P_(G-1) (fr_inv and one product),
+//   out_g = W_g I_g / 2^261 = N_g / D_g,  I_(g-1) = I_g D_g / 2^261 = 2^261 / P_(g-1)
+// — four products per output beside its 2 B and 1 / G of an inversion; W and D wait in registers (18 G VGPRs).  An output past
+// the row's end carries D = 2^261 and leaves the chain as it is.  No denominator is 0 (every factor equal to the node is skipped),
+// so there is nothing to flag.  G = 4: 72 VGPRs of W and D beside node, x, the two running products and a product in flight; the
+// inversion (~14 k instructions) is then 3.5 k per output against the 2 B + 4 products (~8 k at B = 16).
+constexpr int FR_LAGRANGE_G = 4;
+GPBC_INLINE Fr fr_lagrange_in(const uint8_t *p) { return fr_canonical<1, 2>(fr_reduce(fr_load_raw(p))); }
+GPBC_INLINE bool fr_limbs_equal(const Fr &a, const Fr &b) {       // of two canonical values
+    int32_t o = 0;
+#pragma unroll
+    for (int i = 0; i < NL; i++) o |= a.l.v[i] ^ b.l.v[i];
+    return o == 0;
+}
+// set_at(u): the canonical set element u of the lane's row (LDS on the device, a vector in the host harness); nodes: the row's m
+// nodes in the scalar format, or null = the set's own elements (m == B); out: the row's m outputs.
+template <int G, class SetAt>
+GPBC_INLINE void fr_lagrange_lane(const SetAt &set_at, uint32_t B, const uint8_t *nodes, const Fr &x, uint32_t m, uint32_t gi, uint32_t gpr, uint8_t *out) {
+    Fr W[G], D[G], P = fr_one();
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+        const uint32_t t = gi + (uint32_t)g * gpr;
+        Fr n = fr_one(), d = fr_one();
+        if (t < m) {
+            const Fr node = nodes ? fr_lagrange_in(nodes + 32 * (size_t)t) : set_at(t);
+            for (uint32_t u = 0; u < B; u++) {
+                const Fr s = set_at(u);
+                const bool skip = fr_limbs_equal(s, node);
+                n = fr_mul(n, skip ? fr_one() : fr_sub(x, s));
+                d = fr_mul(d, skip ? fr_one() : fr_sub(node, s));
+            }
+        }
+        D[g] = d;
+        W[g] = g ? fr_mul(n, P) : n;
+        P = g ? fr_mul(P, d) : d;
+    }
+    Fr inv = fr_mul(fr_inv(P), fr_plain_one());                // 2^522 / P / 2^261
+#pragma unroll
+    for (int g = G - 1; g >= 0; g--) {
+        const uint32_t t = gi + (uint32_t)g * gpr;
+        if (t < m) fr_store_canonical(out + 32 * (size_t)t, fr_canonical<1, 2>(fr_mul(W[g], inv)));
+        if (g) inv = fr_mul(inv, D[g]);
+    }
+}
+
+// The launch of k_fr_lagrange_basis (csrc/gpbc_fr.hip), in functions the host harness runs as well: one wave of FR_LAG_WAVE lanes per
+// workgroup, gpr = ceil(m / G) lanes per row, rpb rows per workgroup (or bpr workgroups per row when gpr > 64), the sets of a
+// workgroup's rows staged at word offset (local row) x pitch + u x NL of an LDS block of cap x NL + FR_LAG_WAVE words, cap = 256 or 1024
+// set elements.  The pitch is odd, so the rows of a wave start in different banks.
+constexpr int FR_LAG_WAVE = 64, FR_LAG_SMALL = 256, FR_LAG_LARGE = FR_POLY_MAX_B;
+struct LagrangeGeom { uint32_t B, m, gpr, rpb, bpr, large; };
+struct LagrangeLane { size_t row; uint32_t lr, gi; bool active; };
+// rows per workgroup lowered until their sets fit; only B > 16 with m < 64 and a set per row leaves lanes idle
+inline LagrangeGeom fr_lagrange_geometry(size_t B, size_t m, bool shared_set) {
+    LagrangeGeom g;
+    g.B = (uint32_t)B; g.m = (uint32_t)m;
+    g.gpr = (uint32_t)((m + FR_LAGRANGE_G - 1) / FR_LAGRANGE_G);
+    g.bpr = (g.gpr + FR_LAG_WAVE - 1) / FR_LAG_WAVE;
+    g.rpb = g.bpr > 1 ? 1 : FR_LAG_WAVE / g.gpr;
+    const size_t need = shared_set ? B : g.rpb * B;
+    g.large = need > (size_t)FR_LAG_SMALL;
+    if (need > (size_t)FR_LAG_LARGE) g.rpb = (uint32_t)((size_t)FR_LAG_LARGE / B);        // >= 1: B <= 1024
+    return g;
+}
+GPBC_INLINE uint32_t fr_lagrange_pitch(const LagrangeGeom &g) { return (g.B * NL) | 1u; }
+GPBC_INLINE size_t fr_lagrange_row0(const LagrangeGeom &g, uint32_t block) { return (size_t)(block / g.bpr) * g.rpb; }
+GPBC_INLINE uint32_t fr_lagrange_rows(const LagrangeGeom &g, uint32_t block, size_t k) {
+    const size_t left = k - fr_lagrange_row0(g, block);
+    return left < g.rpb ? (uint32_t)left : g.rpb;
+}
+// a lane's share of the staging: put(word offset, canonical element); set_step = 0 stages the one shared set
+template <class Put> GPBC_INLINE void fr_lagrange_stage(const LagrangeGeom &g, uint32_t block, uint32_t lane, size_t k, const uint8_t *set, size_t set_step, const Put &put) {
+    const size_t row0 = fr_lagrange_row0(g, block);
+    const uint32_t staged = set_step ? fr_lagrange_rows(g, block, k) : 1u, pitch = fr_lagrange_pitch(g);
+    for (uint32_t idx = lane; idx < staged * g.B; idx += FR_LAG_WAVE) {
+        const uint32_t lr = idx / g.B, u = idx % g.B;
+        put(lr * pitch + u * NL, fr_lagrange_in(set + (row0 + lr) * set_step + 32 * (size_t)u));
+    }
+}
+GPBC_INLINE LagrangeLane fr_lagrange_map(const LagrangeGeom &g, uint32_t block, uint32_t lane, size_t k) {
+    LagrangeLane l;
+    l.lr = lane / g.gpr;
+    l.gi = (block % g.bpr) * FR_LAG_WAVE + lane % g.gpr;
+    l.row = fr_lagrange_row0(g, block) + l.lr;
+    l.active = l.lr < fr_lagrange_rows(g, block, k) && l.gi < g.gpr;
+    return l;
+}
+GPBC_INLINE size_t fr_lagrange_grid(const LagrangeGeom &g, size_t k) { return (k + g.rpb - 1) / g.rpb * g.bpr; }
+
 }  // namespace gpbc
 #endif

@@ -574,7 +574,7 @@ __global__ void __launch_bounds__(BLOCK) k_fp_mul(const uint8_t *__restrict__ a,
 
 extern "C" {
 
-int gpbc_abi_version(void) { return 7; }   // 7: G1 / G2 add, sub, double batch entries; 6: hash-to-curve entries, release_workspaces, pipelined-Miller knob; fixed-Q _dev entry asynchronous
+int gpbc_abi_version(void) { return 8; }   // 8: gpbc_fr_lagrange_basis; 7: G1 / G2 add, sub, double batch entries; 6: hash-to-curve entries, release_workspaces, pipelined-Miller knob; fixed-Q _dev entry asynchronous
 const char *gpbc_last_error(void) { return g_err; }
 
 int gpbc_device_count(void) {

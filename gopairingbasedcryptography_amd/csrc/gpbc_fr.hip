@@ -1,6 +1,7 @@
 // libgpbc_bn254.so, unit 7 of 7: the scalar field Fr on the device (csrc/fr29.hip.hpp) — elementwise add / sub / mul / neg /
-// inverse and the fr.Element conversions on the ABI's scalar format, and the two polynomial kernels of the AFP25 / GWWW25 opening
-// proofs — with their C-ABI entries (include/gpbc_bn254.h, "scalar field").  gfx950 only.
+// inverse and the fr.Element conversions on the ABI's scalar format, the two polynomial kernels of the AFP25 / GWWW25 opening
+// proofs and the Lagrange basis over a node set per row (SW05 fuzzy IBE) — with their C-ABI entries (include/gpbc_bn254.h,
+// "scalar field").  gfx950 only.
 #include "gpbc_common.hpp"
 #include "fr29.hip.hpp"
 
@@ -130,6 +131,36 @@ __global__ void __launch_bounds__(BLOCK) k_fr_poly_quotients_long(const uint8_t 
     fr_poly_quotients_kernel<FR_POLY_MAX_B>(coeffs, points, B, blocks_per_poly, stride, q_out, ok_out);
 }
 
+// ------------------------------------------------------------------------------------------------ Lagrange basis
+// out[j][t] = prod_{u < B, set[j][u] != nodes[j][t]} (x[j] - set[j][u]) / (nodes[j][t] - set[j][u]): fr_lagrange_lane, one wave per
+// workgroup.  A lane owns FR_LAGRANGE_G nodes of one row, so a row takes gpr = ceil(m / G) lanes: a wave holds rpb = 64 / gpr rows
+// of different sets (m = 16: sixteen lanes-of-four, 16 rows), or a row spreads over bpr = ceil(gpr / 64) workgroups (m > 256).  The
+// workgroup stages the sets of its rows in LDS, canonical, nine limbs each with an odd row pitch (lanes of one row read one address:
+// a broadcast; lanes of different rows read different banks); a shared set (set_step == 0) is staged once.  Two instances as for
+// the quotients: LDS for 256 set elements (9 KB: the common shapes keep every wave slot) and for 1024 (36 KB).  Geometry, staging
+// and lane mapping are fr29.hip.hpp's (fr_lagrange_geometry / _stage / _map), which the host harness runs workgroup by workgroup.
+static_assert(FR_LAG_WAVE == BLOCK, "one wave per workgroup");
+template <int CAP> __device__ __forceinline__ void fr_lagrange_kernel(const uint8_t *__restrict__ set, size_t set_step, const uint8_t *__restrict__ nodes, size_t node_step,
+                                                                       const uint8_t *__restrict__ x, size_t x_step, size_t k, LagrangeGeom gm, uint8_t *__restrict__ out) {
+    __shared__ int32_t ss[CAP * NL + BLOCK];
+    fr_lagrange_stage(gm, blockIdx.x, threadIdx.x, k, set, set_step, [&](uint32_t off, const Fr &v) { lds_put(ss + off, v); });
+    __syncthreads();
+    const LagrangeLane l = fr_lagrange_map(gm, blockIdx.x, threadIdx.x, k);
+    if (!l.active) return;
+    const int32_t *mine = ss + (set_step ? l.lr * fr_lagrange_pitch(gm) : 0u);
+    const Fr xc = x ? fr_lagrange_in(x + l.row * x_step) : fr_zero();
+    fr_lagrange_lane<FR_LAGRANGE_G>([&](uint32_t u) { return lds_get(mine + u * NL); }, gm.B, nodes ? nodes + l.row * node_step : nullptr, xc, gm.m, l.gi, gm.gpr,
+                                    out + l.row * gm.m * 32);
+}
+GPBC_KERNEL_G1 k_fr_lagrange_basis(const uint8_t *__restrict__ set, size_t set_step, const uint8_t *__restrict__ nodes, size_t node_step, const uint8_t *__restrict__ x,
+                                   size_t x_step, size_t k, LagrangeGeom gm, uint8_t *__restrict__ out) {
+    fr_lagrange_kernel<FR_LAG_SMALL>(set, set_step, nodes, node_step, x, x_step, k, gm, out);
+}
+__global__ void __launch_bounds__(BLOCK) k_fr_lagrange_basis_long(const uint8_t *__restrict__ set, size_t set_step, const uint8_t *__restrict__ nodes, size_t node_step, const uint8_t *__restrict__ x,
+                                        size_t x_step, size_t k, LagrangeGeom gm, uint8_t *__restrict__ out) {
+    fr_lagrange_kernel<FR_LAG_LARGE>(set, set_step, nodes, node_step, x, x_step, k, gm, out);
+}
+
 extern "C" {
 
 // ------------------------------------------------------------------------------------------------ elementwise entries
@@ -229,6 +260,55 @@ int gpbc_fr_poly_quotients(const void *coeffs, const void *points, size_t B, siz
                              HostCall().input(coeffs, (B + 1) * GPBC_SCALAR_BYTES).input(points, B * GPBC_SCALAR_BYTES).output(q_out, B * stride * GPBC_SCALAR_BYTES).output(ok_out, B),
                              HostRoute{},
                              [=](const DevCols &d, size_t m, hipStream_t st) { return gpbc_fr_poly_quotients_dev(d.in[0], d.in[1], B, m, stride, d.out[0], d.out[1], st); });
+}
+
+// ------------------------------------------------------------------------------------------------ Lagrange basis entries
+static bool overlap(const void *a, size_t na, const void *b, size_t nb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return a && b && pa < pb + nb && pb < pa + na;
+}
+static int lagrange_args(const void *set, size_t n_set_rows, size_t B, const void *nodes, size_t n_node_rows, size_t m, const void *x, size_t nx, size_t k, const void *out) {
+    if (B < 1 || B > (size_t)FR_POLY_MAX_B || m < 1 || m > (size_t)FR_POLY_MAX_B)
+        return fail(GPBC_ERR_INVALID_ARG, "B and m must be in 1 .. %d (got B = %zu, m = %zu)", FR_POLY_MAX_B, B, m);
+    if (k > (size_t)0x7fffffff / 4) return fail(GPBC_ERR_INVALID_ARG, "too many rows for one call (%zu)", k);
+    if (!k) return GPBC_OK;
+    if (n_set_rows != 1 && n_set_rows != k) return fail(GPBC_ERR_INVALID_ARG, "n_set_rows must be 1 or k (got %zu, k = %zu)", n_set_rows, k);
+    if (nodes && n_node_rows != 1 && n_node_rows != k) return fail(GPBC_ERR_INVALID_ARG, "n_node_rows must be 1 or k (got %zu, k = %zu)", n_node_rows, k);
+    if (!nodes && m != B) return fail(GPBC_ERR_INVALID_ARG, "without nodes m must equal B (got m = %zu, B = %zu)", m, B);
+    if (x ? nx != 1 && nx != k : nx != 0) return fail(GPBC_ERR_INVALID_ARG, "nx must be 1 or k, or 0 with x == NULL (got nx = %zu, k = %zu)", nx, k);
+    if (!set || !out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    const size_t out_bytes = k * m * GPBC_SCALAR_BYTES;
+    if (overlap(out, out_bytes, set, n_set_rows * B * GPBC_SCALAR_BYTES) || overlap(out, out_bytes, nodes, n_node_rows * m * GPBC_SCALAR_BYTES) ||
+        overlap(out, out_bytes, x, nx * GPBC_SCALAR_BYTES))
+        return fail(GPBC_ERR_INVALID_ARG, "out overlaps an input");
+    return GPBC_OK;
+}
+int gpbc_fr_lagrange_basis_dev(const void *d_set, size_t n_set_rows, size_t B, const void *d_nodes, size_t n_node_rows, size_t m, const void *d_x, size_t nx, size_t k,
+                               void *d_out, void *stream) {
+    TRY(lagrange_args(d_set, n_set_rows, B, d_nodes, n_node_rows, m, d_x, nx, k, d_out));
+    if (!k) return GPBC_OK;
+    TRY(bind_device());
+    const bool shared_set = n_set_rows == 1 && k > 1;
+    const LagrangeGeom g = fr_lagrange_geometry(B, m, shared_set);
+    const unsigned grid = (unsigned)fr_lagrange_grid(g, k);
+    const size_t set_step = shared_set ? 0 : B * GPBC_SCALAR_BYTES, node_step = d_nodes && n_node_rows == k && k > 1 ? m * GPBC_SCALAR_BYTES : 0,
+                 x_step = d_x && nx == k && k > 1 ? GPBC_SCALAR_BYTES : 0;
+    const uint8_t *s = (const uint8_t *)d_set, *nd = (const uint8_t *)d_nodes, *xs = (const uint8_t *)d_x;
+    if (g.large) return GPBC_LAUNCH(k_fr_lagrange_basis_long, grid, BLOCK, (hipStream_t)stream, s, set_step, nd, node_step, xs, x_step, k, g, (uint8_t *)d_out);
+    return GPBC_LAUNCH(k_fr_lagrange_basis, grid, BLOCK, (hipStream_t)stream, s, set_step, nd, node_step, xs, x_step, k, g, (uint8_t *)d_out);
+}
+// Host-pointer form: the unit is a row; a shard needs about 2^16 factors to pay for its thread and transfers.  A set, a node list or
+// an x given once travels whole to every shard.
+int gpbc_fr_lagrange_basis(const void *set, size_t n_set_rows, size_t B, const void *nodes, size_t n_node_rows, size_t m, const void *x, size_t nx, size_t k, void *out) {
+    TRY(lagrange_args(set, n_set_rows, B, nodes, n_node_rows, m, x, nx, k, out));
+    if (!k) return GPBC_OK;
+    const bool one_set = n_set_rows == 1, one_nodes = nodes && n_node_rows == 1, one_x = x && nx == 1;
+    const size_t per_row = B * m, shard_min = ((size_t)1 << 16) / per_row;
+    HostCall c = HostCall().input(set, B * GPBC_SCALAR_BYTES, one_set).input(nodes, m * GPBC_SCALAR_BYTES, one_nodes).input(x, GPBC_SCALAR_BYTES, one_x);
+    return host_call_sharded(k, shard_min ? shard_min : 1, c.output(out, m * GPBC_SCALAR_BYTES), HostRoute{},
+                             [=](const DevCols &d, size_t rows, hipStream_t st) {
+                                 return gpbc_fr_lagrange_basis_dev(d.in[0], one_set ? 1 : rows, B, d.in[1], one_nodes ? 1 : rows, m, d.in[2], d.in[2] ? (one_x ? 1 : rows) : 0, rows, d.out[0], st);
+                             });
 }
 
 }  // extern "C"

@@ -1,0 +1,225 @@
+"""Host-side planner for batched Sahai-Waters 2005 fuzzy identity-based decryption (fibe/sw05_fibe_common.go:284-333 and
+fibe/sw05_fibe_large_universe.go:244-291): one user key against a batch of ciphertexts, and computeT (sw05_fibe_large_universe.go:
+302-325) for many attributes at once.
+
+What is computed.  Per ciphertext, S = FindCommonAttributes(S_user, S_msg, d) (utils/find_common_attributes.go: the first d distinct
+attributes of the CIPHERTEXT's list that the key holds) and Delta_i = ComputeLagrangeBasis(i, S, 0) for i in S, then
+
+    small universe   M = e' / prod_i e(D_i, E_i)^Delta_i                  = e' / Pair([Delta_i] D_i ..., E_i ...)
+    large universe   M = e' * prod_i (e(d_i, E_i) / e(E'', D_i))^Delta_i  = e' * Pair([Delta_i] d_i ..., [-Delta_i] E'' ...; E_i ..., D_i ...)
+
+The exponent folds in front of the pairing exactly — e(P, Q)^k = e([k] P, Q) as Fp12 elements, the argument lw11.py makes for its
+weights — so a ciphertext costs one multi-pairing segment (one final exponentiation) and no GT exponentiation.  S differs from
+ciphertext to ciphertext, so unlike the coefficients of bsw07.py and lw11.py (one policy for the whole batch, host integers) the
+Delta_i are per item: engine.fr_lagrange_basis makes them on the device, n rows of d at a time, and they go into
+engine.g1_scalar_mul as they are.
+
+Host orchestration only, engine-agnostic (every function takes the engine: `bn254`, or a stand-in with the same function names).
+Host arrays in give host arrays out; CUDA tensors in give CUDA tensors out, with only the key, the selected attribute values and
+index tables going to the device.  Every ciphertext of a batch carries the same number of attributes."""
+import numpy as np
+
+R_ORDER = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+
+
+def _is_torch(x):
+    return type(x).__module__.startswith("torch")
+
+
+def _scalar_rows(values):
+    """attribute values -> scalar rows (the values of a batch repeat: each distinct one is converted once)"""
+    cache = {}
+
+    def row(v):
+        b = cache.get(v)
+        if b is None:
+            b = cache[v] = (int(v) % R_ORDER).to_bytes(32, "little")
+        return b
+    return np.frombuffer(b"".join([row(v) for v in values]), dtype=np.uint8).reshape(-1, 32).copy()      # writable: it may become a tensor
+
+
+def select_common(key_attrs, ct_attrs, d):
+    """FindCommonAttributes(S_user, S_msg, d) for every ciphertext: walk the ciphertext's list in order and keep the first d distinct
+    attributes (as field elements: modulo r) that the key holds.  Returns (key_pos [n, d], ct_pos [n, d], ok [n]): the positions of
+    the kept attributes in the key's list (its first occurrence) and in the ciphertext's list; ok = 0, and positions 0, where fewer
+    than d are common (the reference returns nil and Decrypt fails)."""
+    if d < 1:
+        raise ValueError("d must be at least 1 (got %s)" % d)
+    first = {}
+    for p, a in enumerate(key_attrs):
+        first.setdefault(int(a) % R_ORDER, p)
+    n = len(ct_attrs)
+    key_pos, ct_pos, ok = np.zeros((n, d), dtype=np.int64), np.zeros((n, d), dtype=np.int64), np.zeros(n, dtype=np.uint8)
+    get = first.get
+    for t, attrs in enumerate(ct_attrs):
+        seen, kp, cp = set(), [], []
+        for p, a in enumerate(attrs):
+            pos = get(a)
+            if pos is None:                                         # not there as it is written; as a field element?
+                a = int(a) % R_ORDER
+                pos = get(a)
+                if pos is None:
+                    continue
+            else:
+                a = int(a) % R_ORDER
+            if a not in seen:
+                seen.add(a)
+                kp.append(pos)
+                cp.append(p)
+                if len(kp) == d:
+                    break
+        if len(kp) == d:
+            key_pos[t], ct_pos[t], ok[t] = kp, cp, 1
+    return key_pos, ct_pos, ok
+
+
+class _Plan:
+    """what both decrypts share: the selection, the Lagrange coefficients of the decryptable ciphertexts and the gathers"""
+
+    def __init__(self, engine, key_attrs, d, ct_attrs, E, e_prime):
+        self.engine, self.d, self.n = engine, d, len(ct_attrs)
+        self.torch = _is_torch(E)
+        if _is_torch(e_prime) != self.torch:
+            raise ValueError("E and e_prime must both be CUDA tensors (or both host arrays)")
+        a = len(ct_attrs[0]) if self.n else 0
+        if any(len(c) != a for c in ct_attrs):
+            raise ValueError("every ciphertext of a batch needs the same number of attributes")
+        size = E.numel() if self.torch else np.asarray(E).size
+        if size != self.n * a * 128 or (e_prime.numel() if self.torch else np.asarray(e_prime).size) != self.n * 384:
+            raise ValueError("E must hold n x %d G2 points and e_prime n GT elements (n = %d)" % (a, self.n))
+        self.key_pos, self.ct_pos, self.ok = select_common(key_attrs, ct_attrs, d)
+        self.good = np.nonzero(self.ok)[0]
+        ng = self.ng = len(self.good)
+        self.E = E.reshape(self.n, a, 128) if self.torch else np.asarray(E, dtype=np.uint8).reshape(self.n, a, 128)
+        self.e_prime = e_prime.reshape(self.n, 384) if self.torch else np.asarray(e_prime, dtype=np.uint8).reshape(self.n, 384)
+        if not ng:
+            return
+        pos = self.ct_pos.tolist()
+        sets = _scalar_rows(ct_attrs[t][p] for t in self.good.tolist() for p in pos[t])
+        self.delta = engine.fr_lagrange_basis(self.put(sets).reshape(-1), d).reshape(ng * d, 32)           # x = 0, the nodes are the set
+        self.seg = lambda pairs: np.arange(0, pairs * ng + 1, pairs, dtype=np.uint64)
+
+    def put(self, a):
+        if not self.torch:
+            return a
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(a)).to(self.E.device)
+
+    def key_rows(self, comp, width):
+        """the key component at the selected positions: [ng, d, width]"""
+        return self.put(np.asarray(comp, dtype=np.uint8).reshape(-1, width)[self.key_pos[self.good].reshape(-1)]).reshape(self.ng, self.d, width)
+
+    def ct_rows(self):
+        """E_i of the selected attributes: [ng, d, 128]"""
+        if self.torch:
+            import torch
+            flat = torch.as_tensor((self.good[:, None] * self.E.shape[1] + self.ct_pos[self.good]).reshape(-1), dtype=torch.long, device=self.E.device)
+            return self.E.reshape(-1, 128).index_select(0, flat).reshape(self.ng, self.d, 128)
+        return self.E[self.good[:, None], self.ct_pos[self.good]]
+
+    def rows(self, a):
+        """the decryptable ciphertexts' rows of a per-ciphertext array"""
+        if self.torch:
+            import torch
+            return a.index_select(0, torch.as_tensor(self.good, dtype=torch.long, device=a.device)).contiguous()
+        return np.ascontiguousarray(a[self.good])
+
+    def scatter(self, msgs):
+        """messages of the decryptable ciphertexts into n rows; the others stay all zero"""
+        if self.torch:
+            import torch
+            out = torch.zeros((self.n, 384), dtype=torch.uint8, device=self.E.device)
+            if self.ng:
+                out[torch.as_tensor(self.good, dtype=torch.long, device=out.device)] = msgs.reshape(self.ng, 384)
+            return out, torch.from_numpy(self.ok.copy()).to(out.device)
+        out = np.zeros((self.n, 384), dtype=np.uint8)
+        if self.ng:
+            out[self.good] = np.asarray(msgs).reshape(self.ng, 384)
+        return out, self.ok.copy()
+
+
+def _flat(a):
+    return a.contiguous().reshape(-1) if _is_torch(a) else np.ascontiguousarray(a).reshape(-1)
+
+
+def _cat(parts, axis):
+    if _is_torch(parts[0]):
+        import torch
+        return torch.cat(parts, dim=axis)
+    return np.concatenate([np.asarray(p) for p in parts], axis=axis)
+
+
+def decrypt_batch(engine, key, d, ct_attrs, E, e_prime):
+    """Small universe.  key = (attrs, D): the key's attribute list and its components D_i = g1^(q(i) / t_i), [len(attrs), 64] host
+    bytes; ct_attrs: [n][a] attribute values (Python ints); E: [n, a, 128] the components E_i = T_i^s in the order of ct_attrs;
+    e_prime: [n, 384].  Returns (messages [n, 384], ok [n]); a ciphertext with fewer than d common attributes has ok = 0 and an
+    all-zero row, as the unmarshal entries do, and takes no part in the engine calls (fr_lagrange_basis, g1_scalar_mul,
+    multi_pair with one segment of d pairs per ciphertext, gt_div)."""
+    attrs, D = key
+    p = _Plan(engine, attrs, d, ct_attrs, E, e_prime)
+    if not p.ng:
+        return p.scatter(None)
+    P = engine.g1_scalar_mul(_flat(p.key_rows(D, 64)), _flat(p.delta))
+    den = engine.multi_pair(_flat(P), _flat(p.ct_rows()), p.seg(d))
+    return p.scatter(engine.gt_div(p.rows(p.e_prime), den))
+
+
+def decrypt_batch_large(engine, key, d, ct_attrs, E, e_pp, e_prime):
+    """Large universe.  key = (attrs, d_i [len(attrs), 64], D_i [len(attrs), 128]) with d_i = g1^r_i, D_i = g2^q(i) T_i^r_i; E as in
+    decrypt_batch; e_pp: [n, 64] the components E'' = g1^s; e_prime: [n, 384].  One segment of 2 d pairs per ciphertext,
+    ([Delta_i] d_i, E_i) ... ([-Delta_i] E'', D_i) ..., with -Delta from engine.fr_neg on the same scalars, then gt_mul.  (The form with
+    d + 1 pairs, which sums [Delta_i] D_i in G2 per ciphertext, is not built.)"""
+    attrs, di, Di = key
+    p = _Plan(engine, attrs, d, ct_attrs, E, e_prime)
+    if (e_pp.numel() if p.torch else np.asarray(e_pp).size) != p.n * 64 or _is_torch(e_pp) != p.torch:
+        raise ValueError("e_pp must hold n G1 points of the kind E is")
+    if not p.ng:
+        return p.scatter(None)
+    ng = p.ng
+    epp = p.rows(e_pp.reshape(p.n, 64) if p.torch else np.asarray(e_pp, dtype=np.uint8).reshape(p.n, 64)).reshape(ng, 1, 64)
+    epp = epp.expand(ng, d, 64) if p.torch else np.broadcast_to(epp, (ng, d, 64))
+    bases = _cat([p.key_rows(di, 64), epp], 1)                                             # [ng, 2 d, 64]
+    delta = p.delta.reshape(ng, d, 32)
+    scalars = _cat([delta, engine.fr_neg(_flat(delta)).reshape(ng, d, 32)], 1)
+    P = engine.g1_scalar_mul(_flat(bases), _flat(scalars))
+    Q = _cat([p.ct_rows(), p.key_rows(Di, 128)], 1)
+    return p.scatter(engine.gt_mul(p.rows(p.e_prime), engine.multi_pair(_flat(P), _flat(Q), p.seg(2 * d))))
+
+
+def compute_t(engine, table, n, xs, nodes=None):
+    """T_x = g2^(x^n) * prod_i t_i^Delta(node_i) for every attribute x of xs (computeT, sw05_fibe_large_universe.go:302-325): [k, 128].
+    table: a G2 FixedBase over [g2, t_0 ... t_n]; xs: k attribute values (Python ints, scalar rows, or a CUDA tensor of rows).
+    A row of scalars is [x^n, Delta_{x,N}(node_0) ... Delta_{x,N}(node_n)] over the ONE set N = {1 ... n+1}: fr_lagrange_basis with a
+    shared set, a shared node list and x per row; x^n by square-and-multiply in fr_mul calls; then one table.msm.
+
+    nodes defaults to the reference's own list, 0 ... n — NOT the set: its loop index is used as the node (:315-318), so node 0 lies
+    outside N and keeps all n + 1 factors, and the element n + 1 of N is never a node.  Keys and ciphertexts made with the paper's
+    nodes 1 ... n+1 do not interoperate with the reference's, which is why the nodes are an argument and not derived from the set."""
+    n = int(n)
+    if n < 1 or n + 1 > 1024:
+        raise ValueError("n must be in 1 .. 1023 (got %d)" % n)
+    nodes = list(range(n + 1)) if nodes is None else [int(v) for v in nodes]
+    if len(nodes) != n + 1 or table.nbase != n + 2:
+        raise ValueError("need n + 1 = %d nodes and a table of n + 2 bases" % (n + 1))
+    dev = _is_torch(xs)
+    if not dev:
+        xs = xs if isinstance(xs, np.ndarray) else _scalar_rows(xs)
+        xs = np.ascontiguousarray(xs, dtype=np.uint8)
+    xs = xs.reshape(-1, 32)
+    k = xs.shape[0]
+
+    def put(a):
+        if not dev:
+            return a
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(a)).to(xs.device)
+    flat = _flat(xs)
+    delta = engine.fr_lagrange_basis(put(_scalar_rows(range(1, n + 2))).reshape(-1), n + 1, put(_scalar_rows(nodes)).reshape(-1), n + 1, flat).reshape(k, n + 1, 32)
+    acc = engine.fr_mul(flat, put(_scalar_rows([1])).reshape(-1))                         # x, canonical
+    base = acc
+    for bit in bin(n)[3:]:
+        acc = engine.fr_mul(_flat(acc), _flat(acc))
+        if bit == "1":
+            acc = engine.fr_mul(_flat(acc), _flat(base))
+    scalars = _cat([acc.reshape(k, 1, 32), delta], 1)
+    return table.msm(_flat(scalars)).reshape(k, 128)

@@ -486,6 +486,64 @@ func FrPolyQuotients(coeffs, points []fr.Element, B, stride int) ([]fr.Element, 
 	return out, ok, frElements(kq, out)
 }
 
+// FrLagrangeBasis: out[j*m + t] = prod over the elements s of set row j with s != node t of row j of (x[j] - s) / (node - s) —
+// utils.ComputeLagrangeBasis for k rows whose node sets differ (fibe/sw05_fibe_common.go:316, fibe/sw05_fibe_large_universe.go:277 over
+// S = FindCommonAttributes(...); computeT, sw05_fibe_large_universe.go:302-325).  set: one row of B elements or k rows; nodes: nil =
+// the set's own elements, else one row of m or k rows; x: nil = evaluate at 0, else one element or k.
+func FrLagrangeBasis(set []fr.Element, B int, nodes []fr.Element, m int, x []fr.Element) ([]fr.Element, error) {
+	defer pin()()
+	if B < 1 || len(set) == 0 || len(set)%B != 0 {
+		return nil, errSizes
+	}
+	ns := len(set) / B
+	nn := ns
+	if nodes == nil {
+		m = B
+	} else if m < 1 || len(nodes) == 0 || len(nodes)%m != 0 {
+		return nil, errSizes
+	} else {
+		nn = len(nodes) / m
+	}
+	nx := len(x)
+	k := ns
+	if nn > k {
+		k = nn
+	}
+	if nx > k {
+		k = nx
+	}
+	if (ns != 1 && ns != k) || (nn != 1 && nn != k) || (nx > 1 && nx != k) {
+		return nil, errSizes
+	}
+	ks, err := frPlain(set)
+	if err != nil {
+		return nil, err
+	}
+	var pn, px unsafe.Pointer
+	if nodes != nil {
+		kn, err := frPlain(nodes)
+		if err != nil {
+			return nil, err
+		}
+		pn = unsafe.Pointer(unsafe.SliceData(kn))
+	}
+	if nx > 0 {
+		kx, err := frPlain(x)
+		if err != nil {
+			return nil, err
+		}
+		px = unsafe.Pointer(unsafe.SliceData(kx))
+	}
+	ko := make([][32]byte, k*m)
+	rc := C.gpbc_fr_lagrange_basis(unsafe.Pointer(unsafe.SliceData(ks)), C.size_t(ns), C.size_t(B), pn, C.size_t(nn), C.size_t(m), px, C.size_t(nx), C.size_t(k),
+		unsafe.Pointer(unsafe.SliceData(ko)))
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	out := make([]fr.Element, len(ko))
+	return out, frElements(ko, out)
+}
+
 // g1GroupOp: Add (sub == false) or Sub over the batch (cgo cannot take a C function as a value, hence the flag)
 func g1GroupOp(sub bool, out, a, b []bn254.G1Affine) ([]bn254.G1Affine, error) {
 	defer pin()()

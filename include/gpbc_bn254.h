@@ -385,6 +385,21 @@ int gpbc_fr_poly_from_roots(const void *roots, size_t B, size_t k, void *coeffs_
 int gpbc_fr_poly_quotients(const void *coeffs, const void *points, size_t B, size_t k, size_t stride, void *q_out, uint8_t *ok_out);
 int gpbc_fr_poly_from_roots_dev(const void *d_roots, size_t B, size_t k, void *d_coeffs_out, void *stream);
 int gpbc_fr_poly_quotients_dev(const void *d_coeffs, const void *d_points, size_t B, size_t k, size_t stride, void *d_q_out, uint8_t *d_ok_out, void *stream);
+/* Lagrange basis, k rows per call (utils.ComputeLagrangeBasis where its node set differs from item to item: once per common
+ * attribute in fibe/sw05_fibe_common.go:316 and fibe/sw05_fibe_large_universe.go:277, over S = FindCommonAttributes(...) of :295 / :246;
+ * and the basis over N = {1 .. n+1} at an attribute in computeT, sw05_fibe_large_universe.go:302-325):
+ *   out[j][t] = prod over u < B with set[j][u] != nodes[j][t] (mod r) of (x[j] - set[j][u]) / (nodes[j][t] - set[j][u])
+ * A set element is skipped when it equals the node BY VALUE modulo r (1 and r + 1 are equal), so no denominator is 0: the function
+ * is total and has no ok output.  A repeated set element gives one factor per occurrence, an empty product is 1, x equal to a set
+ * element other than the node gives 0.  The outputs of a lane's group of 4 share one field inversion.
+ *   set: n_set_rows x B scalars;  nodes: n_node_rows x m scalars, or NULL = the set's own elements (then m must equal B and row j's
+ *   nodes are row j's set);  x: nx scalars, or NULL with nx == 0 = evaluate at 0 (decryption);  out: k x m scalars, overlapping no input.
+ * n_set_rows and n_node_rows are 1 (one list for every row) or k; nx is 0, 1 or k; 1 <= B, m <= 1024; k < 2^29.  Anything else is
+ * GPBC_ERR_INVALID_ARG before any launch; k == 0 is a no-op.  One launch, no workspace; the _dev form is stream-ordered and not
+ * synchronised. */
+int gpbc_fr_lagrange_basis(const void *set, size_t n_set_rows, size_t B, const void *nodes, size_t n_node_rows, size_t m, const void *x, size_t nx, size_t k, void *out);
+int gpbc_fr_lagrange_basis_dev(const void *d_set, size_t n_set_rows, size_t B, const void *d_nodes, size_t n_node_rows, size_t m, const void *d_x, size_t nx, size_t k,
+                               void *d_out, void *stream);
 
 /* ---- per-kernel timing (measurement, bench.py) ---------------------------------------------------
  * Between begin and end every kernel launch of the pairing / scalar-multiplication entries made on `stream` is bracketed by

@@ -15,6 +15,7 @@
 // tests/cpp/ (reference is Go, see INTEGRATION.md for the cgo shim).
 #ifndef GPBC_BN254_HPP
 #define GPBC_BN254_HPP
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstring>
@@ -284,6 +285,19 @@ inline std::vector<Scalar> FrPolyQuotients(const std::vector<Scalar> &coeffs, co
     std::vector<Scalar> out(points.size() * stride);
     ok.assign(points.size(), 0);
     check(gpbc_fr_poly_quotients(coeffs.data(), points.data(), B, points.size() / B, stride, out.data(), ok.data()));
+    return out;
+}
+// Lagrange basis for k rows (utils.ComputeLagrangeBasis with a node set per item): out[j*m + t] = prod over the elements s of set row j with
+// s != node t of row j (mod r) of (x[j] - s) / (node - s).  set: one row of B or k rows; nodes: empty = the set's own elements, else one
+// row of m or k rows; x: empty = evaluate at 0, else one scalar or k.  k is the largest of the three row counts.
+inline std::vector<Scalar> FrLagrangeBasis(const std::vector<Scalar> &set, size_t B, const std::vector<Scalar> &nodes = {}, size_t m = 0, const std::vector<Scalar> &x = {}) {
+    if (B < 1 || set.empty() || set.size() % B) throw std::invalid_argument("need B set elements per row");
+    if (nodes.empty()) m = B;
+    else if (m < 1 || nodes.size() % m) throw std::invalid_argument("need m nodes per row");
+    const size_t ns = set.size() / B, nn = nodes.empty() ? ns : nodes.size() / m, nx = x.size(), k = std::max(ns, std::max(nn, nx));
+    if ((ns != 1 && ns != k) || (nn != 1 && nn != k) || (nx > 1 && nx != k)) throw std::invalid_argument("need one row or one row per output row");
+    std::vector<Scalar> out(k * m);
+    check(gpbc_fr_lagrange_basis(set.data(), ns, B, nodes.empty() ? nullptr : nodes.data(), nn, m, x.empty() ? nullptr : x.data(), nx, k, out.data()));
     return out;
 }
 // k products against ONE list of G2 points (a decryption key against k ciphertexts): out[j] = Pair(P[j*m .. (j+1)*m), Q);

@@ -1,0 +1,118 @@
+"""SW05 fuzzy IBE batched decryption and computeT through the host planner gopairingbasedcryptography_amd/sw05.py, on the oracle
+engine (the same flow runs on the GPU engine in test_sw05_gpu.py): select_common against the reference's FindCommonAttributes rule,
+then small instances made by sw05_fixture.py from known secrets — both decrypts return the messages, byte-identical to the
+reference's loop written out with oracle calls (Pair, GT.Div, GT.Exp by Delta, the running product), and a ciphertext below the
+threshold gives ok = 0 and a zero row; compute_t against the fixture's exponent route."""
+import numpy as np
+import pytest
+
+import bn254_py as o
+from sw05_fixture import Instance, OracleEngine, OracleTable, find_common, kbytes, lagrange, sc, t_exponent
+from gopairingbasedcryptography_amd import sw05
+
+R = o.R
+
+
+def test_select_common_follows_the_reference_rule():
+    key = [7, 3, 11, 5, 3, R + 20]                                     # 3 twice: the first position counts; R + 20 is 20
+    cts = [[5, 9, 3, 7, 11],                                           # more than d = 3 common: the ciphertext's order, 5 3 7
+           [9, 3, 3, 8, 3 + R, 11, 7],                                 # repeats in the ciphertext (one of them only modulo r) are taken once
+           [11, 9, 8, 7, 3],                                           # exactly d
+           [11, 9, 8, 7, 4],                                           # d - 1
+           [20, 1, 2, 5, 7],                                           # 20 is in the key modulo r
+           [1, 2, 4, 6, 8]]                                            # nothing
+    kp, cp, ok = sw05.select_common(key, cts, 3)
+    assert ok.tolist() == [1, 1, 1, 0, 1, 0] and ok.dtype == np.uint8 and kp.shape == cp.shape == (6, 3)
+    assert kp[0].tolist() == [3, 1, 0] and cp[0].tolist() == [0, 2, 3]
+    assert kp[1].tolist() == [1, 2, 0] and cp[1].tolist() == [1, 5, 6]
+    assert kp[2].tolist() == [2, 0, 1] and cp[2].tolist() == [0, 3, 4]
+    assert kp[4].tolist() == [5, 3, 0] and cp[4].tolist() == [0, 3, 4]
+    assert not kp[3].any() and not cp[3].any() and not kp[5].any()
+    for t, c in enumerate(cts):                                        # the same through the Go function restated
+        S = find_common(key, c, 3)
+        assert (S is not None) == bool(ok[t])
+        if S is not None:
+            assert [c[p] % R for p in cp[t]] == S and [key[p] % R for p in kp[t]] == S
+    assert sw05.select_common(key, cts, 1)[2].tolist() == [1, 1, 1, 1, 1, 0]
+    assert sw05.select_common(key, cts, 4)[2].tolist() == [1, 0, 0, 0, 0, 0]
+    assert sw05.select_common(key, [], 2)[0].shape == (0, 2)
+    with pytest.raises(ValueError):
+        sw05.select_common(key, cts, 0)
+
+
+KEY = [4, 9, 2, sc("ka"), 17, R - 3]
+CTS = [[9, 30, 4, 17, 31], [31, 2, R - 3, sc("ka"), 9], [30, 31, 32, 4, 33], [17, 9, 9, 2, 4], [33, 32, 31, 30, 29]]
+
+
+def cts_for(d):
+    """four ciphertexts of five attributes: different common sets, one with exactly d - 1 common attributes (ciphertext 2 has one,
+    ciphertext 4 none)"""
+    return {1: [CTS[0], CTS[1], CTS[4], CTS[3]], 2: [CTS[0], CTS[1], CTS[2], CTS[3]], 3: [CTS[0], CTS[1], [30, 2, 32, 4, 33], CTS[3]]}[d]
+
+
+@pytest.mark.parametrize("large", [False, True])
+@pytest.mark.parametrize("d", [1, 2, 3])
+def test_decrypt_matches_the_reference_loop(oracle, d, large):
+    eng = OracleEngine(oracle)
+    cts = cts_for(d)
+    inst = Instance(eng, d, KEY, cts, n_univ=5 if large else None, tag="p%d" % d)
+    assert inst.decryptable() == [True, True, False, True]
+    calls = []
+    eng.multi_pair = lambda P, Q, off, f=eng.multi_pair: calls.append(("multi_pair", len(off) - 1, np.asarray(P).size // 64)) or f(P, Q, off)
+    eng.gt_exp = lambda *a: pytest.fail("no GT exponentiation in the planner")
+    if large:
+        out, ok = sw05.decrypt_batch_large(eng, inst.key, d, cts, inst.E, inst.e_pp, inst.e_prime)
+    else:
+        out, ok = sw05.decrypt_batch(eng, inst.key, d, cts, inst.E, inst.e_prime)
+    assert calls == [("multi_pair", 3, 3 * d * (2 if large else 1))]    # the ciphertext below the threshold takes no part
+    assert out.shape == (4, 384) and ok.tolist() == [1, 1, 0, 1] and not out[2].any()
+    del eng.gt_exp
+    for t in (0, 1, 3):
+        assert (out[t] == np.asarray(inst.msgs)[t]).all(), t
+        assert (out[t] == inst.reference_shaped_decrypt(oracle, t)).all(), t
+    assert inst.reference_shaped_decrypt(oracle, 2) is None
+
+
+def test_decrypt_with_nothing_decryptable(oracle):
+    eng = OracleEngine(oracle)
+    inst = Instance(eng, 2, KEY, [CTS[2], CTS[4]], tag="none")
+    eng.multi_pair = eng.g1_scalar_mul = eng.fr_lagrange_basis = lambda *a: pytest.fail("no engine call without a decryptable ciphertext")
+    out, ok = sw05.decrypt_batch(eng, inst.key, 2, inst.ct_attrs, inst.E, inst.e_prime)
+    assert ok.tolist() == [0, 0] and out.shape == (2, 384) and not out.any()
+    with pytest.raises(ValueError):
+        sw05.decrypt_batch(eng, inst.key, 2, [CTS[2], CTS[4][:4]], inst.E, inst.e_prime)      # ragged attribute lists
+    with pytest.raises(ValueError):
+        sw05.decrypt_batch(eng, inst.key, 2, inst.ct_attrs, inst.E[:1], inst.e_prime)
+
+
+@pytest.mark.parametrize("n", [1, 4])
+def test_compute_t_against_the_exponent_route(oracle, n):
+    """T_x for attributes outside and inside N = {1 .. n+1}, x = 0 and full-size values, with the reference's node list 0 .. n:
+    equal to [x^n + sum_j tau_j Delta_{x,N}(j)] g2"""
+    eng = OracleEngine(oracle)
+    inst = Instance(eng, 1, [1], [[1]], n_univ=n, tag="ct%d" % n)
+    xs = [0, 1, 2, n + 1, n + 2, 77, sc("x", n), R - 1]
+    table = OracleTable(oracle, inst.table_bases)
+    want = np.asarray(oracle.g2_scalar_mul(inst.g2, kbytes([t_exponent(inst.taus, n, x) for x in xs]))).reshape(-1, 128)
+    got = sw05.compute_t(eng, table, n, xs)
+    assert got.shape == (len(xs), 128) and (got == want).all()
+    assert (sw05.compute_t(eng, table, n, kbytes(xs).reshape(-1, 32)) == want).all()          # scalar rows in
+    # x in N with the reference's nodes: the basis is 0 at node 0 and an indicator on 1 .. n, so T_x = [x^n + tau_x] g2 (x <= n), [x^n] g2 (x = n + 1)
+    assert t_exponent(inst.taus, n, 1) == (1 + inst.taus[1]) % R and t_exponent(inst.taus, n, n + 1) == pow(n + 1, n, R)
+    # the paper's nodes 1 .. n+1 are another function: the nodes are an argument
+    paper = list(range(1, n + 2))
+    want_p = np.asarray(oracle.g2_scalar_mul(inst.g2, kbytes([t_exponent(inst.taus, n, x, paper) for x in xs]))).reshape(-1, 128)
+    got_p = sw05.compute_t(eng, table, n, xs, nodes=paper)
+    assert (got_p == want_p).all() and not (want_p[4] == want[4]).all()
+    with pytest.raises(ValueError):
+        sw05.compute_t(eng, table, n + 1, xs)                                                  # table of another n
+    with pytest.raises(ValueError):
+        sw05.compute_t(eng, table, n, xs, nodes=[0])
+
+
+def test_stand_in_lagrange_is_the_reference_loop():
+    eng = OracleEngine(None)
+    S = [3, 8, R + 3, 12]
+    got = eng.fr_lagrange_basis(kbytes(S), 4)
+    assert got.shape == (1, 4, 32)
+    assert [int.from_bytes(r.tobytes(), "little") for r in got[0]] == [lagrange(i, S, 0) for i in S]

@@ -7,6 +7,7 @@
 #ifndef GPBC_BOUNDS
 #define GPBC_BOUNDS
 #endif
+#include <algorithm>
 #include <cstring>
 #include <tuple>
 #include "../gopairingbasedcryptography_amd/csrc/curve29.hip.hpp"
@@ -145,6 +146,22 @@ template <class F, int K> static void group_host(int op, const uint8_t *A, const
 template <int K> static void fr_inverse_host(const uint8_t *A, size_t n, uint8_t *out) {
     const size_t T = (n + K - 1) / K;
     for (size_t t = 0; t < T; t++) fr_inverse_lane<K>(A, out, n, t, T);
+}
+// k_fr_lagrange_basis: the sets made canonical once (what the workgroup stages), then fr_lagrange_lane for every lane of every row
+// with the kernel's grouping (g = 0: FR_LAGRANGE_G outputs per lane at gi, gi + gpr, ...).  nodes null = the set's own elements,
+// x null = 0; n_set_rows / n_node_rows in {1, k}, nx in {0, 1, k}.
+template <int G> static void fr_lagrange_host(const uint8_t *set, size_t n_set_rows, size_t B, const uint8_t *nodes, size_t n_node_rows, size_t m, const uint8_t *x, size_t nx,
+                                              size_t k, uint8_t *out) {
+    const uint32_t gpr = (uint32_t)((m + G - 1) / G);
+    std::vector<Fr> ss(B);
+    for (size_t j = 0; j < k; j++) {
+        if (j == 0 || n_set_rows != 1)
+            for (size_t u = 0; u < B; u++) ss[u] = fr_lagrange_in(set + ((n_set_rows == 1 ? 0 : j) * B + u) * 32);
+        const Fr xc = x ? fr_lagrange_in(x + (nx == 1 ? 0 : j) * 32) : fr_zero();
+        const uint8_t *nd = nodes ? nodes + (n_node_rows == 1 ? 0 : j) * m * 32 : nullptr;
+        for (uint32_t gi = 0; gi < gpr; gi++)
+            fr_lagrange_lane<G>([&](uint32_t u) { return ss[u]; }, (uint32_t)B, nd, xc, (uint32_t)m, gi, gpr, out + j * m * 32);
+    }
 }
 extern "C" {
 
@@ -586,6 +603,61 @@ int hc_fr_poly_quotients(const uint8_t *coeffs, const uint8_t *points, size_t B,
             memset(row + (ok ? B * 32 : 0), 0, (stride - (ok ? B : 0)) * 32);
         }
     }
+    stats_flush();
+    return 0;
+}
+int hc_fr_lagrange_basis(const uint8_t *set, size_t n_set_rows, size_t B, const uint8_t *nodes, size_t n_node_rows, size_t m, const uint8_t *x, size_t nx, size_t k,
+                         uint8_t *out, int g) {
+    if (B < 1 || B > (size_t)FR_POLY_MAX_B || m < 1 || m > (size_t)FR_POLY_MAX_B) return -1;
+    if (k && ((n_set_rows != 1 && n_set_rows != k) || (nodes ? n_node_rows != 1 && n_node_rows != k : m != B) || (x ? nx != 1 && nx != k : nx != 0))) return -1;
+    switch (g ? g : FR_LAGRANGE_G) {
+        case 1: fr_lagrange_host<1>(set, n_set_rows, B, nodes, n_node_rows, m, x, nx, k, out); break;
+        case 4: fr_lagrange_host<4>(set, n_set_rows, B, nodes, n_node_rows, m, x, nx, k, out); break;
+        default: return -1;
+    }
+    stats_flush();
+    return 0;
+}
+int hc_fr_lagrange_g(void) { return FR_LAGRANGE_G; }
+// k_fr_lagrange_basis as it is LAUNCHED: the geometry, the staging and the lane mapping of fr29.hip.hpp, workgroup by workgroup, on a
+// stand-in for the LDS block that refuses a store outside the block or over another element and a load of anything but a whole
+// staged element.  geom_out: [gpr, rpb, bpr, large, workgroups, active lanes].  Returns -2 on such a refusal.
+int hc_fr_lagrange_launch(const uint8_t *set, size_t n_set_rows, size_t B, const uint8_t *nodes, size_t n_node_rows, size_t m, const uint8_t *x, size_t nx, size_t k,
+                          uint8_t *out, uint32_t *geom_out) {
+    if (B < 1 || B > (size_t)FR_POLY_MAX_B || m < 1 || m > (size_t)FR_POLY_MAX_B || !k) return -1;
+    if ((n_set_rows != 1 && n_set_rows != k) || (nodes ? n_node_rows != 1 && n_node_rows != k : m != B) || (x ? nx != 1 && nx != k : nx != 0)) return -1;
+    const bool shared_set = n_set_rows == 1 && k > 1;
+    const LagrangeGeom g = fr_lagrange_geometry(B, m, shared_set);
+    const size_t set_step = shared_set ? 0 : B * 32, node_step = nodes && n_node_rows == k && k > 1 ? m * 32 : 0, x_step = x && nx == k && k > 1 ? 32 : 0;
+    const size_t words = (size_t)(g.large ? FR_LAG_LARGE : FR_LAG_SMALL) * NL + FR_LAG_WAVE, grid = fr_lagrange_grid(g, k);
+    std::vector<Fr> lds(words);
+    std::vector<int64_t> owner(words);
+    bool bad = false;
+    uint32_t active = 0;
+    for (size_t block = 0; block < grid; block++) {
+        std::fill(owner.begin(), owner.end(), -1);
+        for (uint32_t lane = 0; lane < FR_LAG_WAVE; lane++)
+            fr_lagrange_stage(g, (uint32_t)block, lane, k, set, set_step, [&](uint32_t off, const Fr &v) {
+                if ((size_t)off + NL > words) { bad = true; return; }
+                for (int i = 0; i < NL; i++) { if (owner[off + i] != -1) bad = true; owner[off + i] = off; }
+                lds[off] = v;
+            });
+        for (uint32_t lane = 0; lane < FR_LAG_WAVE && !bad; lane++) {
+            const LagrangeLane l = fr_lagrange_map(g, (uint32_t)block, lane, k);
+            if (!l.active) continue;
+            if (l.row >= k) { bad = true; break; }
+            active++;
+            const uint32_t mine = set_step ? l.lr * fr_lagrange_pitch(g) : 0u;
+            const Fr xc = x ? fr_lagrange_in(x + l.row * x_step) : fr_zero();
+            fr_lagrange_lane<FR_LAGRANGE_G>([&](uint32_t u) {
+                const size_t off = mine + (size_t)u * NL;
+                if (off + NL > words || owner[off] != (int64_t)off) { bad = true; return fr_zero(); }
+                return lds[off];
+            }, g.B, nodes ? nodes + l.row * node_step : nullptr, xc, g.m, l.gi, g.gpr, out + l.row * g.m * 32);
+        }
+        if (bad) return -2;
+    }
+    if (geom_out) { geom_out[0] = g.gpr; geom_out[1] = g.rpb; geom_out[2] = g.bpr; geom_out[3] = g.large; geom_out[4] = (uint32_t)grid; geom_out[5] = active; }
     stats_flush();
     return 0;
 }
