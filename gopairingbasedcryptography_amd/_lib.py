@@ -36,7 +36,7 @@ EXPORTS = [
     "gpbc_fr_add_batch", "gpbc_fr_sub_batch", "gpbc_fr_mul_batch", "gpbc_fr_neg_batch", "gpbc_fr_inverse_batch", "gpbc_fr_from_mont_batch", "gpbc_fr_to_mont_batch",
     "gpbc_fr_add_batch_dev", "gpbc_fr_sub_batch_dev", "gpbc_fr_mul_batch_dev", "gpbc_fr_neg_batch_dev", "gpbc_fr_inverse_batch_dev", "gpbc_fr_from_mont_batch_dev",
     "gpbc_fr_to_mont_batch_dev", "gpbc_fr_poly_from_roots", "gpbc_fr_poly_quotients", "gpbc_fr_poly_from_roots_dev", "gpbc_fr_poly_quotients_dev",
-    "gpbc_fr_lagrange_basis", "gpbc_fr_lagrange_basis_dev",
+    "gpbc_fr_lagrange_basis", "gpbc_fr_lagrange_basis_dev", "gpbc_fr_lsss_weights", "gpbc_fr_lsss_weights_dev",
 ]
 
 _lib = None

@@ -737,6 +737,80 @@ def fr_lagrange_basis(set, B=None, nodes=None, m=None, x=None, out=None):
     return out
 
 
+FR_LSSS_MAX = 64
+
+
+def fr_lsss_weights(matrix, rows=None, cols=None, held=None, out=None, ok_out=None):
+    """(w [k, rows, 32], ok [k]): for k systems the weights with sum_x w[x] M[x] = (1, 0, ..., 0) modulo r over the rows x whose
+    byte in `held` is non-zero — FindLinearCombinationWeight with a policy per item (include/gpbc_bn254.h).  matrix: one
+    rows x cols matrix (shared by the k masks) or k of them, as nested Python ints ([rows][cols] or [n][rows][cols]; rows and cols
+    may then be omitted), a uint8 array or a CUDA tensor of 32-byte scalars; held: k x rows bytes (nested bools / ints, a uint8
+    array or a CUDA tensor).  The used rows are the greedy first basis of the held rows; every other weight is 0; ok = 0 and a
+    zero row where the held rows do not span the target.  Outputs are of the kind that went in (numpy, or CUDA tensors)."""
+    lib = _lib.load()
+    if held is None:
+        raise ValueError("held is required")
+    if not _is_torch(matrix) and not isinstance(matrix, (np.ndarray, bytes, bytearray)):
+        m3 = [list(r) for r in matrix]
+        if m3 and m3[0] and not isinstance(m3[0][0], (list, tuple)):
+            m3 = [m3]                                                        # one [rows][cols] matrix
+        m3 = [[list(r) for r in mat] for mat in m3]
+        rows = len(m3[0]) if m3 and rows is None else rows
+        cols = len(m3[0][0]) if m3 and m3[0] and cols is None else cols
+        if any(len(mat) != rows or any(len(r) != cols for r in mat) for mat in m3):
+            raise ValueError("matrix: every system needs %s rows of %s scalars" % (rows, cols))
+        matrix = [v for mat in m3 for r in mat for v in r]
+    for v, what in ((rows, "rows"), (cols, "cols")):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 1 <= int(v) <= FR_LSSS_MAX:
+            raise ValueError("%s must be in 1 .. %d (got %s)" % (what, FR_LSSS_MAX, v))
+    rows, cols = int(rows), int(cols)
+    per = rows * cols * SCALAR_BYTES
+    if _is_torch(matrix) != _is_torch(held):
+        raise ValueError("matrix and held must both be CUDA tensors (or both host buffers)")
+    if _is_torch(matrix):
+        if matrix.numel() == 0 or matrix.numel() % per or held.numel() % rows:
+            raise ValueError("matrix needs whole systems of %d x %d scalars and held %d bytes per system" % (rows, cols, rows))
+        nm, k = matrix.numel() // per, held.numel() // rows
+        if nm not in (1, k):
+            raise ValueError("need one matrix or one per mask (got %d matrices, %d masks)" % (nm, k))
+        specs = [(matrix, nm * per, "matrix"), (held, k * rows, "held")] + ([(out, k * rows * SCALAR_BYTES, "out")] if out is not None else []) + \
+                ([(ok_out, k, "ok_out")] if ok_out is not None else [])
+        _tchk_static(matrix, *specs)
+        _ensure_init()
+        import torch
+        if out is None:
+            out = torch.empty((k, rows, SCALAR_BYTES), dtype=torch.uint8, device=matrix.device)
+        if ok_out is None:
+            ok_out = torch.empty((k,), dtype=torch.uint8, device=matrix.device)
+        if k:
+            _tchk(matrix, *specs)
+            _lib.check(lib.gpbc_fr_lsss_weights_dev(_tptr(matrix), _sz(nm), _sz(rows), _sz(cols), _tptr(held), _sz(k), _tptr(out), _tptr(ok_out), _torch_stream()))
+        return out, ok_out
+    mb = fr_to_bytes(matrix)
+    if isinstance(held, np.ndarray):
+        if held.dtype not in (np.uint8, np.bool_):
+            raise ValueError("held must be uint8 or bool (got %s)" % held.dtype)
+        hb = np.ascontiguousarray(held).astype(np.uint8, copy=False).reshape(-1)
+    elif isinstance(held, (bytes, bytearray)):
+        hb = np.frombuffer(bytes(held), dtype=np.uint8)
+    else:
+        hrows = [list(h) for h in held]
+        if any(len(h) != rows for h in hrows):
+            raise ValueError("held: every mask needs %d entries" % rows)
+        hb = np.array([1 if v else 0 for h in hrows for v in h], dtype=np.uint8)
+    if mb.size == 0 or mb.size % per or hb.size % rows:
+        raise ValueError("matrix needs whole systems of %d x %d scalars and held %d bytes per system" % (rows, cols, rows))
+    nm, k = mb.size // per, hb.size // rows
+    if nm not in (1, k):
+        raise ValueError("need one matrix or one per mask (got %d matrices, %d masks)" % (nm, k))
+    out = _host_out(out, k * rows * SCALAR_BYTES, (k, rows, SCALAR_BYTES))
+    ok_out = _host_out(ok_out, k, (k,))
+    if k:
+        _ensure_init()
+        _lib.check(lib.gpbc_fr_lsss_weights(_ptr(mb), _sz(nm), _sz(rows), _sz(cols), _ptr(hb), _sz(k), _ptr(out), _ptr(ok_out)))
+    return out, ok_out
+
+
 _gen_tables = {}
 
 

@@ -117,6 +117,9 @@ GPBC_INLINE Fr fr_mul(const Fr &a, const Fr &b) { return fr_mul_core<false>(a, b
 GPBC_INLINE Fr fr_mul2(const Fr &a, const Fr &b, const Fr &c, const Fr &d) { return fr_mul_core<true>(a, b, c, d); }
 #endif
 GPBC_INLINE Fr fr_sqr(const Fr &a) { return fr_mul(a, a); }
+// the two-product form expanded in place: for a kernel whose one hot loop is this product (the leaf takes 36 limbs, four of them
+// through the stack)
+GPBC_INLINE Fr fr_mul2_inline(const Fr &a, const Fr &b, const Fr &c, const Fr &d) { return fr_mul_core<true>(a, b, c, d); }
 
 // [0, r), limbs in [0, 2^29) (limb 8 below 2^22), from a value in [-ADD r, (REPS + 1 - ADD) r): add ADD r while the carries are
 // propagated, then subtract r while that leaves no borrow, REPS times.  A product (fr_mul) needs <1, 2>.
@@ -457,6 +460,129 @@ GPBC_INLINE LagrangeLane fr_lagrange_map(const LagrangeGeom &g, uint32_t block, 
     return l;
 }
 GPBC_INLINE size_t fr_lagrange_grid(const LagrangeGeom &g, size_t k) { return (k + g.rpb - 1) / g.rpb * g.bpr; }
+
+// ------------------------------------------------------------------------------------------------ LSSS reconstruction weights
+// w with sum_x w_x M_x = (1, 0, ..., 0) over the rows x of an LSSS matrix that a key holds, one system per ciphertext:
+// FindLinearCombinationWeight of the reference (access/lsss/lewko_waters_lsss_matrix.go:167-429) as cpabe/waters11 Decrypt calls it
+// (waters11_cpabe.go:254).  The result is DEFINED, so that it is unique: the held rows in ascending order, a row is used iff its vector
+// is independent of the used rows before it (the greedy first basis), w is the one combination of the used rows that gives the target
+// and 0 everywhere else; ok = 0 and w = 0 when the target is not in their span.  That is lw11.reconstruction_weights spread over all
+// rows; it does not depend on which equation an elimination takes as pivot.
+//
+// Gauss-Jordan on the transposed augmented matrix: `cols` equations, one unknown per row of M and the right-hand side e_0 as
+// column `rows`.  A group of gw = max(rows + 1, cols) lanes owns one system, lane li of the group owns column li (rows = 64: the
+// right-hand side is a second column of lane 0, gw = 64); a wave holds spw = 64 / gw systems.  The columns live in LDS (the pivot
+// equation is indexed at run time): column j of local system ls at word ls x sys_words + j x pitch, equation i at + i x NL, pitch odd.
+// A row that is not held is staged as zeros and so never gets a pivot.
+//   step c (one per unknown, in ascending order): lane li < cols tests element (equation li, column c) for == 0 mod r exactly
+//   (canonical form: r itself and a lazily reduced multiple of r count as zero); the group's slice of the wave's ballot is the set
+//   of non-zero equations; the pivot is the lowest one not yet used (none: the row is dependent, weight 0).  Every OTHER non-zero
+//   equation i is eliminated fraction-free, a[i][j] <- (p a[i][j] - f_i a[pivot][j]) / 2^261, one fr_mul2 per element, no
+//   inversion; an equation with f_i == 0 is left as it is.  Scaling an equation scales its right-hand side alike, so neither the
+//   factor p nor the 2^-261 of the product changes the solution.  Nobody writes column c during the step (it holds the factors
+//   every lane reads); its owner zeroes it after a barrier, all but the pivot (fr_lsss_clear).
+//   finish: ok iff the right-hand side is 0 in every unused equation; a lane with a pivot returns rhs[pivot] / a[pivot][own column],
+//   one lane-parallel fr_inv per wave.
+// The lanes of a group branch alike; groups of one wave differ only in which equations their loops visit (no cross-lane operation
+// inside).  The ballots are taken with every lane present.
+constexpr int FR_LSSS_MAX = 64, FR_LSSS_WAVE = 64, FR_LSSS_NONE = 0xff;
+// LDS instances of the kernel (words of the block): 29 KB = three 16 x 16 systems, five workgroups per CU; 80 KB = one system up to
+// 46 x 46, two per CU; 146.5 KB = one 64 x 64 system, alone on its CU
+constexpr int FR_LSSS_WORDS_0 = 7424, FR_LSSS_WORDS_1 = 20480, FR_LSSS_WORDS_2 = (FR_LSSS_MAX + 1) * ((FR_LSSS_MAX * NL) | 1);
+GPBC_INLINE constexpr int fr_lsss_words(uint32_t level) { return level == 0 ? FR_LSSS_WORDS_0 : level == 1 ? FR_LSSS_WORDS_1 : FR_LSSS_WORDS_2; }
+struct LsssGeom { uint32_t rows, cols, gw, spw, pitch, sys_words, level; };
+struct LsssLane { size_t sys; uint32_t base, li, shift; bool active; };
+struct LsssState { uint64_t unused; uint32_t pivot; };
+inline LsssGeom fr_lsss_geometry(size_t rows, size_t cols) {
+    LsssGeom g;
+    g.rows = (uint32_t)rows; g.cols = (uint32_t)cols;
+    g.gw = (uint32_t)(rows + 1 > cols ? rows + 1 : cols);
+    if (g.gw > FR_LSSS_WAVE) g.gw = FR_LSSS_WAVE;
+    g.pitch = (g.cols * NL) | 1u;
+    g.sys_words = (g.rows + 1) * g.pitch;
+    g.spw = FR_LSSS_WAVE / g.gw;
+    g.level = g.sys_words <= (uint32_t)FR_LSSS_WORDS_0 ? 0 : g.sys_words <= (uint32_t)FR_LSSS_WORDS_1 ? 1 : 2;
+    if (g.spw * g.sys_words > (uint32_t)fr_lsss_words(g.level)) g.spw = (uint32_t)fr_lsss_words(g.level) / g.sys_words;      // >= 1
+    return g;
+}
+GPBC_INLINE size_t fr_lsss_grid(const LsssGeom &g, size_t k) { return (k + g.spw - 1) / g.spw; }
+GPBC_INLINE uint32_t fr_lsss_systems(const LsssGeom &g, uint32_t block, size_t k) {
+    const size_t left = k - (size_t)block * g.spw;
+    return left < g.spw ? (uint32_t)left : g.spw;
+}
+// a lane's share of the staging: put(word offset, value).  mat_step = 0: one matrix for every system.
+template <class Put> GPBC_INLINE void fr_lsss_stage(const LsssGeom &g, uint32_t block, uint32_t lane, size_t k, const uint8_t *matrix, size_t mat_step, const uint8_t *held, const Put &put) {
+    const size_t sys0 = (size_t)block * g.spw;
+    const uint32_t per = (g.rows + 1) * g.cols, total = fr_lsss_systems(g, block, k) * per;
+    for (uint32_t idx = lane; idx < total; idx += FR_LSSS_WAVE) {
+        const uint32_t ls = idx / per, j = (idx % per) / g.cols, i = idx % g.cols;
+        Fr v = fr_zero();
+        if (j == g.rows) { if (i == 0) v = fr_plain_one(); }
+        else if (held[(sys0 + ls) * g.rows + j]) v = fr_lagrange_in(matrix + (sys0 + ls) * mat_step + 32 * ((size_t)j * g.cols + i));
+        put(ls * g.sys_words + j * g.pitch + i * NL, v);
+    }
+}
+GPBC_INLINE LsssLane fr_lsss_map(const LsssGeom &g, uint32_t block, uint32_t lane, size_t k) {
+    LsssLane l;
+    const uint32_t ls = lane / g.gw;
+    l.li = lane % g.gw;
+    l.shift = ls * g.gw;
+    l.base = ls * g.sys_words;
+    l.sys = (size_t)block * g.spw + ls;
+    l.active = ls < fr_lsss_systems(g, block, k);
+    if (!l.active) { l.base = 0; l.shift = 0; }
+    return l;
+}
+GPBC_INLINE LsssState fr_lsss_begin(const LsssGeom &g) {
+    LsssState s;
+    s.unused = g.cols == 64 ? ~(uint64_t)0 : (((uint64_t)1 << g.cols) - 1);
+    s.pivot = FR_LSSS_NONE;
+    return s;
+}
+// the lane's ballot bit: element (equation li, column col) of its system is not 0 modulo r
+template <class Get> GPBC_INLINE bool fr_lsss_nonzero(const LsssGeom &g, const LsssLane &l, uint32_t col, const Get &get) {
+    if (!l.active || l.li >= g.cols) return false;
+    return !fr_limbs_zero(fr_canonical<1, 2>(get(l.base + col * g.pitch + l.li * NL)));
+}
+GPBC_INLINE uint32_t fr_lsss_ctz(uint64_t v) { return (uint32_t)__builtin_ctzll(v); }       // v != 0
+template <class Get, class Put> GPBC_INLINE void fr_lsss_step(const LsssGeom &g, const LsssLane &l, uint32_t c, uint64_t ballot, LsssState &s, const Get &get, const Put &put) {
+    const uint64_t all = g.cols == 64 ? ~(uint64_t)0 : (((uint64_t)1 << g.cols) - 1);
+    const uint64_t nz = (ballot >> l.shift) & all, cand = nz & s.unused;
+    if (!l.active || !cand) return;
+    const uint32_t p = fr_lsss_ctz(cand);
+    s.unused &= ~((uint64_t)1 << p);
+    if (l.li == c) s.pivot = p;
+    const uint32_t fcol = l.base + c * g.pitch;
+    const Fr pv = get(fcol + p * NL);
+    for (uint64_t el = nz & ~((uint64_t)1 << p); el; el &= el - 1) {
+        const uint32_t i = fr_lsss_ctz(el);
+        const Fr nf = fr_neg(get(fcol + i * NL));
+        for (uint32_t j = l.li; j <= g.rows; j += FR_LSSS_WAVE) {
+            if (j == c) continue;
+            const uint32_t cj = l.base + j * g.pitch;
+            put(cj + i * NL, fr_mul2_inline(pv, get(cj + i * NL), nf, get(cj + p * NL)));
+        }
+    }
+}
+// after the step, once every lane of the group has read its factors: the owner of column c leaves only the pivot in it
+template <class Put> GPBC_INLINE void fr_lsss_clear(const LsssGeom &g, const LsssLane &l, uint32_t c, const LsssState &s, const Put &put) {
+    if (!l.active || l.li != c || s.pivot == FR_LSSS_NONE) return;
+    for (uint32_t i = 0; i < g.cols; i++)
+        if (i != s.pivot) put(l.base + c * g.pitch + i * NL, fr_zero());
+}
+// ballot: fr_lsss_nonzero of the right-hand side (column `rows`)
+template <class Get> GPBC_INLINE void fr_lsss_finish(const LsssGeom &g, const LsssLane &l, uint64_t ballot, const LsssState &s, const Get &get, uint8_t *w_out, uint8_t *ok_out) {
+    const bool ok = l.active && !((ballot >> l.shift) & s.unused), mine = ok && l.li < g.rows && s.pivot != FR_LSSS_NONE;
+    Fr den = fr_one(), num = fr_zero();
+    if (mine) {
+        den = get(l.base + l.li * g.pitch + s.pivot * NL);
+        num = get(l.base + g.rows * g.pitch + s.pivot * NL);
+    }
+    const Fr w = fr_mul(num, fr_mul(fr_inv(den), fr_plain_one()));             // num x (2^522 / den / 2^261) / 2^261
+    if (!l.active) return;
+    if (l.li < g.rows) fr_store_canonical(w_out + 32 * (l.sys * g.rows + l.li), fr_canonical<1, 2>(w));
+    if (l.li == 0) ok_out[l.sys] = ok ? 1 : 0;
+}
 
 }  // namespace gpbc
 #endif

@@ -1,7 +1,7 @@
 // libgpbc_bn254.so, unit 7 of 7: the scalar field Fr on the device (csrc/fr29.hip.hpp) — elementwise add / sub / mul / neg /
 // inverse and the fr.Element conversions on the ABI's scalar format, the two polynomial kernels of the AFP25 / GWWW25 opening
-// proofs and the Lagrange basis over a node set per row (SW05 fuzzy IBE) — with their C-ABI entries (include/gpbc_bn254.h,
-// "scalar field").  gfx950 only.
+// proofs, the Lagrange basis over a node set per row (SW05 fuzzy IBE) and the LSSS reconstruction weights of a policy per
+// ciphertext (Waters11 CP-ABE) — with their C-ABI entries (include/gpbc_bn254.h, "scalar field").  gfx950 only.
 #include "gpbc_common.hpp"
 #include "fr29.hip.hpp"
 
@@ -161,6 +161,37 @@ __global__ void __launch_bounds__(BLOCK) k_fr_lagrange_basis_long(const uint8_t 
     fr_lagrange_kernel<FR_LAG_LARGE>(set, set_step, nodes, node_step, x, x_step, k, gm, out);
 }
 
+// ------------------------------------------------------------------------------------------------ LSSS reconstruction weights
+// w[t] with sum_x w[t][x] M_t[x] = (1, 0, ..., 0) over the held rows of system t: a batched Gauss-Jordan solve over Fr, one wave per
+// workgroup, spw = 64 / max(rows + 1, cols) systems per wave, a column of the transposed augmented matrix per lane, the columns in
+// LDS.  The arithmetic, the geometry, the staging and the lane mapping are fr29.hip.hpp's (fr_lsss_*), which the host harness runs
+// workgroup by workgroup; here are only the LDS block, the ballots and the barriers.  One barrier per unknown: after it the owner
+// of the pivot column clears it while everybody tests the next column, which the step before the barrier finished.  Three instances
+// by LDS block (fr_lsss_words): 29 KB (three 16 x 16 systems, five workgroups per CU), 80 KB and 146.5 KB (64 x 64, alone on its CU).
+static_assert(FR_LSSS_WAVE == BLOCK, "one wave per workgroup");
+template <int WORDS> __device__ __forceinline__ void fr_lsss_kernel(const uint8_t *__restrict__ matrix, size_t mat_step, const uint8_t *__restrict__ held, size_t k, LsssGeom gm,
+                                                                     uint8_t *__restrict__ w_out, uint8_t *__restrict__ ok_out) {
+    __shared__ int32_t ss[WORDS];
+    const auto get = [&](uint32_t off) { return lds_get(ss + off); };
+    const auto put = [&](uint32_t off, const Fr &v) { lds_put(ss + off, v); };
+    fr_lsss_stage(gm, blockIdx.x, threadIdx.x, k, matrix, mat_step, held, put);
+    __syncthreads();
+    const LsssLane l = fr_lsss_map(gm, blockIdx.x, threadIdx.x, k);
+    LsssState s = fr_lsss_begin(gm);
+    for (uint32_t c = 0; c < gm.rows; c++) {
+        const uint64_t nz = __ballot(fr_lsss_nonzero(gm, l, c, get));
+        fr_lsss_step(gm, l, c, nz, s, get, put);
+        __syncthreads();
+        fr_lsss_clear(gm, l, c, s, put);
+    }
+    const uint64_t nz = __ballot(fr_lsss_nonzero(gm, l, gm.rows, get));
+    fr_lsss_finish(gm, l, nz, s, get, w_out, ok_out);
+}
+#define GPBC_LSSS_ARGS const uint8_t *__restrict__ matrix, size_t mat_step, const uint8_t *__restrict__ held, size_t k, LsssGeom gm, uint8_t *__restrict__ w_out, uint8_t *__restrict__ ok_out
+__global__ void __launch_bounds__(BLOCK) k_fr_lsss_weights(GPBC_LSSS_ARGS) { fr_lsss_kernel<FR_LSSS_WORDS_0>(matrix, mat_step, held, k, gm, w_out, ok_out); }
+__global__ void __launch_bounds__(BLOCK) k_fr_lsss_weights_mid(GPBC_LSSS_ARGS) { fr_lsss_kernel<FR_LSSS_WORDS_1>(matrix, mat_step, held, k, gm, w_out, ok_out); }
+__global__ void __launch_bounds__(BLOCK) k_fr_lsss_weights_large(GPBC_LSSS_ARGS) { fr_lsss_kernel<FR_LSSS_WORDS_2>(matrix, mat_step, held, k, gm, w_out, ok_out); }
+
 extern "C" {
 
 // ------------------------------------------------------------------------------------------------ elementwise entries
@@ -309,6 +340,42 @@ int gpbc_fr_lagrange_basis(const void *set, size_t n_set_rows, size_t B, const v
                              [=](const DevCols &d, size_t rows, hipStream_t st) {
                                  return gpbc_fr_lagrange_basis_dev(d.in[0], one_set ? 1 : rows, B, d.in[1], one_nodes ? 1 : rows, m, d.in[2], d.in[2] ? (one_x ? 1 : rows) : 0, rows, d.out[0], st);
                              });
+}
+
+// ------------------------------------------------------------------------------------------------ LSSS weight entries
+static int lsss_args(const void *matrix, size_t n_matrices, size_t rows, size_t cols, const void *held, size_t k, const void *w_out, const void *ok_out) {
+    if (rows < 1 || rows > (size_t)FR_LSSS_MAX || cols < 1 || cols > (size_t)FR_LSSS_MAX)
+        return fail(GPBC_ERR_INVALID_ARG, "rows and cols must be in 1 .. %d (got rows = %zu, cols = %zu)", FR_LSSS_MAX, rows, cols);
+    if (k > (size_t)0x7fffffff / 4) return fail(GPBC_ERR_INVALID_ARG, "too many systems for one call (%zu)", k);
+    if (!k) return GPBC_OK;
+    if (n_matrices != 1 && n_matrices != k) return fail(GPBC_ERR_INVALID_ARG, "n_matrices must be 1 or k (got %zu, k = %zu)", n_matrices, k);
+    if (!matrix || !held || !w_out || !ok_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    const size_t mb = n_matrices * rows * cols * GPBC_SCALAR_BYTES, hb = k * rows, wb = k * rows * GPBC_SCALAR_BYTES;
+    if (overlap(w_out, wb, matrix, mb) || overlap(w_out, wb, held, hb) || overlap(ok_out, k, matrix, mb) || overlap(ok_out, k, held, hb) || overlap(w_out, wb, ok_out, k))
+        return fail(GPBC_ERR_INVALID_ARG, "an output overlaps an input or the other output");
+    return GPBC_OK;
+}
+int gpbc_fr_lsss_weights_dev(const void *d_matrix, size_t n_matrices, size_t rows, size_t cols, const uint8_t *d_held, size_t k, void *d_w_out, uint8_t *d_ok_out, void *stream) {
+    TRY(lsss_args(d_matrix, n_matrices, rows, cols, d_held, k, d_w_out, d_ok_out));
+    if (!k) return GPBC_OK;
+    TRY(bind_device());
+    const LsssGeom g = fr_lsss_geometry(rows, cols);
+    const unsigned grid = (unsigned)fr_lsss_grid(g, k);
+    const size_t mat_step = n_matrices == 1 && k > 1 ? 0 : rows * cols * GPBC_SCALAR_BYTES;
+    if (g.level == 2) return GPBC_LAUNCH(k_fr_lsss_weights_large, grid, BLOCK, (hipStream_t)stream, (const uint8_t *)d_matrix, mat_step, d_held, k, g, (uint8_t *)d_w_out, d_ok_out);
+    if (g.level == 1) return GPBC_LAUNCH(k_fr_lsss_weights_mid, grid, BLOCK, (hipStream_t)stream, (const uint8_t *)d_matrix, mat_step, d_held, k, g, (uint8_t *)d_w_out, d_ok_out);
+    return GPBC_LAUNCH(k_fr_lsss_weights, grid, BLOCK, (hipStream_t)stream, (const uint8_t *)d_matrix, mat_step, d_held, k, g, (uint8_t *)d_w_out, d_ok_out);
+}
+// Host-pointer form: the unit is a system; a shard needs about 2^16 elements to pay for its thread and transfers.  A matrix given
+// once travels whole to every shard.
+int gpbc_fr_lsss_weights(const void *matrix, size_t n_matrices, size_t rows, size_t cols, const uint8_t *held, size_t k, void *w_out, uint8_t *ok_out) {
+    TRY(lsss_args(matrix, n_matrices, rows, cols, held, k, w_out, ok_out));
+    if (!k) return GPBC_OK;
+    const bool one = n_matrices == 1;
+    const size_t shard_min = ((size_t)1 << 16) / (rows * cols);
+    HostCall c = HostCall().input(matrix, rows * cols * GPBC_SCALAR_BYTES, one).input(held, rows);
+    return host_call_sharded(k, shard_min ? shard_min : 1, c.output(w_out, rows * GPBC_SCALAR_BYTES).output(ok_out, 1), HostRoute{},
+                             [=](const DevCols &d, size_t m, hipStream_t st) { return gpbc_fr_lsss_weights_dev(d.in[0], one ? 1 : m, rows, cols, d.in[1], m, d.out[0], d.out[1], st); });
 }
 
 }  // extern "C"

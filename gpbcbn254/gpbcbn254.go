@@ -544,6 +544,39 @@ func FrLagrangeBasis(set []fr.Element, B int, nodes []fr.Element, m int, x []fr.
 	return out, frElements(ko, out)
 }
 
+// FrLsssWeights: for k systems the weights w with sum_x w[x] M[x] = (1, 0, ..., 0) over the rows the key holds —
+// FindLinearCombinationWeight (access/lsss/lewko_waters_lsss_matrix.go:167-429) where the matrix differs per item, as in the Decrypt of
+// cpabe/waters11 (waters11_cpabe.go:254) over a batch of ciphertexts.  matrix: one rows x cols matrix or k of them, row-major; held:
+// k x rows bytes, non-zero = held.  Returns k x rows weights (0 for a row that is not used) and k ok bytes (0: not satisfied, the row
+// of weights is zero).  The used rows are the greedy first basis of the held rows, see include/gpbc_bn254.h.
+func FrLsssWeights(matrix []fr.Element, rows, cols int, held []byte) ([]fr.Element, []byte, error) {
+	defer pin()()
+	if rows < 1 || cols < 1 || len(matrix) == 0 || len(matrix)%(rows*cols) != 0 || len(held)%rows != 0 {
+		return nil, nil, errSizes
+	}
+	nm := len(matrix) / (rows * cols)
+	k := len(held) / rows
+	if nm != 1 && nm != k {
+		return nil, nil, errSizes
+	}
+	if k == 0 {
+		return nil, nil, nil
+	}
+	km, err := frPlain(matrix)
+	if err != nil {
+		return nil, nil, err
+	}
+	kw := make([][32]byte, k*rows)
+	ok := make([]byte, k)
+	rc := C.gpbc_fr_lsss_weights(unsafe.Pointer(unsafe.SliceData(km)), C.size_t(nm), C.size_t(rows), C.size_t(cols), (*C.uint8_t)(unsafe.SliceData(held)), C.size_t(k),
+		unsafe.Pointer(unsafe.SliceData(kw)), (*C.uint8_t)(unsafe.SliceData(ok)))
+	if err := status(rc); err != nil {
+		return nil, nil, err
+	}
+	out := make([]fr.Element, len(kw))
+	return out, ok, frElements(kw, out)
+}
+
 // g1GroupOp: Add (sub == false) or Sub over the batch (cgo cannot take a C function as a value, hence the flag)
 func g1GroupOp(sub bool, out, a, b []bn254.G1Affine) ([]bn254.G1Affine, error) {
 	defer pin()()

@@ -400,6 +400,23 @@ int gpbc_fr_poly_quotients_dev(const void *d_coeffs, const void *d_points, size_
 int gpbc_fr_lagrange_basis(const void *set, size_t n_set_rows, size_t B, const void *nodes, size_t n_node_rows, size_t m, const void *x, size_t nx, size_t k, void *out);
 int gpbc_fr_lagrange_basis_dev(const void *d_set, size_t n_set_rows, size_t B, const void *d_nodes, size_t n_node_rows, size_t m, const void *d_x, size_t nx, size_t k,
                                void *d_out, void *stream);
+/* LSSS reconstruction weights, k systems per call (FindLinearCombinationWeight, access/lsss/lewko_waters_lsss_matrix.go:167-429, where
+ * the matrix differs from item to item: once per ciphertext in the ciphertext-policy Decrypt of cpabe/waters11, waters11_cpabe.go:254):
+ * weights w with  sum over the held rows x of w[x] M[x] = (1, 0, ..., 0)  modulo r.
+ *   matrix: n_matrices x rows x cols scalars, row x of a system is the share vector M[x]; n_matrices is 1 (one policy, k keys) or k (a
+ *   policy per item).  Entries may be any value below 2^256 and act as their residue (-1 arrives as r - 1).
+ *   held: k x rows bytes, non-zero = the key holds rho(x).   w_out: k x rows canonical scalars.   ok_out: k bytes.
+ * The result is defined so that it is unique.  Take the held rows in ascending order; a held row is USED iff its vector is linearly
+ * independent of the used rows before it (the greedy first basis).  If (1, 0, ..., 0) is in the span of the used rows, ok = 1 and w is
+ * the one combination of the used rows that gives it; every other entry of the row of w_out is 0 (rows not held, dependent rows,
+ * padding rows of zeros).  Otherwise — no held row at all included — ok = 0 and the whole row of w_out is 0.  This does not depend on
+ * which equation the elimination picks as pivot.  It is not necessarily the particular solution the reference's back-substitution
+ * lands on: any valid weights decrypt to the same message, and the planners (lw11.py, waters11.py) follow the scheme here.
+ * 1 <= rows, cols <= 64; k < 2^29; the outputs overlap no input and not each other.  Anything else is GPBC_ERR_INVALID_ARG before any
+ * launch; k == 0 is a no-op.  One launch, no workspace; the _dev form is stream-ordered and not synchronised. */
+int gpbc_fr_lsss_weights(const void *matrix, size_t n_matrices, size_t rows, size_t cols, const uint8_t *held, size_t k, void *w_out, uint8_t *ok_out);
+int gpbc_fr_lsss_weights_dev(const void *d_matrix, size_t n_matrices, size_t rows, size_t cols, const uint8_t *d_held, size_t k, void *d_w_out, uint8_t *d_ok_out,
+                             void *stream);
 
 /* ---- per-kernel timing (measurement, bench.py) ---------------------------------------------------
  * Between begin and end every kernel launch of the pairing / scalar-multiplication entries made on `stream` is bracketed by

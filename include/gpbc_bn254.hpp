@@ -300,6 +300,18 @@ inline std::vector<Scalar> FrLagrangeBasis(const std::vector<Scalar> &set, size_
     check(gpbc_fr_lagrange_basis(set.data(), ns, B, nodes.empty() ? nullptr : nodes.data(), nn, m, x.empty() ? nullptr : x.data(), nx, k, out.data()));
     return out;
 }
+// LSSS reconstruction weights for k systems (FindLinearCombinationWeight with a matrix per item): matrix holds one rows x cols matrix or
+// k of them, held k x rows bytes (non-zero: the key holds the row's attribute).  Returns k x rows weights (0 where a row is not used)
+// and fills ok with k bytes (0: the held rows do not span (1, 0, ..., 0); that row of weights is then all zero).
+inline std::vector<Scalar> FrLsssWeights(const std::vector<Scalar> &matrix, size_t rows, size_t cols, const std::vector<uint8_t> &held, std::vector<uint8_t> &ok) {
+    if (rows < 1 || cols < 1 || matrix.empty() || matrix.size() % (rows * cols) || held.size() % rows) throw std::invalid_argument("need rows x cols scalars per matrix, rows bytes per mask");
+    const size_t nm = matrix.size() / (rows * cols), k = held.size() / rows;
+    if (nm != 1 && nm != k) throw std::invalid_argument("need one matrix or one per mask");
+    std::vector<Scalar> w(k * rows);
+    ok.assign(k, 0);
+    check(gpbc_fr_lsss_weights(matrix.data(), nm, rows, cols, held.data(), k, w.data(), ok.data()));
+    return w;
+}
 // k products against ONE list of G2 points (a decryption key against k ciphertexts): out[j] = Pair(P[j*m .. (j+1)*m), Q);
 // the Miller lines of Q are computed once (gnark: PrecomputeLines / MillerLoopFixedQ)
 inline std::vector<GT> PairFixedQ(const std::vector<G1Affine> &P, const std::vector<G2Affine> &Q) {

@@ -163,6 +163,29 @@ template <int G> static void fr_lagrange_host(const uint8_t *set, size_t n_set_r
             fr_lagrange_lane<G>([&](uint32_t u) { return ss[u]; }, (uint32_t)B, nd, xc, (uint32_t)m, gi, gpr, out + j * m * 32);
     }
 }
+// k_fr_lsss_weights, one workgroup: the staging, then per unknown the ballot of fr_lsss_nonzero over the 64 lanes, fr_lsss_step for
+// every lane, (the barrier,) fr_lsss_clear; the last ballot and fr_lsss_finish — the kernel's sequence with the lanes in turn.
+template <class Get, class Put> static void fr_lsss_block(const LsssGeom &g, uint32_t block, size_t k, const uint8_t *matrix, size_t mat_step, const uint8_t *held, const Get &get,
+                                                          const Put &put, uint8_t *w_out, uint8_t *ok_out, uint32_t *active) {
+    for (uint32_t lane = 0; lane < FR_LSSS_WAVE; lane++) fr_lsss_stage(g, block, lane, k, matrix, mat_step, held, put);
+    LsssLane l[FR_LSSS_WAVE];
+    LsssState st[FR_LSSS_WAVE];
+    for (uint32_t lane = 0; lane < FR_LSSS_WAVE; lane++) {
+        l[lane] = fr_lsss_map(g, block, lane, k);
+        st[lane] = fr_lsss_begin(g);
+        if (active && l[lane].active && l[lane].li < g.rows) ++*active;
+    }
+    for (uint32_t c = 0; c <= g.rows; c++) {
+        uint64_t nz = 0;
+        for (uint32_t lane = 0; lane < FR_LSSS_WAVE; lane++) nz |= (uint64_t)fr_lsss_nonzero(g, l[lane], c, get) << lane;
+        if (c == g.rows) {
+            for (uint32_t lane = 0; lane < FR_LSSS_WAVE; lane++) fr_lsss_finish(g, l[lane], nz, st[lane], get, w_out, ok_out);
+            break;
+        }
+        for (uint32_t lane = 0; lane < FR_LSSS_WAVE; lane++) fr_lsss_step(g, l[lane], c, nz, st[lane], get, put);
+        for (uint32_t lane = 0; lane < FR_LSSS_WAVE; lane++) fr_lsss_clear(g, l[lane], c, st[lane], put);
+    }
+}
 extern "C" {
 
 // one pairing per "wavefront": Miller loop and final exponentiation of the latency form (k_miller_wide / k_final_exp_wide)
@@ -658,6 +681,52 @@ int hc_fr_lagrange_launch(const uint8_t *set, size_t n_set_rows, size_t B, const
         if (bad) return -2;
     }
     if (geom_out) { geom_out[0] = g.gpr; geom_out[1] = g.rpb; geom_out[2] = g.bpr; geom_out[3] = g.large; geom_out[4] = (uint32_t)grid; geom_out[5] = active; }
+    stats_flush();
+    return 0;
+}
+static bool fr_lsss_bad_args(const void *matrix, size_t n_matrices, size_t rows, size_t cols, const void *held, size_t k) {
+    return rows < 1 || rows > (size_t)FR_LSSS_MAX || cols < 1 || cols > (size_t)FR_LSSS_MAX || !k || (n_matrices != 1 && n_matrices != k) || !matrix || !held;
+}
+// the lane functions on one system at a time (a wave of its own, whatever the launch would share)
+int hc_fr_lsss_weights(const uint8_t *matrix, size_t n_matrices, size_t rows, size_t cols, const uint8_t *held, size_t k, uint8_t *w_out, uint8_t *ok_out) {
+    if (fr_lsss_bad_args(matrix, n_matrices, rows, cols, held, k)) return -1;
+    LsssGeom g = fr_lsss_geometry(rows, cols);
+    g.spw = 1;
+    std::vector<Fr> lds(g.sys_words);
+    for (size_t t = 0; t < k; t++)
+        fr_lsss_block(g, 0, 1, matrix + (n_matrices == 1 ? 0 : t) * rows * cols * 32, 0, held + t * rows, [&](uint32_t off) { return lds[off]; },
+                      [&](uint32_t off, const Fr &v) { lds[off] = v; }, w_out + t * rows * 32, ok_out + t, nullptr);
+    stats_flush();
+    return 0;
+}
+// k_fr_lsss_weights as it is LAUNCHED: geometry, staging and lane mapping workgroup by workgroup on a stand-in for the LDS block of the
+// instance the launch would take, which refuses a store outside the block or across element boundaries and a load of anything but a
+// whole element stored before.  geom_out: [gw, spw, pitch, sys_words, LDS instance, workgroups, lanes that own a weight].  -2 on a refusal.
+int hc_fr_lsss_launch(const uint8_t *matrix, size_t n_matrices, size_t rows, size_t cols, const uint8_t *held, size_t k, uint8_t *w_out, uint8_t *ok_out, uint32_t *geom_out) {
+    if (fr_lsss_bad_args(matrix, n_matrices, rows, cols, held, k)) return -1;
+    const LsssGeom g = fr_lsss_geometry(rows, cols);
+    const size_t mat_step = n_matrices == 1 && k > 1 ? 0 : rows * cols * 32;
+    const size_t words = (size_t)fr_lsss_words(g.level), grid = fr_lsss_grid(g, k);
+    std::vector<Fr> lds(words);
+    std::vector<int64_t> owner(words);
+    bool bad = false;
+    uint32_t active = 0;
+    for (size_t block = 0; block < grid && !bad; block++) {
+        std::fill(owner.begin(), owner.end(), -1);
+        fr_lsss_block(g, (uint32_t)block, k, matrix, mat_step, held,
+                      [&](uint32_t off) {
+                          if ((size_t)off + NL > words || owner[off] != (int64_t)off) { bad = true; return fr_zero(); }
+                          return lds[off];
+                      },
+                      [&](uint32_t off, const Fr &v) {
+                          if ((size_t)off + NL > words) { bad = true; return; }
+                          for (int i = 0; i < NL; i++) { if (owner[off + i] != -1 && owner[off + i] != (int64_t)off) bad = true; owner[off + i] = off; }
+                          lds[off] = v;
+                      },
+                      w_out, ok_out, &active);
+    }
+    if (bad) return -2;
+    if (geom_out) { geom_out[0] = g.gw; geom_out[1] = g.spw; geom_out[2] = g.pitch; geom_out[3] = g.sys_words; geom_out[4] = g.level; geom_out[5] = (uint32_t)grid; geom_out[6] = active; }
     stats_flush();
     return 0;
 }
