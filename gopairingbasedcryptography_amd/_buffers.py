@@ -1,0 +1,135 @@
+"""Everything that differs between the two kinds of buffer the package takes: numpy uint8 arrays (host) and torch uint8 tensors
+(HBM-resident on the engine's side; the planners also run on CPU tensors over a stand-in engine).  bn254.py normalises its
+arguments and gets its outputs here, the scheme planners do their few array operations here; nothing else in the package asks
+which kind a buffer is.  Engine-agnostic: this module imports neither the C library nor bn254."""
+import numpy as np
+
+R_ORDER = 21888242871839275222246405745257275088548364400416034343698204186575808495617      # the order r of G1, G2 and GT
+
+
+def is_torch(x):
+    return type(x).__module__.startswith("torch")
+
+
+def device_of(*bufs):
+    """The kind of one call's buffers (None entries are skipped): None when all are host data, the tensors' one torch.device when
+    all are tensors.  Mixed kinds, or tensors on different devices, are a ValueError."""
+    host, tensors = False, []
+    for b in bufs:
+        if b is None:
+            continue
+        if isinstance(b, np.ndarray) or not is_torch(b):                      # arrays first: the common case, and the cheaper test
+            host = True
+        else:
+            tensors.append(b)
+    if not tensors:
+        return None
+    if host:
+        raise ValueError("the buffers of one call must all be CUDA tensors or all host buffers")
+    dev = tensors[0].device
+    if any(b.device != dev for b in tensors):
+        raise ValueError("the tensors of one call must be on one device (got %s)" % ", ".join(sorted({str(b.device) for b in tensors})))
+    return dev
+
+
+def nbytes(x):
+    """number of elements (= bytes, for the uint8 buffers used throughout) of a buffer of either kind"""
+    return x.numel() if is_torch(x) else np.asarray(x).size
+
+
+def rows(x, width, name="buffer"):
+    """(flat, n): an input as a flat contiguous uint8 buffer of n whole rows of `width` bytes.  Host data is converted (and copied
+    only if it has to be); a tensor is taken as it is, so it must already be contiguous uint8 — its raw address goes to a
+    kernel."""
+    if not isinstance(x, np.ndarray) and is_torch(x):
+        if str(x.dtype) != "torch.uint8" or not x.is_contiguous():
+            raise ValueError("%s must be a contiguous uint8 tensor" % name)
+        a, size = x.reshape(-1), x.numel()
+    else:
+        if isinstance(x, (bytes, bytearray)):
+            x = np.frombuffer(bytes(x), dtype=np.uint8)
+        a = np.ascontiguousarray(x, dtype=np.uint8).reshape(-1)
+        size = a.size
+    if size % width:
+        raise ValueError("%s: %d bytes are not a whole number of rows of %d" % (name, size, width))
+    return a, size // width
+
+
+def output(out, shape, dev, name="out"):
+    """The output of a call of kind `dev` (device_of): a new uint8 buffer of `shape`, or the caller's `out` after checking that it
+    can be written through its raw address — a writable contiguous uint8 array (host), a contiguous uint8 CUDA tensor on `dev`
+    (device), of exactly prod(shape) bytes.  A wrong size here would be an out-of-bounds write inside a kernel."""
+    if out is None and dev is None:
+        return np.empty(shape, dtype=np.uint8)
+    n = 1
+    for extent in shape:
+        n *= extent
+    if dev is None:
+        if not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"] and out.size == n):
+            raise ValueError("%s must be a writable contiguous uint8 array of %d bytes" % (name, n))
+        return out
+    if out is None:
+        import torch
+        return torch.empty(shape, dtype=torch.uint8, device=dev)
+    if device_of(out) is None or rows(out, 1, name)[1] != n:
+        raise ValueError("%s must be a contiguous uint8 CUDA tensor of %d bytes" % (name, n))
+    if out.device != dev:
+        raise ValueError("%s is on %s, expected %s" % (name, out.device, dev))
+    return out
+
+
+def address(x):
+    """raw address of a buffer that rows() or output() has passed; anything that is no buffer (a ctypes object) as it is"""
+    if isinstance(x, np.ndarray):
+        return x.ctypes.data
+    return x.data_ptr() if is_torch(x) else x
+
+
+# ------------------------------------------------------------------------------------------------ array operations of the planners
+def view(x, *shape):
+    """x as uint8 rows of `shape` (host data is converted, a tensor reshaped)"""
+    return x.reshape(*shape) if is_torch(x) else np.asarray(x, dtype=np.uint8).reshape(*shape)
+
+
+def copy(a):
+    return a.clone() if is_torch(a) else np.array(a, copy=True)
+
+
+def flat(a):
+    return a.contiguous().reshape(-1) if is_torch(a) else np.ascontiguousarray(a).reshape(-1)
+
+
+def cat(parts, axis=0):
+    if is_torch(parts[0]):
+        import torch
+        return torch.cat(list(parts), dim=axis)
+    return np.concatenate([np.asarray(p) for p in parts], axis=axis)
+
+
+def expand(a, *shape):
+    """broadcast without copying (flat() or cat() make the copy)"""
+    return a.expand(*shape) if is_torch(a) else np.broadcast_to(a, shape)
+
+
+def put(table, like):
+    """a host array as a buffer of the kind of `like`, on its device"""
+    if not is_torch(like):
+        return table
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(table)).to(like.device)
+
+
+def take(a, index, axis=0):
+    """the entries of `a` along `axis` at the host integer array `index`"""
+    index = np.asarray(index, dtype=np.int64)
+    return a.index_select(axis, put(index, a)) if is_torch(a) else np.take(a, index, axis=axis)
+
+
+def empty(shape, like):
+    return output(None, shape, like.device if is_torch(like) else None)
+
+
+def zeros(shape, like):
+    out = empty(shape, like)
+    out[...] = 0
+    return out

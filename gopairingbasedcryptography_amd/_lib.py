@@ -7,37 +7,57 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # GPBC_LIB_PATH: load another build of the same C ABI (kernel-tuning experiments); default is the in-tree library
 LIB_PATH = os.environ.get("GPBC_LIB_PATH") or os.path.join(HERE, "libgpbc_bn254.so")
 
-EXPORTS = [
-    "gpbc_init", "gpbc_init_devices", "gpbc_num_devices", "gpbc_device_at", "gpbc_set_device", "gpbc_get_device",
-    "gpbc_set_host_sharding", "gpbc_shutdown", "gpbc_last_error", "gpbc_device_count", "gpbc_abi_version",
-    "gpbc_comm_init_all", "gpbc_comm_get_unique_id", "gpbc_comm_init_rank", "gpbc_comm_ranks", "gpbc_comm_rank", "gpbc_comm_destroy",
-    "gpbc_allgather_dev", "gpbc_allgather_all_dev",
-    "gpbc_g1_scalar_mul_sum", "gpbc_g2_scalar_mul_sum", "gpbc_g1_scalar_mul_sum_dev", "gpbc_g2_scalar_mul_sum_dev", "gpbc_msm_stats",
-    "gpbc_pair_batch", "gpbc_pair_batch_dev", "gpbc_multi_pair", "gpbc_multi_pair_workspace_bytes",
-    "gpbc_multi_pair_dev", "gpbc_check_segments_dev", "gpbc_multi_pair_hostseg_dev", "gpbc_set_multi_pair_chunk", "gpbc_multi_pair_fixed_q", "gpbc_multi_pair_fixed_q_dev", "gpbc_pairing_check", "gpbc_miller_loop_dev", "gpbc_final_exp_dev",
-    "gpbc_miller_loop", "gpbc_final_exp",
-    "gpbc_g1_scalar_mul_batch", "gpbc_g1_scalar_mul_batch_dev", "gpbc_g2_scalar_mul_batch",
-    "gpbc_g2_scalar_mul_batch_dev", "gpbc_g1_sum", "gpbc_g2_sum", "gpbc_sum_workspace_bytes",
-    "gpbc_g1_sum_dev", "gpbc_g2_sum_dev",
-    "gpbc_gt_exp_batch", "gpbc_gt_exp_batch_dev", "gpbc_gt_multi_exp", "gpbc_gt_multi_exp_workspace_bytes", "gpbc_gt_multi_exp_dev", "gpbc_gt_mul_batch", "gpbc_gt_div_batch",
-    "gpbc_gt_inverse_batch", "gpbc_gt_mul_batch_dev", "gpbc_gt_div_batch_dev", "gpbc_gt_inverse_batch_dev",
-    "gpbc_fp_mul_batch", "gpbc_profile_begin", "gpbc_profile_end",
-    "gpbc_g1_marshal_batch", "gpbc_g2_marshal_batch", "gpbc_gt_marshal_batch",
-    "gpbc_g1_marshal_batch_dev", "gpbc_g2_marshal_batch_dev", "gpbc_gt_marshal_batch_dev",
-    "gpbc_g1_unmarshal_batch", "gpbc_g2_unmarshal_batch", "gpbc_gt_unmarshal_batch",
-    "gpbc_g1_unmarshal_batch_dev", "gpbc_g2_unmarshal_batch_dev", "gpbc_gt_unmarshal_batch_dev",
-    "gpbc_g1_map_to_curve_batch", "gpbc_g2_map_to_curve_batch",
-    "gpbc_g1_map_to_curve_batch_dev", "gpbc_g2_map_to_curve_batch_dev",
-    "gpbc_set_pipelined_miller", "gpbc_set_latency_path", "gpbc_debug_stale_table_once", "gpbc_valu_probe", "gpbc_release_workspaces", "gpbc_hash_to_g1", "gpbc_hash_to_g2", "gpbc_hash_to_field", "gpbc_hash_to_g1_dev", "gpbc_hash_to_g2_dev", "gpbc_hash_to_field_dev",
-    "gpbc_fixed_base_table_bytes", "gpbc_g1_fixed_base_create", "gpbc_g2_fixed_base_create", "gpbc_fixed_base_create_dev",
-    "gpbc_fixed_base_msm", "gpbc_fixed_base_msm_workspace_bytes", "gpbc_fixed_base_msm_dev", "gpbc_fixed_base_destroy",
-    "gpbc_g1_add_batch", "gpbc_g1_sub_batch", "gpbc_g1_double_batch", "gpbc_g2_add_batch", "gpbc_g2_sub_batch", "gpbc_g2_double_batch",
-    "gpbc_g1_add_batch_dev", "gpbc_g1_sub_batch_dev", "gpbc_g1_double_batch_dev", "gpbc_g2_add_batch_dev", "gpbc_g2_sub_batch_dev", "gpbc_g2_double_batch_dev",
-    "gpbc_fr_add_batch", "gpbc_fr_sub_batch", "gpbc_fr_mul_batch", "gpbc_fr_neg_batch", "gpbc_fr_inverse_batch", "gpbc_fr_from_mont_batch", "gpbc_fr_to_mont_batch",
-    "gpbc_fr_add_batch_dev", "gpbc_fr_sub_batch_dev", "gpbc_fr_mul_batch_dev", "gpbc_fr_neg_batch_dev", "gpbc_fr_inverse_batch_dev", "gpbc_fr_from_mont_batch_dev",
-    "gpbc_fr_to_mont_batch_dev", "gpbc_fr_poly_from_roots", "gpbc_fr_poly_quotients", "gpbc_fr_poly_from_roots_dev", "gpbc_fr_poly_quotients_dev",
-    "gpbc_fr_lagrange_basis", "gpbc_fr_lagrange_basis_dev", "gpbc_fr_lsss_weights", "gpbc_fr_lsss_weights_dev",
-]
+# The C signatures of include/gpbc_bn254.h, in its order: symbol -> "return kind : one kind per parameter".
+#   p  pointer (any C type with a `*`)    z  size_t    i  int    l  long    s  const char * (a return only)
+# load() declares every restype and argtypes from this table, so a Python int reaches a size_t or pointer parameter at its full
+# width and a value of the wrong kind is an ArgumentError at the call, not a truncated argument.  tests/test_abi.py holds the
+# table against the header's prototypes.
+SIGNATURES = {
+    "gpbc_init": "i:i", "gpbc_init_devices": "i:pi", "gpbc_num_devices": "i:", "gpbc_device_at": "i:i", "gpbc_set_device": "i:i",
+    "gpbc_get_device": "i:", "gpbc_set_host_sharding": "i:i", "gpbc_shutdown": "i:", "gpbc_release_workspaces": "i:",
+    "gpbc_last_error": "s:", "gpbc_device_count": "i:", "gpbc_abi_version": "i:", "gpbc_comm_init_all": "i:",
+    "gpbc_comm_get_unique_id": "i:p", "gpbc_comm_init_rank": "i:pii", "gpbc_comm_ranks": "i:", "gpbc_comm_rank": "i:",
+    "gpbc_comm_destroy": "i:", "gpbc_allgather_dev": "i:pzpp", "gpbc_allgather_all_dev": "i:pzpp", "gpbc_pair_batch": "i:ppzp",
+    "gpbc_pair_batch_dev": "i:ppzpp", "gpbc_multi_pair": "i:pppzp", "gpbc_multi_pair_workspace_bytes": "z:zz",
+    "gpbc_multi_pair_dev": "i:pppzzppzp", "gpbc_check_segments_dev": "i:pzzp", "gpbc_multi_pair_hostseg_dev": "i:pppzpp",
+    "gpbc_multi_pair_fixed_q": "i:ppzzp", "gpbc_multi_pair_fixed_q_dev": "i:ppzzpp", "gpbc_set_multi_pair_chunk": "i:i",
+    "gpbc_set_pipelined_miller": "i:i", "gpbc_set_latency_path": "i:l", "gpbc_debug_stale_table_once": "i:",
+    "gpbc_pairing_check": "i:pppzp", "gpbc_miller_loop_dev": "i:ppzpp", "gpbc_final_exp_dev": "i:pzpp",
+    "gpbc_miller_loop": "i:ppzp", "gpbc_final_exp": "i:pzp", "gpbc_g1_scalar_mul_batch": "i:pzpzp",
+    "gpbc_g1_scalar_mul_batch_dev": "i:pzpzpp", "gpbc_g2_scalar_mul_batch": "i:pzpzp", "gpbc_g2_scalar_mul_batch_dev": "i:pzpzpp",
+    "gpbc_g1_sum": "i:pzp", "gpbc_g2_sum": "i:pzp", "gpbc_sum_workspace_bytes": "z:zi", "gpbc_g1_sum_dev": "i:pzppzp",
+    "gpbc_g2_sum_dev": "i:pzppzp", "gpbc_g1_add_batch": "i:ppzzp", "gpbc_g1_sub_batch": "i:ppzzp", "gpbc_g1_double_batch": "i:pzp",
+    "gpbc_g2_add_batch": "i:ppzzp", "gpbc_g2_sub_batch": "i:ppzzp", "gpbc_g2_double_batch": "i:pzp",
+    "gpbc_g1_add_batch_dev": "i:ppzzpp", "gpbc_g1_sub_batch_dev": "i:ppzzpp", "gpbc_g1_double_batch_dev": "i:pzpp",
+    "gpbc_g2_add_batch_dev": "i:ppzzpp", "gpbc_g2_sub_batch_dev": "i:ppzzpp", "gpbc_g2_double_batch_dev": "i:pzpp",
+    "gpbc_g1_scalar_mul_sum": "i:ppzp", "gpbc_g2_scalar_mul_sum": "i:ppzp", "gpbc_g1_scalar_mul_sum_dev": "i:ppzpp",
+    "gpbc_g2_scalar_mul_sum_dev": "i:ppzpp", "gpbc_msm_stats": "i:pp", "gpbc_gt_exp_batch": "i:ppzp",
+    "gpbc_gt_exp_batch_dev": "i:ppzpp", "gpbc_gt_mul_batch": "i:ppzp", "gpbc_gt_div_batch": "i:ppzp",
+    "gpbc_gt_inverse_batch": "i:pzp", "gpbc_gt_mul_batch_dev": "i:ppzpp", "gpbc_gt_div_batch_dev": "i:ppzpp",
+    "gpbc_gt_inverse_batch_dev": "i:pzpp", "gpbc_gt_multi_exp": "i:ppzpzp", "gpbc_gt_multi_exp_workspace_bytes": "z:zz",
+    "gpbc_gt_multi_exp_dev": "i:ppzpzzppzp", "gpbc_fixed_base_table_bytes": "z:zi", "gpbc_g1_fixed_base_create": "i:pzp",
+    "gpbc_g2_fixed_base_create": "i:pzp", "gpbc_fixed_base_create_dev": "i:ipzpp", "gpbc_fixed_base_msm": "i:ppzp",
+    "gpbc_fixed_base_msm_workspace_bytes": "z:pz", "gpbc_fixed_base_msm_dev": "i:ppzppzp", "gpbc_fixed_base_destroy": "i:p",
+    "gpbc_g1_marshal_batch": "i:pzip", "gpbc_g2_marshal_batch": "i:pzip", "gpbc_gt_marshal_batch": "i:pzp",
+    "gpbc_g1_marshal_batch_dev": "i:pzipp", "gpbc_g2_marshal_batch_dev": "i:pzipp", "gpbc_gt_marshal_batch_dev": "i:pzpp",
+    "gpbc_g1_unmarshal_batch": "i:pzzpp", "gpbc_g2_unmarshal_batch": "i:pzzpp", "gpbc_gt_unmarshal_batch": "i:pzpp",
+    "gpbc_g1_unmarshal_batch_dev": "i:pzzppp", "gpbc_g2_unmarshal_batch_dev": "i:pzzppp", "gpbc_gt_unmarshal_batch_dev": "i:pzppp",
+    "gpbc_g1_map_to_curve_batch": "i:pzp", "gpbc_g2_map_to_curve_batch": "i:pzp", "gpbc_g1_map_to_curve_batch_dev": "i:pzpp",
+    "gpbc_g2_map_to_curve_batch_dev": "i:pzpp", "gpbc_hash_to_g1": "i:ppzpzp", "gpbc_hash_to_g2": "i:ppzpzp",
+    "gpbc_hash_to_field": "i:ppzpzip", "gpbc_hash_to_g1_dev": "i:ppzzpzpp", "gpbc_hash_to_g2_dev": "i:ppzzpzpp",
+    "gpbc_hash_to_field_dev": "i:ppzzpzipp", "gpbc_fr_add_batch": "i:ppzzp", "gpbc_fr_sub_batch": "i:ppzzp",
+    "gpbc_fr_mul_batch": "i:ppzzp", "gpbc_fr_neg_batch": "i:pzp", "gpbc_fr_inverse_batch": "i:pzp",
+    "gpbc_fr_from_mont_batch": "i:pzp", "gpbc_fr_to_mont_batch": "i:pzp", "gpbc_fr_add_batch_dev": "i:ppzzpp",
+    "gpbc_fr_sub_batch_dev": "i:ppzzpp", "gpbc_fr_mul_batch_dev": "i:ppzzpp", "gpbc_fr_neg_batch_dev": "i:pzpp",
+    "gpbc_fr_inverse_batch_dev": "i:pzpp", "gpbc_fr_from_mont_batch_dev": "i:pzpp", "gpbc_fr_to_mont_batch_dev": "i:pzpp",
+    "gpbc_fr_poly_from_roots": "i:pzzp", "gpbc_fr_poly_quotients": "i:ppzzzpp", "gpbc_fr_poly_from_roots_dev": "i:pzzpp",
+    "gpbc_fr_poly_quotients_dev": "i:ppzzzppp", "gpbc_fr_lagrange_basis": "i:pzzpzzpzzp",
+    "gpbc_fr_lagrange_basis_dev": "i:pzzpzzpzzpp", "gpbc_fr_lsss_weights": "i:pzzzpzpp", "gpbc_fr_lsss_weights_dev": "i:pzzzpzppp",
+    "gpbc_profile_begin": "i:p", "gpbc_profile_end": "i:pppip", "gpbc_valu_probe": "i:p", "gpbc_fp_mul_batch": "i:ppzp",
+}
+EXPORTS = list(SIGNATURES)
+# every pointer is a c_void_p: it takes ints, None, c_void_p, ctypes arrays, byref() and ndarray.ctypes.data_as() alike
+_CTYPES = {"p": ctypes.c_void_p, "z": ctypes.c_size_t, "i": ctypes.c_int, "l": ctypes.c_long, "s": ctypes.c_char_p}
 
 _lib = None
 
@@ -61,18 +81,11 @@ def load():
         except ImportError:
             pass
         lib = ctypes.CDLL(LIB_PATH)
-        lib.gpbc_last_error.restype = ctypes.c_char_p
-        lib.gpbc_multi_pair_workspace_bytes.restype = ctypes.c_size_t
-        lib.gpbc_multi_pair_workspace_bytes.argtypes = [ctypes.c_size_t, ctypes.c_size_t]
-        lib.gpbc_gt_multi_exp_workspace_bytes.restype = ctypes.c_size_t
-        lib.gpbc_gt_multi_exp_workspace_bytes.argtypes = [ctypes.c_size_t, ctypes.c_size_t]
-        lib.gpbc_sum_workspace_bytes.restype = ctypes.c_size_t
-        lib.gpbc_sum_workspace_bytes.argtypes = [ctypes.c_size_t, ctypes.c_int]
-        lib.gpbc_fixed_base_table_bytes.restype = ctypes.c_size_t
-        lib.gpbc_fixed_base_table_bytes.argtypes = [ctypes.c_size_t, ctypes.c_int]
-        lib.gpbc_fixed_base_msm_workspace_bytes.restype = ctypes.c_size_t
-        lib.gpbc_fixed_base_msm_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
-        lib.gpbc_set_latency_path.argtypes = [ctypes.c_long]
+        for name, sig in SIGNATURES.items():
+            ret, params = sig.split(":")
+            fn = getattr(lib, name)
+            fn.restype = _CTYPES[ret]
+            fn.argtypes = [_CTYPES[k] for k in params]
         _lib = lib
     return _lib
 

@@ -13,7 +13,8 @@ Host orchestration only; all group arithmetic goes through the engine (`bn254`).
 """
 import numpy as np
 
-R_ORDER = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+from . import _buffers as bufs
+from ._buffers import R_ORDER
 
 
 def poly_from_roots(roots):
@@ -104,17 +105,10 @@ def decrypt_batch_arrays(engine, D, pi, sk, C1, C2):
     digest D[i], its opening proof pi[i] and key sk[i] — m_i = C2_i / (e(D_i, C1_i[0]) e(pi_i, C1_i[1]) e(sk_i, C1_i[2]))
     (bibe/afp25_bibe/afp25_bibe.go:395-413): ONE multi-pairing of 3-pair segments and one gt_div, BASELINE config 5 at its
     stated size.  D, pi, sk: [n,64]; C1: [n,3,128]; C2: [n,384]."""
-    if type(D).__module__.startswith("torch"):
-        import torch
-        n = D.numel() // 64
-        P = torch.stack([D.reshape(n, 64), pi.reshape(n, 64), sk.reshape(n, 64)], dim=1).contiguous()
-        X = engine.multi_pair(P.reshape(-1), C1.reshape(-1).contiguous(), np.arange(0, 3 * n + 1, 3, dtype=np.uint64))
-        return engine.gt_div(C2.reshape(n, 384).contiguous(), X)
-    n = np.asarray(D).size // 64
-    P = np.stack([np.asarray(D, dtype=np.uint8).reshape(n, 64), np.asarray(pi, dtype=np.uint8).reshape(n, 64),
-                  np.asarray(sk, dtype=np.uint8).reshape(n, 64)], axis=1)
-    X = engine.multi_pair(P, np.asarray(C1, dtype=np.uint8).reshape(3 * n, 128), np.arange(0, 3 * n + 1, 3))
-    return engine.gt_div(np.asarray(C2, dtype=np.uint8).reshape(n, 384), X)
+    n = bufs.nbytes(D) // 64
+    P = bufs.cat([bufs.view(D, n, 1, 64), bufs.view(pi, n, 1, 64), bufs.view(sk, n, 1, 64)], 1)
+    X = engine.multi_pair(bufs.flat(P), bufs.flat(bufs.view(C1, 3 * n, 128)), np.arange(0, 3 * n + 1, 3, dtype=np.uint64))
+    return engine.gt_div(bufs.flat(C2).reshape(n, 384), X)
 
 
 # ----------------------------------------------------------------------------------------------- from identities and SRS
@@ -126,10 +120,6 @@ def decrypt_batch_arrays(engine, D, pi, sk, C1, C2):
 QUOTIENT_SCRATCH_BYTES = 256 << 20      # bound on the quotient rows held at once (k x B x (B + 1) x 32 bytes in all: 2.2 GB at 1024 x 256)
 
 
-def _is_torch(x):
-    return type(x).__module__.startswith("torch")
-
-
 def _identity_rows(engine, table, ids):
     """ids -> (flat scalar rows, k, B) with B = table.nbase - 1: [k][B] Python integers (host rows; the reference's rule that an
     identity occurs exactly once in its batch, afp25_bibe.go:371-381, is checked here), or k*B scalar rows as a uint8 array / CUDA
@@ -137,12 +127,12 @@ def _identity_rows(engine, table, ids):
     B = table.nbase - 1
     if B < 1:
         raise ValueError("the SRS table needs at least two bases (g1 and [tau]_1)")
-    if _is_torch(ids) or isinstance(ids, np.ndarray) and ids.dtype == np.uint8:
+    if bufs.is_torch(ids) or isinstance(ids, np.ndarray) and ids.dtype == np.uint8:
         flat = ids.reshape(-1)
-        n = (flat.numel() if _is_torch(ids) else flat.size) // 32
-        if n * 32 != (flat.numel() if _is_torch(ids) else flat.size) or n == 0 or n % B:
+        size = bufs.nbytes(flat)
+        if size % 32 or size == 0 or (size // 32) % B:
             raise ValueError("ids must hold a whole number of batches of B = %d identities (32 bytes each)" % B)
-        return flat, n // B, B
+        return flat, size // 32 // B, B
     rows = [[int(x) for x in r] for r in ids]
     if not rows or any(len(r) != B for r in rows):
         raise ValueError("ids must hold a whole number of batches of B = %d identities" % B)
@@ -171,14 +161,7 @@ def opening_proofs(engine, table, ids, coeffs=None):
     coeffs = coeffs.reshape(-1)
     per_batch = B * stride * 32
     chunk = min(k, max(1, QUOTIENT_SCRATCH_BYTES // per_batch))
-    if _is_torch(rows):
-        import torch
-        scratch = torch.empty(chunk * per_batch, dtype=torch.uint8, device=rows.device)
-        okbuf = torch.empty(chunk * B, dtype=torch.uint8, device=rows.device)
-        pi = torch.empty((k * B, 64), dtype=torch.uint8, device=rows.device)
-    else:
-        scratch, okbuf = np.empty(chunk * per_batch, dtype=np.uint8), np.empty(chunk * B, dtype=np.uint8)
-        pi = np.empty((k * B, 64), dtype=np.uint8)
+    scratch, okbuf, pi = bufs.empty((chunk * per_batch,), rows), bufs.empty((chunk * B,), rows), bufs.empty((k * B, 64), rows)
     for lo in range(0, k, chunk):
         m = min(chunk, k - lo)
         q, ok = engine.fr_poly_quotients(coeffs[lo * (B + 1) * 32:(lo + m) * (B + 1) * 32], rows[lo * B * 32:(lo + m) * B * 32], B, stride,
@@ -201,12 +184,10 @@ def decrypt_batches(engine, table, ids, sk, C1, C2, D=None):
     n = k * B
 
     def per_item(x, name):
-        size = x.numel() if _is_torch(x) else np.asarray(x).size
+        size = bufs.nbytes(x)
         if size == n * 64:
-            return x.reshape(n, 64)
+            return bufs.view(x, n, 64)
         if size != k * 64:
             raise ValueError("%s must hold one point per batch (%d) or per item (%d)" % (name, k, n))
-        if _is_torch(x):
-            return x.reshape(k, 1, 64).expand(k, B, 64).reshape(n, 64)
-        return np.repeat(np.asarray(x, dtype=np.uint8).reshape(k, 64), B, axis=0)
+        return bufs.expand(bufs.view(x, k, 1, 64), k, B, 64).reshape(n, 64)
     return decrypt_batch_arrays(engine, per_item(D, "D"), pi, per_item(sk, "sk"), C1, C2)

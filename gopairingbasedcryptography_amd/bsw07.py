@@ -20,7 +20,8 @@ reference's debug pairing / prints (access_tree_node.go:99-100,116-127).
 """
 import numpy as np
 
-R_ORDER = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+from . import _buffers as bufs
+from ._buffers import R_ORDER
 
 
 class Leaf:
@@ -131,13 +132,7 @@ def decrypt_batch_arrays(engine, folded, d_key, c_tilde, c, cy, cy_prime):
     leaf_ids, dj_hat, djp_hat = folded
     l = len(leaf_ids)
     q_list = np.concatenate([np.asarray(dj_hat).reshape(l, 128), np.asarray(djp_hat).reshape(l, 128), engine.g2_neg(d_key).reshape(1, 128)])
-    if type(c).__module__.startswith("torch"):
-        import torch
-        n = c.numel() // 64
-        P = torch.cat([cy.reshape(n, l, 64), cy_prime.reshape(n, l, 64), c.reshape(n, 1, 64)], dim=1).contiguous()
-        Q = torch.from_numpy(np.ascontiguousarray(q_list)).to(c.device)
-        return engine.gt_mul(c_tilde.reshape(n, 384).contiguous(), engine.multi_pair_fixed_q(P.reshape(-1), Q.reshape(-1)))
-    n = np.asarray(c).size // 64
-    P = np.concatenate([np.asarray(cy, dtype=np.uint8).reshape(n, l, 64), np.asarray(cy_prime, dtype=np.uint8).reshape(n, l, 64),
-                        np.asarray(c, dtype=np.uint8).reshape(n, 1, 64)], axis=1)
-    return engine.gt_mul(np.asarray(c_tilde, dtype=np.uint8).reshape(n, 384), engine.multi_pair_fixed_q(P, q_list))
+    n = bufs.nbytes(c) // 64
+    P = bufs.cat([bufs.view(cy, n, l, 64), bufs.view(cy_prime, n, l, 64), bufs.view(c, n, 1, 64)], 1)
+    X = engine.multi_pair_fixed_q(bufs.flat(P), bufs.flat(bufs.put(q_list, c)))
+    return engine.gt_mul(bufs.flat(c_tilde).reshape(n, 384), X)

@@ -25,7 +25,8 @@ Host orchestration only, engine-agnostic (every function takes the engine: `bn25
 the elimination is per policy, microseconds in Python integers, and stays on the host."""
 import numpy as np
 
-R_ORDER = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+from . import _buffers as bufs
+from ._buffers import R_ORDER
 
 
 def reconstruction_weights(matrix, rho, attributes):
@@ -89,23 +90,14 @@ def decrypt_batch(engine, folded, c0, c1, c2, c3):
     gt_mul + gt_div."""
     rows, weights, A, B = folded
     k = len(rows)
-    P_seg = np.concatenate([A, B]).reshape(2 * k, 64)
-    if type(c0).__module__.startswith("torch"):
-        import torch
-        n = c0.numel() // 384
-        R = c1.numel() // (n * 384)
-        idx = torch.as_tensor(rows, dtype=torch.long, device=c0.device)
-        g1 = c1.reshape(n, R, 384).index_select(1, idx).contiguous()
-        Q = torch.cat([c3.reshape(n, R, 128).index_select(1, idx), c2.reshape(n, R, 128).index_select(1, idx)], dim=1).contiguous()
-        P = torch.from_numpy(np.ascontiguousarray(P_seg)).to(c0.device).repeat(n, 1).contiguous()
-        E = engine.multi_pair(P.reshape(-1), Q.reshape(-1), np.arange(0, 2 * k * n + 1, 2 * k, dtype=np.uint64))
-        F = engine.gt_multi_exp(g1.reshape(-1), weights, np.arange(0, k * n + 1, k, dtype=np.uint64))
-        return engine.gt_div(c0.reshape(n, 384).contiguous(), engine.gt_mul(E, F))
-    c0 = np.asarray(c0, dtype=np.uint8).reshape(-1, 384)
-    n = c0.shape[0]
-    g1 = np.ascontiguousarray(np.asarray(c1, dtype=np.uint8).reshape(n, -1, 384)[:, rows, :])
-    Q = np.concatenate([np.asarray(c3, dtype=np.uint8).reshape(n, -1, 128)[:, rows, :], np.asarray(c2, dtype=np.uint8).reshape(n, -1, 128)[:, rows, :]], axis=1)
-    P = np.tile(P_seg, (n, 1))
-    E = engine.multi_pair(P.reshape(-1), np.ascontiguousarray(Q).reshape(-1), np.arange(0, 2 * k * n + 1, 2 * k, dtype=np.uint64))
-    F = engine.gt_multi_exp(g1.reshape(-1), weights, np.arange(0, k * n + 1, k, dtype=np.uint64))
-    return engine.gt_div(c0, engine.gt_mul(E, F))
+    bufs.device_of(c0, c1, c2, c3)                                           # one kind of buffer, one device
+    n = bufs.nbytes(c0) // 384
+
+    def used(c, width):
+        """the used rows of a per-row component: [n, k, width]"""
+        return bufs.take(bufs.view(c, n, -1, width), rows, 1)
+    P = bufs.expand(bufs.put(np.concatenate([A, B]).reshape(1, 2 * k, 64), c0), n, 2 * k, 64)
+    Q = bufs.cat([used(c3, 128), used(c2, 128)], 1)
+    E = engine.multi_pair(bufs.flat(P), bufs.flat(Q), np.arange(0, 2 * k * n + 1, 2 * k, dtype=np.uint64))
+    F = engine.gt_multi_exp(bufs.flat(used(c1, 384)), weights, np.arange(0, k * n + 1, k, dtype=np.uint64))
+    return engine.gt_div(bufs.flat(c0).reshape(n, 384), engine.gt_mul(E, F))

@@ -19,11 +19,8 @@ Host arrays in give host arrays out; CUDA tensors in give CUDA tensors out, with
 index tables going to the device.  Every ciphertext of a batch carries the same number of attributes."""
 import numpy as np
 
-R_ORDER = 21888242871839275222246405745257275088548364400416034343698204186575808495617
-
-
-def _is_torch(x):
-    return type(x).__module__.startswith("torch")
+from . import _buffers as bufs
+from ._buffers import R_ORDER
 
 
 def _scalar_rows(values):
@@ -78,20 +75,16 @@ class _Plan:
 
     def __init__(self, engine, key_attrs, d, ct_attrs, E, e_prime):
         self.engine, self.d, self.n = engine, d, len(ct_attrs)
-        self.torch = _is_torch(E)
-        if _is_torch(e_prime) != self.torch:
-            raise ValueError("E and e_prime must both be CUDA tensors (or both host arrays)")
+        bufs.device_of(E, e_prime)                                              # both of one kind, on one device
         a = len(ct_attrs[0]) if self.n else 0
         if any(len(c) != a for c in ct_attrs):
             raise ValueError("every ciphertext of a batch needs the same number of attributes")
-        size = E.numel() if self.torch else np.asarray(E).size
-        if size != self.n * a * 128 or (e_prime.numel() if self.torch else np.asarray(e_prime).size) != self.n * 384:
+        if bufs.nbytes(E) != self.n * a * 128 or bufs.nbytes(e_prime) != self.n * 384:
             raise ValueError("E must hold n x %d G2 points and e_prime n GT elements (n = %d)" % (a, self.n))
         self.key_pos, self.ct_pos, self.ok = select_common(key_attrs, ct_attrs, d)
         self.good = np.nonzero(self.ok)[0]
         ng = self.ng = len(self.good)
-        self.E = E.reshape(self.n, a, 128) if self.torch else np.asarray(E, dtype=np.uint8).reshape(self.n, a, 128)
-        self.e_prime = e_prime.reshape(self.n, 384) if self.torch else np.asarray(e_prime, dtype=np.uint8).reshape(self.n, 384)
+        self.E, self.e_prime = bufs.view(E, self.n, a, 128), bufs.view(e_prime, self.n, 384)
         if not ng:
             return
         pos = self.ct_pos.tolist()
@@ -100,10 +93,7 @@ class _Plan:
         self.seg = lambda pairs: np.arange(0, pairs * ng + 1, pairs, dtype=np.uint64)
 
     def put(self, a):
-        if not self.torch:
-            return a
-        import torch
-        return torch.from_numpy(np.ascontiguousarray(a)).to(self.E.device)
+        return bufs.put(a, self.E)
 
     def key_rows(self, comp, width):
         """the key component at the selected positions: [ng, d, width]"""
@@ -111,42 +101,19 @@ class _Plan:
 
     def ct_rows(self):
         """E_i of the selected attributes: [ng, d, 128]"""
-        if self.torch:
-            import torch
-            flat = torch.as_tensor((self.good[:, None] * self.E.shape[1] + self.ct_pos[self.good]).reshape(-1), dtype=torch.long, device=self.E.device)
-            return self.E.reshape(-1, 128).index_select(0, flat).reshape(self.ng, self.d, 128)
-        return self.E[self.good[:, None], self.ct_pos[self.good]]
+        index = (self.good[:, None] * self.E.shape[1] + self.ct_pos[self.good]).reshape(-1)
+        return bufs.take(self.E.reshape(-1, 128), index).reshape(self.ng, self.d, 128)
 
     def rows(self, a):
         """the decryptable ciphertexts' rows of a per-ciphertext array"""
-        if self.torch:
-            import torch
-            return a.index_select(0, torch.as_tensor(self.good, dtype=torch.long, device=a.device)).contiguous()
-        return np.ascontiguousarray(a[self.good])
+        return bufs.take(a, self.good)
 
     def scatter(self, msgs):
         """messages of the decryptable ciphertexts into n rows; the others stay all zero"""
-        if self.torch:
-            import torch
-            out = torch.zeros((self.n, 384), dtype=torch.uint8, device=self.E.device)
-            if self.ng:
-                out[torch.as_tensor(self.good, dtype=torch.long, device=out.device)] = msgs.reshape(self.ng, 384)
-            return out, torch.from_numpy(self.ok.copy()).to(out.device)
-        out = np.zeros((self.n, 384), dtype=np.uint8)
+        out = bufs.zeros((self.n, 384), self.E)
         if self.ng:
-            out[self.good] = np.asarray(msgs).reshape(self.ng, 384)
-        return out, self.ok.copy()
-
-
-def _flat(a):
-    return a.contiguous().reshape(-1) if _is_torch(a) else np.ascontiguousarray(a).reshape(-1)
-
-
-def _cat(parts, axis):
-    if _is_torch(parts[0]):
-        import torch
-        return torch.cat(parts, dim=axis)
-    return np.concatenate([np.asarray(p) for p in parts], axis=axis)
+            out[self.put(self.good)] = msgs.reshape(self.ng, 384)
+        return out, self.put(self.ok.copy())
 
 
 def decrypt_batch(engine, key, d, ct_attrs, E, e_prime):
@@ -159,8 +126,8 @@ def decrypt_batch(engine, key, d, ct_attrs, E, e_prime):
     p = _Plan(engine, attrs, d, ct_attrs, E, e_prime)
     if not p.ng:
         return p.scatter(None)
-    P = engine.g1_scalar_mul(_flat(p.key_rows(D, 64)), _flat(p.delta))
-    den = engine.multi_pair(_flat(P), _flat(p.ct_rows()), p.seg(d))
+    P = engine.g1_scalar_mul(bufs.flat(p.key_rows(D, 64)), bufs.flat(p.delta))
+    den = engine.multi_pair(bufs.flat(P), bufs.flat(p.ct_rows()), p.seg(d))
     return p.scatter(engine.gt_div(p.rows(p.e_prime), den))
 
 
@@ -171,19 +138,18 @@ def decrypt_batch_large(engine, key, d, ct_attrs, E, e_pp, e_prime):
     d + 1 pairs, which sums [Delta_i] D_i in G2 per ciphertext, is not built.)"""
     attrs, di, Di = key
     p = _Plan(engine, attrs, d, ct_attrs, E, e_prime)
-    if (e_pp.numel() if p.torch else np.asarray(e_pp).size) != p.n * 64 or _is_torch(e_pp) != p.torch:
+    if bufs.nbytes(e_pp) != p.n * 64 or bufs.is_torch(e_pp) != bufs.is_torch(p.E):
         raise ValueError("e_pp must hold n G1 points of the kind E is")
     if not p.ng:
         return p.scatter(None)
     ng = p.ng
-    epp = p.rows(e_pp.reshape(p.n, 64) if p.torch else np.asarray(e_pp, dtype=np.uint8).reshape(p.n, 64)).reshape(ng, 1, 64)
-    epp = epp.expand(ng, d, 64) if p.torch else np.broadcast_to(epp, (ng, d, 64))
-    bases = _cat([p.key_rows(di, 64), epp], 1)                                             # [ng, 2 d, 64]
+    epp = bufs.expand(p.rows(bufs.view(e_pp, p.n, 64)).reshape(ng, 1, 64), ng, d, 64)
+    bases = bufs.cat([p.key_rows(di, 64), epp], 1)                                             # [ng, 2 d, 64]
     delta = p.delta.reshape(ng, d, 32)
-    scalars = _cat([delta, engine.fr_neg(_flat(delta)).reshape(ng, d, 32)], 1)
-    P = engine.g1_scalar_mul(_flat(bases), _flat(scalars))
-    Q = _cat([p.ct_rows(), p.key_rows(Di, 128)], 1)
-    return p.scatter(engine.gt_mul(p.rows(p.e_prime), engine.multi_pair(_flat(P), _flat(Q), p.seg(2 * d))))
+    scalars = bufs.cat([delta, engine.fr_neg(bufs.flat(delta)).reshape(ng, d, 32)], 1)
+    P = engine.g1_scalar_mul(bufs.flat(bases), bufs.flat(scalars))
+    Q = bufs.cat([p.ct_rows(), p.key_rows(Di, 128)], 1)
+    return p.scatter(engine.gt_mul(p.rows(p.e_prime), engine.multi_pair(bufs.flat(P), bufs.flat(Q), p.seg(2 * d))))
 
 
 def compute_t(engine, table, n, xs, nodes=None):
@@ -201,25 +167,20 @@ def compute_t(engine, table, n, xs, nodes=None):
     nodes = list(range(n + 1)) if nodes is None else [int(v) for v in nodes]
     if len(nodes) != n + 1 or table.nbase != n + 2:
         raise ValueError("need n + 1 = %d nodes and a table of n + 2 bases" % (n + 1))
-    dev = _is_torch(xs)
-    if not dev:
-        xs = xs if isinstance(xs, np.ndarray) else _scalar_rows(xs)
-        xs = np.ascontiguousarray(xs, dtype=np.uint8)
-    xs = xs.reshape(-1, 32)
+    if not bufs.is_torch(xs) and not isinstance(xs, np.ndarray):
+        xs = _scalar_rows(xs)
+    xs = bufs.view(xs, -1, 32)
     k = xs.shape[0]
 
     def put(a):
-        if not dev:
-            return a
-        import torch
-        return torch.from_numpy(np.ascontiguousarray(a)).to(xs.device)
-    flat = _flat(xs)
+        return bufs.put(a, xs)
+    flat = bufs.flat(xs)
     delta = engine.fr_lagrange_basis(put(_scalar_rows(range(1, n + 2))).reshape(-1), n + 1, put(_scalar_rows(nodes)).reshape(-1), n + 1, flat).reshape(k, n + 1, 32)
     acc = engine.fr_mul(flat, put(_scalar_rows([1])).reshape(-1))                         # x, canonical
     base = acc
     for bit in bin(n)[3:]:
-        acc = engine.fr_mul(_flat(acc), _flat(acc))
+        acc = engine.fr_mul(bufs.flat(acc), bufs.flat(acc))
         if bit == "1":
-            acc = engine.fr_mul(_flat(acc), _flat(base))
-    scalars = _cat([acc.reshape(k, 1, 32), delta], 1)
-    return table.msm(_flat(scalars)).reshape(k, 128)
+            acc = engine.fr_mul(bufs.flat(acc), bufs.flat(base))
+    scalars = bufs.cat([acc.reshape(k, 1, 32), delta], 1)
+    return table.msm(bufs.flat(scalars)).reshape(k, 128)

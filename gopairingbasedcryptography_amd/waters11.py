@@ -31,14 +31,12 @@ import collections
 
 import numpy as np
 
-from .lw11 import R_ORDER, reconstruction_weights
+from . import _buffers as bufs
+from ._buffers import R_ORDER
+from .lw11 import reconstruction_weights
 
 Padded = collections.namedtuple("Padded", "matrix rho rows cols")      # matrix [n, R, C, 32] uint8 scalars; rho [n, R] int64, -1 = padding
 NO_ATTRIBUTE = -1
-
-
-def _is_torch(x):
-    return type(x).__module__.startswith("torch")
 
 
 def pad_policies(policies, rows=None, cols=None):
@@ -91,37 +89,18 @@ def held_mask(rho_table, key_attrs):
     return (key_index(rho_table, key_attrs) < len(key_attrs)).astype(np.uint8)
 
 
-def _flat(a):
-    return a.contiguous().reshape(-1) if _is_torch(a) else np.ascontiguousarray(a).reshape(-1)
-
-
-def _cat(parts, axis):
-    if _is_torch(parts[0]):
-        import torch
-        return torch.cat(parts, dim=axis)
-    return np.concatenate([np.asarray(p) for p in parts], axis=axis)
-
-
 def _decrypt(engine, key, pad, c, c_prime, cx, dx, weights):
     K, L, kx = key
     n, R = pad.rho.shape
-    dev = _is_torch(c)
-    if any(_is_torch(a) != dev for a in (c_prime, cx, dx)):
-        raise ValueError("c, c_prime, cx and dx must all be CUDA tensors (or all host arrays)")
-    size = (lambda a: a.numel()) if dev else (lambda a: np.asarray(a).size)
-    if size(c) != n * 384 or size(c_prime) != n * 128 or size(cx) != n * R * 64 or size(dx) != n * R * 128:
+    bufs.device_of(c, c_prime, cx, dx)                                         # all of one kind, on one device
+    if bufs.nbytes(c) != n * 384 or bufs.nbytes(c_prime) != n * 128 or bufs.nbytes(cx) != n * R * 64 or bufs.nbytes(dx) != n * R * 128:
         raise ValueError("need c [n, 384], c_prime [n, 128], cx [n, R, 64], dx [n, R, 128] with n = %d, R = %d" % (n, R))
-    if dev:
-        import torch
-        put = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(c.device)
-        c, c_prime, cx, dx = c.reshape(n, 384), c_prime.reshape(n, 1, 128), cx.reshape(n * R, 64), dx.reshape(n, R, 128)
-        zeros = lambda shape: torch.zeros(shape, dtype=torch.uint8, device=c.device)
-    else:
-        put = lambda a: a
-        c, c_prime, cx, dx = (np.asarray(a, dtype=np.uint8).reshape(s) for a, s in ((c, (n, 384)), (c_prime, (n, 1, 128)), (cx, (n * R, 64)), (dx, (n, R, 128))))
-        zeros = lambda shape: np.zeros(shape, dtype=np.uint8)
+
+    def put(a):
+        return bufs.put(a, c)
+    c, c_prime, cx, dx = bufs.view(c, n, 384), bufs.view(c_prime, n, 1, 128), bufs.view(cx, n * R, 64), bufs.view(dx, n, R, 128)
     if not n:
-        return zeros((0, 384)), zeros((0,))
+        return bufs.zeros((0, 384), c), bufs.zeros((0,), c)
     attrs = sorted(int(a) for a in kx)
     comp = np.zeros((len(attrs) + 1, 64), dtype=np.uint8)                 # the last row: the point at infinity, for rows the key lacks
     for i, a in enumerate(attrs):
@@ -129,25 +108,24 @@ def _decrypt(engine, key, pad, c, c_prime, cx, dx, weights):
     index = key_index(pad.rho, attrs)
     held = (index < len(attrs)).astype(np.uint8)
     w, ok = weights(put, held)                                                # [n, R, 32] canonical, [n]
-    nw = engine.fr_neg(_flat(w))
+    nw = engine.fr_neg(bufs.flat(w))
     # S_t = sum_x [-w_tx] C_tx: n R scalar multiplications, then ceil(log2 R) rounds of additions over the row axis
-    S = engine.g1_scalar_mul(_flat(cx), _flat(nw)).reshape(n, R, 64)
+    S = engine.g1_scalar_mul(bufs.flat(cx), bufs.flat(nw)).reshape(n, R, 64)
     m = R
     while m > 1:
         h = m // 2
-        s = engine.g1_add(_flat(S[:, :h]), _flat(S[:, h:2 * h])).reshape(n, h, 64)
-        S = _cat([s, S[:, 2 * h:m]], 1) if m & 1 else s
+        s = engine.g1_add(bufs.flat(S[:, :h]), bufs.flat(S[:, h:2 * h])).reshape(n, h, 64)
+        S = bufs.cat([s, S[:, 2 * h:m]], 1) if m & 1 else s
         m = h + (m & 1)
     # T_tx = [-w_tx] K_rho(t,x)
-    kc = put(comp)
-    gathered = kc.index_select(0, put(index.reshape(-1))) if dev else comp[index.reshape(-1)]
-    T = engine.g1_scalar_mul(_flat(gathered), _flat(nw)).reshape(n, R, 64)
+    gathered = bufs.take(put(comp), index.reshape(-1))
+    T = engine.g1_scalar_mul(bufs.flat(gathered), bufs.flat(nw)).reshape(n, R, 64)
     k_rows = put(np.broadcast_to(np.asarray(K, dtype=np.uint8).reshape(1, 1, 64), (n, 1, 64)))
     l_rows = put(np.broadcast_to(np.asarray(L, dtype=np.uint8).reshape(1, 1, 128), (n, 1, 128)))
-    P = _cat([k_rows, S.reshape(n, 1, 64), T], 1)
-    Q = _cat([c_prime, l_rows, dx], 1)
-    E = engine.multi_pair(_flat(P), _flat(Q), np.arange(0, (R + 2) * n + 1, R + 2, dtype=np.uint64))
-    msgs = engine.gt_div(_flat(c), _flat(E)).reshape(n, 384)
+    P = bufs.cat([k_rows, S.reshape(n, 1, 64), T], 1)
+    Q = bufs.cat([c_prime, l_rows, dx], 1)
+    E = engine.multi_pair(bufs.flat(P), bufs.flat(Q), np.arange(0, (R + 2) * n + 1, R + 2, dtype=np.uint64))
+    msgs = engine.gt_div(bufs.flat(c), bufs.flat(E)).reshape(n, 384)
     ok = ok.reshape(n)
     return msgs * ok.reshape(n, 1), ok                                         # ok is 0 / 1: a row that cannot be decrypted comes back all zero
 

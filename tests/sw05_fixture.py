@@ -7,7 +7,8 @@ x^n + sum_j tau_j Delta_{x,N}(j) in Python integers (the reference's node list j
 multiplication.
 
 Also here: the reference's FindCommonAttributes and Decrypt loops written out (Python integers, oracle calls), and the stand-ins the
-plan tests run the planner on (OracleEngine with fr_lagrange_basis in Python integers, OracleTable for FixedBase).
+plan tests run the planner on (OracleEngine with fr_lagrange_basis in Python integers, OracleTable for FixedBase, and TensorEngine,
+which lets any of the plan tests' stand-ins take CPU tensors so that a planner's tensor path runs without a GPU).
 
 numpy arrays by default; with `dev` a torch device everything per ciphertext is made and kept in HBM (the instances at size)."""
 import numpy as np
@@ -188,3 +189,41 @@ class OracleTable:
     def msm(self, scalars):
         k = np.asarray(scalars, dtype=np.uint8).reshape(-1, self.nbase, 32)
         return np.stack([np.asarray(self.o.g2_sum(self.o.g2_scalar_mul(self.bases, row.reshape(-1), threads=4))).reshape(128) for row in k])
+
+
+class TensorEngine:
+    """Any stand-in engine (numpy only) behind the engine's tensor behaviour: tensors among the arguments go in as numpy arrays, and
+    a call that was given a tensor hands its array results back as CPU tensors.  A call on host data alone passes through."""
+
+    def __init__(self, engine):
+        self._engine = engine
+
+    def __getattr__(self, name):
+        fn = getattr(self._engine, name)
+        if not callable(fn):
+            return fn
+        import torch
+
+        def call(*args, **kw):
+            tensors = [a for a in list(args) + list(kw.values()) if isinstance(a, torch.Tensor)]
+            host = lambda a: a.numpy() if isinstance(a, torch.Tensor) else a
+            res = fn(*[host(a) for a in args], **{k: host(v) for k, v in kw.items()})
+            if not tensors:
+                return res
+            back = lambda r: torch.from_numpy(np.array(r, dtype=np.uint8, copy=True)) if isinstance(r, np.ndarray) else r
+            return tuple(back(r) for r in res) if isinstance(res, tuple) else back(res)
+        return call
+
+
+def tensors(*arrays):
+    """copies of host arrays as CPU uint8 tensors"""
+    import torch
+    return [torch.from_numpy(np.array(a.cpu() if isinstance(a, torch.Tensor) else a, dtype=np.uint8, copy=True)) for a in arrays]
+
+
+def same_on_tensors(got, want):
+    """the tensor run of a planner returned tensors, of the numpy run's shape, holding the numpy run's bytes"""
+    import torch
+    assert isinstance(got, torch.Tensor) and isinstance(want, np.ndarray)
+    assert got.dtype == torch.uint8 and tuple(got.shape) == want.shape
+    return got.numpy().tobytes() == want.tobytes()

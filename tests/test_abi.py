@@ -34,6 +34,49 @@ def test_python_binding_covers_header(lib):
     assert sorted(_lib.EXPORTS) == declared_symbols()
 
 
+def header_prototypes():
+    """{symbol: (return kind, [parameter kinds])} parsed from the header, in the kinds of _lib.SIGNATURES: p for any type with a `*`,
+    z size_t, l long, i int; s for the one `const char *` return"""
+    text = open(os.path.join(ROOT, "include", "gpbc_bn254.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+
+    def kind(decl, ret=False):
+        if "*" in decl:
+            assert not ret or re.fullmatch(r"\s*const\s+char\s*\*\s*", decl), decl
+            return "s" if ret else "p"
+        words = set(re.findall(r"[A-Za-z_]\w*", decl))
+        hits = [k for k, w in (("z", "size_t"), ("l", "long"), ("i", "int")) if w in words]
+        assert len(hits) == 1, decl
+        return hits[0]
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w \t\n\*]*?)\b(gpbc_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
+        assert name not in protos, name
+        params = " ".join(params.split())
+        protos[name] = (kind(ret, ret=True), [] if params in ("", "void") else [kind(p) for p in params.split(",")])
+    return protos
+
+
+def test_signature_table_is_the_header(lib):
+    """Every prototype of the header, return and parameter by parameter, is what _lib.SIGNATURES declares, and load() has given
+    every symbol its restype and argtypes from it: no call relies on ctypes' default of a 32-bit int."""
+    import ctypes
+    from gopairingbasedcryptography_amd import _lib
+    protos = header_prototypes()
+    assert sorted(protos) == declared_symbols() == sorted(_lib.SIGNATURES) and len(protos) == 131
+    ctype = {"p": ctypes.c_void_p, "z": ctypes.c_size_t, "i": ctypes.c_int, "l": ctypes.c_long, "s": ctypes.c_char_p}
+    for name, (ret, params) in protos.items():
+        assert _lib.SIGNATURES[name] == ret + ":" + "".join(params), name
+        fn = getattr(lib, name)
+        assert fn.restype is ctype[ret], name
+        assert fn.argtypes is not None and list(fn.argtypes) == [ctype[k] for k in params], name
+    returns = [ret for ret, _ in protos.values()]
+    assert (returns.count("i"), returns.count("z"), returns.count("s")) == (125, 5, 1)
+    assert [n for n, (_, params) in protos.items() if "l" in params] == ["gpbc_set_latency_path"]
+    with pytest.raises(ctypes.ArgumentError):                              # a size_t value where the header says int
+        lib.gpbc_set_device(ctypes.c_size_t(0))
+
+
 def test_generators_match_oracle():
     import bn254_py as o
     from gopairingbasedcryptography_amd import bn254
@@ -133,12 +176,39 @@ def test_wrapper_rejects_malformed_device_arguments():
         lambda: bn254.hash_to_g1(z(10), b"dst", msg_off=torch.tensor([0, 10], dtype=torch.int64)),   # right shapes, but host tensors
         lambda: bn254.hash_to_field(np.frombuffer(b"abc", dtype=np.uint8), b"dst", 2, msg_off=np.array([0, 5], dtype=np.uint64)),   # offsets beyond the buffer
         lambda: bn254.g1_scalar_mul(np.zeros(64, dtype=np.uint8), np.zeros(4 * 32, dtype=np.uint8), out=np.zeros(3 * 64, dtype=np.uint8)),   # host out too small
+        lambda: bn254.final_exp(z(384 + 1)),                                  # not whole GT elements
+        lambda: bn254.final_exp(z(2 * 384)),                                  # whole elements, but host tensors
+        lambda: bn254.g1_add(z(4 * 64), z(3 * 64)),                           # neither one b nor one per a
+        lambda: bn254.g1_add(z(4 * 64), z(4 * 64), out=z(3 * 64)),
+        lambda: bn254.g2_double(z(4 * 128 - 1)),
+        lambda: bn254.g2_double(z(4 * 128), out=np.zeros(4 * 128, dtype=np.uint8)),   # device points, host out
+        lambda: bn254.fr_mul(z(4 * 32), z(2 * 32)),
+        lambda: bn254.fr_mul(z(4 * 32), z(4 * 32).to(torch.int32)),
+        lambda: bn254.fr_inverse(z(4 * 32 + 1)),
+        lambda: bn254.fr_inverse(z(4 * 32), out=z(5 * 32)),
+        lambda: bn254.g1_marshal(z(4 * 64 + 1)),
+        lambda: bn254.g1_marshal(z(4 * 64)),                                  # host tensors
+        lambda: bn254.map_to_g2(z(3 * 128 + 64)),
+        lambda: bn254.g1_sum(z(4 * 64 + 32)),
+        lambda: bn254.g1_sum(z(4 * 64)[::2]),                                 # not contiguous
+        lambda: bn254.gt_inverse(z(383)),
+        lambda: bn254.gt_multi_exp(z(4 * 384), z(3 * 32), [0, 4]),            # neither one exponent per element nor one list per segment
+        lambda: bn254.gt_multi_exp(z(4 * 384), None, [0, 3]),                 # the table does not end at the element count
+        lambda: bn254.gt_multi_exp(z(4 * 384), None, [0, 4], out=z(2 * 384)),
+        lambda: bn254.gt_mul(z(4 * 384), np.zeros(4 * 384, dtype=np.uint8)),  # mixed host and device operands
+        lambda: bn254.gt_mul(np.zeros(4 * 384, dtype=np.uint8), z(4 * 384)),
+        lambda: bn254.g1_scalar_mul_sum(np.zeros(4 * 64, dtype=np.uint8), z(4 * 32)),
+        lambda: bn254.fr_lsss_weights(z(2 * 2 * 32), 2, 2, held=np.ones(2, dtype=np.uint8)),
+        lambda: bn254.fr_lsss_weights(np.zeros(2 * 2 * 32, dtype=np.uint8), 2, 2, held=z(2)),
+        lambda: bn254.pairing_check(P, Q),                                    # host-only entries: a tensor's address must not reach them
+        lambda: bn254.pairing_check_batch(P, Q, [0, 4]),
+        lambda: bn254.pair(P, Q),
     ]
-    bn254._slots = bn254._slots or {0: 0}                                     # as after init(0); no device is touched below
+    slots = bn254._slots                                                      # no check may need, or make, a bound device
     for i, call in enumerate(bad):
         with pytest.raises(ValueError):
             call()
-        assert True, i
+        assert bn254._slots is slots, i
 
 
 def test_device_list_and_collective_entries_fail_loudly_without_gpu(lib):

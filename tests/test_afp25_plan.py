@@ -6,6 +6,7 @@ import pytest
 
 import bn254_py as o
 from afp25_fixture import Instance
+from sw05_fixture import TensorEngine, same_on_tensors, tensors
 from gopairingbasedcryptography_amd import afp25
 from test_bsw07_plan import OracleEngine
 
@@ -49,3 +50,18 @@ def test_duplicated_identity_is_an_error_as_in_the_reference(oracle):
         afp25.decrypt_batch(eng, inst.g1, inst.tau_powers, inst.D, inst.f, inst.sk, inst.items[:1], identities=dup)
     with pytest.raises(ValueError, match="identity not found in identity list"):
         afp25.decrypt_batch(eng, inst.g1, inst.tau_powers, inst.D, inst.f, inst.sk, inst.items[:1], identities=[i for i in ids if i != inst.items[0][0]])
+
+
+def test_decrypt_on_arrays_and_on_tensors(oracle):
+    """decrypt_batch_arrays with the opening proofs of the host route: the messages on numpy arrays; on CPU tensors (TensorEngine) a
+    tensor with the same bytes"""
+    eng = Eng(oracle)
+    inst = Instance(eng, B=3, n_items=2)
+    n = len(inst.items)
+    pi = np.stack([np.asarray(afp25.commit_g1(eng, inst.g1, inst.tau_powers, afp25.quotient_by_root(inst.f, ident))).reshape(64) for ident, _, _ in inst.items])
+    arrays = [np.tile(np.asarray(inst.D).reshape(1, 64), (n, 1)), pi, np.tile(np.asarray(inst.sk).reshape(1, 64), (n, 1)),
+              np.stack([C1 for _, C1, _ in inst.items]), np.stack([C2 for _, _, C2 in inst.items])]
+    out = afp25.decrypt_batch_arrays(eng, *arrays)
+    assert (np.asarray(out) == np.stack(inst.msgs)).all()
+    out_t = afp25.decrypt_batch_arrays(TensorEngine(eng), *tensors(*arrays))
+    assert same_on_tensors(out_t, np.asarray(out))

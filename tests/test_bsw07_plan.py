@@ -7,6 +7,7 @@ import pytest
 
 import bn254_py as o
 from bsw07_fixture import Instance, example_tree
+from sw05_fixture import TensorEngine, same_on_tensors, tensors
 from gopairingbasedcryptography_amd import bsw07
 
 
@@ -54,3 +55,30 @@ def test_unsatisfied_policy(oracle):
     inst = Instance(eng, example_tree(), user_attrs=[22, 44 + 1], n_ct=1)
     assert bsw07.decrypt_plan(inst.tree, inst.user_attrs) is None          # bsw07_cpabe_test.go:83-141: decrypt must fail
     assert inst.reference_shaped_decrypt(oracle, inst.cts[0]) is None
+
+
+class ArraysEngine(OracleEngine):
+    """what decrypt_batch_arrays needs besides: the fixed-Q multi-pairing as a plain one over the repeated list, G2 negation"""
+
+    def multi_pair_fixed_q(self, P, Q):
+        P, Q = np.asarray(P, dtype=np.uint8).reshape(-1, 64), np.asarray(Q, dtype=np.uint8).reshape(-1, 128)
+        m, k = len(Q), len(P) // len(Q)
+        return self.o.multi_pair(P, np.tile(Q, (k, 1)), np.arange(0, k * m + 1, m), threads=4)
+
+    def g2_neg(self, b):
+        return np.frombuffer(o.g2_to_bytes(o.g2_neg(o.g2_from_bytes(np.asarray(b, dtype=np.uint8).tobytes()))), dtype=np.uint8)
+
+
+def test_decrypt_on_arrays_and_on_tensors(oracle):
+    """decrypt_batch_arrays on numpy arrays returns the messages; on CPU tensors (TensorEngine) a tensor with the same bytes"""
+    eng = ArraysEngine(oracle)
+    inst = Instance(eng, example_tree(), user_attrs=[11, 22, 33, 99], n_ct=2)
+    folded = bsw07.fold_key(eng, bsw07.decrypt_plan(inst.tree, inst.user_attrs), inst.dj, inst.dj_prime)
+    ids = folded[0]
+    arrays = [np.stack([np.asarray(ct["c_tilde"]) for ct in inst.cts]), np.stack([np.asarray(ct["c"]) for ct in inst.cts]),
+              np.stack([np.stack([np.asarray(ct["cy"][i]) for i in ids]) for ct in inst.cts]),
+              np.stack([np.stack([np.asarray(ct["cy_prime"][i]) for i in ids]) for ct in inst.cts])]
+    out = bsw07.decrypt_batch_arrays(eng, folded, inst.D, *arrays)
+    assert (np.asarray(out) == np.stack(inst.msgs)).all()
+    out_t = bsw07.decrypt_batch_arrays(TensorEngine(eng), folded, inst.D, *tensors(*arrays))
+    assert same_on_tensors(out_t, np.asarray(out))

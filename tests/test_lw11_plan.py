@@ -9,6 +9,7 @@ import pytest
 import bn254_py as o
 import gt_multi_exp_cases as gc
 from lw11_fixture import Instance, and_chain_policy, and_or_policy, threshold_policy
+from sw05_fixture import TensorEngine, same_on_tensors, tensors
 from gopairingbasedcryptography_amd import lw11
 
 
@@ -99,6 +100,11 @@ def test_and_or_policy_matches_the_reference_loop(oracle):
         assert (out[t] == inst.msgs[t]).all()
         assert (out[t] == inst.row_by_row_decrypt(oracle, t, rows, w, running=True)).all()
         assert (out[t] == inst.row_by_row_decrypt(oracle, t, rows, w, running=False)).all()
+    # the planner's tensor path, on CPU tensors: a tensor with the same bytes
+    out_t = lw11.decrypt_batch(TensorEngine(eng), folded, *tensors(inst.c0, inst.c1, inst.c2, inst.c3))
+    assert same_on_tensors(out_t, np.asarray(out))
+    with pytest.raises(ValueError):                                       # one call, one kind of buffer
+        lw11.decrypt_batch(eng, folded, tensors(inst.c0)[0], inst.c1, inst.c2, inst.c3)
     # the other branch of the OR with another key: rows 2 and 3
     inst2 = Instance(eng, m, rho, [33, 44], n_ct=2, tag="b")
     rows2, w2 = lw11.reconstruction_weights(m, rho, inst2.user_attrs)

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import bn254_py as o
-from sw05_fixture import Instance, OracleEngine, OracleTable, find_common, kbytes, lagrange, sc, t_exponent
+from sw05_fixture import Instance, OracleEngine, OracleTable, TensorEngine, find_common, kbytes, lagrange, same_on_tensors, sc, t_exponent, tensors
 from gopairingbasedcryptography_amd import sw05
 
 R = o.R
@@ -71,6 +71,25 @@ def test_decrypt_matches_the_reference_loop(oracle, d, large):
         assert (out[t] == np.asarray(inst.msgs)[t]).all(), t
         assert (out[t] == inst.reference_shaped_decrypt(oracle, t)).all(), t
     assert inst.reference_shaped_decrypt(oracle, 2) is None
+
+
+@pytest.mark.parametrize("large", [False, True])
+def test_decrypt_on_tensors_is_decrypt_on_arrays(oracle, large):
+    """the planner's tensor path on CPU tensors (TensorEngine): three ciphertexts, the middle one below the threshold, give tensors
+    with the bytes and the ok rows of the numpy run"""
+    eng = OracleEngine(oracle)
+    cts = cts_for(2)[1:]
+    inst = Instance(eng, 2, KEY, cts, n_univ=5 if large else None, tag="kinds")
+    if large:
+        out, ok = sw05.decrypt_batch_large(eng, inst.key, 2, cts, inst.E, inst.e_pp, inst.e_prime)
+        out_t, ok_t = sw05.decrypt_batch_large(TensorEngine(eng), inst.key, 2, cts, *tensors(inst.E, inst.e_pp, inst.e_prime))
+    else:
+        out, ok = sw05.decrypt_batch(eng, inst.key, 2, cts, inst.E, inst.e_prime)
+        out_t, ok_t = sw05.decrypt_batch(TensorEngine(eng), inst.key, 2, cts, *tensors(inst.E, inst.e_prime))
+    assert ok.tolist() == [1, 0, 1] and (out[0] == np.asarray(inst.msgs)[0]).all()
+    assert same_on_tensors(out_t, out) and same_on_tensors(ok_t, ok)
+    with pytest.raises(ValueError):                                       # one call, one kind of buffer
+        sw05.decrypt_batch(eng, inst.key, 2, cts, tensors(inst.E)[0], inst.e_prime)
 
 
 def test_decrypt_with_nothing_decryptable(oracle):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import bn254_py as o
+from sw05_fixture import TensorEngine, same_on_tensors, tensors
 from waters11_fixture import Instance, OracleEngineW11, and_or_16, small_policies
 from gopairingbasedcryptography_amd import lw11, waters11
 
@@ -58,6 +59,9 @@ def test_decrypt_matches_the_row_by_row_decrypt(oracle):
     out_p, ok_p = waters11.decrypt_batch(eng, inst.key, waters11.pad_policies(pols), inst.c, inst.c_prime, inst.cx, inst.dx)
     assert (out_h == out).all() and ok_h.tolist() == ok.tolist() and (out_p == out).all() and ok_p.tolist() == ok.tolist()
     del eng.gt_exp
+    # the planner's tensor path, on CPU tensors: tensors with the same bytes and the same ok rows
+    out_t, ok_t = waters11.decrypt_batch(TensorEngine(eng), inst.key, pols, *tensors(inst.c, inst.c_prime, inst.cx, inst.dx))
+    assert same_on_tensors(out_t, np.asarray(out)) and same_on_tensors(ok_t, np.asarray(ok))
     for t in range(3):
         assert (out[t] == np.asarray(inst.msgs)[t]).all(), t
         assert (out[t] == inst.row_by_row_decrypt(oracle, t)).all(), t
