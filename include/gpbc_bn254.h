@@ -18,8 +18,32 @@
  * thread-safe.  There is NO CPU fallback: without a usable gfx950 device every compute entry fails
  * with GPBC_ERR_NO_DEVICE.
  *
- * *_dev variants take device pointers (buffers already resident in HBM), enqueue on `stream`
- * (a hipStream_t passed as void*, NULL = default stream) and return without synchronising.
+ * *_dev variants take device pointers (buffers already resident in HBM) and a `stream` (a hipStream_t passed as void*,
+ * NULL = default stream).  The stream contract (tests/test_stream_contract_gpu.py holds every entry to it):
+ *   ORDER   every kernel, copy and memset of the call is enqueued on `stream` and on no other: the call reads its inputs
+ *           after all earlier work on `stream` and its outputs are complete for all later work on `stream`.  Nothing is
+ *           launched on the null stream on the caller's behalf and no input is read by the host outside that order.
+ *   RETURN  the call returns without waiting for `stream`, with these exceptions, which synchronise `stream` (and only
+ *           `stream`) before they return, because the host needs a value the device computes:
+ *             gpbc_multi_pair_hostseg_dev     the echo of the consumed pairs is read back and compared (fail-closed check)
+ *             gpbc_check_segments_dev         its result IS the read-back; it also drains the device when its flag block
+ *                                             goes back to the block cache
+ *             gpbc_g1_scalar_mul_sum_dev,     from 16 384 terms on (the bucket method): the histogram of the longest buckets
+ *             gpbc_g2_scalar_mul_sum_dev      is read back to choose between the bucket and the term-by-term path
+ *           and one that blocks without reading anything back:
+ *             gpbc_fixed_base_create_dev      allocates the table with hipMalloc (the build itself is enqueued and NOT
+ *                                             waited for: the caller keeps `d_bases` alive until `stream` has passed it)
+ *           gpbc_fixed_base_destroy and gpbc_release_workspaces synchronise the whole device.
+ *           (The Python package adds waits of its own on top of entries that do not wait: FixedBase(), FixedBase.msm and
+ *           FixedBase.mul synchronise the current stream, and an entry given a host value beside device buffers — host or
+ *           Python exponents, a host segment table, the generator of g1/g2_scalar_mul_base — uploads it from pageable
+ *           memory, which returns when that copy is done.  DESIGN.md "Stream contract" has the whole table.)
+ *   GROWTH  any entry that uses a library-owned buffer of `stream` (line / table workspace, scratch, pinned staging)
+ *           synchronises `stream` and calls hipMalloc / hipFree when that buffer has to grow: the first call on a stream,
+ *           the first call at a larger size, the first call after gpbc_release_workspaces.  Calls at sizes the stream has
+ *           seen before do not block.
+ * The host-pointer entries (no _dev suffix; gpbc_pairing_check among them) are synchronous: the results are in the
+ * caller's buffers when they return.
  */
 #ifndef GPBC_BN254_H
 #define GPBC_BN254_H
@@ -114,8 +138,8 @@ int gpbc_multi_pair(const void *P, const void *Q, const uint64_t *seg_off, size_
 size_t gpbc_multi_pair_workspace_bytes(size_t n_pairs, size_t k);
 int gpbc_multi_pair_dev(const void *dP, const void *dQ, const uint64_t *d_seg_off, size_t n_pairs, size_t k,
                         void *d_gt_out, void *d_workspace, size_t workspace_bytes, void *stream);
-/* Validation of a device-resident table for gpbc_multi_pair_dev (k+1 entries read): one small kernel, synchronises `stream`,
- * returns GPBC_ERR_INVALID_ARG (first entry not 0, not monotone, last entry != n_pairs) or GPBC_OK.  Optional: the
+/* Validation of a device-resident table for gpbc_multi_pair_dev (k+1 entries read): one small kernel, synchronises `stream`
+ * (and, when it releases its flag block, the device), returns GPBC_ERR_INVALID_ARG (first entry not 0, not monotone, last entry != n_pairs) or GPBC_OK.  Optional: the
  * multi-pairing itself stays asynchronous and safe (clamped) without it. */
 int gpbc_check_segments_dev(const uint64_t *d_seg_off, size_t n_pairs, size_t k, void *stream);
 /* Points and results in device memory, segment table on the HOST (validated like gpbc_multi_pair).  With the table at
@@ -225,7 +249,9 @@ int gpbc_g2_double_batch_dev(const void *d_a, size_t n, void *d_out, void *strea
  * data of a host-pointer call is on the host anyway.
  * _dev form (one process per GPU): the calling rank's shard in device memory; with a communicator (gpbc_comm_init_rank)
  * the partial sums of all ranks are all-gathered and added, so every rank ends with the global sum; without one the
- * result is the local sum.  Stream-ordered, not synchronised. */
+ * result is the local sum.  Stream-ordered.  Below 16 384 terms (one scalar multiplication per term and a sum tree) the call
+ * does not wait for `stream`; from 16 384 terms on it does: the bucket method reads the lengths of the longest buckets back
+ * (4 bytes per window, through the stream's pinned staging) and synchronises `stream` before it chooses its path. */
 int gpbc_g1_scalar_mul_sum(const void *bases, const void *scalars, size_t n, void *out);
 int gpbc_g2_scalar_mul_sum(const void *bases, const void *scalars, size_t n, void *out);
 int gpbc_g1_scalar_mul_sum_dev(const void *d_bases, const void *d_scalars, size_t n, void *d_out, void *stream);
@@ -273,7 +299,9 @@ int gpbc_gt_multi_exp_dev(const void *d_x, const void *d_k, size_t nk, const uin
  * create builds 8-bit window tables [d * 2^(8w)] base_j (d = 1..255, w = 0..31) in HBM — gpbc_fixed_base_table_bytes():
  * 1 MB per G1 base, 2 MB per G2 base — after which a term costs 32 mixed additions and no doublings.  Scalars: n_msm rows
  * of nbase 32-byte little-endian integers (any value < 2^256; no reduction is needed).  The handle is bound to the device
- * it was built on; msm calls may run concurrently, destroy must not race with them. */
+ * it was built on; msm calls may run concurrently, destroy must not race with them.  create_dev blocks in hipMalloc and enqueues
+ * the build on `stream` without waiting for it (d_bases must stay alive until the stream has passed it); msm_dev is asynchronous
+ * on `stream` and must be ordered behind the build by the caller (same stream, or an event); destroy drains the device. */
 typedef struct gpbc_fixed_base gpbc_fixed_base;
 size_t gpbc_fixed_base_table_bytes(size_t nbase, int is_g2);
 int gpbc_g1_fixed_base_create(const void *bases, size_t nbase, gpbc_fixed_base **out);
