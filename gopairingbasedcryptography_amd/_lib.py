@@ -56,6 +56,13 @@ SIGNATURES = {
     "gpbc_profile_begin": "i:p", "gpbc_profile_end": "i:pppip", "gpbc_valu_probe": "i:p", "gpbc_fp_mul_batch": "i:ppzp",
 }
 EXPORTS = list(SIGNATURES)
+# The same for include/gpbc_bn254_ext.h, the entries added since the main header was frozen (tests/test_multi_scalar_mul.py holds
+# this table against that header).
+EXT_SIGNATURES = {
+    "gpbc_ext_version": "i:", "gpbc_g1_multi_scalar_mul": "i:ppzpzp", "gpbc_g2_multi_scalar_mul": "i:ppzpzp",
+    "gpbc_multi_scalar_mul_workspace_bytes": "z:zzi", "gpbc_g1_multi_scalar_mul_dev": "i:ppzpzzppzp",
+    "gpbc_g2_multi_scalar_mul_dev": "i:ppzpzzppzp",
+}
 # every pointer is a c_void_p: it takes ints, None, c_void_p, ctypes arrays, byref() and ndarray.ctypes.data_as() alike
 _CTYPES = {"p": ctypes.c_void_p, "z": ctypes.c_size_t, "i": ctypes.c_int, "l": ctypes.c_long, "s": ctypes.c_char_p}
 
@@ -81,7 +88,7 @@ def load():
         except ImportError:
             pass
         lib = ctypes.CDLL(LIB_PATH)
-        for name, sig in SIGNATURES.items():
+        for name, sig in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
             ret, params = sig.split(":")
             fn = getattr(lib, name)
             fn.restype = _CTYPES[ret]

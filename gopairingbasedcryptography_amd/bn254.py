@@ -337,6 +337,81 @@ def g2_scalar_mul(bases, scalars, out=None):
     return _scalar_mul("g2", G2_BYTES, bases, scalars, out)
 
 
+def _multi_scalar_mul(group, width, bases, scalars, seg_off, out, workspace):
+    """out[s] = sum_{i in [seg_off[s], seg_off[s+1])} [scalars[i]] bases[i] (include/gpbc_bn254_ext.h): gt_multi_exp's shape in G1 / G2"""
+    if isinstance(scalars, int):
+        scalars = [scalars]
+    if isinstance(scalars, (list, tuple)):
+        if any(not 0 <= int(s) < (1 << 256) for s in scalars):
+            raise ValueError("scalars must be in [0, 2^256) (they act as their residue mod r)")
+        scalars = np.frombuffer(b"".join(int(s).to_bytes(32, "little") for s in scalars), dtype=np.uint8)
+    k = None if scalars is None else scalars_to_bytes(scalars)
+    dev_table = bufs.is_torch(seg_off)
+    dev = bufs.device_of(bases, seg_off if dev_table else None, k if bufs.is_torch(k) else None)   # a host scalar list may go with device bases
+    bases, n = bufs.rows(bases, width, "bases")
+    if dev_table:
+        n_seg = _device_segments(seg_off, dev, "points")
+    else:
+        seg = np.ascontiguousarray(seg_off, dtype=np.uint64).reshape(-1)
+        n_seg = seg.size - 1
+        if n_seg < 1 or int(seg[0]) != 0 or int(seg[-1]) != n or (np.diff(seg.astype(np.int64)) < 0).any():
+            raise ValueError("seg_off must have n_seg + 1 >= 2 non-decreasing entries from 0 to the number of points")
+    nk = 0
+    if k is not None:
+        k, nk = bufs.rows(k, SCALAR_BYTES, "scalars")
+        if nk != n:
+            if nk > n or nk * n_seg != n:
+                raise ValueError("scalars must hold one per point, or one list for segments of equal length (nk = %d, n = %d, n_seg = %d)" % (nk, n, n_seg))
+            if not dev_table and (np.diff(seg.astype(np.int64)) != nk).any():
+                raise ValueError("a shared scalar list of %d needs segments of exactly %d points" % (nk, nk))
+    out = bufs.output(out, (n_seg, width), dev)
+    name = group + "_multi_scalar_mul"
+    if dev is None:
+        _call(name, None, bases, k, nk, seg, n_seg, out)
+        return out
+    # The device form is a call of its own, as in gt_multi_exp: a segment table in device memory (the caller's, validated by a
+    # kernel, or the host table copied there), n, a caller-side workspace, and a host scalar list next to device bases.
+    if k is not None and not bufs.is_torch(k):
+        k = bufs.put(k.copy(), bases)
+    if dev_table:
+        _check_segments(dev, seg_off, n, n_seg)
+        import torch
+        if nk != n and k is not None and bool((seg_off.view(torch.int64).diff() != nk).any()):
+            raise ValueError("a shared scalar list of %d needs segments of exactly %d points" % (nk, nk))
+    else:
+        seg_off = bufs.put(seg.astype(np.int64), bases)
+    ws = _workspace(workspace, _lib.load().gpbc_multi_scalar_mul_workspace_bytes(n, n_seg, int(group == "g2")), dev)
+    if bufs.address(ws[0]) % 16:
+        raise ValueError("workspace must be 16-byte aligned")
+    _call(name, dev, bases, k, nk, seg_off, n, n_seg, out, *ws)
+    return out
+
+
+def g1_multi_scalar_mul(bases, scalars, seg_off, out=None, workspace=None):
+    """out[s] = sum_{i in [seg_off[s], seg_off[s+1])} [scalars[i]] bases[i] in G1: the per-item sums of a few scalar multiples of
+    ciphertext points (S = sum_x [-w_x] C_x of Waters11 Decrypt) as one call, every term with ScalarMultiplication's semantics, the
+    doublings shared by four terms, one affine conversion per segment.  scalars: one per point, or ONE list of m when every segment
+    has exactly m points (the weights of a policy against many ciphertexts), or None for the plain sums; Python ints must be in
+    [0, 2^256).  numpy arrays in, numpy array out; CUDA tensors in (seg_off a host sequence, or an int64 / uint64 CUDA tensor that
+    is then validated on the device), CUDA tensor out, enqueued on the current torch stream.  Arguments are checked before the
+    engine is touched."""
+    return _multi_scalar_mul("g1", G1_BYTES, bases, scalars, seg_off, out, workspace)
+
+
+def g2_multi_scalar_mul(bases, scalars, seg_off, out=None, workspace=None):
+    """g1_multi_scalar_mul in G2 (sum_x w_x c3x of LW11 Decrypt)."""
+    return _multi_scalar_mul("g2", G2_BYTES, bases, scalars, seg_off, out, workspace)
+
+
+def g1_sum_segments(pts, seg_off):
+    """out[s] = sum pts[seg_off[s]:seg_off[s+1]]: g1_multi_scalar_mul without scalars (no tables, no doublings)."""
+    return g1_multi_scalar_mul(pts, None, seg_off)
+
+
+def g2_sum_segments(pts, seg_off):
+    return g2_multi_scalar_mul(pts, None, seg_off)
+
+
 # --------------------------------------------------------------------------------------- elementwise group law
 def g1_add(a, b, out=None):
     """out[i] = a[i] + b[i] (or + b[0] for a single b): G1Affine.Add, batched.  A single Add is cheaper in gnark on the host."""

@@ -16,6 +16,10 @@ e(K, c2x)^-w = e([-w]K, c2x) exactly as Fp12 elements, so per ciphertext
 c1x is ciphertext data in GT: it cannot be folded into a key or in front of a pairing, which is why this scheme needs a product of
 powers of varying GT bases per ciphertext (engine.gt_multi_exp with ONE exponent list for all ciphertexts).
 
+The pairings against H(GID) fold further by bilinearity, prod_x e([w_x]H, c3x) = e(H, sum_x w_x c3x): decrypt_batch_msm takes the sum
+from engine.g2_multi_scalar_mul (the weights as ONE scalar list for all ciphertexts) and spends k + 1 pairings per ciphertext where
+decrypt_batch spends 2k; the messages are the same bytes.
+
 The reference's loop is not that formula: it raises the RUNNING product to the weight at every row, ((1 * t_0)^w * t_1)^w' ...,
 and it indexes the compacted weight slice by the matrix row number (lw11_dabe.go:191-195; SURVEY.md's notes on Waters11 / DABE
 record both).  The two agree when every weight is 1 — the solution that Lewko-Waters matrices of AND / OR formulas have — and this
@@ -100,4 +104,26 @@ def decrypt_batch(engine, folded, c0, c1, c2, c3):
     Q = bufs.cat([used(c3, 128), used(c2, 128)], 1)
     E = engine.multi_pair(bufs.flat(P), bufs.flat(Q), np.arange(0, 2 * k * n + 1, 2 * k, dtype=np.uint64))
     F = engine.gt_multi_exp(bufs.flat(used(c1, 384)), weights, np.arange(0, k * n + 1, k, dtype=np.uint64))
+    return engine.gt_div(bufs.flat(c0).reshape(n, 384), engine.gt_mul(E, F))
+
+
+def decrypt_batch_msm(engine, folded, h_gid, c0, c1, c2, c3):
+    """decrypt_batch with the k pairings against H(GID) folded into one: E = Pair([H, B_x...], [sum_x w_x c3x, c2x...]), one segment
+    of k + 1 pairs per ciphertext, the sum from engine.g2_multi_scalar_mul with the shared weight list (n segments of k terms).  F and
+    the division are decrypt_batch's, and so are the messages, byte for byte (bilinearity, canonical GT output).  h_gid: the 64-byte
+    H(GID) that fold_key was given."""
+    rows, weights, _, B = folded
+    k = len(rows)
+    bufs.device_of(c0, c1, c2, c3)                                           # one kind of buffer, one device
+    n = bufs.nbytes(c0) // 384
+
+    def used(c, width):
+        return bufs.take(bufs.view(c, n, -1, width), rows, 1)
+    table = np.arange(0, k * n + 1, k, dtype=np.uint64)
+    S = engine.g2_multi_scalar_mul(bufs.flat(used(c3, 128)), weights, table).reshape(n, 1, 128)
+    hb = np.concatenate([np.asarray(h_gid, dtype=np.uint8).reshape(1, 64), B])
+    P = bufs.expand(bufs.put(hb.reshape(1, k + 1, 64), c0), n, k + 1, 64)
+    Q = bufs.cat([S, used(c2, 128)], 1)
+    E = engine.multi_pair(bufs.flat(P), bufs.flat(Q), np.arange(0, (k + 1) * n + 1, k + 1, dtype=np.uint64))
+    F = engine.gt_multi_exp(bufs.flat(used(c1, 384)), weights, table)
     return engine.gt_div(bufs.flat(c0).reshape(n, 384), engine.gt_mul(E, F))

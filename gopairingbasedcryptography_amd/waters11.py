@@ -15,8 +15,9 @@ against the one L fold into one: prod_x e(C_x, L)^-w_x = e(S, L), S = sum_x [-w_
 
 The weights differ from ciphertext to ciphertext, so unlike lw11.py (one policy for the whole batch, one elimination in host
 integers) they are per item: engine.fr_lsss_weights solves the n systems on the device, and the weights go into engine.fr_neg and
-engine.g1_scalar_mul as they are.  A row whose attribute the key lacks, a dependent row and a padding row get weight 0, hence the
-point at infinity, which the group law and the pairing treat as gnark does (e(0, Q) = 1).
+engine.g1_scalar_mul (with msm=True: into engine.g1_multi_scalar_mul for S) as they are.  A row whose attribute the key lacks, a
+dependent row and a padding row get weight 0, hence the point at infinity, which the group law and the pairing treat as gnark does
+(e(0, Q) = 1).
 
 The reference's loop is not quite that formula: it indexes the COMPACTED weight slice by the matrix row number (wSlice[i],
 waters11_cpabe.go:280; SURVEY.md's notes on Waters11 / DABE), which agrees with the scheme only when the used rows are the first
@@ -89,7 +90,24 @@ def held_mask(rho_table, key_attrs):
     return (key_index(rho_table, key_attrs) < len(key_attrs)).astype(np.uint8)
 
 
-def _decrypt(engine, key, pad, c, c_prime, cx, dx, weights):
+def _row_sums_composed(engine, cx, nw, n, R):
+    """S_t = sum_x [-w_tx] C_tx: n R scalar multiplications, then ceil(log2 R) rounds of additions over the row axis"""
+    S = engine.g1_scalar_mul(bufs.flat(cx), bufs.flat(nw)).reshape(n, R, 64)
+    m = R
+    while m > 1:
+        h = m // 2
+        s = engine.g1_add(bufs.flat(S[:, :h]), bufs.flat(S[:, h:2 * h])).reshape(n, h, 64)
+        S = bufs.cat([s, S[:, 2 * h:m]], 1) if m & 1 else s
+        m = h + (m & 1)
+    return S
+
+
+def _row_sums_msm(engine, cx, nw, n, R):
+    """the same sums from one segmented multi-scalar multiplication: n segments of R terms, the doublings shared by four terms"""
+    return engine.g1_multi_scalar_mul(bufs.flat(cx), bufs.flat(nw), np.arange(0, n * R + 1, R, dtype=np.uint64))
+
+
+def _decrypt(engine, key, pad, c, c_prime, cx, dx, weights, row_sums=_row_sums_composed):
     K, L, kx = key
     n, R = pad.rho.shape
     bufs.device_of(c, c_prime, cx, dx)                                         # all of one kind, on one device
@@ -109,14 +127,7 @@ def _decrypt(engine, key, pad, c, c_prime, cx, dx, weights):
     held = (index < len(attrs)).astype(np.uint8)
     w, ok = weights(put, held)                                                # [n, R, 32] canonical, [n]
     nw = engine.fr_neg(bufs.flat(w))
-    # S_t = sum_x [-w_tx] C_tx: n R scalar multiplications, then ceil(log2 R) rounds of additions over the row axis
-    S = engine.g1_scalar_mul(bufs.flat(cx), bufs.flat(nw)).reshape(n, R, 64)
-    m = R
-    while m > 1:
-        h = m // 2
-        s = engine.g1_add(bufs.flat(S[:, :h]), bufs.flat(S[:, h:2 * h])).reshape(n, h, 64)
-        S = bufs.cat([s, S[:, 2 * h:m]], 1) if m & 1 else s
-        m = h + (m & 1)
+    S = row_sums(engine, cx, nw, n, R)
     # T_tx = [-w_tx] K_rho(t,x)
     gathered = bufs.take(put(comp), index.reshape(-1))
     T = engine.g1_scalar_mul(bufs.flat(gathered), bufs.flat(nw)).reshape(n, R, 64)
@@ -130,18 +141,19 @@ def _decrypt(engine, key, pad, c, c_prime, cx, dx, weights):
     return msgs * ok.reshape(n, 1), ok                                         # ok is 0 / 1: a row that cannot be decrypted comes back all zero
 
 
-def decrypt_batch(engine, key, policies_or_padded, c, c_prime, cx, dx):
+def decrypt_batch(engine, key, policies_or_padded, c, c_prime, cx, dx, msm=False):
     """The n messages of n ciphertexts, each under its own policy, for one key.  key = (K [64], L [128], kx: attribute -> [64]) as
     host bytes; policies_or_padded: n (matrix, rho) pairs or the Padded block of pad_policies; c [n, 384], c_prime [n, 128],
     cx [n, R, 64], dx [n, R, 128] with R the padded row count (rows past a policy's own may hold anything: their weight is 0).
     Returns (messages [n, 384], ok [n]); a ciphertext whose policy the key does not satisfy has ok = 0 and an all-zero row.
     Engine calls: fr_lsss_weights (a matrix per ciphertext), fr_neg, g1_scalar_mul twice over n R points with the device scalars,
-    ceil(log2 R) rounds of g1_add, multi_pair with one segment of R + 2 pairs per ciphertext, gt_div."""
+    ceil(log2 R) rounds of g1_add, multi_pair with one segment of R + 2 pairs per ciphertext, gt_div.  With msm=True the first
+    g1_scalar_mul and the rounds of g1_add are ONE g1_multi_scalar_mul (n segments of R terms); the messages are the same bytes."""
     pad = policies_or_padded if isinstance(policies_or_padded, Padded) else pad_policies(policies_or_padded)
 
     def weights(put, held):
         return engine.fr_lsss_weights(put(pad.matrix).reshape(-1), pad.rows, pad.cols, put(held).reshape(-1))
-    return _decrypt(engine, key, pad, c, c_prime, cx, dx, weights)
+    return _decrypt(engine, key, pad, c, c_prime, cx, dx, weights, _row_sums_msm if msm else _row_sums_composed)
 
 
 def decrypt_batch_host_weights(engine, key, policies, c, c_prime, cx, dx):

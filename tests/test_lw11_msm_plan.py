@@ -1,0 +1,59 @@
+"""lw11.decrypt_batch_msm on the oracle engine: the k pairings against H(GID) folded into e(H, sum_x w_x c3x), the sum from ONE
+g2_multi_scalar_mul with the shared weight list — the messages of decrypt_batch byte for byte, with k + 1 pairs per segment."""
+import numpy as np
+
+import gmsm_cases as gc
+from lw11_fixture import Instance, and_or_policy, threshold_policy
+from test_lw11_plan import OracleEngine
+from gopairingbasedcryptography_amd import lw11
+
+
+class OracleEngineMsm(OracleEngine):
+    """+ g2_multi_scalar_mul from the oracle: scalar multiplication per term, the oracle's sum per segment"""
+
+    def g2_multi_scalar_mul(self, bases, scalars, seg_off):
+        x = np.asarray(bases, dtype=np.uint8).reshape(-1, 128)
+        seg = [int(v) for v in seg_off]
+        ks = [int(k) for k in scalars]
+        return gc.expect(self.o, True, x, ks, seg, len(ks) != len(x))
+
+
+def recorded(eng, names):
+    calls = []
+    for name in names:
+        def wrap(*a, _f=getattr(eng, name), _n=name):
+            calls.append((_n, a))
+            return _f(*a)
+        setattr(eng, name, wrap)
+    return calls
+
+
+def run_both(oracle, m, rho, attrs, n_ct, tag):
+    eng = OracleEngineMsm(oracle)
+    inst = Instance(eng, m, rho, attrs, n_ct=n_ct, tag=tag)
+    rows, w = lw11.reconstruction_weights(m, rho, inst.user_attrs)
+    folded = lw11.fold_key(eng, rows, w, inst.h_gid, inst.k_by_row)
+    calls = recorded(eng, ("multi_pair", "g2_multi_scalar_mul", "gt_multi_exp"))
+    want = lw11.decrypt_batch(eng, folded, inst.c0, inst.c1, inst.c2, inst.c3)
+    k = len(rows)
+    assert [(name, [int(v) for v in a[2]]) for name, a in calls if name == "multi_pair"] == [("multi_pair", list(range(0, 2 * k * n_ct + 1, 2 * k)))]
+    del calls[:]
+    got = lw11.decrypt_batch_msm(eng, folded, inst.h_gid, inst.c0, inst.c1, inst.c2, inst.c3)
+    assert (np.asarray(got) == np.asarray(want)).all() and (np.asarray(got) == np.asarray(inst.msgs)).all()
+    pairs = [a for name, a in calls if name == "multi_pair"]
+    assert len(pairs) == 1 and [int(v) for v in pairs[0][2]] == list(range(0, (k + 1) * n_ct + 1, k + 1))                    # k + 1 pairs per segment
+    sums = [a for name, a in calls if name == "g2_multi_scalar_mul"]
+    assert len(sums) == 1 and np.asarray(sums[0][0]).size == n_ct * k * 128 and len(sums[0][1]) == k                         # ONE list for all ciphertexts
+    assert [int(v) for v in sums[0][2]] == list(range(0, k * n_ct + 1, k))
+    return rows, w
+
+
+def test_and_or_policy(oracle):
+    m, rho = and_or_policy()
+    assert run_both(oracle, m, rho, [11, 22, 44, 99], 3, "") == ([0, 1], [1, 1])
+
+
+def test_weights_other_than_one(oracle):
+    m, rho = threshold_policy(3, 4)
+    rows, w = run_both(oracle, m, rho, [rho[0], rho[1], rho[3]], 3, "t")
+    assert rows == [0, 1, 3] and all(x not in (0, 1) for x in w)

@@ -20,6 +20,7 @@
 #include "../gopairingbasedcryptography_amd/csrc/group29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/fr29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/gtmexp29.hip.hpp"
+#include "../gopairingbasedcryptography_amd/csrc/gmsm29.hip.hpp"
 #include <condition_variable>
 #include <mutex>
 #include <thread>
@@ -186,8 +187,50 @@ template <class Get, class Put> static void fr_lsss_block(const LsssGeom &g, uin
         for (uint32_t lane = 0; lane < FR_LSSS_WAVE; lane++) fr_lsss_clear(g, l[lane], c, st[lane], put);
     }
 }
+// segmented multi-scalar multiplication exactly as gpbc_g1/g2_multi_scalar_mul_dev (csrc/gpbc_gmsm.hip) run it: the same plan (gmsm_pieces
+// per level, gmsm_piece_range per piece), the same lane functions (gmsm_lane; gmsm_sum_lane for K = null and for the folds), one piece
+// per lane, the lanes one after the other; a piece's segment range is gmsm_segment_range's, the function the kernel calls.
+template <class F, class LoadA, class StoreA> static void gmsm_host(const uint8_t *B, const uint8_t *K, size_t nk, const uint64_t *seg_off, size_t n, size_t n_seg, uint8_t *out,
+                                                                     size_t pt, LoadA ld, StoreA st) {
+    std::vector<uint8_t> val[2];
+    std::vector<int32_t> block(gmsm_lane_dwords<F>() + 32);
+    int32_t *ws = block.data();
+    while ((uintptr_t)ws & 127) ws++;                      // the lane's block: 128-byte aligned like the device's
+    const uint8_t *x = B;
+    const bool shared = K && nk != n;
+    size_t cur_n = n, m = 0;                               // m: uniform segment length of the fold levels (seg_off = null there)
+    for (int level = 0;; level++) {
+        const size_t J = gmsm_pieces(cur_n, n_seg, K != nullptr), pieces = n_seg * J;
+        uint8_t *dst = out;
+        if (J > 1) { val[level & 1].assign(pieces * pt, 0); dst = val[level & 1].data(); }
+        for (size_t P = 0; P < pieces; P++) {
+            size_t lo, hi, a, b;
+            gmsm_segment_range(seg_off, m, cur_n, P / J, shared ? nk : 0, lo, hi);
+            gmsm_piece_range(lo, hi, P % J, J, a, b);
+            const size_t k0 = shared ? lo : 0;
+            auto base = [&](size_t i) { return ld(x + (a + i) * pt); };
+            JacP<F> r = K ? gmsm_lane<F>(b - a, base, [&](size_t i, uint32_t *k) { memcpy(k, K + 32 * (a + i - k0), 32); }, ws) : gmsm_sum_lane<F>(b - a, base);
+            AffP<F> o;
+            jac_to_affine(o, r);
+            st(dst + P * pt, o);
+        }
+        if (J == 1) return;
+        x = dst; K = nullptr; seg_off = nullptr; m = J; cur_n = pieces;
+    }
+}
 extern "C" {
 
+// out[s] = sum_{i in [seg_off[s], seg_off[s+1])} [K_i] B_i; nk = n, or one list of nk scalars for all segments; K null = plain sums
+void hc_multi_scalar_mul(int is_g2, const uint8_t *B, const uint8_t *K, size_t nk, const uint64_t *seg_off, size_t n, size_t n_seg, uint8_t *out) {
+    if (is_g2)
+        gmsm_host<F2>(B, K, nk, seg_off, n, n_seg, out, 128, [](const uint8_t *p) { return AffP<F2>{f2_load(p), f2_load(p + 64), bytes_all_zero(p, 32)}; },
+                      [](uint8_t *p, const AffP<F2> &r) { f2_store(p, r.x); f2_store(p + 64, r.y); });
+    else
+        gmsm_host<Fe>(B, K, nk, seg_off, n, n_seg, out, 64, [](const uint8_t *p) { return AffP<Fe>{fe_load(p), fe_load(p + 32), bytes_all_zero(p, 16)}; },
+                      [](uint8_t *p, const AffP<Fe> &r) { fe_store(p, r.x); fe_store(p + 32, r.y); });
+    stats_flush();
+}
+int hc_gmsm_group(int is_g2) { (void)is_g2; return GMSM_GROUP; }
 // one pairing per "wavefront": Miller loop and final exponentiation of the latency form (k_miller_wide / k_final_exp_wide)
 void hc_pair_wide(const uint8_t *P, const uint8_t *Q, size_t n, uint8_t *out, int do_final_exp) {
     for (size_t i = 0; i < n; i++) {
