@@ -1,7 +1,7 @@
 """Compile libgpbc_bn254.so for gfx950 with hipcc (in-tree, next to this file).
 
-Nine translation units (csrc/gpbc_core.hip, gpbc_pairing.hip, gpbc_curve.hip, gpbc_wire.hip, gpbc_msm.hip, gpbc_group.hip, gpbc_fr.hip, gpbc_gtmexp.hip,
-gpbc_gmsm.hip) are compiled in parallel and
+Ten translation units (csrc/gpbc_core.hip, gpbc_pairing.hip, gpbc_curve.hip, gpbc_wire.hip, gpbc_msm.hip, gpbc_group.hip, gpbc_fr.hip, gpbc_gtmexp.hip,
+gpbc_gmsm.hip, gpbc_subset.hip) are compiled in parallel and
 linked into one shared library; every unit carries its own device code (no relocatable device code is needed: kernels are
 launched from the unit that defines them)."""
 import hashlib
@@ -14,9 +14,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgpbc_bn254.so")
 STAMP = os.path.join(HERE, "libgpbc_bn254.buildhash")
-SOURCES = ["gpbc_core.hip", "gpbc_pairing.hip", "gpbc_curve.hip", "gpbc_wire.hip", "gpbc_msm.hip", "gpbc_group.hip", "gpbc_fr.hip", "gpbc_gtmexp.hip", "gpbc_gmsm.hip"]
+SOURCES = ["gpbc_core.hip", "gpbc_pairing.hip", "gpbc_curve.hip", "gpbc_wire.hip", "gpbc_msm.hip", "gpbc_group.hip", "gpbc_fr.hip", "gpbc_gtmexp.hip", "gpbc_gmsm.hip", "gpbc_subset.hip"]
 HEADERS = ["gpbc_common.hpp", "fe29.hip.hpp", "tower29.hip.hpp", "tower29_pair.hip.hpp", "curve29.hip.hpp", "pairing29.hip.hpp", "pairing29_pair.hip.hpp", "wide29.hip.hpp", "curve29_quad.hip.hpp", "curve29_oct.hip.hpp",
-           "wire29.hip.hpp", "h2c29.hip.hpp", "xmd29.hip.hpp", "msm29.hip.hpp", "group29.hip.hpp", "fr29.hip.hpp", "gtmexp29.hip.hpp", "gmsm29.hip.hpp", "bn254_constants.hip.hpp", "bn254_constants29.hip.hpp"]
+           "wire29.hip.hpp", "h2c29.hip.hpp", "xmd29.hip.hpp", "msm29.hip.hpp", "group29.hip.hpp", "fr29.hip.hpp", "gtmexp29.hip.hpp", "gmsm29.hip.hpp", "subset29.hip.hpp", "bn254_constants.hip.hpp", "bn254_constants29.hip.hpp"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
 # host-only measurement program over the C ABI (bench.py runs it: calls/s of concurrent one-element calls); built next to the library
 CALLS_SRC = os.path.join(HERE, "..", "tools", "concurrent_calls.cpp")
@@ -25,7 +25,7 @@ CALLS_EXE = os.path.join(HERE, "gpbc_concurrent_calls")
 
 def _source_hash():
     h = hashlib.sha256(" ".join(FLAGS).encode())
-    deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS] + [os.path.join(HERE, "..", "include", name) for name in ("gpbc_bn254.h", "gpbc_bn254_ext.h")] + [CALLS_SRC]
+    deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS] + [os.path.join(HERE, "..", "include", name) for name in ("gpbc_bn254.h", "gpbc_bn254_ext.h", "gpbc_bn254_subset.h")] + [CALLS_SRC]
     for d in deps:
         with open(d, "rb") as f:
             h.update(f.read())

@@ -63,6 +63,13 @@ EXT_SIGNATURES = {
     "gpbc_multi_scalar_mul_workspace_bytes": "z:zzi", "gpbc_g1_multi_scalar_mul_dev": "i:ppzpzzppzp",
     "gpbc_g2_multi_scalar_mul_dev": "i:ppzpzzppzp",
 }
+# ... and for include/gpbc_bn254_subset.h, the bit-selected sums over a fixed set (tests/test_subset_sum.py holds this table against
+# that header).  The three tables are disjoint.
+SUBSET_SIGNATURES = {
+    "gpbc_subset_version": "i:", "gpbc_subset_table_bytes": "z:zi", "gpbc_g1_subset_table_create": "i:pzpp",
+    "gpbc_g2_subset_table_create": "i:pzpp", "gpbc_subset_table_create_dev": "i:ipzppp", "gpbc_subset_sum": "i:ppzp",
+    "gpbc_subset_sum_workspace_bytes": "z:pz", "gpbc_subset_sum_dev": "i:ppzppzp", "gpbc_subset_table_destroy": "i:p",
+}
 # every pointer is a c_void_p: it takes ints, None, c_void_p, ctypes arrays, byref() and ndarray.ctypes.data_as() alike
 _CTYPES = {"p": ctypes.c_void_p, "z": ctypes.c_size_t, "i": ctypes.c_int, "l": ctypes.c_long, "s": ctypes.c_char_p}
 
@@ -88,7 +95,7 @@ def load():
         except ImportError:
             pass
         lib = ctypes.CDLL(LIB_PATH)
-        for name, sig in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
+        for name, sig in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(SUBSET_SIGNATURES.items()):
             ret, params = sig.split(":")
             fn = getattr(lib, name)
             fn.restype = _CTYPES[ret]

@@ -1049,3 +1049,154 @@ class FixedBase:
             self.close()
         except Exception:
             pass
+
+
+# --------------------------------------------------------------------------------------- bit-selected sums over a fixed set
+SUBSET_MAX_BITS = 16384
+
+
+def _subset_points(bases, offset, width):
+    """(kind, bases, nbits, offset) of a table's points, checked: whole points, 1 .. SUBSET_MAX_BITS of them, an offset of exactly one"""
+    dev = bufs.device_of(bases, offset)
+    bases, nbits = bufs.rows(bases, width, "bases")
+    if not 1 <= nbits <= SUBSET_MAX_BITS:
+        raise ValueError("a subset table takes 1 .. %d bases (got %d)" % (SUBSET_MAX_BITS, nbits))
+    if offset is not None:
+        offset, k = bufs.rows(offset, width, "offset")
+        if k != 1:
+            raise ValueError("offset must be one point of %d bytes" % width)
+    return dev, bases, nbits, offset
+
+
+def _subset_masks(masks, nbits):
+    """(kind, flat masks, n): masks as n rows of W = ceil(nbits / 8) bytes.  [n, W] uint8 (array or CUDA tensor) goes as it is; a host
+    [n, nbits] array of 0 / 1 is packed with numpy.packbits (most significant bit first: the reference's Id[] order).  For nbits = 1
+    both shapes are [n, 1]: the row is then the packed byte (0x80 selects the base)."""
+    W = (nbits + 7) // 8
+    dev = bufs.device_of(masks)
+    if dev is None:
+        try:
+            masks = np.asarray(masks)
+        except ValueError:
+            raise ValueError("masks must be a rectangular [n, %d] byte array or [n, %d] 0 / 1 array" % (W, nbits)) from None
+        if masks.dtype == object:
+            raise ValueError("masks must be a rectangular [n, %d] byte array or [n, %d] 0 / 1 array" % (W, nbits))
+    if masks.ndim != 2 or masks.shape[1] not in (W, nbits):
+        raise ValueError("masks must be [n, %d] bytes or [n, %d] bits (got shape %s)" % (W, nbits, tuple(masks.shape)))
+    if masks.shape[1] != W:
+        if dev is not None:
+            raise ValueError("device masks must be packed: [n, %d] uint8" % W)
+        if ((masks != 0) & (masks != 1)).any():
+            raise ValueError("a bit array may hold only 0 and 1")
+        masks = np.packbits(masks.astype(np.uint8), axis=1)
+    elif dev is None and (masks.dtype.kind not in "ui" or masks.size and (masks.min() < 0 or masks.max() > 255)):
+        raise ValueError("mask bytes must be integers in 0 .. 255")
+    flat, n = bufs.rows(masks, W, "masks")
+    return dev, flat, n
+
+
+class SubsetTable:
+    """Subset-sum tables of a fixed set of points over 8-bit windows of a BIT STRING, kept in HBM (include/gpbc_bn254_subset.h):
+    afterwards  offset + sum_{i : bit i} bases[i]  costs one mixed addition per mask byte and no doublings, from the mask alone.
+    Serves the Waters hash U' + sum_{Id[i]=1} U_i (ibe/waters05_ibe/waters05_ibe.go:172-179, 226-233) and sums of members' keys under
+    a participation bitmap.  256 rows of 128 B (G1) / 256 B (G2) per 8 bases: 2 MiB for Waters05's 256 G2 points.
+
+        t = SubsetTable(bases, offset=None, g2=False)   # bases: [nbits, 64|128] uint8, offset: one point or None (numpy or CUDA tensors)
+        out = t.sum(masks)                              # masks: [n, ceil(nbits / 8)] uint8 (bit 7 - t of byte w selects bases[8 w + t],
+                                                        # numpy.packbits' order) or a host [n, nbits] 0 / 1 array -> [n, 64|128]
+
+    Device points are read by a build enqueued on the current torch stream (the table keeps them alive); host masks give a host
+    array, CUDA masks a CUDA tensor enqueued on the current stream and not synchronised.  Argument errors are ValueError before any C call."""
+
+    def __init__(self, bases, offset=None, g2=False):
+        self.g2 = bool(g2)
+        self.width = G2_BYTES if g2 else G1_BYTES
+        self._h = ctypes.c_void_p()
+        dev, bases, self.nbits, offset = _subset_points(bases, offset, self.width)
+        self.W = (self.nbits + 7) // 8
+        self._lib = _lib.load()
+        off = None if offset is None else bufs.address(offset)
+        # called directly, as FixedBase does: one host symbol per group, the device symbol takes the group as a flag and the stream before the handle
+        if dev is None:
+            _ensure_init()
+            fn = self._lib.gpbc_g2_subset_table_create if g2 else self._lib.gpbc_g1_subset_table_create
+            _lib.check(fn(bufs.address(bases), self.nbits, off, ctypes.byref(self._h)))
+        else:
+            _bind(dev)
+            _lib.check(self._lib.gpbc_subset_table_create_dev(int(self.g2), bufs.address(bases), self.nbits, off, _torch_stream(), ctypes.byref(self._h)))
+            self._points = (bases, offset)                       # the build may still be reading them
+            self._build_stream = _current_stream()               # ... and is ordered on this stream alone (see _after_build)
+
+    _points = _build_stream = None
+
+    def _after_build(self, dev):
+        """A table built from device points is ordered on the stream it was built on.  The host form runs on a stream of the library's
+        own, so it waits for the build once; a device sum on another torch stream is put behind the build."""
+        if self._build_stream is None:
+            return
+        if dev is None:
+            self._build_stream.synchronize()
+            self._points = self._build_stream = None
+        elif _current_stream() != self._build_stream:
+            _current_stream().wait_stream(self._build_stream)
+
+    def table_bytes(self):
+        return int(self._lib.gpbc_subset_table_bytes(self.nbits, int(self.g2)))
+
+    def workspace_bytes(self, n):
+        return int(self._lib.gpbc_subset_sum_workspace_bytes(self._h, n))
+
+    def sum(self, masks, out=None, workspace=None):
+        dev, masks, n = _subset_masks(masks, self.nbits)
+        bufs.device_of(masks, out)
+        out = bufs.output(out, (n, self.width), dev)
+        if not self._h:
+            raise ValueError("the table is closed")
+        if dev is None:
+            if workspace is not None:
+                raise ValueError("only the device form takes a workspace")
+            self._after_build(None)
+            _call("subset_sum", None, self._h, masks, n, out)
+            return out
+        _bind(dev)
+        self._after_build(dev)
+        need = self.workspace_bytes(n)
+        ws = (None, 0) if not need and workspace is None else _workspace(workspace, need, dev)
+        _call("subset_sum", dev, self._h, masks, n, out, *ws)
+        return out
+
+    def close(self):
+        if self._h:
+            self._lib.gpbc_subset_table_destroy(self._h)
+            self._h = ctypes.c_void_p()
+            self._points = self._build_stream = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _subset_sum(g2, bases, masks, offset, out):
+    width = G2_BYTES if g2 else G1_BYTES
+    pdev, bases, nbits, offset = _subset_points(bases, offset, width)
+    dev, flat, n = _subset_masks(masks, nbits)
+    if (pdev is None) != (dev is None) or (dev is not None and dev != pdev):
+        raise ValueError("the buffers of one call must all be CUDA tensors on one device or all host buffers")
+    bufs.device_of(flat, out)
+    out = bufs.output(out, (n, width), dev)
+    table = SubsetTable(bases, offset, g2=g2)
+    try:
+        return table.sum(flat.reshape(n, -1), out=out)
+    finally:
+        table.close()                                            # drains the device: the result is there on return
+
+
+def g1_subset_sum(bases, masks, offset=None, out=None):
+    """out[m] = offset + sum_{i : bit i of masks[m]} bases[i] in G1 with a table built for this one call (SubsetTable keeps it)."""
+    return _subset_sum(False, bases, masks, offset, out)
+
+
+def g2_subset_sum(bases, masks, offset=None, out=None):
+    return _subset_sum(True, bases, masks, offset, out)

@@ -121,6 +121,9 @@ constexpr size_t MSM_MIN_TERMS = 16384;
 constexpr int MSM_SKEWED = 1;                     // msm_dev: the scalars are too unevenly spread for buckets (not an error; nothing was written)
 constexpr uint32_t MSM_MAX_BUCKET_BASE = 256;     // longest bucket accepted: this + 8 x the mean bucket length
 int msm_dev(bool g2, const void *d_bases, const void *d_scalars, size_t n, void *d_out, hipStream_t st);
+// One level of the point-sum tree (gpbc_curve.hip): out[t] = in[t] + in[t + n_out] + ... over n_in affine points, t < n_out; asynchronous
+// on `st`.  Folds chunk-major partial sums (partial[c * n + m], n_out = n) in one launch.
+int point_sum_strided_dev(bool g2, const void *d_in, size_t n_in, void *d_out, size_t n_out, hipStream_t st);
 // RCCL communicator of the current device (gpbc_core.hip): number of ranks (0 = none), this device's rank, all-gather
 int comm_ranks();
 int comm_rank();

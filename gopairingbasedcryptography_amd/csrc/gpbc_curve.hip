@@ -198,6 +198,12 @@ GPBC_KERNEL k_g2_fb_msm_quad(const int32_t *__restrict__ table, const uint8_t *_
     fb_msm_lane<F2, true>(table, base_inf, nbase, scalars, n_msm, C, n_chunks, partial);
 }
 
+// one launch of the strided point sum for the other units (gpbc_common.hpp): out[t] = in[t] + in[t + n_out] + in[t + 2 n_out] + ...
+int point_sum_strided_dev(bool g2, const void *d_in, size_t n_in, void *d_out, size_t n_out, hipStream_t st) {
+    if (g2) return GPBC_LAUNCH(k_g2_sum_level, grid_for(n_out), BLOCK, st, (const uint8_t *)d_in, n_in, (uint8_t *)d_out, n_out);
+    return GPBC_LAUNCH(k_g1_sum_level, grid_for(n_out), BLOCK, st, (const uint8_t *)d_in, n_in, (uint8_t *)d_out, n_out);
+}
+
 extern "C" {
 
 constexpr size_t FB_AUTO_MIN = 16384;

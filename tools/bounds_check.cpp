@@ -21,6 +21,7 @@
 #include "../gopairingbasedcryptography_amd/csrc/fr29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/gtmexp29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/gmsm29.hip.hpp"
+#include "../gopairingbasedcryptography_amd/csrc/subset29.hip.hpp"
 #include <condition_variable>
 #include <mutex>
 #include <thread>
@@ -218,8 +219,69 @@ template <class F, class LoadA, class StoreA> static void gmsm_host(const uint8_
         x = dst; K = nullptr; seg_off = nullptr; m = J; cur_n = pieces;
     }
 }
+// bit-selected sums exactly as gpbc_subset_sum_dev (csrc/gpbc_subset.hip) runs them: subset_entry per table row, subset_shape's chunks,
+// subset_lane per (item, chunk), the chunk-major partial sums folded as the strided point-sum kernel folds them.  Only the rows the
+// masks reach are built (a row depends on nothing but its own (w, v)), plus the row a window past W reads.  n_shape != 0: the chunks of
+// a call of n_shape items (so that a few items walk the one long chain of a call that fills the chip).
+template <class F, class LoadA, class StoreA> static void subset_host(const uint8_t *B, size_t nbits, const uint8_t *O, const uint8_t *masks, size_t n, size_t n_shape, uint8_t *out,
+                                                                       size_t pt, LoadA ld, StoreA st) {
+    const size_t W = subset_windows(nbits), entries = subset_entries(nbits);
+    constexpr size_t ED = (size_t)TabLayout<F>::ENTRY_DWORDS;
+    std::vector<int32_t> mem(entries * ED + 32);
+    int32_t *table = mem.data();
+    while ((uintptr_t)table & 127) table++;                // rows 128-byte aligned like the device's
+    std::vector<uint8_t> flags(entries, 0), built(entries, 0);
+    AffP<F> off;
+    if (O) off = ld(O);
+    auto build = [&](size_t e) {
+        if (built[e]) return;
+        AffP<F> a;
+        subset_entry<F>(a, [&](size_t i) { return ld(B + i * pt); }, nbits, O ? &off : nullptr, e >> 8, (int)(e & 255));
+        subset_entry_store<F>(table, flags.data(), e, a);
+        built[e] = 1;
+    };
+    build((W - 1) * 256);
+    for (size_t m = 0; m < n; m++)
+        for (size_t w = 0; w < W; w++) build(w * 256 + masks[m * W + w]);
+    size_t C, n_chunks;
+    subset_shape(W, n_shape ? n_shape : n, C, n_chunks);
+    std::vector<uint8_t> partial(n_chunks > 1 ? n_chunks * n * pt : 0);
+    uint8_t *dst = n_chunks > 1 ? partial.data() : out;
+    for (size_t t = 0; t < n * n_chunks; t++) {
+        const size_t m = t % n, c = t / n;
+        JacP<F> acc = subset_lane<F>(table, flags.data(), masks + m * W, W, c * C, C);
+        AffP<F> a;
+        jac_to_affine(a, acc);
+        st(dst + t * pt, a);
+    }
+    if (n_chunks > 1)
+        for (size_t t = 0; t < n; t++) {
+            JacP<F> acc;
+            jac_set_inf(acc);
+            for (size_t i = t; i < n * n_chunks; i += n) jac_add_mixed(acc, acc, ld(dst + i * pt));
+            AffP<F> r;
+            jac_to_affine(r, acc);
+            st(out + t * pt, r);
+        }
+}
 extern "C" {
 
+// out[m] = O + sum_{i : bit i of masks row m} B_i; O null = no offset; masks: n rows of ceil(nbits / 8) bytes
+void hc_subset_sum(int is_g2, const uint8_t *B, size_t nbits, const uint8_t *O, const uint8_t *masks, size_t n, size_t n_shape, uint8_t *out) {
+    if (is_g2)
+        subset_host<F2>(B, nbits, O, masks, n, n_shape, out, 128, [](const uint8_t *p) { return AffP<F2>{f2_load(p), f2_load(p + 64), bytes_all_zero(p, 32)}; },
+                        [](uint8_t *p, const AffP<F2> &r) { f2_store(p, r.x); f2_store(p + 64, r.y); });
+    else
+        subset_host<Fe>(B, nbits, O, masks, n, n_shape, out, 64, [](const uint8_t *p) { return AffP<Fe>{fe_load(p), fe_load(p + 32), bytes_all_zero(p, 16)}; },
+                        [](uint8_t *p, const AffP<Fe> &r) { fe_store(p, r.x); fe_store(p + 32, r.y); });
+    stats_flush();
+}
+// [max bits, windows per chunk at least, chunks of a call of n items over W windows, windows per chunk of it]
+void hc_subset_shape(size_t W, size_t n, size_t *out4) {
+    size_t C, n_chunks;
+    subset_shape(W, n, C, n_chunks);
+    out4[0] = SUBSET_MAX_BITS; out4[1] = SUBSET_CHUNK_MIN; out4[2] = n_chunks; out4[3] = C;
+}
 // out[s] = sum_{i in [seg_off[s], seg_off[s+1])} [K_i] B_i; nk = n, or one list of nk scalars for all segments; K null = plain sums
 void hc_multi_scalar_mul(int is_g2, const uint8_t *B, const uint8_t *K, size_t nk, const uint64_t *seg_off, size_t n, size_t n_seg, uint8_t *out) {
     if (is_g2)
