@@ -61,7 +61,7 @@ GPBC_KERNEL k_miller_lines(const uint8_t *__restrict__ P, const uint8_t *__restr
     G1A a{fe_load(p), fe_load(p + 32)};
     G2A b{f2_load(q), f2_load(q + 64)};
     int step = 0;
-    miller_lines(a, b, [&](const LineS &l) { line_store(lines, stride, i, step++, l); });
+    miller_lines<true>(a, b, [&](const LineS &l) { line_store(lines, stride, i, step++, l); });
 }
 
 // Phase B and the final exponentiation run with one pairing per LANE PAIR (even lane: C0, odd lane: C1 of every Fp12
@@ -108,7 +108,7 @@ GPBC_KERNEL k_miller_pipelined(const uint8_t *__restrict__ P, const uint8_t *__r
         G1A a{fe_load(p), fe_load(p + 32)};
         G2A b{f2_load(q), f2_load(q + 64)};
         int step = 0;
-        miller_lines(a, b, [&](const LineS &l) {
+        miller_lines<true>(a, b, [&](const LineS &l) {
             line_store(lines, stride, i, step++, l);
             __hip_atomic_store(progress + i, (uint32_t)step, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
         });
@@ -135,7 +135,7 @@ GPBC_KERNEL k_miller_pipelined(const uint8_t *__restrict__ P, const uint8_t *__r
                     G1A a{fe_load(p), fe_load(p + 32)};
                     G2A b{f2_load(q), f2_load(q + 64)};
                     int s2 = 0;
-                    miller_lines(a, b, [&](const LineS &l) { line_store(lines, stride, i, s2++, l); });
+                    miller_lines<true>(a, b, [&](const LineS &l) { line_store(lines, stride, i, s2++, l); });
                     __threadfence();
                 }
             }
@@ -196,7 +196,8 @@ GPBC_KERNEL k_miller_accumulate_chunks(const uint8_t *__restrict__ P, const uint
 // Fixed-Q multi-pairing (gpbc_multi_pair_fixed_q): k segments pair their own m points P[j*m + i] with ONE shared list
 // Q[0..m) — a BSW07 key against k ciphertexts, a public key against k signatures.  The raw line coefficients of every Q_i
 // are computed once (k_q_lines: 88 x 54 int32 per Q_i, laid out [line][word][i]) and scaled to c0 = 1 (k_q_lines_scale), the
-// P's become (x/y, 1/y) in internal form once (k_g1_line_point), and the accumulator kernel evaluates a line at its own P (two
+// P's become (x/2y, 1/2y) in internal form once (k_g1_line_point: half the point gives half the line, which is what the four-product
+// sparse multiplication takes), and the accumulator kernel evaluates a line at its own P (two
 // Fp x Fp2 products, one per lane of the pair) right before the sparse multiplication.  Lane pairs are numbered chunk-major (t = c * k + j): the 32 lane pairs of a wave then work on
 // the same Q_i at the same time, so their line loads are one broadcast transaction.
 // A chunk here may be much longer than MULTI_CHUNK: the lines live once per Q_i, not once per (pair, slot), so the only cost of a
@@ -232,16 +233,18 @@ GPBC_KERNEL k_q_lines_scale(const int32_t *__restrict__ qlines, int32_t *__restr
 #pragma unroll
         for (int w = 0; w < NL; w++) o[(size_t)(e * NL + w) * m] = fe[e]->v[w];
 }
-// The evaluation point of such a line: (x / y, 1 / y) in internal limbs (the division by yP is the Fp factor that makes c0 = 1).
-// 20 int32 per point: x/y (9), 1/y (9), infinity flag, pad.  One lane converts LINE_POINT_GROUP consecutive points with ONE Fp
+// The evaluation point of such a line, HALVED: (x / 2y, 1 / 2y) in internal limbs (the division by yP is the Fp factor that makes
+// c0 = 1; the accumulator's four-product sparse multiplication takes half the line, f12p_mul_34_half).
+// 20 int32 per point: x/2y (9), 1/2y (9), infinity flag, pad.  One lane converts LINE_POINT_GROUP consecutive points with ONE Fp
 // inversion (fe_batch_inverse); a zero y — infinity, or a point outside the group — does not spoil its neighbours.
 constexpr int LINE_POINT_GROUP = 8;
 GPBC_KERNEL_G1 k_g1_line_point(const uint8_t *__restrict__ P, int32_t *__restrict__ out, size_t n) {
     const size_t base = ((size_t)blockIdx.x * BLOCK + threadIdx.x) * LINE_POINT_GROUP;
     if (base >= n) return;
     const int cnt = n - base < (size_t)LINE_POINT_GROUP ? (int)(n - base) : LINE_POINT_GROUP;
-    fe_batch_inverse<LINE_POINT_GROUP>(cnt, [&](int j) { return fe_load(P + (base + j) * GPBC_G1_BYTES + 32); }, [&](int j, const Fe &yinv) {
+    fe_batch_inverse<LINE_POINT_GROUP>(cnt, [&](int j) { return fe_load(P + (base + j) * GPBC_G1_BYTES + 32); }, [&](int j, const Fe &y_inverse) {
         const uint8_t *pb = P + (base + j) * GPBC_G1_BYTES;
+        const Fe yinv = fe_halve(y_inverse);
         Fe xoy = fe_mul(fe_load(pb), yinv);
         int32_t *o = out + (base + j) * 20;
 #pragma unroll
@@ -265,12 +268,12 @@ GPBC_KERNEL k_miller_accumulate_fixed_q(const int32_t *__restrict__ Pint, const 
     if (n == 0) h = f12p_one(x);
     else h = miller_accumulate_multi_34(x, n, [&](int p, int li) -> Line34 {
         const size_t i = (size_t)vi[p];
-        // the line at P: c3 = (r1 / r0) (xP / yP), c4 = (r2 / r0) / yP.  Both lanes of the pair need both; each loads ONE coefficient
+        // half the line at P: c3 / 2 = (r1 / r0) (xP / 2yP), c4 / 2 = (r2 / r0) / 2yP.  Both lanes of the pair need both; each loads ONE coefficient
         // of the table row (the same address for all even / all odd lanes of the wave) and ONE coordinate, computes its Fp x Fp2
         // product (even lane c3, odd lane c4), and they swap the products.  (The LDS stage of k_miller_accumulate was tried here as
         // well and is 1 % SLOWER: these loads hit L2 — the table row is shared by the whole grid — and have little latency to hide.)
         const int32_t *lb = q34 + ((size_t)li * LINE34_WORDS + (x.odd ? 2 * NL : 0)) * m + i;
-        const int32_t *pp = Pint + (j * m + i) * 20 + (x.odd ? NL : 0);                 // odd: 1 / yP, even: xP / yP
+        const int32_t *pp = Pint + (j * m + i) * 20 + (x.odd ? NL : 0);                 // odd: 1 / 2yP, even: xP / 2yP
         F2 coef;
         Fe pc;
 #pragma unroll

@@ -89,10 +89,14 @@ GPBC_INLINE LineS line_scale(const LineE &l, const G1A &p) { return LineS{f2_mul
 // an Fp factor, which the final exponentiation removes — and the LAST line carries the constant t^-N (F29_ISO_KFIX, derived in
 // tools/gen_constants.py iso_twist_constants) that cancels their product, so that the Miller value itself, not only the pairing, is
 // the one the other forms and gnark's MillerLoop give.
-template <class Sink> GPBC_INLINE void miller_lines(const G1A &p0, const G2A &q0, Sink &&sink) {
-    constexpr int32_t T2[NL] = F29_ISO_T2, T3[NL] = F29_ISO_T3, KF[NL] = F29_ISO_KFIX;
+// X2: the lines for the accumulator whose sparse products come out DOUBLED (miller_accumulate_pair, f12p_mul_034_x2).  Every line
+// carries 2 c0 in place of c0 (yP is mapped by 2 t^3 instead of t^3: the doubling the seven-product form needs on its c0 half), and
+// the last line's constant is t^-N 2^-E (F29_ISO_KFIX_X2), E = the twos of the 88 lines weighted by the squarings that follow them,
+// so that the Miller value is again exactly the one above.
+template <bool X2 = false, class Sink> GPBC_INLINE void miller_lines(const G1A &p0, const G2A &q0, Sink &&sink) {
+    constexpr int32_t T2[NL] = F29_ISO_T2, T3[NL] = F29_ISO_T3, KF[NL] = F29_ISO_KFIX, T3X2[NL] = F29_ISO_T3_X2, KFX2[NL] = F29_ISO_KFIX_X2;
     const Fe t2 = fe_const(T2), t3 = fe_const(T3);
-    const G1A p{fe_mul(p0.x, t2), fe_mul(p0.y, t3)};
+    const G1A p{fe_mul(p0.x, t2), fe_mul(p0.y, fe_const(X2 ? T3X2 : T3))};
     const G2A q{f2_mul_fe(q0.x, t2), f2_mul_fe(q0.y, t3)};
     G2P t{q.x, q.y, f2_one()};
     const F2 ny = f2_neg(q.y);
@@ -111,7 +115,7 @@ template <class Sink> GPBC_INLINE void miller_lines(const G1A &p0, const G2A &q0
     g2_add_step(t, l, q1);
     sink(line_scale(l, p));
     g2_line_step(t, l, q2);
-    const Fe k = fe_const(KF);
+    const Fe k = fe_const(X2 ? KFX2 : KF);
     sink(LineS{f2_mul_fe(l.r0, fe_mul(p.y, k)), f2_mul_fe(l.r1, fe_mul(p.x, k)), f2_mul_fe(l.r2, k)});
 }
 

@@ -16,25 +16,27 @@ namespace gpbc {
 // but the operands' round trips through private memory doubled the wait share (14 -> 29 % of wave-cycles) and the kernel went from
 // 56.1 to 66.5 ms on the same box — profiles/r03_variant_line_pairs.txt.  Two F6 operands, the parked product and the operand sums
 // do not fit 256 registers, and this kernel's LDS holds the line stage.)
+// The lines are those of miller_lines<true>: c0 holds 2 c0, every sparse product returns twice the product in seven F2 products per
+// lane (f12p_mul_034_x2), the first line enters doubled as well, and the last line's constant cancels all the twos.
 template <class X, class Src> GPBC_INLINE F6 miller_accumulate_pair(const X &x, Src &&next) {
     // the accumulator stays positive-normalised throughout (PN forms: every step ends in a normalisation), so the F6 products inside
     // run in the subtractive Karatsuba form with no operand normalisations
     LineS l0 = next();
-    F6 h = f6_norm(f6_sel(x.odd, F6{l0.c3, l0.c4, f2_zero()}, F6{l0.c0, f2_zero(), f2_zero()}));
+    F6 h = f6_norm(f6_sel(x.odd, F6{f2_dbl(l0.c3), f2_dbl(l0.c4), f2_zero()}, F6{l0.c0, f2_zero(), f2_zero()}));
     for (int i = BN254_ATE_NAF_LEN - 2; i >= 0; i--) {
         if (i != BN254_ATE_NAF_LEN - 2) {
             h = f12p_sqr<true>(x, h);
             LineS l = next();
-            h = f12p_mul_034<true>(x, h, l.c0, l.c3, l.c4);
+            h = f12p_mul_034_x2(x, h, l.c0, l.c3, l.c4);
         }
         if (ate_naf_digit(i) != 0) {
             LineS l = next();
-            h = f12p_mul_034<true>(x, h, l.c0, l.c3, l.c4);
+            h = f12p_mul_034_x2(x, h, l.c0, l.c3, l.c4);
         }
     }
     for (int k = 0; k < 2; k++) {
         LineS l = next();
-        h = f12p_mul_034<true>(x, h, l.c0, l.c3, l.c4);
+        h = f12p_mul_034_x2(x, h, l.c0, l.c3, l.c4);
     }
     return h;
 }
@@ -72,18 +74,20 @@ template <class X, class LineAt> GPBC_INLINE F6 miller_accumulate_multi(const X 
     return h;
 }
 
-// The same for lines scaled to c0 = 1 (fixed-Q table: Line34 = the w and vw coefficients).  With five F2 products per lane a
-// sparse product is cheaper than half of (line product + full product), so the lines enter one by one.
+// The same for lines scaled to c0 = 1 (fixed-Q table: the w and vw coefficients).  With four F2 products per lane a sparse product is
+// cheaper than half of (line product + full product), so the lines enter one by one.  line(p, li) yields HALF the line, (c3 / 2,
+// c4 / 2): that is what the four-product form takes (f12p_mul_34_half), and the caller gets it for nothing by halving the evaluation
+// point once.
 struct Line34 { F2 c3, c4; };
 template <class X, class LineAt> GPBC_INLINE F6 miller_accumulate_multi_34(const X &x, int m, LineAt &&line) {
     int li = 0;
     auto mul_lines = [&](F6 h, int from) {
-        for (int p = from; p < m; p++) { Line34 l = line(p, li); h = f12p_mul_34<true>(x, h, l.c3, l.c4); }
+        for (int p = from; p < m; p++) { Line34 l = line(p, li); h = f12p_mul_34_half(x, h, l.c3, l.c4); }
         li++;
         return h;
     };
     Line34 l0 = line(0, li);
-    F6 h = f6_norm(f6_sel(x.odd, F6{l0.c3, l0.c4, f2_zero()}, F6{f2_one(), f2_zero(), f2_zero()}));   // positive-normalised from here on (PN forms)
+    F6 h = f6_norm(f6_sel(x.odd, F6{f2_dbl(l0.c3), f2_dbl(l0.c4), f2_zero()}, F6{f2_one(), f2_zero(), f2_zero()}));   // positive-normalised from here on (PN forms)
     h = mul_lines(h, 1);
     for (int i = BN254_ATE_NAF_LEN - 2; i >= 0; i--) {
         if (i != BN254_ATE_NAF_LEN - 2) h = mul_lines(f12p_sqr<true>(x, h), 0);

@@ -233,6 +233,26 @@ template <bool RX> GPBC_INLINE F6 f6_mul_01_pn_t(const F6 &x, const F2 &c0, cons
     F2 t2 = f2_add(f2_sub(a, f2_mul(f2_sub(x.b0, x.b2), c0)), b);
     return F6{t0, t1, f2_norm(t2)};
 }
+// That sparse product in FOUR F2 products instead of five.  q(v) = x(v)(c0 + c1 v) has degree three, so its values at 0, at
+// infinity, at 1 and at -1 determine it:
+//   A = x0 c0,   B = x2 c1,   C = (x0 + x1 + x2)(c0 + c1),   D' = (x1 - x0 - x2)(c0 - c1) = -q(-1)
+//   2 (x0 c1 + x1 c0) = C + D' - 2B,   2 (x1 c1 + x2 c0) = C - D' - 2A,   and mod v^3 - xi the constant term is A + xi B.
+// The interpolation's halving is never computed here; the caller chooses where it goes by what it passes for s and d:
+//   X2 = true:   s = norm(c0 + c1), d = norm(c0 - c1)       ->  2 x (c0 + c1 v); the caller carries the factor two (an Fp constant: the
+//                Miller loop folds all of them into the constant of its last line, tools/gen_constants.py iso_twist_constants)
+//   X2 = false:  s = (c0 + c1) / 2, d = (c0 - c1) / 2       ->  x (c0 + c1 v) itself
+// x positive-normalised.  The two three-term operands are normalised here (their limbs reach 3 * 2^29), and -q(-1) is taken instead
+// of q(-1) so that the second coefficient stays above -2^30 (it enters the value reduction un-normalised, which subtracts up to 2^29
+// more).  Outputs: first coefficient within [0, 2^30 + 2^5], second within (-2^30, 2^30), third normalised.
+template <bool X2> GPBC_INLINE F6 f6_mul_01_pn4_t(const F6 &x, const F2 &c0, const F2 &c1, const F2 &s, const F2 &d) {
+    F2 e = f2_add(x.b0, x.b2);
+    F2 A = f2_mul(x.b0, c0), B = f2_mul(x.b2, c1);
+    F2 C = f2_mul(f2_norm(f2_add(e, x.b1)), s), Dn = f2_mul(f2_norm(f2_sub(x.b1, e)), d);
+    F2 t0 = X2 ? f2_dbl(f2_norm(f2_add(f2_mul_xi(B), A))) : f2_add(f2_mul_xi_nn(B), A);
+    F2 t1 = f2_sub(f2_add(C, Dn), X2 ? f2_dbl(B) : B);
+    F2 t2 = f2_sub(f2_sub(C, Dn), X2 ? f2_dbl(A) : A);
+    return F6{t0, t1, f2_norm(t2)};
+}
 GPBC_INLINE F6 f6_inv(const F6 &x) {
     F2 t0 = f2_norm(f2_sub(f2_sqr(x.b0), f2_mul_xi_n(f2_mul(x.b1, x.b2))));
     F2 t1 = f2_norm(f2_sub(f2_mul_xi_n(f2_sqr(x.b2)), f2_mul(x.b0, x.b1)));

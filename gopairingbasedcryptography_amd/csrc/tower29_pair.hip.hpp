@@ -7,6 +7,7 @@
 //
 //   f12 square  (complex method)   even: m = c0*c1           odd: st = (c0+c1)(c0+v c1)      -> 6 F2 products / lane
 //   f12 * line  (034-sparse)       both: h*l0 and h*l1 on the lane's own half                 -> 8 F2 products / lane
+//                                  (7 in the Miller accumulator: the l1 half by four-point interpolation, f12p_mul_034_x2)
 //   f12 * f12   (Karatsuba)        even: a0*b0 + diagonal part of the third product,
 //                                  odd:  a1*b1 + cross part of the third product              -> 9 F2 products / lane
 //   cyclotomic square              4.5 F2 squarings / lane (the ninth is split: real part on one lane, imaginary on the other)
@@ -106,6 +107,8 @@ template <bool PN = false, class X> GPBC_INLINE F6 f12p_sqr(const X &x, const F6
 // Each lane multiplies its own half by l0 and by l1 (3 + 5 F2 products), then the l1-products are swapped.
 // PN = true: h positive-normalised in, positive-normalised out (the value reduction goes in front of the normalisation), and the
 // five-product half in the subtractive form (f6_mul_01_pn_t).
+// (The Miller accumulators use the seven-product form below; this one serves the odd line of a chunk, PN = false, and is what the
+// tools compare the seven-product form with.)
 template <bool PN = false, class X> GPBC_INLINE F6 f12p_mul_034(const X &x, const F6 &h, const F2 &c0, const F2 &c3, const F2 &c4) {
     F2 s34 = f2_norm(PN ? f2_sub(c3, c4) : f2_add(c3, c4));
     F6 r0 = f6_mul_f2(h, c0);
@@ -126,6 +129,27 @@ template <bool PN = false, class X> GPBC_INLINE F6 f12p_mul_34(const X &x, const
     F6 send = f6_sel(x.odd, f6_mul_v_t<false>(r1), r1);       // as in f12p_mul_034
     F6 sum = f6p_add_swap(x, h, send);
     return PN ? f6_reduce_arith_norm(sum) : f6_reduce_arith(f6_norm(sum));
+}
+
+// TWICE the sparse product in SEVEN F2 products per lane: the l1 half by four-point interpolation (f6_mul_01_pn4_t<true>, which leaves
+// the interpolation's halving out), the l0 half by a c0 the caller has doubled already — c0x2 = 2 c0; in the Miller loop c0 = r0 yP
+// and the line phase maps yP by a constant anyway (miller_lines<true>), so the doubling costs nothing.  Returns 2 f l.  Seven is the
+// floor: a lane produces seven independent bilinear outputs.  h positive-normalised in and out.
+template <class X> GPBC_INLINE F6 f12p_mul_034_x2(const X &x, const F6 &h, const F2 &c0x2, const F2 &c3, const F2 &c4) {
+    F6 r0 = f6_mul_f2(h, c0x2);
+    F6 r1 = f6_mul_01_pn4_t<true>(h, c3, c4, f2_norm(f2_add(c3, c4)), f2_norm(f2_sub(c3, c4)));
+    F6 send = f6_sel(x.odd, f6_mul_v_t<false>(r1), r1);       // as in f12p_mul_034
+    return f6_reduce_arith_norm(f6p_add_swap(x, r0, send));
+}
+// The same for a line scaled to c0 = 1, f (1 + l1 w) in four F2 products per lane instead of five, from HALF the line: c3h = c3 / 2,
+// c4h = c4 / 2 (the fixed-Q form evaluates its lines at (xP / yP, 1 / yP), and halves those two once per point).  Their sum and
+// difference are the halved operands of the interpolation, so the product comes out as it is and nothing is left to cancel; c3 and
+// c4 themselves are the halves doubled.  (With h entering the sum directly there is no room for a doubled product here: 2 h plus a
+// doubled coefficient passes 2^31, and the value bound of the sum passes the 256 p the reduction takes.)
+template <class X> GPBC_INLINE F6 f12p_mul_34_half(const X &x, const F6 &h, const F2 &c3h, const F2 &c4h) {
+    F6 r1 = f6_mul_01_pn4_t<false>(h, f2_norm(f2_dbl(c3h)), f2_norm(f2_dbl(c4h)), f2_norm(f2_add(c3h, c4h)), f2_norm(f2_sub(c3h, c4h)));
+    F6 send = f6_sel(x.odd, f6_mul_v_t<false>(r1), r1);
+    return f6_reduce_arith_norm(f6p_add_swap(x, h, send));
 }
 
 // Product of two lines, (c0 + (c3 + c4 v) w)(d0 + (d3 + d4 v) w), as a lane-pair value:

@@ -426,7 +426,7 @@ void hc_pair_lanes(const uint8_t *P, const uint8_t *Q, size_t n, uint8_t *out, i
         G2A b{f2_load(q), f2_load(q + 64)};
         LineS lines[MILLER_LINES];
         int cnt = 0;
-        miller_lines(a, b, [&](const LineS &l) { lines[cnt++] = l; });
+        miller_lines<true>(a, b, [&](const LineS &l) { lines[cnt++] = l; });
         PairRendezvous rv;
         auto lane = [&](bool odd) {
             PairHost x{odd, &rv};
@@ -434,6 +434,46 @@ void hc_pair_lanes(const uint8_t *P, const uint8_t *Q, size_t n, uint8_t *out, i
             F6 h = miller_accumulate_pair(x, [&]() -> LineS { return lines[k++]; });
             if (do_final_exp) h = final_exp_pair(x, h);
             f6_store(out + 384 * i + (odd ? 192 : 0), h);
+            stats_flush();
+        };
+        std::thread t1(lane, true);
+        lane(false);
+        t1.join();
+    }
+}
+// The sparse line products of the lane-pair accumulators side by side on the same operands: the eight-product form (five at c0 = 1)
+// and the doubled seven-product form (four).  H: n x 2 x 54 int32, the RAW limbs of a positive-normalised accumulator (even lane's
+// half, then the odd lane's) — limbs 0..7 within [-2^4, 2^29 + 2^4], the value's sign in the top limb, |value| < 0.51 p: the class
+// every step of miller_accumulate_pair ends in, so the extremes of that class can be put in directly.  L: n x 4 x 64 bytes, gnark
+// E2 values (c0, c3, u, w) with c4 = u - w entering un-normalised, as a tangent's r2 = E - B does.  one = 0: f12p_mul_034<true> into
+// out_old, f12p_mul_034_x2 into out_new; one = 1: f12p_mul_34<true> and f12p_mul_34_half on half the line (c0 is not read).  Canonical
+// gnark bytes; the caller checks out_new = 2 out_old (one = 0) or out_new = out_old (one = 1).
+static Fe fe_raw_pn(const int32_t *w) {
+    Fe r;
+    for (int i = 0; i < NL; i++) r.v[i] = w[i];
+    constexpr double P8 = (double)f29_p(NL - 1);
+    r.lo[0] = 0; r.hi[0] = (double)LMASK;
+    for (int i = 1; i < NL - 1; i++) { r.lo[i] = -16; r.hi[i] = (double)LMASK + 16; }
+    r.hi[NL - 1] = P8 / 2 + 270 + 16; r.lo[NL - 1] = -r.hi[NL - 1];
+    r.vb = 0.51;
+    check_limbs(r, "raw positive-normalised limb");
+    return r;
+}
+static F6 f6_raw_pn(const int32_t *w) {
+    return F6{F2{fe_raw_pn(w), fe_raw_pn(w + NL)}, F2{fe_raw_pn(w + 2 * NL), fe_raw_pn(w + 3 * NL)}, F2{fe_raw_pn(w + 4 * NL), fe_raw_pn(w + 5 * NL)}};
+}
+void hc_sparse_products(const int32_t *H, const uint8_t *L, size_t n, int one, uint8_t *out_old, uint8_t *out_new) {
+    for (size_t i = 0; i < n; i++) {
+        const uint8_t *l = L + 256 * i;
+        const F2 c0 = f2_load(l), c3 = f2_load(l + 64), c4 = f2_sub(f2_load(l + 128), f2_load(l + 192));
+        const F2 c0x2 = f2_norm(f2_dbl(c0));
+        PairRendezvous rv;
+        auto lane = [&](bool odd) {
+            PairHost x{odd, &rv};
+            const F6 h = f6_raw_pn(H + (2 * i + (odd ? 1 : 0)) * LINE_WORDS);
+            const size_t o = 384 * i + (odd ? 192 : 0);
+            f6_store(out_old + o, one ? f12p_mul_34<true>(x, h, c3, c4) : f12p_mul_034<true>(x, h, c0, c3, c4));
+            f6_store(out_new + o, one ? f12p_mul_34_half(x, h, f2_halve(c3), f2_halve(f2_norm(c4))) : f12p_mul_034_x2(x, h, c0x2, c3, c4));
             stats_flush();
         };
         std::thread t1(lane, true);
@@ -462,15 +502,15 @@ void hc_pair_lanes_multi(const uint8_t *P, const uint8_t *Q, size_t n, uint8_t *
     t1.join();
 }
 // fixed-Q multi-pairing exactly as k_q_lines + k_q_lines_scale + k_g1_line_point + k_miller_accumulate_fixed_q do it: the RAW line
-// coefficients of every Q_i (miller_lines_raw) scaled to c0 = 1, evaluated at (xP / yP, 1 / yP) inside the accumulator (one
+// coefficients of every Q_i (miller_lines_raw) scaled to c0 = 1, evaluated at (xP / 2yP, 1 / 2yP) inside the accumulator (one
 // Fp x Fp2 product per lane, swapped), shared squarings on one lane pair; out = the Miller value of prod e(P_i, Q_i) up to a
 // factor in Fp2 (do_final_exp = 0: the caller applies the final exponentiation, which removes it) or the GT value
 void hc_pair_fixed_q(const uint8_t *P, const uint8_t *Q, size_t n, uint8_t *out, int do_final_exp) {
     std::vector<Line34> tab(n * MILLER_LINES);
-    std::vector<G1A> pts(n);                                    // (x / y, 1 / y)
+    std::vector<G1A> pts(n);                                    // (x / 2y, 1 / 2y)
     for (size_t base = 0; base < n; base += 8)                  // k_g1_line_point: groups of 8 points share one inversion
         fe_batch_inverse<8>(n - base < 8 ? (int)(n - base) : 8, [&](int j) { return fe_load(P + 64 * (base + j) + 32); },
-                            [&](int j, const Fe &yinv) { pts[base + j] = G1A{fe_mul(fe_load(P + 64 * (base + j)), yinv), yinv}; });
+                            [&](int j, const Fe &y_inverse) { const Fe yinv = fe_halve(y_inverse); pts[base + j] = G1A{fe_mul(fe_load(P + 64 * (base + j)), yinv), yinv}; });
     for (size_t i = 0; i < n; i++) {
         G2A b{f2_load(Q + 128 * i), f2_load(Q + 128 * i + 64)};
         int cnt = 0;

@@ -7,7 +7,7 @@ NAME=$1; shift
 R=$(cd "$(dirname "$0")/.." && pwd)
 SRC=$(cd "${GPBC_SRC:-$R/gopairingbasedcryptography_amd/csrc}" && pwd)
 T=$(mktemp -d)
-for s in gpbc_core gpbc_pairing gpbc_curve gpbc_wire gpbc_msm gpbc_group gpbc_fr gpbc_gtmexp gpbc_gmsm; do
+for s in gpbc_core gpbc_pairing gpbc_curve gpbc_wire gpbc_msm gpbc_group gpbc_fr gpbc_gtmexp gpbc_gmsm gpbc_subset; do
   /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -fPIC -I$R/include "$@" -c $SRC/$s.hip -o $T/$s.o &
 done
 wait

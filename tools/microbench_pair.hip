@@ -32,6 +32,11 @@ __global__ void __launch_bounds__(64, 2) bench(const uint8_t *in, uint8_t *out, 
         else if (OP == 9) { F12 z = f12_mul(F12{h, g}, F12{g, h}); h = z.c0; g = z.c1; }
         else if (OP == 10) { F12 z = f12_sqr(F12{h, g}); h = f6_reduce(z.c0); g = f6_reduce(z.c1); }
         else if (OP == 11) h = f12p_cyclo_sqr_alt(x, h);          // the alternating-sign form used inside runs (x^u)
+        // the accumulator's sparse products, positive-normalised forms: eight / seven F2 products, and five / four at c0 = 1
+        else if (OP == 12) h = f12p_mul_034<true>(x, h, g.b0, g.b1, g.b2);
+        else if (OP == 13) h = f12p_mul_034_x2(x, h, g.b0, g.b1, g.b2);
+        else if (OP == 14) h = f12p_mul_34<true>(x, h, g.b1, g.b2);
+        else if (OP == 15) h = f12p_mul_34_half(x, h, g.b1, g.b2);
     }
     uint8_t *o = out + 384 * (i & 63);
     if (OP >= 8) h = f6_norm(f6_add(h, g));
@@ -64,6 +69,10 @@ int main() {
         run<1>("f12p_mul (9 F2 mul)", din, dout, ncu, w, 200, 9 * 486);
         run<2>("f12p_sqr (6 F2 mul) + reduce", din, dout, ncu, w, 200, 6 * 486);
         run<3>("f12p_mul_034 (8 F2 mul)", din, dout, ncu, w, 200, 8 * 486);
+        run<12>("f12p_mul_034<PN> (8 F2 mul)", din, dout, ncu, w, 200, 8 * 486);
+        run<13>("f12p_mul_034_x2 (7 F2 mul)", din, dout, ncu, w, 200, 7 * 486);
+        run<14>("f12p_mul_34<PN> (5 F2 mul)", din, dout, ncu, w, 200, 5 * 486);
+        run<15>("f12p_mul_34_half (4 F2 mul)", din, dout, ncu, w, 200, 4 * 486);
         run<4>("3 x f2_mul leaf", din, dout, ncu, w, 400, 3 * 486);
         run<5>("3 x f2_sqr leaf", din, dout, ncu, w, 400, 3 * 324);
         run<6>("f6 add+norm+reduce", din, dout, ncu, w, 2000, 0);
