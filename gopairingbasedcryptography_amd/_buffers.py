@@ -133,3 +133,13 @@ def zeros(shape, like):
     out = empty(shape, like)
     out[...] = 0
     return out
+
+
+def rows_nonzero(a):
+    """per row of a two-dimensional uint8 buffer: 1 where any byte is set, else 0 (uint8 [n], of the buffer's kind)"""
+    return (a != 0).any(1).to(a.dtype) if is_torch(a) else (a != 0).any(1).astype(np.uint8)
+
+
+def rows_equal(a, b):
+    """per row of two uint8 buffers of one shape and kind: 1 where the rows hold the same bytes, else 0"""
+    return (a == b).all(1).to(a.dtype) if is_torch(a) else (a == b).all(1).astype(np.uint8)

@@ -70,6 +70,12 @@ SUBSET_SIGNATURES = {
     "gpbc_g2_subset_table_create": "i:pzpp", "gpbc_subset_table_create_dev": "i:ipzppp", "gpbc_subset_sum": "i:ppzp",
     "gpbc_subset_sum_workspace_bytes": "z:pz", "gpbc_subset_sum_dev": "i:ppzppzp", "gpbc_subset_table_destroy": "i:p",
 }
+# ... and for include/gpbc_bn254_hash.h, SHA-256 on the device with the digest as bytes or as a scalar (tests/test_transcript_hash.py
+# holds this table against that header).  The four tables are disjoint.
+HASH_SIGNATURES = {
+    "gpbc_hash_version": "i:", "gpbc_sha256_batch": "i:ppzip", "gpbc_sha256_batch_dev": "i:ppzzipp",
+    "gpbc_hash_g1_gt_gt_to_fr": "i:pppzp", "gpbc_hash_g1_gt_gt_to_fr_dev": "i:pppzpp",
+}
 # every pointer is a c_void_p: it takes ints, None, c_void_p, ctypes arrays, byref() and ndarray.ctypes.data_as() alike
 _CTYPES = {"p": ctypes.c_void_p, "z": ctypes.c_size_t, "i": ctypes.c_int, "l": ctypes.c_long, "s": ctypes.c_char_p}
 
@@ -95,7 +101,7 @@ def load():
         except ImportError:
             pass
         lib = ctypes.CDLL(LIB_PATH)
-        for name, sig in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(SUBSET_SIGNATURES.items()):
+        for name, sig in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(SUBSET_SIGNATURES.items()) + list(HASH_SIGNATURES.items()):
             ret, params = sig.split(":")
             fn = getattr(lib, name)
             fn.restype = _CTYPES[ret]

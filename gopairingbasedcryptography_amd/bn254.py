@@ -925,17 +925,10 @@ def map_to_g2(u):
     return _rowwise("g2_map_to_curve_batch", G2_BYTES, (u, G2_BYTES, "field elements"))
 
 
-def _hash_messages(what, msgs, dst, msg_off=None):
-    """Shared body of hash_to_g1 / hash_to_g2 / hash_to_field.  what: 0 G1, 1 G2, 2 / 4 field elements per message.
-    msgs: a list of bytes-like messages (host), or the concatenated bytes as a numpy array / CUDA uint8 tensor with
-    msg_off (n + 1 offsets; numpy uint64 for host data, an int64 CUDA tensor for device data)."""
-    dst = bytes(dst)
-    if len(dst) > 255:                                           # gnark's ExpandMsgXmd refuses it ("invalid domain size"), so does the Go shim
-        raise ValueError("invalid domain size (>255 bytes)")
-    width = G1_BYTES if what == 0 else G2_BYTES if what == 1 else 32 * what
-    name = ("hash_to_g1", "hash_to_g2", "hash_to_field")[min(what, 2)]
-    dbuf = ctypes.create_string_buffer(dst, len(dst) if dst else 1)
-    count = (what,) if what >= 2 else ()
+def _messages(msgs, msg_off):
+    """(dev, data, msg_off, nbytes, n) of the entries that take n messages.  msgs: a list of bytes-like messages (host), or the
+    concatenated bytes as a numpy array / CUDA uint8 tensor with msg_off (n + 1 offsets; numpy uint64 for host data, an int64 CUDA
+    tensor for device data).  nbytes: the arguments the device form takes besides — the length of the message buffer — as a tuple."""
     if bufs.is_torch(msgs):
         # The three message forms are the reason this body names the buffer kind: the device form takes its offsets as an int64
         # tensor and the length of the message buffer besides.
@@ -946,9 +939,7 @@ def _hash_messages(what, msgs, dst, msg_off=None):
         n = msg_off.numel() - 1
         if n < 0:
             raise ValueError("msg_off needs n + 1 entries")
-        out = bufs.output(None, (n, width), dev)
-        _call(name, dev, msgs, msg_off, nbytes, n, dbuf, len(dst), *count, out)
-        return out
+        return dev, msgs, msg_off, (nbytes,), n
     if msg_off is None:
         msgs = [bytes(m) for m in msgs]
         msg_off = np.zeros(len(msgs) + 1, dtype=np.uint64)
@@ -962,10 +953,23 @@ def _hash_messages(what, msgs, dst, msg_off=None):
             raise ValueError("message offsets exceed the message buffer")
         if data.size == 0:
             data = np.zeros(1, dtype=np.uint8)
-    n = msg_off.size - 1
-    out = np.empty((n, width), dtype=np.uint8)
-    if n:
-        _call(name, None, data, msg_off, n, dbuf, len(dst), *count, out)
+    return None, data, msg_off, (), msg_off.size - 1
+
+
+def _hash_messages(what, msgs, dst, msg_off=None):
+    """Shared body of hash_to_g1 / hash_to_g2 / hash_to_field.  what: 0 G1, 1 G2, 2 / 4 field elements per message; the messages as
+    _messages takes them."""
+    dst = bytes(dst)
+    if len(dst) > 255:                                           # gnark's ExpandMsgXmd refuses it ("invalid domain size"), so does the Go shim
+        raise ValueError("invalid domain size (>255 bytes)")
+    width = G1_BYTES if what == 0 else G2_BYTES if what == 1 else 32 * what
+    name = ("hash_to_g1", "hash_to_g2", "hash_to_field")[min(what, 2)]
+    dbuf = ctypes.create_string_buffer(dst, len(dst) if dst else 1)
+    count = (what,) if what >= 2 else ()
+    dev, data, msg_off, nbytes, n = _messages(msgs, msg_off)
+    out = bufs.output(None, (n, width), dev)
+    if n or dev is not None:
+        _call(name, dev, data, msg_off, *nbytes, n, dbuf, len(dst), *count, out)
     return out
 
 
@@ -984,6 +988,25 @@ def hash_to_field(msgs, dst, count=2, msg_off=None):
     if count not in (2, 4):
         raise ValueError("count must be 2 or 4")
     return _hash_messages(count, msgs, dst, msg_off)
+
+
+# --------------------------------------------------------------------------------------- SHA-256 with the digest as bytes or as a scalar
+def sha256(msgs, msg_off=None, to_fr=False, out=None):
+    """SHA-256 of every message on the device (include/gpbc_bn254_hash.h): [n, 32] digests as SHA-256 writes them — the identity masks
+    of NewWaters05IBEIdentity — or, with to_fr, fr.Element.SetBytes(digest) in the scalar format (little-endian, canonical).  The
+    messages as hash_to_field takes them: a list of bytes, or a flat buffer plus offsets, host or CUDA."""
+    dev, data, msg_off, nbytes, n = _messages(msgs, msg_off)
+    out = bufs.output(out, (n, 32), dev)
+    if n or dev is not None:
+        _call("sha256_batch", dev, data, msg_off, *nbytes, n, 1 if to_fr else 0, out)
+    return out
+
+
+def hash_g1_gt_gt_to_fr(u, v, w, out=None):
+    """beta = H(u, v, w) of Gentry06 (ibe/gentry06_ibe/gentry06_ibe.go:319-343) for n items: fr.SetBytes(SHA-256(u.Bytes() ||
+    v.Bytes() || w.Bytes())) with u [n, 64] G1 points and v, w [n, 384] GT elements -> [n, 32] scalars, canonical.  One launch; the
+    800 bytes are never written.  The output is of the kind the inputs are."""
+    return _rowwise("hash_g1_gt_gt_to_fr", SCALAR_BYTES, (u, G1_BYTES, "u"), (v, GT_BYTES, "v"), (w, GT_BYTES, "w"), out=out)
 
 
 # --------------------------------------------------------------------------------------- fixed-base tables / MSM

@@ -1,0 +1,61 @@
+// libgpbc_bn254.so, unit 11 of 11: SHA-256 on the device with the digest as bytes or as a scalar — the transcript hash H(u, v, w) of
+// Gentry06 and the plain batched SHA-256 (csrc/transcript29.hip.hpp) with their C-ABI entries (include/gpbc_bn254_hash.h).  gfx950 only.
+#include "gpbc_common.hpp"
+#include "../../include/gpbc_bn254_hash.h"
+#include "transcript29.hip.hpp"
+
+// one item per lane: 832 bytes in, 32 out
+GPBC_KERNEL_G1 k_hash_g1_gt_gt_to_fr(const uint8_t *__restrict__ u, const uint8_t *__restrict__ v, const uint8_t *__restrict__ w, size_t n, uint8_t *__restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    hash_g1_gt_gt_to_fr_lane(u + i * GPBC_G1_BYTES, v + i * GPBC_GT_BYTES, w + i * GPBC_GT_BYTES, out + i * GPBC_SCALAR_BYTES);
+}
+// one message per lane: message i is msgs[off[i], off[i+1]), the offsets clamped as the hash-to-curve kernels clamp them (msg_range)
+GPBC_KERNEL_G1 k_sha256(const uint8_t *__restrict__ msgs, const uint64_t *__restrict__ off, size_t total, size_t n, int to_fr, uint8_t *__restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    uint64_t lo, len;
+    msg_range(off, total, i, lo, len);
+    sha256_lane(msgs + lo, len, to_fr != 0, out + i * 32);
+}
+
+extern "C" {
+
+int gpbc_hash_version(void) { return 1; }
+
+int gpbc_sha256_batch_dev(const void *d_msgs, const uint64_t *d_msg_off, size_t msgs_bytes, size_t n, int to_fr, void *d_out, void *stream) {
+    if (!n) return GPBC_OK;
+    if (!d_msg_off || !d_out || (msgs_bytes && !d_msgs)) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    TRY(bind_device());
+    return GPBC_LAUNCH(k_sha256, grid_for(n), BLOCK, (hipStream_t)stream, (const uint8_t *)d_msgs, d_msg_off, msgs_bytes, n, to_fr, (uint8_t *)d_out);
+}
+// Host pointers: the shared staging path (host_call) through device blocks on the calling thread's current device — the messages the
+// offsets span and the offsets rebased to them travel as whole columns; not combined with other threads' calls, not sharded.
+int gpbc_sha256_batch(const void *msgs, const uint64_t *msg_off, size_t n, int to_fr, void *out) {
+    if (!n) return GPBC_OK;
+    if (!msg_off || !out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    for (size_t i = 0; i < n; i++) if (msg_off[i + 1] < msg_off[i]) return fail(GPBC_ERR_INVALID_ARG, "message offsets must not decrease");
+    const uint64_t base = msg_off[0], bytes = msg_off[n] - base;
+    if (bytes && !msgs) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    std::vector<uint64_t> rel(n + 1);
+    for (size_t i = 0; i <= n; i++) rel[i] = msg_off[i] - base;
+    HostCall c = HostCall().input(bytes ? (const uint8_t *)msgs + base : nullptr, bytes, true).input(rel.data(), (n + 1) * sizeof(uint64_t), true).output(out, 32);
+    return host_call(n, c, HostRoute{}, [&](const DevCols &d, size_t m, hipStream_t st) {
+        return gpbc_sha256_batch_dev(d.in[0], (const uint64_t *)d.in[1], bytes, m, to_fr, d.out[0], st);
+    });
+}
+
+int gpbc_hash_g1_gt_gt_to_fr_dev(const void *d_u, const void *d_v, const void *d_w, size_t n, void *d_out, void *stream) {
+    if (!n) return GPBC_OK;
+    if (!d_u || !d_v || !d_w || !d_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    TRY(bind_device());
+    return GPBC_LAUNCH(k_hash_g1_gt_gt_to_fr, grid_for(n), BLOCK, (hipStream_t)stream, (const uint8_t *)d_u, (const uint8_t *)d_v, (const uint8_t *)d_w, n, (uint8_t *)d_out);
+}
+int gpbc_hash_g1_gt_gt_to_fr(const void *u, const void *v, const void *w, size_t n, void *out) {
+    if (!n) return GPBC_OK;
+    if (!u || !v || !w || !out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    return host_call(n, HostCall().input(u, GPBC_G1_BYTES).input(v, GPBC_GT_BYTES).input(w, GPBC_GT_BYTES).output(out, GPBC_SCALAR_BYTES), HostRoute{},
+                     [](const DevCols &d, size_t m, hipStream_t st) { return gpbc_hash_g1_gt_gt_to_fr_dev(d.in[0], d.in[1], d.in[2], m, d.out[0], st); });
+}
+
+}  // extern "C"

@@ -114,14 +114,8 @@ GPBC_KERNEL k_g2_map_fields(const uint8_t *__restrict__ u, uint8_t *__restrict__
     g2_store_aff(out + i * GPBC_G2_BYTES, r);
 }
 
-// ---- hash to curve, whole (csrc/xmd29.hip.hpp + h2c29.hip.hpp): one message per lane.  Message i is msgs[off[i], off[i+1]);
-// the offsets are clamped to [0, total] and made monotone, so a malformed device-resident table cannot read outside the buffer.
-__device__ __forceinline__ void msg_range(const uint64_t *__restrict__ off, size_t total, size_t i, uint64_t &lo, uint64_t &len) {
-    uint64_t a = off[i], b = off[i + 1];
-    if (a > total) a = total;
-    if (b > total) b = total;
-    lo = a; len = b > a ? b - a : 0;
-}
+// ---- hash to curve, whole (csrc/xmd29.hip.hpp + h2c29.hip.hpp): one message per lane.  Message i is msgs[off[i], off[i+1]),
+// clamped to the buffer by msg_range (xmd29.hip.hpp).
 template <int COUNT> GPBC_KERNEL k_hash_to_field(const uint8_t *__restrict__ msgs, const uint64_t *__restrict__ off, size_t total, size_t n, XmdDst dst,
                                                  uint8_t *__restrict__ out) {
     size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;

@@ -7,7 +7,8 @@
 //     b_0 = H(Z_pad(64 zero bytes) || msg || I2OSP(len_in_bytes, 2) || 0 || DST') — the zero block's state is a constant
 //     b_1 = H(b_0 || 1 || DST'),   b_i = H((b_0 xor b_(i-1)) || i || DST'),   DST' = DST || I2OSP(len(DST), 1)
 // DST (at most 255 bytes; longer ones are hashed down by the caller as the RFC prescribes) travels in the kernel arguments.
-// Device only: the host build of the bounds harness has no use for it (the field operations it ends in are covered there).
+// Host-compilable like the arithmetic it ends in (GPBC_INLINE): the bounds harness runs the lane functions of transcript29.hip.hpp,
+// which hash with the compression and the block builder below.
 #ifndef GPBC_XMD29_HIP_HPP
 #define GPBC_XMD29_HIP_HPP
 #include "wire29.hip.hpp"
@@ -16,9 +17,9 @@ namespace gpbc {
 
 struct XmdDst { uint8_t b[256]; uint32_t len; };          // kernel argument: uniform, read with scalar loads
 
-__device__ __forceinline__ uint32_t sha_rotr(uint32_t x, int n) { return __builtin_rotateright32(x, n); }
+GPBC_INLINE uint32_t sha_rotr(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }          // 0 < n < 32; compiles to one rotate
 // one SHA-256 compression (FIPS 180-4 §6.2.2); w is consumed (rolling message schedule)
-__device__ __noinline__ void sha256_compress(uint32_t (&st)[8], uint32_t (&w)[16]) {
+GPBC_INLINE void sha256_compress_core(uint32_t (&st)[8], uint32_t (&w)[16]) {
     constexpr uint32_t K[64] = {
         0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu, 0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u, 0xd807aa98u, 0x12835b01u, 0x243185beu,
         0x550c7dc3u, 0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u, 0xc19bf174u, 0xe49b69c1u, 0xefbe4786u, 0x0fc19dc6u, 0x240ca1ccu, 0x2de92c6fu, 0x4a7484aau,
@@ -39,16 +40,45 @@ __device__ __noinline__ void sha256_compress(uint32_t (&st)[8], uint32_t (&w)[16
     }
     st[0] += a; st[1] += b; st[2] += c; st[3] += d; st[4] += e; st[5] += f; st[6] += g; st[7] += h;
 }
-__device__ __forceinline__ void sha256_iv(uint32_t (&st)[8]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+// On the device the compression exists once per code object, as a leaf with the 8 + 16 words passed as scalars and the new state returned
+// by value (fe_mul_leaf's reason, fe29.hip.hpp: 24 scalars travel in VGPRs; two arrays passed by reference would have to live in private
+// memory on both sides of the call).
+struct ShaState { uint32_t s[8]; };
+#define GPBC_SHA_ARGS8(x) uint32_t x##0, uint32_t x##1, uint32_t x##2, uint32_t x##3, uint32_t x##4, uint32_t x##5, uint32_t x##6, uint32_t x##7
+#define GPBC_SHA_PASS8(x, o) x[o], x[o + 1], x[o + 2], x[o + 3], x[o + 4], x[o + 5], x[o + 6], x[o + 7]
+__device__ __noinline__ ShaState sha256_compress_leaf(GPBC_SHA_ARGS8(s), GPBC_SHA_ARGS8(a), GPBC_SHA_ARGS8(b)) {
+    uint32_t st[8] = {s0, s1, s2, s3, s4, s5, s6, s7}, w[16] = {a0, a1, a2, a3, a4, a5, a6, a7, b0, b1, b2, b3, b4, b5, b6, b7};
+    sha256_compress_core(st, w);
+    return ShaState{{st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7]}};
+}
+GPBC_INLINE void sha256_compress(uint32_t (&st)[8], uint32_t (&w)[16]) {
+    const ShaState r = sha256_compress_leaf(GPBC_SHA_PASS8(st, 0), GPBC_SHA_PASS8(w, 0), GPBC_SHA_PASS8(w, 8));
+#pragma unroll
+    for (int i = 0; i < 8; i++) st[i] = r.s[i];
+}
+#else
+GPBC_INLINE void sha256_compress(uint32_t (&st)[8], uint32_t (&w)[16]) { sha256_compress_core(st, w); }
+#endif
+GPBC_INLINE void sha256_iv(uint32_t (&st)[8]) {
     constexpr uint32_t IV[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
 #pragma unroll
     for (int i = 0; i < 8; i++) st[i] = IV[i];
 }
 
+// Message i of a batch is msgs[off[i], off[i+1]): the offsets are clamped to [0, total] and made monotone, so a malformed
+// device-resident table cannot read outside the buffer.
+GPBC_INLINE void msg_range(const uint64_t *__restrict__ off, size_t total, size_t i, uint64_t &lo, uint64_t &len) {
+    uint64_t a = off[i], b = off[i + 1];
+    if (a > total) a = total;
+    if (b > total) b = total;
+    lo = a; len = b > a ? b - a : 0;
+}
+
 // Hashes the stream  byte_at(pos), pos < body_len,  then the SHA-256 padding for a message of done + body_len bytes of which
 // `done` (a multiple of 64) are already in st.  STATIC_BLOCKS > 0 unrolls the block loop (every position is then a compile-time
 // constant, so a byte_at that indexes registers stays in registers); 0 loops over the data-dependent number of blocks.
-template <class ByteAt> __device__ __forceinline__ void sha256_block_from(uint32_t (&w)[16], uint64_t blk, uint64_t body_len, uint64_t n_blocks, uint64_t bits, ByteAt &&byte_at) {
+template <class ByteAt> GPBC_INLINE void sha256_block_from(uint32_t (&w)[16], uint64_t blk, uint64_t body_len, uint64_t n_blocks, uint64_t bits, ByteAt &&byte_at) {
 #pragma unroll
     for (int j = 0; j < 16; j++) {
         uint32_t word = 0;
@@ -65,7 +95,7 @@ template <class ByteAt> __device__ __forceinline__ void sha256_block_from(uint32
         w[j] = word;
     }
 }
-template <int STATIC_BLOCKS, class ByteAt> __device__ __forceinline__ void sha256_tail(uint32_t (&st)[8], uint64_t done, uint64_t body_len, ByteAt &&byte_at) {
+template <int STATIC_BLOCKS, class ByteAt> GPBC_INLINE void sha256_tail(uint32_t (&st)[8], uint64_t done, uint64_t body_len, ByteAt &&byte_at) {
     const uint64_t n_blocks = (body_len + 9 + 63) / 64, bits = (done + body_len) * 8;
     uint32_t w[16];
     if (STATIC_BLOCKS > 0) {
@@ -78,7 +108,7 @@ template <int STATIC_BLOCKS, class ByteAt> __device__ __forceinline__ void sha25
 }
 
 // uniform bytes of expand_message_xmd as N_DIGESTS x 8 big-endian words (len_in_bytes = 32 * N_DIGESTS... the callers use 96 and 192)
-template <int N_DIGESTS> __device__ __forceinline__ void expand_message_xmd(uint32_t (&out)[N_DIGESTS * 8], const uint8_t *msg, uint64_t mlen, const XmdDst &dst) {
+template <int N_DIGESTS> GPBC_INLINE void expand_message_xmd(uint32_t (&out)[N_DIGESTS * 8], const uint8_t *msg, uint64_t mlen, const XmdDst &dst) {
     constexpr uint32_t len_in_bytes = 32 * N_DIGESTS;
     const uint32_t dlen = dst.len;
     // b_0: the state after the 64 zero bytes of Z_pad is a constant
@@ -111,7 +141,7 @@ template <int N_DIGESTS> __device__ __forceinline__ void expand_message_xmd(uint
 }
 
 // field element e of the uniform bytes: OS2IP(48 bytes) mod p, internal form.  v = hi 2^256 + lo with hi < 2^128.
-template <int N_WORDS> __device__ __forceinline__ Fe xmd_field(const uint32_t (&u)[N_WORDS], int e) {
+template <int N_WORDS> GPBC_INLINE Fe xmd_field(const uint32_t (&u)[N_WORDS], int e) {
     uint32_t lo[8], hi[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) { lo[i] = u[12 * e + 11 - i]; hi[i] = i < 4 ? u[12 * e + 3 - i] : 0u; }

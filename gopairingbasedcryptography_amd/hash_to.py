@@ -10,6 +10,9 @@ hash_to_g1 / hash_to_g2 below are the product path (csrc/xmd29.hip.hpp + h2c29.h
 in this file are the hashlib restatement the tests hold against RFC 9380's K.1 vectors and against the device's field
 elements; hash_to_g1_via_host_fields / _g2_ keep the older split (host hashing, device map) for that comparison.
 
+sha256_to_fr is fr.Element.SetBytes(SHA-256(msg)) per message on the device (bn254.sha256; csrc/transcript29.hip.hpp), and
+bn254.hash_g1_gt_gt_to_fr the same over the encodings of (u, v, w) — Gentry06's H (ibe/gentry06_ibe/gentry06_ibe.go:319-343).
+
 The reference's ToField / BytesToField do not hash at all and are not reproduced here.
 """
 import hashlib
@@ -79,6 +82,11 @@ def hash_to_g2_via_host_fields(msgs, dst):
     if not msgs:
         return np.zeros((0, bn254.G2_BYTES), dtype=np.uint8)
     return bn254.map_to_g2(_mont_rows(4, msgs, dst))
+
+
+def sha256_to_fr(engine, msgs):
+    """[n, 32] scalars: the SHA-256 digest of every message as a big-endian integer mod r (engine: bn254, or a stand-in)."""
+    return engine.sha256([bytes(m) for m in msgs], to_fr=True)
 
 
 # the reference's four entry points (single value in, single point out)

@@ -41,6 +41,18 @@ def identity_masks(strings):
     return np.frombuffer(b"".join(rows), dtype=np.uint8).reshape(-1, ID_BYTES).copy()
 
 
+def identity_masks_device(engine, strings_or_buffer, msg_off=None):
+    """identity_masks through engine.sha256: the [n, 32] digests computed on the device.  A list of identity strings (or bytes), or the
+    concatenated bytes with msg_off as engine.sha256 takes them — host arrays give a host array, CUDA tensors a CUDA tensor that goes
+    into the batch functions as it is.  An empty string in a list is refused, as the reference refuses it; offsets are not inspected."""
+    if msg_off is not None:
+        return engine.sha256(strings_or_buffer, msg_off)
+    msgs = [s.encode() if isinstance(s, str) else bytes(s) for s in strings_or_buffer]
+    if not all(msgs):
+        raise ValueError("identity string cannot be empty")
+    return engine.sha256(msgs)
+
+
 def hash_table(engine, u_prime, ui):
     """the Waters hash as a table: engine.SubsetTable over the 256 U_i ([256, 128]) with offset U' ([128]); table.close() frees it"""
     if bufs.nbytes(ui) != ID_BITS * 128 or bufs.nbytes(u_prime) != 128:

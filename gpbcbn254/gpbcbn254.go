@@ -14,6 +14,7 @@ package gpbcbn254
 #cgo CFLAGS: -I${SRCDIR}/../include
 #cgo LDFLAGS: -L${SRCDIR}/../gopairingbasedcryptography_amd -lgpbc_bn254 -Wl,-rpath,${SRCDIR}/../gopairingbasedcryptography_amd
 #include "gpbc_bn254.h"
+#include "gpbc_bn254_hash.h"
 */
 import "C"
 
@@ -991,6 +992,49 @@ func HashToG1Batch(msgs [][]byte, dst []byte) ([]bn254.G1Affine, error) {
 	rc := C.gpbc_hash_to_g1(unsafe.Pointer(unsafe.SliceData(data)), (*C.uint64_t)(unsafe.SliceData(off)), C.size_t(len(msgs)),
 		dstPointer(dst), C.size_t(len(dst)), unsafe.Pointer(unsafe.SliceData(out)))
 	return out, status(rc)
+}
+
+// HashG1GTGTToFr is h(u, v, w) of ibe/gentry06_ibe/gentry06_ibe.go:319-343 for n items: fr.SetBytes(SHA-256(u.Bytes() || v.Bytes() || w.Bytes())).
+func HashG1GTGTToFr(u []bn254.G1Affine, v, w []bn254.GT) ([]fr.Element, error) {
+	defer pin()()
+	if len(u) != len(v) || len(u) != len(w) {
+		return nil, errSizes
+	}
+	k, out := make([][32]byte, len(u)), make([]fr.Element, len(u))
+	if len(u) == 0 {
+		return out, nil
+	}
+	rc := C.gpbc_hash_g1_gt_gt_to_fr(unsafe.Pointer(unsafe.SliceData(u)), unsafe.Pointer(unsafe.SliceData(v)), unsafe.Pointer(unsafe.SliceData(w)),
+		C.size_t(len(u)), unsafe.Pointer(unsafe.SliceData(k)))
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	return out, frElements(k, out)
+}
+
+// Sha256Batch is sha256.Sum256 per message (NewWaters05IBEIdentity, NewBB04IBEIdentity); Sha256ToFrBatch is fr.SetBytes of it.
+func Sha256Batch(msgs [][]byte) ([][32]byte, error) {
+	defer pin()()
+	out := make([][32]byte, len(msgs))
+	if len(msgs) == 0 {
+		return out, nil
+	}
+	data, off := flatten(msgs)
+	rc := C.gpbc_sha256_batch(unsafe.Pointer(unsafe.SliceData(data)), (*C.uint64_t)(unsafe.SliceData(off)), C.size_t(len(msgs)), 0, unsafe.Pointer(unsafe.SliceData(out)))
+	return out, status(rc)
+}
+func Sha256ToFrBatch(msgs [][]byte) ([]fr.Element, error) {
+	defer pin()()
+	k, out := make([][32]byte, len(msgs)), make([]fr.Element, len(msgs))
+	if len(msgs) == 0 {
+		return out, nil
+	}
+	data, off := flatten(msgs)
+	rc := C.gpbc_sha256_batch(unsafe.Pointer(unsafe.SliceData(data)), (*C.uint64_t)(unsafe.SliceData(off)), C.size_t(len(msgs)), 1, unsafe.Pointer(unsafe.SliceData(k)))
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	return out, frElements(k, out)
 }
 
 // MapToG1Batch is the group part alone for callers that hold gnark's fp.Hash(msg, dst, 2) output already: u has two

@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 #include "gpbc_bn254.h"
+#include "gpbc_bn254_hash.h"
 
 namespace bn254 {
 
@@ -207,6 +208,22 @@ inline std::vector<G2Affine> HashToG2Batch(const std::vector<std::string> &msgs,
 }
 inline G1Affine HashToG1(const std::string &msg, const std::string &dst) { return HashToG1Batch({msg}, dst)[0]; }
 inline G2Affine HashToG2(const std::string &msg, const std::string &dst) { return HashToG2Batch({msg}, dst)[0]; }
+// h(u, v, w) of Gentry06 (ibe/gentry06_ibe/gentry06_ibe.go:319-343) for n items, and fr.SetBytes(SHA-256(msg)) per message (gpbc_bn254_hash.h)
+inline std::vector<Scalar> HashG1GTGTToFr(const std::vector<G1Affine> &u, const std::vector<GT> &v, const std::vector<GT> &w) {
+    if (u.size() != v.size() || u.size() != w.size()) throw std::invalid_argument("invalid inputs sizes");
+    std::vector<Scalar> out(u.size());
+    check(gpbc_hash_g1_gt_gt_to_fr(u.data(), v.data(), w.data(), u.size(), out.data()));
+    return out;
+}
+inline std::vector<Scalar> Sha256ToFrBatch(const std::vector<std::string> &msgs) {
+    std::vector<Scalar> out(msgs.size());
+    std::string data;
+    std::vector<uint64_t> off(msgs.size() + 1, 0);
+    for (size_t i = 0; i < msgs.size(); i++) { data += msgs[i]; off[i + 1] = data.size(); }
+    if (data.empty()) data.push_back('\0');
+    check(gpbc_sha256_batch(data.data(), off.data(), msgs.size(), 1, out.data()));
+    return out;
+}
 // batched forms the engine adds
 inline std::vector<GT> PairBatch(const std::vector<G1Affine> &P, const std::vector<G2Affine> &Q) {
     if (P.empty() || P.size() != Q.size()) throw std::invalid_argument("invalid inputs sizes");

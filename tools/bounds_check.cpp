@@ -22,6 +22,7 @@
 #include "../gopairingbasedcryptography_amd/csrc/gtmexp29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/gmsm29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/subset29.hip.hpp"
+#include "../gopairingbasedcryptography_amd/csrc/transcript29.hip.hpp"
 #include <condition_variable>
 #include <mutex>
 #include <thread>
@@ -622,6 +623,20 @@ void hc_wire_decode(int kind, const uint8_t *in, int elem_bytes, size_t n, uint8
         else if (kind == 1) ok[i] = g2_wire_decode(out + 128 * i, in + (size_t)elem_bytes * i, elem_bytes);
         else ok[i] = gt_wire_decode(out + 384 * i, in + 384 * i);
     }
+}
+// the transcript hash and the plain SHA-256 (csrc/transcript29.hip.hpp): the lane functions of k_hash_g1_gt_gt_to_fr and k_sha256, one
+// item after the other; the offsets go through msg_range as in the kernel (total = the length of the message buffer)
+void hc_hash_g1_gt_gt_to_fr(const uint8_t *u, const uint8_t *v, const uint8_t *w, size_t n, uint8_t *out) {
+    for (size_t i = 0; i < n; i++) hash_g1_gt_gt_to_fr_lane(u + 64 * i, v + 384 * i, w + 384 * i, out + 32 * i);
+    stats_flush();
+}
+void hc_sha256(const uint8_t *msgs, const uint64_t *off, size_t total, size_t n, int to_fr, uint8_t *out) {
+    for (size_t i = 0; i < n; i++) {
+        uint64_t lo, len;
+        msg_range(off, total, i, lo, len);
+        sha256_lane(msgs + lo, len, to_fr != 0, out + 32 * i);
+    }
+    stats_flush();
 }
 // the square roots of csrc/wire29.hip.hpp on their own (gnark fp.Element / E2 in and out): out = the value returned, ok = whether it is a root
 void hc_fe_sqrt(const uint8_t *A, size_t n, uint8_t *out, uint8_t *ok) {
