@@ -20,6 +20,7 @@ inputs sizes").  Everything computes on the GPU; a missing extension or device r
 Every entry is written once for both kinds of buffer: it normalises its arguments (_buffers.py), checks its own shape
 relations, gets its output, and only then touches the engine through _call, which picks the host or the device symbol.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -337,54 +338,68 @@ def g2_scalar_mul(bases, scalars, out=None):
     return _scalar_mul("g2", G2_BYTES, bases, scalars, out)
 
 
-def _multi_scalar_mul(group, width, bases, scalars, seg_off, out, workspace):
-    """out[s] = sum_{i in [seg_off[s], seg_off[s+1])} [scalars[i]] bases[i] (include/gpbc_bn254_ext.h): gt_multi_exp's shape in G1 / G2"""
-    if isinstance(scalars, int):
-        scalars = [scalars]
-    if isinstance(scalars, (list, tuple)):
-        if any(not 0 <= int(s) < (1 << 256) for s in scalars):
-            raise ValueError("scalars must be in [0, 2^256) (they act as their residue mod r)")
-        scalars = np.frombuffer(b"".join(int(s).to_bytes(32, "little") for s in scalars), dtype=np.uint8)
-    k = None if scalars is None else scalars_to_bytes(scalars)
+# What differs between the segmented reductions (gt_multi_exp, g1 / g2_multi_scalar_mul) for _segmented_reduce: the C entry, the element
+# width, the words of the messages, the workspace-size call (lib, n, n_seg) and the alignment the kernels need of the workspace.
+_SegRed = collections.namedtuple("_SegRed", "entry width x_name k_name elements per_element shared int_range ws_bytes ws_align")
+
+
+def _segmented_reduce(op, x, k, seg_off, out, workspace):
+    """out[s] = the reduction of x[seg_off[s]:seg_off[s+1]] with one k per element, one list of k for segments of equal length, or none"""
+    if isinstance(k, int):
+        k = [k]
+    if isinstance(k, (list, tuple)):
+        if any(not 0 <= int(e) < (1 << 256) for e in k):
+            raise ValueError(op.int_range)
+        k = np.frombuffer(b"".join(int(e).to_bytes(32, "little") for e in k), dtype=np.uint8)
     dev_table = bufs.is_torch(seg_off)
-    dev = bufs.device_of(bases, seg_off if dev_table else None, k if bufs.is_torch(k) else None)   # a host scalar list may go with device bases
-    bases, n = bufs.rows(bases, width, "bases")
+    dev = bufs.device_of(x, seg_off if dev_table else None, k if bufs.is_torch(k) else None)     # a host k may go with device bases
+    x, n = bufs.rows(x, op.width, op.x_name)
     if dev_table:
-        n_seg = _device_segments(seg_off, dev, "points")
+        n_seg = _device_segments(seg_off, dev, op.elements)
     else:
         seg = np.ascontiguousarray(seg_off, dtype=np.uint64).reshape(-1)
         n_seg = seg.size - 1
         if n_seg < 1 or int(seg[0]) != 0 or int(seg[-1]) != n or (np.diff(seg.astype(np.int64)) < 0).any():
-            raise ValueError("seg_off must have n_seg + 1 >= 2 non-decreasing entries from 0 to the number of points")
+            raise ValueError("seg_off must have n_seg + 1 >= 2 non-decreasing entries from 0 to the number of %s" % op.elements)
     nk = 0
     if k is not None:
-        k, nk = bufs.rows(k, SCALAR_BYTES, "scalars")
+        k, nk = bufs.rows(k, SCALAR_BYTES, op.k_name)
         if nk != n:
             if nk > n or nk * n_seg != n:
-                raise ValueError("scalars must hold one per point, or one list for segments of equal length (nk = %d, n = %d, n_seg = %d)" % (nk, n, n_seg))
+                raise ValueError("%s must hold %s, or one list for segments of equal length (nk = %d, n = %d, n_seg = %d)" % (op.k_name, op.per_element, nk, n, n_seg))
             if not dev_table and (np.diff(seg.astype(np.int64)) != nk).any():
-                raise ValueError("a shared scalar list of %d needs segments of exactly %d points" % (nk, nk))
-    out = bufs.output(out, (n_seg, width), dev)
-    name = group + "_multi_scalar_mul"
+                raise ValueError("a shared %s list of %d needs segments of exactly %d %s" % (op.shared, nk, nk, op.elements))
+    out = bufs.output(out, (n_seg, op.width), dev)
     if dev is None:
-        _call(name, None, bases, k, nk, seg, n_seg, out)
+        _call(op.entry, None, x, k, nk, seg, n_seg, out)
         return out
-    # The device form is a call of its own, as in gt_multi_exp: a segment table in device memory (the caller's, validated by a
-    # kernel, or the host table copied there), n, a caller-side workspace, and a host scalar list next to device bases.
+    # The device form is a call of its own, which is why this body names the buffer kind: the *_dev entry walks a segment table in
+    # device memory (the caller's, validated by a kernel, or the host table copied there), takes n and a caller-side workspace, and
+    # accepts a host list of k next to device bases.
     if k is not None and not bufs.is_torch(k):
-        k = bufs.put(k.copy(), bases)
+        k = bufs.put(k.copy(), x)
     if dev_table:
         _check_segments(dev, seg_off, n, n_seg)
         import torch
         if nk != n and k is not None and bool((seg_off.view(torch.int64).diff() != nk).any()):
-            raise ValueError("a shared scalar list of %d needs segments of exactly %d points" % (nk, nk))
+            raise ValueError("a shared %s list of %d needs segments of exactly %d %s" % (op.shared, nk, nk, op.elements))
     else:
-        seg_off = bufs.put(seg.astype(np.int64), bases)
-    ws = _workspace(workspace, _lib.load().gpbc_multi_scalar_mul_workspace_bytes(n, n_seg, int(group == "g2")), dev)
-    if bufs.address(ws[0]) % 16:
-        raise ValueError("workspace must be 16-byte aligned")
-    _call(name, dev, bases, k, nk, seg_off, n, n_seg, out, *ws)
+        seg_off = bufs.put(seg.astype(np.int64), x)
+    ws = _workspace(workspace, op.ws_bytes(_lib.load(), n, n_seg), dev)
+    if bufs.address(ws[0]) % op.ws_align:
+        raise ValueError("workspace must be %d-byte aligned" % op.ws_align)
+    _call(op.entry, dev, x, k, nk, seg_off, n, n_seg, out, *ws)
     return out
+
+
+def _multi_scalar_mul(group, width, bases, scalars, seg_off, out, workspace):
+    """out[s] = sum_{i in [seg_off[s], seg_off[s+1])} [scalars[i]] bases[i] (include/gpbc_bn254_ext.h): gt_multi_exp's shape in G1 / G2"""
+    op = _SegRed(group + "_multi_scalar_mul", width, "bases", "scalars", "points", "one per point", "scalar",
+                 "scalars must be in [0, 2^256) (they act as their residue mod r)",
+                 lambda lib, n, n_seg: lib.gpbc_multi_scalar_mul_workspace_bytes(n, n_seg, int(group == "g2")), 16)
+    if scalars is not None and not isinstance(scalars, (int, list, tuple)):
+        scalars = scalars_to_bytes(scalars)                                  # a buffer as it is; any other iterable of integers mod r
+    return _segmented_reduce(op, bases, scalars, seg_off, out, workspace)
 
 
 def g1_multi_scalar_mul(bases, scalars, seg_off, out=None, workspace=None):
@@ -781,49 +796,9 @@ def gt_multi_exp(x, k, seg_off, out=None, workspace=None):
     against many ciphertexts), or None for the plain product; Python ints must be in [0, 2^256).  numpy arrays in, numpy array out;
     CUDA tensors in (seg_off a host sequence, or an int64 / uint64 CUDA tensor that is then validated on the device), CUDA tensor
     out, enqueued on the current torch stream.  Arguments are checked before the engine is touched."""
-    if isinstance(k, int):
-        k = [k]
-    if isinstance(k, (list, tuple)):
-        if any(not 0 <= int(e) < (1 << 256) for e in k):
-            raise ValueError("exponents must be in [0, 2^256): invert the base for a negative one")
-        k = np.frombuffer(b"".join(int(e).to_bytes(32, "little") for e in k), dtype=np.uint8)
-    dev_table = bufs.is_torch(seg_off)
-    dev = bufs.device_of(x, seg_off if dev_table else None, k if bufs.is_torch(k) else None)     # a host k may go with device bases
-    x, n = bufs.rows(x, GT_BYTES, "x")
-    if dev_table:
-        n_seg = _device_segments(seg_off, dev, "elements")
-    else:
-        seg = np.ascontiguousarray(seg_off, dtype=np.uint64).reshape(-1)
-        n_seg = seg.size - 1
-        if n_seg < 1 or int(seg[0]) != 0 or int(seg[-1]) != n or (np.diff(seg.astype(np.int64)) < 0).any():
-            raise ValueError("seg_off must have n_seg + 1 >= 2 non-decreasing entries from 0 to the number of elements")
-    nk = 0
-    if k is not None:
-        k, nk = bufs.rows(k, SCALAR_BYTES, "k")
-        if nk != n:
-            if nk > n or nk * n_seg != n:
-                raise ValueError("k must hold one exponent per element, or one list for segments of equal length (nk = %d, n = %d, n_seg = %d)" % (nk, n, n_seg))
-            if not dev_table and (np.diff(seg.astype(np.int64)) != nk).any():
-                raise ValueError("a shared exponent list of %d needs segments of exactly %d elements" % (nk, nk))
-    out = bufs.output(out, (n_seg, GT_BYTES), dev)
-    if dev is None:
-        _call("gt_multi_exp", None, x, k, nk, seg, n_seg, out)
-        return out
-    # The device form is a call of its own, which is why this body names the buffer kind: gpbc_gt_multi_exp_dev walks a segment
-    # table in device memory (the caller's, validated by a kernel, or the host table copied there), takes n and a caller-side
-    # workspace, and accepts a host exponent list next to device bases.
-    if k is not None and not bufs.is_torch(k):
-        k = bufs.put(k.copy(), x)
-    if dev_table:
-        _check_segments(dev, seg_off, n, n_seg)
-        import torch
-        if nk != n and k is not None and bool((seg_off.view(torch.int64).diff() != nk).any()):
-            raise ValueError("a shared exponent list of %d needs segments of exactly %d elements" % (nk, nk))
-    else:
-        seg_off = bufs.put(seg.astype(np.int64), x)
-    ws = _workspace(workspace, _lib.load().gpbc_gt_multi_exp_workspace_bytes(n, n_seg), dev)
-    _call("gt_multi_exp", dev, x, k, nk, seg_off, n, n_seg, out, *ws)
-    return out
+    op = _SegRed("gt_multi_exp", GT_BYTES, "x", "k", "elements", "one exponent per element", "exponent",
+                 "exponents must be in [0, 2^256): invert the base for a negative one", lambda lib, n, n_seg: lib.gpbc_gt_multi_exp_workspace_bytes(n, n_seg), 1)
+    return _segmented_reduce(op, x, k, seg_off, out, workspace)
 
 
 def gt_prod(x, seg_off=None):

@@ -21,11 +21,12 @@
 // wavefront (G and G + 1 terms side by side; DESIGN.md 15 has what was seen) — a suspected compiler problem that was not reduced
 // further; every lane now reads its own result back from memory after the loop.  The next group overwrites the tables and the
 // window words, so the block is a lane's whole footprint whatever the run's length.
-// The same file cuts the work (gmsm_pieces / gmsm_segment_range / gmsm_piece_range): the kernels (csrc/gpbc_gmsm.hip) and the host interval harness
-// (tools/bounds_check.cpp, hc_multi_scalar_mul) run one plan.
+// The work is cut by csrc/segred29.hip.hpp with GMSM_SHAPE (one lane per piece): the kernels (csrc/gpbc_gmsm.hip) and the host interval
+// harness (tools/bounds_check.cpp, hc_multi_scalar_mul) run one plan.
 #ifndef GPBC_GMSM29_HIP_HPP
 #define GPBC_GMSM29_HIP_HPP
 #include "curve29.hip.hpp"
+#include "segred29.hip.hpp"
 
 namespace gpbc {
 
@@ -34,39 +35,10 @@ namespace gpbc {
 #endif
 static_assert(GMSM_GROUP >= 1 && GMSM_GROUP <= 8, "a window word holds four index bits for each of at most 8 terms");
 constexpr int GMSM_DIGIT_DWORDS = 128;                                       // 80 two-bit windows of a 160-bit GLV half / 96 bits of a GLS quarter, padded to a whole number of 128-byte rows
-constexpr size_t GMSM_FILL = 131072;                                         // lanes that fill the chip: 256 CUs x 4 SIMDs x 2 waves x 64 lanes
-constexpr size_t GMSM_SUM_MIN = 8;                                           // a piece of a plain sum has at least this many points on average
+// lanes that fill the chip: 256 CUs x 4 SIMDs x 2 waves x 64 lanes; a piece of a plain sum has at least 8 points on average
+constexpr SegRedShape GMSM_SHAPE{131072, GMSM_GROUP, 8};
 template <class F> constexpr int gmsm_acc_dwords() { return (int)((sizeof(JacP<F>) + 127) / 128) * 32; }   // the piece's accumulator, whole 128-byte rows
 template <class F> constexpr int gmsm_lane_dwords() { return GMSM_GROUP * glv_table_dwords<F>() + GMSM_DIGIT_DWORDS + gmsm_acc_dwords<F>(); }
-
-// Pieces per segment, from the sizes alone (the segment table may live in device memory): enough pieces to fill the chip, but none
-// shorter on average than one group of terms (with scalars) or GMSM_SUM_MIN points (plain sums).  1 = no cut: a lane per segment
-// writes the result itself.  n_seg x J <= GMSM_FILL + n_seg whatever the segment lengths are.
-GPBC_INLINE size_t gmsm_pieces(size_t n, size_t n_seg, bool has_k) {
-    if (!n_seg) return 1;
-    const size_t by_len = (n / n_seg) / (has_k ? (size_t)GMSM_GROUP : GMSM_SUM_MIN);
-    const size_t by_fill = (GMSM_FILL + n_seg - 1) / n_seg;
-    const size_t j = by_len < by_fill ? by_len : by_fill;
-    return j ? j : 1;
-}
-// Segment s as [lo, hi): from the table with every offset clamped to n (a malformed table shortens segments, it never reaches outside
-// the points), or, without a table (the folds), uniform segments of m; with a shared scalar list (nk_shared != 0) a segment ends after
-// nk_shared terms, so the list is never overrun.
-GPBC_INLINE void gmsm_segment_range(const uint64_t *seg_off, size_t m, size_t n, size_t s, size_t nk_shared, size_t &lo, size_t &hi) {
-    if (seg_off) {
-        const uint64_t o0 = seg_off[s], o1 = seg_off[s + 1];
-        lo = o0 < n ? (size_t)o0 : n;
-        hi = o1 < n ? (size_t)o1 : n;
-        if (hi < lo) hi = lo;
-    } else { lo = s * m; hi = lo + m; }
-    if (nk_shared && hi - lo > nk_shared) hi = lo + nk_shared;
-}
-// Terms [a, b) of piece j of J of the segment [lo, hi): the J pieces tile the segment, their lengths differ by at most one.
-GPBC_INLINE void gmsm_piece_range(size_t lo, size_t hi, size_t j, size_t J, size_t &a, size_t &b) {
-    const size_t len = hi - lo;
-    a = lo + (size_t)((uint64_t)len * j / J);                               // len < 2^46, J <= 2^17 + 1: no overflow
-    b = lo + (size_t)((uint64_t)len * (j + 1) / J);
-}
 
 // ---- one term: split, table, window indices.  Returns the term's highest window (-1: the term contributes nothing — a base at
 // infinity or a scalar = 0 mod r — and has no table; its indices stay 0).  slot = the term's position in the group.

@@ -1,4 +1,4 @@
-// Shared by the translation units of libgpbc_bn254.so (gpbc_core.hip, gpbc_pairing.hip, gpbc_curve.hip, gpbc_wire.hip):
+// Shared by the translation units of libgpbc_bn254.so (the list is in _build.py):
 // launch-bound macros, small device-side load / store helpers, and the host-side plumbing every entry point uses
 // (thread-local error text, device binding, RAII device buffers, the per-stream internal workspace).  The units are compiled
 // separately (each carries its own copy of the device code it needs; no relocatable device code) and linked into one
@@ -17,6 +17,7 @@
 #include <vector>
 #include "../../include/gpbc_bn254.h"
 #include "curve29.hip.hpp"
+#include "segred29.hip.hpp"
 
 using namespace gpbc;
 
@@ -300,5 +301,33 @@ using HostCallBody = std::function<int(const DevCols &d, size_t n, hipStream_t s
 int host_call(size_t n, const HostCall &c, const HostRoute &r, const HostCallBody &body);
 int host_call_sharded(size_t n, size_t min_units, const HostCall &c, const HostRoute &r, const HostCallBody &body);
 void free_call_lanes();
+
+// ---- Segment tables on the host.  check_segment_table: k + 1 offsets, the first 0, none below its predecessor; *n = the last.
+// run_sharded_segments cuts the segments [0, k) of a checked table with run_sharded (segments are the independent units; min_units
+// counts elements, at the table's mean segment length) and hands the body a run of whole segments [lo, hi) with its table rebased to
+// zero (hi - lo + 1 offsets; the caller's own table for the whole range) and `base`, the offset of the run's first element.
+int check_segment_table(const uint64_t *seg_off, size_t k, size_t *n);
+int run_sharded_segments(const uint64_t *seg_off, size_t k, size_t min_units, const std::function<int(size_t lo, size_t hi, const uint64_t *seg, size_t base)> &body);
+
+// ---- Segmented reductions (csrc/segred29.hip.hpp has the plan): what differs between the GT multi-exponentiation and the G1 / G2
+// multi-scalar multiplication, and one driver for the rest.  launch enqueues the pieces [piece0, piece0 + n_pieces) of one level on
+// the stream (with k: tabws holds the tables of that many pieces); it lives in the unit that defines the kernels and knows how many
+// lanes a piece takes.
+struct SegRedOp {
+    SegRedShape shape;
+    size_t elem_bytes, tab_bytes;                      // per element of x / out; of tables per piece
+    size_t ws_align;                                   // what the kernels need of the workspace's address (1: nothing)
+    const char *elements, *scalars, *scalar, *x_name, *ws_fn;     // the words of the messages
+    int (*launch)(const SegRedArgs &g, int32_t *tabws, hipStream_t st);
+};
+size_t segred_workspace_bytes(const SegRedOp &op, size_t n, size_t n_seg);
+// The device entry: the argument rules (everything that needs no look at a table), the plan, the workspace checks, then one level
+// after the other in chunks of at most shape.fill pieces; asynchronous on `stream`.
+int segred_dev(const SegRedOp &op, const void *d_x, const void *d_k, size_t nk, const uint64_t *d_seg_off, size_t n, size_t n_seg, void *d_out,
+               void *d_workspace, size_t workspace_bytes, void *stream);
+// The host-pointer entry: the table is validated here and a shared list asks for segments of exactly nk; a shard is a run of whole
+// segments, each through host_call: a call of up to SMALL_CALL_MAX_UNITS elements on a call lane of its own (not combined), a larger
+// one through device blocks.
+int segred_host(const SegRedOp &op, const void *x, const void *k, size_t nk, const uint64_t *seg_off, size_t n_seg, void *out);
 
 #endif

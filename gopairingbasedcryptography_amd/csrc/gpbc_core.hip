@@ -1,4 +1,4 @@
-// libgpbc_bn254.so, unit 1 of 4: process-wide state and lifetime entries of the C ABI (include/gpbc_bn254.h): the list of
+// libgpbc_bn254.so, one of the units listed in _build.py: process-wide state and lifetime entries of the C ABI (include/gpbc_bn254.h): the list of
 // bound devices with a thread-local current device, host-side sharding of batch entries over the devices, the RCCL
 // communicator(s) and the all-gather entries, the per-(device, stream) internal workspace, and the field-level test
 // entry.  gfx950 only.
@@ -372,6 +372,87 @@ int host_call_sharded(size_t n, size_t min_units, const HostCall &c, const HostR
         for (int i = 0; i < 3; i++) if (s.in[i] && !s.in_one[i]) s.in[i] = (const uint8_t *)s.in[i] + lo * s.in_bytes[i];
         for (int i = 0; i < 2; i++) if (s.out[i]) s.out[i] = (uint8_t *)s.out[i] + lo * s.out_bytes[i];
         return host_call(hi - lo, s, r, body);
+    });
+}
+
+// ---- segment tables on the host and the segmented-reduction driver (gpbc_common.hpp)
+int check_segment_table(const uint64_t *seg_off, size_t k, size_t *n) {
+    if (!seg_off) return fail(GPBC_ERR_INVALID_ARG, "null segment table");
+    if (seg_off[0] != 0) return fail(GPBC_ERR_INVALID_ARG, "seg_off[0] must be 0");
+    for (size_t j = 0; j < k; j++)
+        if (seg_off[j + 1] < seg_off[j]) return fail(GPBC_ERR_INVALID_ARG, "segment table not monotone at %zu", j);
+    *n = (size_t)seg_off[k];
+    return GPBC_OK;
+}
+int run_sharded_segments(const uint64_t *seg_off, size_t k, size_t min_units, const std::function<int(size_t, size_t, const uint64_t *, size_t)> &body) {
+    const size_t n = (size_t)seg_off[k], avg = k && n / k ? n / k : 1;
+    return run_sharded(k, (min_units + avg - 1) / avg, [&](size_t lo, size_t hi) {
+        if (lo == 0 && hi == k) return body(lo, hi, seg_off, 0);
+        std::vector<uint64_t> sub(hi - lo + 1);
+        const uint64_t base = seg_off[lo];
+        for (size_t j = lo; j <= hi; j++) sub[j - lo] = seg_off[j] - base;
+        return body(lo, hi, sub.data(), (size_t)base);
+    });
+}
+size_t segred_workspace_bytes(const SegRedOp &op, size_t n, size_t n_seg) {
+    const size_t a = segred_plan(op.shape, op.elem_bytes, op.tab_bytes, n, n_seg, true).bytes(), b = segred_plan(op.shape, op.elem_bytes, op.tab_bytes, n, n_seg, false).bytes();
+    return a > b ? a : b;
+}
+// the argument rules shared by the host and the device entry (everything that needs no look at a table).  `out` is written while
+// other pieces still read x and k, so it may overlap neither.
+static int segred_check_args(const SegRedOp &op, const void *x, const void *k, size_t nk, const void *seg_off, size_t n, size_t n_seg, const void *out) {
+    if (!n_seg) return fail(GPBC_ERR_INVALID_ARG, "invalid inputs sizes");
+    if (!seg_off) return fail(GPBC_ERR_INVALID_ARG, "null segment table");
+    if ((n && !x) || !out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    if (!k && nk) return fail(GPBC_ERR_INVALID_ARG, "nk must be 0 without %s (got nk = %zu)", op.scalars, nk);
+    if (k && nk != n && (nk > n || nk * n_seg != n))
+        return fail(GPBC_ERR_INVALID_ARG, "nk must be n, or n / n_seg when every segment has that many %s (got nk = %zu, n = %zu, n_seg = %zu)", op.elements, nk, n, n_seg);
+    const uint8_t *xb = (const uint8_t *)x, *kb = (const uint8_t *)k, *ob = (const uint8_t *)out;
+    if (n && xb < ob + n_seg * op.elem_bytes && ob < xb + n * op.elem_bytes) return fail(GPBC_ERR_INVALID_ARG, "out must not overlap %s", op.x_name);
+    if (k && nk && kb < ob + n_seg * op.elem_bytes && ob < kb + nk * GPBC_SCALAR_BYTES) return fail(GPBC_ERR_INVALID_ARG, "out must not overlap the %s", op.scalars);
+    return GPBC_OK;
+}
+int segred_dev(const SegRedOp &op, const void *d_x, const void *d_k, size_t nk, const uint64_t *d_seg_off, size_t n, size_t n_seg, void *d_out,
+               void *d_workspace, size_t workspace_bytes, void *stream) {
+    TRY(segred_check_args(op, d_x, d_k, nk, d_seg_off, n, n_seg, d_out));
+    const SegRedPlan plan = segred_plan(op.shape, op.elem_bytes, op.tab_bytes, n, n_seg, d_k != nullptr);
+    if (plan.bytes() && (!d_workspace || workspace_bytes < plan.bytes()))
+        return fail(GPBC_ERR_INVALID_ARG, "workspace too small: %zu bytes given, %zu needed (%s)", workspace_bytes, plan.bytes(), op.ws_fn);
+    if (plan.bytes() && ((uintptr_t)d_workspace & (op.ws_align - 1)))
+        return fail(GPBC_ERR_INVALID_ARG, "workspace must be %zu-byte aligned (its rows are read and written 128 bits at a time)", op.ws_align);
+    TRY(bind_device());
+    const hipStream_t st = (hipStream_t)stream;
+    uint8_t *ws = (uint8_t *)d_workspace;
+    uint8_t *const val[2] = {ws + plan.tab_bytes, ws + plan.tab_bytes + plan.val_bytes[0]};
+    return segred_walk(op.shape, segred_args(d_x, d_k, nk, d_seg_off, n, n_seg), val, d_out, [&](SegRedArgs g, size_t pieces) {
+        for (g.piece0 = 0; g.piece0 < pieces; g.piece0 += op.shape.fill) {
+            g.n_pieces = pieces - g.piece0 < op.shape.fill ? pieces - g.piece0 : op.shape.fill;
+            TRY(op.launch(g, (int32_t *)ws, st));
+        }
+        return (int)GPBC_OK;
+    });
+}
+int segred_host(const SegRedOp &op, const void *x, const void *k, size_t nk, const uint64_t *seg_off, size_t n_seg, void *out) {
+    if (!n_seg) return fail(GPBC_ERR_INVALID_ARG, "invalid inputs sizes");
+    size_t n = 0;
+    TRY(check_segment_table(seg_off, n_seg, &n));
+    TRY(segred_check_args(op, x, k, nk, seg_off, n, n_seg, out));
+    const bool shared = k && nk != n;
+    if (shared)
+        for (size_t j = 0; j < n_seg; j++)
+            if (seg_off[j + 1] - seg_off[j] != nk)
+                return fail(GPBC_ERR_INVALID_ARG, "a shared %s list of %zu needs segments of %zu %s (segment %zu has %zu)", op.scalar, nk, nk, op.elements, j, (size_t)(seg_off[j + 1] - seg_off[j]));
+    constexpr size_t SHARD_MIN_ELEMENTS = 4096;
+    return run_sharded_segments(seg_off, n_seg, SHARD_MIN_ELEMENTS, [&](size_t lo, size_t hi, const uint64_t *seg, size_t base) {
+        const size_t segs = hi - lo, ns = (size_t)seg[segs], nks = shared ? nk : k ? ns : 0;
+        const void *ks = k && !shared ? (const uint8_t *)k + base * GPBC_SCALAR_BYTES : k;
+        HostCall c = HostCall().input((const uint8_t *)x + base * op.elem_bytes, ns * op.elem_bytes, true).input(ks, nks * GPBC_SCALAR_BYTES, true)
+                         .input(seg, (segs + 1) * sizeof(uint64_t), true).output((uint8_t *)out + lo * op.elem_bytes, op.elem_bytes);
+        c.units = ns > segs ? ns : segs;
+        const size_t wsb = segred_workspace_bytes(op, ns, segs);
+        return host_call(segs, c, HostRoute{CALL_KINDS, nullptr, 0, SMALL_CALL_MAX_UNITS, 0, wsb}, [&](const DevCols &d, size_t, hipStream_t st) {
+            return segred_dev(op, d.in[0], d.in[1], nks, (const uint64_t *)d.in[2], ns, segs, d.out[0], d.tmp, wsb, st);
+        });
     });
 }
 

@@ -1,4 +1,4 @@
-// libgpbc_bn254.so, unit 3 of 4: G1 / G2 scalar multiplication, point sums, fixed-base window tables and the sums over
+// libgpbc_bn254.so, one of the units listed in _build.py: G1 / G2 scalar multiplication, point sums, fixed-base window tables and the sums over
 // them, with their C-ABI entries (include/gpbc_bn254.h).  gfx950 only.
 #include "gpbc_common.hpp"
 #include "curve29_oct.hip.hpp"

@@ -1,4 +1,4 @@
-// libgpbc_bn254.so, unit 6 of 6: the elementwise group law — G1 / G2 addition, subtraction and doubling of affine points
+// libgpbc_bn254.so, one of the units listed in _build.py: the elementwise group law — G1 / G2 addition, subtraction and doubling of affine points
 // (csrc/group29.hip.hpp) with their C-ABI entries (include/gpbc_bn254.h).  gfx950 only.
 #include "gpbc_common.hpp"
 #include "group29.hip.hpp"

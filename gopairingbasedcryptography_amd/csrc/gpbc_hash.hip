@@ -1,4 +1,4 @@
-// libgpbc_bn254.so, unit 11 of 11: SHA-256 on the device with the digest as bytes or as a scalar — the transcript hash H(u, v, w) of
+// libgpbc_bn254.so, one of the units listed in _build.py: SHA-256 on the device with the digest as bytes or as a scalar — the transcript hash H(u, v, w) of
 // Gentry06 and the plain batched SHA-256 (csrc/transcript29.hip.hpp) with their C-ABI entries (include/gpbc_bn254_hash.h).  gfx950 only.
 #include "gpbc_common.hpp"
 #include "../../include/gpbc_bn254_hash.h"

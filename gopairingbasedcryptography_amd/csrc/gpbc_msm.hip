@@ -1,4 +1,4 @@
-// libgpbc_bn254.so, unit 5 of 5: bucket (Pippenger) multi-scalar multiplication over variable bases (csrc/msm29.hip.hpp) —
+// libgpbc_bn254.so, one of the units listed in _build.py: bucket (Pippenger) multi-scalar multiplication over variable bases (csrc/msm29.hip.hpp) —
 // the engine behind gpbc_g1/g2_scalar_mul_sum(_dev) from 16 384 terms on.  gfx950 only.
 //
 // Device plan for n terms, c-bit windows (c = 16 from 2^17 terms on, else 12), W = ceil(256 / c), M = W * 2^c bucket keys:

@@ -1,4 +1,4 @@
-// libgpbc_bn254.so, unit 2 of 4: Miller loop (two phases, single pairs / shared-squaring chunks / fixed Q), final
+// libgpbc_bn254.so, one of the units listed in _build.py: Miller loop (two phases, single pairs / shared-squaring chunks / fixed Q), final
 // exponentiation, segment products and the GT kernels, with their C-ABI entries (include/gpbc_bn254.h).  gfx950 only.
 #include "gpbc_common.hpp"
 #include "wide29.hip.hpp"
@@ -892,14 +892,6 @@ int gpbc_pair_batch(const void *P, const void *Q, size_t n, void *gt_out) {
                              HostRoute{CALL_PAIRS, small_pairs_run, small_limit(), 0, PIPE_CHUNK},
                              [](const DevCols &d, size_t m, hipStream_t st) { return gpbc_pair_batch_dev(d.in[0], d.in[1], m, d.out[0], st); });
 }
-static int check_segments(const uint64_t *seg_off, size_t k, size_t *n_pairs) {
-    if (!seg_off) return fail(GPBC_ERR_INVALID_ARG, "null segment table");
-    if (seg_off[0] != 0) return fail(GPBC_ERR_INVALID_ARG, "seg_off[0] must be 0");
-    for (size_t j = 0; j < k; j++)
-        if (seg_off[j + 1] < seg_off[j]) return fail(GPBC_ERR_INVALID_ARG, "segment table not monotone at %zu", j);
-    *n_pairs = (size_t)seg_off[k];
-    return GPBC_OK;
-}
 // Core of the multi-pairing with the segment table on the HOST and the points in device memory: every segment is cut into
 // chunks of at most L <= MULTI_CHUNK pairs, one lane pair runs the Miller accumulator of a whole chunk with shared
 // squarings (k_miller_accumulate_chunks), the chunk values of each segment are multiplied (one lane per segment) and one
@@ -1087,7 +1079,7 @@ int gpbc_multi_pair_fixed_q(const void *P, const void *Q, size_t m, size_t k, vo
 int gpbc_multi_pair_hostseg_dev(const void *dP, const void *dQ, const uint64_t *seg_off, size_t k, void *d_gt_out, void *stream) {
     if (!k) return fail(GPBC_ERR_INVALID_ARG, "invalid inputs sizes");
     size_t n_pairs = 0;
-    TRY(check_segments(seg_off, k, &n_pairs));
+    TRY(check_segment_table(seg_off, k, &n_pairs));
     if ((n_pairs && (!dP || !dQ)) || !d_gt_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
     TRY(bind_device());
     return multi_pair_core((const uint8_t *)dP, (const uint8_t *)dQ, seg_off, k, n_pairs, (uint8_t *)d_gt_out, nullptr, (hipStream_t)stream);
@@ -1095,7 +1087,7 @@ int gpbc_multi_pair_hostseg_dev(const void *dP, const void *dQ, const uint64_t *
 static int multi_pair_host(const void *P, const void *Q, const uint64_t *seg_off, size_t k, void *gt_out, uint8_t *ok_out) {
     if (!k) return fail(GPBC_ERR_INVALID_ARG, "invalid inputs sizes");
     size_t n_pairs = 0;
-    TRY(check_segments(seg_off, k, &n_pairs));
+    TRY(check_segment_table(seg_off, k, &n_pairs));
     if ((n_pairs && (!P || !Q)) || (!gt_out && !ok_out)) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
     // one run of segments: a latency call (Pair / PairingCheck as the reference makes them) through the call lanes (small_pairs_run),
     // a larger one by multi_pair_core; the GT values of a PairingCheck land in the body's temporary block
@@ -1108,14 +1100,9 @@ static int multi_pair_host(const void *P, const void *Q, const uint64_t *seg_off
         });
     };
     // segments are the independent units: a shard is a run of whole segments with its table rebased to zero
-    const size_t avg = n_pairs / k ? n_pairs / k : 1;
-    return run_sharded(k, (SHARD_MIN_UNITS + avg - 1) / avg, [=](size_t lo, size_t hi) {
-        if (lo == 0 && hi == k) return run(P, Q, seg_off, k, n_pairs, gt_out, ok_out);
-        std::vector<uint64_t> sub(hi - lo + 1);
-        const uint64_t base = seg_off[lo];
-        for (size_t j = lo; j <= hi; j++) sub[j - lo] = seg_off[j] - base;
-        return run((const uint8_t *)P + base * GPBC_G1_BYTES, (const uint8_t *)Q + base * GPBC_G2_BYTES, sub.data(), hi - lo,
-                   (size_t)sub.back(), gt_out ? (uint8_t *)gt_out + lo * GPBC_GT_BYTES : nullptr, ok_out ? ok_out + lo : nullptr);
+    return run_sharded_segments(seg_off, k, SHARD_MIN_UNITS, [=](size_t lo, size_t hi, const uint64_t *seg, size_t base) {
+        return run((const uint8_t *)P + base * GPBC_G1_BYTES, (const uint8_t *)Q + base * GPBC_G2_BYTES, seg, hi - lo,
+                   (size_t)seg[hi - lo], gt_out ? (uint8_t *)gt_out + lo * GPBC_GT_BYTES : nullptr, ok_out ? ok_out + lo : nullptr);
     });
 }
 int gpbc_multi_pair(const void *P, const void *Q, const uint64_t *seg_off, size_t k, void *gt_out) {

@@ -1,4 +1,4 @@
-// libgpbc_bn254.so, unit 10 of 10: bit-selected sums over a fixed set in G1 / G2 — the subset-sum tables over the bit string and the
+// libgpbc_bn254.so, one of the units listed in _build.py: bit-selected sums over a fixed set in G1 / G2 — the subset-sum tables over the bit string and the
 // sums over them (csrc/subset29.hip.hpp) with their C-ABI entries (include/gpbc_bn254_subset.h).  gfx950 only.
 #include "gpbc_common.hpp"
 #include "../../include/gpbc_bn254_subset.h"

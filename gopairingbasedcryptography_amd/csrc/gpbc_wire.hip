@@ -1,4 +1,4 @@
-// libgpbc_bn254.so, unit 4 of 5: gnark wire formats (csrc/wire29.hip.hpp) and hash to curve — hash_to_field
+// libgpbc_bn254.so, one of the units listed in _build.py: gnark wire formats (csrc/wire29.hip.hpp) and hash to curve — hash_to_field
 // (csrc/xmd29.hip.hpp) and the group part (csrc/h2c29.hip.hpp) — with their C-ABI entries (include/gpbc_bn254.h).  gfx950 only.
 #include "gpbc_common.hpp"
 #include "curve29_oct.hip.hpp"

@@ -4,35 +4,20 @@
 // window costs 4 squarings + 4 table products for the four of them — 63 + 77.25 x 2.34 = 244 squaring-equivalents per factor
 // where f12p_exp256 spends 252 + 77 x 2.34 = 432.  The tables of ONE group are the whole workspace of a lane (GT_MEXP_TAB_DWORDS
 // int32, 16 KB), whatever the length of the run: the next group overwrites them.
-// The same file cuts the work (gt_mexp_pieces / gt_mexp_piece_range): the kernels (csrc/gpbc_gtmexp.hip) and the host interval
-// harness (tools/bounds_check.cpp, hc_gt_multi_exp_pair) run one plan.
+// The work is cut by csrc/segred29.hip.hpp with GT_MEXP_SHAPE (one lane pair per piece): the kernels (csrc/gpbc_gtmexp.hip) and the host
+// interval harness (tools/bounds_check.cpp, hc_gt_multi_exp_pair) run one plan.
 #ifndef GPBC_GTMEXP29_HIP_HPP
 #define GPBC_GTMEXP29_HIP_HPP
 #include "pairing29_pair.hip.hpp"
+#include "segred29.hip.hpp"
 
 namespace gpbc {
 
 constexpr int GT_MEXP_GROUP = 4;                                             // factors that share a squaring chain
 constexpr int GT_MEXP_TAB_DWORDS = GT_MEXP_GROUP * GT_EXP_TAB_DWORDS;        // per lane: 4 tables x 16 rows x 256 bytes
-constexpr size_t GT_MEXP_FILL = 65536;                                       // lane pairs that fill the chip: 256 CUs x 4 SIMDs x 2 waves x 32 pairs
-constexpr size_t GT_MEXP_PROD_MIN = 8;                                       // a product-only piece has at least this many factors on average
-
-// Pieces per segment, from the sizes alone (the segment table may live in device memory): enough pieces to fill the chip, but none
-// shorter on average than one group of factors (with exponents) or GT_MEXP_PROD_MIN factors (product only).  1 = no cut: a lane
-// pair per segment writes the result itself.  n_seg x J <= GT_MEXP_FILL + n_seg whatever the segment lengths are.
-GPBC_INLINE size_t gt_mexp_pieces(size_t n, size_t n_seg, bool has_k) {
-    if (!n_seg) return 1;
-    const size_t by_len = (n / n_seg) / (has_k ? (size_t)GT_MEXP_GROUP : GT_MEXP_PROD_MIN);
-    const size_t by_fill = (GT_MEXP_FILL + n_seg - 1) / n_seg;
-    const size_t j = by_len < by_fill ? by_len : by_fill;
-    return j ? j : 1;
-}
-// Factors [a, b) of piece j of J of the segment [lo, hi): the J pieces tile the segment, their lengths differ by at most one.
-GPBC_INLINE void gt_mexp_piece_range(size_t lo, size_t hi, size_t j, size_t J, size_t &a, size_t &b) {
-    const size_t len = hi - lo;
-    a = lo + (size_t)((uint64_t)len * j / J);                               // len < 2^47, J <= 2^16 + 1: no overflow
-    b = lo + (size_t)((uint64_t)len * (j + 1) / J);
-}
+constexpr size_t GT_MEXP_TAB_BYTES = 2 * (size_t)GT_MEXP_TAB_DWORDS * sizeof(int32_t);      // per piece: both lanes of the pair
+// lane pairs that fill the chip: 256 CUs x 4 SIMDs x 2 waves x 32 pairs; a product-only piece has at least 8 factors on average
+constexpr SegRedShape GT_MEXP_SHAPE{65536, GT_MEXP_GROUP, 8};
 
 // prod_{i < cnt} base(i)^{k_i}, digit(i, w) = window w (0 = lowest) of k_i.  Every lane of the wavefront must call it (x.all); the
 // trip counts are the wavefront's longest, pairs with fewer factors ride along on one = row 0 of a table that holds nothing else.

@@ -2,7 +2,7 @@
 GPU tests (test_multi_scalar_mul_gpu.py): bases, scalars, segment tables, and the expected bytes from the oracle (g*_scalar_mul per
 term, the terms of a segment added up by the oracle's g*_sum).
 
-The plan the cases aim at (csrc/gmsm29.hip.hpp): a call of n terms in n_seg segments cuts every segment into
+The plan the cases aim at (csrc/segred29.hip.hpp with the shape of csrc/gmsm29.hip.hpp): a call of n terms in n_seg segments cuts every segment into
 J = max(1, min(n // n_seg // G, ceil(131072 / n_seg))) pieces (plain sums: // 8), G = GMSM_GROUP read from the harness
 (hc_gmsm_group), a lane takes the terms of its piece G at a time, and the J piece values of every segment are folded by the plain-sum
 form of the same plan.  For one segment of L terms J = L // G, so J steps at every multiple of G; the lists hold the first steps
@@ -60,7 +60,7 @@ def group(g2):
 
 
 def pieces(n, n_seg, has_k, g2=False):
-    """gmsm_pieces of the header, restated"""
+    """segred_pieces (csrc/segred29.hip.hpp) with GMSM_SHAPE, restated"""
     return max(1, min(n // n_seg // (group(g2) if has_k else SUM_MIN), -(-FILL // n_seg)))
 
 

@@ -2,7 +2,7 @@
 (test_gt_multi_exp_gpu.py): bases, exponents, segment tables, and the expected bytes from the oracle (gt_exp per factor, folded
 with gt_mul from the left, starting at one).
 
-The plan the cases aim at (csrc/gtmexp29.hip.hpp): a call of n factors in n_seg segments cuts every segment into
+The plan the cases aim at (csrc/segred29.hip.hpp with the shape of csrc/gtmexp29.hip.hpp): a call of n factors in n_seg segments cuts every segment into
 J = max(1, min(n // n_seg // 4, ceil(65536 / n_seg))) pieces (product only: // 8), a lane pair takes the factors of its piece four
 at a time, and the J piece values of every segment are folded by the product-only form of the same plan.  So the boundaries are:
 group length 4 (3 / 4 / 5 factors), J stepping 1 -> 2 at 8 factors per segment (7 / 8 / 9; product only: 15 / 16 / 17), a second
@@ -29,7 +29,7 @@ EDGE_EXPS = [0, 1, 2, 15, 16, R - 1, R, R + 1, 1 << 255, (1 << 256) - 1, int("f"
 
 
 def pieces(n, n_seg, has_k):
-    """gt_mexp_pieces of the header, restated"""
+    """segred_pieces (csrc/segred29.hip.hpp) with GT_MEXP_SHAPE, restated"""
     return max(1, min(n // n_seg // (GROUP if has_k else PROD_MIN), -(-FILL // n_seg)))
 
 

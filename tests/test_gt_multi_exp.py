@@ -62,6 +62,15 @@ def test_cases_under_bounds(hc, oracle):
     assert len(seen) > 40
 
 
+def test_table_past_n_is_clamped_as_on_the_device(hc, oracle):
+    """what a device-resident table can do: the last offset lies past n.  The harness runs the kernels' own segment range, which clamps
+    every offset to n: 6 factors, table [0, 4, 9] -> out[1] is the product over x[4:6], and nothing past x[5] is read (x and k hold
+    exactly 6 rows)"""
+    x, k = gc.take(gc.pool(oracle)["pair"], 6), gc.rand_exps("past-n", 6)
+    got = hc_run(hc, x, k, [0, 4, 9])
+    assert (got == gc.expect(oracle, x, k, [0, 4, 6], False)).all()
+
+
 def test_one_element_segments_are_gt_exp(hc, oracle):
     """segments of one element are GT.Exp itself, for the harness form of k_gt_exp too (hc_gt_exp_pair)"""
     p = gc.pool(oracle)
@@ -148,6 +157,8 @@ def test_c_entries_reject_invalid_arguments(lib):
         (p(x), p(k), 6, p(ok_seg), 3, p(x)),                         # out overlaps x
         (p(x), p(k), 6, p(ok_seg), 3, VP(x.ctypes.data + 5 * G)),
         (p(x), None, 0, p(ok_seg), 3, VP(x.ctypes.data + G)),
+        (p(x), p(k), 6, p(ok_seg), 3, p(k)),                         # out overlaps k
+        (p(x), p(k), 2, p(ok_seg), 3, VP(k.ctypes.data + 32)),       # out overlaps a shared list of 2
     ]
     for i, a in enumerate(bad_host):
         rc = host(a[0], a[1], SZ(a[2]), a[3], SZ(a[4]), a[5])
@@ -164,6 +175,7 @@ def test_c_entries_reject_invalid_arguments(lib):
         (None, p(k), 6, p(ok_seg), 6, 3, p(out), p(ws), ws.size),
         (p(x), p(k), 6, p(ok_seg), 6, 3, None, p(ws), ws.size),
         (p(x), p(k), 6, p(ok_seg), 6, 3, p(x), p(ws), ws.size),          # overlap
+        (p(x), p(k), 6, p(ok_seg), 6, 3, p(k), p(ws), ws.size),          # out overlaps k
         (p(x), p(k), 6, p(ok_seg), 6, 3, p(out), p(ws), need - 1),       # workspace one byte short
         (p(x), p(k), 6, p(ok_seg), 6, 3, p(out), None, need),            # no workspace
     ]
@@ -171,7 +183,7 @@ def test_c_entries_reject_invalid_arguments(lib):
         rc = dev(a[0], a[1], SZ(a[2]), a[3], SZ(a[4]), SZ(a[5]), a[6], a[7], SZ(a[8]), None)
         assert rc == -1 and lib.gpbc_last_error(), i
     assert b"workspace" in lib.gpbc_last_error()
-    assert not out.any() and not x.any() and not ws.any()
+    assert not out.any() and not x.any() and not k.any() and not ws.any()
 
 
 def test_workspace_is_bounded_independently_of_the_segment_length(lib):

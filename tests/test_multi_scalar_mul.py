@@ -69,6 +69,11 @@ def test_cases_under_bounds(hc, oracle, g2):
         assert (got == want[label]).all(), (label, np.nonzero((got != want[label]).any(axis=1))[0][:8])
         seen.add(label)
     assert len(seen) > 60
+    if not g2:
+        # what a device-resident table can do: the last offset lies past n.  The kernels' own segment range clamps every offset to n:
+        # 6 points, table [0, 4, 9] -> out[1] is the sum over x[4:6], and nothing past x[5] is read (x and k hold exactly 6 rows)
+        x, k = gc.take(gc.pool(g2)["pt"], 6), gc.rand_scalars("past-n", 6)
+        assert (hc_run(hc, g2, x, k, [0, 4, 9]) == gc.expect(oracle, g2, x, k, [0, 4, 6], False)).all()
 
 
 def test_cases_reach_the_exceptional_additions(oracle):

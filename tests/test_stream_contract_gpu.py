@@ -354,7 +354,7 @@ def sized(eng, pool, family):
     if family == "gt sizes":
         GT = eng.pair_batch(P[:4097], Q[:4097])
         yield "gt_exp n=4097", eng.gt_exp, (GT, S[:4097].copy()), none
-        for n in (5, 37):                      # gt_mexp_pieces: one segment is cut, and its pieces folded, from 8 factors with exponents and 16 without
+        for n in (5, 37):                      # segred_pieces with GT_MEXP_SHAPE: one segment is cut, and its pieces folded, from 8 factors with exponents and 16 without
             yield "gt_multi_exp one segment of %d" % n, eng.gt_multi_exp, (GT[:n].copy(), S[:n].copy(), [0, n]), none
         yield "gt_prod one segment of 37", eng.gt_prod, (GT[:37].copy(),), none                                   # (5 factors: "gt_prod" of the table)
     if family == "fixed q sizes":

@@ -189,36 +189,32 @@ template <class Get, class Put> static void fr_lsss_block(const LsssGeom &g, uin
         for (uint32_t lane = 0; lane < FR_LSSS_WAVE; lane++) fr_lsss_clear(g, l[lane], c, st[lane], put);
     }
 }
-// segmented multi-scalar multiplication exactly as gpbc_g1/g2_multi_scalar_mul_dev (csrc/gpbc_gmsm.hip) run it: the same plan (gmsm_pieces
-// per level, gmsm_piece_range per piece), the same lane functions (gmsm_lane; gmsm_sum_lane for K = null and for the folds), one piece
-// per lane, the lanes one after the other; a piece's segment range is gmsm_segment_range's, the function the kernel calls.
+// segmented multi-scalar multiplication exactly as gpbc_g1/g2_multi_scalar_mul_dev (csrc/gpbc_gmsm.hip) run it: the plan and the level
+// walk of csrc/segred29.hip.hpp with GMSM_SHAPE (segred_piece per piece, the function the kernel calls; the value buffers sized by
+// segred_plan), the same lane functions (gmsm_lane; gmsm_sum_lane for K = null and for the folds), one piece per lane, the lanes one
+// after the other.
 template <class F, class LoadA, class StoreA> static void gmsm_host(const uint8_t *B, const uint8_t *K, size_t nk, const uint64_t *seg_off, size_t n, size_t n_seg, uint8_t *out,
                                                                      size_t pt, LoadA ld, StoreA st) {
-    std::vector<uint8_t> val[2];
+    const SegRedPlan plan = segred_plan(GMSM_SHAPE, pt, sizeof(int32_t) * (size_t)gmsm_lane_dwords<F>(), n, n_seg, K != nullptr);
+    std::vector<uint8_t> v0(plan.val_bytes[0]), v1(plan.val_bytes[1]);
+    uint8_t *const val[2] = {v0.data(), v1.data()};
     std::vector<int32_t> block(gmsm_lane_dwords<F>() + 32);
     int32_t *ws = block.data();
     while ((uintptr_t)ws & 127) ws++;                      // the lane's block: 128-byte aligned like the device's
-    const uint8_t *x = B;
-    const bool shared = K && nk != n;
-    size_t cur_n = n, m = 0;                               // m: uniform segment length of the fold levels (seg_off = null there)
-    for (int level = 0;; level++) {
-        const size_t J = gmsm_pieces(cur_n, n_seg, K != nullptr), pieces = n_seg * J;
-        uint8_t *dst = out;
-        if (J > 1) { val[level & 1].assign(pieces * pt, 0); dst = val[level & 1].data(); }
-        for (size_t P = 0; P < pieces; P++) {
-            size_t lo, hi, a, b;
-            gmsm_segment_range(seg_off, m, cur_n, P / J, shared ? nk : 0, lo, hi);
-            gmsm_piece_range(lo, hi, P % J, J, a, b);
-            const size_t k0 = shared ? lo : 0;
-            auto base = [&](size_t i) { return ld(x + (a + i) * pt); };
-            JacP<F> r = K ? gmsm_lane<F>(b - a, base, [&](size_t i, uint32_t *k) { memcpy(k, K + 32 * (a + i - k0), 32); }, ws) : gmsm_sum_lane<F>(b - a, base);
+    segred_walk(GMSM_SHAPE, segred_args(B, K, nk, seg_off, n, n_seg), val, out, [&](SegRedArgs g, size_t pieces) {
+        g.n_pieces = pieces;
+        for (size_t lane = 0; lane < pieces; lane++) {
+            size_t lo, a, b, P;
+            segred_piece(g, lane, lo, a, b, P);
+            const size_t k0 = g.k_shared ? lo : 0;
+            auto base = [&](size_t i) { return ld(g.x + (a + i) * pt); };
+            JacP<F> r = g.k ? gmsm_lane<F>(b - a, base, [&](size_t i, uint32_t *k) { memcpy(k, g.k + 32 * (a + i - k0), 32); }, ws) : gmsm_sum_lane<F>(b - a, base);
             AffP<F> o;
             jac_to_affine(o, r);
-            st(dst + P * pt, o);
+            st(g.out + P * pt, o);
         }
-        if (J == 1) return;
-        x = dst; K = nullptr; seg_off = nullptr; m = J; cur_n = pieces;
-    }
+        return 0;
+    });
 }
 // bit-selected sums exactly as gpbc_subset_sum_dev (csrc/gpbc_subset.hip) runs them: subset_entry per table row, subset_shape's chunks,
 // subset_lane per (item, chunk), the chunk-major partial sums folded as the strided point-sum kernel folds them.  Only the rows the
@@ -572,42 +568,38 @@ void hc_gt_exp_pair(const uint8_t *A, const uint8_t *K, size_t n, uint8_t *out) 
         t1.join();
     }
 }
-// segmented GT multi-exponentiation exactly as gpbc_gt_multi_exp_dev (csrc/gpbc_gtmexp.hip) runs it: the same plan (gt_mexp_pieces per
-// level, gt_mexp_piece_range per piece), the same lane functions (f12p_multi_exp, f12p_product for K = null and for the folds), one
-// piece per lane pair.  out[s] = prod_{i in [seg_off[s], seg_off[s+1])} A[i]^K[i]; nk = n, or one list of nk exponents for all segments
+// segmented GT multi-exponentiation exactly as gpbc_gt_multi_exp_dev (csrc/gpbc_gtmexp.hip) runs it: the plan and the level walk of
+// csrc/segred29.hip.hpp with GT_MEXP_SHAPE (segred_piece per piece, the function the kernel calls, so a table is clamped as on the
+// device; the value buffers sized by segred_plan), the same lane functions (f12p_multi_exp, f12p_product for K = null and for the
+// folds), one piece per lane pair.  out[s] = prod_{i in [seg_off[s], seg_off[s+1])} A[i]^K[i]; nk = n, or one list of nk exponents for all segments
 void hc_gt_multi_exp_pair(const uint8_t *A, const uint8_t *K, size_t nk, const uint64_t *seg_off, size_t n, size_t n_seg, uint8_t *out) {
-    std::vector<uint8_t> val[2];
-    const uint8_t *x = A;
-    const bool shared = K && nk != n;
-    size_t cur_n = n, m = 0;                               // m: uniform segment length of the fold levels (seg_off = null there)
-    for (int level = 0;; level++) {
-        const size_t J = gt_mexp_pieces(cur_n, n_seg, K != nullptr), pieces = n_seg * J;
-        uint8_t *dst = out;
-        if (J > 1) { val[level & 1].assign(pieces * 384, 0); dst = val[level & 1].data(); }
-        for (size_t P = 0; P < pieces; P++) {
-            const size_t s = P / J;
-            size_t lo = seg_off ? (size_t)seg_off[s] : s * m, hi = seg_off ? (size_t)seg_off[s + 1] : lo + m, a, b;
-            gt_mexp_piece_range(lo, hi, P % J, J, a, b);
+    const SegRedPlan plan = segred_plan(GT_MEXP_SHAPE, 384, GT_MEXP_TAB_BYTES, n, n_seg, K != nullptr);
+    std::vector<uint8_t> v0(plan.val_bytes[0]), v1(plan.val_bytes[1]);
+    uint8_t *const val[2] = {v0.data(), v1.data()};
+    segred_walk(GT_MEXP_SHAPE, segred_args(A, K, nk, seg_off, n, n_seg), val, out, [&](SegRedArgs g, size_t pieces) {
+        g.n_pieces = pieces;
+        for (size_t pair = 0; pair < pieces; pair++) {
+            size_t lo, a, b, P;
+            segred_piece(g, pair, lo, a, b, P);
             PairRendezvous rv;
             auto lane = [&](bool odd) {
                 PairHost px{odd, &rv};
-                const size_t half = odd ? 192 : 0, k0 = shared ? lo : 0;
-                auto base = [&](size_t i) { return f6_load(x + (a + i) * 384 + half); };
+                const size_t half = odd ? 192 : 0, k0 = g.k_shared ? lo : 0;
+                auto base = [&](size_t i) { return f6_load(g.x + (a + i) * 384 + half); };
                 F6 r;
-                if (K) {
+                if (g.k) {
                     alignas(16) static thread_local int32_t tab[GT_MEXP_TAB_DWORDS];
-                    r = f12p_multi_exp(px, b - a, base, [&](size_t i, int w) { uint32_t d; memcpy(&d, K + 32 * (a + i - k0) + 4 * (w >> 3), 4); return (int)((d >> (4 * (w & 7))) & 15); }, tab);
+                    r = f12p_multi_exp(px, b - a, base, [&](size_t i, int w) { uint32_t d; memcpy(&d, g.k + 32 * (a + i - k0) + 4 * (w >> 3), 4); return (int)((d >> (4 * (w & 7))) & 15); }, tab);
                 } else r = f12p_product(px, b - a, base);
-                f6_store(dst + P * 384 + half, r);
+                f6_store(g.out + P * 384 + half, r);
                 stats_flush();
             };
             std::thread t1(lane, true);
             lane(false);
             t1.join();
         }
-        if (J == 1) return;
-        x = dst; K = nullptr; seg_off = nullptr; m = J; cur_n = pieces;
-    }
+        return 0;
+    });
 }
 // wire formats (csrc/wire29.hip.hpp): kind 0 G1, 1 G2, 2 GT; the same per-element functions the kernels call
 void hc_wire_encode(int kind, const uint8_t *in, size_t n, int compressed, uint8_t *out) {
