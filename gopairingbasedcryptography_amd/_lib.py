@@ -76,6 +76,13 @@ HASH_SIGNATURES = {
     "gpbc_hash_version": "i:", "gpbc_sha256_batch": "i:ppzip", "gpbc_sha256_batch_dev": "i:ppzzipp",
     "gpbc_hash_g1_gt_gt_to_fr": "i:pppzp", "gpbc_hash_g1_gt_gt_to_fr_dev": "i:pppzpp",
 }
+# ... and for include/gpbc_bn254_share.h, polynomial evaluation and the shares of a threshold tree in Fr (tests/test_fr_share.py holds
+# this table against that header).  The five tables are disjoint.
+SHARE_SIGNATURES = {
+    "gpbc_share_version": "i:", "gpbc_fr_poly_eval": "i:pzzpzzzp", "gpbc_fr_poly_eval_dev": "i:pzzpzzzpp",
+    "gpbc_share_tree_create": "i:pzp", "gpbc_share_tree_destroy": "i:p", "gpbc_share_tree_leaves": "z:p",
+    "gpbc_share_tree_coeffs": "z:p", "gpbc_fr_share_tree": "i:pppzp", "gpbc_fr_share_tree_dev": "i:pppzpp",
+}
 # every pointer is a c_void_p: it takes ints, None, c_void_p, ctypes arrays, byref() and ndarray.ctypes.data_as() alike
 _CTYPES = {"p": ctypes.c_void_p, "z": ctypes.c_size_t, "i": ctypes.c_int, "l": ctypes.c_long, "s": ctypes.c_char_p}
 
@@ -101,7 +108,7 @@ def load():
         except ImportError:
             pass
         lib = ctypes.CDLL(LIB_PATH)
-        for name, sig in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(SUBSET_SIGNATURES.items()) + list(HASH_SIGNATURES.items()):
+        for name, sig in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(SUBSET_SIGNATURES.items()) + list(HASH_SIGNATURES.items()) + list(SHARE_SIGNATURES.items()):
             ret, params = sig.split(":")
             fn = getattr(lib, name)
             fn.restype = _CTYPES[ret]

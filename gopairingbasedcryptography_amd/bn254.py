@@ -605,6 +605,132 @@ def fr_lagrange_basis(set, B=None, nodes=None, m=None, x=None, out=None):
     return out
 
 
+def fr_poly_eval(coeffs, points, d=None, m=None, out=None):
+    """out[j][t] = sum_i coeffs[j][i] * points[j][t]^i modulo r for k rows: utils.ComputePolynomialValue, one polynomial and one point
+    list per row (include/gpbc_bn254_share.h).  coeffs: [rows][d] Python ints, lowest degree first, or rows x d scalar rows (uint8 array /
+    bytes / CUDA tensor) with d; points likewise with m.  Each has one row (shared by all) or k; k is the larger count.
+    Returns [k, m, 32] canonical scalars of the kind that went in (numpy, or a CUDA tensor enqueued on the current stream)."""
+    c, nc, d = _fr_rows_arg(coeffs, d, "coeffs")
+    p, npts, m = _fr_rows_arg(points, m, "points")
+    dev = bufs.device_of(c, p, out)
+    k = max(nc, npts)
+    if k and (nc not in (1, k) or npts not in (1, k)):
+        raise ValueError("coeffs and points need one row or one row per output row (got %d, %d)" % (nc, npts))
+    if k > (1 << 29) - 1:
+        raise ValueError("too many rows for one call (%d)" % k)
+    out = bufs.output(out, (k, m, SCALAR_BYTES), dev)
+    if k:
+        if _overlaps(out, c, p):
+            raise ValueError("out overlaps an input")
+        _call("fr_poly_eval", dev, c, nc, d, p, npts, m, k, out)
+    return out
+
+
+def _overlaps(out, *inputs):
+    lo = bufs.address(out)
+    hi = lo + bufs.nbytes(out)
+    return any(x is not None and bufs.address(x) < hi and lo < bufs.address(x) + bufs.nbytes(x) for x in inputs)
+
+
+SHARE_MAX = 1024
+SHARE_ROOT = 0xFFFFFFFF
+
+
+class ShareTree:
+    """A threshold access tree uploaded once (include/gpbc_bn254_share.h): afterwards the shares of k secrets — AccessTreeNode.ShareSecret,
+    the polynomial of every gate evaluated at its children's positions down to the leaves — are one launch.
+
+        t = ShareTree(nodes)                     # nodes: [(parent, threshold)] in depth-first preorder; parent = SHARE_ROOT for node 0,
+                                                 # threshold 0 = a leaf (bsw07.share_plan makes the list from a Leaf / Threshold tree)
+        t.leaves, t.coeffs                       # L shares and C = sum of (threshold - 1) coefficients per item
+        out = t.share(secrets, coeffs)           # secrets: k scalars, coeffs: [k, C] scalars (None when C == 0) -> [k, L, 32], leaf order
+
+    Scalars are Python ints, uint8 arrays or CUDA tensors; CUDA tensors give a CUDA tensor enqueued on the current stream and not
+    synchronised.  A malformed tree and every argument error are ValueError before the device is touched."""
+
+    def __init__(self, nodes):
+        self._h = ctypes.c_void_p()
+        try:
+            arr = np.ascontiguousarray(np.asarray(nodes, dtype=np.int64).reshape(-1, 2))
+        except (ValueError, TypeError):
+            raise ValueError("nodes must be a list of (parent, threshold) pairs") from None
+        if arr.size and (arr.min() < 0 or arr.max() > SHARE_ROOT):
+            raise ValueError("parents and thresholds are unsigned 32-bit values")
+        why = share_tree_check(arr.tolist())
+        if why:
+            raise ValueError("malformed tree: " + why)
+        self.nodes = arr.astype(np.uint32)
+        self.leaves = int((self.nodes[:, 1] == 0).sum())
+        self.coeffs = int((self.nodes[:, 1].astype(np.int64) - 1)[self.nodes[:, 1] != 0].sum())
+        self._lib = _lib.load()
+        _ensure_init()
+        _lib.check(self._lib.gpbc_share_tree_create(self.nodes.ctypes.data, len(self.nodes), ctypes.byref(self._h)))
+        assert (self.leaves, self.coeffs) == (self._lib.gpbc_share_tree_leaves(self._h), self._lib.gpbc_share_tree_coeffs(self._h))
+
+    def share(self, secrets, coeffs=None, out=None):
+        s, k = bufs.rows(_fr_in(secrets), SCALAR_BYTES, "secrets")
+        if coeffs is not None and not bufs.is_torch(coeffs) and not isinstance(coeffs, (np.ndarray, bytes, bytearray)):
+            coeffs = [v for row in coeffs for v in (row if isinstance(row, (list, tuple)) else [row])]
+        c = None
+        if self.coeffs:
+            if coeffs is None:
+                raise ValueError("the tree needs %d coefficients per item" % self.coeffs)
+            c, nc = bufs.rows(_fr_in(coeffs), SCALAR_BYTES, "coeffs")
+            if nc != k * self.coeffs:
+                raise ValueError("coeffs holds %d scalars, expected %d x %d" % (nc, k, self.coeffs))
+        elif coeffs is not None and bufs.nbytes(_fr_in(coeffs)):
+            raise ValueError("the tree takes no coefficients")
+        dev = bufs.device_of(s, c, out)
+        if k > (1 << 29) - 1:
+            raise ValueError("too many items for one call (%d)" % k)
+        out = bufs.output(out, (k, self.leaves, SCALAR_BYTES), dev)
+        if not self._h:
+            raise ValueError("the tree is closed")
+        if k:
+            if _overlaps(out, s, c):
+                raise ValueError("out overlaps an input")
+            _call("fr_share_tree", dev, self._h, s, c, k, out)
+        return out
+
+    def close(self):
+        if self._h:
+            self._lib.gpbc_share_tree_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def share_tree_check(nodes):
+    """None, or why gpbc_share_tree_create would refuse the node list [(parent, threshold)] (the rules of include/gpbc_bn254_share.h)"""
+    if not nodes:
+        return "a tree needs at least one node"
+    if nodes[0][0] != SHARE_ROOT:
+        return "node 0 must carry the root marker"
+    children, leaves, gates = [0] * len(nodes), 0, 0
+    for i, (parent, threshold) in enumerate(nodes):
+        if i:
+            if parent == SHARE_ROOT:
+                return "a second root"
+            if parent >= i:
+                return "a parent must come before its children"
+            if not nodes[parent][1]:
+                return "the parent of a node is a leaf"
+            children[parent] += 1
+        leaves, gates = leaves + (not threshold), gates + bool(threshold)
+    if leaves > SHARE_MAX or gates > SHARE_MAX:
+        return "more than %d leaves or %d gates" % (SHARE_MAX, SHARE_MAX)
+    for (_, threshold), n in zip(nodes, children):
+        if n > SHARE_MAX:
+            return "more than %d children of one gate" % SHARE_MAX
+        if threshold > n:
+            return "a gate's threshold exceeds its number of children"
+    return None
+
+
 FR_LSSS_MAX = 64
 
 

@@ -1,4 +1,4 @@
-"""Host-side planner for batched BSW07 CP-ABE decryption (BASELINE config 4).
+"""Host-side planner for batched BSW07 CP-ABE decryption (BASELINE config 4) and, below it, batched Encrypt.
 
 The reference decrypts one ciphertext at a time by walking the threshold access tree
 (access/tree/access_tree_node.go:96-164, cpabe/bsw07/bsw07_cpabe.go:172-195): per satisfied leaf two full pairings and a
@@ -136,3 +136,78 @@ def decrypt_batch_arrays(engine, folded, d_key, c_tilde, c, cy, cy_prime):
     P = bufs.cat([bufs.view(cy, n, l, 64), bufs.view(cy_prime, n, l, 64), bufs.view(c, n, 1, 64)], 1)
     X = engine.multi_pair_fixed_q(bufs.flat(P), bufs.flat(bufs.put(q_list, c)))
     return engine.gt_mul(bufs.flat(c_tilde).reshape(n, 384), X)
+
+
+# ------------------------------------------------------------------------------------------------ Encrypt
+# cpabe/bsw07/bsw07_cpabe.go:133-170: C~ = M e(g1, g2)^(alpha s), C = h^s, and per leaf y of the policy Cy = g1^(q_y(0)), Cy' = H1(att(y))^(q_y(0)),
+# the q_y(0) from AccessTreeNode.ShareSecret(s).  The sharing is engine.ShareTree (one launch for the whole batch); the randomness — s and
+# the polynomial coefficients of every gate — is passed in, as in waters05.encrypt_batch and gentry06.encrypt_batch.
+ROOT_MARK = 0xFFFFFFFF
+
+
+def share_plan(tree):
+    """(nodes, attributes) of a Leaf / Threshold tree: the node list [(parent, threshold)] in depth-first preorder that engine.ShareTree
+    takes (threshold 0 = a leaf, parent ROOT_MARK for the root) and the leaves' attributes in leaf-id order.  Assigns the leaf ids as
+    the reference's GenerateLeafID does (assign_leaf_ids), so column y - 1 of the shares belongs to leaf id y."""
+    assign_leaf_ids(tree)
+    nodes, attributes = [], []
+
+    def walk(node, parent):
+        me = len(nodes)
+        if isinstance(node, Leaf):
+            nodes.append((parent, 0))
+            attributes.append(node.attribute)
+            return
+        nodes.append((parent, node.k))
+        for c in node.children:
+            walk(c, me)
+    walk(tree, ROOT_MARK)
+    return nodes, attributes
+
+
+def encrypt_batch(engine, tree_or_plan, h, e_alpha, h1, messages, s, coeffs):
+    """n ciphertexts under one policy.  tree_or_plan: a Leaf / Threshold tree or share_plan(tree); h = g1^beta (64 B) and
+    e_alpha = e(g1, g2)^alpha (384 B) of the public key; h1: {attribute: 64-byte G1 point} (H1 of every attribute of the policy);
+    messages [n, 384]; s: n scalars; coeffs: [n, C] scalars, a gate's threshold - 1 coefficients in the order ShareSecret draws them
+    (None or empty when C == 0).  Returns exactly the operands of decrypt_batch_arrays with the columns in leaf-id order:
+    (c_tilde [n, 384], c [n, 64], cy [n, L, 64], cy_prime [n, L, 64]).  numpy in gives numpy out; CUDA tensors (messages, s, coeffs) give
+    tensors, and only the public key, the L points of h1 and the tree go to the device."""
+    nodes, attributes = share_plan(tree_or_plan) if isinstance(tree_or_plan, (Leaf, Threshold)) else tree_or_plan
+    L = len(attributes)
+    n = bufs.nbytes(messages) // 384
+    if bufs.nbytes(messages) != n * 384:
+        raise ValueError("messages must hold whole GT elements")
+    scalars = lambda v, what: v if bufs.is_torch(v) or isinstance(v, np.ndarray) else bufs.put(_scalar_bytes(v, what), messages)
+    s = scalars(s, "s")
+    coeffs = None if coeffs is None else scalars(coeffs, "coeffs")
+    bufs.device_of(messages, s, coeffs)                                              # all of one kind, on one device
+    if bufs.nbytes(s) != n * 32:
+        raise ValueError("s must hold n = %d scalars" % n)
+
+    def public(x, width, what):
+        if bufs.is_torch(x):
+            x = x.cpu().numpy()
+        x = np.array(x, dtype=np.uint8, copy=True).reshape(-1)
+        if x.size != width:
+            raise ValueError("%s must be %d bytes" % (what, width))
+        return bufs.put(x, messages)
+    tree = engine.ShareTree(nodes)
+    try:
+        if tree.leaves != L:
+            raise ValueError("the plan names %d attributes for %d leaves" % (L, tree.leaves))
+        shares = bufs.flat(tree.share(bufs.flat(s), None if coeffs is None or not bufs.nbytes(coeffs) else bufs.flat(coeffs)))          # [n, L, 32]
+    finally:
+        tree.close()
+    base = bufs.flat(bufs.expand(bufs.view(public(e_alpha, 384, "e_alpha"), 1, 384), n, 384))
+    c_tilde = engine.gt_mul(engine.gt_exp(base, bufs.flat(s)), bufs.flat(messages))
+    c = engine.g1_scalar_mul(public(h, 64, "h"), bufs.flat(s))
+    cy = engine.g1_scalar_mul_base(shares)
+    hy = bufs.put(np.stack([np.asarray(h1[a], dtype=np.uint8).reshape(64) for a in attributes]), messages)
+    cy_prime = engine.g1_scalar_mul(bufs.flat(bufs.expand(bufs.view(hy, 1, L, 64), n, L, 64)), shares)
+    return bufs.view(c_tilde, n, 384), bufs.view(c, n, 64), bufs.view(cy, n, L, 64), bufs.view(cy_prime, n, L, 64)
+
+
+def _scalar_bytes(values, what):
+    """Python ints (a list, or a list of rows) as scalar rows modulo r"""
+    flat = [v for row in values for v in (row if isinstance(row, (list, tuple)) else [row])]
+    return np.frombuffer(b"".join((int(v) % R_ORDER).to_bytes(32, "little") for v in flat), dtype=np.uint8).reshape(-1, 32).copy()

@@ -1,9 +1,12 @@
 // libgpbc_bn254.so, one of the units listed in _build.py: the scalar field Fr on the device (csrc/fr29.hip.hpp) — elementwise add / sub / mul / neg /
 // inverse and the fr.Element conversions on the ABI's scalar format, the two polynomial kernels of the AFP25 / GWWW25 opening
 // proofs, the Lagrange basis over a node set per row (SW05 fuzzy IBE) and the LSSS reconstruction weights of a policy per
-// ciphertext (Waters11 CP-ABE) — with their C-ABI entries (include/gpbc_bn254.h, "scalar field").  gfx950 only.
+// ciphertext (Waters11 CP-ABE) — with their C-ABI entries (include/gpbc_bn254.h, "scalar field"), and secret sharing (csrc/share29.hip.hpp):
+// polynomial evaluation and the shares of a threshold tree (include/gpbc_bn254_share.h).  gfx950 only.
 #include "gpbc_common.hpp"
 #include "fr29.hip.hpp"
+#include "share29.hip.hpp"
+#include "../../include/gpbc_bn254_share.h"
 
 // ------------------------------------------------------------------------------------------------ elementwise
 // one element per lane (no __restrict__: out may be a, or b)
@@ -192,6 +195,51 @@ __global__ void __launch_bounds__(BLOCK) k_fr_lsss_weights(GPBC_LSSS_ARGS) { fr_
 __global__ void __launch_bounds__(BLOCK) k_fr_lsss_weights_mid(GPBC_LSSS_ARGS) { fr_lsss_kernel<FR_LSSS_WORDS_1>(matrix, mat_step, held, k, gm, w_out, ok_out); }
 __global__ void __launch_bounds__(BLOCK) k_fr_lsss_weights_large(GPBC_LSSS_ARGS) { fr_lsss_kernel<FR_LSSS_WORDS_2>(matrix, mat_step, held, k, gm, w_out, ok_out); }
 
+// ------------------------------------------------------------------------------------------------ secret sharing
+// out[j][t] = coeffs[j](points[j][t]) and the shares of k secrets over one threshold tree: share29.hip.hpp has the arithmetic, the
+// geometry, the staging and the lane mapping (the host harness runs them workgroup by workgroup); here are the LDS blocks and the barriers.
+// One wave per workgroup, two LDS instances each.
+static_assert(FR_SHARE_WAVE == BLOCK, "one wave per workgroup");
+template <int CAP> __device__ __forceinline__ void fr_poly_eval_kernel(const uint8_t *__restrict__ coeffs, size_t coeff_step, const uint8_t *__restrict__ points, size_t point_step, size_t k,
+                                                                        PolyEvalGeom gm, uint8_t *__restrict__ out) {
+    __shared__ int32_t cs[CAP * NL + BLOCK];
+    fr_poly_eval_stage(gm, blockIdx.x, threadIdx.x, k, coeffs, coeff_step, [&](uint32_t off, const Fr &v) { lds_put(cs + off, v); });
+    __syncthreads();
+    const PolyEvalLane l = fr_poly_eval_map(gm, blockIdx.x, threadIdx.x, k);
+    if (!l.active) return;
+    const int32_t *mine = cs + (coeff_step ? l.lr * fr_poly_eval_pitch(gm) : 0u);
+    fr_poly_eval_lane([&](uint32_t i) { return lds_get(mine + i * NL); }, gm.d, points + l.row * point_step + 32 * (size_t)l.t, out + 32 * (l.row * gm.m + l.t));
+}
+GPBC_KERNEL_G1 k_fr_poly_eval(const uint8_t *__restrict__ coeffs, size_t coeff_step, const uint8_t *__restrict__ points, size_t point_step, size_t k, PolyEvalGeom gm,
+                              uint8_t *__restrict__ out) {
+    fr_poly_eval_kernel<FR_EVAL_SMALL>(coeffs, coeff_step, points, point_step, k, gm, out);
+}
+__global__ void __launch_bounds__(BLOCK) k_fr_poly_eval_long(const uint8_t *__restrict__ coeffs, size_t coeff_step, const uint8_t *__restrict__ points, size_t point_step, size_t k, PolyEvalGeom gm,
+                                   uint8_t *__restrict__ out) {
+    fr_poly_eval_kernel<FR_EVAL_LARGE>(coeffs, coeff_step, points, point_step, k, gm, out);
+}
+template <int CAP> __device__ __forceinline__ void fr_share_tree_kernel(const ShareUnit *__restrict__ units, const uint32_t *__restrict__ level_off, const uint8_t *__restrict__ secrets,
+                                                                         const uint8_t *__restrict__ coeffs, size_t k, ShareGeom gm, uint8_t *__restrict__ out) {
+    __shared__ int32_t ss[CAP * NL + BLOCK];
+    if (!gm.G) { fr_share_single(blockIdx.x, threadIdx.x, k, secrets, out); return; }
+    const auto get = [&](uint32_t off) { return lds_get(ss + off); };
+    const auto put = [&](uint32_t off, const Fr &v) { lds_put(ss + off, v); };
+    fr_share_stage(gm, blockIdx.x, threadIdx.x, k, secrets, coeffs, put);
+    __syncthreads();
+    for (uint32_t lv = 1; lv <= gm.depth; lv++) {
+        fr_share_level(gm, units, level_off, lv, blockIdx.x, threadIdx.x, k, get, put, out);
+        __syncthreads();
+    }
+}
+GPBC_KERNEL_G1 k_fr_share_tree(const ShareUnit *__restrict__ units, const uint32_t *__restrict__ level_off, const uint8_t *__restrict__ secrets, const uint8_t *__restrict__ coeffs,
+                               size_t k, ShareGeom gm, uint8_t *__restrict__ out) {
+    fr_share_tree_kernel<FR_TREE_SMALL>(units, level_off, secrets, coeffs, k, gm, out);
+}
+__global__ void __launch_bounds__(BLOCK) k_fr_share_tree_large(const ShareUnit *__restrict__ units, const uint32_t *__restrict__ level_off, const uint8_t *__restrict__ secrets, const uint8_t *__restrict__ coeffs,
+                                     size_t k, ShareGeom gm, uint8_t *__restrict__ out) {
+    fr_share_tree_kernel<FR_TREE_LARGE>(units, level_off, secrets, coeffs, k, gm, out);
+}
+
 extern "C" {
 
 // ------------------------------------------------------------------------------------------------ elementwise entries
@@ -376,6 +424,115 @@ int gpbc_fr_lsss_weights(const void *matrix, size_t n_matrices, size_t rows, siz
     HostCall c = HostCall().input(matrix, rows * cols * GPBC_SCALAR_BYTES, one).input(held, rows);
     return host_call_sharded(k, shard_min ? shard_min : 1, c.output(w_out, rows * GPBC_SCALAR_BYTES).output(ok_out, 1), HostRoute{},
                              [=](const DevCols &d, size_t m, hipStream_t st) { return gpbc_fr_lsss_weights_dev(d.in[0], one ? 1 : m, rows, cols, d.in[1], m, d.out[0], d.out[1], st); });
+}
+
+// ------------------------------------------------------------------------------------------------ secret sharing entries (include/gpbc_bn254_share.h)
+int gpbc_share_version(void) { return 1; }
+static int poly_eval_args(const void *coeffs, size_t n_coeff_rows, size_t d, const void *points, size_t n_point_rows, size_t m, size_t k, const void *out) {
+    if (d < 1 || d > (size_t)FR_POLY_MAX_B || m < 1 || m > (size_t)FR_POLY_MAX_B)
+        return fail(GPBC_ERR_INVALID_ARG, "d and m must be in 1 .. %d (got d = %zu, m = %zu)", FR_POLY_MAX_B, d, m);
+    if (k > (size_t)0x7fffffff / 4) return fail(GPBC_ERR_INVALID_ARG, "too many rows for one call (%zu)", k);
+    if (!k) return GPBC_OK;
+    if (n_coeff_rows != 1 && n_coeff_rows != k) return fail(GPBC_ERR_INVALID_ARG, "n_coeff_rows must be 1 or k (got %zu, k = %zu)", n_coeff_rows, k);
+    if (n_point_rows != 1 && n_point_rows != k) return fail(GPBC_ERR_INVALID_ARG, "n_point_rows must be 1 or k (got %zu, k = %zu)", n_point_rows, k);
+    if (!coeffs || !points || !out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    const size_t out_bytes = k * m * GPBC_SCALAR_BYTES;
+    if (overlap(out, out_bytes, coeffs, n_coeff_rows * d * GPBC_SCALAR_BYTES) || overlap(out, out_bytes, points, n_point_rows * m * GPBC_SCALAR_BYTES))
+        return fail(GPBC_ERR_INVALID_ARG, "out overlaps an input");
+    return GPBC_OK;
+}
+int gpbc_fr_poly_eval_dev(const void *d_coeffs, size_t n_coeff_rows, size_t d, const void *d_points, size_t n_point_rows, size_t m, size_t k, void *d_out, void *stream) {
+    TRY(poly_eval_args(d_coeffs, n_coeff_rows, d, d_points, n_point_rows, m, k, d_out));
+    if (!k) return GPBC_OK;
+    TRY(bind_device());
+    const bool shared = n_coeff_rows == 1 && k > 1;
+    const PolyEvalGeom g = fr_poly_eval_geometry(d, m, shared);
+    const unsigned grid = (unsigned)fr_poly_eval_grid(g, k);
+    const size_t coeff_step = shared ? 0 : d * GPBC_SCALAR_BYTES, point_step = n_point_rows == k && k > 1 ? m * GPBC_SCALAR_BYTES : 0;
+    if (g.large) return GPBC_LAUNCH(k_fr_poly_eval_long, grid, BLOCK, (hipStream_t)stream, (const uint8_t *)d_coeffs, coeff_step, (const uint8_t *)d_points, point_step, k, g, (uint8_t *)d_out);
+    return GPBC_LAUNCH(k_fr_poly_eval, grid, BLOCK, (hipStream_t)stream, (const uint8_t *)d_coeffs, coeff_step, (const uint8_t *)d_points, point_step, k, g, (uint8_t *)d_out);
+}
+// Host-pointer form: the unit is a row; a shard needs about 2^16 steps to pay for its thread and transfers.  A coefficient row or a point
+// row given once travels whole to every shard.
+int gpbc_fr_poly_eval(const void *coeffs, size_t n_coeff_rows, size_t d, const void *points, size_t n_point_rows, size_t m, size_t k, void *out) {
+    TRY(poly_eval_args(coeffs, n_coeff_rows, d, points, n_point_rows, m, k, out));
+    if (!k) return GPBC_OK;
+    const bool one_c = n_coeff_rows == 1, one_p = n_point_rows == 1;
+    const size_t shard_min = ((size_t)1 << 16) / (d * m);
+    HostCall c = HostCall().input(coeffs, d * GPBC_SCALAR_BYTES, one_c).input(points, m * GPBC_SCALAR_BYTES, one_p);
+    return host_call_sharded(k, shard_min ? shard_min : 1, c.output(out, m * GPBC_SCALAR_BYTES), HostRoute{},
+                             [=](const DevCols &dc, size_t rows, hipStream_t st) { return gpbc_fr_poly_eval_dev(dc.in[0], one_c ? 1 : rows, d, dc.in[1], one_p ? 1 : rows, m, rows, dc.out[0], st); });
+}
+
+struct gpbc_share_tree {
+    int device;
+    ShareGeom geom;
+    ShareUnit *units;
+    uint32_t *level_off;
+};
+int gpbc_share_tree_create(const gpbc_share_node *nodes, size_t n_nodes, gpbc_share_tree **out) {
+    static_assert(sizeof(gpbc_share_node) == sizeof(ShareNode), "the public node is the plan's node");
+    if (!out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    *out = nullptr;
+    SharePlan plan;
+    const char *why = fr_share_plan(reinterpret_cast<const ShareNode *>(nodes), n_nodes, plan);
+    if (why) return fail(GPBC_ERR_INVALID_ARG, "malformed tree: %s", why);
+    TRY(bind_device());
+    gpbc_share_tree *h = new gpbc_share_tree{current_device(), fr_share_geometry(plan), nullptr, nullptr};
+    const size_t ub = (plan.units.size() ? plan.units.size() : 1) * sizeof(ShareUnit), lb = plan.level_off.size() * sizeof(uint32_t);
+    hipError_t e = hipMalloc((void **)&h->units, ub);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->level_off, lb);
+    if (e == hipSuccess && plan.units.size()) e = hipMemcpy(h->units, plan.units.data(), plan.units.size() * sizeof(ShareUnit), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(h->level_off, plan.level_off.data(), lb, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (h->units) (void)hipFree(h->units);
+        if (h->level_off) (void)hipFree(h->level_off);
+        delete h;
+        return fail(GPBC_ERR_HIP, "uploading a share tree failed: %s", hipGetErrorString(e));
+    }
+    *out = h;
+    return GPBC_OK;
+}
+int gpbc_share_tree_destroy(gpbc_share_tree *t) {
+    if (!t) return GPBC_OK;
+    (void)hipSetDevice(t->device);
+    (void)hipDeviceSynchronize();
+    (void)hipFree(t->units);
+    (void)hipFree(t->level_off);
+    delete t;
+    return GPBC_OK;
+}
+size_t gpbc_share_tree_leaves(const gpbc_share_tree *t) { return t ? t->geom.L : 0; }
+size_t gpbc_share_tree_coeffs(const gpbc_share_tree *t) { return t ? t->geom.C : 0; }
+static int share_tree_args(const gpbc_share_tree *t, const void *secrets, const void *coeffs, size_t k, const void *out) {
+    if (!t) return fail(GPBC_ERR_INVALID_ARG, "null tree handle");
+    if (k > (size_t)0x7fffffff / 4) return fail(GPBC_ERR_INVALID_ARG, "too many items for one call (%zu)", k);
+    if (!k) return GPBC_OK;
+    if (!secrets || !out || (t->geom.C && !coeffs)) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    const size_t out_bytes = k * t->geom.L * GPBC_SCALAR_BYTES;
+    if (overlap(out, out_bytes, secrets, k * GPBC_SCALAR_BYTES) || (t->geom.C && overlap(out, out_bytes, coeffs, k * t->geom.C * GPBC_SCALAR_BYTES)))
+        return fail(GPBC_ERR_INVALID_ARG, "out overlaps an input");
+    return GPBC_OK;
+}
+int gpbc_fr_share_tree_dev(const gpbc_share_tree *t, const void *d_secrets, const void *d_coeffs, size_t k, void *d_out, void *stream) {
+    TRY(share_tree_args(t, d_secrets, d_coeffs, k, d_out));
+    if (!k) return GPBC_OK;
+    TRY(bind_device());
+    if (current_device() != t->device) return fail(GPBC_ERR_INVALID_ARG, "tree was created on device %d", t->device);
+    const unsigned grid = (unsigned)fr_share_grid(t->geom, k);
+    if (t->geom.large)
+        return GPBC_LAUNCH(k_fr_share_tree_large, grid, BLOCK, (hipStream_t)stream, t->units, t->level_off, (const uint8_t *)d_secrets, (const uint8_t *)d_coeffs, k, t->geom, (uint8_t *)d_out);
+    return GPBC_LAUNCH(k_fr_share_tree, grid, BLOCK, (hipStream_t)stream, t->units, t->level_off, (const uint8_t *)d_secrets, (const uint8_t *)d_coeffs, k, t->geom, (uint8_t *)d_out);
+}
+// Host pointers: the shared staging path on the tree's device only (the handle lives there), not combined with other threads' calls.
+int gpbc_fr_share_tree(const gpbc_share_tree *t, const void *secrets, const void *coeffs, size_t k, void *out) {
+    TRY(share_tree_args(t, secrets, coeffs, k, out));
+    if (!k) return GPBC_OK;
+    HostCall c = HostCall().input(secrets, GPBC_SCALAR_BYTES);
+    if (t->geom.C) c.input(coeffs, t->geom.C * GPBC_SCALAR_BYTES);
+    const bool has = t->geom.C != 0;
+    return host_call(k, c.output(out, t->geom.L * GPBC_SCALAR_BYTES), HostRoute{CALL_KINDS, nullptr, 0, LANE_CALL_MAX_UNITS},
+                     [=](const DevCols &dc, size_t m, hipStream_t st) { return gpbc_fr_share_tree_dev(t, dc.in[0], has ? dc.in[1] : nullptr, m, dc.out[0], st); });
 }
 
 }  // extern "C"

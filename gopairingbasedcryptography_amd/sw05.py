@@ -1,6 +1,6 @@
 """Host-side planner for batched Sahai-Waters 2005 fuzzy identity-based decryption (fibe/sw05_fibe_common.go:284-333 and
-fibe/sw05_fibe_large_universe.go:244-291): one user key against a batch of ciphertexts, and computeT (sw05_fibe_large_universe.go:
-302-325) for many attributes at once.
+fibe/sw05_fibe_large_universe.go:244-291): one user key against a batch of ciphertexts, computeT (sw05_fibe_large_universe.go:
+302-325) for many attributes at once, and KeyGenerate of both universes for many users at once (keygen_batch, keygen_batch_large below).
 
 What is computed.  Per ciphertext, S = FindCommonAttributes(S_user, S_msg, d) (utils/find_common_attributes.go: the first d distinct
 attributes of the CIPHERTEXT's list that the key holds) and Delta_i = ComputeLagrangeBasis(i, S, 0) for i in S, then
@@ -184,3 +184,61 @@ def compute_t(engine, table, n, xs, nodes=None):
             acc = engine.fr_mul(bufs.flat(acc), bufs.flat(base))
     scalars = bufs.cat([acc.reshape(k, 1, 32), delta], 1)
     return table.msm(bufs.flat(scalars)).reshape(k, 128)
+
+
+# ------------------------------------------------------------------------------------------------ KeyGenerate
+# fibe/sw05_fibe_common.go:205-210 and fibe/sw05_fibe_large_universe.go:153-167: a random polynomial q of degree d - 1 with q(0) = y per user
+# (utils.GenerateRandomPolynomial) and utils.ComputePolynomialValue(q, i) per attribute i — engine.fr_poly_eval, k users x m attributes in
+# one launch.  The randomness is passed in.  Ragged attribute counts are the caller's to group: rows are rectangular.
+def _matrix(x, like, what):
+    """(buffer [rows, cols, 32], rows, cols) of a scalar matrix: nested Python ints [rows][cols], or a [rows, cols, 32] uint8 array / tensor"""
+    if not bufs.is_torch(x) and not isinstance(x, np.ndarray):
+        grid = [list(r) for r in x]
+        cols = len(grid[0]) if grid else 0
+        if any(len(r) != cols for r in grid):
+            raise ValueError("%s: every row needs %d scalars" % (what, cols))
+        x = _scalar_rows(v for r in grid for v in r).reshape(len(grid), cols, 32)
+        if like is not None:
+            x = bufs.put(x, like)
+    if len(x.shape) != 3 or x.shape[2] != 32:
+        raise ValueError("%s must be [rows, columns, 32] scalar rows" % what)
+    return x, int(x.shape[0]), int(x.shape[1])
+
+
+def _shares(engine, y, coeffs, attrs):
+    """q_j(attrs[j][i]) for the k polynomials y + coeffs[j][0] X + ...: ([k, m, 32], attrs [k, m, 32], k, m)"""
+    tensor = next((v for v in (attrs, coeffs) if bufs.is_torch(v)), None)
+    attrs, k, m = _matrix(attrs, tensor, "attrs")
+    coeffs, kc, dm1 = _matrix(coeffs if coeffs is not None else bufs.empty((k, 0, 32), attrs), attrs, "coeffs")
+    if kc != k:
+        raise ValueError("coeffs needs one row per user (got %d, k = %d)" % (kc, k))
+    bufs.device_of(attrs, coeffs)
+    y = bufs.put(_scalar_rows([y]) if isinstance(y, int) else np.array(y, dtype=np.uint8, copy=True).reshape(1, 32), attrs)
+    rows = bufs.cat([bufs.expand(bufs.view(y, 1, 1, 32), k, 1, 32), coeffs], 1)                     # [k, d, 32]: q_j, constant term first
+    q = engine.fr_poly_eval(bufs.flat(rows), bufs.flat(attrs), dm1 + 1, m)
+    return bufs.view(q, k, m, 32), attrs, k, m
+
+
+def keygen_batch(engine, y, coeffs, attrs, t):
+    """Small universe, k users of m attributes each.  y: the master secret (an int or 32 bytes); coeffs: [k, d - 1] scalars, the
+    coefficients of X^1 .. X^(d-1) of every user's polynomial (d == 1: no columns, or None); attrs: [k, m] attribute values;
+    t: [k, m] the master t_i of every attribute.  Scalars are nested Python ints or [k, columns, 32] uint8 arrays / CUDA tensors.
+    Returns D [k, m, 64] with D_i = g1^(q(i) / t_i): fr_poly_eval, fr_inverse, fr_mul, generator multiplications."""
+    q, attrs, k, m = _shares(engine, y, coeffs, attrs)
+    t, kt, mt = _matrix(t, attrs, "t")
+    if (kt, mt) != (k, m):
+        raise ValueError("t must be [%d, %d] like attrs" % (k, m))
+    e = engine.fr_mul(bufs.flat(q), bufs.flat(engine.fr_inverse(bufs.flat(t))))
+    return bufs.view(engine.g1_scalar_mul_base(bufs.flat(e)), k, m, 64)
+
+
+def keygen_batch_large(engine, table, n, y, coeffs, attrs, r):
+    """Large universe.  table, n: as for compute_t; y, coeffs, attrs as for keygen_batch; r: [k, m] scalars, the r_i of every attribute.
+    Returns (d [k, m, 64], D [k, m, 128]) with d_i = g1^(r_i) and D_i = g2^(q(i)) + [r_i] T_i, T_i = compute_t of the attribute."""
+    q, attrs, k, m = _shares(engine, y, coeffs, attrs)
+    r, kr, mr = _matrix(r, attrs, "r")
+    if (kr, mr) != (k, m):
+        raise ValueError("r must be [%d, %d] like attrs" % (k, m))
+    T = compute_t(engine, table, n, bufs.view(bufs.flat(attrs), k * m, 32))
+    D = engine.g2_add(bufs.flat(engine.g2_scalar_mul_base(bufs.flat(q))), bufs.flat(engine.g2_scalar_mul(bufs.flat(T), bufs.flat(r))))
+    return bufs.view(engine.g1_scalar_mul_base(bufs.flat(r)), k, m, 64), bufs.view(D, k, m, 128)

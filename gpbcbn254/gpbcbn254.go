@@ -15,6 +15,7 @@ package gpbcbn254
 #cgo LDFLAGS: -L${SRCDIR}/../gopairingbasedcryptography_amd -lgpbc_bn254 -Wl,-rpath,${SRCDIR}/../gopairingbasedcryptography_amd
 #include "gpbc_bn254.h"
 #include "gpbc_bn254_hash.h"
+#include "gpbc_bn254_share.h"
 */
 import "C"
 
@@ -538,6 +539,92 @@ func FrLagrangeBasis(set []fr.Element, B int, nodes []fr.Element, m int, x []fr.
 	ko := make([][32]byte, k*m)
 	rc := C.gpbc_fr_lagrange_basis(unsafe.Pointer(unsafe.SliceData(ks)), C.size_t(ns), C.size_t(B), pn, C.size_t(nn), C.size_t(m), px, C.size_t(nx), C.size_t(k),
 		unsafe.Pointer(unsafe.SliceData(ko)))
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	out := make([]fr.Element, len(ko))
+	return out, frElements(ko, out)
+}
+
+// FrPolyEval: out[j*m + t] = sum_i coeffs[j*d + i] points[j*m + t]^i — utils.ComputePolynomialValue over the coefficients of
+// utils.GenerateRandomPolynomial for k rows (fibe/sw05_fibe_common.go:205-210, fibe/sw05_fibe_large_universe.go:153-167).  coeffs: one row
+// of d elements (lowest degree first) or k rows; points: one row of m or k rows.
+func FrPolyEval(coeffs []fr.Element, d int, points []fr.Element, m int) ([]fr.Element, error) {
+	defer pin()()
+	if d < 1 || len(coeffs) == 0 || len(coeffs)%d != 0 || m < 1 || len(points) == 0 || len(points)%m != 0 {
+		return nil, errSizes
+	}
+	nc, np := len(coeffs)/d, len(points)/m
+	k := nc
+	if np > k {
+		k = np
+	}
+	if (nc != 1 && nc != k) || (np != 1 && np != k) {
+		return nil, errSizes
+	}
+	kc, err := frPlain(coeffs)
+	if err != nil {
+		return nil, err
+	}
+	kp, err := frPlain(points)
+	if err != nil {
+		return nil, err
+	}
+	ko := make([][32]byte, k*m)
+	rc := C.gpbc_fr_poly_eval(unsafe.Pointer(unsafe.SliceData(kc)), C.size_t(nc), C.size_t(d), unsafe.Pointer(unsafe.SliceData(kp)), C.size_t(np), C.size_t(m), C.size_t(k),
+		unsafe.Pointer(unsafe.SliceData(ko)))
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	out := make([]fr.Element, len(ko))
+	return out, frElements(ko, out)
+}
+
+// ShareNode is one node of a threshold tree in depth-first preorder: Parent is the index of its parent (ShareRoot for node 0),
+// Threshold 0 marks a leaf, otherwise the gate's k of k-of-n.
+type ShareNode struct{ Parent, Threshold uint32 }
+
+const ShareRoot = 0xffffffff
+
+// ShareTree is a threshold tree uploaded once; Share is AccessTreeNode.ShareSecret (access/tree/access_tree_node.go:58-75) for k secrets
+// in one launch: coeffs holds Coeffs() elements per secret, gate by gate in the order ShareSecret draws them, and the result Leaves()
+// shares per secret in leaf order (leaf id y of GenerateLeafID is column y - 1).
+type ShareTree struct{ h *C.gpbc_share_tree }
+
+func NewShareTree(nodes []ShareNode) (*ShareTree, error) {
+	defer pin()()
+	t := &ShareTree{}
+	rc := C.gpbc_share_tree_create((*C.gpbc_share_node)(unsafe.Pointer(unsafe.SliceData(nodes))), C.size_t(len(nodes)), &t.h)
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	return t, nil
+}
+func (t *ShareTree) Leaves() int { return int(C.gpbc_share_tree_leaves(t.h)) }
+func (t *ShareTree) Coeffs() int { return int(C.gpbc_share_tree_coeffs(t.h)) }
+func (t *ShareTree) Close() {
+	C.gpbc_share_tree_destroy(t.h)
+	t.h = nil
+}
+func (t *ShareTree) Share(secrets, coeffs []fr.Element) ([]fr.Element, error) {
+	defer pin()()
+	if len(coeffs) != len(secrets)*t.Coeffs() {
+		return nil, errSizes
+	}
+	ks, err := frPlain(secrets)
+	if err != nil {
+		return nil, err
+	}
+	var pc unsafe.Pointer
+	if len(coeffs) > 0 {
+		kc, err := frPlain(coeffs)
+		if err != nil {
+			return nil, err
+		}
+		pc = unsafe.Pointer(unsafe.SliceData(kc))
+	}
+	ko := make([][32]byte, len(secrets)*t.Leaves())
+	rc := C.gpbc_fr_share_tree(t.h, unsafe.Pointer(unsafe.SliceData(ks)), pc, C.size_t(len(secrets)), unsafe.Pointer(unsafe.SliceData(ko)))
 	if err := status(rc); err != nil {
 		return nil, err
 	}

@@ -24,6 +24,7 @@
 #include <vector>
 #include "gpbc_bn254.h"
 #include "gpbc_bn254_hash.h"
+#include "gpbc_bn254_share.h"
 
 namespace bn254 {
 
@@ -317,6 +318,36 @@ inline std::vector<Scalar> FrLagrangeBasis(const std::vector<Scalar> &set, size_
     check(gpbc_fr_lagrange_basis(set.data(), ns, B, nodes.empty() ? nullptr : nodes.data(), nn, m, x.empty() ? nullptr : x.data(), nx, k, out.data()));
     return out;
 }
+// Polynomial evaluation for k rows (utils.ComputePolynomialValue): out[j*m + t] = sum_i coeffs[j*d + i] points[j*m + t]^i, coefficients
+// lowest degree first.  coeffs: one row of d or k rows; points: one row of m or k rows; k is the larger row count.
+inline std::vector<Scalar> FrPolyEval(const std::vector<Scalar> &coeffs, size_t d, const std::vector<Scalar> &points, size_t m) {
+    if (d < 1 || coeffs.empty() || coeffs.size() % d) throw std::invalid_argument("need d coefficients per row");
+    if (m < 1 || points.empty() || points.size() % m) throw std::invalid_argument("need m points per row");
+    const size_t nc = coeffs.size() / d, np = points.size() / m, k = std::max(nc, np);
+    if ((nc != 1 && nc != k) || (np != 1 && np != k)) throw std::invalid_argument("need one row or one row per output row");
+    std::vector<Scalar> out(k * m);
+    check(gpbc_fr_poly_eval(coeffs.data(), nc, d, points.data(), np, m, k, out.data()));
+    return out;
+}
+// A threshold tree uploaded once (AccessTreeNode.ShareSecret for k secrets per call): nodes in depth-first preorder, node i =
+// (parent, threshold), parent GPBC_SHARE_ROOT for node 0, threshold 0 = a leaf.  Share returns k x Leaves() scalars, item-major, leaf order.
+class ShareTree {
+public:
+    explicit ShareTree(const std::vector<gpbc_share_node> &nodes) { check(gpbc_share_tree_create(nodes.data(), nodes.size(), &h_)); }
+    ShareTree(const ShareTree &) = delete;
+    ShareTree &operator=(const ShareTree &) = delete;
+    ~ShareTree() { gpbc_share_tree_destroy(h_); }
+    size_t Leaves() const { return gpbc_share_tree_leaves(h_); }
+    size_t Coeffs() const { return gpbc_share_tree_coeffs(h_); }
+    std::vector<Scalar> Share(const std::vector<Scalar> &secrets, const std::vector<Scalar> &coeffs) const {
+        if (coeffs.size() != secrets.size() * Coeffs()) throw std::invalid_argument("need Coeffs() coefficients per secret");
+        std::vector<Scalar> out(secrets.size() * Leaves());
+        check(gpbc_fr_share_tree(h_, secrets.data(), coeffs.empty() ? nullptr : coeffs.data(), secrets.size(), out.data()));
+        return out;
+    }
+private:
+    gpbc_share_tree *h_ = nullptr;
+};
 // LSSS reconstruction weights for k systems (FindLinearCombinationWeight with a matrix per item): matrix holds one rows x cols matrix or
 // k of them, held k x rows bytes (non-zero: the key holds the row's attribute).  Returns k x rows weights (0 where a row is not used)
 // and fills ok with k bytes (0: the held rows do not span (1, 0, ..., 0); that row of weights is then all zero).

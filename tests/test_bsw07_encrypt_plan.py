@@ -1,0 +1,101 @@
+"""BSW07 Encrypt through the host planner (gopairingbasedcryptography_amd/bsw07.py: share_plan, encrypt_batch) on the oracle stand-in
+engine (tests/share_standin.py; the same flow runs on the GPU engine in test_bsw07_encrypt_gpu.py): fed the fixture's own s and
+polynomial scalars it returns the fixture's ciphertext bytes, and the existing decrypt_batch_arrays returns the fixture's messages."""
+import numpy as np
+import pytest
+
+import bn254_py as o
+from bsw07_fixture import Instance, example_tree, sc as fsc
+import share_cases as sc
+from share_standin import ShareEngine
+from sw05_fixture import TensorEngine, same_on_tensors, tensors
+from gopairingbasedcryptography_amd import bsw07
+
+L, T = bsw07.Leaf, bsw07.Threshold
+ROOT = bsw07.ROOT_MARK
+
+
+def test_share_plan():
+    nodes, attrs = bsw07.share_plan(example_tree())
+    assert nodes == [(ROOT, 2), (0, 0), (0, 2), (2, 0), (2, 0), (0, 0), (0, 1), (6, 0), (6, 0)] and attrs == [11, 22, 33, 44, 55, 11]
+    tree = T(1, T(2, L("a"), T(3, L("b"), L("c"), L("d")), L("e")), L("f"), T(1, L("a")))
+    nodes, attrs = bsw07.share_plan(tree)
+    assert nodes == [(ROOT, 1), (0, 2), (1, 0), (1, 3), (3, 0), (3, 0), (3, 0), (1, 0), (0, 0), (0, 1), (9, 0)]
+    assert attrs == ["a", "b", "c", "d", "e", "f", "a"] and [l.leaf_id for l in (tree.children[0].children[0], tree.children[1], tree.children[2].children[0])] == [1, 6, 7]
+    assert nodes == sc.preorder(tree)
+    assert bsw07.share_plan(L(5)) == ([(ROOT, 0)], [5])
+
+
+def fixture_inputs(inst, n):
+    """what Instance drew: s, the "poly%d" stream in its draw order, and the public key it encrypts under"""
+    C = sc.n_coeffs(inst.tree)
+    s = [fsc("s", t) for t in range(n)]
+    coeffs = [[fsc("poly%d" % t, i + 1) for i in range(C)] for t in range(n)]
+    h = inst.eng.g1_scalar_mul(inst.g1, [fsc("beta")])[0]
+    attrs = sorted({l.attribute for l in leaves(inst.tree)})
+    h1 = {a: inst.eng.g1_scalar_mul(inst.g1, [fsc("h", a)])[0] for a in attrs}
+    return s, coeffs, h, h1
+
+
+def leaves(node):
+    return [node] if isinstance(node, L) else [l for c in node.children for l in leaves(c)]
+
+
+def fixture_arrays(inst):
+    ids = [l.leaf_id for l in leaves(inst.tree)]
+    return (np.stack([np.asarray(ct["c_tilde"]) for ct in inst.cts]), np.stack([np.asarray(ct["c"]) for ct in inst.cts]),
+            np.stack([np.stack([np.asarray(ct["cy"][i]) for i in ids]) for ct in inst.cts]), np.stack([np.stack([np.asarray(ct["cy_prime"][i]) for i in ids]) for ct in inst.cts]))
+
+
+@pytest.fixture(scope="module")
+def setup(oracle):
+    eng = ShareEngine(oracle)
+    inst = Instance(eng, example_tree(), user_attrs=[11, 22, 33, 99], n_ct=3)
+    return eng, inst, fixture_inputs(inst, 3)
+
+
+def test_encrypt_batch_returns_the_fixture_ciphertexts(setup):
+    eng, inst, (s, coeffs, h, h1) = setup
+    msgs = np.stack(inst.msgs)
+    for policy in (inst.tree, bsw07.share_plan(inst.tree)):
+        got = bsw07.encrypt_batch(eng, policy, h, inst.e_alpha, h1, msgs, s, coeffs)
+        for g, w, shape in zip(got, fixture_arrays(inst), ((3, 384), (3, 64), (3, 6, 64), (3, 6, 64))):
+            assert g.shape == shape and g.tobytes() == w.tobytes()
+    # scalars as bytes are the same call
+    again = bsw07.encrypt_batch(eng, inst.tree, h, inst.e_alpha, h1, msgs, sc.rows(s).reshape(3, 32), sc.rows([v for q in coeffs for v in q]).reshape(3, -1, 32))
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(again, got))
+
+
+def test_decrypt_of_the_encrypted_batch_returns_the_messages(setup):
+    eng, inst, (s, coeffs, h, h1) = setup
+    eng.g2_neg = lambda q: np.frombuffer(o.g2_to_bytes(o.g2_neg(o.g2_from_bytes(np.asarray(q, dtype=np.uint8).tobytes()))), dtype=np.uint8)
+    eng.multi_pair_fixed_q = lambda P, Q: eng.multi_pair(P, np.tile(np.asarray(Q).reshape(-1), 3), np.arange(0, 3 * (np.asarray(Q).size // 128) + 1, np.asarray(Q).size // 128, dtype=np.uint64))
+    c_tilde, c, cy, cy_prime = bsw07.encrypt_batch(eng, inst.tree, h, inst.e_alpha, h1, np.stack(inst.msgs), s, coeffs)
+    plan = bsw07.decrypt_plan(inst.tree, inst.user_attrs)
+    folded = bsw07.fold_key(eng, plan, inst.dj, inst.dj_prime)
+    cols = [i - 1 for i in folded[0]]
+    out = bsw07.decrypt_batch_arrays(eng, folded, inst.D, c_tilde, c, cy[:, cols], cy_prime[:, cols])
+    assert np.asarray(out).tobytes() == np.stack(inst.msgs).tobytes()
+
+
+def test_encrypt_on_tensors_is_encrypt_on_arrays(setup):
+    eng, inst, (s, coeffs, h, h1) = setup
+    msgs = np.stack(inst.msgs)
+    want = bsw07.encrypt_batch(eng, inst.tree, h, inst.e_alpha, h1, msgs, s, coeffs)
+    tm, ts, tq = tensors(msgs, sc.rows(s).reshape(3, 32), sc.rows([v for q in coeffs for v in q]).reshape(3, -1, 32))
+    got = bsw07.encrypt_batch(TensorEngine(eng), inst.tree, h, inst.e_alpha, h1, tm, ts, tq)
+    assert all(same_on_tensors(g, w) for g, w in zip(got, want))
+
+
+def test_policies_without_coefficients_and_argument_errors(setup):
+    eng, inst, (s, coeffs, h, h1) = setup
+    msgs = np.stack(inst.msgs)
+    one = bsw07.encrypt_batch(eng, L(11), h, inst.e_alpha, h1, msgs, s, None)
+    assert one[2].shape == (3, 1, 64) and one[2].tobytes() == eng.g1_scalar_mul_base(s).tobytes()             # a single leaf: Cy = g1^s
+    anyof = bsw07.encrypt_batch(eng, T(1, L(11), L(22)), h, inst.e_alpha, h1, msgs, s, [])
+    assert (anyof[2][:, 0] == anyof[2][:, 1]).all() and anyof[2][:, 0].tobytes() == one[2].tobytes()
+    for bad in (lambda: bsw07.encrypt_batch(eng, inst.tree, h, inst.e_alpha, h1, msgs, s[:2], coeffs),
+                lambda: bsw07.encrypt_batch(eng, inst.tree, h[:32], inst.e_alpha, h1, msgs, s, coeffs),
+                lambda: bsw07.encrypt_batch(eng, inst.tree, h, inst.e_alpha, h1, msgs.reshape(-1)[:-1], s, coeffs)):
+        with pytest.raises(ValueError):
+            bad()

@@ -1,0 +1,103 @@
+"""SW05 KeyGenerate of both universes through the host planner (gopairingbasedcryptography_amd/sw05.py: keygen_batch,
+keygen_batch_large) on the oracle stand-in engine (tests/share_standin.py; the same flow runs on the GPU engine in
+test_sw05_keygen_gpu.py): fed the fixture's y, "q" coefficients, t / taus and r it reproduces sw05_fixture.Instance.key byte for byte."""
+import numpy as np
+import pytest
+
+import bn254_py as o
+from share_standin import ShareEngine
+from sw05_fixture import Instance, OracleTable, TensorEngine, same_on_tensors, sc, tensors
+from gopairingbasedcryptography_amd import sw05
+
+R = o.R
+
+
+def attributes(n):
+    """small integers and full-size field elements, as sw05_fixture.at_size_attributes mixes them"""
+    return [u + 1 if u % 3 else sc("attr", u) for u in range(n)]
+
+
+def instance(eng, d, n_univ, key_attrs=None, tag=None):
+    key = key_attrs or attributes(5)
+    return Instance(eng, d, key, [key[:3] + [77, 78]], n_univ=n_univ, tag=tag or "kg%d" % d)
+
+
+def fixture_inputs(inst, tag):
+    d = inst.d
+    return sc(tag + "y"), [[sc(tag + "q", j) for j in range(1, d)]], [list(inst.key_attrs)]
+
+
+@pytest.mark.parametrize("d", [1, 4, 16])
+def test_small_universe_key_is_the_fixture_key(oracle, d):
+    eng = ShareEngine(oracle)
+    inst = instance(eng, d, None)
+    y, coeffs, attrs = fixture_inputs(inst, "kg%d" % d)
+    t = [[inst.t[a % R] for a in attrs[0]]]
+    D = sw05.keygen_batch(eng, y, coeffs if d > 1 else None, attrs, t)
+    assert D.shape == (1, 5, 64) and D.tobytes() == np.asarray(inst.key[1]).tobytes()
+    if d == 1:
+        assert sw05.keygen_batch(eng, y, np.zeros((1, 0, 32), dtype=np.uint8), attrs, t).tobytes() == D.tobytes()
+
+
+@pytest.mark.parametrize("d", [1, 4, 16])
+def test_large_universe_key_is_the_fixture_key(oracle, d):
+    eng = ShareEngine(oracle)
+    inst = instance(eng, d, 3)
+    y, coeffs, attrs = fixture_inputs(inst, "kg%d" % d)
+    r = [[sc("kg%dr" % d, k) for k in range(5)]]
+    dk, Dk = sw05.keygen_batch_large(eng, OracleTable(oracle, inst.table_bases), 3, y, coeffs if d > 1 else None, attrs, r)
+    assert dk.shape == (1, 5, 64) and Dk.shape == (1, 5, 128)
+    assert dk.tobytes() == np.asarray(inst.key[1]).tobytes() and Dk.tobytes() == np.asarray(inst.key[2]).tobytes()
+
+
+def three_users(d):
+    attrs = [attributes(4), [9, sc("attr", 30), 2, R - 5], [sc("attr", 33), 4, 1 << 200, 6]]
+    coeffs = [[sc("u%d" % j, i) for i in range(d - 1)] for j in range(3)]
+    side = [[sc("side%d" % j, i) for i in range(4)] for j in range(3)]
+    return attrs, coeffs, side
+
+
+def test_three_users_are_three_single_user_calls(oracle):
+    eng = ShareEngine(oracle)
+    inst = instance(eng, 2, 3)
+    table = OracleTable(oracle, inst.table_bases)
+    attrs, coeffs, side = three_users(4)
+    y = sc("y3")
+    D = sw05.keygen_batch(eng, y, coeffs, attrs, side)
+    dl, Dl = sw05.keygen_batch_large(eng, table, 3, y, coeffs, attrs, side)
+    assert D.shape == (3, 4, 64) and dl.shape == (3, 4, 64) and Dl.shape == (3, 4, 128)
+    for j in range(3):
+        assert sw05.keygen_batch(eng, y, coeffs[j:j + 1], attrs[j:j + 1], side[j:j + 1]).tobytes() == D[j].tobytes()
+        a, b = sw05.keygen_batch_large(eng, table, 3, y, coeffs[j:j + 1], attrs[j:j + 1], side[j:j + 1])
+        assert a.tobytes() == dl[j].tobytes() and b.tobytes() == Dl[j].tobytes()
+    # D_i = g1^(q(i) / t_i) spelled out for one entry
+    q = (y + sum(c * pow(attrs[1][2], i + 1, R) for i, c in enumerate(coeffs[1]))) % R
+    assert D[1, 2].tobytes() == eng.g1_scalar_mul_base([q * pow(side[1][2], -1, R) % R]).tobytes()
+
+
+def test_keygen_on_tensors_is_keygen_on_arrays(oracle):
+    eng = ShareEngine(oracle)
+    inst = instance(eng, 2, 3)
+    attrs, coeffs, side = three_users(3)
+    y = sc("y3")
+    rows = lambda m: np.frombuffer(b"".join((v % R).to_bytes(32, "little") for r in m for v in r), dtype=np.uint8).reshape(len(m), -1, 32)
+    want = sw05.keygen_batch(eng, y, coeffs, attrs, side)
+    tc, ta, ts = tensors(rows(coeffs), rows(attrs), rows(side))
+    assert same_on_tensors(sw05.keygen_batch(TensorEngine(eng), y, tc, ta, ts), want)
+    assert sw05.keygen_batch(eng, y, rows(coeffs), rows(attrs), rows(side)).tobytes() == want.tobytes()
+    assert same_on_tensors(sw05.keygen_batch(TensorEngine(eng), y, None, ta, ts), sw05.keygen_batch(eng, y, None, attrs, side))       # d = 1 on tensors
+    wl = sw05.keygen_batch_large(eng, OracleTable(oracle, inst.table_bases), 3, y, coeffs, attrs, side)
+    table = OracleTable(oracle, inst.table_bases)
+    table.msm = lambda s, f=table.msm: __import__("torch").from_numpy(f(s.numpy()))
+    gl = sw05.keygen_batch_large(TensorEngine(eng), table, 3, y, tc, ta, ts)
+    assert same_on_tensors(gl[0], wl[0]) and same_on_tensors(gl[1], wl[1])
+
+
+def test_argument_errors(oracle):
+    eng = ShareEngine(oracle)
+    attrs, coeffs, side = three_users(3)
+    for bad in (lambda: sw05.keygen_batch(eng, 5, coeffs[:2], attrs, side), lambda: sw05.keygen_batch(eng, 5, coeffs, attrs, side[:2]),
+                lambda: sw05.keygen_batch(eng, 5, coeffs, [[1, 2], [3]], side), lambda: sw05.keygen_batch(eng, 5, coeffs, attrs, [r[:3] for r in side]),
+                lambda: sw05.keygen_batch(eng, 5, np.zeros((3, 64), dtype=np.uint8), attrs, side)):
+        with pytest.raises(ValueError):
+            bad()

@@ -23,6 +23,7 @@
 #include "../gopairingbasedcryptography_amd/csrc/gmsm29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/subset29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/transcript29.hip.hpp"
+#include "../gopairingbasedcryptography_amd/csrc/share29.hip.hpp"
 #include <condition_variable>
 #include <mutex>
 #include <thread>
@@ -879,6 +880,86 @@ int hc_fr_lsss_launch(const uint8_t *matrix, size_t n_matrices, size_t rows, siz
     }
     if (bad) return -2;
     if (geom_out) { geom_out[0] = g.gw; geom_out[1] = g.spw; geom_out[2] = g.pitch; geom_out[3] = g.sys_words; geom_out[4] = g.level; geom_out[5] = (uint32_t)grid; geom_out[6] = active; }
+    stats_flush();
+    return 0;
+}
+// A stand-in for an LDS block of `words` words that refuses a store outside the block or across the boundaries of another element and a
+// load of anything but a whole element stored before (k_fr_poly_eval and k_fr_share_tree as they are LAUNCHED, below)
+struct CheckedLds {
+    std::vector<Fr> v;
+    std::vector<int64_t> owner;
+    bool bad = false;
+    explicit CheckedLds(size_t words) : v(words), owner(words, -1) {}
+    void reset() { std::fill(owner.begin(), owner.end(), -1); }
+    Fr get(uint32_t off) {
+        if ((size_t)off + NL > v.size() || owner[off] != (int64_t)off) { bad = true; return fr_zero(); }
+        return v[off];
+    }
+    void put(uint32_t off, const Fr &x) {
+        if ((size_t)off + NL > v.size()) { bad = true; return; }
+        for (int i = 0; i < NL; i++) { if (owner[off + i] != -1 && owner[off + i] != (int64_t)off) bad = true; owner[off + i] = off; }
+        v[off] = x;
+    }
+};
+// k_fr_poly_eval as it is launched: geometry, staging and lane mapping of share29.hip.hpp, workgroup by workgroup.
+// geom_out: [rpb, bpr, large, workgroups, active lanes].  -1: arguments the entry refuses; -2: a refusal of the LDS stand-in or a lane outside the rows.
+int hc_fr_poly_eval(const uint8_t *coeffs, size_t n_coeff_rows, size_t d, const uint8_t *points, size_t n_point_rows, size_t m, size_t k, uint8_t *out, uint32_t *geom_out) {
+    if (d < 1 || d > (size_t)FR_POLY_MAX_B || m < 1 || m > (size_t)FR_POLY_MAX_B || !k) return -1;
+    if ((n_coeff_rows != 1 && n_coeff_rows != k) || (n_point_rows != 1 && n_point_rows != k) || !coeffs || !points || !out) return -1;
+    const bool shared = n_coeff_rows == 1 && k > 1;
+    const PolyEvalGeom g = fr_poly_eval_geometry(d, m, shared);
+    const size_t coeff_step = shared ? 0 : d * 32, point_step = n_point_rows == k && k > 1 ? m * 32 : 0;
+    CheckedLds lds((size_t)(g.large ? FR_EVAL_LARGE : FR_EVAL_SMALL) * NL + FR_SHARE_WAVE);
+    const size_t grid = fr_poly_eval_grid(g, k);
+    uint32_t active = 0;
+    for (size_t block = 0; block < grid; block++) {
+        lds.reset();
+        for (uint32_t lane = 0; lane < FR_SHARE_WAVE; lane++)
+            fr_poly_eval_stage(g, (uint32_t)block, lane, k, coeffs, coeff_step, [&](uint32_t off, const Fr &v) { lds.put(off, v); });
+        for (uint32_t lane = 0; lane < FR_SHARE_WAVE && !lds.bad; lane++) {
+            const PolyEvalLane l = fr_poly_eval_map(g, (uint32_t)block, lane, k);
+            if (!l.active) continue;
+            if (l.row >= k || l.t >= m) return -2;
+            active++;
+            const uint32_t mine = coeff_step ? l.lr * fr_poly_eval_pitch(g) : 0u;
+            fr_poly_eval_lane([&](uint32_t i) { return lds.get(mine + i * NL); }, g.d, points + l.row * point_step + 32 * (size_t)l.t, out + 32 * (l.row * g.m + l.t));
+        }
+        if (lds.bad) return -2;
+    }
+    if (geom_out) { geom_out[0] = g.rpb; geom_out[1] = g.bpr; geom_out[2] = g.large; geom_out[3] = (uint32_t)grid; geom_out[4] = active; }
+    stats_flush();
+    return 0;
+}
+// the plan of a node list alone: sizes_out [L, G, C, depth, narrowest level, units]; -1 and the reason in why (up to 96 bytes) when it is refused
+int hc_fr_share_plan(const uint32_t *nodes, size_t n_nodes, uint32_t *sizes_out, char *why) {
+    SharePlan p;
+    const char *w = fr_share_plan(reinterpret_cast<const ShareNode *>(nodes), n_nodes, p);
+    if (w) { if (why) snprintf(why, 96, "%s", w); return -1; }
+    if (sizes_out) { sizes_out[0] = p.L; sizes_out[1] = p.G; sizes_out[2] = p.C; sizes_out[3] = p.depth; sizes_out[4] = p.wmin; sizes_out[5] = (uint32_t)p.units.size(); }
+    return 0;
+}
+// k_fr_share_tree as it is launched: the plan, the geometry, the staging and every level of share29.hip.hpp, workgroup by workgroup, a
+// barrier = the end of a loop over the lanes.  geom_out: [L, G, C, depth, ipb, large, workgroups].  -1: a refused tree or argument; -2 as above.
+int hc_fr_share_tree(const uint32_t *nodes, size_t n_nodes, const uint8_t *secrets, const uint8_t *coeffs, size_t k, uint8_t *out, uint32_t *geom_out) {
+    SharePlan p;
+    if (fr_share_plan(reinterpret_cast<const ShareNode *>(nodes), n_nodes, p) || !k || !secrets || !out || (p.C && !coeffs)) return -1;
+    const ShareGeom g = fr_share_geometry(p);
+    CheckedLds lds((size_t)(g.large ? FR_TREE_LARGE : FR_TREE_SMALL) * NL + FR_SHARE_WAVE);
+    const size_t grid = fr_share_grid(g, k);
+    const auto get = [&](uint32_t off) { return lds.get(off); };
+    const auto put = [&](uint32_t off, const Fr &v) { lds.put(off, v); };
+    for (size_t block = 0; block < grid; block++) {
+        lds.reset();
+        if (!g.G) {
+            for (uint32_t lane = 0; lane < FR_SHARE_WAVE; lane++) fr_share_single((uint32_t)block, lane, k, secrets, out);
+            continue;
+        }
+        for (uint32_t lane = 0; lane < FR_SHARE_WAVE; lane++) fr_share_stage(g, (uint32_t)block, lane, k, secrets, coeffs, put);
+        for (uint32_t lv = 1; lv <= g.depth && !lds.bad; lv++)
+            for (uint32_t lane = 0; lane < FR_SHARE_WAVE; lane++) fr_share_level(g, p.units.data(), p.level_off.data(), lv, (uint32_t)block, lane, k, get, put, out);
+        if (lds.bad) return -2;
+    }
+    if (geom_out) { geom_out[0] = g.L; geom_out[1] = g.G; geom_out[2] = g.C; geom_out[3] = g.depth; geom_out[4] = g.ipb; geom_out[5] = g.large; geom_out[6] = (uint32_t)grid; }
     stats_flush();
     return 0;
 }
