@@ -61,7 +61,7 @@ EXPORTS = list(SIGNATURES)
 EXT_SIGNATURES = {
     "gpbc_ext_version": "i:", "gpbc_g1_multi_scalar_mul": "i:ppzpzp", "gpbc_g2_multi_scalar_mul": "i:ppzpzp",
     "gpbc_multi_scalar_mul_workspace_bytes": "z:zzi", "gpbc_g1_multi_scalar_mul_dev": "i:ppzpzzppzp",
-    "gpbc_g2_multi_scalar_mul_dev": "i:ppzpzzppzp",
+    "gpbc_g2_multi_scalar_mul_dev": "i:ppzpzzppzp", "gpbc_small_call_stats": "i:pppp",
 }
 # ... and for include/gpbc_bn254_subset.h, the bit-selected sums over a fixed set (tests/test_subset_sum.py holds this table against
 # that header).  The three tables are disjoint.

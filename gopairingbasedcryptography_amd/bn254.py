@@ -75,6 +75,14 @@ def release_workspaces():
     _lib.check(_lib.load().gpbc_release_workspaces())
 
 
+def small_call_stats():
+    """(batches, calls, largest_batch, failed_in_shared_batches) of the small-call combiner since the library was loaded
+    (gpbc_small_call_stats); needs no device."""
+    v = [ctypes.c_uint64() for _ in range(4)]
+    _lib.check(_lib.load().gpbc_small_call_stats(*(ctypes.byref(x) for x in v)))
+    return tuple(int(x.value) for x in v)
+
+
 def shutdown():
     global _slots
     for t in list(_gen_tables.values()):

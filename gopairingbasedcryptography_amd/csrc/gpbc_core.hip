@@ -152,6 +152,15 @@ int CallLane::reserve(size_t pin_need, size_t dev_need) {
     }
     return GPBC_OK;
 }
+// What the combiner did since load (gpbc_small_call_stats: tests assert that their calls shared launches).  Written by leaders under calls_mu
+// of their device slot; atomics because the slots have a lock each and the reader takes none.
+static std::atomic<uint64_t> g_small_batches{0}, g_small_calls{0}, g_small_largest{0}, g_small_failed_shared{0};
+extern "C" int gpbc_small_call_stats(uint64_t *batches_out, uint64_t *calls_out, uint64_t *largest_batch_out, uint64_t *failed_in_shared_batches_out) {
+    if (!batches_out || !calls_out || !largest_batch_out || !failed_in_shared_batches_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    *batches_out = g_small_batches.load(); *calls_out = g_small_calls.load();
+    *largest_batch_out = g_small_largest.load(); *failed_in_shared_batches_out = g_small_failed_shared.load();
+    return GPBC_OK;
+}
 int small_call(SmallKind kind, SmallCall &c, SmallBatchFn run) {
     const int n = g_ndev.load(), di = cur_index();
     if (n <= 0 || di >= n) return fail(GPBC_ERR_NO_DEVICE, "gpbc_init() has not bound a HIP device (no CPU fallback exists)");
@@ -182,6 +191,9 @@ int small_call(SmallKind kind, SmallCall &c, SmallBatchFn run) {
         }
         lane->busy = true;
         lane->device = di;
+        g_small_batches.fetch_add(1);
+        g_small_calls.fetch_add(batch.size());
+        for (uint64_t seen = g_small_largest.load(); seen < batch.size() && !g_small_largest.compare_exchange_weak(seen, batch.size());) {}
         lk.unlock();
         int rc = GPBC_OK;
         if (!lane->stream && hipStreamCreateWithFlags(&lane->stream, hipStreamNonBlocking) != hipSuccess) rc = fail(GPBC_ERR_HIP, "hipStreamCreateWithFlags failed for a call lane");
@@ -194,6 +206,7 @@ int small_call(SmallKind kind, SmallCall &c, SmallBatchFn run) {
         lane->busy = false;
         for (SmallCall *b : batch) {
             if (rc != GPBC_OK && b->rc == GPBC_OK) { b->rc = rc; snprintf(b->err, sizeof b->err, "%s", g_err); }
+            if (b->rc != GPBC_OK && batch.size() >= 2) g_small_failed_shared.fetch_add(1);
             b->done = true;
             if (b != &c) b->cv.notify_one();
         }

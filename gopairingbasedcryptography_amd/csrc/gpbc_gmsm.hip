@@ -59,7 +59,7 @@ template <class F> static const SegRedOp GMSM_OP{GMSM_SHAPE, GmsmPoint<F>::BYTES
 
 extern "C" {
 
-int gpbc_ext_version(void) { return 1; }
+int gpbc_ext_version(void) { return 2; }
 size_t gpbc_multi_scalar_mul_workspace_bytes(size_t n, size_t n_seg, int is_g2) { return segred_workspace_bytes(is_g2 ? GMSM_OP<F2> : GMSM_OP<Fe>, n, n_seg); }
 int gpbc_g1_multi_scalar_mul_dev(const void *d_bases, const void *d_scalars, size_t nk, const uint64_t *d_seg_off, size_t n, size_t n_seg, void *d_out,
                                  void *d_workspace, size_t workspace_bytes, void *stream) {

@@ -846,7 +846,11 @@ static int small_pairs_run(SmallKind, CallLane &lane, SmallCall *const *calls, s
     table[K] = N;
     uint64_t *pin_seg = (uint64_t *)(lane.pin + oSeg), *h_echo = (uint64_t *)(lane.pin + oEcho);
     memcpy(pin_seg, table.data(), (K + 1) * sizeof(uint64_t));
-    if (g_fault_table.exchange(0)) pin_seg[K] = pin_seg[K - 1];  // test knob: the device sees a last segment that is empty
+    if (g_fault_table.exchange(0)) {                             // test knob: the device sees the batch's last non-empty segment as empty
+        size_t j = K - 1;                                        // (N > 0: one exists.  Segments behind it are empty in the caller's table too
+        while (table[j + 1] == table[j]) j--;                    // and stay so, so exactly the call that owns segment j must fail.)
+        for (size_t i = j + 1; i <= K; i++) pin_seg[i] = pin_seg[j];
+    }
     memset(h_echo, 0xff, 2 * K * sizeof(uint64_t));
     TRY(GPBC_LAUNCH(k_miller_wide, (unsigned)N, WIDE_MILLER_THREADS, lane.stream, lane.d_pin + oP, lane.d_pin + oQ, lane.dev, N, 0));
     TRY(segments_wide(lane.dev, (const uint64_t *)(lane.d_pin + oSeg), 0, K, N, lane.d_pin + oGt, (uint64_t *)(lane.d_pin + oEcho), lane.stream, lane.d_pin + oOk));

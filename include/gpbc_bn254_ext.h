@@ -9,6 +9,7 @@
  *       sum_x w_x c3x of LW11 Decrypt (dabe/lw11_dabe.go:176-203): prod_x e([w_x]H, c3x) = e(H, sum_x w_x c3x)
  *   sum of the points of every segment, no scalars           the same entries with scalars == NULL, nk == 0
  *   bytes of device memory the _dev entries need             gpbc_multi_scalar_mul_workspace_bytes
+ *   what the small-call combiner did since load              gpbc_small_call_stats (revision 2)
  */
 #ifndef GPBC_BN254_EXT_H
 #define GPBC_BN254_EXT_H
@@ -17,7 +18,7 @@
 extern "C" {
 #endif
 
-int gpbc_ext_version(void);                /* 1 */
+int gpbc_ext_version(void);                /* 2 */
 
 /* Reductions in G1 / G2: out[s] = sum over i in [seg_off[s], seg_off[s+1]) of [k_i] P_i, each term with the semantics of
  * gpbc_g1/g2_scalar_mul_batch (scalars are the ABI's one 32-byte little-endian format: any value < 2^256, acting as its residue mod r;
@@ -46,6 +47,16 @@ int gpbc_g1_multi_scalar_mul_dev(const void *d_bases, const void *d_scalars, siz
                                  void *d_workspace, size_t workspace_bytes, void *stream);
 int gpbc_g2_multi_scalar_mul_dev(const void *d_bases, const void *d_scalars, size_t nk, const uint64_t *d_seg_off, size_t n, size_t n_seg, void *d_out,
                                  void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* Host-pointer calls of up to 2 048 units that arrive from several threads while the device is busy share launches (the main header's
+ * threading notes; gpbc_msm_stats is the same kind of entry: tests assert which path a workload took).  Process-wide counts since the
+ * library was loaded, over all device slots:
+ *   batches                   launches of the combiner, counted when a leader has taken its batch and before it launches
+ *   calls                     requests served by those batches (calls - batches = requests that rode in another caller's launch)
+ *   largest_batch             the most requests in one batch
+ *   failed_in_shared_batches  requests that ended with a status other than GPBC_OK in a batch of two or more
+ * Needs no device (all zero before any call).  A null pointer is GPBC_ERR_INVALID_ARG with nothing written. */
+int gpbc_small_call_stats(uint64_t *batches_out, uint64_t *calls_out, uint64_t *largest_batch_out, uint64_t *failed_in_shared_batches_out);
 
 #ifdef __cplusplus
 }

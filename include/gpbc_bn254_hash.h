@@ -1,5 +1,5 @@
 /* SHA-256 on the device with the digest as bytes or as a scalar, entries of libgpbc_bn254.so added after the main header (gpbc_bn254.h)
- * was frozen at gpbc_abi_version() 8, beside the extension header (gpbc_bn254_ext.h, gpbc_ext_version() 1) and the subset header
+ * was frozen at gpbc_abi_version() 8, beside the extension header (gpbc_bn254_ext.h, gpbc_ext_version() 2) and the subset header
  * (gpbc_bn254_subset.h, gpbc_subset_version() 1).  Everything the main header says about status codes, gpbc_last_error(), devices,
  * host-pointer entries (synchronous) and *_dev entries (device pointers and a `stream`, asynchronous) holds here; gpbc_hash_version()
  * counts the revisions of this file.

@@ -1,5 +1,5 @@
 /* Bit-selected sums over a fixed set of points, entries of libgpbc_bn254.so added after the main header (gpbc_bn254.h) was frozen at
- * gpbc_abi_version() 8 and beside the extension header (gpbc_bn254_ext.h, gpbc_ext_version() 1).  Everything the main header says
+ * gpbc_abi_version() 8 and beside the extension header (gpbc_bn254_ext.h, gpbc_ext_version() 2).  Everything the main header says
  * about status codes, gpbc_last_error(), devices, host-pointer entries (synchronous) and *_dev entries (device pointers and a
  * `stream`, asynchronous) holds here; gpbc_subset_version() counts the revisions of this file.
  *

@@ -162,7 +162,7 @@ def test_ext_signature_table_is_the_extension_header(lib):
     and the main table does not hold the new names (it mirrors the main header alone)"""
     from gopairingbasedcryptography_amd import _lib
     protos = ext_prototypes()
-    assert sorted(protos) == sorted(_lib.EXT_SIGNATURES) and len(protos) == 6
+    assert sorted(protos) == sorted(_lib.EXT_SIGNATURES) and len(protos) == 7
     assert not set(_lib.EXT_SIGNATURES) & set(_lib.SIGNATURES) and not set(_lib.EXT_SIGNATURES) & set(_lib.EXPORTS)
     ctype = {"p": ctypes.c_void_p, "z": ctypes.c_size_t, "i": ctypes.c_int}
     for name, (ret, params) in protos.items():
@@ -170,8 +170,58 @@ def test_ext_signature_table_is_the_extension_header(lib):
         fn = getattr(lib, name)
         assert fn.restype is ctype[ret], name
         assert fn.argtypes is not None and list(fn.argtypes) == [ctype[k] for k in params], name
-    assert lib.gpbc_ext_version() == 1 and lib.gpbc_abi_version() == 8
+    assert lib.gpbc_ext_version() == 2 and lib.gpbc_abi_version() == 8
     assert '#include "gpbc_bn254.h"' in open(os.path.join(ROOT, "include", "gpbc_bn254_ext.h")).read()
+
+
+def test_small_call_stats_symbol_and_signature(lib):
+    """revision 2 of the extension header: four uint64_t out-pointers, an int status, declared in EXT_SIGNATURES and wrapped as a tuple"""
+    from gopairingbasedcryptography_amd import _lib, bn254
+    text = re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "gpbc_bn254_ext.h")).read())
+    assert ("int gpbc_small_call_stats(uint64_t *batches_out, uint64_t *calls_out, uint64_t *largest_batch_out, "
+            "uint64_t *failed_in_shared_batches_out);") in text
+    assert _lib.EXT_SIGNATURES["gpbc_small_call_stats"] == "i:pppp" and ext_prototypes()["gpbc_small_call_stats"] == ("i", ["p"] * 4)
+    fn = lib.gpbc_small_call_stats
+    assert fn.restype is ctypes.c_int and list(fn.argtypes) == [ctypes.c_void_p] * 4
+    v = [ctypes.c_uint64(1 << 63) for _ in range(4)]
+    assert fn(*(ctypes.byref(x) for x in v)) == 0
+    got = bn254.small_call_stats()
+    assert isinstance(got, tuple) and len(got) == 4 and all(isinstance(x, int) for x in got)
+    # counters only grow, and a batch holds at least one call and at most all of them
+    assert all(a.value <= b for a, b in zip(v, got)) and got[0] <= got[1] and got[2] <= got[1] and got[3] <= got[1]
+
+
+def test_small_call_stats_are_zero_before_any_call():
+    """a fresh process that loads the library and binds no device: all four counters are zero, and stay zero after a small call that is
+    refused for want of a device (nothing was batched).  A process of its own, because the counters are process-wide since load."""
+    import subprocess
+    import sys
+    from gopairingbasedcryptography_amd import _build, _lib
+    _build.build_library()
+    prog = ("import ctypes, sys\n"
+            "lib = ctypes.CDLL(sys.argv[1])\n"
+            "v = [ctypes.c_uint64(7) for _ in range(4)]\n"
+            "rc = [lib.gpbc_small_call_stats(*(ctypes.byref(x) for x in v))]\n"
+            "first = [x.value for x in v]\n"
+            "P, Q, out = ctypes.create_string_buffer(64), ctypes.create_string_buffer(128), ctypes.create_string_buffer(384)\n"
+            "lib.gpbc_pair_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]\n"
+            "rc.append(lib.gpbc_pair_batch(P, Q, 1, out))\n"
+            "rc.append(lib.gpbc_small_call_stats(*(ctypes.byref(x) for x in v)))\n"
+            "print(rc, first, [x.value for x in v])\n")
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="")      # (no device even where the machine has one)
+    r = subprocess.run([sys.executable, "-c", prog, _lib.LIB_PATH], capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stdout.split("\n")[0] == "[0, -2, 0] [0, 0, 0, 0] [0, 0, 0, 0]", r.stdout          # -2: GPBC_ERR_NO_DEVICE
+
+
+def test_small_call_stats_refuse_null(lib):
+    """any null out-pointer is GPBC_ERR_INVALID_ARG with a message and nothing written to the others"""
+    for hole in range(4):
+        v = [ctypes.c_uint64(0xA5A5A5A5A5A5A5A5) for _ in range(4)]
+        args = [None if i == hole else ctypes.addressof(x) for i, x in enumerate(v)]
+        assert lib.gpbc_small_call_stats(*args) == -1 and b"null" in lib.gpbc_last_error(), hole
+        assert all(x.value == 0xA5A5A5A5A5A5A5A5 for x in v), hole
+    assert lib.gpbc_small_call_stats(None, None, None, None) == -1
 
 
 def test_wrapper_rejects_malformed_arguments():

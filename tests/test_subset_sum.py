@@ -170,9 +170,9 @@ def test_subset_signature_table_is_the_subset_header(lib):
         fn = getattr(lib, name)
         assert fn.restype is ctype[ret], name
         assert fn.argtypes is not None and list(fn.argtypes) == [ctype[k] for k in params], name
-    assert lib.gpbc_subset_version() == 1 and lib.gpbc_abi_version() == 8 and lib.gpbc_ext_version() == 1
+    assert lib.gpbc_subset_version() == 1 and lib.gpbc_abi_version() == 8 and lib.gpbc_ext_version() == 2
     assert '#include "gpbc_bn254.h"' in open(os.path.join(ROOT, "include", "gpbc_bn254_subset.h")).read()
-    assert len(_lib.SIGNATURES) == 131 and len(_lib.EXT_SIGNATURES) == 6
+    assert len(_lib.SIGNATURES) == 131 and len(_lib.EXT_SIGNATURES) == 7
 
 
 def test_source_hash_covers_the_new_header_and_unit():
