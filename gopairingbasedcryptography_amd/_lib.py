@@ -83,6 +83,12 @@ SHARE_SIGNATURES = {
     "gpbc_share_tree_create": "i:pzp", "gpbc_share_tree_destroy": "i:p", "gpbc_share_tree_leaves": "z:p",
     "gpbc_share_tree_coeffs": "z:p", "gpbc_fr_share_tree": "i:pppzp", "gpbc_fr_share_tree_dev": "i:pppzpp",
 }
+# ... and for include/gpbc_bn254_indexed.h, the indexed sums over fixed-base tables and LSSS share generation (tests/test_indexed_abi.py
+# holds this table against that header).  The six tables are disjoint.
+INDEXED_SIGNATURES = {
+    "gpbc_indexed_version": "i:", "gpbc_fixed_base_indexed": "i:ppzzpzpp", "gpbc_fixed_base_indexed_dev": "i:ppzzpzppp",
+    "gpbc_fr_lsss_shares": "i:pzzzpzp", "gpbc_fr_lsss_shares_dev": "i:pzzzpzpp",
+}
 # every pointer is a c_void_p: it takes ints, None, c_void_p, ctypes arrays, byref() and ndarray.ctypes.data_as() alike
 _CTYPES = {"p": ctypes.c_void_p, "z": ctypes.c_size_t, "i": ctypes.c_int, "l": ctypes.c_long, "s": ctypes.c_char_p}
 
@@ -108,7 +114,7 @@ def load():
         except ImportError:
             pass
         lib = ctypes.CDLL(LIB_PATH)
-        for name, sig in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(SUBSET_SIGNATURES.items()) + list(HASH_SIGNATURES.items()) + list(SHARE_SIGNATURES.items()):
+        for name, sig in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(SUBSET_SIGNATURES.items()) + list(HASH_SIGNATURES.items()) + list(SHARE_SIGNATURES.items()) + list(INDEXED_SIGNATURES.items()):
             ret, params = sig.split(":")
             fn = getattr(lib, name)
             fn.restype = _CTYPES[ret]

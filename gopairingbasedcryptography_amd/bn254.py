@@ -789,6 +789,49 @@ def fr_lsss_weights(matrix, rows=None, cols=None, held=None, out=None, ok_out=No
     return out, ok_out
 
 
+def fr_lsss_shares(matrix, vectors, rows=None, cols=None, out=None):
+    """out[j][x] = sum_c matrix[j or 0][x][c] * vectors[j][c] modulo r, for k vectors: the shares lambda_x = M_x . v of
+    LewkoWatersLsssMatrix.ComputeVector with v = (s, v_2, ..) per item (include/gpbc_bn254_indexed.h).  matrix: one rows x cols matrix
+    (shared by the k vectors) or k of them, as nested Python ints ([rows][cols] or [n][rows][cols]; rows and cols may then be omitted), a
+    uint8 array or a CUDA tensor of 32-byte scalars, in the layout fr_lsss_weights takes; vectors: [k][cols] ints or k x cols scalar rows.
+    Entries are any value below 2^256 and act as their residue (-1 goes in as r - 1).  Returns [k, rows, 32] canonical scalars of the kind
+    that went in (numpy, or a CUDA tensor enqueued on the current stream)."""
+    if not bufs.is_torch(matrix) and not isinstance(matrix, (np.ndarray, bytes, bytearray)):
+        m3 = [list(r) for r in matrix]
+        if m3 and m3[0] and not isinstance(m3[0][0], (list, tuple)):
+            m3 = [m3]                                                        # one [rows][cols] matrix
+        m3 = [[list(r) for r in mat] for mat in m3]
+        rows = len(m3[0]) if m3 and rows is None else rows
+        cols = len(m3[0][0]) if m3 and m3[0] and cols is None else cols
+        if any(len(mat) != rows or any(len(r) != cols for r in mat) for mat in m3):
+            raise ValueError("matrix: every system needs %s rows of %s scalars" % (rows, cols))
+        matrix = [v for mat in m3 for r in mat for v in r]
+    for v, what in ((rows, "rows"), (cols, "cols")):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 1 <= int(v) <= FR_LSSS_MAX:
+            raise ValueError("%s must be in 1 .. %d (got %s)" % (what, FR_LSSS_MAX, v))
+    rows, cols = int(rows), int(cols)
+    if not bufs.is_torch(vectors) and not isinstance(vectors, (np.ndarray, bytes, bytearray)):
+        vrows = [list(r) for r in vectors]
+        if any(len(r) != cols for r in vrows):
+            raise ValueError("vectors: every vector needs %d scalars" % cols)
+        vectors = [v for r in vrows for v in r]
+    (mb, nscalars), (vb, nv) = bufs.rows(_fr_in(matrix), SCALAR_BYTES, "matrix"), bufs.rows(_fr_in(vectors), SCALAR_BYTES, "vectors")
+    dev = bufs.device_of(mb, vb, out)
+    if nscalars == 0 or nscalars % (rows * cols) or nv % cols:
+        raise ValueError("matrix needs whole systems of %d x %d scalars and vectors %d scalars each" % (rows, cols, cols))
+    nm, k = nscalars // (rows * cols), nv // cols
+    if k and nm not in (1, k):
+        raise ValueError("need one matrix or one per vector (got %d matrices, %d vectors)" % (nm, k))
+    if k > (1 << 29) - 1:
+        raise ValueError("too many vectors for one call (%d)" % k)
+    out = bufs.output(out, (k, rows, SCALAR_BYTES), dev)
+    if k:
+        if _overlaps(out, mb, vb):
+            raise ValueError("out overlaps an input")
+        _call("fr_lsss_shares", dev, mb, nm, rows, cols, vb, k, out)
+    return out
+
+
 _gen_tables = {}
 
 
@@ -1119,6 +1162,10 @@ def hash_g1_gt_gt_to_fr(u, v, w, out=None):
 
 
 # --------------------------------------------------------------------------------------- fixed-base tables / MSM
+INDEX_NONE = 0xFFFFFFFF          # GPBC_INDEX_NONE: "no term" in an index row of FixedBase.indexed
+INDEXED_MAX_TERMS = 16
+
+
 class FixedBase:
     """8-bit window tables of a fixed set of bases kept in HBM (1 MB per G1 base, 2 MB per G2 base): afterwards a term of
     a sum costs 32 mixed additions and no doublings.  Serves (*G1Affine|*G2Affine).ScalarMultiplicationBase (one base: the
@@ -1170,6 +1217,58 @@ class FixedBase:
         if self.nbase != 1:
             raise ValueError("mul() is the single-base form; use msm()")
         return self.msm(scalars)
+
+    def indexed(self, index, scalars, terms=None, out=None):
+        """(out [n, 64|128], ok [n]): out[i] = sum_{t < terms} [scalars[i][t]] base[index[i % rows][t]] (include/gpbc_bn254_indexed.h).
+        index: rows x terms entries as a uint32 array / CUDA tensor of the int32 or uint32 kind with `terms`, or a list of rows with None
+        (INDEX_NONE) for "no term"; rows == n gives every output its own row, fewer rows repeat with that period.  scalars: [n][terms]
+        ints or n x terms scalar rows, any value below 2^256, used as they are (so [r] B is infinity).  1 <= terms <= 16.  An index
+        >= nbase other than INDEX_NONE gives an all-zero row and ok = 0.  CUDA tensors in give CUDA tensors out, enqueued on the
+        current stream and not synchronised."""
+        if not bufs.is_torch(index) and not isinstance(index, np.ndarray):
+            irows = [list(r) if isinstance(r, (list, tuple)) else [r] for r in index]
+            terms = len(irows[0]) if irows and terms is None else terms
+            if any(len(r) != terms for r in irows):
+                raise ValueError("index: every row needs %s entries" % terms)
+            flat = [INDEX_NONE if v is None else int(v) for r in irows for v in r]
+            if any(v < 0 or v > INDEX_NONE for v in flat):
+                raise ValueError("index entries are unsigned 32-bit values")
+            index = np.array(flat, dtype=np.uint32)
+        if not isinstance(terms, (int, np.integer)) or isinstance(terms, bool) or not 1 <= int(terms) <= INDEXED_MAX_TERMS:
+            raise ValueError("terms must be in 1 .. %d (got %s)" % (INDEXED_MAX_TERMS, terms))
+        terms = int(terms)
+        if bufs.is_torch(index):
+            if str(index.dtype) not in ("torch.int32", "torch.uint32") or not index.is_contiguous():
+                raise ValueError("a device index must be a contiguous int32 / uint32 tensor")
+            nidx = index.numel()
+        else:
+            if index.dtype != np.uint32:
+                raise ValueError("index must be uint32 (got %s)" % index.dtype)
+            index = np.ascontiguousarray(index).reshape(-1)
+            nidx = index.size
+        if not bufs.is_torch(scalars) and not isinstance(scalars, (np.ndarray, bytes, bytearray)):
+            srows = [list(r) if isinstance(r, (list, tuple)) else [r] for r in scalars]
+            if any(len(r) != terms for r in srows):
+                raise ValueError("scalars: every output needs %d scalars" % terms)
+            scalars = [v for r in srows for v in r]
+        k, nscalars = bufs.rows(_fr_in(scalars), SCALAR_BYTES, "scalars")
+        dev = bufs.device_of(index, k, out)
+        if nscalars % terms or nidx % terms:
+            raise ValueError("scalars and index need whole rows of %d" % terms)
+        n, nrows = nscalars // terms, nidx // terms
+        if n and not 1 <= nrows <= n:
+            raise ValueError("index needs between 1 and n = %d rows (got %d)" % (n, nrows))
+        if n * terms >> 32:
+            raise ValueError("n * terms must stay below 2^32")
+        out = bufs.output(out, (n, self.width), dev)
+        ok = bufs.output(None, (n,), dev, "ok")
+        if n:
+            if not self._h:
+                raise ValueError("the table is closed")
+            if _overlaps(out, index.view(np.uint8) if dev is None else None, k):
+                raise ValueError("out overlaps an input")
+            _call("fixed_base_indexed", dev, self._h, index, nrows, terms, k, n, out, ok)
+        return out, ok
 
     def close(self):
         if self._h:

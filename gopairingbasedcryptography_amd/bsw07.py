@@ -165,13 +165,17 @@ def share_plan(tree):
     return nodes, attributes
 
 
-def encrypt_batch(engine, tree_or_plan, h, e_alpha, h1, messages, s, coeffs):
+def encrypt_batch(engine, tree_or_plan, h, e_alpha, h1, messages, s, coeffs, tables=False):
     """n ciphertexts under one policy.  tree_or_plan: a Leaf / Threshold tree or share_plan(tree); h = g1^beta (64 B) and
     e_alpha = e(g1, g2)^alpha (384 B) of the public key; h1: {attribute: 64-byte G1 point} (H1 of every attribute of the policy);
     messages [n, 384]; s: n scalars; coeffs: [n, C] scalars, a gate's threshold - 1 coefficients in the order ShareSecret draws them
     (None or empty when C == 0).  Returns exactly the operands of decrypt_batch_arrays with the columns in leaf-id order:
     (c_tilde [n, 384], c [n, 64], cy [n, L, 64], cy_prime [n, L, 64]).  numpy in gives numpy out; CUDA tensors (messages, s, coeffs) give
-    tensors, and only the public key, the L points of h1 and the tree go to the device."""
+    tensors, and only the public key, the L points of h1 and the tree go to the device.
+
+    tables=True (opt-in; the same bytes): Cy' comes from a fixed-base table over the L points of h1 — engine.FixedBase.indexed with
+    terms = 1 and the L index rows repeating per ciphertext, 32 mixed additions per leaf and no doublings — instead of the variable-base
+    kernel on the L points expanded n times.  The table costs 1 MB of device memory per leaf while the call runs."""
     nodes, attributes = share_plan(tree_or_plan) if isinstance(tree_or_plan, (Leaf, Threshold)) else tree_or_plan
     L = len(attributes)
     n = bufs.nbytes(messages) // 384
@@ -203,7 +207,15 @@ def encrypt_batch(engine, tree_or_plan, h, e_alpha, h1, messages, s, coeffs):
     c = engine.g1_scalar_mul(public(h, 64, "h"), bufs.flat(s))
     cy = engine.g1_scalar_mul_base(shares)
     hy = bufs.put(np.stack([np.asarray(h1[a], dtype=np.uint8).reshape(64) for a in attributes]), messages)
-    cy_prime = engine.g1_scalar_mul(bufs.flat(bufs.expand(bufs.view(hy, 1, L, 64), n, L, 64)), shares)
+    if tables and n:
+        index = np.arange(L, dtype=np.uint32).reshape(L, 1)
+        table = engine.FixedBase(hy, g2=False)
+        try:
+            cy_prime, _ = table.indexed(bufs.put(index.view(np.int32), messages) if bufs.is_torch(messages) else index, shares, terms=1)
+        finally:
+            table.close()
+    else:
+        cy_prime = engine.g1_scalar_mul(bufs.flat(bufs.expand(bufs.view(hy, 1, L, 64), n, L, 64)), shares)
     return bufs.view(c_tilde, n, 384), bufs.view(c, n, 64), bufs.view(cy, n, L, 64), bufs.view(cy_prime, n, L, 64)
 
 

@@ -1,7 +1,10 @@
 // libgpbc_bn254.so, one of the units listed in _build.py: G1 / G2 scalar multiplication, point sums, fixed-base window tables and the sums over
-// them, with their C-ABI entries (include/gpbc_bn254.h).  gfx950 only.
+// them, with their C-ABI entries (include/gpbc_bn254.h), and the indexed sums over the same tables (csrc/fbindex29.hip.hpp,
+// include/gpbc_bn254_indexed.h).  gfx950 only.
 #include "gpbc_common.hpp"
 #include "curve29_oct.hip.hpp"
+#include "fbindex29.hip.hpp"
+#include "../../include/gpbc_bn254_indexed.h"
 
 // Scalar multiplication: a lane owns SMUL_K points (t, t+T, t+2T, ...; T = ceil(n / SMUL_K)) whose Jacobian results share
 // one field inversion.  Measured on MI355X (2^20 points): K = 1 -> 36.9 M G1 / 15.0 M G2 per second, K = 2 -> 36.9 / 13.7,
@@ -196,6 +199,31 @@ GPBC_KERNEL_G1 k_g1_fb_msm_quad(const int32_t *__restrict__ table, const uint8_t
 GPBC_KERNEL k_g2_fb_msm_quad(const int32_t *__restrict__ table, const uint8_t *__restrict__ base_inf, size_t nbase, const uint8_t *__restrict__ scalars,
                              size_t n_msm, size_t C, size_t n_chunks, uint8_t *__restrict__ partial) {
     fb_msm_lane<F2, true>(table, base_inf, nbase, scalars, n_msm, C, n_chunks, partial);
+}
+
+// Indexed sums over the tables: one lane per output, `terms` terms of 32 mixed additions each, one inversion, one store
+// (fb_indexed_lane).  Which output a lane owns is fb_index_output's: the natural order, or with periodic index rows the grouped one, in
+// which a workgroup's lanes share the index row and the workgroups run index-row-major.
+static_assert(FBI_ENTRIES == FB_ENTRIES && FBI_WAVE == BLOCK && GPBC_INDEX_NONE == FBI_NONE, "fbindex29.hip.hpp restates the table geometry");
+#ifndef GPBC_FBINDEX_GROUP_MIN
+#define GPBC_FBINDEX_GROUP_MIN 64      /* outputs per index row from which the grouped order is taken (a build with SIZE_MAX here never takes it: the A/B of DESIGN.md) */
+#endif
+template <class F> __device__ __forceinline__ void fb_indexed_kernel(const int32_t *table, const uint8_t *base_inf, size_t nbase, const uint32_t *index, FbIndexMap map, uint32_t terms,
+                                                                     const uint8_t *scalars, uint8_t *out, uint8_t *ok_out) {
+    const size_t i = fb_index_output(map, blockIdx.x, threadIdx.x);
+    if (i >= map.n) return;
+    constexpr size_t PT = sizeof(F) == sizeof(Fe) ? GPBC_G1_BYTES : GPBC_G2_BYTES;
+    fb_indexed_lane<F>(table, base_inf, nbase, index + (i % map.P) * terms, terms, scalars + i * terms * GPBC_SCALAR_BYTES, out + i * PT, ok_out ? ok_out + i : nullptr,
+                       [](uint32_t *k, const uint8_t *p) { load_scalar(k, p); },
+                       [](uint8_t *p, const AffP<F> &a) { if constexpr (sizeof(F) == sizeof(Fe)) g1_store_aff(p, a); else g2_store_aff(p, a); });
+}
+GPBC_KERNEL_G1 k_g1_fb_indexed(const int32_t *__restrict__ table, const uint8_t *__restrict__ base_inf, size_t nbase, const uint32_t *__restrict__ index, FbIndexMap map, uint32_t terms,
+                               const uint8_t *__restrict__ scalars, uint8_t *__restrict__ out, uint8_t *__restrict__ ok_out) {
+    fb_indexed_kernel<Fe>(table, base_inf, nbase, index, map, terms, scalars, out, ok_out);
+}
+GPBC_KERNEL k_g2_fb_indexed(const int32_t *__restrict__ table, const uint8_t *__restrict__ base_inf, size_t nbase, const uint32_t *__restrict__ index, FbIndexMap map, uint32_t terms,
+                            const uint8_t *__restrict__ scalars, uint8_t *__restrict__ out, uint8_t *__restrict__ ok_out) {
+    fb_indexed_kernel<F2>(table, base_inf, nbase, index, map, terms, scalars, out, ok_out);
 }
 
 // one launch of the strided point sum for the other units (gpbc_common.hpp): out[t] = in[t] + in[t + n_out] + in[t + 2 n_out] + ...
@@ -557,6 +585,56 @@ int gpbc_fixed_base_msm(const gpbc_fixed_base *h, const void *scalars, size_t n_
     const size_t wsb = gpbc_fixed_base_msm_workspace_bytes(h, n_msm);
     return host_call(n_msm, c, HostRoute{CALL_FIXED_BASE, small_fixed_base_run, SMALL_CALL_MAX_UNITS, LANE_CALL_MAX_UNITS, 0, wsb},
                      [=](const DevCols &d, size_t m, hipStream_t st) { return gpbc_fixed_base_msm_dev(h, d.in[0], m, d.out[0], d.tmp, wsb, st); });
+}
+
+// ----------------------------------------------------------------------------------------------- indexed sums (include/gpbc_bn254_indexed.h)
+int gpbc_indexed_version(void) { return 1; }
+static bool fbi_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return a && b && pa < pb + nb && pb < pa + na;
+}
+// everything that can be said without the device; *todo = whether there is anything to launch
+static int fb_indexed_args(const gpbc_fixed_base *h, const uint32_t *index, size_t n_index_rows, size_t terms, const void *scalars, size_t n, const void *out, const uint8_t *ok_out) {
+    if (terms < 1 || terms > FBI_MAX_TERMS) return fail(GPBC_ERR_INVALID_ARG, "terms must be in 1 .. %zu (got %zu)", FBI_MAX_TERMS, terms);
+    if (n > (size_t)0xffffffffu / terms) return fail(GPBC_ERR_INVALID_ARG, "n * terms must stay below 2^32 (got n = %zu, terms = %zu)", n, terms);
+    if (!h) return fail(GPBC_ERR_INVALID_ARG, "null table handle");
+    if (!n) return GPBC_OK;
+    if (n_index_rows < 1 || n_index_rows > n) return fail(GPBC_ERR_INVALID_ARG, "n_index_rows must be in 1 .. n (got %zu, n = %zu)", n_index_rows, n);
+    if (!index || !scalars || !out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    const size_t ib = n_index_rows * terms * sizeof(uint32_t), sb = n * terms * GPBC_SCALAR_BYTES, ob = n * (h->is_g2 ? GPBC_G2_BYTES : GPBC_G1_BYTES);
+    if (fbi_overlap(out, ob, index, ib) || fbi_overlap(out, ob, scalars, sb) || fbi_overlap(ok_out, n, index, ib) || fbi_overlap(ok_out, n, scalars, sb) || fbi_overlap(out, ob, ok_out, n))
+        return fail(GPBC_ERR_INVALID_ARG, "an output overlaps an input or the other output");
+    return GPBC_OK;
+}
+int gpbc_fixed_base_indexed_dev(const gpbc_fixed_base *h, const uint32_t *d_index, size_t n_index_rows, size_t terms, const void *d_scalars, size_t n, void *d_out, uint8_t *d_ok_out,
+                                void *stream) {
+    TRY(fb_indexed_args(h, d_index, n_index_rows, terms, d_scalars, n, d_out, d_ok_out));
+    if (!n) return GPBC_OK;
+    TRY(bind_device());
+    if (current_device() != h->device) return fail(GPBC_ERR_INVALID_ARG, "table was built on device %d", h->device);
+    const FbIndexMap map = fb_index_map(n, n_index_rows, (size_t)GPBC_FBINDEX_GROUP_MIN);
+    const unsigned grid = (unsigned)fb_index_grid(map);              // at most n / 64 + n_index_rows workgroups, n < 2^32
+    if (h->is_g2)
+        return GPBC_LAUNCH(k_g2_fb_indexed, grid, BLOCK, (hipStream_t)stream, h->table, h->base_inf, h->nbase, d_index, map, (uint32_t)terms, (const uint8_t *)d_scalars, (uint8_t *)d_out, d_ok_out);
+    return GPBC_LAUNCH(k_g1_fb_indexed, grid, BLOCK, (hipStream_t)stream, h->table, h->base_inf, h->nbase, d_index, map, (uint32_t)terms, (const uint8_t *)d_scalars, (uint8_t *)d_out, d_ok_out);
+}
+// Host pointers: the shared staging path on the table's device only (the handle lives there), not combined with other threads' calls and
+// not cut into chunks (a periodic index row belongs to an output by its position in the whole call).
+int gpbc_fixed_base_indexed(const gpbc_fixed_base *h, const uint32_t *index, size_t n_index_rows, size_t terms, const void *scalars, size_t n, void *out, uint8_t *ok_out) {
+    TRY(fb_indexed_args(h, index, n_index_rows, terms, scalars, n, out, ok_out));
+    if (!n) return GPBC_OK;
+    TRY(bind_device());
+    if (current_device() != h->device) return fail(GPBC_ERR_INVALID_ARG, "table was built on device %d", h->device);
+    const bool own = n_index_rows == n;
+    HostCall c = HostCall().input(scalars, terms * GPBC_SCALAR_BYTES);
+    if (own) c.input(index, terms * sizeof(uint32_t)); else c.input(index, n_index_rows * terms * sizeof(uint32_t), true);
+    c.output(out, h->is_g2 ? GPBC_G2_BYTES : GPBC_G1_BYTES);
+    if (ok_out) c.output(ok_out, 1);
+    const bool has_ok = ok_out != nullptr;
+    return host_call(n, c, HostRoute{CALL_KINDS, nullptr, 0, LANE_CALL_MAX_UNITS},
+                     [=](const DevCols &d, size_t m, hipStream_t st) {
+                         return gpbc_fixed_base_indexed_dev(h, (const uint32_t *)d.in[1], own ? m : n_index_rows, terms, d.in[0], m, d.out[0], has_ok ? d.out[1] : nullptr, st);
+                     });
 }
 
 }  // extern "C"

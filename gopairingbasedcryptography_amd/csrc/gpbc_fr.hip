@@ -2,11 +2,14 @@
 // inverse and the fr.Element conversions on the ABI's scalar format, the two polynomial kernels of the AFP25 / GWWW25 opening
 // proofs, the Lagrange basis over a node set per row (SW05 fuzzy IBE) and the LSSS reconstruction weights of a policy per
 // ciphertext (Waters11 CP-ABE) — with their C-ABI entries (include/gpbc_bn254.h, "scalar field"), and secret sharing (csrc/share29.hip.hpp):
-// polynomial evaluation and the shares of a threshold tree (include/gpbc_bn254_share.h).  gfx950 only.
+// polynomial evaluation and the shares of a threshold tree (include/gpbc_bn254_share.h), and LSSS share generation (csrc/lsss29.hip.hpp,
+// include/gpbc_bn254_indexed.h).  gfx950 only.
 #include "gpbc_common.hpp"
 #include "fr29.hip.hpp"
 #include "share29.hip.hpp"
+#include "lsss29.hip.hpp"
 #include "../../include/gpbc_bn254_share.h"
+#include "../../include/gpbc_bn254_indexed.h"
 
 // ------------------------------------------------------------------------------------------------ elementwise
 // one element per lane (no __restrict__: out may be a, or b)
@@ -238,6 +241,29 @@ GPBC_KERNEL_G1 k_fr_share_tree(const ShareUnit *__restrict__ units, const uint32
 __global__ void __launch_bounds__(BLOCK) k_fr_share_tree_large(const ShareUnit *__restrict__ units, const uint32_t *__restrict__ level_off, const uint8_t *__restrict__ secrets, const uint8_t *__restrict__ coeffs,
                                      size_t k, ShareGeom gm, uint8_t *__restrict__ out) {
     fr_share_tree_kernel<FR_TREE_LARGE>(units, level_off, secrets, coeffs, k, gm, out);
+}
+
+// ------------------------------------------------------------------------------------------------ LSSS share generation
+// out[j][x] = M_x . v_j: lsss29.hip.hpp has the arithmetic, the geometry, the staging and the lane mapping; here is the LDS block of the
+// one shared matrix's row group and the barrier.  mat_step != 0: a matrix per item, read by the lanes that own its rows.
+static_assert(FR_LSSS_SHARES_WAVE == BLOCK, "one wave per workgroup");
+GPBC_KERNEL_G1 k_fr_lsss_shares(const uint8_t *__restrict__ matrix, size_t mat_step, const uint8_t *__restrict__ vectors, size_t k, LsssSharesGeom gm, uint8_t *__restrict__ out) {
+    __shared__ int32_t ms[FR_SHARES_CAP * NL + BLOCK];
+    if (!mat_step) {
+        fr_lsss_shares_stage(gm, blockIdx.x, threadIdx.x, matrix, [&](uint32_t off, const Fr &v) { lds_put(ms + off, v); });
+        __syncthreads();
+    }
+    const LsssSharesLane l = fr_lsss_shares_map(gm, blockIdx.x, threadIdx.x, k);
+    if (!l.active) return;
+    const uint8_t *vec = vectors + l.item * gm.cols * GPBC_SCALAR_BYTES;
+    uint8_t *o = out + (l.item * gm.rows + l.x) * GPBC_SCALAR_BYTES;
+    if (mat_step) {
+        const uint8_t *row = matrix + l.item * mat_step + (size_t)l.x * gm.cols * GPBC_SCALAR_BYTES;
+        fr_lsss_shares_lane([&](uint32_t c) { return fr_load_raw(row + 32 * (size_t)c); }, gm.cols, vec, o);
+    } else {
+        const int32_t *mine = ms + l.xr * gm.pitch;
+        fr_lsss_shares_lane([&](uint32_t c) { return lds_get(mine + c * NL); }, gm.cols, vec, o);
+    }
 }
 
 extern "C" {
@@ -533,6 +559,40 @@ int gpbc_fr_share_tree(const gpbc_share_tree *t, const void *secrets, const void
     const bool has = t->geom.C != 0;
     return host_call(k, c.output(out, t->geom.L * GPBC_SCALAR_BYTES), HostRoute{CALL_KINDS, nullptr, 0, LANE_CALL_MAX_UNITS},
                      [=](const DevCols &dc, size_t m, hipStream_t st) { return gpbc_fr_share_tree_dev(t, dc.in[0], has ? dc.in[1] : nullptr, m, dc.out[0], st); });
+}
+
+// ------------------------------------------------------------------------------------------------ LSSS share entries (include/gpbc_bn254_indexed.h)
+static int lsss_shares_args(const void *matrix, size_t n_matrices, size_t rows, size_t cols, const void *vectors, size_t k, const void *out) {
+    if (rows < 1 || rows > (size_t)FR_LSSS_MAX || cols < 1 || cols > (size_t)FR_LSSS_MAX)
+        return fail(GPBC_ERR_INVALID_ARG, "rows and cols must be in 1 .. %d (got rows = %zu, cols = %zu)", FR_LSSS_MAX, rows, cols);
+    if (k > (size_t)0x7fffffff / 4) return fail(GPBC_ERR_INVALID_ARG, "too many vectors for one call (%zu)", k);
+    if (!k) return GPBC_OK;
+    if (n_matrices != 1 && n_matrices != k) return fail(GPBC_ERR_INVALID_ARG, "n_matrices must be 1 or k (got %zu, k = %zu)", n_matrices, k);
+    if (!matrix || !vectors || !out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    const size_t ob = k * rows * GPBC_SCALAR_BYTES;
+    if (overlap(out, ob, matrix, n_matrices * rows * cols * GPBC_SCALAR_BYTES) || overlap(out, ob, vectors, k * cols * GPBC_SCALAR_BYTES))
+        return fail(GPBC_ERR_INVALID_ARG, "out overlaps an input");
+    return GPBC_OK;
+}
+int gpbc_fr_lsss_shares_dev(const void *d_matrix, size_t n_matrices, size_t rows, size_t cols, const void *d_vectors, size_t k, void *d_out, void *stream) {
+    TRY(lsss_shares_args(d_matrix, n_matrices, rows, cols, d_vectors, k, d_out));
+    if (!k) return GPBC_OK;
+    TRY(bind_device());
+    const bool shared = n_matrices == 1 && k > 1;
+    const LsssSharesGeom g = fr_lsss_shares_geometry(rows, cols, shared);
+    const size_t mat_step = shared ? 0 : rows * cols * GPBC_SCALAR_BYTES;
+    return GPBC_LAUNCH(k_fr_lsss_shares, (unsigned)fr_lsss_shares_grid(g, k), BLOCK, (hipStream_t)stream, (const uint8_t *)d_matrix, mat_step, (const uint8_t *)d_vectors, k, g, (uint8_t *)d_out);
+}
+// Host-pointer form: the unit is a vector; a shard needs about 2^16 products to pay for its thread and transfers.  A matrix given once
+// travels whole to every shard.
+int gpbc_fr_lsss_shares(const void *matrix, size_t n_matrices, size_t rows, size_t cols, const void *vectors, size_t k, void *out) {
+    TRY(lsss_shares_args(matrix, n_matrices, rows, cols, vectors, k, out));
+    if (!k) return GPBC_OK;
+    const bool one = n_matrices == 1;
+    const size_t shard_min = ((size_t)1 << 16) / (rows * cols);
+    HostCall c = HostCall().input(matrix, rows * cols * GPBC_SCALAR_BYTES, one).input(vectors, cols * GPBC_SCALAR_BYTES);
+    return host_call_sharded(k, shard_min ? shard_min : 1, c.output(out, rows * GPBC_SCALAR_BYTES), HostRoute{},
+                             [=](const DevCols &d, size_t m, hipStream_t st) { return gpbc_fr_lsss_shares_dev(d.in[0], one ? 1 : m, rows, cols, d.in[1], m, d.out[0], st); });
 }
 
 }  // extern "C"

@@ -127,3 +127,85 @@ def decrypt_batch_msm(engine, folded, h_gid, c0, c1, c2, c3):
     E = engine.multi_pair(bufs.flat(P), bufs.flat(Q), np.arange(0, (k + 1) * n + 1, k + 1, dtype=np.uint64))
     F = engine.gt_multi_exp(bufs.flat(used(c1, 384)), weights, table)
     return engine.gt_div(bufs.flat(c0).reshape(n, 384), engine.gt_mul(E, F))
+
+
+# ------------------------------------------------------------------------------------------------ Encrypt
+INDEX_NONE = 0xFFFFFFFF
+
+
+def encrypt_table(engine, g2_y, g2=None):
+    """The G2 fixed-base table of encrypt_batch over (g2, g2^y_u ...), u in ascending order: built once, passed as `table` to any number
+    of calls, closed by the caller.  g2: the generator's 128 bytes (None: engine.generators()[1])."""
+    attrs = sorted(g2_y)
+    gen = np.asarray(engine.generators()[1] if g2 is None else g2, dtype=np.uint8).reshape(128)
+    return engine.FixedBase(np.stack([gen] + [np.asarray(g2_y[u], dtype=np.uint8).reshape(128) for u in attrs]), g2=True)
+
+
+def encrypt_batch(engine, e, egg_alpha, g2_y, matrix, rho, messages, s, v, w, r, table=None):
+    """n ciphertexts under one policy (Encrypt, dabe/lw11_dabe.go:100-174).  e = e(g1, g2) (384 B); egg_alpha: {attribute:
+    e(g1, g2)^alpha_u (384 B)} and g2_y: {attribute: g2^y_u (128 B)}, the authorities' public keys; (matrix, rho): the policy, R rows and
+    C columns; messages [n, 384]; s: n scalars; v, w: [n, C - 1] scalars, the rest of the share vectors (s, v_2, ..) and (0, w_2, ..);
+    r: [n, R] scalars.  Scalars are Python ints, uint8 arrays or CUDA tensors.
+
+    The shares are taken over every ROW of the matrix, lambda_x = M_x . (s, v) and omega_x = M_x . (0, w), as the scheme and
+    decrypt_batch have it; the reference's loop runs to ColumnNumber() (lw11_dabe.go:111,139), which covers every row only for a square
+    matrix.
+
+    Returns exactly the operands of decrypt_batch: (c0 [n, 384], c1 [n, R, 384], c2 [n, R, 128], c3 [n, R, 128]) with
+    c0 = M e^s, c1x = e^lambda_x (e^alpha_rho(x))^r_x, c2x = [r_x] g2, c3x = [r_x] g2^y_rho(x) + [omega_x] g2.  An attribute of rho
+    without a public key is a ValueError (the reference's attribute check).  table: encrypt_table(engine, g2_y) built once by the
+    caller; None builds and closes one here.  Engine calls: fr_lsss_shares twice (one matrix for the batch), gt_multi_exp over n R
+    segments of two factors, g2_scalar_mul_base, FixedBase.indexed (G2, terms = 2, the R index rows periodic), gt_exp, gt_mul."""
+    R, C = len(matrix), len(matrix[0]) if len(matrix) else 0
+    if not R or not C or len(rho) != R or any(len(row) != C for row in matrix):
+        raise ValueError("the policy needs R >= 1 rows of C >= 1 entries and one attribute per row")
+    attrs = sorted(g2_y)
+    where = {u: i for i, u in enumerate(attrs)}
+    for u in rho:
+        if u not in where or u not in egg_alpha:
+            raise ValueError("attribute %s is not in the universe" % (u,))
+    n = bufs.nbytes(messages) // 384
+    if bufs.nbytes(messages) != n * 384:
+        raise ValueError("messages must hold whole GT elements")
+
+    def scalars(x):
+        if x is None or bufs.is_torch(x) or isinstance(x, np.ndarray):
+            return x
+        flat = [y for row in x for y in (row if isinstance(row, (list, tuple)) else [row])]
+        return bufs.put(np.frombuffer(b"".join((int(y) % R_ORDER).to_bytes(32, "little") for y in flat), dtype=np.uint8).reshape(-1, 32).copy(), messages)
+    s, v, w, r = scalars(s), scalars(v), scalars(w), scalars(r)
+    bufs.device_of(messages, s, v, w, r)                                       # one kind of buffer, one device
+    size = lambda x: 0 if x is None else bufs.nbytes(x)
+    if size(s) != n * 32 or size(v) != n * (C - 1) * 32 or size(w) != n * (C - 1) * 32 or size(r) != n * R * 32:
+        raise ValueError("need s [n], v and w [n, C - 1], r [n, R] scalars with n = %d, R = %d, C = %d" % (n, R, C))
+    if not n:
+        z = lambda *shape: bufs.zeros(shape, messages)
+        return z(0, 384), z(0, R, 384), z(0, R, 128), z(0, R, 128)
+    put = lambda a: bufs.put(np.ascontiguousarray(a), messages)
+    s3 = bufs.view(s, n, 1, 32)
+    mat = put(np.frombuffer(b"".join((int(x) % R_ORDER).to_bytes(32, "little") for row in matrix for x in row), dtype=np.uint8).copy())
+    vec_s = s3 if C == 1 else bufs.cat([s3, bufs.view(v, n, C - 1, 32)], 1)
+    vec_0 = bufs.zeros((n, 1, 32), messages) if C == 1 else bufs.cat([bufs.zeros((n, 1, 32), messages), bufs.view(w, n, C - 1, 32)], 1)
+    lam = engine.fr_lsss_shares(mat, bufs.flat(vec_s), R, C)                   # [n, R, 32]
+    om = engine.fr_lsss_shares(mat, bufs.flat(vec_0), R, C)
+    r2 = bufs.view(r, n * R, 1, 32)
+    # c1x = e^lambda_x (e^alpha_rho(x))^r_x: one segment of two factors per (ciphertext, row)
+    pairs = np.stack([np.stack([np.asarray(e, dtype=np.uint8).reshape(384), np.asarray(egg_alpha[u], dtype=np.uint8).reshape(384)]) for u in rho])     # [R, 2, 384]
+    gt_bases = bufs.flat(bufs.expand(bufs.view(put(pairs), 1, 2 * R, 384), n, 2 * R, 384))
+    c1 = engine.gt_multi_exp(gt_bases, bufs.flat(bufs.cat([bufs.view(lam, n * R, 1, 32), r2], 1)), np.arange(0, 2 * n * R + 1, 2, dtype=np.uint64))
+    c2 = engine.g2_scalar_mul_base(bufs.flat(r))
+    # c3x = [r_x] g2^y_rho(x) + [omega_x] g2: base 0 is g2, base 1 + i the i-th public key; the R index rows repeat per ciphertext
+    index = np.array([[1 + where[u], 0] for u in rho], dtype=np.uint32)
+    index = bufs.put(index.view(np.int32), messages) if bufs.is_torch(messages) else index
+    own = table is None
+    table = encrypt_table(engine, g2_y) if own else table
+    try:
+        if table.nbase != 1 + len(attrs):
+            raise ValueError("the table holds %d bases, the public keys need %d" % (table.nbase, 1 + len(attrs)))
+        c3, ok = table.indexed(index, bufs.flat(bufs.cat([r2, bufs.view(om, n * R, 1, 32)], 1)), terms=2)
+    finally:
+        if own:
+            table.close()
+    eb = bufs.flat(bufs.expand(bufs.view(put(np.asarray(e, dtype=np.uint8).reshape(384)), 1, 384), n, 384))
+    c0 = engine.gt_mul(engine.gt_exp(eb, bufs.flat(s)), bufs.flat(messages))
+    return bufs.view(c0, n, 384), bufs.view(c1, n, R, 384), bufs.view(c2, n, R, 128), bufs.view(c3, n, R, 128)

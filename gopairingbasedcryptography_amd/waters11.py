@@ -173,3 +173,153 @@ def decrypt_batch_host_weights(engine, key, policies, c, c_prime, cx, dx):
                     w[t, x] = np.frombuffer(int(wx).to_bytes(32, "little"), dtype=np.uint8)
         return put(w), put(ok)
     return _decrypt(engine, key, pad, c, c_prime, cx, dx, weights)
+
+
+# ------------------------------------------------------------------------------------------------ Encrypt and KeyGenerate
+# cpabe/waters11/waters11_cpabe.go:82-237.  Every base of the two loops is a public parameter — g1^a and the h_u of the universe — so
+# they are sums over ONE fixed-base table (engine.FixedBase.indexed): base 0 is g1^a, base 1 + i the h of the i-th attribute in
+# ascending order.  The shares are engine.fr_lsss_shares on the padded matrices as decrypt_batch takes them.  The randomness is passed
+# in, as in bsw07.encrypt_batch.
+INDEX_NONE = 0xFFFFFFFF
+
+
+def _universe(h):
+    attrs = sorted(int(u) for u in h)
+    if any(a < 0 for a in attrs):
+        raise ValueError("attributes must be integers in [0, 2^63)")
+    return attrs
+
+
+def encrypt_table(engine, g1a, h):
+    """The fixed-base table of encrypt_batch and keygen_batch over (g1^a, h_u ...), h_u in ascending order of u: built once, passed
+    as `table` to any number of calls, closed by the caller (table.close())."""
+    attrs = _universe(h)
+    bases = np.stack([np.asarray(g1a, dtype=np.uint8).reshape(64)] + [np.asarray(h[u], dtype=np.uint8).reshape(64) for u in attrs])
+    return engine.FixedBase(bases, g2=False)
+
+
+def _attribute_positions(table_attrs, wanted, what):
+    """1 + position in the universe per wanted attribute (base 0 is g1^a); NO_ATTRIBUTE stays NO_ATTRIBUTE.  An attribute outside the
+    universe is the reference's checkAttributes error."""
+    univ = np.array(table_attrs, dtype=np.int64)
+    wanted = np.asarray(wanted, dtype=np.int64)
+    real = wanted != NO_ATTRIBUTE
+    if real.any() and not univ.size:
+        raise ValueError("%s: attribute %d is not in the universe" % (what, int(wanted[real][0])))
+    pos = np.minimum(np.searchsorted(univ, wanted), max(univ.size - 1, 0))
+    miss = real & (univ[pos] != wanted if univ.size else real)
+    if miss.any():
+        raise ValueError("%s: attribute %d is not in the universe" % (what, int(wanted[miss][0])))
+    return np.where(real, pos + 1, NO_ATTRIBUTE)
+
+
+def _index_rows(rows, like):
+    """an index table for FixedBase.indexed of the kind of `like`: uint32 on the host, the same bits as int32 on the device"""
+    idx = np.ascontiguousarray(np.where(rows < 0, INDEX_NONE, rows).astype(np.uint32))
+    return bufs.put(idx.view(np.int32), like) if bufs.is_torch(like) else idx
+
+
+def _scalars(v, like):
+    if bufs.is_torch(v) or isinstance(v, np.ndarray):
+        return v
+    flat = [x for row in v for x in (row if isinstance(row, (list, tuple)) else [row])]
+    return bufs.put(np.frombuffer(b"".join((int(x) % R_ORDER).to_bytes(32, "little") for x in flat), dtype=np.uint8).reshape(-1, 32).copy(), like)
+
+
+def _public(x, width, what, like):
+    if bufs.is_torch(x):
+        x = x.cpu().numpy()
+    x = np.array(x, dtype=np.uint8, copy=True).reshape(-1)
+    if x.size != width:
+        raise ValueError("%s must be %d bytes" % (what, width))
+    return bufs.put(x, like)
+
+
+def encrypt_batch(engine, g1a, e_alpha, h, policies_or_padded, messages, s, v, r, table=None):
+    """n ciphertexts, each under a policy of its own (Encrypt, waters11_cpabe.go:170-237).  g1a = g1^a (64 B) and e_alpha =
+    e(g1, g2)^alpha (384 B) of the public key; h: {attribute: 64-byte G1 point}, the universe; policies_or_padded: n (matrix, rho) pairs
+    or pad_policies' block [n, R, C]; messages [n, 384]; s: n scalars; v: [n, C - 1] scalars, the rest of the share vector (s, v_2, ..);
+    r: [n, R] scalars, r_x of every row.  Scalars are Python ints, uint8 arrays or CUDA tensors.
+
+    The shares are taken over every ROW of the matrix, lambda_x = M_x . (s, v), as the scheme and decrypt_batch have it; the reference's
+    loop runs to ColumnNumber() (waters11_cpabe.go:182,211), which covers every row only for a square matrix.
+
+    Returns exactly the operands of decrypt_batch: (c [n, 384], c_prime [n, 128], cx [n, R, 64], dx [n, R, 128]) with
+    C_x = [lambda_x] g1^a + [-r_x] h_rho(x), D_x = [r_x] g2, C' = [s] g2, C = M e(g1, g2)^(alpha s).  A padding row (zero matrix row,
+    attribute -1) gets the index (0, none), so its C_x is the point at infinity; its D_x is [r_x] g2 like any other.  An attribute of a
+    policy that is not in h is a ValueError (checkAttributes).  table: encrypt_table(engine, g1a, h) built once by the caller; None
+    builds and closes one here.  Engine calls: fr_lsss_shares (a matrix per ciphertext), fr_neg, FixedBase.indexed (terms = 2, an index
+    row per output), g2_scalar_mul_base twice, gt_exp, gt_mul."""
+    pad = policies_or_padded if isinstance(policies_or_padded, Padded) else pad_policies(policies_or_padded)
+    n, R = pad.rho.shape
+    C = pad.cols
+    attrs = _universe(h)
+    pos = _attribute_positions(attrs, pad.rho, "policy")                      # before anything touches the engine
+    if bufs.nbytes(messages) != n * 384:
+        raise ValueError("messages must hold n = %d GT elements" % n)
+    s, v, r = _scalars(s, messages), (None if v is None else _scalars(v, messages)), _scalars(r, messages)
+    bufs.device_of(messages, s, v, r)                                          # all of one kind, on one device
+    if bufs.nbytes(s) != n * 32 or (bufs.nbytes(v) if v is not None else 0) != n * (C - 1) * 32 or bufs.nbytes(r) != n * R * 32:
+        raise ValueError("need s [n], v [n, C - 1], r [n, R] scalars with n = %d, R = %d, C = %d" % (n, R, C))
+    if not n:
+        return bufs.zeros((0, 384), messages), bufs.zeros((0, 128), messages), bufs.zeros((0, R, 64), messages), bufs.zeros((0, R, 128), messages)
+    s, r = bufs.view(s, n, 1, 32), bufs.view(r, n * R, 1, 32)
+    vec = s if C == 1 else bufs.cat([s, bufs.view(v, n, C - 1, 32)], 1)
+    lam = engine.fr_lsss_shares(bufs.flat(bufs.put(pad.matrix, messages)), bufs.flat(vec), pad.rows, pad.cols)        # [n, R, 32]
+    nr = engine.fr_neg(bufs.flat(r))
+    index = np.stack([np.zeros(n * R, dtype=np.int64), pos.reshape(-1)], 1)                                           # (g1^a, h_rho(x)); padding: (g1^a, none)
+    own = table is None
+    table = encrypt_table(engine, g1a, h) if own else table
+    try:
+        if table.nbase != 1 + len(attrs):
+            raise ValueError("the table holds %d bases, the universe needs %d" % (table.nbase, 1 + len(attrs)))
+        scal = bufs.cat([bufs.view(lam, n * R, 1, 32), bufs.view(nr, n * R, 1, 32)], 1)
+        cx, ok = table.indexed(_index_rows(index, messages), bufs.flat(scal), terms=2)
+    finally:
+        if own:
+            table.close()
+    dx = engine.g2_scalar_mul_base(bufs.flat(r))
+    c_prime = engine.g2_scalar_mul_base(bufs.flat(s))
+    base = bufs.flat(bufs.expand(bufs.view(_public(e_alpha, 384, "e_alpha", messages), 1, 384), n, 384))
+    c = engine.gt_mul(engine.gt_exp(base, bufs.flat(s)), bufs.flat(messages))
+    return bufs.view(c, n, 384), bufs.view(c_prime, n, 128), bufs.view(cx, n, R, 64), bufs.view(dx, n, R, 128)
+
+
+def keygen_batch(engine, g1_alpha, g1a, h, user_attrs, t, table=None):
+    """Keys of n users (KeyGenerate, waters11_cpabe.go:130-168): K = g1^alpha + [t] g1^a, L = [t] g2, K_x = [t] h_x for the user's
+    attributes.  g1_alpha = g1^alpha (64 B, the master key), g1a and h as in encrypt_batch; user_attrs: n lists of attributes, each
+    within the universe (ValueError otherwise: checkAttributes) and without repeats; t: n scalars.  Returns (K [n, 64], L [n, 128],
+    kx [n, A, 64], attrs [n, A] int64) with A the largest attribute count: a user's attributes in ascending order, then NO_ATTRIBUTE
+    with the point at infinity.  (K[j], L[j], {attrs[j][i]: kx[j][i]}) is the key decrypt_batch takes.  Engine calls:
+    FixedBase.indexed (terms = 1, 1 + A outputs per user), g1_add, g2_scalar_mul_base."""
+    attrs = _universe(h)
+    users = [sorted(int(a) for a in ua) for ua in user_attrs]
+    n = len(users)
+    if any(len(set(u)) != len(u) for u in users):
+        raise ValueError("a user's attributes must be distinct")
+    A = max([len(u) for u in users] + [1])
+    held = np.full((n, A), NO_ATTRIBUTE, dtype=np.int64)
+    for j, u in enumerate(users):
+        held[j, :len(u)] = u
+    pos = _attribute_positions(attrs, held, "user")
+    like = t if bufs.is_torch(t) else np.zeros(0, dtype=np.uint8)
+    t = _scalars(t, like)
+    if bufs.nbytes(t) != n * 32:
+        raise ValueError("t must hold n = %d scalars" % n)
+    if not n:
+        return bufs.zeros((0, 64), t), bufs.zeros((0, 128), t), bufs.zeros((0, A, 64), t), held
+    t = bufs.view(t, n, 1, 32)
+    index = np.concatenate([np.zeros((n, 1), dtype=np.int64), pos], 1).reshape(-1, 1)                                 # [t] g1^a, then [t] h_x
+    own = table is None
+    table = encrypt_table(engine, g1a, h) if own else table
+    try:
+        if table.nbase != 1 + len(attrs):
+            raise ValueError("the table holds %d bases, the universe needs %d" % (table.nbase, 1 + len(attrs)))
+        pts, ok = table.indexed(_index_rows(index, t), bufs.flat(bufs.expand(t, n, 1 + A, 32)), terms=1)
+    finally:
+        if own:
+            table.close()
+    pts = bufs.view(pts, n, 1 + A, 64)
+    K = engine.g1_add(bufs.flat(bufs.expand(bufs.view(_public(g1_alpha, 64, "g1_alpha", t), 1, 64), n, 64)), bufs.flat(pts[:, 0]))
+    L = engine.g2_scalar_mul_base(bufs.flat(t))
+    return bufs.view(K, n, 64), bufs.view(L, n, 128), pts[:, 1:], held

@@ -16,6 +16,7 @@ package gpbcbn254
 #include "gpbc_bn254.h"
 #include "gpbc_bn254_hash.h"
 #include "gpbc_bn254_share.h"
+#include "gpbc_bn254_indexed.h"
 */
 import "C"
 
@@ -663,6 +664,40 @@ func FrLsssWeights(matrix []fr.Element, rows, cols int, held []byte) ([]fr.Eleme
 	}
 	out := make([]fr.Element, len(kw))
 	return out, ok, frElements(kw, out)
+}
+
+// FrLsssShares: the shares lambda_x = M_x . v of LewkoWatersLsssMatrix.ComputeVector for k vectors in one launch
+// (include/gpbc_bn254_indexed.h): matrix holds one rows x cols matrix (shared by the k vectors) or k of them, vectors k x cols
+// elements.  Returns k x rows elements.
+func FrLsssShares(matrix []fr.Element, rows, cols int, vectors []fr.Element) ([]fr.Element, error) {
+	defer pin()()
+	if rows < 1 || cols < 1 || len(matrix) == 0 || len(matrix)%(rows*cols) != 0 || len(vectors)%cols != 0 {
+		return nil, errSizes
+	}
+	nm := len(matrix) / (rows * cols)
+	k := len(vectors) / cols
+	if k == 0 {
+		return nil, nil
+	}
+	if nm != 1 && nm != k {
+		return nil, errSizes
+	}
+	km, err := frPlain(matrix)
+	if err != nil {
+		return nil, err
+	}
+	kv, err := frPlain(vectors)
+	if err != nil {
+		return nil, err
+	}
+	ko := make([][32]byte, k*rows)
+	rc := C.gpbc_fr_lsss_shares(unsafe.Pointer(unsafe.SliceData(km)), C.size_t(nm), C.size_t(rows), C.size_t(cols), unsafe.Pointer(unsafe.SliceData(kv)), C.size_t(k),
+		unsafe.Pointer(unsafe.SliceData(ko)))
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	out := make([]fr.Element, len(ko))
+	return out, frElements(ko, out)
 }
 
 // g1GroupOp: Add (sub == false) or Sub over the batch (cgo cannot take a C function as a value, hence the flag)

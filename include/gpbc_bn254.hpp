@@ -25,6 +25,7 @@
 #include "gpbc_bn254.h"
 #include "gpbc_bn254_hash.h"
 #include "gpbc_bn254_share.h"
+#include "gpbc_bn254_indexed.h"
 
 namespace bn254 {
 
@@ -382,11 +383,31 @@ public:
         check(gpbc_fixed_base_msm(h_, scalars.data(), out.size(), out.data()));
         return out;
     }
+    // out[i] = sum_{t < terms} [scalars[i * terms + t]] base[index[(i % rows) * terms + t]] (include/gpbc_bn254_indexed.h): index holds
+    // rows x terms entries, rows == the number of outputs or fewer (periodic); GPBC_INDEX_NONE = no term; ok[i] = 0 and an all-zero point
+    // where an index names no base
+    std::vector<G1Affine> Indexed(const std::vector<uint32_t> &index, size_t terms, const std::vector<Scalar> &scalars, std::vector<uint8_t> &ok) const {
+        if (terms < 1 || index.empty() || index.size() % terms || scalars.size() % terms) throw std::invalid_argument("need whole rows of `terms` indices and scalars");
+        std::vector<G1Affine> out(scalars.size() / terms);
+        ok.assign(out.size(), 0);
+        check(gpbc_fixed_base_indexed(h_, index.data(), index.size() / terms, terms, scalars.data(), out.size(), out.data(), ok.data()));
+        return out;
+    }
     size_t NBases() const { return n_; }
 private:
     gpbc_fixed_base *h_ = nullptr;
     size_t n_;
 };
+// LSSS shares lambda_x = M_x . v for k vectors (LewkoWatersLsssMatrix.ComputeVector per item): matrix holds one rows x cols matrix or k of
+// them, vectors k x cols scalars.  Returns k x rows canonical scalars.
+inline std::vector<Scalar> FrLsssShares(const std::vector<Scalar> &matrix, size_t rows, size_t cols, const std::vector<Scalar> &vectors) {
+    if (rows < 1 || cols < 1 || matrix.empty() || matrix.size() % (rows * cols) || vectors.size() % cols) throw std::invalid_argument("need rows x cols scalars per matrix, cols per vector");
+    const size_t nm = matrix.size() / (rows * cols), k = vectors.size() / cols;
+    if (k && nm != 1 && nm != k) throw std::invalid_argument("need one matrix or one per vector");
+    std::vector<Scalar> out(k * rows);
+    check(gpbc_fr_lsss_shares(matrix.data(), nm, rows, cols, vectors.data(), k, out.data()));
+    return out;
+}
 static_assert(sizeof(Scalar) == GPBC_SCALAR_BYTES, "scalar layout");
 
 }  // namespace bn254

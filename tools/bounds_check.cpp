@@ -24,6 +24,8 @@
 #include "../gopairingbasedcryptography_amd/csrc/subset29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/transcript29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/share29.hip.hpp"
+#include "../gopairingbasedcryptography_amd/csrc/lsss29.hip.hpp"
+#include "../gopairingbasedcryptography_amd/csrc/fbindex29.hip.hpp"
 #include <condition_variable>
 #include <mutex>
 #include <thread>
@@ -962,6 +964,100 @@ int hc_fr_share_tree(const uint32_t *nodes, size_t n_nodes, const uint8_t *secre
     if (geom_out) { geom_out[0] = g.L; geom_out[1] = g.G; geom_out[2] = g.C; geom_out[3] = g.depth; geom_out[4] = g.ipb; geom_out[5] = g.large; geom_out[6] = (uint32_t)grid; }
     stats_flush();
     return 0;
+}
+// k_fr_lsss_shares as it is launched: geometry, staging of the one matrix's row group and lane mapping of lsss29.hip.hpp, workgroup by
+// workgroup.  geom_out: [rg, nrg, ipb, pitch, workgroups, active lanes].  -1: arguments the entry refuses; -2: a refusal of the LDS
+// stand-in or a lane outside the outputs.
+int hc_fr_lsss_shares(const uint8_t *matrix, size_t n_matrices, size_t rows, size_t cols, const uint8_t *vectors, size_t k, uint8_t *out, uint32_t *geom_out) {
+    if (rows < 1 || rows > (size_t)FR_LSSS_MAX || cols < 1 || cols > (size_t)FR_LSSS_MAX || !k || (n_matrices != 1 && n_matrices != k) || !matrix || !vectors || !out) return -1;
+    const bool shared = n_matrices == 1 && k > 1;
+    const LsssSharesGeom g = fr_lsss_shares_geometry(rows, cols, shared);
+    const size_t mat_step = shared ? 0 : rows * cols * 32, grid = fr_lsss_shares_grid(g, k);
+    CheckedLds lds((size_t)FR_SHARES_CAP * NL + FR_LSSS_SHARES_WAVE);
+    uint32_t active = 0;
+    for (size_t block = 0; block < grid; block++) {
+        lds.reset();
+        if (!mat_step)
+            for (uint32_t lane = 0; lane < FR_LSSS_SHARES_WAVE; lane++) fr_lsss_shares_stage(g, (uint32_t)block, lane, matrix, [&](uint32_t off, const Fr &v) { lds.put(off, v); });
+        for (uint32_t lane = 0; lane < FR_LSSS_SHARES_WAVE && !lds.bad; lane++) {
+            const LsssSharesLane l = fr_lsss_shares_map(g, (uint32_t)block, lane, k);
+            if (!l.active) continue;
+            if (l.item >= k || l.x >= rows) return -2;
+            active++;
+            const uint8_t *vec = vectors + l.item * cols * 32, *row = matrix + l.item * mat_step + (size_t)l.x * cols * 32;
+            uint8_t *o = out + (l.item * rows + l.x) * 32;
+            if (mat_step) fr_lsss_shares_lane([&](uint32_t c) { return fr_load_raw(row + 32 * (size_t)c); }, g.cols, vec, o);
+            else fr_lsss_shares_lane([&](uint32_t c) { return lds.get(l.xr * g.pitch + c * NL); }, g.cols, vec, o);
+        }
+        if (lds.bad) return -2;
+    }
+    if (geom_out) { geom_out[0] = g.rg; geom_out[1] = g.nrg; geom_out[2] = g.ipb; geom_out[3] = g.pitch; geom_out[4] = (uint32_t)grid; geom_out[5] = active; }
+    stats_flush();
+    return 0;
+}
+}  // extern "C"
+// k_g1_fb_indexed / k_g2_fb_indexed as they are launched: the window tables of the bases (only the rows the scalars reach are built, by
+// the scalar multiplication k_g1/g2_fb_build uses), then fb_index_map / fb_index_output / fb_indexed_lane for every lane of every
+// workgroup.  group_min: as GPBC_FBINDEX_GROUP_MIN of the build (0 = its default 64).  geom_out: [grouped, workgroups, lanes with an
+// output].  -1: arguments the entry refuses; -2: a lane outside the outputs or an output owned twice.
+template <class F, class LoadA, class StoreA> static int fb_indexed_host(const uint8_t *B, size_t nbase, const uint32_t *index, size_t n_index_rows, size_t terms, const uint8_t *K, size_t n,
+                                                                          size_t group_min, uint8_t *out, uint8_t *ok_out, uint32_t *geom_out, size_t pt, LoadA ld, StoreA st) {
+    constexpr size_t ED = (size_t)TabLayout<F>::ENTRY_DWORDS;
+    std::vector<int32_t> mem(nbase * (size_t)FBI_ENTRIES * ED + 32);
+    int32_t *table = mem.data();
+    while ((uintptr_t)table & 127) table++;                // rows 128-byte aligned like the device's
+    std::vector<uint8_t> inf(nbase), built(nbase * (size_t)FBI_ENTRIES, 0);
+    std::vector<AffP<F>> bases(nbase);
+    for (size_t b = 0; b < nbase; b++) { bases[b] = ld(B + pt * b); inf[b] = bases[b].inf ? 1 : 0; }
+    for (size_t i = 0; i < n; i++)
+        for (size_t t = 0; t < terms; t++) {
+            const uint32_t j = index[(i % n_index_rows) * terms + t];
+            if (j == FBI_NONE || j >= nbase || inf[j]) continue;
+            uint32_t k[8]; memcpy(k, K + 32 * (i * terms + t), 32);
+            for (int w = 0; w < FBI_WINDOWS; w++) {
+                const int d = (int)((k[w >> 2] >> (8 * (w & 3))) & 255u);
+                const size_t e = ((size_t)j * FBI_WINDOWS + w) * FBI_DIGITS + d - 1;
+                if (!d || built[e]) continue;
+                uint32_t kk[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+                kk[w >> 2] = (uint32_t)d << (8 * (w & 3));
+                alignas(16) int32_t tab[glv_table_dwords<F>()];
+                JacP<F> r; scalar_mul29_best(r, bases[j], kk, tab);
+                AffP<F> a; jac_to_affine(a, r);
+                tab_store(table + e * ED, 0, a);
+                built[e] = 1;
+            }
+        }
+    const FbIndexMap map = fb_index_map(n, n_index_rows, group_min ? group_min : 64);
+    const size_t grid = fb_index_grid(map);
+    std::vector<uint8_t> seen(n, 0);
+    uint32_t lanes = 0;
+    for (size_t block = 0; block < grid; block++)
+        for (uint32_t lane = 0; lane < FBI_WAVE; lane++) {
+            const size_t i = fb_index_output(map, block, lane);
+            if (i == n) continue;
+            if (i > n || seen[i]) return -2;
+            seen[i] = 1; lanes++;
+            fb_indexed_lane<F>(table, inf.data(), nbase, index + (i % map.P) * terms, (uint32_t)terms, K + 32 * i * terms, out + pt * i, ok_out ? ok_out + i : nullptr,
+                               [](uint32_t *k, const uint8_t *p) { memcpy(k, p, 32); }, st);
+        }
+    if (geom_out) { geom_out[0] = map.grouped; geom_out[1] = (uint32_t)grid; geom_out[2] = lanes; }
+    return lanes == n ? 0 : -2;
+}
+extern "C" {
+int hc_fb_indexed(int is_g2, const uint8_t *B, size_t nbase, const uint32_t *index, size_t n_index_rows, size_t terms, const uint8_t *K, size_t n, size_t group_min, uint8_t *out,
+                  uint8_t *ok_out, uint32_t *geom_out) {
+    if (terms < 1 || terms > FBI_MAX_TERMS || !n || n_index_rows < 1 || n_index_rows > n || !nbase || !B || !index || !K || !out) return -1;
+    int rc;
+    if (is_g2)
+        rc = fb_indexed_host<F2>(B, nbase, index, n_index_rows, terms, K, n, group_min, out, ok_out, geom_out, 128,
+                                 [](const uint8_t *p) { return AffP<F2>{f2_load(p), f2_load(p + 64), bytes_all_zero(p, 32)}; },
+                                 [](uint8_t *p, const AffP<F2> &r) { f2_store(p, r.x); f2_store(p + 64, r.y); });
+    else
+        rc = fb_indexed_host<Fe>(B, nbase, index, n_index_rows, terms, K, n, group_min, out, ok_out, geom_out, 64,
+                                 [](const uint8_t *p) { return AffP<Fe>{fe_load(p), fe_load(p + 32), bytes_all_zero(p, 16)}; },
+                                 [](uint8_t *p, const AffP<Fe> &r) { fe_store(p, r.x); fe_store(p + 32, r.y); });
+    stats_flush();
+    return rc;
 }
 // worst-case figures since process start: [max |int64 column|, max limb bound, max value bound (units of p),
 // #products (fe_mul + fe_mul2), #norms, #fe_mul2, #reduces]  (out must hold 7 doubles)
