@@ -89,6 +89,11 @@ INDEXED_SIGNATURES = {
     "gpbc_indexed_version": "i:", "gpbc_fixed_base_indexed": "i:ppzzpzpp", "gpbc_fixed_base_indexed_dev": "i:ppzzpzppp",
     "gpbc_fr_lsss_shares": "i:pzzzpzp", "gpbc_fr_lsss_shares_dev": "i:pzzzpzpp",
 }
+# ... and for include/gpbc_bn254_recon.h, the reconstruction weights of a threshold tree (tests/test_fr_tree_weights.py holds this table
+# against that header).  The seven tables are disjoint.
+RECON_SIGNATURES = {
+    "gpbc_recon_version": "i:", "gpbc_fr_tree_weights": "i:ppzpp", "gpbc_fr_tree_weights_dev": "i:ppzppp",
+}
 # every pointer is a c_void_p: it takes ints, None, c_void_p, ctypes arrays, byref() and ndarray.ctypes.data_as() alike
 _CTYPES = {"p": ctypes.c_void_p, "z": ctypes.c_size_t, "i": ctypes.c_int, "l": ctypes.c_long, "s": ctypes.c_char_p}
 
@@ -114,7 +119,7 @@ def load():
         except ImportError:
             pass
         lib = ctypes.CDLL(LIB_PATH)
-        for name, sig in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(SUBSET_SIGNATURES.items()) + list(HASH_SIGNATURES.items()) + list(SHARE_SIGNATURES.items()) + list(INDEXED_SIGNATURES.items()):
+        for name, sig in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(SUBSET_SIGNATURES.items()) + list(HASH_SIGNATURES.items()) + list(SHARE_SIGNATURES.items()) + list(INDEXED_SIGNATURES.items()) + list(RECON_SIGNATURES.items()):
             ret, params = sig.split(":")
             fn = getattr(lib, name)
             fn.restype = _CTYPES[ret]

@@ -652,6 +652,7 @@ class ShareTree:
                                                  # threshold 0 = a leaf (bsw07.share_plan makes the list from a Leaf / Threshold tree)
         t.leaves, t.coeffs                       # L shares and C = sum of (threshold - 1) coefficients per item
         out = t.share(secrets, coeffs)           # secrets: k scalars, coeffs: [k, C] scalars (None when C == 0) -> [k, L, 32], leaf order
+        w, ok = t.weights(held)                  # held: [k, L] bytes, non-zero = leaf held -> weights [k, L, 32] with sum w * share = secret, ok [k]
 
     Scalars are Python ints, uint8 arrays or CUDA tensors; CUDA tensors give a CUDA tensor enqueued on the current stream and not
     synchronised.  A malformed tree and every argument error are ValueError before the device is touched."""
@@ -699,6 +700,39 @@ class ShareTree:
                 raise ValueError("out overlaps an input")
             _call("fr_share_tree", dev, self._h, s, c, k, out)
         return out
+
+    def weights(self, held, out=None, ok_out=None):
+        """(w [k, L, 32], ok [k]): the reconstruction weights of k attribute sets — AccessTreeNode.DecryptNode with the Lagrange
+        coefficients multiplied down each leaf's path (include/gpbc_bn254_recon.h).  held: k x L bytes in leaf order, non-zero = the item
+        holds the leaf's attribute (nested bools / ints, a uint8 or bool array, bytes, or a CUDA tensor).  A gate uses its first `threshold`
+        satisfied children; every leaf that is not used gets 0; ok = 0 and a zero row where the root is not satisfied.  For ok = 1,
+        sum_y w[y] share[y] is the secret for every output of share().  Outputs are of the kind that went in."""
+        L = self.leaves
+        if isinstance(held, np.ndarray):
+            if held.dtype not in (np.uint8, np.bool_):
+                raise ValueError("held must be uint8 or bool (got %s)" % held.dtype)
+            held = held.astype(np.uint8, copy=False)
+        elif not bufs.is_torch(held) and not isinstance(held, (bytes, bytearray)):
+            hrows = [list(h) for h in held]
+            if any(len(h) != L for h in hrows):
+                raise ValueError("held: every item needs %d entries" % L)
+            held = np.array([1 if v else 0 for h in hrows for v in h], dtype=np.uint8)
+        hb, nheld = bufs.rows(held, 1, "held")
+        if nheld % L:
+            raise ValueError("held holds %d bytes, not whole items of %d leaves" % (nheld, L))
+        k = nheld // L
+        dev = bufs.device_of(hb, out, ok_out)
+        if k > (1 << 29) - 1:
+            raise ValueError("too many items for one call (%d)" % k)
+        out = bufs.output(out, (k, L, SCALAR_BYTES), dev)
+        ok_out = bufs.output(ok_out, (k,), dev, "ok_out")
+        if k:
+            if _overlaps(out, hb, ok_out) or _overlaps(ok_out, hb):
+                raise ValueError("an output overlaps the input or the other output")
+            if not self._h:
+                raise ValueError("the tree is closed")
+            _call("fr_tree_weights", dev, self._h, hb, k, out, ok_out)
+        return out, ok_out
 
     def close(self):
         if self._h:

@@ -223,3 +223,116 @@ def _scalar_bytes(values, what):
     """Python ints (a list, or a list of rows) as scalar rows modulo r"""
     flat = [v for row in values for v in (row if isinstance(row, (list, tuple)) else [row])]
     return np.frombuffer(b"".join((int(v) % R_ORDER).to_bytes(32, "little") for v in flat), dtype=np.uint8).reshape(-1, 32).copy()
+
+
+# ------------------------------------------------------------------------------------------------ Decrypt, one key per item
+# One policy, n users with attribute sets of their own: what decrypt_plan + fold_key do per key on the host — the walk of
+# AccessTreeNode.DecryptNode and the Lagrange coefficients down every path — is engine.ShareTree.weights for the whole batch (one launch),
+# and the coefficients are folded into the ciphertext's G1 components instead of the key's G2 components (half the cost; exact in Fp12
+# all the same, SURVEY §8a-3).
+def leaf_mask(tree_or_plan, attribute_sets):
+    """[n, L] uint8: 1 where set t holds the attribute of leaf y, the leaves in leaf-id order (column y - 1 for leaf id y) — the `held`
+    of decrypt_batch_keys and of engine.ShareTree.weights.  An attribute that sits on several leaves marks all of them."""
+    _, attributes = share_plan(tree_or_plan) if isinstance(tree_or_plan, (Leaf, Threshold)) else tree_or_plan
+    sets = [s if isinstance(s, (set, frozenset)) else set(s) for s in attribute_sets]
+    out = np.zeros((len(sets), len(attributes)), dtype=np.uint8)
+    for t, s in enumerate(sets):
+        out[t] = [a in s for a in attributes]
+    return out
+
+
+def leaf_rows(held, L):
+    """nested 0 / 1 / bool values as [n][L] of 0 / 1"""
+    rows = [list(h) for h in held]
+    if any(len(h) != L for h in rows):
+        raise ValueError("held: every item needs %d entries" % L)
+    return [[1 if v else 0 for v in h] for h in rows] if rows else np.zeros((0, L), dtype=np.uint8)
+
+
+def used_columns(used):
+    """(index [n, U] int64, mask [n, U] uint8, U) of a [n, L] array that is non-zero where item t uses leaf y: the used columns of
+    every item in ascending order, U = the largest count; the slots behind an item's last used column have mask 0 (and index 0)."""
+    used = np.asarray(used) != 0
+    n, L = used.shape
+    count = used.sum(1)
+    U = int(count.max()) if n else 0
+    order = np.argsort(~used, axis=1, kind="stable")[:, :U]                          # the used columns first, each group in ascending order
+    mask = (np.arange(U)[None, :] < count[:, None])
+    return np.where(mask, order, 0).astype(np.int64), mask.astype(np.uint8), U
+
+
+def decrypt_batch_keys(engine, tree_or_plan, held, d_key, dj, dj_prime, c_tilde, c, cy, cy_prime):
+    """n (key, ciphertext) items under one policy.  tree_or_plan: a Leaf / Threshold tree or share_plan(tree); held [n, L]: non-zero
+    where item t's key holds the attribute of leaf y (leaf_mask: a uint8 or bool array, nested values, or a uint8 CUDA tensor); d_key: D as [128] (one key against n ciphertexts) or [n, 128];
+    dj, dj_prime [n, L, 128]: the key components of leaf y's attribute in leaf order — the rows of leaves that are not used, those
+    with held = 0 among them, may hold anything: they never reach the engine, whose lists carry the all-zero encoding (the point at
+    infinity) in their place; c_tilde [n, 384], c [n, 64], cy, cy_prime [n, L, 64]: the outputs of encrypt_batch, or one ciphertext
+    repeated.  numpy in gives numpy out, CUDA tensors give tensors.  Returns (messages [n, 384], ok [n]): an item whose attributes do
+    not satisfy the policy has ok = 0 and an all-zero row and takes no part in the group operations.
+
+    Engine calls: ShareTree.weights (w), fr_neg (-w), one g1_scalar_mul ([w_y] Cy, [-w_y] Cy'), one multi_pair over uniform segments
+    [[w] Cy ..., [-w] Cy' ..., C] against [Dj ..., Dj' ..., -D], one gt_mul with c_tilde.  Only used leaves cost Miller loops: the used
+    columns of every item are gathered in leaf order up to U, the largest used count of the batch, so a segment is 2 U + 1 pairs and not
+    2 L + 1; an item with fewer used leaves is padded with points at infinity, which Pair skips.  Which leaves are used comes back
+    from the device once (n L bytes): the one point where the call waits for the stream."""
+    nodes, attributes = share_plan(tree_or_plan) if isinstance(tree_or_plan, (Leaf, Threshold)) else tree_or_plan
+    L = len(attributes)
+    if isinstance(held, np.ndarray):                                                 # as ShareTree.weights takes it: uint8 or bool
+        if held.dtype not in (np.uint8, np.bool_):
+            raise ValueError("held must be uint8 or bool (got %s)" % held.dtype)
+        held = held.astype(np.uint8, copy=False)
+    elif not bufs.is_torch(held):
+        held = np.asarray(leaf_rows(held, L), dtype=np.uint8)
+    n = bufs.nbytes(c) // 64
+    one_key = bufs.nbytes(d_key) == 128                                              # a public-size value: it goes through the host like h of encrypt_batch
+    bufs.device_of(held, dj, dj_prime, c_tilde, c, cy, cy_prime, *([] if one_key else [d_key]))     # all of one kind, on one device
+    if (bufs.nbytes(c) != n * 64 or bufs.nbytes(c_tilde) != n * 384 or bufs.nbytes(cy) != n * L * 64 or bufs.nbytes(cy_prime) != n * L * 64
+            or bufs.nbytes(dj) != n * L * 128 or bufs.nbytes(dj_prime) != n * L * 128 or bufs.nbytes(held) != n * L or bufs.nbytes(d_key) not in (128, n * 128)):
+        raise ValueError("need held [n, L], d_key [128] or [n, 128], dj and dj_prime [n, L, 128], c_tilde [n, 384], c [n, 64], cy and cy_prime [n, L, 64] with n = %d, L = %d" % (n, L))
+
+    def put(a):
+        return bufs.put(a, c)
+
+    def host(a):
+        return a.cpu().numpy() if bufs.is_torch(a) else np.asarray(a)
+    if not n:
+        return bufs.zeros((0, 384), c), bufs.zeros((0,), c)
+    tree = engine.ShareTree(nodes)
+    try:
+        if tree.leaves != L:
+            raise ValueError("the plan names %d attributes for %d leaves" % (L, tree.leaves))
+        w, ok = tree.weights(bufs.flat(bufs.view(held, n * L)))                      # [n, L, 32] canonical, [n]
+    finally:
+        tree.close()
+    w = bufs.view(w, n * L, 32)
+    ok_host = host(ok).reshape(n)
+    good = np.nonzero(ok_host)[0]
+    ng = len(good)
+    out = bufs.zeros((n, 384), c)
+    if not ng:
+        return out, bufs.view(ok, n)
+    used = host(bufs.rows_nonzero(w)).reshape(n, L)[good]                            # a factor is never 0 modulo r: used <=> weight != 0
+    index, mask, U = used_columns(used)
+    flat_index = (good[:, None] * L + index).reshape(-1)
+    keep = put(mask.reshape(-1, 1))
+
+    def gather(a, width):
+        """the used columns of the satisfied items, [ng, U, width]; the padding slots all zero"""
+        return (bufs.take(bufs.view(a, n * L, width), flat_index) * keep).reshape(ng, U, width)
+    wg = gather(w, 32)
+    scalars = bufs.cat([wg, bufs.view(engine.fr_neg(bufs.flat(wg)), ng, U, 32)], 1)
+    bases = bufs.cat([gather(cy, 64), gather(cy_prime, 64)], 1)
+    folded = bufs.view(engine.g1_scalar_mul(bufs.flat(bases), bufs.flat(scalars)), ng, 2 * U, 64)
+    if one_key:
+        d_host = host(d_key).reshape(128)
+        neg_d = bufs.expand(bufs.view(put(np.array(engine.g2_neg(d_host), dtype=np.uint8, copy=True)), 1, 1, 128), ng, 1, 128)
+    else:
+        d_rows = bufs.take(bufs.view(d_key, n, 128), good)
+        neg_d = bufs.view(engine.g2_sub(bufs.flat(bufs.zeros((ng, 128), c)), bufs.flat(d_rows)), ng, 1, 128)      # infinity - D
+    P = bufs.cat([folded, bufs.take(bufs.view(c, n, 64), good).reshape(ng, 1, 64)], 1)
+    Q = bufs.cat([gather(dj, 128), gather(dj_prime, 128), neg_d], 1)
+    m = 2 * U + 1
+    X = engine.multi_pair(bufs.flat(P), bufs.flat(Q), np.arange(0, ng * m + 1, m, dtype=np.uint64))
+    msgs = engine.gt_mul(bufs.flat(bufs.take(bufs.view(c_tilde, n, 384), good)), bufs.flat(X))
+    out[put(good)] = bufs.view(msgs, ng, 384)
+    return out, bufs.view(ok, n)

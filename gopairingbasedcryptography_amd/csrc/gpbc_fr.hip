@@ -3,13 +3,16 @@
 // proofs, the Lagrange basis over a node set per row (SW05 fuzzy IBE) and the LSSS reconstruction weights of a policy per
 // ciphertext (Waters11 CP-ABE) — with their C-ABI entries (include/gpbc_bn254.h, "scalar field"), and secret sharing (csrc/share29.hip.hpp):
 // polynomial evaluation and the shares of a threshold tree (include/gpbc_bn254_share.h), and LSSS share generation (csrc/lsss29.hip.hpp,
-// include/gpbc_bn254_indexed.h).  gfx950 only.
+// include/gpbc_bn254_indexed.h), and the reconstruction weights of a threshold tree (csrc/recon29.hip.hpp, include/gpbc_bn254_recon.h).
+// gfx950 only.
 #include "gpbc_common.hpp"
 #include "fr29.hip.hpp"
 #include "share29.hip.hpp"
+#include "recon29.hip.hpp"
 #include "lsss29.hip.hpp"
 #include "../../include/gpbc_bn254_share.h"
 #include "../../include/gpbc_bn254_indexed.h"
+#include "../../include/gpbc_bn254_recon.h"
 
 // ------------------------------------------------------------------------------------------------ elementwise
 // one element per lane (no __restrict__: out may be a, or b)
@@ -242,6 +245,35 @@ __global__ void __launch_bounds__(BLOCK) k_fr_share_tree_large(const ShareUnit *
                                      size_t k, ShareGeom gm, uint8_t *__restrict__ out) {
     fr_share_tree_kernel<FR_TREE_LARGE>(units, level_off, secrets, coeffs, k, gm, out);
 }
+
+// ------------------------------------------------------------------------------------------------ threshold-tree weights
+// w[j][y] with sum_y w[j][y] share_y = secret for the leaves item j holds: recon29.hip.hpp has the arithmetic, the plan, the geometry, the
+// staging and both passes; here are the LDS block (gate weights, state words and used words of ipb items) and the barriers.
+static_assert(FR_RECON_WAVE == BLOCK, "one wave per workgroup");
+template <int CAP> __device__ __forceinline__ void fr_tree_weights_kernel(const ReconUnit *__restrict__ units, const uint32_t *__restrict__ level_off, const ReconGate *__restrict__ gates,
+                                                                           const uint32_t *__restrict__ gate_off, const uint8_t *__restrict__ held, size_t k, ReconGeom gm,
+                                                                           uint8_t *__restrict__ w_out, uint8_t *__restrict__ ok_out) {
+    __shared__ int32_t ss[CAP + BLOCK];
+    if (!gm.G) { fr_recon_single(blockIdx.x, threadIdx.x, k, held, w_out, ok_out); return; }
+    const auto get = [&](uint32_t off) { return lds_get(ss + off); };
+    const auto put = [&](uint32_t off, const Fr &v) { lds_put(ss + off, v); };
+    const auto getw = [&](uint32_t off) { return (uint32_t)ss[off]; };
+    const auto putw = [&](uint32_t off, uint32_t v) { ss[off] = (int32_t)v; };
+    fr_recon_stage(gm, units, blockIdx.x, threadIdx.x, k, held, put, putw);
+    __syncthreads();
+    for (uint32_t lv = gm.depth; lv-- > 0;) {
+        fr_recon_up(gm, gates, gate_off, lv, blockIdx.x, threadIdx.x, k, getw, putw, ok_out);
+        __syncthreads();
+    }
+    for (uint32_t lv = 1; lv <= gm.depth; lv++) {
+        fr_recon_down<FR_RECON_G>(gm, units, level_off, lv, blockIdx.x, threadIdx.x, k, get, put, getw, putw, w_out);
+        __syncthreads();
+    }
+}
+#define GPBC_RECON_ARGS const ReconUnit *__restrict__ units, const uint32_t *__restrict__ level_off, const ReconGate *__restrict__ gates, const uint32_t *__restrict__ gate_off, \
+                        const uint8_t *__restrict__ held, size_t k, ReconGeom gm, uint8_t *__restrict__ w_out, uint8_t *__restrict__ ok_out
+GPBC_KERNEL_G1 k_fr_tree_weights(GPBC_RECON_ARGS) { fr_tree_weights_kernel<FR_RECON_SMALL>(units, level_off, gates, gate_off, held, k, gm, w_out, ok_out); }
+__global__ void __launch_bounds__(BLOCK) k_fr_tree_weights_large(GPBC_RECON_ARGS) { fr_tree_weights_kernel<FR_RECON_LARGE>(units, level_off, gates, gate_off, held, k, gm, w_out, ok_out); }
 
 // ------------------------------------------------------------------------------------------------ LSSS share generation
 // out[j][x] = M_x . v_j: lsss29.hip.hpp has the arithmetic, the geometry, the staging and the lane mapping; here is the LDS block of the
@@ -490,11 +522,16 @@ int gpbc_fr_poly_eval(const void *coeffs, size_t n_coeff_rows, size_t d, const v
                              [=](const DevCols &dc, size_t rows, hipStream_t st) { return gpbc_fr_poly_eval_dev(dc.in[0], one_c ? 1 : rows, d, dc.in[1], one_p ? 1 : rows, m, rows, dc.out[0], st); });
 }
 
+// the sharing plan and, behind it, the reconstruction plan of the same node list (recon29.hip.hpp; level_off serves both)
 struct gpbc_share_tree {
     int device;
     ShareGeom geom;
     ShareUnit *units;
     uint32_t *level_off;
+    ReconGeom rgeom;
+    ReconUnit *runits;
+    ReconGate *rgates;
+    uint32_t *rgate_off;
 };
 int gpbc_share_tree_create(const gpbc_share_node *nodes, size_t n_nodes, gpbc_share_tree **out) {
     static_assert(sizeof(gpbc_share_node) == sizeof(ShareNode), "the public node is the plan's node");
@@ -503,16 +540,31 @@ int gpbc_share_tree_create(const gpbc_share_node *nodes, size_t n_nodes, gpbc_sh
     SharePlan plan;
     const char *why = fr_share_plan(reinterpret_cast<const ShareNode *>(nodes), n_nodes, plan);
     if (why) return fail(GPBC_ERR_INVALID_ARG, "malformed tree: %s", why);
+    ReconPlan rplan;
+    why = fr_recon_plan(reinterpret_cast<const ShareNode *>(nodes), n_nodes, rplan);
+    if (why) return fail(GPBC_ERR_INVALID_ARG, "malformed tree: %s", why);      // fr_share_plan's reasons: nothing that passed above is refused here
+    if (!fr_recon_plan_ok(rplan)) return fail(GPBC_ERR_INTERNAL, "the reconstruction plan of a share tree points outside its tables");
     TRY(bind_device());
-    gpbc_share_tree *h = new gpbc_share_tree{current_device(), fr_share_geometry(plan), nullptr, nullptr};
+    gpbc_share_tree *h = new gpbc_share_tree{current_device(), fr_share_geometry(plan), nullptr, nullptr, fr_recon_geometry(rplan), nullptr, nullptr, nullptr};
     const size_t ub = (plan.units.size() ? plan.units.size() : 1) * sizeof(ShareUnit), lb = plan.level_off.size() * sizeof(uint32_t);
+    const size_t rub = (rplan.units.size() ? rplan.units.size() : 1) * sizeof(ReconUnit), rgb = (rplan.gates.size() ? rplan.gates.size() : 1) * sizeof(ReconGate),
+                 rob = rplan.gate_off.size() * sizeof(uint32_t);
     hipError_t e = hipMalloc((void **)&h->units, ub);
     if (e == hipSuccess) e = hipMalloc((void **)&h->level_off, lb);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->runits, rub);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->rgates, rgb);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->rgate_off, rob);
     if (e == hipSuccess && plan.units.size()) e = hipMemcpy(h->units, plan.units.data(), plan.units.size() * sizeof(ShareUnit), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(h->level_off, plan.level_off.data(), lb, hipMemcpyHostToDevice);
+    if (e == hipSuccess && rplan.units.size()) e = hipMemcpy(h->runits, rplan.units.data(), rplan.units.size() * sizeof(ReconUnit), hipMemcpyHostToDevice);
+    if (e == hipSuccess && rplan.gates.size()) e = hipMemcpy(h->rgates, rplan.gates.data(), rplan.gates.size() * sizeof(ReconGate), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(h->rgate_off, rplan.gate_off.data(), rob, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         if (h->units) (void)hipFree(h->units);
         if (h->level_off) (void)hipFree(h->level_off);
+        if (h->runits) (void)hipFree(h->runits);
+        if (h->rgates) (void)hipFree(h->rgates);
+        if (h->rgate_off) (void)hipFree(h->rgate_off);
         delete h;
         return fail(GPBC_ERR_HIP, "uploading a share tree failed: %s", hipGetErrorString(e));
     }
@@ -525,6 +577,9 @@ int gpbc_share_tree_destroy(gpbc_share_tree *t) {
     (void)hipDeviceSynchronize();
     (void)hipFree(t->units);
     (void)hipFree(t->level_off);
+    (void)hipFree(t->runits);
+    (void)hipFree(t->rgates);
+    (void)hipFree(t->rgate_off);
     delete t;
     return GPBC_OK;
 }
@@ -559,6 +614,37 @@ int gpbc_fr_share_tree(const gpbc_share_tree *t, const void *secrets, const void
     const bool has = t->geom.C != 0;
     return host_call(k, c.output(out, t->geom.L * GPBC_SCALAR_BYTES), HostRoute{CALL_KINDS, nullptr, 0, LANE_CALL_MAX_UNITS},
                      [=](const DevCols &dc, size_t m, hipStream_t st) { return gpbc_fr_share_tree_dev(t, dc.in[0], has ? dc.in[1] : nullptr, m, dc.out[0], st); });
+}
+
+// ------------------------------------------------------------------------------------------------ threshold-tree weight entries (include/gpbc_bn254_recon.h)
+int gpbc_recon_version(void) { return 1; }
+static int tree_weights_args(const gpbc_share_tree *t, const uint8_t *held, size_t k, const void *w_out, const uint8_t *ok_out) {
+    if (!t) return fail(GPBC_ERR_INVALID_ARG, "null tree handle");
+    if (k > (size_t)0x7fffffff / 4) return fail(GPBC_ERR_INVALID_ARG, "too many items for one call (%zu)", k);
+    if (!k) return GPBC_OK;
+    if (!held || !w_out || !ok_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    const size_t L = t->rgeom.L, wb = k * L * GPBC_SCALAR_BYTES;
+    if (overlap(w_out, wb, held, k * L) || overlap(ok_out, k, held, k * L) || overlap(w_out, wb, ok_out, k))
+        return fail(GPBC_ERR_INVALID_ARG, "an output overlaps an input or the other output");
+    return GPBC_OK;
+}
+int gpbc_fr_tree_weights_dev(const gpbc_share_tree *t, const uint8_t *d_held, size_t k, void *d_w_out, uint8_t *d_ok_out, void *stream) {
+    TRY(tree_weights_args(t, d_held, k, d_w_out, d_ok_out));
+    if (!k) return GPBC_OK;
+    TRY(bind_device());
+    if (current_device() != t->device) return fail(GPBC_ERR_INVALID_ARG, "tree was created on device %d", t->device);
+    const unsigned grid = (unsigned)fr_recon_grid(t->rgeom, k);
+    if (t->rgeom.large)
+        return GPBC_LAUNCH(k_fr_tree_weights_large, grid, BLOCK, (hipStream_t)stream, t->runits, t->level_off, t->rgates, t->rgate_off, d_held, k, t->rgeom, (uint8_t *)d_w_out, d_ok_out);
+    return GPBC_LAUNCH(k_fr_tree_weights, grid, BLOCK, (hipStream_t)stream, t->runits, t->level_off, t->rgates, t->rgate_off, d_held, k, t->rgeom, (uint8_t *)d_w_out, d_ok_out);
+}
+// Host pointers: as gpbc_fr_share_tree, the shared staging path on the tree's device only.
+int gpbc_fr_tree_weights(const gpbc_share_tree *t, const uint8_t *held, size_t k, void *w_out, uint8_t *ok_out) {
+    TRY(tree_weights_args(t, held, k, w_out, ok_out));
+    if (!k) return GPBC_OK;
+    const size_t L = t->rgeom.L;
+    return host_call(k, HostCall().input(held, L).output(w_out, L * GPBC_SCALAR_BYTES).output(ok_out, 1), HostRoute{CALL_KINDS, nullptr, 0, LANE_CALL_MAX_UNITS},
+                     [=](const DevCols &dc, size_t m, hipStream_t st) { return gpbc_fr_tree_weights_dev(t, (const uint8_t *)dc.in[0], m, dc.out[0], (uint8_t *)dc.out[1], st); });
 }
 
 // ------------------------------------------------------------------------------------------------ LSSS share entries (include/gpbc_bn254_indexed.h)

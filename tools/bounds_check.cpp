@@ -24,6 +24,7 @@
 #include "../gopairingbasedcryptography_amd/csrc/subset29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/transcript29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/share29.hip.hpp"
+#include "../gopairingbasedcryptography_amd/csrc/recon29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/lsss29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/fbindex29.hip.hpp"
 #include <condition_variable>
@@ -962,6 +963,68 @@ int hc_fr_share_tree(const uint32_t *nodes, size_t n_nodes, const uint8_t *secre
         if (lds.bad) return -2;
     }
     if (geom_out) { geom_out[0] = g.L; geom_out[1] = g.G; geom_out[2] = g.C; geom_out[3] = g.depth; geom_out[4] = g.ipb; geom_out[5] = g.large; geom_out[6] = (uint32_t)grid; }
+    stats_flush();
+    return 0;
+}
+// The LDS block of k_fr_tree_weights: elements of NL words and single words side by side.  A store outside the block, an element across
+// a word or another element's boundaries, a word inside an element, and a load of anything but what was stored whole at that offset
+// are refused.
+struct CheckedMixed {
+    std::vector<Fr> v;
+    std::vector<uint32_t> w;
+    std::vector<int64_t> owner;                 // -1 free, off: a word of the element at off, -2 - off: the single word at off
+    bool bad = false;
+    explicit CheckedMixed(size_t words) : v(words), w(words, 0), owner(words, -1) {}
+    void reset() { std::fill(owner.begin(), owner.end(), -1); }
+    Fr get(uint32_t off) {
+        if ((size_t)off + NL > v.size() || owner[off] != (int64_t)off) { bad = true; return fr_zero(); }
+        return v[off];
+    }
+    void put(uint32_t off, const Fr &x) {
+        if ((size_t)off + NL > v.size()) { bad = true; return; }
+        for (int i = 0; i < NL; i++) { if (owner[off + i] != -1 && owner[off + i] != (int64_t)off) bad = true; owner[off + i] = off; }
+        v[off] = x;
+    }
+    uint32_t getw(uint32_t off) {
+        if ((size_t)off >= w.size() || owner[off] != -2 - (int64_t)off) { bad = true; return 0; }
+        return w[off];
+    }
+    void putw(uint32_t off, uint32_t x) {
+        if ((size_t)off >= w.size() || (owner[off] != -1 && owner[off] != -2 - (int64_t)off)) { bad = true; return; }
+        owner[off] = -2 - (int64_t)off;
+        w[off] = x;
+    }
+};
+// k_fr_tree_weights as it is launched: the plan, the geometry, the staging and both passes of recon29.hip.hpp, workgroup by workgroup, a
+// barrier = the end of a loop over the lanes.  geom_out: [L, G, U, depth, ipb, pitch, large, workgroups].  -1: a refused tree or argument;
+// -2: a refusal of the LDS stand-in, a plan index outside its table or an output outside the rows.
+int hc_fr_tree_weights(const uint32_t *nodes, size_t n_nodes, const uint8_t *held, size_t k, uint8_t *w_out, uint8_t *ok_out, uint32_t *geom_out) {
+    ReconPlan p;
+    if (fr_recon_plan(reinterpret_cast<const ShareNode *>(nodes), n_nodes, p) || !k || !held || !w_out || !ok_out) return -1;
+    const ReconGeom g = fr_recon_geometry(p);
+    if (g.G && (size_t)g.ipb * g.pitch > (size_t)(g.large ? FR_RECON_LARGE : FR_RECON_SMALL)) return -2;
+    if (!fr_recon_plan_ok(p)) return -2;
+    CheckedMixed lds((size_t)(g.large ? FR_RECON_LARGE : FR_RECON_SMALL) + FR_RECON_WAVE);
+    const size_t grid = fr_recon_grid(g, k);
+    const auto get = [&](uint32_t off) { return lds.get(off); };
+    const auto put = [&](uint32_t off, const Fr &v) { lds.put(off, v); };
+    const auto getw = [&](uint32_t off) { return lds.getw(off); };
+    const auto putw = [&](uint32_t off, uint32_t v) { lds.putw(off, v); };
+    for (size_t block = 0; block < grid; block++) {
+        lds.reset();
+        if (!g.G) {
+            for (uint32_t lane = 0; lane < FR_RECON_WAVE; lane++) fr_recon_single((uint32_t)block, lane, k, held, w_out, ok_out);
+            continue;
+        }
+        for (uint32_t lane = 0; lane < FR_RECON_WAVE; lane++) fr_recon_stage(g, p.units.data(), (uint32_t)block, lane, k, held, put, putw);
+        for (uint32_t lv = g.depth; lv-- > 0 && !lds.bad;)
+            for (uint32_t lane = 0; lane < FR_RECON_WAVE; lane++) fr_recon_up(g, p.gates.data(), p.gate_off.data(), lv, (uint32_t)block, lane, k, getw, putw, ok_out);
+        for (uint32_t lv = 1; lv <= g.depth && !lds.bad; lv++)
+            for (uint32_t lane = 0; lane < FR_RECON_WAVE; lane++)
+                fr_recon_down<FR_RECON_G>(g, p.units.data(), p.level_off.data(), lv, (uint32_t)block, lane, k, get, put, getw, putw, w_out);
+        if (lds.bad) return -2;
+    }
+    if (geom_out) { geom_out[0] = g.L; geom_out[1] = g.G; geom_out[2] = g.U; geom_out[3] = g.depth; geom_out[4] = g.ipb; geom_out[5] = g.pitch; geom_out[6] = g.large; geom_out[7] = (uint32_t)grid; }
     stats_flush();
     return 0;
 }
