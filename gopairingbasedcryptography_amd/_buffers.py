@@ -120,7 +120,9 @@ def put(table, like):
 
 
 def take(a, index, axis=0):
-    """the entries of `a` along `axis` at the host integer array `index`"""
+    """the entries of `a` along `axis` at the integer array `index`: a host array or, for a tensor, also a tensor on its device"""
+    if is_torch(index):
+        return a.index_select(axis, index.reshape(-1).long())
     index = np.asarray(index, dtype=np.int64)
     return a.index_select(axis, put(index, a)) if is_torch(a) else np.take(a, index, axis=axis)
 

@@ -94,6 +94,11 @@ INDEXED_SIGNATURES = {
 RECON_SIGNATURES = {
     "gpbc_recon_version": "i:", "gpbc_fr_tree_weights": "i:ppzpp", "gpbc_fr_tree_weights_dev": "i:ppzppp",
 }
+# ... and for include/gpbc_bn254_select.h, the common attributes of a list and a set (tests/test_fr_find_common.py holds this table
+# against that header).  The eight tables are disjoint.
+SELECT_SIGNATURES = {
+    "gpbc_select_version": "i:", "gpbc_fr_find_common": "i:pzzpzzzpppp", "gpbc_fr_find_common_dev": "i:pzzpzzzppppp",
+}
 # every pointer is a c_void_p: it takes ints, None, c_void_p, ctypes arrays, byref() and ndarray.ctypes.data_as() alike
 _CTYPES = {"p": ctypes.c_void_p, "z": ctypes.c_size_t, "i": ctypes.c_int, "l": ctypes.c_long, "s": ctypes.c_char_p}
 
@@ -119,7 +124,7 @@ def load():
         except ImportError:
             pass
         lib = ctypes.CDLL(LIB_PATH)
-        for name, sig in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(SUBSET_SIGNATURES.items()) + list(HASH_SIGNATURES.items()) + list(SHARE_SIGNATURES.items()) + list(INDEXED_SIGNATURES.items()) + list(RECON_SIGNATURES.items()):
+        for name, sig in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(SUBSET_SIGNATURES.items()) + list(HASH_SIGNATURES.items()) + list(SHARE_SIGNATURES.items()) + list(INDEXED_SIGNATURES.items()) + list(RECON_SIGNATURES.items()) + list(SELECT_SIGNATURES.items()):
             ret, params = sig.split(":")
             fn = getattr(lib, name)
             fn.restype = _CTYPES[ret]

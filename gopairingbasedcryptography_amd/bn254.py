@@ -866,6 +866,57 @@ def fr_lsss_shares(matrix, vectors, rows=None, cols=None, out=None):
     return out
 
 
+FR_SELECT_MAX = 1024
+
+
+def fr_find_common(sets, lists, m, a, d, set_pos_out=None, list_pos_out=None, common_out=None, ok_out=None):
+    """(set_pos [k, d], list_pos [k, d], common [k, d, 32], ok [k]): utils.FindCommonAttributes for k items in one launch
+    (include/gpbc_bn254_select.h).  lists: k x a scalar rows, the attributes of k ciphertexts; sets: m scalar rows (one key for all items)
+    or k x m (a key per item).  Rows are 32-byte little-endian values below 2^256, compared modulo r; uint8 arrays or CUDA tensors,
+    not mixed.  Per item the list is walked in order and an element is kept iff the set holds it and no earlier equal element was
+    kept, up to d: slot s of the rows is the s-th kept element's position in the set (its first occurrence there), its position in the
+    list and its canonical value — `common` is the node set fr_lagrange_basis takes.  ok = 0 and all-zero rows where fewer than d are
+    kept.  The positions come back as int32; a caller's set_pos_out / list_pos_out are uint8 buffers of k x d x 4 bytes, 4-byte aligned.
+    Outputs are of the kind that went in; tensors are enqueued on the current stream and not synchronised."""
+    for v, what in ((m, "m"), (a, "a"), (d, "d")):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 1 <= int(v) <= FR_SELECT_MAX:
+            raise ValueError("%s must be in 1 .. %d (got %s)" % (what, FR_SELECT_MAX, v))
+    m, a, d = int(m), int(a), int(d)
+    for v, what in ((sets, "sets"), (lists, "lists")):
+        if not bufs.is_torch(v) and not isinstance(v, (np.ndarray, bytes, bytearray)):
+            raise ValueError("%s must be a uint8 array or a CUDA tensor of 32-byte rows (sw05.attribute_rows makes them from integers)" % what)
+        if isinstance(v, np.ndarray) and v.dtype != np.uint8:
+            raise ValueError("%s must be uint8 (got %s)" % (what, v.dtype))
+    (sb, ns), (lb, nl) = bufs.rows(sets, SCALAR_BYTES, "sets"), bufs.rows(lists, SCALAR_BYTES, "lists")
+    outs = (set_pos_out, list_pos_out, common_out, ok_out)
+    dev = bufs.device_of(sb, lb, *outs)
+    if ns == 0 or ns % m or nl % a:
+        raise ValueError("sets needs whole sets of %d scalars and lists whole lists of %d" % (m, a))
+    n_sets, k = ns // m, nl // a
+    if k and n_sets not in (1, k):
+        raise ValueError("need one set or one per list (got %d sets, %d lists)" % (n_sets, k))
+    if k > (1 << 29) - 1:
+        raise ValueError("too many items for one call (%d)" % k)
+    sp = bufs.output(set_pos_out, (k, d, 4), dev, "set_pos_out")
+    lp = bufs.output(list_pos_out, (k, d, 4), dev, "list_pos_out")
+    cm = bufs.output(common_out, (k, d, SCALAR_BYTES), dev, "common_out")
+    ok = bufs.output(ok_out, (k,), dev, "ok_out")
+    if bufs.address(sp) % 4 or bufs.address(lp) % 4:
+        raise ValueError("set_pos_out and list_pos_out must be 4-byte aligned")
+    if k:
+        got = (sp, lp, cm, ok)
+        if any(_overlaps(o, sb, lb, *got[:i]) for i, o in enumerate(got)):
+            raise ValueError("an output overlaps an input or another output")
+        _call("fr_find_common", dev, sb, n_sets, m, lb, a, d, k, sp, lp, cm, ok)
+
+    def positions(x):
+        if bufs.is_torch(x):
+            import torch
+            return x.reshape(-1).view(torch.int32).reshape(k, d)
+        return x.reshape(-1).view(np.int32).reshape(k, d)
+    return positions(sp), positions(lp), cm.reshape(k, d, SCALAR_BYTES), ok.reshape(k)
+
+
 _gen_tables = {}
 
 

@@ -3,16 +3,19 @@
 // proofs, the Lagrange basis over a node set per row (SW05 fuzzy IBE) and the LSSS reconstruction weights of a policy per
 // ciphertext (Waters11 CP-ABE) — with their C-ABI entries (include/gpbc_bn254.h, "scalar field"), and secret sharing (csrc/share29.hip.hpp):
 // polynomial evaluation and the shares of a threshold tree (include/gpbc_bn254_share.h), and LSSS share generation (csrc/lsss29.hip.hpp,
-// include/gpbc_bn254_indexed.h), and the reconstruction weights of a threshold tree (csrc/recon29.hip.hpp, include/gpbc_bn254_recon.h).
+// include/gpbc_bn254_indexed.h), and the reconstruction weights of a threshold tree (csrc/recon29.hip.hpp, include/gpbc_bn254_recon.h),
+// and the common attributes of a list and a set (csrc/select29.hip.hpp, include/gpbc_bn254_select.h).
 // gfx950 only.
 #include "gpbc_common.hpp"
 #include "fr29.hip.hpp"
 #include "share29.hip.hpp"
 #include "recon29.hip.hpp"
 #include "lsss29.hip.hpp"
+#include "select29.hip.hpp"
 #include "../../include/gpbc_bn254_share.h"
 #include "../../include/gpbc_bn254_indexed.h"
 #include "../../include/gpbc_bn254_recon.h"
+#include "../../include/gpbc_bn254_select.h"
 
 // ------------------------------------------------------------------------------------------------ elementwise
 // one element per lane (no __restrict__: out may be a, or b)
@@ -296,6 +299,35 @@ GPBC_KERNEL_G1 k_fr_lsss_shares(const uint8_t *__restrict__ matrix, size_t mat_s
         const int32_t *mine = ms + l.xr * gm.pitch;
         fr_lsss_shares_lane([&](uint32_t c) { return lds_get(mine + c * NL); }, gm.cols, vec, o);
     }
+}
+
+// ------------------------------------------------------------------------------------------------ common attributes
+// FindCommonAttributes for k (set, list) items: select29.hip.hpp has the geometry, the staging, the lane map and the four phases; here are
+// the LDS block (the staged sets, a pos word and a keep word per list element) and the three barriers.  Two instances by LDS block.
+static_assert(FR_SELECT_WAVE == BLOCK, "one wave per workgroup");
+template <int WORDS> __device__ __forceinline__ void fr_find_common_kernel(const uint8_t *__restrict__ sets, const uint8_t *__restrict__ lists, size_t k, SelectGeom gm, SelectOut o) {
+    __shared__ uint32_t ss[WORDS];
+    const auto gete = [&](uint32_t off, int i) { return ss[off + i]; };
+    const auto getw = [&](uint32_t off) { return ss[off]; };
+    const auto putw = [&](uint32_t off, uint32_t v) { ss[off] = v; };
+    fr_select_stage(gm, blockIdx.x, threadIdx.x, k, sets, [&](uint32_t off, const uint32_t (&w)[FR_SELECT_EW]) {
+#pragma unroll
+        for (int i = 0; i < FR_SELECT_EW; i++) ss[off + i] = w[i];
+    });
+    __syncthreads();
+    fr_select_match(gm, blockIdx.x, threadIdx.x, k, lists, gete, putw);
+    __syncthreads();
+    fr_select_mark(gm, blockIdx.x, threadIdx.x, k, getw, putw);
+    __syncthreads();
+    fr_select_pick(gm, blockIdx.x, threadIdx.x, k, gete, getw,
+                   [&](size_t item, uint32_t slot, uint32_t sp, uint32_t lp, const uint32_t (&w)[FR_SELECT_EW]) { fr_select_store(o, item, slot, sp, lp, w); },
+                   [&](size_t item, bool ok) { o.ok[item] = ok ? 1 : 0; });
+}
+GPBC_KERNEL_G1 k_fr_find_common(const uint8_t *__restrict__ sets, const uint8_t *__restrict__ lists, size_t k, SelectGeom gm, SelectOut o) {
+    fr_find_common_kernel<FR_SELECT_WORDS_SMALL>(sets, lists, k, gm, o);
+}
+__global__ void __launch_bounds__(BLOCK) k_fr_find_common_large(const uint8_t *__restrict__ sets, const uint8_t *__restrict__ lists, size_t k, SelectGeom gm, SelectOut o) {
+    fr_find_common_kernel<FR_SELECT_WORDS_LARGE>(sets, lists, k, gm, o);
 }
 
 extern "C" {
@@ -645,6 +677,63 @@ int gpbc_fr_tree_weights(const gpbc_share_tree *t, const uint8_t *held, size_t k
     const size_t L = t->rgeom.L;
     return host_call(k, HostCall().input(held, L).output(w_out, L * GPBC_SCALAR_BYTES).output(ok_out, 1), HostRoute{CALL_KINDS, nullptr, 0, LANE_CALL_MAX_UNITS},
                      [=](const DevCols &dc, size_t m, hipStream_t st) { return gpbc_fr_tree_weights_dev(t, (const uint8_t *)dc.in[0], m, dc.out[0], (uint8_t *)dc.out[1], st); });
+}
+
+// ------------------------------------------------------------------------------------------------ common attribute entries (include/gpbc_bn254_select.h)
+int gpbc_select_version(void) { return 1; }
+static int find_common_args(const void *sets, size_t n_sets, size_t m, const void *lists, size_t a, size_t d, size_t k, const void *set_pos_out, const void *list_pos_out,
+                            const void *common_out, const void *ok_out) {
+    const size_t lim = (size_t)FR_SELECT_MAX;
+    if (m < 1 || m > lim || a < 1 || a > lim || d < 1 || d > lim) return fail(GPBC_ERR_INVALID_ARG, "m, a and d must be in 1 .. %d (got m = %zu, a = %zu, d = %zu)", FR_SELECT_MAX, m, a, d);
+    if (k > (size_t)0x7fffffff / 4) return fail(GPBC_ERR_INVALID_ARG, "too many items for one call (%zu)", k);
+    if (!k) return GPBC_OK;
+    if (n_sets != 1 && n_sets != k) return fail(GPBC_ERR_INVALID_ARG, "n_sets must be 1 or k (got %zu, k = %zu)", n_sets, k);
+    if (!sets || !lists || !set_pos_out || !list_pos_out || !common_out || !ok_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    const void *p[6] = {sets, lists, set_pos_out, list_pos_out, common_out, ok_out};
+    const size_t nb[6] = {n_sets * m * GPBC_SCALAR_BYTES, k * a * GPBC_SCALAR_BYTES, k * d * sizeof(uint32_t), k * d * sizeof(uint32_t), k * d * GPBC_SCALAR_BYTES, k};
+    for (int i = 2; i < 6; i++)
+        for (int j = 0; j < i; j++)
+            if (overlap(p[i], nb[i], p[j], nb[j])) return fail(GPBC_ERR_INVALID_ARG, "an output overlaps an input or another output");
+    return GPBC_OK;
+}
+static int find_common_launch(const void *d_sets, size_t n_sets, size_t m, const void *d_lists, size_t a, size_t d, size_t k, const SelectOut &o, void *stream) {
+    TRY(bind_device());
+    const SelectGeom g = fr_select_geometry(m, a, d, n_sets == 1);
+    const unsigned grid = (unsigned)fr_select_grid(g, k);
+    if (g.large) return GPBC_LAUNCH(k_fr_find_common_large, grid, BLOCK, (hipStream_t)stream, (const uint8_t *)d_sets, (const uint8_t *)d_lists, k, g, o);
+    return GPBC_LAUNCH(k_fr_find_common, grid, BLOCK, (hipStream_t)stream, (const uint8_t *)d_sets, (const uint8_t *)d_lists, k, g, o);
+}
+int gpbc_fr_find_common_dev(const void *d_sets, size_t n_sets, size_t m, const void *d_lists, size_t a, size_t d, size_t k, uint32_t *d_set_pos_out, uint32_t *d_list_pos_out,
+                            void *d_common_out, uint8_t *d_ok_out, void *stream) {
+    TRY(find_common_args(d_sets, n_sets, m, d_lists, a, d, k, d_set_pos_out, d_list_pos_out, d_common_out, d_ok_out));
+    if (!k) return GPBC_OK;
+    return find_common_launch(d_sets, n_sets, m, d_lists, a, d, k,
+                              SelectOut{(uint8_t *)d_set_pos_out, (uint8_t *)d_list_pos_out, (uint8_t *)d_common_out, d_ok_out, d * sizeof(uint32_t), d * GPBC_SCALAR_BYTES}, stream);
+}
+// Host-pointer form: the unit is an item; a shard needs about 2^16 comparisons to pay for its thread and transfers.  A set given once
+// travels whole to every shard.  The staging path carries two output columns, so an item's three rows travel as one record of 40 d bytes
+// (set positions, list positions, values; the kernel writes the record's parts at the record's pitch) and are dealt out here.
+int gpbc_fr_find_common(const void *sets, size_t n_sets, size_t m, const void *lists, size_t a, size_t d, size_t k, uint32_t *set_pos_out, uint32_t *list_pos_out, void *common_out,
+                        uint8_t *ok_out) {
+    TRY(find_common_args(sets, n_sets, m, lists, a, d, k, set_pos_out, list_pos_out, common_out, ok_out));
+    if (!k) return GPBC_OK;
+    const bool one = n_sets == 1;
+    const size_t shard_min = ((size_t)1 << 16) / (m * a), pb = d * sizeof(uint32_t), cb = d * GPBC_SCALAR_BYTES, rec = 2 * pb + cb;
+    std::vector<uint8_t> records, oks;
+    try { records.resize(k * rec); oks.resize(k); } catch (const std::bad_alloc &) { return fail(GPBC_ERR_INTERNAL, "out of host memory for %zu records", k); }
+    HostCall c = HostCall().input(sets, m * GPBC_SCALAR_BYTES, one).input(lists, a * GPBC_SCALAR_BYTES);
+    TRY(host_call_sharded(k, shard_min ? shard_min : 1, c.output(records.data(), rec).output(oks.data(), 1), HostRoute{},
+                          [=](const DevCols &dc, size_t n, hipStream_t st) {
+                              return find_common_launch(dc.in[0], one ? 1 : n, m, dc.in[1], a, d, n, SelectOut{dc.out[0], dc.out[0] + pb, dc.out[0] + 2 * pb, dc.out[1], rec, rec}, st);
+                          }));
+    for (size_t j = 0; j < k; j++) {
+        const uint8_t *r = records.data() + j * rec;
+        memcpy((uint8_t *)set_pos_out + j * pb, r, pb);
+        memcpy((uint8_t *)list_pos_out + j * pb, r + pb, pb);
+        memcpy((uint8_t *)common_out + j * cb, r + 2 * pb, cb);
+    }
+    memcpy(ok_out, oks.data(), k);
+    return GPBC_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ LSSS share entries (include/gpbc_bn254_indexed.h)

@@ -16,7 +16,12 @@ engine.g1_scalar_mul as they are.
 
 Host orchestration only, engine-agnostic (every function takes the engine: `bn254`, or a stand-in with the same function names).
 Host arrays in give host arrays out; CUDA tensors in give CUDA tensors out, with only the key, the selected attribute values and
-index tables going to the device.  Every ciphertext of a batch carries the same number of attributes."""
+index tables going to the device.  Every ciphertext of a batch carries the same number of attributes.
+
+Two input forms.  Attributes as nested Python integers: the selection is select_common below, a host loop per ciphertext.  Attributes as
+scalar rows ([n, a, 32] uint8, an array or a CUDA tensor — where hash_to_field, sha256(to_fr=True) or an unmarshalled ciphertext left
+them): the selection is engine.fr_find_common, its `common` rows are the Lagrange sets as they are, the gathers take its positions on the
+device, and only ok (n bytes) comes back to the host — the call's one wait.  Both forms give the same bytes."""
 import numpy as np
 
 from . import _buffers as bufs
@@ -33,6 +38,22 @@ def _scalar_rows(values):
             b = cache[v] = (int(v) % R_ORDER).to_bytes(32, "little")
         return b
     return np.frombuffer(b"".join([row(v) for v in values]), dtype=np.uint8).reshape(-1, 32).copy()      # writable: it may become a tensor
+
+
+def attribute_rows(values):
+    """attribute values (Python ints, reduced modulo r) as scalar rows: [len, 32] uint8, or [n, a, 32] for nested lists [n][a] of one
+    length — what the rows form of decrypt_batch / decrypt_batch_large and engine.fr_find_common take"""
+    values = list(values)
+    if values and isinstance(values[0], (list, tuple)):
+        a = len(values[0])
+        if any(len(v) != a for v in values):
+            raise ValueError("every row needs %d values" % a)
+        return _scalar_rows(x for v in values for x in v).reshape(len(values), a, 32)
+    return _scalar_rows(values)
+
+
+def _is_rows(x):
+    return (bufs.is_torch(x) or isinstance(x, np.ndarray)) and len(x.shape) == 3 and x.shape[2] == 32 and str(x.dtype) in ("uint8", "torch.uint8")
 
 
 def select_common(key_attrs, ct_attrs, d):
@@ -116,14 +137,68 @@ class _Plan:
         return out, self.put(self.ok.copy())
 
 
+class _RowsPlan(_Plan):
+    """the same from attribute rows: the selection on the device, its positions used where they are"""
+
+    def __init__(self, engine, key_attrs, d, ct_attrs, E, e_prime):
+        if d < 1:
+            raise ValueError("d must be at least 1 (got %s)" % d)
+        self.engine, self.d, self.n = engine, d, int(ct_attrs.shape[0])
+        n, a = self.n, int(ct_attrs.shape[1])
+        if not bufs.is_torch(key_attrs) and not isinstance(key_attrs, np.ndarray):
+            key_attrs = bufs.put(attribute_rows(key_attrs), ct_attrs)                         # converted once
+        shape = tuple(key_attrs.shape)
+        if len(shape) not in (2, 3) or shape[-1] != 32 or (len(shape) == 3 and shape[0] != n):
+            raise ValueError("the key's attributes must be [m, 32] or [n, m, 32] scalar rows (n = %d)" % n)
+        bufs.device_of(ct_attrs, key_attrs, E, e_prime)                                       # all of one kind, on one device
+        self.per_item, self.m, self.a = len(shape) == 3, int(shape[-2]), a
+        if bufs.nbytes(E) != n * a * 128 or bufs.nbytes(e_prime) != n * 384:
+            raise ValueError("E must hold n x %d G2 points and e_prime n GT elements (n = %d)" % (a, n))
+        self.E, self.e_prime = bufs.view(E, n, a, 128), bufs.view(e_prime, n, 384)
+        self.ok, self.good, self.ng = np.zeros(n, dtype=np.uint8), np.zeros(0, dtype=np.int64), 0
+        if not n:
+            return
+        set_pos, list_pos, common, ok = engine.fr_find_common(bufs.flat(key_attrs), bufs.flat(ct_attrs), self.m, a, d)
+        self.ok = np.array(ok.cpu().numpy() if bufs.is_torch(ok) else ok, dtype=np.uint8, copy=True).reshape(n)      # the one wait
+        self.good = np.nonzero(self.ok)[0]
+        ng = self.ng = len(self.good)
+        if not ng:
+            return
+        self.key_pos, self.ct_pos = bufs.take(set_pos.reshape(n, d), self.good), bufs.take(list_pos.reshape(n, d), self.good)
+        self.delta = engine.fr_lagrange_basis(bufs.flat(bufs.take(common.reshape(n, d * 32), self.good)), d).reshape(ng * d, 32)
+        self.seg = lambda pairs: np.arange(0, pairs * ng + 1, pairs, dtype=np.uint64)
+
+    def _index(self, pos, width):
+        """positions inside the rows of the decryptable items as positions in the flattened [n x width] table"""
+        return (pos + self.put(self.good * width).reshape(self.ng, 1)).reshape(-1)
+
+    def key_rows(self, comp, width):
+        comp = comp if bufs.is_torch(comp) else self.put(np.asarray(comp, dtype=np.uint8))
+        if bufs.nbytes(comp) != (self.n if self.per_item else 1) * self.m * width:
+            raise ValueError("a key component must hold %s%d x %d bytes" % ("n x " if self.per_item else "", self.m, width))
+        index = self._index(self.key_pos, self.m) if self.per_item else self.key_pos.reshape(-1)
+        return bufs.take(comp.reshape(-1, width), index).reshape(self.ng, self.d, width)
+
+    def ct_rows(self):
+        return bufs.take(self.E.reshape(-1, 128), self._index(self.ct_pos, self.a)).reshape(self.ng, self.d, 128)
+
+
+def _plan(engine, key_attrs, d, ct_attrs, E, e_prime):
+    return (_RowsPlan if _is_rows(ct_attrs) else _Plan)(engine, key_attrs, d, ct_attrs, E, e_prime)
+
+
 def decrypt_batch(engine, key, d, ct_attrs, E, e_prime):
     """Small universe.  key = (attrs, D): the key's attribute list and its components D_i = g1^(q(i) / t_i), [len(attrs), 64] host
     bytes; ct_attrs: [n][a] attribute values (Python ints); E: [n, a, 128] the components E_i = T_i^s in the order of ct_attrs;
     e_prime: [n, 384].  Returns (messages [n, 384], ok [n]); a ciphertext with fewer than d common attributes has ok = 0 and an
     all-zero row, as the unmarshal entries do, and takes no part in the engine calls (fr_lagrange_basis, g1_scalar_mul,
-    multi_pair with one segment of d pairs per ciphertext, gt_div)."""
+    multi_pair with one segment of d pairs per ciphertext, gt_div).
+
+    Rows form: ct_attrs a [n, a, 32] uint8 array or CUDA tensor of scalar rows (attribute_rows makes them from integers), of the kind E
+    is.  attrs is then [m, 32] rows or a list of integers (converted once), D [m, 64]; or a key per item — attrs [n, m, 32] with
+    D [n, m, 64] — for n (key, ciphertext) pairs.  The selection is engine.fr_find_common; messages and ok are those of the integer form."""
     attrs, D = key
-    p = _Plan(engine, attrs, d, ct_attrs, E, e_prime)
+    p = _plan(engine, attrs, d, ct_attrs, E, e_prime)
     if not p.ng:
         return p.scatter(None)
     P = engine.g1_scalar_mul(bufs.flat(p.key_rows(D, 64)), bufs.flat(p.delta))
@@ -135,9 +210,10 @@ def decrypt_batch_large(engine, key, d, ct_attrs, E, e_pp, e_prime):
     """Large universe.  key = (attrs, d_i [len(attrs), 64], D_i [len(attrs), 128]) with d_i = g1^r_i, D_i = g2^q(i) T_i^r_i; E as in
     decrypt_batch; e_pp: [n, 64] the components E'' = g1^s; e_prime: [n, 384].  One segment of 2 d pairs per ciphertext,
     ([Delta_i] d_i, E_i) ... ([-Delta_i] E'', D_i) ..., with -Delta from engine.fr_neg on the same scalars, then gt_mul.  (The form with
-    d + 1 pairs, which sums [Delta_i] D_i in G2 per ciphertext, is not built.)"""
+    d + 1 pairs, which sums [Delta_i] D_i in G2 per ciphertext, is not built.)  The rows form is decrypt_batch's, with d_i [m, 64] and
+    D_i [m, 128], or [n, m, 64] and [n, m, 128] with a key per item."""
     attrs, di, Di = key
-    p = _Plan(engine, attrs, d, ct_attrs, E, e_prime)
+    p = _plan(engine, attrs, d, ct_attrs, E, e_prime)
     if bufs.nbytes(e_pp) != p.n * 64 or bufs.is_torch(e_pp) != bufs.is_torch(p.E):
         raise ValueError("e_pp must hold n G1 points of the kind E is")
     if not p.ng:

@@ -17,6 +17,7 @@ package gpbcbn254
 #include "gpbc_bn254_hash.h"
 #include "gpbc_bn254_share.h"
 #include "gpbc_bn254_indexed.h"
+#include "gpbc_bn254_select.h"
 */
 import "C"
 
@@ -698,6 +699,41 @@ func FrLsssShares(matrix []fr.Element, rows, cols int, vectors []fr.Element) ([]
 	}
 	out := make([]fr.Element, len(ko))
 	return out, frElements(ko, out)
+}
+
+// FrFindCommon: utils.FindCommonAttributes for k lists of a elements in one launch (include/gpbc_bn254_select.h): sets holds one set
+// of m elements (shared by the k lists) or k of them.  Per list and slot s < d: the position of the s-th kept element in the set (its
+// first occurrence) and in the list, and the element; ok[j] == 0, and zero rows, where fewer than d are common.
+func FrFindCommon(sets []fr.Element, m int, lists []fr.Element, a, d int) (setPos, listPos []uint32, common []fr.Element, ok []uint8, err error) {
+	defer pin()()
+	if m < 1 || a < 1 || d < 1 || len(sets) == 0 || len(sets)%m != 0 || len(lists)%a != 0 {
+		return nil, nil, nil, nil, errSizes
+	}
+	ns := len(sets) / m
+	k := len(lists) / a
+	if k == 0 {
+		return nil, nil, nil, nil, nil
+	}
+	if ns != 1 && ns != k {
+		return nil, nil, nil, nil, errSizes
+	}
+	ks, err := frPlain(sets)
+	if err != nil {
+		return nil, nil, nil, nil, err
+	}
+	kl, err := frPlain(lists)
+	if err != nil {
+		return nil, nil, nil, nil, err
+	}
+	setPos, listPos, ok = make([]uint32, k*d), make([]uint32, k*d), make([]uint8, k)
+	kc := make([][32]byte, k*d)
+	rc := C.gpbc_fr_find_common(unsafe.Pointer(unsafe.SliceData(ks)), C.size_t(ns), C.size_t(m), unsafe.Pointer(unsafe.SliceData(kl)), C.size_t(a), C.size_t(d), C.size_t(k),
+		(*C.uint32_t)(unsafe.SliceData(setPos)), (*C.uint32_t)(unsafe.SliceData(listPos)), unsafe.Pointer(unsafe.SliceData(kc)), (*C.uint8_t)(unsafe.SliceData(ok)))
+	if err := status(rc); err != nil {
+		return nil, nil, nil, nil, err
+	}
+	common = make([]fr.Element, len(kc))
+	return setPos, listPos, common, ok, frElements(kc, common)
 }
 
 // g1GroupOp: Add (sub == false) or Sub over the batch (cgo cannot take a C function as a value, hence the flag)

@@ -26,6 +26,7 @@
 #include "gpbc_bn254_hash.h"
 #include "gpbc_bn254_share.h"
 #include "gpbc_bn254_indexed.h"
+#include "gpbc_bn254_select.h"
 
 namespace bn254 {
 
@@ -406,6 +407,22 @@ inline std::vector<Scalar> FrLsssShares(const std::vector<Scalar> &matrix, size_
     if (k && nm != 1 && nm != k) throw std::invalid_argument("need one matrix or one per vector");
     std::vector<Scalar> out(k * rows);
     check(gpbc_fr_lsss_shares(matrix.data(), nm, rows, cols, vectors.data(), k, out.data()));
+    return out;
+}
+// FindCommonAttributes(set, list, d) for k lists of `a` scalars (include/gpbc_bn254_select.h): sets holds one set of m scalars or k of them.
+// Per item and slot s < d: the s-th kept element's position in the set and in the list, and its canonical value; ok[j] = 0 and zero rows
+// where fewer than d are common.
+struct CommonAttributes {
+    std::vector<uint32_t> set_pos, list_pos;      // k x d
+    std::vector<Scalar> common;                   // k x d
+    std::vector<uint8_t> ok;                      // k
+};
+inline CommonAttributes FrFindCommon(const std::vector<Scalar> &sets, size_t m, const std::vector<Scalar> &lists, size_t a, size_t d) {
+    if (m < 1 || a < 1 || d < 1 || sets.empty() || sets.size() % m || lists.size() % a) throw std::invalid_argument("need m scalars per set, a per list");
+    const size_t n_sets = sets.size() / m, k = lists.size() / a;
+    if (k && n_sets != 1 && n_sets != k) throw std::invalid_argument("need one set or one per list");
+    CommonAttributes out{std::vector<uint32_t>(k * d), std::vector<uint32_t>(k * d), std::vector<Scalar>(k * d), std::vector<uint8_t>(k)};
+    check(gpbc_fr_find_common(sets.data(), n_sets, m, lists.data(), a, d, k, out.set_pos.data(), out.list_pos.data(), out.common.data(), out.ok.data()));
     return out;
 }
 static_assert(sizeof(Scalar) == GPBC_SCALAR_BYTES, "scalar layout");

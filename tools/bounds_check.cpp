@@ -26,6 +26,7 @@
 #include "../gopairingbasedcryptography_amd/csrc/share29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/recon29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/lsss29.hip.hpp"
+#include "../gopairingbasedcryptography_amd/csrc/select29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/fbindex29.hip.hpp"
 #include <condition_variable>
 #include <mutex>
@@ -1055,6 +1056,79 @@ int hc_fr_lsss_shares(const uint8_t *matrix, size_t n_matrices, size_t rows, siz
         if (lds.bad) return -2;
     }
     if (geom_out) { geom_out[0] = g.rg; geom_out[1] = g.nrg; geom_out[2] = g.ipb; geom_out[3] = g.pitch; geom_out[4] = (uint32_t)grid; geom_out[5] = active; }
+    stats_flush();
+    return 0;
+}
+// The LDS block of k_fr_find_common: set elements of eight words and single words (pos, keep) side by side.  A store outside the block, an
+// element over anything stored before, a word inside an element, a load of an element's word through anything but the element's own
+// offset and a load of a word that was not stored are refused.
+struct CheckedWords {
+    std::vector<uint32_t> w;
+    std::vector<int64_t> owner;                 // -1 free, off: a word of the element at off, -2 - off: the single word at off
+    bool bad = false;
+    explicit CheckedWords(size_t words) : w(words, 0), owner(words, -1) {}
+    void reset() { std::fill(owner.begin(), owner.end(), -1); }
+    uint32_t gete(uint32_t off, int i) {
+        if ((size_t)off + FR_SELECT_EW > w.size() || i < 0 || i >= FR_SELECT_EW || owner[off + i] != (int64_t)off) { bad = true; return 0; }
+        return w[off + i];
+    }
+    void pute(uint32_t off, const uint32_t (&x)[FR_SELECT_EW]) {
+        if ((size_t)off + FR_SELECT_EW > w.size()) { bad = true; return; }
+        for (int i = 0; i < FR_SELECT_EW; i++) { if (owner[off + i] != -1) bad = true; owner[off + i] = off; w[off + i] = x[i]; }
+    }
+    uint32_t getw(uint32_t off) {
+        if ((size_t)off >= w.size() || owner[off] != -2 - (int64_t)off) { bad = true; return 0; }
+        return w[off];
+    }
+    void putw(uint32_t off, uint32_t x) {
+        if ((size_t)off >= w.size() || (owner[off] != -1 && owner[off] != -2 - (int64_t)off)) { bad = true; return; }
+        owner[off] = -2 - (int64_t)off;
+        w[off] = x;
+    }
+};
+// k_fr_find_common as it is launched: the geometry, the staging and the three phases behind it of select29.hip.hpp, workgroup by workgroup,
+// a barrier = the end of a loop over the lanes.  geom_out: [lpi, ipb, chunks, pitch, large, shared, workgroups, active lanes].
+// -1: arguments the entry refuses; -2: a refusal of the LDS stand-in, a lane outside the outputs, or a slot written twice or never.
+int hc_fr_find_common(const uint8_t *sets, size_t n_sets, size_t m, const uint8_t *lists, size_t a, size_t d, size_t k, uint32_t *set_pos_out, uint32_t *list_pos_out,
+                      uint8_t *common_out, uint8_t *ok_out, uint32_t *geom_out) {
+    const size_t lim = (size_t)FR_SELECT_MAX;
+    if (m < 1 || m > lim || a < 1 || a > lim || d < 1 || d > lim || !k || (n_sets != 1 && n_sets != k)) return -1;
+    if (!sets || !lists || !set_pos_out || !list_pos_out || !common_out || !ok_out) return -1;
+    const SelectGeom g = fr_select_geometry(m, a, d, n_sets == 1);
+    CheckedWords lds((size_t)fr_select_words(g.large));
+    const size_t grid = fr_select_grid(g, k);
+    std::vector<uint8_t> slot_seen(k * d, 0), item_seen(k, 0);
+    bool outside = false;
+    uint32_t active = 0;
+    const SelectOut o{(uint8_t *)set_pos_out, (uint8_t *)list_pos_out, common_out, ok_out, d * sizeof(uint32_t), d * 32};
+    const auto gete = [&](uint32_t off, int i) { return lds.gete(off, i); };
+    const auto getw = [&](uint32_t off) { return lds.getw(off); };
+    const auto putw = [&](uint32_t off, uint32_t v) { lds.putw(off, v); };
+    for (size_t block = 0; block < grid; block++) {
+        lds.reset();
+        for (uint32_t lane = 0; lane < FR_SELECT_WAVE; lane++)
+            fr_select_stage(g, (uint32_t)block, lane, k, sets, [&](uint32_t off, const uint32_t (&w)[FR_SELECT_EW]) { lds.pute(off, w); });
+        for (uint32_t lane = 0; lane < FR_SELECT_WAVE; lane++) {
+            const SelectLane l = fr_select_map(g, (uint32_t)block, lane, k);
+            if (l.active && l.item >= k) return -2;
+            active += l.active ? 1u : 0u;
+            fr_select_match(g, (uint32_t)block, lane, k, lists, gete, putw);
+        }
+        for (uint32_t lane = 0; lane < FR_SELECT_WAVE && !lds.bad; lane++) fr_select_mark(g, (uint32_t)block, lane, k, getw, putw);
+        for (uint32_t lane = 0; lane < FR_SELECT_WAVE && !lds.bad; lane++)
+            fr_select_pick(g, (uint32_t)block, lane, k, gete, getw,
+                           [&](size_t item, uint32_t slot, uint32_t sp, uint32_t lp, const uint32_t (&w)[FR_SELECT_EW]) {
+                               if (item >= k || slot >= d || slot_seen[item * d + slot]++) { outside = true; return; }
+                               fr_select_store(o, item, slot, sp, lp, w);
+                           },
+                           [&](size_t item, bool ok) {
+                               if (item >= k || item_seen[item]++) { outside = true; return; }
+                               ok_out[item] = ok ? 1 : 0;
+                           });
+        if (lds.bad || outside) return -2;
+    }
+    if (std::count(slot_seen.begin(), slot_seen.end(), 1) != (ptrdiff_t)(k * d) || std::count(item_seen.begin(), item_seen.end(), 1) != (ptrdiff_t)k) return -2;
+    if (geom_out) { geom_out[0] = g.lpi; geom_out[1] = g.ipb; geom_out[2] = g.chunks; geom_out[3] = g.pitch; geom_out[4] = g.large; geom_out[5] = g.shared; geom_out[6] = (uint32_t)grid; geom_out[7] = active; }
     stats_flush();
     return 0;
 }
