@@ -13,7 +13,7 @@ Host orchestration only; all group arithmetic goes through the engine (`bn254`).
 """
 import numpy as np
 
-from . import _buffers as bufs
+from . import _buffers as bufs, _plan
 from ._buffers import R_ORDER
 
 
@@ -95,8 +95,7 @@ def decrypt_batch(engine, g1, tau_powers, D, f_coeffs, sk, items, table=None, id
         P_rows.append(np.stack([np.asarray(D, dtype=np.uint8), np.asarray(pi, dtype=np.uint8).reshape(64), np.asarray(sk, dtype=np.uint8)]))
         Q_rows.append(np.asarray(C1, dtype=np.uint8).reshape(3, 128))
         c2.append(np.asarray(C2, dtype=np.uint8))
-    off = np.arange(0, 3 * len(items) + 1, 3)
-    X = engine.multi_pair(np.concatenate(P_rows), np.concatenate(Q_rows), off)
+    X = engine.multi_pair(np.concatenate(P_rows), np.concatenate(Q_rows), _plan.segments(len(items), 3))
     return engine.gt_div(np.stack(c2), X)
 
 
@@ -107,7 +106,7 @@ def decrypt_batch_arrays(engine, D, pi, sk, C1, C2):
     stated size.  D, pi, sk: [n,64]; C1: [n,3,128]; C2: [n,384]."""
     n = bufs.nbytes(D) // 64
     P = bufs.cat([bufs.view(D, n, 1, 64), bufs.view(pi, n, 1, 64), bufs.view(sk, n, 1, 64)], 1)
-    X = engine.multi_pair(bufs.flat(P), bufs.flat(bufs.view(C1, 3 * n, 128)), np.arange(0, 3 * n + 1, 3, dtype=np.uint64))
+    X = engine.multi_pair(bufs.flat(P), bufs.flat(bufs.view(C1, 3 * n, 128)), _plan.segments(n, 3))
     return engine.gt_div(bufs.flat(C2).reshape(n, 384), X)
 
 

@@ -20,7 +20,7 @@ reference's debug pairing / prints (access_tree_node.go:99-100,116-127).
 """
 import numpy as np
 
-from . import _buffers as bufs
+from . import _buffers as bufs, _plan
 from ._buffers import R_ORDER
 
 
@@ -116,8 +116,7 @@ def decrypt_batch(engine, folded, d_key, cts, neg_g1):
         # the folded key is the same G2 list for every ciphertext: its Miller lines are computed once for the whole batch
         X = engine.multi_pair_fixed_q(np.concatenate(P_rows), Q_seg)
     else:
-        off = np.arange(0, len(cts) * m + 1, m)
-        X = engine.multi_pair(np.concatenate(P_rows), np.concatenate([Q_seg] * len(cts)), off)
+        X = engine.multi_pair(np.concatenate(P_rows), np.concatenate([Q_seg] * len(cts)), _plan.segments(len(cts), m))
     return engine.gt_mul(np.stack(ctil), X)                                          # C~ * A / e(C, D) per ciphertext
 
 
@@ -181,48 +180,28 @@ def encrypt_batch(engine, tree_or_plan, h, e_alpha, h1, messages, s, coeffs, tab
     n = bufs.nbytes(messages) // 384
     if bufs.nbytes(messages) != n * 384:
         raise ValueError("messages must hold whole GT elements")
-    scalars = lambda v, what: v if bufs.is_torch(v) or isinstance(v, np.ndarray) else bufs.put(_scalar_bytes(v, what), messages)
-    s = scalars(s, "s")
-    coeffs = None if coeffs is None else scalars(coeffs, "coeffs")
+    s = _plan.scalars(s, messages)
+    coeffs = None if coeffs is None else _plan.scalars(coeffs, messages)
     bufs.device_of(messages, s, coeffs)                                              # all of one kind, on one device
     if bufs.nbytes(s) != n * 32:
         raise ValueError("s must hold n = %d scalars" % n)
-
-    def public(x, width, what):
-        if bufs.is_torch(x):
-            x = x.cpu().numpy()
-        x = np.array(x, dtype=np.uint8, copy=True).reshape(-1)
-        if x.size != width:
-            raise ValueError("%s must be %d bytes" % (what, width))
-        return bufs.put(x, messages)
-    tree = engine.ShareTree(nodes)
-    try:
-        if tree.leaves != L:
-            raise ValueError("the plan names %d attributes for %d leaves" % (L, tree.leaves))
+    with _share_tree(engine, nodes, L) as tree:
         shares = bufs.flat(tree.share(bufs.flat(s), None if coeffs is None or not bufs.nbytes(coeffs) else bufs.flat(coeffs)))          # [n, L, 32]
-    finally:
-        tree.close()
-    base = bufs.flat(bufs.expand(bufs.view(public(e_alpha, 384, "e_alpha"), 1, 384), n, 384))
-    c_tilde = engine.gt_mul(engine.gt_exp(base, bufs.flat(s)), bufs.flat(messages))
-    c = engine.g1_scalar_mul(public(h, 64, "h"), bufs.flat(s))
+    c_tilde = _plan.blind(engine, _plan.public(e_alpha, 1, 384, messages, "e_alpha"), s, messages, n)
+    c = engine.g1_scalar_mul(bufs.flat(_plan.public(h, 1, 64, messages, "h")), bufs.flat(s))
     cy = engine.g1_scalar_mul_base(shares)
     hy = bufs.put(np.stack([np.asarray(h1[a], dtype=np.uint8).reshape(64) for a in attributes]), messages)
     if tables and n:
-        index = np.arange(L, dtype=np.uint32).reshape(L, 1)
-        table = engine.FixedBase(hy, g2=False)
-        try:
-            cy_prime, _ = table.indexed(bufs.put(index.view(np.int32), messages) if bufs.is_torch(messages) else index, shares, terms=1)
-        finally:
-            table.close()
+        with _plan.handle(None, lambda: engine.FixedBase(hy, g2=False), "nbase", L, "the table holds %(got)d bases for %(want)d leaves") as table:
+            cy_prime, _ = table.indexed(_plan.index_rows(np.arange(L).reshape(L, 1), messages), shares, terms=1)
     else:
         cy_prime = engine.g1_scalar_mul(bufs.flat(bufs.expand(bufs.view(hy, 1, L, 64), n, L, 64)), shares)
     return bufs.view(c_tilde, n, 384), bufs.view(c, n, 64), bufs.view(cy, n, L, 64), bufs.view(cy_prime, n, L, 64)
 
 
-def _scalar_bytes(values, what):
-    """Python ints (a list, or a list of rows) as scalar rows modulo r"""
-    flat = [v for row in values for v in (row if isinstance(row, (list, tuple)) else [row])]
-    return np.frombuffer(b"".join((int(v) % R_ORDER).to_bytes(32, "little") for v in flat), dtype=np.uint8).reshape(-1, 32).copy()
+def _share_tree(engine, nodes, L):
+    """engine.ShareTree over the plan's nodes, closed on the way out; its leaves must be the plan's L attributes"""
+    return _plan.handle(None, lambda: engine.ShareTree(nodes), "leaves", L, "the plan names %(want)d attributes for %(got)d leaves")
 
 
 # ------------------------------------------------------------------------------------------------ Decrypt, one key per item
@@ -297,20 +276,13 @@ def decrypt_batch_keys(engine, tree_or_plan, held, d_key, dj, dj_prime, c_tilde,
         return a.cpu().numpy() if bufs.is_torch(a) else np.asarray(a)
     if not n:
         return bufs.zeros((0, 384), c), bufs.zeros((0,), c)
-    tree = engine.ShareTree(nodes)
-    try:
-        if tree.leaves != L:
-            raise ValueError("the plan names %d attributes for %d leaves" % (L, tree.leaves))
+    with _share_tree(engine, nodes, L) as tree:
         w, ok = tree.weights(bufs.flat(bufs.view(held, n * L)))                      # [n, L, 32] canonical, [n]
-    finally:
-        tree.close()
     w = bufs.view(w, n * L, 32)
-    ok_host = host(ok).reshape(n)
-    good = np.nonzero(ok_host)[0]
-    ng = len(good)
-    out = bufs.zeros((n, 384), c)
+    items = _plan.Good(host(ok).reshape(n), c)
+    good, ng = items.index, items.count
     if not ng:
-        return out, bufs.view(ok, n)
+        return items.scatter(None), bufs.view(ok, n)
     used = host(bufs.rows_nonzero(w)).reshape(n, L)[good]                            # a factor is never 0 modulo r: used <=> weight != 0
     index, mask, U = used_columns(used)
     flat_index = (good[:, None] * L + index).reshape(-1)
@@ -327,12 +299,10 @@ def decrypt_batch_keys(engine, tree_or_plan, held, d_key, dj, dj_prime, c_tilde,
         d_host = host(d_key).reshape(128)
         neg_d = bufs.expand(bufs.view(put(np.array(engine.g2_neg(d_host), dtype=np.uint8, copy=True)), 1, 1, 128), ng, 1, 128)
     else:
-        d_rows = bufs.take(bufs.view(d_key, n, 128), good)
+        d_rows = items.rows(bufs.view(d_key, n, 128))
         neg_d = bufs.view(engine.g2_sub(bufs.flat(bufs.zeros((ng, 128), c)), bufs.flat(d_rows)), ng, 1, 128)      # infinity - D
-    P = bufs.cat([folded, bufs.take(bufs.view(c, n, 64), good).reshape(ng, 1, 64)], 1)
+    P = bufs.cat([folded, items.rows(bufs.view(c, n, 64)).reshape(ng, 1, 64)], 1)
     Q = bufs.cat([gather(dj, 128), gather(dj_prime, 128), neg_d], 1)
-    m = 2 * U + 1
-    X = engine.multi_pair(bufs.flat(P), bufs.flat(Q), np.arange(0, ng * m + 1, m, dtype=np.uint64))
-    msgs = engine.gt_mul(bufs.flat(bufs.take(bufs.view(c_tilde, n, 384), good)), bufs.flat(X))
-    out[put(good)] = bufs.view(msgs, ng, 384)
-    return out, bufs.view(ok, n)
+    X = engine.multi_pair(bufs.flat(P), bufs.flat(Q), _plan.segments(ng, 2 * U + 1))
+    msgs = engine.gt_mul(bufs.flat(items.rows(bufs.view(c_tilde, n, 384))), bufs.flat(X))
+    return items.scatter(msgs), bufs.view(ok, n)

@@ -21,54 +21,12 @@ Host orchestration only, engine-agnostic (every function takes the engine: `bn25
 randomness r / s comes in as arguments (scalar rows, or Python integers).  Host arrays in give host arrays out; CUDA tensors in give
 CUDA tensors out, every step takes device rows and leaves device rows, and nothing per item crosses PCIe but what the caller passes
 in and takes out (the shared points and pairings, and integer arguments, travel once)."""
-import numpy as np
-
-from . import _buffers as bufs
-from ._buffers import R_ORDER
-
-
-def _ints(v):
-    """a scalar argument given as Python integers (one, a list, a list of lists), as one flat list; None for a buffer"""
-    if isinstance(v, (int, np.integer)):
-        return [int(v)]
-    if isinstance(v, (list, tuple)):
-        return [int(x) for row in v for x in (row if isinstance(row, (list, tuple)) else [row])]
-    return None
-
-
-def _scalars(k, n, like, what):
-    """n scalar rows, flat, of the kind of `like`: rows as they are, Python integers reduced mod r"""
-    ints = _ints(k)
-    if ints is not None:
-        k = bufs.put(np.frombuffer(b"".join((v % R_ORDER).to_bytes(32, "little") for v in ints), dtype=np.uint8).copy(), like)
-    if bufs.is_torch(k) != bufs.is_torch(like) or bufs.nbytes(k) != n * 32:
-        raise ValueError("%s must hold %d 32-byte scalars of the kind the other arguments are" % (what, n))
-    return bufs.flat(bufs.view(k, n * 32))
-
-
-def _shared(x, rows, width, like, what):
-    """public values, [rows, width] of the kind of `like`: a tensor as it is, host data copied and put there"""
-    if bufs.nbytes(x) != rows * width:
-        raise ValueError("%s must hold %d x %d bytes" % (what, rows, width))
-    if not bufs.is_torch(x):
-        x = bufs.put(np.array(x, dtype=np.uint8, copy=True).reshape(-1), like)
-    elif not bufs.is_torch(like):
-        raise ValueError("%s must be of the kind the other arguments are" % what)
-    return bufs.view(x, rows, width)
+from . import _buffers as bufs, _plan
 
 
 def _repeat(x, n, rows, width):
     """[rows, width] once per item: [n * rows * width], flat"""
     return bufs.flat(bufs.expand(bufs.view(x, 1, rows, width), n, rows, width))
-
-
-def _count(v, unit, what):
-    ints = _ints(v)
-    size = len(ints) if ints is not None else bufs.nbytes(v)
-    unit = 1 if ints is not None else unit
-    if size % unit:
-        raise ValueError("%s is not a whole number of rows of %d bytes" % (what, unit))
-    return size // unit
 
 
 def _k_of(rows, what):
@@ -85,8 +43,9 @@ def keygen_batch(engine, alpha, h, ids, r):
     (the inverse of 0 is 0 and [0] P is the point at infinity, so its lanes do no harm); every other identity is unaffected."""
     k = _k_of(bufs.nbytes(h) // 128 if bufs.nbytes(h) % 128 == 0 else 0, "h")
     h = bufs.view(h, k, 128)
-    n = _count(ids, 32, "ids")
-    ids, r, alpha = _scalars(ids, n, h, "ids"), _scalars(r, n * k, h, "r"), _scalars(alpha, 1, h, "alpha")
+    ids = _plan.scalars(ids, h)
+    n = bufs.nbytes(ids) // 32
+    ids, r, alpha = _plan.scalars(ids, h, n, "ids"), _plan.scalars(r, h, n * k, "r"), _plan.scalars(alpha, h, 1, "alpha")
     d = bufs.view(engine.fr_sub(_repeat(alpha, n, 1, 32), ids), n, 32)                    # alpha - ID, canonical
     ok = bufs.rows_nonzero(d)
     inv = engine.fr_inverse(bufs.flat(d))
@@ -100,8 +59,8 @@ def public_pairings(engine, g1, g2, h):
     """(e_gg [384], e_gh [k, 384]): e(g1, g2) and e(g1, h_j), one pair_batch of 1 + k pairs per public parameters."""
     k = _k_of(bufs.nbytes(h) // 128 if bufs.nbytes(h) % 128 == 0 else 0, "h")
     h = bufs.view(h, k, 128)
-    P = _repeat(_shared(g1, 1, 64, h, "g1"), 1 + k, 1, 64)
-    Q = bufs.flat(bufs.cat([_shared(g2, 1, 128, h, "g2"), h], 0))
+    P = _repeat(_plan.public(g1, 1, 64, h, "g1"), 1 + k, 1, 64)
+    Q = bufs.flat(bufs.cat([_plan.public(g2, 1, 128, h, "g2"), h], 0))
     e = bufs.view(engine.pair_batch(P, Q), 1 + k, 384)
     return e[0], e[1:]
 
@@ -121,10 +80,10 @@ def encrypt_batch(engine, g1_alpha, e_gg, e_gh, messages, ids, s):
     if bufs.nbytes(messages) != n * 384:
         raise ValueError("messages are GT elements, rows of 384 bytes")
     messages = bufs.view(messages, n, 384)
-    ids, s = _scalars(ids, n, messages, "ids"), _scalars(s, n, messages, "s")
-    e_gg, e_gh = _shared(e_gg, 1, 384, messages, "e_gg"), _shared(e_gh, k, 384, messages, "e_gh")
+    ids, s = _plan.scalars(ids, messages, n, "ids"), _plan.scalars(s, messages, n, "s")
+    e_gg, e_gh = _plan.public(e_gg, 1, 384, messages, "e_gg"), _plan.public(e_gh, k, 384, messages, "e_gh")
     neg_s = engine.fr_neg(s)
-    u = engine.g1_add(engine.g1_scalar_mul(bufs.flat(_shared(g1_alpha, 1, 64, messages, "g1_alpha")), s),
+    u = engine.g1_add(engine.g1_scalar_mul(bufs.flat(_plan.public(g1_alpha, 1, 64, messages, "g1_alpha")), s),
                       engine.g1_scalar_mul_base(engine.fr_mul(bufs.flat(neg_s), ids)))
     vw = bufs.view(engine.gt_exp(bufs.cat([_repeat(e_gg, n, 1, 384), _repeat(e_gh[0], n, 1, 384)]), bufs.cat([s, bufs.flat(neg_s)])), 2, n, 384)
     v = vw[0]
@@ -152,17 +111,7 @@ def decrypt_batch(engine, key, u, v, w, y=None):
     k = 1 if y is None else 3
     u, v, w = bufs.view(u, n, 64), bufs.view(v, n, 384), bufs.view(w, n, 384)
     rids, hids = key
-
-    def rows(x, width, what):
-        if not bufs.is_torch(x):
-            x = bufs.put(np.array(x, dtype=np.uint8, copy=True).reshape(-1), u)
-        elif not bufs.is_torch(u):
-            raise ValueError("the key must be of the kind the ciphertexts are")
-        if bufs.nbytes(x) not in (k * width, n * k * width):
-            raise ValueError("%s must hold %d rows of %d bytes, or as many per ciphertext" % (what, k, width))
-        x = bufs.view(x, -1, k, width)
-        return x if x.shape[0] == n else bufs.expand(x, n, k, width)
-    rids, hids = rows(rids, 32, "rids"), rows(hids, 128, "hids")
+    rids, hids = _plan.per_item(rids, n, k, 32, u, "rids"), _plan.per_item(hids, n, k, 128, u, "hids")
     if not n:
         return bufs.view(w, 0, 384), bufs.empty((0,), u)
     if k == 1:

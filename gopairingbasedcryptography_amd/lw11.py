@@ -29,8 +29,9 @@ Host orchestration only, engine-agnostic (every function takes the engine: `bn25
 the elimination is per policy, microseconds in Python integers, and stays on the host."""
 import numpy as np
 
-from . import _buffers as bufs
+from . import _buffers as bufs, _plan
 from ._buffers import R_ORDER
+from ._plan import INDEX_NONE      # noqa: F401 (for callers that build index rows themselves)
 
 
 def reconstruction_weights(matrix, rho, attributes):
@@ -102,8 +103,8 @@ def decrypt_batch(engine, folded, c0, c1, c2, c3):
         return bufs.take(bufs.view(c, n, -1, width), rows, 1)
     P = bufs.expand(bufs.put(np.concatenate([A, B]).reshape(1, 2 * k, 64), c0), n, 2 * k, 64)
     Q = bufs.cat([used(c3, 128), used(c2, 128)], 1)
-    E = engine.multi_pair(bufs.flat(P), bufs.flat(Q), np.arange(0, 2 * k * n + 1, 2 * k, dtype=np.uint64))
-    F = engine.gt_multi_exp(bufs.flat(used(c1, 384)), weights, np.arange(0, k * n + 1, k, dtype=np.uint64))
+    E = engine.multi_pair(bufs.flat(P), bufs.flat(Q), _plan.segments(n, 2 * k))
+    F = engine.gt_multi_exp(bufs.flat(used(c1, 384)), weights, _plan.segments(n, k))
     return engine.gt_div(bufs.flat(c0).reshape(n, 384), engine.gt_mul(E, F))
 
 
@@ -119,20 +120,17 @@ def decrypt_batch_msm(engine, folded, h_gid, c0, c1, c2, c3):
 
     def used(c, width):
         return bufs.take(bufs.view(c, n, -1, width), rows, 1)
-    table = np.arange(0, k * n + 1, k, dtype=np.uint64)
+    table = _plan.segments(n, k)
     S = engine.g2_multi_scalar_mul(bufs.flat(used(c3, 128)), weights, table).reshape(n, 1, 128)
     hb = np.concatenate([np.asarray(h_gid, dtype=np.uint8).reshape(1, 64), B])
     P = bufs.expand(bufs.put(hb.reshape(1, k + 1, 64), c0), n, k + 1, 64)
     Q = bufs.cat([S, used(c2, 128)], 1)
-    E = engine.multi_pair(bufs.flat(P), bufs.flat(Q), np.arange(0, (k + 1) * n + 1, k + 1, dtype=np.uint64))
+    E = engine.multi_pair(bufs.flat(P), bufs.flat(Q), _plan.segments(n, k + 1))
     F = engine.gt_multi_exp(bufs.flat(used(c1, 384)), weights, table)
     return engine.gt_div(bufs.flat(c0).reshape(n, 384), engine.gt_mul(E, F))
 
 
 # ------------------------------------------------------------------------------------------------ Encrypt
-INDEX_NONE = 0xFFFFFFFF
-
-
 def encrypt_table(engine, g2_y, g2=None):
     """The G2 fixed-base table of encrypt_batch over (g2, g2^y_u ...), u in ascending order: built once, passed as `table` to any number
     of calls, closed by the caller.  g2: the generator's 128 bytes (None: engine.generators()[1])."""
@@ -167,13 +165,7 @@ def encrypt_batch(engine, e, egg_alpha, g2_y, matrix, rho, messages, s, v, w, r,
     n = bufs.nbytes(messages) // 384
     if bufs.nbytes(messages) != n * 384:
         raise ValueError("messages must hold whole GT elements")
-
-    def scalars(x):
-        if x is None or bufs.is_torch(x) or isinstance(x, np.ndarray):
-            return x
-        flat = [y for row in x for y in (row if isinstance(row, (list, tuple)) else [row])]
-        return bufs.put(np.frombuffer(b"".join((int(y) % R_ORDER).to_bytes(32, "little") for y in flat), dtype=np.uint8).reshape(-1, 32).copy(), messages)
-    s, v, w, r = scalars(s), scalars(v), scalars(w), scalars(r)
+    s, v, w, r = (x if x is None else _plan.scalars(x, messages) for x in (s, v, w, r))
     bufs.device_of(messages, s, v, w, r)                                       # one kind of buffer, one device
     size = lambda x: 0 if x is None else bufs.nbytes(x)
     if size(s) != n * 32 or size(v) != n * (C - 1) * 32 or size(w) != n * (C - 1) * 32 or size(r) != n * R * 32:
@@ -183,7 +175,7 @@ def encrypt_batch(engine, e, egg_alpha, g2_y, matrix, rho, messages, s, v, w, r,
         return z(0, 384), z(0, R, 384), z(0, R, 128), z(0, R, 128)
     put = lambda a: bufs.put(np.ascontiguousarray(a), messages)
     s3 = bufs.view(s, n, 1, 32)
-    mat = put(np.frombuffer(b"".join((int(x) % R_ORDER).to_bytes(32, "little") for row in matrix for x in row), dtype=np.uint8).copy())
+    mat = put(_plan.scalar_rows(x for row in matrix for x in row).reshape(-1))
     vec_s = s3 if C == 1 else bufs.cat([s3, bufs.view(v, n, C - 1, 32)], 1)
     vec_0 = bufs.zeros((n, 1, 32), messages) if C == 1 else bufs.cat([bufs.zeros((n, 1, 32), messages), bufs.view(w, n, C - 1, 32)], 1)
     lam = engine.fr_lsss_shares(mat, bufs.flat(vec_s), R, C)                   # [n, R, 32]
@@ -192,20 +184,11 @@ def encrypt_batch(engine, e, egg_alpha, g2_y, matrix, rho, messages, s, v, w, r,
     # c1x = e^lambda_x (e^alpha_rho(x))^r_x: one segment of two factors per (ciphertext, row)
     pairs = np.stack([np.stack([np.asarray(e, dtype=np.uint8).reshape(384), np.asarray(egg_alpha[u], dtype=np.uint8).reshape(384)]) for u in rho])     # [R, 2, 384]
     gt_bases = bufs.flat(bufs.expand(bufs.view(put(pairs), 1, 2 * R, 384), n, 2 * R, 384))
-    c1 = engine.gt_multi_exp(gt_bases, bufs.flat(bufs.cat([bufs.view(lam, n * R, 1, 32), r2], 1)), np.arange(0, 2 * n * R + 1, 2, dtype=np.uint64))
+    c1 = engine.gt_multi_exp(gt_bases, bufs.flat(bufs.cat([bufs.view(lam, n * R, 1, 32), r2], 1)), _plan.segments(n * R, 2))
     c2 = engine.g2_scalar_mul_base(bufs.flat(r))
     # c3x = [r_x] g2^y_rho(x) + [omega_x] g2: base 0 is g2, base 1 + i the i-th public key; the R index rows repeat per ciphertext
-    index = np.array([[1 + where[u], 0] for u in rho], dtype=np.uint32)
-    index = bufs.put(index.view(np.int32), messages) if bufs.is_torch(messages) else index
-    own = table is None
-    table = encrypt_table(engine, g2_y) if own else table
-    try:
-        if table.nbase != 1 + len(attrs):
-            raise ValueError("the table holds %d bases, the public keys need %d" % (table.nbase, 1 + len(attrs)))
+    index = _plan.index_rows(np.array([[1 + where[u], 0] for u in rho]), messages)
+    with _plan.handle(table, lambda: encrypt_table(engine, g2_y), "nbase", 1 + len(attrs), "the table holds %(got)d bases, the public keys need %(want)d") as table:
         c3, ok = table.indexed(index, bufs.flat(bufs.cat([r2, bufs.view(om, n * R, 1, 32)], 1)), terms=2)
-    finally:
-        if own:
-            table.close()
-    eb = bufs.flat(bufs.expand(bufs.view(put(np.asarray(e, dtype=np.uint8).reshape(384)), 1, 384), n, 384))
-    c0 = engine.gt_mul(engine.gt_exp(eb, bufs.flat(s)), bufs.flat(messages))
+    c0 = _plan.blind(engine, put(np.asarray(e, dtype=np.uint8).reshape(384)), s, messages, n)
     return bufs.view(c0, n, 384), bufs.view(c1, n, R, 384), bufs.view(c2, n, R, 128), bufs.view(c3, n, R, 128)

@@ -24,20 +24,8 @@ them): the selection is engine.fr_find_common, its `common` rows are the Lagrang
 device, and only ok (n bytes) comes back to the host — the call's one wait.  Both forms give the same bytes."""
 import numpy as np
 
-from . import _buffers as bufs
+from . import _buffers as bufs, _plan
 from ._buffers import R_ORDER
-
-
-def _scalar_rows(values):
-    """attribute values -> scalar rows (the values of a batch repeat: each distinct one is converted once)"""
-    cache = {}
-
-    def row(v):
-        b = cache.get(v)
-        if b is None:
-            b = cache[v] = (int(v) % R_ORDER).to_bytes(32, "little")
-        return b
-    return np.frombuffer(b"".join([row(v) for v in values]), dtype=np.uint8).reshape(-1, 32).copy()      # writable: it may become a tensor
 
 
 def attribute_rows(values):
@@ -48,12 +36,12 @@ def attribute_rows(values):
         a = len(values[0])
         if any(len(v) != a for v in values):
             raise ValueError("every row needs %d values" % a)
-        return _scalar_rows(x for v in values for x in v).reshape(len(values), a, 32)
-    return _scalar_rows(values)
+        return _plan.scalar_rows(values).reshape(len(values), a, 32)
+    return _plan.scalar_rows(values)
 
 
 def _is_rows(x):
-    return (bufs.is_torch(x) or isinstance(x, np.ndarray)) and len(x.shape) == 3 and x.shape[2] == 32 and str(x.dtype) in ("uint8", "torch.uint8")
+    return _plan.is_buffer(x) and len(x.shape) == 3 and x.shape[2] == 32 and str(x.dtype) in ("uint8", "torch.uint8")
 
 
 def select_common(key_attrs, ct_attrs, d):
@@ -102,19 +90,25 @@ class _Plan:
             raise ValueError("every ciphertext of a batch needs the same number of attributes")
         if bufs.nbytes(E) != self.n * a * 128 or bufs.nbytes(e_prime) != self.n * 384:
             raise ValueError("E must hold n x %d G2 points and e_prime n GT elements (n = %d)" % (a, self.n))
-        self.key_pos, self.ct_pos, self.ok = select_common(key_attrs, ct_attrs, d)
-        self.good = np.nonzero(self.ok)[0]
-        ng = self.ng = len(self.good)
         self.E, self.e_prime = bufs.view(E, self.n, a, 128), bufs.view(e_prime, self.n, 384)
-        if not ng:
+        self.key_pos, self.ct_pos, ok = select_common(key_attrs, ct_attrs, d)
+        if not self._select(ok):
             return
         pos = self.ct_pos.tolist()
-        sets = _scalar_rows(ct_attrs[t][p] for t in self.good.tolist() for p in pos[t])
-        self.delta = engine.fr_lagrange_basis(self.put(sets).reshape(-1), d).reshape(ng * d, 32)           # x = 0, the nodes are the set
-        self.seg = lambda pairs: np.arange(0, pairs * ng + 1, pairs, dtype=np.uint64)
+        sets = _plan.scalar_rows(ct_attrs[t][p] for t in self.good.tolist() for p in pos[t])
+        self.delta = engine.fr_lagrange_basis(self.put(sets).reshape(-1), d).reshape(self.ng * d, 32)      # x = 0, the nodes are the set
+
+    def _select(self, ok):
+        """the decryptable ciphertexts from the host's ok; their count"""
+        self.ok, self.items = ok, _plan.Good(ok, self.E)
+        self.good, self.ng, self.rows = self.items.index, self.items.count, self.items.rows
+        return self.ng
 
     def put(self, a):
         return bufs.put(a, self.E)
+
+    def seg(self, pairs):
+        return _plan.segments(self.ng, pairs)
 
     def key_rows(self, comp, width):
         """the key component at the selected positions: [ng, d, width]"""
@@ -125,16 +119,9 @@ class _Plan:
         index = (self.good[:, None] * self.E.shape[1] + self.ct_pos[self.good]).reshape(-1)
         return bufs.take(self.E.reshape(-1, 128), index).reshape(self.ng, self.d, 128)
 
-    def rows(self, a):
-        """the decryptable ciphertexts' rows of a per-ciphertext array"""
-        return bufs.take(a, self.good)
-
     def scatter(self, msgs):
         """messages of the decryptable ciphertexts into n rows; the others stay all zero"""
-        out = bufs.zeros((self.n, 384), self.E)
-        if self.ng:
-            out[self.put(self.good)] = msgs.reshape(self.ng, 384)
-        return out, self.put(self.ok.copy())
+        return self.items.scatter(msgs), self.put(self.ok.copy())
 
 
 class _RowsPlan(_Plan):
@@ -145,7 +132,7 @@ class _RowsPlan(_Plan):
             raise ValueError("d must be at least 1 (got %s)" % d)
         self.engine, self.d, self.n = engine, d, int(ct_attrs.shape[0])
         n, a = self.n, int(ct_attrs.shape[1])
-        if not bufs.is_torch(key_attrs) and not isinstance(key_attrs, np.ndarray):
+        if not _plan.is_buffer(key_attrs):
             key_attrs = bufs.put(attribute_rows(key_attrs), ct_attrs)                         # converted once
         shape = tuple(key_attrs.shape)
         if len(shape) not in (2, 3) or shape[-1] != 32 or (len(shape) == 3 and shape[0] != n):
@@ -155,18 +142,15 @@ class _RowsPlan(_Plan):
         if bufs.nbytes(E) != n * a * 128 or bufs.nbytes(e_prime) != n * 384:
             raise ValueError("E must hold n x %d G2 points and e_prime n GT elements (n = %d)" % (a, n))
         self.E, self.e_prime = bufs.view(E, n, a, 128), bufs.view(e_prime, n, 384)
-        self.ok, self.good, self.ng = np.zeros(n, dtype=np.uint8), np.zeros(0, dtype=np.int64), 0
         if not n:
+            self._select(np.zeros(0, dtype=np.uint8))
             return
         set_pos, list_pos, common, ok = engine.fr_find_common(bufs.flat(key_attrs), bufs.flat(ct_attrs), self.m, a, d)
-        self.ok = np.array(ok.cpu().numpy() if bufs.is_torch(ok) else ok, dtype=np.uint8, copy=True).reshape(n)      # the one wait
-        self.good = np.nonzero(self.ok)[0]
-        ng = self.ng = len(self.good)
+        ng = self._select(np.array(ok.cpu().numpy() if bufs.is_torch(ok) else ok, dtype=np.uint8, copy=True).reshape(n))      # the one wait
         if not ng:
             return
         self.key_pos, self.ct_pos = bufs.take(set_pos.reshape(n, d), self.good), bufs.take(list_pos.reshape(n, d), self.good)
         self.delta = engine.fr_lagrange_basis(bufs.flat(bufs.take(common.reshape(n, d * 32), self.good)), d).reshape(ng * d, 32)
-        self.seg = lambda pairs: np.arange(0, pairs * ng + 1, pairs, dtype=np.uint64)
 
     def _index(self, pos, width):
         """positions inside the rows of the decryptable items as positions in the flattened [n x width] table"""
@@ -183,7 +167,7 @@ class _RowsPlan(_Plan):
         return bufs.take(self.E.reshape(-1, 128), self._index(self.ct_pos, self.a)).reshape(self.ng, self.d, 128)
 
 
-def _plan(engine, key_attrs, d, ct_attrs, E, e_prime):
+def _plan_for(engine, key_attrs, d, ct_attrs, E, e_prime):
     return (_RowsPlan if _is_rows(ct_attrs) else _Plan)(engine, key_attrs, d, ct_attrs, E, e_prime)
 
 
@@ -198,7 +182,7 @@ def decrypt_batch(engine, key, d, ct_attrs, E, e_prime):
     is.  attrs is then [m, 32] rows or a list of integers (converted once), D [m, 64]; or a key per item — attrs [n, m, 32] with
     D [n, m, 64] — for n (key, ciphertext) pairs.  The selection is engine.fr_find_common; messages and ok are those of the integer form."""
     attrs, D = key
-    p = _plan(engine, attrs, d, ct_attrs, E, e_prime)
+    p = _plan_for(engine, attrs, d, ct_attrs, E, e_prime)
     if not p.ng:
         return p.scatter(None)
     P = engine.g1_scalar_mul(bufs.flat(p.key_rows(D, 64)), bufs.flat(p.delta))
@@ -213,7 +197,7 @@ def decrypt_batch_large(engine, key, d, ct_attrs, E, e_pp, e_prime):
     d + 1 pairs, which sums [Delta_i] D_i in G2 per ciphertext, is not built.)  The rows form is decrypt_batch's, with d_i [m, 64] and
     D_i [m, 128], or [n, m, 64] and [n, m, 128] with a key per item."""
     attrs, di, Di = key
-    p = _plan(engine, attrs, d, ct_attrs, E, e_prime)
+    p = _plan_for(engine, attrs, d, ct_attrs, E, e_prime)
     if bufs.nbytes(e_pp) != p.n * 64 or bufs.is_torch(e_pp) != bufs.is_torch(p.E):
         raise ValueError("e_pp must hold n G1 points of the kind E is")
     if not p.ng:
@@ -243,16 +227,16 @@ def compute_t(engine, table, n, xs, nodes=None):
     nodes = list(range(n + 1)) if nodes is None else [int(v) for v in nodes]
     if len(nodes) != n + 1 or table.nbase != n + 2:
         raise ValueError("need n + 1 = %d nodes and a table of n + 2 bases" % (n + 1))
-    if not bufs.is_torch(xs) and not isinstance(xs, np.ndarray):
-        xs = _scalar_rows(xs)
+    if not _plan.is_buffer(xs):
+        xs = _plan.scalar_rows(xs)
     xs = bufs.view(xs, -1, 32)
     k = xs.shape[0]
 
     def put(a):
         return bufs.put(a, xs)
     flat = bufs.flat(xs)
-    delta = engine.fr_lagrange_basis(put(_scalar_rows(range(1, n + 2))).reshape(-1), n + 1, put(_scalar_rows(nodes)).reshape(-1), n + 1, flat).reshape(k, n + 1, 32)
-    acc = engine.fr_mul(flat, put(_scalar_rows([1])).reshape(-1))                         # x, canonical
+    delta = engine.fr_lagrange_basis(put(_plan.scalar_rows(range(1, n + 2))).reshape(-1), n + 1, put(_plan.scalar_rows(nodes)).reshape(-1), n + 1, flat).reshape(k, n + 1, 32)
+    acc = engine.fr_mul(flat, put(_plan.scalar_rows([1])).reshape(-1))                         # x, canonical
     base = acc
     for bit in bin(n)[3:]:
         acc = engine.fr_mul(bufs.flat(acc), bufs.flat(acc))
@@ -268,12 +252,12 @@ def compute_t(engine, table, n, xs, nodes=None):
 # one launch.  The randomness is passed in.  Ragged attribute counts are the caller's to group: rows are rectangular.
 def _matrix(x, like, what):
     """(buffer [rows, cols, 32], rows, cols) of a scalar matrix: nested Python ints [rows][cols], or a [rows, cols, 32] uint8 array / tensor"""
-    if not bufs.is_torch(x) and not isinstance(x, np.ndarray):
+    if not _plan.is_buffer(x):
         grid = [list(r) for r in x]
         cols = len(grid[0]) if grid else 0
         if any(len(r) != cols for r in grid):
             raise ValueError("%s: every row needs %d scalars" % (what, cols))
-        x = _scalar_rows(v for r in grid for v in r).reshape(len(grid), cols, 32)
+        x = _plan.scalar_rows(grid).reshape(len(grid), cols, 32)
         if like is not None:
             x = bufs.put(x, like)
     if len(x.shape) != 3 or x.shape[2] != 32:
@@ -289,7 +273,7 @@ def _shares(engine, y, coeffs, attrs):
     if kc != k:
         raise ValueError("coeffs needs one row per user (got %d, k = %d)" % (kc, k))
     bufs.device_of(attrs, coeffs)
-    y = bufs.put(_scalar_rows([y]) if isinstance(y, int) else np.array(y, dtype=np.uint8, copy=True).reshape(1, 32), attrs)
+    y = bufs.put(_plan.scalar_rows(y) if isinstance(y, int) else np.array(y, dtype=np.uint8, copy=True).reshape(1, 32), attrs)
     rows = bufs.cat([bufs.expand(bufs.view(y, 1, 1, 32), k, 1, 32), coeffs], 1)                     # [k, d, 32]: q_j, constant term first
     q = engine.fr_poly_eval(bufs.flat(rows), bufs.flat(attrs), dm1 + 1, m)
     return bufs.view(q, k, m, 32), attrs, k, m

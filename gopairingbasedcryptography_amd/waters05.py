@@ -23,8 +23,7 @@ import hashlib
 
 import numpy as np
 
-from . import _buffers as bufs
-from ._buffers import R_ORDER
+from . import _buffers as bufs, _plan
 
 ID_BITS, ID_BYTES = 256, 32
 
@@ -66,26 +65,15 @@ def _masks(masks):
     return bufs.view(masks, -1, ID_BYTES)
 
 
-def _scalars(k, n, like, what):
-    """n scalar rows of the kind of `like`: rows as they are, Python integers reduced mod r"""
-    if isinstance(k, (list, tuple)):
-        k = bufs.put(np.frombuffer(b"".join((int(v) % R_ORDER).to_bytes(32, "little") for v in k), dtype=np.uint8).copy(), like)
-    if bufs.is_torch(k) != bufs.is_torch(like) or bufs.nbytes(k) != n * 32:
-        raise ValueError("%s must hold one 32-byte scalar per identity (%d), of the kind the masks are" % (what, n))
-    return bufs.flat(bufs.view(k, n, 32))
-
-
 def keygen_batch(engine, table, g2_alpha, masks, r):
     """(d1 [n, 128], d2 [n, 64]) for n identities: d2 = [r] g1 (g1_scalar_mul_base), d1 = g2^alpha + [r] H(id) (table.sum,
     g2_scalar_mul, g2_add with the one shared g2^alpha)."""
     masks = _masks(masks)
     n = masks.shape[0]
-    r = _scalars(r, n, masks, "r")
-    if bufs.nbytes(g2_alpha) != 128:
-        raise ValueError("g2_alpha is one G2 point")
+    r = _plan.scalars(r, masks, n, "r")
+    ga = bufs.flat(_plan.public(g2_alpha, 1, 128, masks, "g2_alpha"))
     d2 = engine.g1_scalar_mul_base(r)
     h = table.sum(masks)
-    ga = bufs.flat(g2_alpha) if bufs.is_torch(g2_alpha) else bufs.put(np.array(g2_alpha, dtype=np.uint8, copy=True).reshape(-1), masks)
     d1 = engine.g2_add(engine.g2_scalar_mul(bufs.flat(h), r), ga)
     return bufs.view(d1, n, 128), bufs.view(d2, n, 64)
 
@@ -95,12 +83,10 @@ def encrypt_batch(engine, table, e_alpha, messages, masks, t):
     GT element, is replicated and raised to t by gt_exp, c1 = gt_mul(that, M); c2 = [t] g1; c3 = [t] H(id)."""
     masks = _masks(masks)
     n = masks.shape[0]
-    t = _scalars(t, n, masks, "t")
-    if bufs.nbytes(e_alpha) != 384 or bufs.nbytes(messages) != n * 384 or bufs.is_torch(messages) != bufs.is_torch(masks):
-        raise ValueError("need one GT element e_alpha and n = %d messages of the kind the masks are" % n)
-    e = e_alpha if bufs.is_torch(e_alpha) else bufs.put(np.array(e_alpha, dtype=np.uint8, copy=True).reshape(-1), masks)
-    base = bufs.flat(bufs.expand(bufs.view(e, 1, 384), n, 384))
-    c1 = engine.gt_mul(engine.gt_exp(base, t), bufs.flat(messages))
+    t = _plan.scalars(t, masks, n, "t")
+    if bufs.nbytes(messages) != n * 384 or bufs.is_torch(messages) != bufs.is_torch(masks):
+        raise ValueError("need n = %d messages of the kind the masks are" % n)
+    c1 = _plan.blind(engine, _plan.public(e_alpha, 1, 384, masks, "e_alpha"), t, messages, n)
     c2 = engine.g1_scalar_mul_base(t)
     c3 = engine.g2_scalar_mul(bufs.flat(table.sum(masks)), t)
     return bufs.view(c1, n, 384), bufs.view(c2, n, 64), bufs.view(c3, n, 128)
@@ -116,21 +102,11 @@ def decrypt_batch(engine, key, c1, c2, c3):
     if bufs.nbytes(c1) != n * 384 or bufs.nbytes(c2) != n * 64 or bufs.nbytes(c3) != n * 128:
         raise ValueError("c1, c2, c3 must hold n GT, G1 and G2 elements")
     c2, c3 = bufs.view(c2, n, 1, 64), bufs.view(c3, n, 1, 128)
-
-    def rows(k, width, what):
-        if not bufs.is_torch(k):
-            k = bufs.put(np.array(k, dtype=np.uint8, copy=True).reshape(-1), c2)
-        elif not bufs.is_torch(c2):
-            raise ValueError("the key must be of the kind the ciphertexts are")
-        if bufs.nbytes(k) not in (width, n * width):
-            raise ValueError("%s must hold one point or one per ciphertext" % what)
-        k = bufs.view(k, -1, 1, width)
-        return k if k.shape[0] == n else bufs.expand(k, n, 1, width)
-    d1, d2 = rows(d1, 128, "d1"), rows(d2, 64, "d2")
+    d1, d2 = _plan.per_item(d1, n, 1, 128, c2, "d1"), _plan.per_item(d2, n, 1, 64, c2, "d2")
     if not n:
         return bufs.view(c1, 0, 384)
     neg_c2 = bufs.view(engine.g1_sub(bufs.zeros((n * 64,), c2), bufs.flat(c2)), n, 1, 64)
     P = bufs.flat(bufs.cat([d2, neg_c2], 1))                                     # [n, 2, 64]: (d2, -c2)
     Q = bufs.flat(bufs.cat([c3, d1], 1))                                         # [n, 2, 128]: (c3, d1)
-    pairs = engine.multi_pair(P, Q, np.arange(0, 2 * n + 1, 2, dtype=np.uint64))
+    pairs = engine.multi_pair(P, Q, _plan.segments(n, 2))
     return bufs.view(engine.gt_mul(bufs.flat(c1), bufs.flat(pairs)), n, 384)

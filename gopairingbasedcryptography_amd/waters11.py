@@ -32,12 +32,11 @@ import collections
 
 import numpy as np
 
-from . import _buffers as bufs
-from ._buffers import R_ORDER
+from . import _buffers as bufs, _plan
+from ._plan import INDEX_NONE, NO_ATTRIBUTE      # noqa: F401 (INDEX_NONE: for callers that build index rows themselves)
 from .lw11 import reconstruction_weights
 
 Padded = collections.namedtuple("Padded", "matrix rho rows cols")      # matrix [n, R, C, 32] uint8 scalars; rho [n, R] int64, -1 = padding
-NO_ATTRIBUTE = -1
 
 
 def pad_policies(policies, rows=None, cols=None):
@@ -60,7 +59,7 @@ def pad_policies(policies, rows=None, cols=None):
                 raise ValueError("policy %d: attributes must be integers in [0, 2^63)" % t)
             one = np.zeros((R, C, 32), dtype=np.uint8)
             if r and c:
-                one[:r, :c] = np.frombuffer(b"".join((int(v) % R_ORDER).to_bytes(32, "little") for row in m for v in row), dtype=np.uint8).reshape(r, c, 32)
+                one[:r, :c] = _plan.scalar_rows(v for row in m for v in row).reshape(r, c, 32)
             att = np.full(R, NO_ATTRIBUTE, dtype=np.int64)
             att[:r] = [int(a) for a in rho]
             done[key] = (one, att)
@@ -104,7 +103,7 @@ def _row_sums_composed(engine, cx, nw, n, R):
 
 def _row_sums_msm(engine, cx, nw, n, R):
     """the same sums from one segmented multi-scalar multiplication: n segments of R terms, the doublings shared by four terms"""
-    return engine.g1_multi_scalar_mul(bufs.flat(cx), bufs.flat(nw), np.arange(0, n * R + 1, R, dtype=np.uint64))
+    return engine.g1_multi_scalar_mul(bufs.flat(cx), bufs.flat(nw), _plan.segments(n, R))
 
 
 def _decrypt(engine, key, pad, c, c_prime, cx, dx, weights, row_sums=_row_sums_composed):
@@ -135,7 +134,7 @@ def _decrypt(engine, key, pad, c, c_prime, cx, dx, weights, row_sums=_row_sums_c
     l_rows = put(np.broadcast_to(np.asarray(L, dtype=np.uint8).reshape(1, 1, 128), (n, 1, 128)))
     P = bufs.cat([k_rows, S.reshape(n, 1, 64), T], 1)
     Q = bufs.cat([c_prime, l_rows, dx], 1)
-    E = engine.multi_pair(bufs.flat(P), bufs.flat(Q), np.arange(0, (R + 2) * n + 1, R + 2, dtype=np.uint64))
+    E = engine.multi_pair(bufs.flat(P), bufs.flat(Q), _plan.segments(n, R + 2))
     msgs = engine.gt_div(bufs.flat(c), bufs.flat(E)).reshape(n, 384)
     ok = ok.reshape(n)
     return msgs * ok.reshape(n, 1), ok                                         # ok is 0 / 1: a row that cannot be decrypted comes back all zero
@@ -169,8 +168,7 @@ def decrypt_batch_host_weights(engine, key, policies, c, c_prime, cx, dx):
             got = reconstruction_weights(m, rho, attrs) if len(m) else None
             if got is not None:
                 ok[t] = 1
-                for x, wx in zip(*got):
-                    w[t, x] = np.frombuffer(int(wx).to_bytes(32, "little"), dtype=np.uint8)
+                w[t, got[0]] = _plan.scalar_rows(got[1])
         return put(w), put(ok)
     return _decrypt(engine, key, pad, c, c_prime, cx, dx, weights)
 
@@ -180,9 +178,6 @@ def decrypt_batch_host_weights(engine, key, policies, c, c_prime, cx, dx):
 # they are sums over ONE fixed-base table (engine.FixedBase.indexed): base 0 is g1^a, base 1 + i the h of the i-th attribute in
 # ascending order.  The shares are engine.fr_lsss_shares on the padded matrices as decrypt_batch takes them.  The randomness is passed
 # in, as in bsw07.encrypt_batch.
-INDEX_NONE = 0xFFFFFFFF
-
-
 def _universe(h):
     attrs = sorted(int(u) for u in h)
     if any(a < 0 for a in attrs):
@@ -213,26 +208,9 @@ def _attribute_positions(table_attrs, wanted, what):
     return np.where(real, pos + 1, NO_ATTRIBUTE)
 
 
-def _index_rows(rows, like):
-    """an index table for FixedBase.indexed of the kind of `like`: uint32 on the host, the same bits as int32 on the device"""
-    idx = np.ascontiguousarray(np.where(rows < 0, INDEX_NONE, rows).astype(np.uint32))
-    return bufs.put(idx.view(np.int32), like) if bufs.is_torch(like) else idx
-
-
-def _scalars(v, like):
-    if bufs.is_torch(v) or isinstance(v, np.ndarray):
-        return v
-    flat = [x for row in v for x in (row if isinstance(row, (list, tuple)) else [row])]
-    return bufs.put(np.frombuffer(b"".join((int(x) % R_ORDER).to_bytes(32, "little") for x in flat), dtype=np.uint8).reshape(-1, 32).copy(), like)
-
-
-def _public(x, width, what, like):
-    if bufs.is_torch(x):
-        x = x.cpu().numpy()
-    x = np.array(x, dtype=np.uint8, copy=True).reshape(-1)
-    if x.size != width:
-        raise ValueError("%s must be %d bytes" % (what, width))
-    return bufs.put(x, like)
+def _table(engine, table, g1a, h, attrs):
+    """the caller's table, or encrypt_table's for this call alone; either way over g1^a and the whole universe"""
+    return _plan.handle(table, lambda: encrypt_table(engine, g1a, h), "nbase", 1 + len(attrs), "the table holds %(got)d bases, the universe needs %(want)d")
 
 
 def encrypt_batch(engine, g1a, e_alpha, h, policies_or_padded, messages, s, v, r, table=None):
@@ -257,7 +235,7 @@ def encrypt_batch(engine, g1a, e_alpha, h, policies_or_padded, messages, s, v, r
     pos = _attribute_positions(attrs, pad.rho, "policy")                      # before anything touches the engine
     if bufs.nbytes(messages) != n * 384:
         raise ValueError("messages must hold n = %d GT elements" % n)
-    s, v, r = _scalars(s, messages), (None if v is None else _scalars(v, messages)), _scalars(r, messages)
+    s, v, r = _plan.scalars(s, messages), (None if v is None else _plan.scalars(v, messages)), _plan.scalars(r, messages)
     bufs.device_of(messages, s, v, r)                                          # all of one kind, on one device
     if bufs.nbytes(s) != n * 32 or (bufs.nbytes(v) if v is not None else 0) != n * (C - 1) * 32 or bufs.nbytes(r) != n * R * 32:
         raise ValueError("need s [n], v [n, C - 1], r [n, R] scalars with n = %d, R = %d, C = %d" % (n, R, C))
@@ -268,20 +246,12 @@ def encrypt_batch(engine, g1a, e_alpha, h, policies_or_padded, messages, s, v, r
     lam = engine.fr_lsss_shares(bufs.flat(bufs.put(pad.matrix, messages)), bufs.flat(vec), pad.rows, pad.cols)        # [n, R, 32]
     nr = engine.fr_neg(bufs.flat(r))
     index = np.stack([np.zeros(n * R, dtype=np.int64), pos.reshape(-1)], 1)                                           # (g1^a, h_rho(x)); padding: (g1^a, none)
-    own = table is None
-    table = encrypt_table(engine, g1a, h) if own else table
-    try:
-        if table.nbase != 1 + len(attrs):
-            raise ValueError("the table holds %d bases, the universe needs %d" % (table.nbase, 1 + len(attrs)))
+    with _table(engine, table, g1a, h, attrs) as table:
         scal = bufs.cat([bufs.view(lam, n * R, 1, 32), bufs.view(nr, n * R, 1, 32)], 1)
-        cx, ok = table.indexed(_index_rows(index, messages), bufs.flat(scal), terms=2)
-    finally:
-        if own:
-            table.close()
+        cx, ok = table.indexed(_plan.index_rows(index, messages), bufs.flat(scal), terms=2)
     dx = engine.g2_scalar_mul_base(bufs.flat(r))
     c_prime = engine.g2_scalar_mul_base(bufs.flat(s))
-    base = bufs.flat(bufs.expand(bufs.view(_public(e_alpha, 384, "e_alpha", messages), 1, 384), n, 384))
-    c = engine.gt_mul(engine.gt_exp(base, bufs.flat(s)), bufs.flat(messages))
+    c = _plan.blind(engine, _plan.public(e_alpha, 1, 384, messages, "e_alpha"), s, messages, n)
     return bufs.view(c, n, 384), bufs.view(c_prime, n, 128), bufs.view(cx, n, R, 64), bufs.view(dx, n, R, 128)
 
 
@@ -303,23 +273,16 @@ def keygen_batch(engine, g1_alpha, g1a, h, user_attrs, t, table=None):
         held[j, :len(u)] = u
     pos = _attribute_positions(attrs, held, "user")
     like = t if bufs.is_torch(t) else np.zeros(0, dtype=np.uint8)
-    t = _scalars(t, like)
+    t = _plan.scalars(t, like)
     if bufs.nbytes(t) != n * 32:
         raise ValueError("t must hold n = %d scalars" % n)
     if not n:
         return bufs.zeros((0, 64), t), bufs.zeros((0, 128), t), bufs.zeros((0, A, 64), t), held
     t = bufs.view(t, n, 1, 32)
     index = np.concatenate([np.zeros((n, 1), dtype=np.int64), pos], 1).reshape(-1, 1)                                 # [t] g1^a, then [t] h_x
-    own = table is None
-    table = encrypt_table(engine, g1a, h) if own else table
-    try:
-        if table.nbase != 1 + len(attrs):
-            raise ValueError("the table holds %d bases, the universe needs %d" % (table.nbase, 1 + len(attrs)))
-        pts, ok = table.indexed(_index_rows(index, t), bufs.flat(bufs.expand(t, n, 1 + A, 32)), terms=1)
-    finally:
-        if own:
-            table.close()
+    with _table(engine, table, g1a, h, attrs) as table:
+        pts, ok = table.indexed(_plan.index_rows(index, t), bufs.flat(bufs.expand(t, n, 1 + A, 32)), terms=1)
     pts = bufs.view(pts, n, 1 + A, 64)
-    K = engine.g1_add(bufs.flat(bufs.expand(bufs.view(_public(g1_alpha, 64, "g1_alpha", t), 1, 64), n, 64)), bufs.flat(pts[:, 0]))
+    K = engine.g1_add(bufs.flat(bufs.expand(_plan.public(g1_alpha, 1, 64, t, "g1_alpha"), n, 64)), bufs.flat(pts[:, 0]))
     L = engine.g2_scalar_mul_base(bufs.flat(t))
     return bufs.view(K, n, 64), bufs.view(L, n, 128), pts[:, 1:], held

@@ -1,5 +1,5 @@
 """Test helper: BSW07 keys of many users under one policy, from the known secrets of tests/bsw07_fixture.py (alpha, beta, H(a) = [h_a] g),
-in the arrays bsw07.decrypt_batch_keys takes, and the stand-in engine of its plan test.
+in the arrays bsw07.decrypt_batch_keys takes (the stand-in engine of its plan test is tests/standin_engine.py).
 
 KeyGenerate (cpabe/bsw07/bsw07_cpabe.go:97-130) for user u with attributes A_u: D = g2^((alpha + r_u) / beta) and per attribute a
 Dj = g2^r_u H2(a)^rj, Dj' = g2^rj.  With H2(a) = [h_a] g2 every component is a multiple of the generator by a known scalar, so the keys
@@ -9,8 +9,6 @@ import numpy as np
 import bn254_py as o
 import fr_cases as fc
 from bsw07_fixture import leaves, sc
-from share_standin import ShareEngine, StandInTree
-from gopairingbasedcryptography_amd import bsw07
 
 R = o.R
 GARBAGE = 0xEE                       # what the rows of leaves a key does not hold are filled with: no point, and it must not matter
@@ -44,56 +42,3 @@ def ciphertext_arrays(inst, picks):
     cts = [inst.cts[t] for t in picks]
     return (np.stack([np.asarray(ct["c_tilde"]) for ct in cts]), np.stack([np.asarray(ct["c"]) for ct in cts]),
             np.stack([np.stack([np.asarray(ct["cy"][i]) for i in ids]) for ct in cts]), np.stack([np.stack([np.asarray(ct["cy_prime"][i]) for i in ids]) for ct in cts]))
-
-
-# ------------------------------------------------------------------------------------------------ the stand-in engine
-class KeysTree(StandInTree):
-    """ShareTree.weights as bsw07.decrypt_plan in Python integers, on the tree with leaf y carrying attribute y"""
-
-    def weights(self, held):
-        assert not self.closed
-        tensor = type(held).__module__.startswith("torch")
-        h = np.asarray(held.numpy() if tensor else held, dtype=np.uint8).reshape(-1, self.leaves)
-        bsw07.assign_leaf_ids(self.tree)                                     # (StandInTree's leaves carry their node index: distinct attributes)
-        ids = [l.attribute for l in leaves(self.tree)]
-        w, ok = np.zeros((len(h), self.leaves, 32), dtype=np.uint8), np.zeros(len(h), dtype=np.uint8)
-        for j, row in enumerate(h):
-            plan = bsw07.decrypt_plan(self.tree, {ids[y] for y in range(self.leaves) if row[y]})
-            if plan is not None:
-                ok[j] = 1
-                for leaf_id, (_, delta) in plan.items():
-                    w[j, leaf_id - 1] = np.frombuffer(int(delta).to_bytes(32, "little"), dtype=np.uint8)
-        if tensor:
-            import torch
-            return torch.from_numpy(w), torch.from_numpy(ok)
-        return w, ok
-
-
-class KeysEngine(ShareEngine):
-    """ShareEngine with what decrypt_batch_keys calls besides: the weights, the two negations, scalar multiples of the point at
-    infinity, and a record of every list that reaches multi_pair"""
-    ShareTree = KeysTree
-
-    def __init__(self, oracle):
-        super().__init__(oracle)
-        self.pairs = []
-
-    def g2_neg(self, q):
-        return np.frombuffer(o.g2_to_bytes(o.g2_neg(o.g2_from_bytes(np.asarray(q, dtype=np.uint8).tobytes()))), dtype=np.uint8)
-
-    def g2_sub(self, a, b):
-        a, b = np.asarray(a, dtype=np.uint8).reshape(-1, 128), np.asarray(b, dtype=np.uint8).reshape(-1, 128)
-        assert not a.any(), "the stand-in subtracts from the point at infinity only"
-        return np.stack([self.g2_neg(q) for q in b])
-
-    def g1_scalar_mul(self, b, k):
-        b, k = np.asarray(b, dtype=np.uint8).reshape(-1, 64), np.asarray(self._k(k), dtype=np.uint8).reshape(-1, 32)
-        out = np.zeros((len(b), 64), dtype=np.uint8)
-        live = np.nonzero(b.any(1) & k.any(1))[0]                            # [k] infinity and [0] P are the point at infinity
-        if len(live):
-            out[live] = np.asarray(self.o.g1_scalar_mul(b[live].reshape(-1), k[live].reshape(-1), threads=4)).reshape(-1, 64)
-        return out
-
-    def multi_pair(self, P, Q, off):
-        self.pairs.append((np.array(P, copy=True).reshape(-1, 64), np.array(Q, copy=True).reshape(-1, 128), np.array(off, copy=True)))
-        return super().multi_pair(P, Q, off)

@@ -7,15 +7,14 @@ and ciphertext component is ONE multiplication of a generator (or one power of e
 
 computed with oracle calls and hashlib alone: a route that shares nothing with the planner's sequence of engine calls.
 
-Also here: the reference's own sequences of KeyGenerate / Encrypt / Decrypt written out with oracle calls, one identity at a time, and
-the stand-in engine the plan test runs the planner on (hash_g1_gt_gt_to_fr is the hashlib restatement)."""
+Also here: the reference's own sequences of KeyGenerate / Encrypt / Decrypt written out with oracle calls, one identity at a time.  The
+stand-in engine the plan test runs the planner on is tests/standin_engine.py (its hash_g1_gt_gt_to_fr is beta_rows, the hashlib restatement)."""
 import hashlib
 
 import numpy as np
 
 import bn254_py as o
 from sw05_fixture import kbytes, kints
-from waters05_fixture import Engine as Waters05Engine
 
 R = o.R
 G1 = np.frombuffer(o.g1_to_bytes(o.G1_GEN), dtype=np.uint8)
@@ -133,26 +132,3 @@ def tamper(inst, oracle, how, rows):
         return (u, v, w, y), [0, 1]
     u[0] = np.frombuffer(o.g1_to_bytes(o.g1_neg(o.g1_from_bytes(u[0].tobytes()))), dtype=np.uint8)
     return (u, v, w, y), [0]
-
-
-class Engine(Waters05Engine):
-    """the stand-in engine of the Waters05 plan test plus the names gentry06.py calls besides; H by hashlib"""
-
-    def fr_add(self, a, b):
-        return kbytes([x + y for x, y in zip(kints(a), kints(b))]).reshape(-1, 32)
-
-    def fr_sub(self, a, b):
-        return kbytes([x - y for x, y in zip(kints(a), kints(b))]).reshape(-1, 32)
-
-    def fr_inverse(self, a):
-        return kbytes([pow(x % R, -1, R) if x % R else 0 for x in kints(a)]).reshape(-1, 32)
-
-    def g2_scalar_mul_base(self, k):
-        return self.o.g2_scalar_mul(G2, self._k(k), threads=4)
-
-    def g1_add(self, a, b):
-        a, b = np.asarray(a, dtype=np.uint8).reshape(-1, 64), np.asarray(b, dtype=np.uint8).reshape(-1, 64)
-        return np.stack([self.o.g1_sum(np.stack([x, y])) for x, y in zip(a, b)])
-
-    def hash_g1_gt_gt_to_fr(self, u, v, w):
-        return beta_rows(u, v, w)

@@ -6,9 +6,8 @@ shared base).  The large-universe T_x shares nothing with sw05.compute_t: t_j = 
 x^n + sum_j tau_j Delta_{x,N}(j) in Python integers (the reference's node list j = 0 .. n over N = 1 .. n+1), one generator
 multiplication.
 
-Also here: the reference's FindCommonAttributes and Decrypt loops written out (Python integers, oracle calls), and the stand-ins the
-plan tests run the planner on (OracleEngine with fr_lagrange_basis in Python integers, OracleTable for FixedBase, and TensorEngine,
-which lets any of the plan tests' stand-ins take CPU tensors so that a planner's tensor path runs without a GPU).
+Also here: the reference's FindCommonAttributes and Decrypt loops written out (Python integers, oracle calls).  The stand-in engine
+the plan tests run the planner on is tests/standin_engine.py (fr_lagrange_basis from lagrange() below).
 
 numpy arrays by default; with `dev` a torch device everything per ciphertext is made and kept in HBM (the instances at size)."""
 import numpy as np
@@ -146,84 +145,3 @@ def at_size_attributes(n_ct, a, n_key, d, every, seed=2005):
         attrs = [key[i] for i in rng.permutation(n_key)[:c]] + [other[i] for i in rng.permutation(a)[:a - c]]
         cts.append([attrs[i] for i in rng.permutation(a)])
     return key, cts
-
-
-# ------------------------------------------------------------------------------------------------ stand-ins for the plan tests
-class OracleEngine:
-    """the engine's function names on the oracle (host arrays only); fr_* in Python integers"""
-
-    def __init__(self, oracle):
-        self.o = oracle
-
-    def _k(self, ks):
-        return kbytes(ks) if isinstance(ks, (list, tuple)) else ks
-
-    def pair_batch(self, P, Q): return self.o.pair_batch(P, Q)
-    def multi_pair(self, P, Q, off): return self.o.multi_pair(P, Q, off, threads=4)
-    def g1_scalar_mul(self, b, k): return self.o.g1_scalar_mul(b, self._k(k), threads=4)
-    def g2_scalar_mul(self, b, k): return self.o.g2_scalar_mul(b, self._k(k), threads=4)
-    def gt_mul(self, a, b): return self.o.gt_mul(a, b)
-    def gt_div(self, a, b): return self.o.gt_div(a, b)
-    def gt_exp(self, x, k): return self.o.gt_exp(x, self._k(k))
-    def fr_neg(self, a): return kbytes([-v for v in kints(a)]).reshape(-1, 32)
-    def fr_mul(self, a, b):
-        a, b = kints(a), kints(b)
-        return kbytes([x * b[i if len(b) > 1 else 0] for i, x in enumerate(a)]).reshape(-1, 32)
-
-    def fr_lagrange_basis(self, set, B, nodes=None, m=None, x=None):
-        S = np.asarray(kints(set), dtype=object).reshape(-1, B)
-        N = S if nodes is None else np.asarray(kints(nodes), dtype=object).reshape(-1, m)
-        X = [0] if x is None else kints(x)
-        k = max(len(S), len(N), len(X))
-        pick = lambda a, j: a[j if len(a) > 1 else 0]
-        return kbytes([lagrange(t, list(pick(S, j)), pick(X, j)) for j in range(k) for t in pick(N, j)]).reshape(k, -1, 32)
-
-
-class OracleTable:
-    """FixedBase(bases, g2=True).msm on the oracle: one scalar multiplication per base and a sum per row"""
-
-    def __init__(self, oracle, bases):
-        self.o, self.bases = oracle, np.asarray(bases, dtype=np.uint8).reshape(-1, 128)
-        self.nbase = self.bases.shape[0]
-
-    def msm(self, scalars):
-        k = np.asarray(scalars, dtype=np.uint8).reshape(-1, self.nbase, 32)
-        return np.stack([np.asarray(self.o.g2_sum(self.o.g2_scalar_mul(self.bases, row.reshape(-1), threads=4))).reshape(128) for row in k])
-
-
-class TensorEngine:
-    """Any stand-in engine (numpy only) behind the engine's tensor behaviour: tensors among the arguments go in as numpy arrays, and
-    a call that was given a tensor hands its array results back as CPU tensors.  A call on host data alone passes through."""
-
-    def __init__(self, engine):
-        self._engine = engine
-
-    def __getattr__(self, name):
-        fn = getattr(self._engine, name)
-        if not callable(fn):
-            return fn
-        import torch
-
-        def call(*args, **kw):
-            tensors = [a for a in list(args) + list(kw.values()) if isinstance(a, torch.Tensor)]
-            host = lambda a: a.numpy() if isinstance(a, torch.Tensor) else a
-            res = fn(*[host(a) for a in args], **{k: host(v) for k, v in kw.items()})
-            if not tensors:
-                return res
-            back = lambda r: torch.from_numpy(np.array(r, dtype=np.uint8, copy=True)) if isinstance(r, np.ndarray) else r
-            return tuple(back(r) for r in res) if isinstance(res, tuple) else back(res)
-        return call
-
-
-def tensors(*arrays):
-    """copies of host arrays as CPU uint8 tensors"""
-    import torch
-    return [torch.from_numpy(np.array(a.cpu() if isinstance(a, torch.Tensor) else a, dtype=np.uint8, copy=True)) for a in arrays]
-
-
-def same_on_tensors(got, want):
-    """the tensor run of a planner returned tensors, of the numpy run's shape, holding the numpy run's bytes"""
-    import torch
-    assert isinstance(got, torch.Tensor) and isinstance(want, np.ndarray)
-    assert got.dtype == torch.uint8 and tuple(got.shape) == want.shape
-    return got.numpy().tobytes() == want.tobytes()

@@ -6,14 +6,13 @@ import pytest
 
 import bn254_py as o
 from afp25_fixture import Instance
-from sw05_fixture import TensorEngine, same_on_tensors, tensors
+from standin_engine import StandInEngine, TensorEngine, same_on_tensors, tensors
 from gopairingbasedcryptography_amd import afp25
-from test_bsw07_plan import OracleEngine
 
 
-class Eng(OracleEngine):
-    def g1_sum(self, p): return self.o.g1_sum(p)
-    def gt_div(self, a, b): return self.o.gt_div(a, b)
+def Eng(oracle):
+    """the stand-in has no g1_scalar_mul_sum: commit_g1 takes its g1_scalar_mul + g1_sum branch"""
+    return StandInEngine(oracle)
 
 
 def test_polynomials():

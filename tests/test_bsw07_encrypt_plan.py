@@ -1,5 +1,5 @@
 """BSW07 Encrypt through the host planner (gopairingbasedcryptography_amd/bsw07.py: share_plan, encrypt_batch) on the oracle stand-in
-engine (tests/share_standin.py; the same flow runs on the GPU engine in test_bsw07_encrypt_gpu.py): fed the fixture's own s and
+engine (tests/standin_engine.py; the same flow runs on the GPU engine in test_bsw07_encrypt_gpu.py): fed the fixture's own s and
 polynomial scalars it returns the fixture's ciphertext bytes, and the existing decrypt_batch_arrays returns the fixture's messages."""
 import numpy as np
 import pytest
@@ -7,8 +7,7 @@ import pytest
 import bn254_py as o
 from bsw07_fixture import Instance, example_tree, sc as fsc
 import share_cases as sc
-from share_standin import ShareEngine
-from sw05_fixture import TensorEngine, same_on_tensors, tensors
+from standin_engine import StandInEngine, TensorEngine, same_on_tensors, tensors
 from gopairingbasedcryptography_amd import bsw07
 
 L, T = bsw07.Leaf, bsw07.Threshold
@@ -49,7 +48,7 @@ def fixture_arrays(inst):
 
 @pytest.fixture(scope="module")
 def setup(oracle):
-    eng = ShareEngine(oracle)
+    eng = StandInEngine(oracle)
     inst = Instance(eng, example_tree(), user_attrs=[11, 22, 33, 99], n_ct=3)
     return eng, inst, fixture_inputs(inst, 3)
 

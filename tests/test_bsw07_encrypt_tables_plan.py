@@ -1,5 +1,5 @@
 """BSW07 Encrypt with tables=True through the host planner (gopairingbasedcryptography_amd/bsw07.py: encrypt_batch) on the oracle
-stand-in engine (tests/indexed_standin.py; the same flow runs on the GPU engine in test_lsss_encrypt_gpu.py): Cy' from a fixed-base
+stand-in engine (tests/standin_engine.py; the same flow runs on the GPU engine in test_lsss_encrypt_gpu.py): Cy' from a fixed-base
 table over the L points of h1 with the L index rows repeating per ciphertext is the fixture's ciphertext, byte for byte what the
 default route returns, and the default route does not touch a table."""
 import numpy as np
@@ -7,15 +7,14 @@ import pytest
 
 import share_cases as sc
 from bsw07_fixture import Instance, example_tree
-from indexed_standin import IndexedEngine
-from sw05_fixture import TensorEngine, same_on_tensors, tensors
+from standin_engine import StandInEngine, TensorEngine, same_on_tensors, tensors
 from test_bsw07_encrypt_plan import fixture_arrays, fixture_inputs
 from gopairingbasedcryptography_amd import bsw07
 
 
 @pytest.fixture(scope="module")
 def setup(oracle):
-    eng = IndexedEngine(oracle)
+    eng = StandInEngine(oracle)
     inst = Instance(eng, example_tree(), user_attrs=[11, 22, 33, 99], n_ct=3)
     return eng, inst, fixture_inputs(inst, 3)
 

@@ -6,8 +6,8 @@ import numpy as np
 import pytest
 
 from bsw07_fixture import Instance, example_tree
-from bsw07_keys_fixture import GARBAGE, KeysEngine, ciphertext_arrays, user_keys
-from sw05_fixture import TensorEngine, same_on_tensors, tensors
+from bsw07_keys_fixture import GARBAGE, ciphertext_arrays, user_keys
+from standin_engine import StandInEngine, TensorEngine, recorded, same_on_tensors, tensors
 from gopairingbasedcryptography_amd import bsw07
 
 L, T = bsw07.Leaf, bsw07.Threshold
@@ -38,7 +38,8 @@ def test_used_columns_are_compacted_in_leaf_order():
 
 @pytest.fixture(scope="module")
 def setup(oracle):
-    eng = KeysEngine(oracle)
+    eng = StandInEngine(oracle)
+    eng.pairs = recorded(eng, ("multi_pair",))                               # every list that reaches multi_pair
     inst = Instance(eng, example_tree(), user_attrs=[], n_ct=3)
     picks = [t % 3 for t in range(len(SETS))]
     D, dj, djp, _, _ = user_keys(eng, inst.tree, SETS)
@@ -54,7 +55,8 @@ def test_messages_ok_flags_and_the_lists_that_reach_the_engine(setup):
     for t in range(n):
         assert msgs[t].tobytes() == (np.asarray(inst.msgs[picks[t]]).tobytes() if USED[t] else bytes(384)), t
     # one multi_pair: a segment per satisfied item, 2 U + 1 pairs with U = 3 and not 2 L + 1 = 13
-    (P, Q, off), = eng.pairs
+    (_, (P, Q, off)), = eng.pairs
+    P, Q, off = np.asarray(P).reshape(-1, 64), np.asarray(Q).reshape(-1, 128), np.asarray(off)
     good = [t for t in range(n) if USED[t]]
     assert off.tolist() == list(range(0, 7 * len(good) + 1, 7)) and len(P) == len(Q) == 7 * len(good)
     assert not (Q == GARBAGE).all(1).any()                                   # no row of a leaf that is not held went in

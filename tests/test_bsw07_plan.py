@@ -7,26 +7,13 @@ import pytest
 
 import bn254_py as o
 from bsw07_fixture import Instance, example_tree
-from sw05_fixture import TensorEngine, same_on_tensors, tensors
+from standin_engine import StandInEngine, TensorEngine, same_on_tensors, tensors
 from gopairingbasedcryptography_amd import bsw07
 
 
-class OracleEngine:
-    def __init__(self, oracle):
-        self.o = oracle
-
-    def _k(self, ks):
-        if isinstance(ks, (list, tuple)):
-            return np.frombuffer(b"".join(o.scalar_to_bytes(int(k) % o.R) for k in ks), dtype=np.uint8)
-        return ks
-
-    def pair_batch(self, P, Q): return self.o.pair_batch(P, Q)
-    def multi_pair(self, P, Q, off): return self.o.multi_pair(P, Q, off, threads=4)
-    def g1_scalar_mul(self, b, k): return self.o.g1_scalar_mul(b, self._k(k))
-    def g2_scalar_mul(self, b, k): return self.o.g2_scalar_mul(b, self._k(k))
-    def g2_sum(self, p): return self.o.g2_sum(p)
-    def gt_mul(self, a, b): return self.o.gt_mul(a, b)
-    def gt_exp(self, x, k): return self.o.gt_exp(x, self._k(k))
+def plain_engine(oracle):
+    """an engine without the fixed-Q entry: decrypt_batch takes its multi_pair branch"""
+    return StandInEngine(oracle, without=("multi_pair_fixed_q",))
 
 
 def test_lagrange_and_plan():
@@ -40,7 +27,7 @@ def test_lagrange_and_plan():
 
 
 def test_folded_decrypt_matches_reference_shape(oracle):
-    eng = OracleEngine(oracle)
+    eng = plain_engine(oracle)
     inst = Instance(eng, example_tree(), user_attrs=[11, 22, 33, 99], n_ct=3)
     plan = bsw07.decrypt_plan(inst.tree, inst.user_attrs)
     folded = bsw07.fold_key(eng, plan, inst.dj, inst.dj_prime)
@@ -51,27 +38,15 @@ def test_folded_decrypt_matches_reference_shape(oracle):
 
 
 def test_unsatisfied_policy(oracle):
-    eng = OracleEngine(oracle)
+    eng = plain_engine(oracle)
     inst = Instance(eng, example_tree(), user_attrs=[22, 44 + 1], n_ct=1)
     assert bsw07.decrypt_plan(inst.tree, inst.user_attrs) is None          # bsw07_cpabe_test.go:83-141: decrypt must fail
     assert inst.reference_shaped_decrypt(oracle, inst.cts[0]) is None
 
 
-class ArraysEngine(OracleEngine):
-    """what decrypt_batch_arrays needs besides: the fixed-Q multi-pairing as a plain one over the repeated list, G2 negation"""
-
-    def multi_pair_fixed_q(self, P, Q):
-        P, Q = np.asarray(P, dtype=np.uint8).reshape(-1, 64), np.asarray(Q, dtype=np.uint8).reshape(-1, 128)
-        m, k = len(Q), len(P) // len(Q)
-        return self.o.multi_pair(P, np.tile(Q, (k, 1)), np.arange(0, k * m + 1, m), threads=4)
-
-    def g2_neg(self, b):
-        return np.frombuffer(o.g2_to_bytes(o.g2_neg(o.g2_from_bytes(np.asarray(b, dtype=np.uint8).tobytes()))), dtype=np.uint8)
-
-
 def test_decrypt_on_arrays_and_on_tensors(oracle):
     """decrypt_batch_arrays on numpy arrays returns the messages; on CPU tensors (TensorEngine) a tensor with the same bytes"""
-    eng = ArraysEngine(oracle)
+    eng = StandInEngine(oracle)
     inst = Instance(eng, example_tree(), user_attrs=[11, 22, 33, 99], n_ct=2)
     folded = bsw07.fold_key(eng, bsw07.decrypt_plan(inst.tree, inst.user_attrs), inst.dj, inst.dj_prime)
     ids = folded[0]

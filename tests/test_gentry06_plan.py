@@ -2,12 +2,12 @@
 the oracle, H by hashlib — against (a) the on-exponent expectation of gentry06_fixture.py, single generator multiplications that share
 nothing with the planner's sequence, and (b) the reference's own sequences of KeyGenerate / Encrypt / Decrypt written out with oracle
 calls.  N = 8 identities, k = 1 (gentry06_cpa_ibe) and k = 3 (gentry06_ibe); identity 5 equals alpha, the reference's "ID equals alpha"
-error.  The same runs on CPU tensors (sw05_fixture.TensorEngine) cover the tensor path of the planner without a GPU."""
+error.  The same runs on CPU tensors (standin_engine.TensorEngine) cover the tensor path of the planner without a GPU."""
 import numpy as np
 import pytest
 
 import gentry06_fixture as gf
-from sw05_fixture import TensorEngine, same_on_tensors, tensors
+from standin_engine import StandInEngine, TensorEngine, same_on_tensors, tensors
 
 N, ALPHA_AT = 8, 5
 KS = [1, 3]
@@ -28,7 +28,7 @@ def planner():
 
 @pytest.fixture(scope="module")
 def eng(oracle):
-    return gf.Engine(oracle)
+    return StandInEngine(oracle)
 
 
 def same(a, b):

@@ -1,5 +1,5 @@
 """LW11 decentralised ABE Encrypt through the host planner (gopairingbasedcryptography_amd/lw11.py: encrypt_batch) on the oracle
-stand-in engine (tests/indexed_standin.py; the same flow runs on the GPU engine in test_lsss_encrypt_gpu.py): fed the fixture's own
+stand-in engine (tests/standin_engine.py; the same flow runs on the GPU engine in test_lsss_encrypt_gpu.py): fed the fixture's own
 secrets it returns the fixture's ciphertext bytes, and the existing decrypt_batch / decrypt_batch_msm recover the messages — for the
 AND / OR policy and for 3 of 5 as Shamir rows, whose weights are neither 0 nor 1."""
 import numpy as np
@@ -7,9 +7,9 @@ import pytest
 
 import bn254_py as o
 import gmsm_cases as gc
-from indexed_standin import IndexedEngine
 from lw11_fixture import Instance, and_or_policy, sc as fsc, threshold_policy
-from sw05_fixture import TensorEngine, kbytes, same_on_tensors, tensors
+from standin_engine import StandInEngine, TensorEngine, same_on_tensors, tensors
+from sw05_fixture import kbytes
 from gopairingbasedcryptography_amd import lw11
 
 G1 = np.frombuffer(o.g1_to_bytes(o.G1_GEN), dtype=np.uint8)
@@ -40,7 +40,7 @@ POLICIES = {"and-or": (and_or_policy, [11, 22, 44, 99]), "3of5": (lambda: thresh
 
 @pytest.fixture(scope="module", params=list(POLICIES))
 def setup(oracle, request):
-    eng = IndexedEngine(oracle)
+    eng = StandInEngine(oracle)
     make, held = POLICIES[request.param]
     m, rho = make()
     inst = Instance(eng, m, rho, held, n_ct=N)

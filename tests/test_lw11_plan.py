@@ -7,33 +7,9 @@ import numpy as np
 import pytest
 
 import bn254_py as o
-import gt_multi_exp_cases as gc
 from lw11_fixture import Instance, and_chain_policy, and_or_policy, threshold_policy
-from sw05_fixture import TensorEngine, same_on_tensors, tensors
+from standin_engine import StandInEngine, TensorEngine, same_on_tensors, tensors
 from gopairingbasedcryptography_amd import lw11
-
-
-class OracleEngine:
-    def __init__(self, oracle):
-        self.o = oracle
-
-    def _k(self, ks):
-        if isinstance(ks, (list, tuple)):
-            return np.frombuffer(b"".join(o.scalar_to_bytes(int(k) % o.R) for k in ks), dtype=np.uint8)
-        return ks
-
-    def pair_batch(self, P, Q): return self.o.pair_batch(P, Q)
-    def multi_pair(self, P, Q, off): return self.o.multi_pair(P, Q, off, threads=4)
-    def g1_scalar_mul(self, b, k): return self.o.g1_scalar_mul(b, self._k(k))
-    def g2_scalar_mul(self, b, k): return self.o.g2_scalar_mul(b, self._k(k))
-    def gt_mul(self, a, b): return self.o.gt_mul(a, b)
-    def gt_div(self, a, b): return self.o.gt_div(a, b)
-    def gt_exp(self, x, k): return self.o.gt_exp(x, self._k(k))
-
-    def gt_multi_exp(self, x, k, seg):
-        x = np.asarray(x, dtype=np.uint8).reshape(-1, 384)
-        seg = [int(v) for v in seg]
-        return gc.expect(self.o, x, k, seg, k is not None and len(k) != len(x))
 
 
 def check_identity(matrix, rows, weights):
@@ -88,7 +64,7 @@ def test_weights_that_are_not_zero_or_one():
 def test_and_or_policy_matches_the_reference_loop(oracle):
     """3 ciphertexts, 4 rows, (11 and 22) or (33 and 44), key for 11, 22, 44: the messages come back and every one is bit-identical
     to the reference's loop (running product raised at every row, weights indexed by row number) — all weights are 1 there"""
-    eng = OracleEngine(oracle)
+    eng = StandInEngine(oracle)
     m, rho = and_or_policy()
     inst = Instance(eng, m, rho, [11, 22, 44, 99], n_ct=3)
     rows, w = lw11.reconstruction_weights(m, rho, inst.user_attrs)
@@ -117,7 +93,7 @@ def test_weights_other_than_one_return_the_message(oracle):
     """3 of 4 as Shamir rows, key for rows 0, 1, 3: Lagrange weights.  decrypt_batch returns the messages, and so does the row by
     row evaluation of the scheme.  (The reference's loop as written does not: it raises the running product at every row and
     reads wSlice[x] at the row number, which for rows [0, 1, 3] is out of the compacted slice's range.  Stated, not asserted.)"""
-    eng = OracleEngine(oracle)
+    eng = StandInEngine(oracle)
     m, rho = threshold_policy(3, 4)
     inst = Instance(eng, m, rho, [rho[0], rho[1], rho[3]], n_ct=3, tag="t")
     rows, w = lw11.reconstruction_weights(m, rho, inst.user_attrs)
@@ -131,7 +107,7 @@ def test_weights_other_than_one_return_the_message(oracle):
 
 
 def test_fold_key_arguments(oracle):
-    eng = OracleEngine(oracle)
+    eng = StandInEngine(oracle)
     with pytest.raises(ValueError):
         lw11.fold_key(eng, [0, 1], [1], np.zeros(64, np.uint8), {0: np.zeros(64, np.uint8), 1: np.zeros(64, np.uint8)})
     with pytest.raises(ValueError):

@@ -1,12 +1,12 @@
 """SW05 KeyGenerate of both universes through the host planner (gopairingbasedcryptography_amd/sw05.py: keygen_batch,
-keygen_batch_large) on the oracle stand-in engine (tests/share_standin.py; the same flow runs on the GPU engine in
+keygen_batch_large) on the oracle stand-in engine (tests/standin_engine.py; the same flow runs on the GPU engine in
 test_sw05_keygen_gpu.py): fed the fixture's y, "q" coefficients, t / taus and r it reproduces sw05_fixture.Instance.key byte for byte."""
 import numpy as np
 import pytest
 
 import bn254_py as o
-from share_standin import ShareEngine
-from sw05_fixture import Instance, OracleTable, TensorEngine, same_on_tensors, sc, tensors
+from standin_engine import StandInEngine, StandInFixedBase, TensorEngine, same_on_tensors, tensors
+from sw05_fixture import Instance, sc
 from gopairingbasedcryptography_amd import sw05
 
 R = o.R
@@ -29,7 +29,7 @@ def fixture_inputs(inst, tag):
 
 @pytest.mark.parametrize("d", [1, 4, 16])
 def test_small_universe_key_is_the_fixture_key(oracle, d):
-    eng = ShareEngine(oracle)
+    eng = StandInEngine(oracle)
     inst = instance(eng, d, None)
     y, coeffs, attrs = fixture_inputs(inst, "kg%d" % d)
     t = [[inst.t[a % R] for a in attrs[0]]]
@@ -41,11 +41,11 @@ def test_small_universe_key_is_the_fixture_key(oracle, d):
 
 @pytest.mark.parametrize("d", [1, 4, 16])
 def test_large_universe_key_is_the_fixture_key(oracle, d):
-    eng = ShareEngine(oracle)
+    eng = StandInEngine(oracle)
     inst = instance(eng, d, 3)
     y, coeffs, attrs = fixture_inputs(inst, "kg%d" % d)
     r = [[sc("kg%dr" % d, k) for k in range(5)]]
-    dk, Dk = sw05.keygen_batch_large(eng, OracleTable(oracle, inst.table_bases), 3, y, coeffs if d > 1 else None, attrs, r)
+    dk, Dk = sw05.keygen_batch_large(eng, StandInFixedBase(oracle, inst.table_bases, g2=True), 3, y, coeffs if d > 1 else None, attrs, r)
     assert dk.shape == (1, 5, 64) and Dk.shape == (1, 5, 128)
     assert dk.tobytes() == np.asarray(inst.key[1]).tobytes() and Dk.tobytes() == np.asarray(inst.key[2]).tobytes()
 
@@ -58,9 +58,9 @@ def three_users(d):
 
 
 def test_three_users_are_three_single_user_calls(oracle):
-    eng = ShareEngine(oracle)
+    eng = StandInEngine(oracle)
     inst = instance(eng, 2, 3)
-    table = OracleTable(oracle, inst.table_bases)
+    table = StandInFixedBase(oracle, inst.table_bases, g2=True)
     attrs, coeffs, side = three_users(4)
     y = sc("y3")
     D = sw05.keygen_batch(eng, y, coeffs, attrs, side)
@@ -76,7 +76,7 @@ def test_three_users_are_three_single_user_calls(oracle):
 
 
 def test_keygen_on_tensors_is_keygen_on_arrays(oracle):
-    eng = ShareEngine(oracle)
+    eng = StandInEngine(oracle)
     inst = instance(eng, 2, 3)
     attrs, coeffs, side = three_users(3)
     y = sc("y3")
@@ -86,15 +86,15 @@ def test_keygen_on_tensors_is_keygen_on_arrays(oracle):
     assert same_on_tensors(sw05.keygen_batch(TensorEngine(eng), y, tc, ta, ts), want)
     assert sw05.keygen_batch(eng, y, rows(coeffs), rows(attrs), rows(side)).tobytes() == want.tobytes()
     assert same_on_tensors(sw05.keygen_batch(TensorEngine(eng), y, None, ta, ts), sw05.keygen_batch(eng, y, None, attrs, side))       # d = 1 on tensors
-    wl = sw05.keygen_batch_large(eng, OracleTable(oracle, inst.table_bases), 3, y, coeffs, attrs, side)
-    table = OracleTable(oracle, inst.table_bases)
+    wl = sw05.keygen_batch_large(eng, StandInFixedBase(oracle, inst.table_bases, g2=True), 3, y, coeffs, attrs, side)
+    table = StandInFixedBase(oracle, inst.table_bases, g2=True)
     table.msm = lambda s, f=table.msm: __import__("torch").from_numpy(f(s.numpy()))
     gl = sw05.keygen_batch_large(TensorEngine(eng), table, 3, y, tc, ta, ts)
     assert same_on_tensors(gl[0], wl[0]) and same_on_tensors(gl[1], wl[1])
 
 
 def test_argument_errors(oracle):
-    eng = ShareEngine(oracle)
+    eng = StandInEngine(oracle)
     attrs, coeffs, side = three_users(3)
     for bad in (lambda: sw05.keygen_batch(eng, 5, coeffs[:2], attrs, side), lambda: sw05.keygen_batch(eng, 5, coeffs, attrs, side[:2]),
                 lambda: sw05.keygen_batch(eng, 5, coeffs, [[1, 2], [3]], side), lambda: sw05.keygen_batch(eng, 5, coeffs, attrs, [r[:3] for r in side]),

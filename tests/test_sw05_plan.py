@@ -7,7 +7,8 @@ import numpy as np
 import pytest
 
 import bn254_py as o
-from sw05_fixture import Instance, OracleEngine, OracleTable, TensorEngine, find_common, kbytes, lagrange, same_on_tensors, sc, t_exponent, tensors
+from standin_engine import StandInEngine, StandInFixedBase, TensorEngine, same_on_tensors, tensors
+from sw05_fixture import Instance, find_common, kbytes, lagrange, sc, t_exponent
 from gopairingbasedcryptography_amd import sw05
 
 R = o.R
@@ -53,7 +54,7 @@ def cts_for(d):
 @pytest.mark.parametrize("large", [False, True])
 @pytest.mark.parametrize("d", [1, 2, 3])
 def test_decrypt_matches_the_reference_loop(oracle, d, large):
-    eng = OracleEngine(oracle)
+    eng = StandInEngine(oracle)
     cts = cts_for(d)
     inst = Instance(eng, d, KEY, cts, n_univ=5 if large else None, tag="p%d" % d)
     assert inst.decryptable() == [True, True, False, True]
@@ -77,7 +78,7 @@ def test_decrypt_matches_the_reference_loop(oracle, d, large):
 def test_decrypt_on_tensors_is_decrypt_on_arrays(oracle, large):
     """the planner's tensor path on CPU tensors (TensorEngine): three ciphertexts, the middle one below the threshold, give tensors
     with the bytes and the ok rows of the numpy run"""
-    eng = OracleEngine(oracle)
+    eng = StandInEngine(oracle)
     cts = cts_for(2)[1:]
     inst = Instance(eng, 2, KEY, cts, n_univ=5 if large else None, tag="kinds")
     if large:
@@ -93,7 +94,7 @@ def test_decrypt_on_tensors_is_decrypt_on_arrays(oracle, large):
 
 
 def test_decrypt_with_nothing_decryptable(oracle):
-    eng = OracleEngine(oracle)
+    eng = StandInEngine(oracle)
     inst = Instance(eng, 2, KEY, [CTS[2], CTS[4]], tag="none")
     eng.multi_pair = eng.g1_scalar_mul = eng.fr_lagrange_basis = lambda *a: pytest.fail("no engine call without a decryptable ciphertext")
     out, ok = sw05.decrypt_batch(eng, inst.key, 2, inst.ct_attrs, inst.E, inst.e_prime)
@@ -108,10 +109,10 @@ def test_decrypt_with_nothing_decryptable(oracle):
 def test_compute_t_against_the_exponent_route(oracle, n):
     """T_x for attributes outside and inside N = {1 .. n+1}, x = 0 and full-size values, with the reference's node list 0 .. n:
     equal to [x^n + sum_j tau_j Delta_{x,N}(j)] g2"""
-    eng = OracleEngine(oracle)
+    eng = StandInEngine(oracle)
     inst = Instance(eng, 1, [1], [[1]], n_univ=n, tag="ct%d" % n)
     xs = [0, 1, 2, n + 1, n + 2, 77, sc("x", n), R - 1]
-    table = OracleTable(oracle, inst.table_bases)
+    table = StandInFixedBase(oracle, inst.table_bases, g2=True)
     want = np.asarray(oracle.g2_scalar_mul(inst.g2, kbytes([t_exponent(inst.taus, n, x) for x in xs]))).reshape(-1, 128)
     got = sw05.compute_t(eng, table, n, xs)
     assert got.shape == (len(xs), 128) and (got == want).all()
@@ -130,7 +131,7 @@ def test_compute_t_against_the_exponent_route(oracle, n):
 
 
 def test_stand_in_lagrange_is_the_reference_loop():
-    eng = OracleEngine(None)
+    eng = StandInEngine(None)
     S = [3, 8, R + 3, 12]
     got = eng.fr_lagrange_basis(kbytes(S), 4)
     assert got.shape == (1, 4, 32)

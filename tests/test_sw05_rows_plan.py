@@ -1,43 +1,24 @@
 """The SW05 planners from attribute rows (sw05.decrypt_batch / decrypt_batch_large with ct_attrs as [n, a, 32] scalar rows), CPU part: on the
-stand-in engine of tests/sw05_fixture.py with fr_find_common in Python integers, and behind TensorEngine, against the integer form of the
+stand-in engine of tests/standin_engine.py with fr_find_common in Python integers, and behind TensorEngine, against the integer form of the
 same planner on the same instance — the bytes must be the same."""
 import numpy as np
 import pytest
 
 import select_cases as sel
-from sw05_fixture import Instance, OracleEngine, TensorEngine, kints, same_on_tensors, tensors
+from standin_engine import StandInEngine, TensorEngine, recorded, same_on_tensors, tensors
+from sw05_fixture import Instance, kints
 from test_sw05_plan import CTS, KEY, cts_for
 from gopairingbasedcryptography_amd import sw05
 
 R = sel.R
 
 
-class RowsEngine(OracleEngine):
-    """OracleEngine with the selection entry: utils/find_common_attributes.go through tests/select_cases.py, in Python integers"""
-
-    def __init__(self, oracle):
-        super().__init__(oracle)
-        self.selections = []
-
-    def fr_find_common(self, sets, lists, m, a, d):
-        S, L = np.asarray(kints_raw(sets), dtype=object).reshape(-1, m), np.asarray(kints_raw(lists), dtype=object).reshape(-1, a)
-        case = dict(label="stand-in", m=m, a=a, d=d, k=len(L), shared=len(S) == 1, sets=[list(s) for s in S], lists=[list(l) for l in L])
-        self.selections.append((len(S), len(L), m, a, d))
-        sp, lp, cm, ok = sel.expected(case)
-        return sp.astype(np.int32), lp.astype(np.int32), cm, ok
-
-
-def kints_raw(buf):
-    return [int.from_bytes(r.tobytes(), "little") for r in np.asarray(buf, dtype=np.uint8).reshape(-1, 32)]
-
-
-class RowsTensorEngine(TensorEngine):
-    """TensorEngine hands arrays back as uint8 tensors; the positions of fr_find_common are int32 and stay so"""
-
-    def fr_find_common(self, sets, lists, m, a, d):
-        import torch
-        sp, lp, cm, ok = self._engine.fr_find_common(sets.numpy(), lists.numpy(), m, a, d)
-        return torch.from_numpy(sp), torch.from_numpy(lp), torch.from_numpy(cm), torch.from_numpy(ok)
+def RowsEngine(oracle):
+    """the stand-in engine with a record of its selections: (key sets, lists, m, a, d) per fr_find_common call"""
+    eng = StandInEngine(oracle)
+    calls = recorded(eng, ("fr_find_common",))
+    eng.selections = lambda: [(np.asarray(sets).size // (32 * m), np.asarray(lists).size // (32 * a), m, a, d) for _, (sets, lists, m, a, d) in calls]
+    return eng
 
 
 def decrypt(eng, inst, d, ct_attrs, large, key=None, parts=None):
@@ -64,12 +45,12 @@ def test_rows_form_is_the_integer_form(oracle, d, large):
     cts = cts_for(d)
     inst = Instance(eng, d, KEY, cts, n_univ=5 if large else None, tag="p%d" % d)
     want, want_ok = decrypt(eng, inst, d, cts, large)
-    assert want_ok.tolist() == [1, 1, 0, 1] and eng.selections == []
+    assert want_ok.tolist() == [1, 1, 0, 1] and eng.selections() == []
     rows = sel.rows(v for c in cts for v in c).reshape(4, 5, 32)                                  # unreduced: r - 3 and full-size values as they are
     calls = []
     eng.multi_pair = lambda P, Q, off, f=eng.multi_pair: calls.append((len(off) - 1, np.asarray(P).size // 64)) or f(P, Q, off)
     got, ok = decrypt(eng, inst, d, rows, large)
-    assert eng.selections == [(1, 4, 6, 5, d)] and calls == [(3, 3 * d * (2 if large else 1))]    # one selection; the item below the threshold takes no part
+    assert eng.selections() == [(1, 4, 6, 5, d)] and calls == [(3, 3 * d * (2 if large else 1))]    # one selection; the item below the threshold takes no part
     assert ok.dtype == np.uint8 and ok.tolist() == [1, 1, 0, 1] and got.shape == (4, 384)
     assert got.tobytes() == np.asarray(want).tobytes() and not got[2].any()
     for t in (0, 1, 3):
@@ -80,10 +61,10 @@ def test_rows_form_is_the_integer_form(oracle, d, large):
         assert again.tobytes() == got.tobytes() and ok2.tolist() == [1, 1, 0, 1]
     # behind TensorEngine: tensors in, tensors out, the same bytes
     parts = tensors(inst.E, inst.e_prime, *([inst.e_pp] if large else []))
-    got_t, ok_t = decrypt(RowsTensorEngine(eng), inst, d, tensors(rows)[0], large, parts=parts)
+    got_t, ok_t = decrypt(TensorEngine(eng), inst, d, tensors(rows)[0], large, parts=parts)
     assert same_on_tensors(got_t, got) and same_on_tensors(ok_t, ok)
     key_t = tuple(tensors(sw05.attribute_rows(KEY), *inst.key[1:]))
-    got_t, ok_t = decrypt(RowsTensorEngine(eng), inst, d, tensors(rows)[0], large, key=key_t, parts=parts)
+    got_t, ok_t = decrypt(TensorEngine(eng), inst, d, tensors(rows)[0], large, key=key_t, parts=parts)
     assert same_on_tensors(got_t, got) and same_on_tensors(ok_t, ok)
 
 
@@ -102,17 +83,17 @@ def test_a_key_per_item(oracle, large):
         out, ok = decrypt(eng, inst, d, [cts[t]], large, parts=parts)
         want.append(np.asarray(out).reshape(384))
         want_ok.append(int(ok[0]))
-    assert want_ok == [1, 1, 0, 1, 1, 1, 0] and eng.selections == []              # ciphertext 2 shares one attribute (4) with either key
+    assert want_ok == [1, 1, 0, 1, 1, 1, 0] and eng.selections() == []              # ciphertext 2 shares one attribute (4) with either key
     stack = lambda f: np.stack([np.asarray(f(insts[i], t)) for i, t in pairs])
     rows = stack(lambda inst, t: sel.rows(cts[t]))
     attrs = stack(lambda inst, t: sel.rows(inst.key[0]))
     key = (attrs,) + tuple(stack(lambda inst, t, c=c: inst.key[c]) for c in range(1, 3 if large else 2))
     parts = [stack(lambda inst, t: inst.E[t]), stack(lambda inst, t: inst.e_prime.reshape(-1, 384)[t])] + ([stack(lambda inst, t: inst.e_pp.reshape(-1, 64)[t])] if large else [])
     got, ok = decrypt(eng, None, d, rows, large, key=key, parts=parts)
-    assert eng.selections == [(7, 7, 6, 5, d)] and ok.tolist() == want_ok
+    assert eng.selections() == [(7, 7, 6, 5, d)] and ok.tolist() == want_ok
     assert got.tobytes() == np.stack(want).tobytes() and not got[2].any() and not got[6].any()
     assert (got[0] != got[4]).any()                                                               # the keys do differ
-    got_t, ok_t = decrypt(RowsTensorEngine(eng), None, d, tensors(rows)[0], large, key=tuple(tensors(*key)), parts=tensors(*parts))
+    got_t, ok_t = decrypt(TensorEngine(eng), None, d, tensors(rows)[0], large, key=tuple(tensors(*key)), parts=tensors(*parts))
     assert same_on_tensors(got_t, got) and same_on_tensors(ok_t, ok)
 
 

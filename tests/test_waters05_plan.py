@@ -8,8 +8,8 @@ import hashlib
 import numpy as np
 import pytest
 
-from sw05_fixture import TensorEngine, same_on_tensors, tensors
-from waters05_fixture import Engine, Instance, id_bits
+from standin_engine import StandInEngine, TensorEngine, same_on_tensors, tensors
+from waters05_fixture import Instance, id_bits
 from gopairingbasedcryptography_amd import waters05
 
 IDS = ["alice@example.com", "bob@example.com", "carol", "身份", "x"]
@@ -32,7 +32,7 @@ def test_identity_masks_are_the_reference_bits():
 
 
 def test_keygen_and_encrypt_match_the_reference_sequence(oracle, inst):
-    eng = Engine(oracle)
+    eng = StandInEngine(oracle)
     n = len(IDS)
     table = waters05.hash_table(eng, inst.u_prime, inst.ui)
     assert table.nbits == 256 and table.g2 and (table.O == inst.u_prime).all()
@@ -58,7 +58,7 @@ def test_keygen_and_encrypt_match_the_reference_sequence(oracle, inst):
 
 
 def test_decrypt_returns_the_messages(oracle, inst):
-    eng = Engine(oracle)
+    eng = StandInEngine(oracle)
     n = len(IDS)
     calls = []
     eng.multi_pair = lambda P, Q, off, f=eng.multi_pair: calls.append((len(off) - 1, np.asarray(P).size // 64)) or f(P, Q, off)
@@ -82,7 +82,7 @@ def test_decrypt_returns_the_messages(oracle, inst):
 
 def test_planner_on_tensors_is_the_planner_on_arrays(oracle, inst):
     """the tensor path on CPU tensors (TensorEngine): the bytes of the numpy run, as tensors"""
-    eng = Engine(oracle)
+    eng = StandInEngine(oracle)
     table = waters05.hash_table(eng, inst.u_prime, inst.ui)
     masks = waters05.identity_masks(IDS[:3])
     tm, tr, tt, tmsg = tensors(masks, inst.rows(inst.r[:3]), inst.rows(inst.t[:3]), inst.messages[:3])

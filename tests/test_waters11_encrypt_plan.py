@@ -1,5 +1,5 @@
 """Waters11 CP-ABE Encrypt and KeyGenerate through the host planner (gopairingbasedcryptography_amd/waters11.py: encrypt_batch,
-keygen_batch) on the oracle stand-in engine (tests/indexed_standin.py; the same flow runs on the GPU engine in
+keygen_batch) on the oracle stand-in engine (tests/standin_engine.py; the same flow runs on the GPU engine in
 test_lsss_encrypt_gpu.py): fed the fixture's own secrets it returns the fixture's ciphertext bytes on every real row and the point at
 infinity on every padding row, the existing decrypt_batch recovers the messages (and reports the policy the key does not satisfy),
 and keygen_batch returns the fixture's key construction."""
@@ -7,8 +7,8 @@ import numpy as np
 import pytest
 
 import bn254_py as o
-from indexed_standin import IndexedEngine
-from sw05_fixture import TensorEngine, kbytes, same_on_tensors, tensors
+from standin_engine import StandInEngine, TensorEngine, same_on_tensors, tensors
+from sw05_fixture import kbytes
 from waters11_fixture import Instance, sc as fsc, small_policies
 from gopairingbasedcryptography_amd import waters11
 
@@ -50,7 +50,7 @@ def check_ciphertexts(inst, got, back=np.asarray):
 
 @pytest.fixture(scope="module")
 def setup(oracle):
-    eng = IndexedEngine(oracle)
+    eng = StandInEngine(oracle)
     policies, key_attrs = small_policies()
     inst = Instance(eng, key_attrs, policies)
     return eng, inst, fixture_inputs(inst)

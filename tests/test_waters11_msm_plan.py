@@ -4,35 +4,16 @@ fixture's four-policy batch, and the engine calls that the docstring promises.""
 import numpy as np
 import pytest
 
-import gmsm_cases as gc
-from sw05_fixture import kints
-from waters11_fixture import Instance, OracleEngineW11, small_policies
+from standin_engine import StandInEngine, recorded
+from waters11_fixture import Instance, small_policies
 from gopairingbasedcryptography_amd import waters11
-
-
-class OracleEngineMsm(OracleEngineW11):
-    """+ g1_multi_scalar_mul from the oracle: scalar multiplication per term, the oracle's sum per segment"""
-
-    def g1_multi_scalar_mul(self, bases, scalars, seg_off):
-        seg = [int(v) for v in seg_off]
-        return gc.expect(self.o, False, np.asarray(bases, dtype=np.uint8).reshape(-1, 64), kints(scalars), seg, False)
-
-
-def recorded(eng, names):
-    calls = []
-    for name in names:
-        def wrap(*a, _f=getattr(eng, name), _n=name):
-            calls.append((_n, a))
-            return _f(*a)
-        setattr(eng, name, wrap)
-    return calls
 
 
 def test_msm_route_gives_the_same_bytes_with_one_sum_call(oracle):
     pols, key = small_policies()
-    inst = Instance(OracleEngineMsm(oracle), key, pols, tag="plan")
+    inst = Instance(StandInEngine(oracle), key, pols, tag="plan")
     n, R = 4, 5
-    eng = OracleEngineMsm(oracle)
+    eng = StandInEngine(oracle)
     calls = recorded(eng, ("g1_add", "g1_scalar_mul", "g1_multi_scalar_mul", "multi_pair"))
     out0, ok0 = waters11.decrypt_batch(eng, inst.key, pols, inst.c, inst.c_prime, inst.cx, inst.dx)
     names0 = [c[0] for c in calls]
@@ -56,7 +37,7 @@ def test_msm_route_gives_the_same_bytes_with_one_sum_call(oracle):
 def test_msm_route_without_the_entry_is_an_error(oracle):
     """an engine without g1_multi_scalar_mul cannot take the route: no quiet fall-back to the composed one"""
     pols, key = small_policies()
-    eng = OracleEngineW11(oracle)
+    eng = StandInEngine(oracle, without=("g1_multi_scalar_mul",))
     inst = Instance(eng, key, pols[:2], tag="args")
     with pytest.raises(AttributeError):
         waters11.decrypt_batch(eng, inst.key, pols[:2], inst.c, inst.c_prime, inst.cx, inst.dx, msm=True)

@@ -7,8 +7,8 @@ import numpy as np
 import pytest
 
 import bn254_py as o
-from sw05_fixture import TensorEngine, same_on_tensors, tensors
-from waters11_fixture import Instance, OracleEngineW11, and_or_16, small_policies
+from standin_engine import StandInEngine, TensorEngine, same_on_tensors, tensors
+from waters11_fixture import Instance, and_or_16, small_policies
 from gopairingbasedcryptography_amd import lw11, waters11
 
 R = o.R
@@ -45,7 +45,7 @@ def test_and_or_16_is_what_it_says():
 
 
 def test_decrypt_matches_the_row_by_row_decrypt(oracle):
-    eng = OracleEngineW11(oracle)
+    eng = StandInEngine(oracle)
     pols, key = small_policies()
     inst = Instance(eng, key, pols, tag="plan")
     assert inst.satisfied() == [True, True, True, False]
@@ -69,7 +69,7 @@ def test_decrypt_matches_the_row_by_row_decrypt(oracle):
 
 
 def test_decrypt_argument_checks(oracle):
-    eng = OracleEngineW11(oracle)
+    eng = StandInEngine(oracle)
     pols, key = small_policies()
     inst = Instance(eng, key, pols[:2], tag="args")
     with pytest.raises(ValueError):

@@ -4,13 +4,13 @@ outputs of KeyGenerate and Encrypt are single generator multiplications too (the
 h = u' + sum_{Id[i] = 1} u_i): a route that shares nothing with the table sums under test.
 
 Also here: the reference's own sequence of operations written out with oracle calls (the chain of G2Affine.Add over Id[], the scalar
-multiplication, Pair / Mul / Div of Decrypt), and the stand-in engine the plan test runs the planner on."""
+multiplication, Pair / Mul / Div of Decrypt).  The stand-in engine the plan test runs the planner on is tests/standin_engine.py."""
 import hashlib
 
 import numpy as np
 
 import bn254_py as o
-from sw05_fixture import OracleEngine, kbytes
+from sw05_fixture import kbytes
 
 R = o.R
 G1 = np.frombuffer(o.g1_to_bytes(o.G1_GEN), dtype=np.uint8)
@@ -71,47 +71,3 @@ class Instance:
     def reference_decrypt(self, d1, d2, c1, c2, c3):
         m = self.oracle.gt_mul(c1, self.oracle.pair_batch(d2, c3)[0])[0]
         return self.oracle.gt_div(m, self.oracle.pair_batch(c2, d1)[0])[0]
-
-
-class OracleSubsetTable:
-    """bn254.SubsetTable on the oracle: the point sum over [offset] + the selected bases, row by row"""
-
-    def __init__(self, oracle, bases, offset=None, g2=False):
-        self.o, self.g2, self.width = oracle, g2, 128 if g2 else 64
-        self.B = np.asarray(bases, dtype=np.uint8).reshape(-1, self.width)
-        self.O = None if offset is None else np.asarray(offset, dtype=np.uint8).reshape(1, self.width)
-        self.nbits, self.closed, self.calls = len(self.B), False, 0
-
-    def sum(self, masks):
-        self.calls += 1
-        masks = np.asarray(masks, dtype=np.uint8).reshape(-1, (self.nbits + 7) // 8)
-        sel = np.unpackbits(masks, axis=1)[:, :self.nbits].astype(bool)
-        add = self.o.g2_sum if self.g2 else self.o.g1_sum
-        out = np.zeros((len(masks), self.width), dtype=np.uint8)
-        for m in range(len(masks)):
-            pts = np.concatenate(([] if self.O is None else [self.O]) + [self.B[sel[m]]])
-            if len(pts):
-                out[m] = add(pts)
-        return out
-
-    def close(self):
-        self.closed = True
-
-
-class Engine(OracleEngine):
-    """sw05_fixture.OracleEngine plus the names waters05.py calls besides"""
-
-    def g1_scalar_mul_base(self, k):
-        return self.o.g1_scalar_mul(G1, self._k(k), threads=4)
-
-    def g2_add(self, a, b):
-        a, b = np.asarray(a, dtype=np.uint8).reshape(-1, 128), np.asarray(b, dtype=np.uint8).reshape(-1, 128)
-        return np.stack([self.o.g2_sum(np.stack([x, b[i if len(b) > 1 else 0]])) for i, x in enumerate(a)])
-
-    def g1_sub(self, a, b):
-        a, b = np.asarray(a, dtype=np.uint8).reshape(-1, 64), np.asarray(b, dtype=np.uint8).reshape(-1, 64)
-        neg = lambda p: np.frombuffer(o.g1_to_bytes(o.g1_neg(o.g1_from_bytes(p.tobytes()))), dtype=np.uint8)
-        return np.stack([self.o.g1_sum(np.stack([x, neg(b[i if len(b) > 1 else 0])])) for i, x in enumerate(a)])
-
-    def SubsetTable(self, bases, offset=None, g2=False):
-        return OracleSubsetTable(self.o, bases, offset, g2)

@@ -7,14 +7,14 @@ base).  One key against n ciphertexts, each under a policy of its own, all padde
 to the column count, waters11_cpabe.go:182,211: the same thing for its square test matrices).
 
 Also here: the scheme's Decrypt row by row with oracle calls (each row's own term raised to its own weight), the policies of the
-tests and the stand-in engine the plan tests run the planner on (fr_lsss_weights from lw11.reconstruction_weights).
+tests.  The stand-in engine the plan tests run the planner on is tests/standin_engine.py.
 
 numpy arrays by default; with `dev` a torch device everything per ciphertext is made and kept in HBM (the instances at size)."""
 import numpy as np
 
 import bn254_py as o
 import lw11_fixture as lf
-from sw05_fixture import OracleEngine, kbytes, kints
+from sw05_fixture import kbytes
 from gopairingbasedcryptography_amd import lw11
 
 R = o.R
@@ -121,26 +121,3 @@ def at_size_policies(n, every=64):
     key = chain16[1] + thr[1][3:12] + andor[1][8:] + [600 + i for i in range(5)]          # 9 of the 16 Shamir rows, the second AND branch
     bad = ([[1, 1], [0, -1]], [700, 701])                                                  # needs 700 and 701: the key has neither
     return [bad if j % every == every - 1 else shapes[j % 4] for j in range(n)], key
-
-
-# ------------------------------------------------------------------------------------------------ stand-in for the plan tests
-class OracleEngineW11(OracleEngine):
-    """+ g1_add on the oracle's sum and fr_lsss_weights from the elimination in Python integers"""
-
-    def g1_add(self, a, b):
-        a, b = np.asarray(a, dtype=np.uint8).reshape(-1, 64), np.asarray(b, dtype=np.uint8).reshape(-1, 64)
-        return np.stack([np.asarray(self.o.g1_sum(np.concatenate([x, y]))).reshape(64) for x, y in zip(a, b)])
-
-    def g1_scalar_mul(self, b, k):
-        return np.asarray(self.o.g1_scalar_mul(b, self._k(k), threads=4)).reshape(-1, 64)
-
-    def fr_lsss_weights(self, matrix, rows, cols, held):
-        held = np.asarray(held, dtype=np.uint8).reshape(-1, rows)
-        mats = np.asarray(kints(matrix), dtype=object).reshape(-1, rows, cols)
-        w, ok = np.zeros((len(held), rows, 32), dtype=np.uint8), np.zeros(len(held), dtype=np.uint8)
-        for j, h in enumerate(held):
-            got = lw11.reconstruction_weights(mats[j if len(mats) > 1 else 0].tolist(), list(range(rows)), [x for x in range(rows) if h[x]])
-            if got is not None:
-                ok[j] = 1
-                w[j, got[0]] = kbytes(got[1]).reshape(-1, 32)
-        return w, ok
