@@ -112,8 +112,10 @@ def expand(a, *shape):
 
 
 def put(table, like):
-    """a host array as a buffer of the kind of `like`, on its device"""
+    """a host array as a buffer of the kind of `like`, on its device; a tensor already there passes through"""
     if not is_torch(like):
+        return table
+    if is_torch(table) and table.device == like.device:
         return table
     import torch
     return torch.from_numpy(np.ascontiguousarray(table)).to(like.device)

@@ -99,6 +99,12 @@ RECON_SIGNATURES = {
 SELECT_SIGNATURES = {
     "gpbc_select_version": "i:", "gpbc_fr_find_common": "i:pzzpzzzpppp", "gpbc_fr_find_common_dev": "i:pzzpzzzppppp",
 }
+# ... and for include/gpbc_bn254_formula.h, LSSS matrices and 0 / 1 weights from boolean formulas (tests/test_formula.py holds this table
+# against that header).  The nine tables are disjoint.
+FORMULA_SIGNATURES = {
+    "gpbc_formula_version": "i:", "gpbc_fr_lsss_from_formula": "i:pzzzzpppp", "gpbc_fr_lsss_from_formula_dev": "i:pzzzzppppp",
+    "gpbc_formula_select": "i:pzzpzzpp", "gpbc_formula_select_dev": "i:pzzpzzppp",
+}
 # every pointer is a c_void_p: it takes ints, None, c_void_p, ctypes arrays, byref() and ndarray.ctypes.data_as() alike
 _CTYPES = {"p": ctypes.c_void_p, "z": ctypes.c_size_t, "i": ctypes.c_int, "l": ctypes.c_long, "s": ctypes.c_char_p}
 
@@ -124,7 +130,7 @@ def load():
         except ImportError:
             pass
         lib = ctypes.CDLL(LIB_PATH)
-        for name, sig in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(SUBSET_SIGNATURES.items()) + list(HASH_SIGNATURES.items()) + list(SHARE_SIGNATURES.items()) + list(INDEXED_SIGNATURES.items()) + list(RECON_SIGNATURES.items()) + list(SELECT_SIGNATURES.items()):
+        for name, sig in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(SUBSET_SIGNATURES.items()) + list(HASH_SIGNATURES.items()) + list(SHARE_SIGNATURES.items()) + list(INDEXED_SIGNATURES.items()) + list(RECON_SIGNATURES.items()) + list(SELECT_SIGNATURES.items()) + list(FORMULA_SIGNATURES.items()):
             ret, params = sig.split(":")
             fn = getattr(lib, name)
             fn.restype = _CTYPES[ret]

@@ -917,6 +917,103 @@ def fr_find_common(sets, lists, m, a, d, set_pos_out=None, list_pos_out=None, co
     return positions(sp), positions(lp), cm.reshape(k, d, SCALAR_BYTES), ok.reshape(k)
 
 
+FORMULA_MAX_NODES = 127
+
+
+def _formula_nodes(nodes):
+    """(buffer, number of formulas, n_nodes) of an int64 array or CUDA tensor [k, N] (or [N]: one formula) of formula codes"""
+    if bufs.is_torch(nodes):
+        if str(nodes.dtype) != "torch.int64" or not nodes.is_contiguous():
+            raise ValueError("nodes must be a contiguous int64 tensor")
+    elif isinstance(nodes, np.ndarray):
+        if nodes.dtype != np.int64:
+            raise ValueError("nodes must be int64 (got %s)" % nodes.dtype)
+        nodes = np.ascontiguousarray(nodes)
+    else:
+        raise ValueError("nodes must be an int64 array or a CUDA tensor of formula codes (formula.encode makes them)")
+    if nodes.ndim not in (1, 2) or not 1 <= nodes.shape[-1] <= FORMULA_MAX_NODES:
+        raise ValueError("nodes must be [k, N] or [N] with N in 1 .. %d (got shape %s)" % (FORMULA_MAX_NODES, tuple(nodes.shape)))
+    return nodes, (1 if nodes.ndim == 1 else int(nodes.shape[0])), int(nodes.shape[-1])
+
+
+def _formula_size(v, what):
+    if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 1 <= int(v) <= FR_LSSS_MAX:
+        raise ValueError("%s must be in 1 .. %d (got %s)" % (what, FR_LSSS_MAX, v))
+    return int(v)
+
+
+def _typed(x, dtype, *shape):
+    """a uint8 output buffer as its typed view"""
+    if bufs.is_torch(x):
+        import torch
+        return x.reshape(-1).view(getattr(torch, dtype)).reshape(*shape)
+    return x.reshape(-1).view(getattr(np, dtype)).reshape(*shape)
+
+
+def fr_lsss_from_formula(nodes, rows, cols, matrix_out=None, rho_out=None, dims_out=None, ok_out=None):
+    """(matrix [k, rows, cols, 32], rho [k, rows] int64, dims [k, 2] int32, ok [k]): the Lewko-Waters share matrices of k boolean
+    formulas in one launch — NewLSSSMatrixFromBinaryTree per item (include/gpbc_bn254_formula.h).  nodes: [k, N] int64 codes, a numpy
+    array or a CUDA tensor (formula.encode makes them): a tree in preorder, a code >= 0 a leaf with that attribute, -2 AND, -3 OR, -1
+    padding behind the tree.  The matrix is in the layout fr_lsss_shares and fr_lsss_weights read: entries 0, 1 and r - 1, rows and
+    columns past an item's own all zero, rho there -1; dims is the item's own (rows, columns).  ok = 0 with a zero matrix, rho all -1 and
+    dims (0, 0) for a malformed formula, more leaves than `rows` or more columns than `cols`.  A caller's outputs are uint8 buffers of
+    k x rows x cols x 32, k x rows x 8 (8-byte aligned), k x 2 x 4 (4-byte aligned) and k bytes.  Outputs are of the kind that went in;
+    tensors are enqueued on the current stream and not synchronised."""
+    rows, cols = _formula_size(rows, "rows"), _formula_size(cols, "cols")
+    nodes, k, N = _formula_nodes(nodes)
+    outs = (matrix_out, rho_out, dims_out, ok_out)
+    dev = bufs.device_of(nodes, *outs)
+    if k > (1 << 29) - 1:
+        raise ValueError("too many items for one call (%d)" % k)
+    mat = bufs.output(matrix_out, (k, rows, cols, SCALAR_BYTES), dev, "matrix_out")
+    rho = bufs.output(rho_out, (k, rows, 8), dev, "rho_out")
+    dims = bufs.output(dims_out, (k, 2, 4), dev, "dims_out")
+    ok = bufs.output(ok_out, (k,), dev, "ok_out")
+    if bufs.address(rho) % 8 or bufs.address(dims) % 4:
+        raise ValueError("rho_out must be 8-byte aligned and dims_out 4-byte aligned")
+    if k:
+        got = (mat, rho, dims, ok)
+        nb = _typed(nodes, "uint8", -1)
+        if any(_overlaps(o, nb, *got[:i]) for i, o in enumerate(got)):
+            raise ValueError("an output overlaps the input or another output")
+        _call("fr_lsss_from_formula", dev, nodes, N, k, rows, cols, mat, rho, dims, ok)
+    return mat.reshape(k, rows, cols, SCALAR_BYTES), _typed(rho, "int64", k, rows), _typed(dims, "int32", k, 2), ok.reshape(k)
+
+
+def formula_select(nodes, held, rows, chosen_out=None, ok_out=None):
+    """(chosen [k, rows], ok [k]): for k keys the leaves of a formula whose rows recombine with weight 1 (include/gpbc_bn254_formula.h).
+    nodes: [k, N] int64 codes, or [N] / [1, N] for one formula shared by all keys; held: k x rows bytes in leaf order, the mask
+    fr_lsss_weights takes on the matrix of fr_lsss_from_formula.  From a satisfied root both children of an AND are taken and, at an OR,
+    the left child if it is satisfied, else the right; chosen is 1 at the leaves reached.  ok = 0 and a zero row for an unsatisfied root,
+    a malformed formula or more leaves than `rows`.  For ok = 1 the chosen rows of the matrix sum to (1, 0, ..., 0).  Outputs are of the
+    kind that went in; tensors are enqueued on the current stream and not synchronised."""
+    rows = _formula_size(rows, "rows")
+    nodes, nf, N = _formula_nodes(nodes)
+    if isinstance(held, np.ndarray):
+        if held.dtype not in (np.uint8, np.bool_):
+            raise ValueError("held must be uint8 or bool (got %s)" % held.dtype)
+        held = held.astype(np.uint8, copy=False)
+    elif not bufs.is_torch(held):
+        raise ValueError("held must be a uint8 array or a CUDA tensor")
+    hb, nheld = bufs.rows(held, 1, "held")
+    dev = bufs.device_of(nodes, hb, chosen_out, ok_out)
+    if nheld % rows:
+        raise ValueError("held needs %d bytes per item" % rows)
+    k = nheld // rows
+    if k and nf not in (1, k):
+        raise ValueError("need one formula or one per mask (got %d formulas, %d masks)" % (nf, k))
+    if k > (1 << 29) - 1:
+        raise ValueError("too many items for one call (%d)" % k)
+    chosen = bufs.output(chosen_out, (k, rows), dev, "chosen_out")
+    ok = bufs.output(ok_out, (k,), dev, "ok_out")
+    if k:
+        nb = _typed(nodes, "uint8", -1)
+        if _overlaps(chosen, nb, hb) or _overlaps(ok, nb, hb, chosen):
+            raise ValueError("an output overlaps an input or the other output")
+        _call("formula_select", dev, nodes, nf, N, hb, k, rows, chosen, ok)
+    return chosen.reshape(k, rows), ok.reshape(k)
+
+
 _gen_tables = {}
 
 

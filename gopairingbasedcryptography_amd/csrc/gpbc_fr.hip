@@ -4,7 +4,8 @@
 // ciphertext (Waters11 CP-ABE) — with their C-ABI entries (include/gpbc_bn254.h, "scalar field"), and secret sharing (csrc/share29.hip.hpp):
 // polynomial evaluation and the shares of a threshold tree (include/gpbc_bn254_share.h), and LSSS share generation (csrc/lsss29.hip.hpp,
 // include/gpbc_bn254_indexed.h), and the reconstruction weights of a threshold tree (csrc/recon29.hip.hpp, include/gpbc_bn254_recon.h),
-// and the common attributes of a list and a set (csrc/select29.hip.hpp, include/gpbc_bn254_select.h).
+// and the common attributes of a list and a set (csrc/select29.hip.hpp, include/gpbc_bn254_select.h),
+// and LSSS matrices and 0 / 1 weights from boolean formulas (csrc/formula29.hip.hpp, include/gpbc_bn254_formula.h).
 // gfx950 only.
 #include "gpbc_common.hpp"
 #include "fr29.hip.hpp"
@@ -12,10 +13,12 @@
 #include "recon29.hip.hpp"
 #include "lsss29.hip.hpp"
 #include "select29.hip.hpp"
+#include "formula29.hip.hpp"
 #include "../../include/gpbc_bn254_share.h"
 #include "../../include/gpbc_bn254_indexed.h"
 #include "../../include/gpbc_bn254_recon.h"
 #include "../../include/gpbc_bn254_select.h"
+#include "../../include/gpbc_bn254_formula.h"
 
 // ------------------------------------------------------------------------------------------------ elementwise
 // one element per lane (no __restrict__: out may be a, or b)
@@ -328,6 +331,33 @@ GPBC_KERNEL_G1 k_fr_find_common(const uint8_t *__restrict__ sets, const uint8_t 
 }
 __global__ void __launch_bounds__(BLOCK) k_fr_find_common_large(const uint8_t *__restrict__ sets, const uint8_t *__restrict__ lists, size_t k, SelectGeom gm, SelectOut o) {
     fr_find_common_kernel<FR_SELECT_WORDS_LARGE>(sets, lists, k, gm, o);
+}
+
+// ------------------------------------------------------------------------------------------------ formulas
+// NewLSSSMatrixFromBinaryTree for k formulas and the 0 / 1 weights of such a matrix: formula29.hip.hpp has the geometry, the staging, the
+// walks and the write-out; here are the LDS blocks (the items' codes; for the matrices also a stack, the leaf records and the verdict per
+// item) and the barriers.
+static_assert(FORMULA_WAVE == BLOCK, "one wave per workgroup");
+GPBC_KERNEL_G1 k_fr_lsss_from_formula(const int64_t *__restrict__ nodes, size_t k, FormulaGeom gm, FormulaOut o) {
+    __shared__ uint32_t ss[FORMULA_BUILD_WORDS];
+    const auto getw = [&](uint32_t off) { return ss[off]; };
+    const auto putw = [&](uint32_t off, uint32_t v) { ss[off] = v; };
+    formula_stage(gm, blockIdx.x, threadIdx.x, k, nodes, putw);
+    __syncthreads();
+    formula_build_walk(gm, blockIdx.x, threadIdx.x, k, getw, putw);
+    __syncthreads();
+    formula_build_write(gm, blockIdx.x, threadIdx.x, k, getw,
+                        [&](size_t item, uint32_t p, const uint32_t (&w)[4]) { formula_store_piece(gm, o, item, p, w); },
+                        [&](size_t item, uint32_t x, int64_t a) { formula_store_rho(o, item, x, a); },
+                        [&](size_t item, bool ok, uint32_t nrows, uint32_t ncols) { formula_store_done(o, item, ok, nrows, ncols); });
+}
+GPBC_KERNEL_G1 k_formula_select(const int64_t *__restrict__ nodes, const uint8_t *__restrict__ held, size_t k, FormulaGeom gm, uint8_t *__restrict__ chosen_out,
+                                uint8_t *__restrict__ ok_out) {
+    __shared__ uint32_t ss[FORMULA_SELECT_WORDS];
+    formula_stage(gm, blockIdx.x, threadIdx.x, k, nodes, [&](uint32_t off, uint32_t v) { ss[off] = v; });
+    __syncthreads();
+    formula_select_lane(gm, blockIdx.x, threadIdx.x, k, [&](uint32_t off) { return ss[off]; }, held,
+                        [&](size_t item, bool ok, uint64_t chosen) { formula_store_chosen(gm, chosen_out, ok_out, item, ok, chosen); });
 }
 
 extern "C" {
@@ -768,6 +798,88 @@ int gpbc_fr_lsss_shares(const void *matrix, size_t n_matrices, size_t rows, size
     HostCall c = HostCall().input(matrix, rows * cols * GPBC_SCALAR_BYTES, one).input(vectors, cols * GPBC_SCALAR_BYTES);
     return host_call_sharded(k, shard_min ? shard_min : 1, c.output(out, rows * GPBC_SCALAR_BYTES), HostRoute{},
                              [=](const DevCols &d, size_t m, hipStream_t st) { return gpbc_fr_lsss_shares_dev(d.in[0], one ? 1 : m, rows, cols, d.in[1], m, d.out[0], st); });
+}
+
+// ------------------------------------------------------------------------------------------------ formula entries (include/gpbc_bn254_formula.h)
+int gpbc_formula_version(void) { return 1; }
+static int formula_sizes(size_t n_nodes, size_t rows, size_t cols, size_t k) {
+    if (n_nodes < 1 || n_nodes > (size_t)FORMULA_MAX_NODES) return fail(GPBC_ERR_INVALID_ARG, "n_nodes must be in 1 .. %d (got %zu)", FORMULA_MAX_NODES, n_nodes);
+    if (rows < 1 || rows > (size_t)FORMULA_MAX || cols < 1 || cols > (size_t)FORMULA_MAX)
+        return fail(GPBC_ERR_INVALID_ARG, "rows and cols must be in 1 .. %d (got rows = %zu, cols = %zu)", FORMULA_MAX, rows, cols);
+    if (k > (size_t)0x7fffffff / 4) return fail(GPBC_ERR_INVALID_ARG, "too many items for one call (%zu)", k);
+    return GPBC_OK;
+}
+static int from_formula_args(const void *nodes, size_t n_nodes, size_t k, size_t rows, size_t cols, const void *matrix_out, const void *rho_out, const void *dims_out, const void *ok_out) {
+    TRY(formula_sizes(n_nodes, rows, cols, k));
+    if (!k) return GPBC_OK;
+    if (!nodes || !matrix_out || !rho_out || !ok_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    const void *p[5] = {nodes, matrix_out, rho_out, ok_out, dims_out};
+    const size_t nb[5] = {k * n_nodes * sizeof(int64_t), k * rows * cols * GPBC_SCALAR_BYTES, k * rows * sizeof(int64_t), k, k * 2 * sizeof(uint32_t)};
+    for (int i = 1; i < (dims_out ? 5 : 4); i++)
+        for (int j = 0; j < i; j++)
+            if (overlap(p[i], nb[i], p[j], nb[j])) return fail(GPBC_ERR_INVALID_ARG, "an output overlaps the input or another output");
+    return GPBC_OK;
+}
+static int from_formula_launch(const void *d_nodes, size_t n_nodes, size_t k, size_t rows, size_t cols, const FormulaOut &o, void *stream) {
+    TRY(bind_device());
+    const FormulaGeom g = formula_build_geometry(n_nodes, rows, cols, (((uintptr_t)o.matrix | o.mat_step) & 15) == 0);
+    return GPBC_LAUNCH(k_fr_lsss_from_formula, (unsigned)formula_grid(g, k), BLOCK, (hipStream_t)stream, (const int64_t *)d_nodes, k, g, o);
+}
+int gpbc_fr_lsss_from_formula_dev(const int64_t *d_nodes, size_t n_nodes, size_t k, size_t rows, size_t cols, void *d_matrix_out, int64_t *d_rho_out, uint32_t *d_dims_out,
+                                  uint8_t *d_ok_out, void *stream) {
+    TRY(from_formula_args(d_nodes, n_nodes, k, rows, cols, d_matrix_out, d_rho_out, d_dims_out, d_ok_out));
+    if (!k) return GPBC_OK;
+    return from_formula_launch(d_nodes, n_nodes, k, rows, cols,
+                               FormulaOut{(uint8_t *)d_matrix_out, (uint8_t *)d_rho_out, (uint8_t *)d_dims_out, d_ok_out, rows * cols * GPBC_SCALAR_BYTES, rows * sizeof(int64_t), 2 * sizeof(uint32_t)}, stream);
+}
+// Host-pointer form: the shared staging path on the current device.  It carries two output columns, so an item's matrix, rho and dims travel
+// as one record (the kernel writes the record's parts at the record's pitch, a multiple of 16) and are dealt out here.
+int gpbc_fr_lsss_from_formula(const int64_t *nodes, size_t n_nodes, size_t k, size_t rows, size_t cols, void *matrix_out, int64_t *rho_out, uint32_t *dims_out, uint8_t *ok_out) {
+    TRY(from_formula_args(nodes, n_nodes, k, rows, cols, matrix_out, rho_out, dims_out, ok_out));
+    if (!k) return GPBC_OK;
+    const size_t mb = rows * cols * GPBC_SCALAR_BYTES, rb = rows * sizeof(int64_t), db = 2 * sizeof(uint32_t), rec = (mb + rb + db + 15) / 16 * 16;
+    std::vector<uint8_t> records, oks;
+    try { records.resize(k * rec); oks.resize(k); } catch (const std::bad_alloc &) { return fail(GPBC_ERR_INTERNAL, "out of host memory for %zu records", k); }
+    TRY(host_call(k, HostCall().input(nodes, n_nodes * sizeof(int64_t)).output(records.data(), rec).output(oks.data(), 1), HostRoute{},
+                  [=](const DevCols &dc, size_t n, hipStream_t st) {
+                      return from_formula_launch(dc.in[0], n_nodes, n, rows, cols, FormulaOut{dc.out[0], dc.out[0] + mb, dc.out[0] + mb + rb, dc.out[1], rec, rec, rec}, st);
+                  }));
+    for (size_t j = 0; j < k; j++) {
+        const uint8_t *r = records.data() + j * rec;
+        memcpy((uint8_t *)matrix_out + j * mb, r, mb);
+        memcpy((uint8_t *)rho_out + j * rb, r + mb, rb);
+        if (dims_out) memcpy((uint8_t *)dims_out + j * db, r + mb + rb, db);
+    }
+    memcpy(ok_out, oks.data(), k);
+    return GPBC_OK;
+}
+static int formula_select_args(const void *nodes, size_t n_formulas, size_t n_nodes, const void *held, size_t k, size_t rows, const void *chosen_out, const void *ok_out) {
+    TRY(formula_sizes(n_nodes, rows, 1, k));
+    if (!k) return GPBC_OK;
+    if (n_formulas != 1 && n_formulas != k) return fail(GPBC_ERR_INVALID_ARG, "n_formulas must be 1 or k (got %zu, k = %zu)", n_formulas, k);
+    if (!nodes || !held || !chosen_out || !ok_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    const size_t fb = n_formulas * n_nodes * sizeof(int64_t), hb = k * rows;
+    if (overlap(chosen_out, hb, nodes, fb) || overlap(chosen_out, hb, held, hb) || overlap(ok_out, k, nodes, fb) || overlap(ok_out, k, held, hb) || overlap(chosen_out, hb, ok_out, k))
+        return fail(GPBC_ERR_INVALID_ARG, "an output overlaps an input or the other output");
+    return GPBC_OK;
+}
+int gpbc_formula_select_dev(const int64_t *d_nodes, size_t n_formulas, size_t n_nodes, const uint8_t *d_held, size_t k, size_t rows, uint8_t *d_chosen_out, uint8_t *d_ok_out,
+                            void *stream) {
+    TRY(formula_select_args(d_nodes, n_formulas, n_nodes, d_held, k, rows, d_chosen_out, d_ok_out));
+    if (!k) return GPBC_OK;
+    TRY(bind_device());
+    const FormulaGeom g = formula_select_geometry(n_nodes, rows, n_formulas == 1 && k > 1);
+    return GPBC_LAUNCH(k_formula_select, (unsigned)formula_grid(g, k), BLOCK, (hipStream_t)stream, d_nodes, d_held, k, g, d_chosen_out, d_ok_out);
+}
+// Host-pointer form: the shared staging path on the current device; one formula travels once.
+int gpbc_formula_select(const int64_t *nodes, size_t n_formulas, size_t n_nodes, const uint8_t *held, size_t k, size_t rows, uint8_t *chosen_out, uint8_t *ok_out) {
+    TRY(formula_select_args(nodes, n_formulas, n_nodes, held, k, rows, chosen_out, ok_out));
+    if (!k) return GPBC_OK;
+    const bool one = n_formulas == 1;
+    return host_call(k, HostCall().input(nodes, n_nodes * sizeof(int64_t), one).input(held, rows).output(chosen_out, rows).output(ok_out, 1), HostRoute{},
+                     [=](const DevCols &dc, size_t n, hipStream_t st) {
+                         return gpbc_formula_select_dev((const int64_t *)dc.in[0], one ? 1 : n, n_nodes, dc.in[1], n, rows, dc.out[0], dc.out[1], st);
+                     });
 }
 
 }  // extern "C"

@@ -25,6 +25,10 @@ rows of the matrix or all weights are equal.  This planner follows the scheme, a
 ones of the greedy first basis of the held rows (include/gpbc_bn254.h), not necessarily the solution the reference's
 back-substitution lands on: any valid weights give the same message.
 
+Policies written as boolean formulas (formula.py) need neither the solve nor the multiplications: the matrix of a formula recombines
+with weights 0 and 1, and decrypt_batch_formulas takes the rows with weight 1 from engine.formula_select (opt-in; decrypt_batch is
+unchanged and takes formula.padded(...) like any other block).
+
 Host orchestration only, engine-agnostic (every function takes the engine: `bn254`, or a stand-in with the same function names).
 Host arrays in give host arrays out; CUDA tensors in give CUDA tensors out, with only the key, the padded matrices, the mask and
 an index table going to the device."""
@@ -171,6 +175,54 @@ def decrypt_batch_host_weights(engine, key, policies, c, c_prime, cx, dx):
                 w[t, got[0]] = _plan.scalar_rows(got[1])
         return put(w), put(ok)
     return _decrypt(engine, key, pad, c, c_prime, cx, dx, weights)
+
+
+def decrypt_batch_formulas(engine, key, nodes, c, c_prime, cx, dx, rows=None):
+    """decrypt_batch for ciphertexts whose policies are boolean formulas (formula.encode: [n, N] int64 codes, a host array or a tensor
+    where the ciphertexts are), encrypted under formula.padded(...).  The matrix of a formula recombines with weights 0 and 1: the
+    leaves engine.formula_select reaches from a satisfied root.  So no system is solved and no point is multiplied:
+
+        S = -(sum of the chosen C_x),  T_x = -K_rho(x) for the chosen rows, the point at infinity elsewhere,
+
+    in front of the same multi-pairing segments of R + 2 pairs and gt_div.  rows: R of cx and dx (None: the largest leaf count).
+    Returns (messages [n, 384], ok [n]), byte for byte those of decrypt_batch on formula.padded(...): GT output is canonical and any
+    valid weights give the same message.  An unsatisfied or malformed formula has ok = 0 and an all-zero row.  Engine calls:
+    formula_select, g1_sum_segments (n segments of R points), g1_sub twice (the n sums and the key's components from infinity),
+    multi_pair, gt_div."""
+    from . import formula
+    K, L, kx = key
+    rho = formula.leaves(nodes, rows, strict=False)
+    n, R = rho.shape
+    bufs.device_of(c, c_prime, cx, dx)                                         # all of one kind, on one device
+    if bufs.nbytes(c) != n * 384 or bufs.nbytes(c_prime) != n * 128 or bufs.nbytes(cx) != n * R * 64 or bufs.nbytes(dx) != n * R * 128:
+        raise ValueError("need c [n, 384], c_prime [n, 128], cx [n, R, 64], dx [n, R, 128] with n = %d, R = %d" % (n, R))
+
+    def put(a):
+        return bufs.put(a, c)
+    c, c_prime, cx, dx = bufs.view(c, n, 384), bufs.view(c_prime, n, 1, 128), bufs.view(cx, n * R, 64), bufs.view(dx, n, R, 128)
+    if not n:
+        return bufs.zeros((0, 384), c), bufs.zeros((0,), c)
+    attrs = sorted(int(a) for a in kx)
+    comp = np.zeros((len(attrs) + 1, 64), dtype=np.uint8)                 # the last row: the point at infinity, for rows the key lacks
+    for i, a in enumerate(attrs):
+        comp[i] = np.asarray(kx[a], dtype=np.uint8).reshape(64)
+    index = key_index(rho, attrs)
+    held = (index < len(attrs)).astype(np.uint8)
+    codes = nodes if bufs.is_torch(nodes) else put(np.ascontiguousarray(nodes, dtype=np.int64))
+    chosen, ok = engine.formula_select(codes, put(held).reshape(-1), R)        # [n, R] of 0 / 1, [n]
+    chosen = bufs.view(chosen, n * R, 1)
+    sums = engine.g1_sum_segments(bufs.flat(cx * chosen), _plan.segments(n, R))
+    S = engine.g1_sub(bufs.flat(bufs.zeros((n, 64), c)), bufs.flat(sums))
+    neg = engine.g1_sub(bufs.flat(bufs.zeros((len(attrs) + 1, 64), c)), bufs.flat(put(comp)))
+    T = (bufs.take(bufs.view(neg, len(attrs) + 1, 64), index.reshape(-1)) * chosen).reshape(n, R, 64)
+    k_rows = put(np.broadcast_to(np.asarray(K, dtype=np.uint8).reshape(1, 1, 64), (n, 1, 64)))
+    l_rows = put(np.broadcast_to(np.asarray(L, dtype=np.uint8).reshape(1, 1, 128), (n, 1, 128)))
+    P = bufs.cat([k_rows, bufs.view(S, n, 1, 64), T], 1)
+    Q = bufs.cat([c_prime, l_rows, dx], 1)
+    E = engine.multi_pair(bufs.flat(P), bufs.flat(Q), _plan.segments(n, R + 2))
+    msgs = engine.gt_div(bufs.flat(c), bufs.flat(E)).reshape(n, 384)
+    ok = ok.reshape(n)
+    return msgs * ok.reshape(n, 1), ok
 
 
 # ------------------------------------------------------------------------------------------------ Encrypt and KeyGenerate

@@ -27,6 +27,7 @@
 #include "../gopairingbasedcryptography_amd/csrc/recon29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/lsss29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/select29.hip.hpp"
+#include "../gopairingbasedcryptography_amd/csrc/formula29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/fbindex29.hip.hpp"
 #include <condition_variable>
 #include <mutex>
@@ -1130,6 +1131,72 @@ int hc_fr_find_common(const uint8_t *sets, size_t n_sets, size_t m, const uint8_
     if (std::count(slot_seen.begin(), slot_seen.end(), 1) != (ptrdiff_t)(k * d) || std::count(item_seen.begin(), item_seen.end(), 1) != (ptrdiff_t)k) return -2;
     if (geom_out) { geom_out[0] = g.lpi; geom_out[1] = g.ipb; geom_out[2] = g.chunks; geom_out[3] = g.pitch; geom_out[4] = g.large; geom_out[5] = g.shared; geom_out[6] = (uint32_t)grid; geom_out[7] = active; }
     stats_flush();
+    return 0;
+}
+// k_fr_lsss_from_formula as it is launched: the staging, the walk and the write-out of formula29.hip.hpp, workgroup by workgroup, a barrier =
+// the end of a loop over the lanes, the LDS block a CheckedWords of single words.  wide: the 128-bit store of a piece (matrix_out 16-byte
+// aligned) or the byte stores.  geom_out: [items per workgroup, LDS words, workgroups, pieces written].
+// -1: arguments the entry refuses; -2: a refusal of the LDS stand-in, a lane outside the outputs, or a piece, a rho or a verdict written twice or never.
+int hc_fr_lsss_from_formula(const int64_t *nodes, size_t n_nodes, size_t k, size_t rows, size_t cols, uint8_t *matrix_out, int64_t *rho_out, uint32_t *dims_out, uint8_t *ok_out,
+                            int wide, uint32_t *geom_out) {
+    if (n_nodes < 1 || n_nodes > (size_t)FORMULA_MAX_NODES || rows < 1 || rows > (size_t)FORMULA_MAX || cols < 1 || cols > (size_t)FORMULA_MAX || !k) return -1;
+    if (!nodes || !matrix_out || !rho_out || !ok_out || (wide && ((uintptr_t)matrix_out & 15))) return -1;
+    const FormulaGeom g = formula_build_geometry(n_nodes, rows, cols, wide != 0);
+    const FormulaOut o{matrix_out, (uint8_t *)rho_out, (uint8_t *)dims_out, ok_out, rows * cols * 32, rows * sizeof(int64_t), 2 * sizeof(uint32_t)};
+    CheckedWords lds((size_t)FORMULA_BUILD_WORDS);
+    const size_t grid = formula_grid(g, k), pieces = rows * cols * 2;
+    std::vector<uint8_t> piece_seen(k * pieces, 0), rho_seen(k * rows, 0), item_seen(k, 0);
+    bool outside = false;
+    const auto getw = [&](uint32_t off) { return lds.getw(off); };
+    const auto putw = [&](uint32_t off, uint32_t v) { lds.putw(off, v); };
+    for (size_t block = 0; block < grid; block++) {
+        lds.reset();
+        for (uint32_t lane = 0; lane < FORMULA_WAVE; lane++) formula_stage(g, (uint32_t)block, lane, k, nodes, putw);
+        for (uint32_t lane = 0; lane < FORMULA_WAVE && !lds.bad; lane++) formula_build_walk(g, (uint32_t)block, lane, k, getw, putw);
+        for (uint32_t lane = 0; lane < FORMULA_WAVE && !lds.bad; lane++)
+            formula_build_write(g, (uint32_t)block, lane, k, getw,
+                                [&](size_t item, uint32_t p, const uint32_t (&w)[4]) {
+                                    if (item >= k || p >= pieces || piece_seen[item * pieces + p]++) { outside = true; return; }
+                                    formula_store_piece(g, o, item, p, w);
+                                },
+                                [&](size_t item, uint32_t x, int64_t a) {
+                                    if (item >= k || x >= rows || rho_seen[item * rows + x]++) { outside = true; return; }
+                                    formula_store_rho(o, item, x, a);
+                                },
+                                [&](size_t item, bool ok, uint32_t nrows, uint32_t ncols) {
+                                    if (item >= k || item_seen[item]++) { outside = true; return; }
+                                    formula_store_done(o, item, ok, nrows, ncols);
+                                });
+        if (lds.bad || outside) return -2;
+    }
+    if (std::count(piece_seen.begin(), piece_seen.end(), 1) != (ptrdiff_t)(k * pieces) || std::count(rho_seen.begin(), rho_seen.end(), 1) != (ptrdiff_t)(k * rows) ||
+        std::count(item_seen.begin(), item_seen.end(), 1) != (ptrdiff_t)k)
+        return -2;
+    if (geom_out) { geom_out[0] = g.ipb; geom_out[1] = (uint32_t)FORMULA_BUILD_WORDS; geom_out[2] = (uint32_t)grid; geom_out[3] = (uint32_t)(k * pieces); }
+    return 0;
+}
+// k_formula_select as it is launched.  geom_out: [items per workgroup, pitch, shared, workgroups].  Return codes as above.
+int hc_formula_select(const int64_t *nodes, size_t n_formulas, size_t n_nodes, const uint8_t *held, size_t k, size_t rows, uint8_t *chosen_out, uint8_t *ok_out, uint32_t *geom_out) {
+    if (n_nodes < 1 || n_nodes > (size_t)FORMULA_MAX_NODES || rows < 1 || rows > (size_t)FORMULA_MAX || !k || (n_formulas != 1 && n_formulas != k)) return -1;
+    if (!nodes || !held || !chosen_out || !ok_out) return -1;
+    const FormulaGeom g = formula_select_geometry(n_nodes, rows, n_formulas == 1 && k > 1);
+    CheckedWords lds((size_t)FORMULA_SELECT_WORDS);
+    const size_t grid = formula_grid(g, k);
+    std::vector<uint8_t> item_seen(k, 0);
+    bool outside = false;
+    for (size_t block = 0; block < grid; block++) {
+        lds.reset();
+        for (uint32_t lane = 0; lane < FORMULA_WAVE; lane++) formula_stage(g, (uint32_t)block, lane, k, nodes, [&](uint32_t off, uint32_t v) { lds.putw(off, v); });
+        for (uint32_t lane = 0; lane < FORMULA_WAVE && !lds.bad; lane++)
+            formula_select_lane(g, (uint32_t)block, lane, k, [&](uint32_t off) { return lds.getw(off); }, held,
+                                [&](size_t item, bool ok, uint64_t chosen) {
+                                    if (item >= k || item_seen[item]++) { outside = true; return; }
+                                    formula_store_chosen(g, chosen_out, ok_out, item, ok, chosen);
+                                });
+        if (lds.bad || outside) return -2;
+    }
+    if (std::count(item_seen.begin(), item_seen.end(), 1) != (ptrdiff_t)k) return -2;
+    if (geom_out) { geom_out[0] = g.ipb; geom_out[1] = g.pitch; geom_out[2] = g.shared; geom_out[3] = (uint32_t)grid; }
     return 0;
 }
 }  // extern "C"
