@@ -105,6 +105,12 @@ FORMULA_SIGNATURES = {
     "gpbc_formula_version": "i:", "gpbc_fr_lsss_from_formula": "i:pzzzzpppp", "gpbc_fr_lsss_from_formula_dev": "i:pzzzzppppp",
     "gpbc_formula_select": "i:pzzpzzpp", "gpbc_formula_select_dev": "i:pzzpzzppp",
 }
+# ... and for include/gpbc_bn254_random.h, ChaCha20 blocks and scalars addressed by (seed, stream, index) and the 64-byte reduction into
+# Fr (tests/test_random_abi.py holds this table against that header).  The ten tables are disjoint.
+RANDOM_SIGNATURES = {
+    "gpbc_random_version": "i:", "gpbc_random_bytes": "i:pzzzp", "gpbc_random_bytes_dev": "i:pzzzpp", "gpbc_fr_random": "i:pzzzp",
+    "gpbc_fr_random_dev": "i:pzzzpp", "gpbc_fr_set_bytes64": "i:pzp", "gpbc_fr_set_bytes64_dev": "i:pzpp",
+}
 # every pointer is a c_void_p: it takes ints, None, c_void_p, ctypes arrays, byref() and ndarray.ctypes.data_as() alike
 _CTYPES = {"p": ctypes.c_void_p, "z": ctypes.c_size_t, "i": ctypes.c_int, "l": ctypes.c_long, "s": ctypes.c_char_p}
 
@@ -130,7 +136,7 @@ def load():
         except ImportError:
             pass
         lib = ctypes.CDLL(LIB_PATH)
-        for name, sig in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(SUBSET_SIGNATURES.items()) + list(HASH_SIGNATURES.items()) + list(SHARE_SIGNATURES.items()) + list(INDEXED_SIGNATURES.items()) + list(RECON_SIGNATURES.items()) + list(SELECT_SIGNATURES.items()) + list(FORMULA_SIGNATURES.items()):
+        for name, sig in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(SUBSET_SIGNATURES.items()) + list(HASH_SIGNATURES.items()) + list(SHARE_SIGNATURES.items()) + list(INDEXED_SIGNATURES.items()) + list(RECON_SIGNATURES.items()) + list(SELECT_SIGNATURES.items()) + list(FORMULA_SIGNATURES.items()) + list(RANDOM_SIGNATURES.items()):
             ret, params = sig.split(":")
             fn = getattr(lib, name)
             fn.restype = _CTYPES[ret]

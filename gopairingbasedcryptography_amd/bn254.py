@@ -1343,6 +1343,64 @@ def hash_g1_gt_gt_to_fr(u, v, w, out=None):
     return _rowwise("hash_g1_gt_gt_to_fr", SCALAR_BYTES, (u, G1_BYTES, "u"), (v, GT_BYTES, "v"), (w, GT_BYTES, "w"), out=out)
 
 
+# --------------------------------------------------------------------------------------- randomness addressed by (seed, stream, index)
+RANDOM_SEED_BYTES = 32
+RANDOM_BLOCK_BYTES = 64
+
+
+def _seed_arg(seed):
+    """the 32 seed bytes as a ctypes buffer of their own (the C entries take a host pointer); no message ever shows them"""
+    if isinstance(seed, np.ndarray) and seed.dtype == np.uint8:
+        seed = seed.tobytes()
+    if not isinstance(seed, (bytes, bytearray)) or len(seed) != RANDOM_SEED_BYTES:
+        raise ValueError("seed must be %d bytes" % RANDOM_SEED_BYTES)
+    return (ctypes.c_char * RANDOM_SEED_BYTES).from_buffer_copy(bytes(seed))
+
+
+def _random(name, width, seed, n, stream, first, out, like):
+    for what, v in (("n", n), ("stream", stream), ("first", first)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) < 1 << 64:
+            raise ValueError("%s must be an integer in [0, 2^64)" % what)
+    n, stream, first = int(n), int(stream), int(first)
+    if first + n > 1 << 64:
+        raise ValueError("first + n exceeds 2^64")
+    seed = _seed_arg(seed)
+    dev = bufs.device_of(out, like)
+    out = bufs.output(out, (n, width), dev)
+    if n:
+        _call(name, dev, seed, stream, first, n, out)
+    return out.reshape(n, width)
+
+
+def random_bytes(seed, n_blocks, stream=0, first=0, out=None, like=None):
+    """[n_blocks, 64]: the ChaCha20 blocks first .. first + n_blocks - 1 of `stream` under the 32-byte `seed` (include/gpbc_bn254_random.h:
+    RFC 8439's block function, `first + i` the 64-bit block counter, `stream` the 64-bit nonce), made on the device in one launch.
+    A numpy array by default; a CUDA tensor as `out` or `like` gives a tensor, enqueued on the current stream and not synchronised.
+    The seed is key material: whoever holds it can recompute the output."""
+    return _random("random_bytes", RANDOM_BLOCK_BYTES, seed, n_blocks, stream, first, out, like)
+
+
+def fr_random(seed, n, stream=0, first=0, out=None, like=None):
+    """[n, 32] scalars: scalar i is OS2IP(block first + i of `stream`) mod r, canonical — one fr.Element.SetRandom() each, but a function
+    of (seed, stream, index) alone, the same from Python, C and Go (include/gpbc_bn254_random.h).  Buffers as for random_bytes.  The seed
+    is key material: whoever holds it can recompute every scalar."""
+    return _random("fr_random", SCALAR_BYTES, seed, n, stream, first, out, like)
+
+
+def fr_set_bytes64(x, out=None):
+    """[n, 32] scalars: out[i] = OS2IP(x[64 i .. 64 i + 63]) mod r, fr.Element.SetBytes / hash.BytesToField on 64-byte strings — the
+    reduction of fr_random on the caller's strings.  x: n x 64 bytes, a uint8 array, bytes or a CUDA tensor; the output is of its kind
+    and must not overlap it."""
+    dev = bufs.device_of(x, out)
+    x, n = bufs.rows(x, RANDOM_BLOCK_BYTES, "x")
+    out = bufs.output(out, (n, SCALAR_BYTES), dev)
+    if n:
+        if _overlaps(out, x):
+            raise ValueError("out overlaps x")
+        _call("fr_set_bytes64", dev, x, n, out)
+    return out.reshape(n, SCALAR_BYTES)
+
+
 # --------------------------------------------------------------------------------------- fixed-base tables / MSM
 INDEX_NONE = 0xFFFFFFFF          # GPBC_INDEX_NONE: "no term" in an index row of FixedBase.indexed
 INDEXED_MAX_TERMS = 16

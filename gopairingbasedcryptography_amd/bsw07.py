@@ -199,6 +199,21 @@ def encrypt_batch(engine, tree_or_plan, h, e_alpha, h1, messages, s, coeffs, tab
     return bufs.view(c_tilde, n, 384), bufs.view(c, n, 64), bufs.view(cy, n, L, 64), bufs.view(cy_prime, n, L, 64)
 
 
+def encrypt_batch_seeded(engine, tree_or_plan, h, e_alpha, h1, messages, rng, tables=False):
+    """encrypt_batch with its randomness drawn on the device: rng is an rng.Randomness over the engine, everything else as there, and
+    the return value is exactly encrypt_batch's on the scalars drawn.  The draws, in this order (the order is part of the interface:
+    it is what makes the ciphertexts reproducible from the seed): s [n], then coeffs [n, C] with C the sum of (threshold - 1) over the
+    gates — two stream ids, one when C == 0 (a draw of no columns takes none), none when n == 0.  The scalars are of the kind of
+    `messages`: CUDA tensors in, and nothing but the seed crosses to the device.  The seed is key material: whoever holds it can
+    recompute s and with it every message."""
+    nodes, attributes = share_plan(tree_or_plan) if isinstance(tree_or_plan, (Leaf, Threshold)) else tree_or_plan
+    n = bufs.nbytes(messages) // 384
+    C = sum(int(t) - 1 for _, t in nodes if int(t))
+    s = rng.scalars(messages, n)
+    coeffs = rng.scalars(messages, n, C) if C else None
+    return encrypt_batch(engine, (nodes, attributes), h, e_alpha, h1, messages, s, coeffs, tables=tables)
+
+
 def _share_tree(engine, nodes, L):
     """engine.ShareTree over the plan's nodes, closed on the way out; its leaves must be the plan's L attributes"""
     return _plan.handle(None, lambda: engine.ShareTree(nodes), "leaves", L, "the plan names %(want)d attributes for %(got)d leaves")

@@ -200,6 +200,20 @@ GPBC_INLINE Fr fr_reduce(const Fr &a) { return fr_mul(a, fr_one()); }
 GPBC_INLINE Fr fr_to_internal(const Fr &plain) { constexpr int32_t C[NL] = FR29_RSQ; return fr_mul(plain, fr_const(C)); }
 // x == 0 (mod r), exactly, for a loaded value
 GPBC_INLINE bool fr_is_zero(const Fr &a) { return fr_limbs_zero(fr_canonical<1, 2>(fr_reduce(a))); }
+// OS2IP(64 bytes) mod r, canonical: fr.Element.SetBytes / hash.BytesToField on a 64-byte string, held in registers as the sixteen
+// little-endian words of its bytes in order (a ChaCha20 block as it comes out).  Read big-endian the string is hi 2^256 + lo with
+// hi = bytes 0..31 and lo = bytes 32..63: word k of a half is the byte-swapped word 7 - k of its bytes.  Both halves go through the
+// scalar format's raw load (below 2^256 < 5.3 r each); hi 2^256 is ONE product with 2^517 mod r (mont(x, 2^517) = x 2^256, the
+// constant of the fr.Element conversion), in (-eps r, (1 + eps) r); the sum with lo is below 6.3 r + eps r, and the canonical form
+// subtracts r at most seven times.
+GPBC_INLINE Fr fr_wide_reduce(const uint32_t (&w)[16]) {
+    uint32_t hi[8], lo[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) { hi[k] = __builtin_bswap32(w[7 - k]); lo[k] = __builtin_bswap32(w[15 - k]); }
+    constexpr int32_t C[NL] = FR29_PLAIN_TO_MONT;
+    const Fr top = fr_mul(fr_load_raw(reinterpret_cast<const uint8_t *>(hi)), fr_const(C));
+    return fr_canonical<1, 7>(fr_add(top, fr_load_raw(reinterpret_cast<const uint8_t *>(lo))));
+}
 
 // ------------------------------------------------------------------------------------------------ inversion
 // x -> 2^522 / x (the internal inverse of an internal x; 0 -> 0): fe_inv's safegcd with the modulus r.  The divsteps and the (f, g)

@@ -192,3 +192,18 @@ def encrypt_batch(engine, e, egg_alpha, g2_y, matrix, rho, messages, s, v, w, r,
         c3, ok = table.indexed(index, bufs.flat(bufs.cat([r2, bufs.view(om, n * R, 1, 32)], 1)), terms=2)
     c0 = _plan.blind(engine, put(np.asarray(e, dtype=np.uint8).reshape(384)), s, messages, n)
     return bufs.view(c0, n, 384), bufs.view(c1, n, R, 384), bufs.view(c2, n, R, 128), bufs.view(c3, n, R, 128)
+
+
+def encrypt_batch_seeded(engine, e, egg_alpha, g2_y, matrix, rho, messages, rng, table=None):
+    """encrypt_batch with its randomness drawn on the device: rng is an rng.Randomness over the engine, everything else as there, and
+    the return value is exactly encrypt_batch's on the scalars drawn.  The draws, in this order (the order is part of the interface: it
+    is what makes the ciphertexts reproducible from the seed): s [n], v [n, C - 1], w [n, C - 1], r [n, R] — four stream ids, two when
+    C == 1 (a draw of no columns takes none), none when n == 0.  The scalars are of the kind of `messages`.  The seed is key material:
+    whoever holds it can recompute s and with it every message."""
+    R, C = len(matrix), len(matrix[0]) if len(matrix) else 0
+    n = bufs.nbytes(messages) // 384
+    s = rng.scalars(messages, n)
+    v = rng.scalars(messages, n, C - 1) if C > 1 else None
+    w = rng.scalars(messages, n, C - 1) if C > 1 else None
+    r = rng.scalars(messages, n, R)
+    return encrypt_batch(engine, e, egg_alpha, g2_y, matrix, rho, messages, s, v, w, r, table=table)

@@ -302,3 +302,32 @@ def keygen_batch_large(engine, table, n, y, coeffs, attrs, r):
     T = compute_t(engine, table, n, bufs.view(bufs.flat(attrs), k * m, 32))
     D = engine.g2_add(bufs.flat(engine.g2_scalar_mul_base(bufs.flat(q))), bufs.flat(engine.g2_scalar_mul(bufs.flat(T), bufs.flat(r))))
     return bufs.view(engine.g1_scalar_mul_base(bufs.flat(r)), k, m, 64), bufs.view(D, k, m, 128)
+
+
+def _seeded_polynomials(attrs, other, d, rng):
+    """(attrs [k, m, 32] as a buffer, coeffs [k, d - 1, 32] drawn from rng or None for d == 1, k, m); the buffers are tensors where
+    attrs or `other` is one"""
+    if not isinstance(d, (int, np.integer)) or isinstance(d, bool) or d < 1:
+        raise ValueError("d must be an integer >= 1 (got %s)" % (d,))
+    attrs, k, m = _matrix(attrs, next((v for v in (attrs, other) if bufs.is_torch(v)), None), "attrs")
+    return attrs, (rng.scalars(attrs, k, int(d) - 1) if d > 1 else None), k, m
+
+
+def keygen_batch_seeded(engine, y, d, attrs, t, rng):
+    """keygen_batch with its randomness drawn on the device: d is the threshold (the polynomials have degree d - 1), rng an
+    rng.Randomness over the engine, y, attrs and t as there; returns exactly keygen_batch's D on the coefficients drawn.  The one draw
+    (the order is part of the interface): coeffs [k, d - 1], user-major — one stream id, none when d == 1 or k == 0.  The coefficients
+    are of the kind of attrs (or of t, where attrs are Python integers).  The seed is key material: whoever holds it can recompute every
+    user's polynomial."""
+    attrs, coeffs, _, _ = _seeded_polynomials(attrs, t, d, rng)
+    return keygen_batch(engine, y, coeffs, attrs, t)
+
+
+def keygen_batch_large_seeded(engine, table, n, y, d, attrs, rng):
+    """keygen_batch_large with its randomness drawn on the device: d, rng as for keygen_batch_seeded, the rest as there; returns exactly
+    keygen_batch_large's (d, D) on the scalars drawn.  The draws, in this order (the order is part of the interface): coeffs [k, d - 1],
+    then r [k, m] — two stream ids, one when d == 1, none when k == 0.  The seed is key material: whoever holds it can recompute every
+    user's polynomial and every r_i."""
+    attrs, coeffs, k, m = _seeded_polynomials(attrs, None, d, rng)
+    r = rng.scalars(attrs, k, m)
+    return keygen_batch_large(engine, table, n, y, coeffs, attrs, r)

@@ -307,6 +307,20 @@ def encrypt_batch(engine, g1a, e_alpha, h, policies_or_padded, messages, s, v, r
     return bufs.view(c, n, 384), bufs.view(c_prime, n, 128), bufs.view(cx, n, R, 64), bufs.view(dx, n, R, 128)
 
 
+def encrypt_batch_seeded(engine, g1a, e_alpha, h, policies_or_padded, messages, rng, table=None):
+    """encrypt_batch with its randomness drawn on the device: rng is an rng.Randomness over the engine, everything else as there, and
+    the return value is exactly encrypt_batch's on the scalars drawn.  The draws, in this order (the order is part of the interface: it
+    is what makes the ciphertexts reproducible from the seed): s [n], v [n, C - 1], r [n, R], with R and C the padded block's common
+    shape — three stream ids, two when C == 1 (a draw of no columns takes none), none when n == 0.  The scalars are of the kind of
+    `messages`.  The seed is key material: whoever holds it can recompute s and with it every message."""
+    pad = policies_or_padded if isinstance(policies_or_padded, Padded) else pad_policies(policies_or_padded)
+    n, R = pad.rho.shape
+    s = rng.scalars(messages, n)
+    v = rng.scalars(messages, n, pad.cols - 1) if pad.cols > 1 else None
+    r = rng.scalars(messages, n, R)
+    return encrypt_batch(engine, g1a, e_alpha, h, pad, messages, s, v, r, table=table)
+
+
 def keygen_batch(engine, g1_alpha, g1a, h, user_attrs, t, table=None):
     """Keys of n users (KeyGenerate, waters11_cpabe.go:130-168): K = g1^alpha + [t] g1^a, L = [t] g2, K_x = [t] h_x for the user's
     attributes.  g1_alpha = g1^alpha (64 B, the master key), g1a and h as in encrypt_batch; user_attrs: n lists of attributes, each

@@ -29,6 +29,7 @@
 #include "../gopairingbasedcryptography_amd/csrc/select29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/formula29.hip.hpp"
 #include "../gopairingbasedcryptography_amd/csrc/fbindex29.hip.hpp"
+#include "../gopairingbasedcryptography_amd/csrc/chacha29.hip.hpp"
 #include <condition_variable>
 #include <mutex>
 #include <thread>
@@ -1197,6 +1198,43 @@ int hc_formula_select(const int64_t *nodes, size_t n_formulas, size_t n_nodes, c
     }
     if (std::count(item_seen.begin(), item_seen.end(), 1) != (ptrdiff_t)k) return -2;
     if (geom_out) { geom_out[0] = g.ipb; geom_out[1] = g.pitch; geom_out[2] = g.shared; geom_out[3] = (uint32_t)grid; }
+    return 0;
+}
+// The seed-addressed generator (csrc/chacha29.hip.hpp, fr_wide_reduce of csrc/fr29.hip.hpp) as the kernels of csrc/gpbc_hash.hip run a
+// lane.  hc_chacha_blocks is k_random_bytes: the key from the seed bytes, index first + i by a 64-bit add, the block, its 64 bytes through
+// the 128-bit or the byte stores.  hc_fr_wide_reduce is k_fr_set_bytes64: sixteen words in, the reduction under the interval bounds (the
+// product's columns, the canonical form's range), 32 bytes out.  hc_fr_random is k_fr_random: the two in a row.
+int hc_chacha_blocks(const uint8_t *seed, uint64_t stream, uint64_t first, size_t n, uint8_t *out, int wide) {
+    if (!seed || !out || (first && n > (size_t)0 - first) || (wide && ((uintptr_t)out & 15))) return -1;
+    const ChaChaKey key = chacha_key(seed, stream);
+    for (size_t i = 0; i < n; i++) {
+        uint32_t w[16];
+        chacha20_block(w, key, first + i);
+        chacha_store<4>(out + 64 * i, w, wide != 0);
+    }
+    return 0;
+}
+int hc_fr_wide_reduce(const uint8_t *in, size_t n, uint8_t *out, int wide_in, int wide_out) {
+    if (!in || !out || (wide_in && ((uintptr_t)in & 15)) || (wide_out && ((uintptr_t)out & 15))) return -1;
+    for (size_t i = 0; i < n; i++) {
+        uint32_t w[16], s[8];
+        chacha_load64(w, in + 64 * i, wide_in != 0);
+        fr_words(s, fr_wide_reduce(w));
+        chacha_store<2>(out + 32 * i, s, wide_out != 0);
+    }
+    stats_flush();
+    return 0;
+}
+int hc_fr_random(const uint8_t *seed, uint64_t stream, uint64_t first, size_t n, uint8_t *out) {
+    if (!seed || !out || (first && n > (size_t)0 - first)) return -1;
+    const ChaChaKey key = chacha_key(seed, stream);
+    for (size_t i = 0; i < n; i++) {
+        uint32_t w[16], s[8];
+        chacha20_block(w, key, first + i);
+        fr_words(s, fr_wide_reduce(w));
+        chacha_store<2>(out + 32 * i, s, false);
+    }
+    stats_flush();
     return 0;
 }
 }  // extern "C"
