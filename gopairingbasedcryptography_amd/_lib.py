@@ -111,6 +111,13 @@ RANDOM_SIGNATURES = {
     "gpbc_random_version": "i:", "gpbc_random_bytes": "i:pzzzp", "gpbc_random_bytes_dev": "i:pzzzpp", "gpbc_fr_random": "i:pzzzp",
     "gpbc_fr_random_dev": "i:pzzzpp", "gpbc_fr_set_bytes64": "i:pzp", "gpbc_fr_set_bytes64_dev": "i:pzpp",
 }
+# ... and for include/gpbc_bn254_forest.h, sharing and weights over a forest of threshold trees, a tree per item (tests/test_fr_forest.py
+# holds this table against that header).  The eleven tables are disjoint.
+FOREST_SIGNATURES = {
+    "gpbc_forest_version": "i:", "gpbc_share_forest_create": "i:ppzp", "gpbc_share_forest_destroy": "i:p", "gpbc_share_forest_trees": "z:p",
+    "gpbc_share_forest_leaves": "z:p", "gpbc_share_forest_coeffs": "z:p", "gpbc_share_forest_tree_leaves": "z:pz", "gpbc_share_forest_tree_coeffs": "z:pz",
+    "gpbc_fr_share_forest": "i:ppppzpp", "gpbc_fr_share_forest_dev": "i:ppppzppp", "gpbc_fr_forest_weights": "i:pppzpp", "gpbc_fr_forest_weights_dev": "i:pppzppp",
+}
 # every pointer is a c_void_p: it takes ints, None, c_void_p, ctypes arrays, byref() and ndarray.ctypes.data_as() alike
 _CTYPES = {"p": ctypes.c_void_p, "z": ctypes.c_size_t, "i": ctypes.c_int, "l": ctypes.c_long, "s": ctypes.c_char_p}
 
@@ -136,7 +143,7 @@ def load():
         except ImportError:
             pass
         lib = ctypes.CDLL(LIB_PATH)
-        for name, sig in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(SUBSET_SIGNATURES.items()) + list(HASH_SIGNATURES.items()) + list(SHARE_SIGNATURES.items()) + list(INDEXED_SIGNATURES.items()) + list(RECON_SIGNATURES.items()) + list(SELECT_SIGNATURES.items()) + list(FORMULA_SIGNATURES.items()) + list(RANDOM_SIGNATURES.items()):
+        for name, sig in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(SUBSET_SIGNATURES.items()) + list(HASH_SIGNATURES.items()) + list(SHARE_SIGNATURES.items()) + list(INDEXED_SIGNATURES.items()) + list(RECON_SIGNATURES.items()) + list(SELECT_SIGNATURES.items()) + list(FORMULA_SIGNATURES.items()) + list(RANDOM_SIGNATURES.items()) + list(FOREST_SIGNATURES.items()):
             ret, params = sig.split(":")
             fn = getattr(lib, name)
             fn.restype = _CTYPES[ret]

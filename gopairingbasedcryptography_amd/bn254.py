@@ -746,6 +746,158 @@ class ShareTree:
             pass
 
 
+FOREST_MAX_TREES = 65536
+
+
+def _held_bytes(held, width):
+    """held as ShareTree.weights takes it — nested bools / ints, a uint8 or bool array, bytes, or a CUDA tensor — as a flat byte buffer"""
+    if isinstance(held, np.ndarray):
+        if held.dtype not in (np.uint8, np.bool_):
+            raise ValueError("held must be uint8 or bool (got %s)" % held.dtype)
+        return held.astype(np.uint8, copy=False)
+    if bufs.is_torch(held) or isinstance(held, (bytes, bytearray)):
+        return held
+    hrows = [list(h) for h in held]
+    if any(len(h) != width for h in hrows):
+        raise ValueError("held: every item needs %d entries" % width)
+    return np.array([1 if v else 0 for h in hrows for v in h], dtype=np.uint8)
+
+
+class ShareForest:
+    """T threshold access trees uploaded once (include/gpbc_bn254_forest.h): afterwards the shares of k secrets, item i over the tree
+    tree_of[i], are one launch, and so are the reconstruction weights of k attribute sets — ShareTree with a policy per item.
+
+        f = ShareForest([nodes_0, nodes_1, ...])   # each a node list as ShareTree takes it
+        f.trees, f.leaves, f.coeffs                # T, Lmax and Cmax: the columns of the per-item arrays
+        f.tree_leaves, f.tree_coeffs               # [L_t], [C_t]
+        out, ok = f.share(tree_of, secrets, coeffs)    # tree_of: k ids (uint32), coeffs: [k, Cmax] scalars, item i reads its first C_t
+                                                       # -> [k, Lmax, 32] with the columns >= L_t zero; ok [k]: 1 where tree_of[i] < T
+        w, ok = f.weights(tree_of, held)           # held: [k, Lmax] bytes, the columns >= L_t ignored -> [k, Lmax, 32], ok [k]:
+                                                   # 0 where the root is unsatisfied OR the tree id is out of range (a zero row either way)
+
+    Scalars are Python ints, uint8 arrays or CUDA tensors; tree_of is a list of ints, a uint32 array or an int32 CUDA tensor (the same
+    bits).  CUDA tensors give CUDA tensors enqueued on the current stream and not synchronised.  A malformed tree and every argument error
+    are ValueError before the device is touched."""
+
+    def __init__(self, node_lists):
+        self._h = ctypes.c_void_p()
+        lists = list(node_lists)
+        if not lists:
+            raise ValueError("a forest needs at least one tree")
+        if len(lists) > FOREST_MAX_TREES:
+            raise ValueError("more than %d trees" % FOREST_MAX_TREES)
+        arrays = []
+        for t, nodes in enumerate(lists):
+            try:
+                arr = np.ascontiguousarray(np.asarray(nodes, dtype=np.int64).reshape(-1, 2))
+            except (ValueError, TypeError):
+                raise ValueError("tree %d: nodes must be a list of (parent, threshold) pairs" % t) from None
+            if arr.size and (arr.min() < 0 or arr.max() > SHARE_ROOT):
+                raise ValueError("tree %d: parents and thresholds are unsigned 32-bit values" % t)
+            why = share_tree_check(arr.tolist())
+            if why:
+                raise ValueError("malformed tree %d: %s" % (t, why))
+            arrays.append(arr.astype(np.uint32))
+        self.nodes = np.ascontiguousarray(np.concatenate(arrays))
+        self.node_off = np.cumsum([0] + [len(a) for a in arrays]).astype(np.uint32)
+        self.trees = len(arrays)
+        self.tree_leaves = [int((a[:, 1] == 0).sum()) for a in arrays]
+        self.tree_coeffs = [int((a[:, 1].astype(np.int64) - 1)[a[:, 1] != 0].sum()) for a in arrays]
+        self.leaves, self.coeffs = max(self.tree_leaves), max(self.tree_coeffs)
+        self._lib = _lib.load()
+        _ensure_init()
+        _lib.check(self._lib.gpbc_share_forest_create(self.nodes.ctypes.data, self.node_off.ctypes.data, self.trees, ctypes.byref(self._h)))
+        assert (self.trees, self.leaves, self.coeffs) == (self._lib.gpbc_share_forest_trees(self._h), self._lib.gpbc_share_forest_leaves(self._h), self._lib.gpbc_share_forest_coeffs(self._h))
+        assert all((L, C) == (self._lib.gpbc_share_forest_tree_leaves(self._h, t), self._lib.gpbc_share_forest_tree_coeffs(self._h, t))
+                   for t, (L, C) in enumerate(zip(self.tree_leaves, self.tree_coeffs)))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @staticmethod
+    def _ids(tree_of):
+        """(the k tree ids as a flat uint8 buffer of 4 k bytes, k): uint32 on the host, the same bits as int32 on the device"""
+        if bufs.is_torch(tree_of):
+            import torch
+            if tree_of.dtype != torch.int32 or not tree_of.is_contiguous():
+                raise ValueError("tree_of must be a contiguous int32 tensor (the bits of uint32 ids)")
+            return tree_of.reshape(-1).view(torch.uint8), tree_of.numel()
+        if isinstance(tree_of, np.ndarray):
+            if tree_of.dtype != np.uint32:
+                raise ValueError("tree_of must be uint32 (got %s)" % tree_of.dtype)
+            ids = np.ascontiguousarray(tree_of).reshape(-1)
+        else:
+            ids = [int(t) for t in tree_of]
+            if any(t < 0 or t > 0xFFFFFFFF for t in ids):
+                raise ValueError("tree ids are unsigned 32-bit values")
+            ids = np.array(ids, dtype=np.uint32)
+        return ids.view(np.uint8), ids.size
+
+    def share(self, tree_of, secrets, coeffs=None, out=None, ok_out=None):
+        ids, k = self._ids(tree_of)
+        s, ns = bufs.rows(_fr_in(secrets), SCALAR_BYTES, "secrets")
+        if ns != k:
+            raise ValueError("secrets holds %d scalars for %d tree ids" % (ns, k))
+        if coeffs is not None and not bufs.is_torch(coeffs) and not isinstance(coeffs, (np.ndarray, bytes, bytearray)):
+            coeffs = [v for row in coeffs for v in (row if isinstance(row, (list, tuple)) else [row])]
+        c = None
+        if self.coeffs:
+            if coeffs is None:
+                raise ValueError("the forest needs %d coefficients per item" % self.coeffs)
+            c, nc = bufs.rows(_fr_in(coeffs), SCALAR_BYTES, "coeffs")
+            if nc != k * self.coeffs:
+                raise ValueError("coeffs holds %d scalars, expected %d x %d" % (nc, k, self.coeffs))
+        elif coeffs is not None and bufs.nbytes(_fr_in(coeffs)):
+            raise ValueError("the forest takes no coefficients")
+        dev = bufs.device_of(ids, s, c, out, ok_out)
+        if k > (1 << 29) - 1:
+            raise ValueError("too many items for one call (%d)" % k)
+        out = bufs.output(out, (k, self.leaves, SCALAR_BYTES), dev)
+        ok_out = bufs.output(ok_out, (k,), dev, "ok_out")
+        if k:
+            if _overlaps(out, ids, s, c, ok_out) or _overlaps(ok_out, ids, s, c):
+                raise ValueError("an output overlaps an input or the other output")
+            if not self._h:
+                raise ValueError("the forest is closed")
+            _call("fr_share_forest", dev, self._h, ids, s, c, k, out, ok_out)
+        return out, ok_out
+
+    def weights(self, tree_of, held, out=None, ok_out=None):
+        """(w [k, Lmax, 32], ok [k]): ShareTree.weights with item i over the tree tree_of[i].  held: k x Lmax bytes, an item's first L_t
+        columns in its tree's leaf order.  ok = 0 and a zero row where the root is not satisfied or the tree id is T or more."""
+        L = self.leaves
+        ids, k = self._ids(tree_of)
+        hb, nheld = bufs.rows(_held_bytes(held, L), 1, "held")
+        if nheld != k * L:
+            raise ValueError("held holds %d bytes, expected %d x %d" % (nheld, k, L))
+        dev = bufs.device_of(ids, hb, out, ok_out)
+        if k > (1 << 29) - 1:
+            raise ValueError("too many items for one call (%d)" % k)
+        out = bufs.output(out, (k, L, SCALAR_BYTES), dev)
+        ok_out = bufs.output(ok_out, (k,), dev, "ok_out")
+        if k:
+            if _overlaps(out, ids, hb, ok_out) or _overlaps(ok_out, ids, hb):
+                raise ValueError("an output overlaps an input or the other output")
+            if not self._h:
+                raise ValueError("the forest is closed")
+            _call("fr_forest_weights", dev, self._h, ids, hb, k, out, ok_out)
+        return out, ok_out
+
+    def close(self):
+        if self._h:
+            self._lib.gpbc_share_forest_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def share_tree_check(nodes):
     """None, or why gpbc_share_tree_create would refuse the node list [(parent, threshold)] (the rules of include/gpbc_bn254_share.h)"""
     if not nodes:

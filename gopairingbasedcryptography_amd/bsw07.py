@@ -271,6 +271,16 @@ def decrypt_batch_keys(engine, tree_or_plan, held, d_key, dj, dj_prime, c_tilde,
     from the device once (n L bytes): the one point where the call waits for the stream."""
     nodes, attributes = share_plan(tree_or_plan) if isinstance(tree_or_plan, (Leaf, Threshold)) else tree_or_plan
     L = len(attributes)
+    held, n, one_key = _keys_args(held, L, d_key, dj, dj_prime, c_tilde, c, cy, cy_prime)
+    if not n:
+        return bufs.zeros((0, 384), c), bufs.zeros((0,), c)
+    with _share_tree(engine, nodes, L) as tree:
+        w, ok = tree.weights(bufs.flat(bufs.view(held, n * L)))                      # [n, L, 32] canonical, [n]
+    return _decrypt_weighted(engine, n, L, one_key, w, ok, d_key, dj, dj_prime, c_tilde, c, cy, cy_prime)
+
+
+def _keys_args(held, L, d_key, dj, dj_prime, c_tilde, c, cy, cy_prime, *more):
+    """(held as bytes, n, whether d_key is one key for all) of decrypt_batch_keys' arguments, checked: one kind, one device, the sizes"""
     if isinstance(held, np.ndarray):                                                 # as ShareTree.weights takes it: uint8 or bool
         if held.dtype not in (np.uint8, np.bool_):
             raise ValueError("held must be uint8 or bool (got %s)" % held.dtype)
@@ -279,20 +289,20 @@ def decrypt_batch_keys(engine, tree_or_plan, held, d_key, dj, dj_prime, c_tilde,
         held = np.asarray(leaf_rows(held, L), dtype=np.uint8)
     n = bufs.nbytes(c) // 64
     one_key = bufs.nbytes(d_key) == 128                                              # a public-size value: it goes through the host like h of encrypt_batch
-    bufs.device_of(held, dj, dj_prime, c_tilde, c, cy, cy_prime, *([] if one_key else [d_key]))     # all of one kind, on one device
+    bufs.device_of(held, dj, dj_prime, c_tilde, c, cy, cy_prime, *more, *([] if one_key else [d_key]))     # all of one kind, on one device
     if (bufs.nbytes(c) != n * 64 or bufs.nbytes(c_tilde) != n * 384 or bufs.nbytes(cy) != n * L * 64 or bufs.nbytes(cy_prime) != n * L * 64
             or bufs.nbytes(dj) != n * L * 128 or bufs.nbytes(dj_prime) != n * L * 128 or bufs.nbytes(held) != n * L or bufs.nbytes(d_key) not in (128, n * 128)):
         raise ValueError("need held [n, L], d_key [128] or [n, 128], dj and dj_prime [n, L, 128], c_tilde [n, 384], c [n, 64], cy and cy_prime [n, L, 64] with n = %d, L = %d" % (n, L))
+    return held, n, one_key
 
+
+def _decrypt_weighted(engine, n, L, one_key, w, ok, d_key, dj, dj_prime, c_tilde, c, cy, cy_prime):
+    """decrypt_batch_keys behind the weights w [n, L, 32] and ok [n]: the used columns, the folding, one multi_pair, gt_mul"""
     def put(a):
         return bufs.put(a, c)
 
     def host(a):
         return a.cpu().numpy() if bufs.is_torch(a) else np.asarray(a)
-    if not n:
-        return bufs.zeros((0, 384), c), bufs.zeros((0,), c)
-    with _share_tree(engine, nodes, L) as tree:
-        w, ok = tree.weights(bufs.flat(bufs.view(held, n * L)))                      # [n, L, 32] canonical, [n]
     w = bufs.view(w, n * L, 32)
     items = _plan.Good(host(ok).reshape(n), c)
     good, ng = items.index, items.count
@@ -321,3 +331,140 @@ def decrypt_batch_keys(engine, tree_or_plan, held, d_key, dj, dj_prime, c_tilde,
     X = engine.multi_pair(bufs.flat(P), bufs.flat(Q), _plan.segments(ng, 2 * U + 1))
     msgs = engine.gt_mul(bufs.flat(items.rows(bufs.view(c_tilde, n, 384))), bufs.flat(X))
     return items.scatter(msgs), bufs.view(ok, n)
+
+
+# ------------------------------------------------------------------------------------------------ a policy per ciphertext
+# n items over T distinct policies: item i names its policy in policy_of[i], and engine.ShareForest walks every item's own tree in one
+# launch (shares on the way in, weights on the way out).  Per-item arrays are padded to the forest's maxima: Lmax leaf columns, Cmax
+# coefficient columns.  A padded column holds the all-zero encoding — a zero share, the point at infinity — and costs no group operation
+# that Pair or the sums would not skip.
+def forest_plan(trees):
+    """(plans, attributes, index) of T Leaf / Threshold trees: plans[t] = share_plan(tree t); attributes: the distinct attributes over all
+    trees in the order they are first met; index [T, Lmax] int64: the position in `attributes` of the attribute of leaf y of tree t, and
+    _plan.NO_ATTRIBUTE in the columns tree t does not have."""
+    plans = [share_plan(t) for t in trees]
+    if not plans:
+        raise ValueError("a forest needs at least one tree")
+    attributes, where = [], {}
+    for _, attrs in plans:
+        for a in attrs:
+            if a not in where:
+                where[a] = len(attributes)
+                attributes.append(a)
+    index = np.full((len(plans), max(len(attrs) for _, attrs in plans)), _plan.NO_ATTRIBUTE, dtype=np.int64)
+    for t, (_, attrs) in enumerate(plans):
+        index[t, :len(attrs)] = [where[a] for a in attrs]
+    return plans, attributes, index
+
+
+def _forest(trees_or_plan):
+    """(plans, attributes, index, Cmax) of a list of trees or of forest_plan's result"""
+    is_plan = isinstance(trees_or_plan, tuple) and len(trees_or_plan) == 3 and isinstance(trees_or_plan[2], np.ndarray)
+    plans, attributes, index = trees_or_plan if is_plan else forest_plan(trees_or_plan)
+    return plans, attributes, index, max(sum(int(t) - 1 for _, t in nodes if int(t)) for nodes, _ in plans)
+
+
+def _policy_ids(policy_of, T, like):
+    """policy_of as ShareForest takes tree ids, of the kind of `like`: host values (checked against T here) as a uint32 array or, beside
+    tensors, the same bits as an int32 tensor; an int32 tensor is used as it is (an id of T or more gives a zero row and ok = 0 there)"""
+    if bufs.is_torch(policy_of):
+        return policy_of
+    ids = np.asarray(policy_of, dtype=np.int64).reshape(-1)
+    if ids.size and (ids.min() < 0 or ids.max() >= T):
+        raise ValueError("policy_of names a policy outside 0 .. %d" % (T - 1))
+    ids = ids.astype(np.uint32)
+    return bufs.put(ids.view(np.int32), like) if bufs.is_torch(like) else ids
+
+
+def _share_forest(engine, plans, Lmax):
+    """engine.ShareForest over the plans' node lists, closed on the way out"""
+    return _plan.handle(None, lambda: engine.ShareForest([nodes for nodes, _ in plans]), "leaves", Lmax, "the plans name %(want)d attributes at most for %(got)d leaves")
+
+
+def encrypt_batch_policies(engine, trees_or_plan, policy_of, h, e_alpha, h1, messages, s, coeffs, tables=False):
+    """n ciphertexts, ciphertext i under policy policy_of[i].  trees_or_plan: a list of T Leaf / Threshold trees or forest_plan(trees);
+    policy_of: n policy numbers below T (a list, an integer array, or beside CUDA tensors an int32 tensor); h, e_alpha, messages, s as
+    encrypt_batch takes them; h1: {attribute: 64-byte G1 point} for every attribute of every policy; coeffs: [n, Cmax] scalars — every
+    item carries Cmax columns and uses its first C_t, gate by gate as encrypt_batch reads them; the rest may hold anything (None or empty
+    when Cmax == 0).  Returns (c_tilde [n, 384], c [n, 64], cy [n, Lmax, 64], cy_prime [n, Lmax, 64]): the first L_t columns of item i
+    are exactly encrypt_batch's under policy t on the same s and coefficients, and every padded column is the all-zero encoding, the
+    point at infinity — what decrypt_batch_policies takes.
+
+    Engine calls: ShareForest.share (one launch for all policies), gt_exp and gt_mul, g1_scalar_mul (C), g1_scalar_mul_base (Cy), and for
+    Cy' the variable-base kernel on the H1 points gathered by policy with an all-zero row in the padding, or with tables=True (opt-in; the
+    same bytes) FixedBase.indexed with terms = 1 over ONE table of the distinct H1 points, its index rows gathered by policy with
+    GPBC_INDEX_NONE in the padding."""
+    plans, attributes, index, Cmax = _forest(trees_or_plan)
+    T, Lmax = index.shape
+    n = bufs.nbytes(messages) // 384
+    if bufs.nbytes(messages) != n * 384:
+        raise ValueError("messages must hold whole GT elements")
+    s = _plan.scalars(s, messages)
+    coeffs = None if coeffs is None else _plan.scalars(coeffs, messages)
+    ids = _policy_ids(policy_of, T, messages)
+    bufs.device_of(messages, s, coeffs, ids)                                         # all of one kind, on one device
+    if bufs.nbytes(s) != n * 32 or bufs.nbytes(ids) != n:
+        raise ValueError("s and policy_of must hold n = %d entries" % n)
+    if Cmax and (coeffs is None or bufs.nbytes(coeffs) != n * Cmax * 32):
+        raise ValueError("coeffs must hold n x Cmax = %d x %d scalars" % (n, Cmax))
+    with _share_forest(engine, plans, Lmax) as forest:
+        shares, _ = forest.share(ids, bufs.flat(s), bufs.flat(coeffs) if Cmax else None)                     # [n, Lmax, 32], zero in the padding
+    shares = bufs.flat(shares)
+    c_tilde = _plan.blind(engine, _plan.public(e_alpha, 1, 384, messages, "e_alpha"), s, messages, n)
+    c = engine.g1_scalar_mul(bufs.flat(_plan.public(h, 1, 64, messages, "h")), bufs.flat(s))
+    cy = engine.g1_scalar_mul_base(shares)
+    hy = np.stack([np.asarray(h1[a], dtype=np.uint8).reshape(64) for a in attributes])
+    A = len(attributes)
+    if tables and n:
+        rows = bufs.take(_plan.index_rows(index, messages), ids)                     # [n, Lmax] of the table's kind
+        with _plan.handle(None, lambda: engine.FixedBase(bufs.put(hy, messages), g2=False), "nbase", A, "the table holds %(got)d bases for %(want)d attributes") as table:
+            cy_prime, _ = table.indexed(bufs.flat(rows).reshape(n * Lmax, 1), shares, terms=1)
+    else:
+        padded = bufs.put(np.concatenate([hy, np.zeros((1, 64), dtype=np.uint8)]), messages)                 # row A: the point at infinity
+        rows = bufs.take(bufs.put(np.where(index < 0, A, index), messages), ids)
+        cy_prime = engine.g1_scalar_mul(bufs.flat(bufs.take(padded, bufs.flat(rows))), shares)
+    return bufs.view(c_tilde, n, 384), bufs.view(c, n, 64), bufs.view(cy, n, Lmax, 64), bufs.view(cy_prime, n, Lmax, 64)
+
+
+def encrypt_batch_policies_seeded(engine, trees_or_plan, policy_of, h, e_alpha, h1, messages, rng, tables=False):
+    """encrypt_batch_policies with its randomness drawn on the device: rng is an rng.Randomness over the engine, everything else as there,
+    and the return value is exactly encrypt_batch_policies' on the scalars drawn.  The draws, in this order (the order is part of the
+    interface: it is what makes the ciphertexts reproducible from the seed): s [n], then coeffs [n, Cmax] with Cmax the largest
+    coefficient count of any policy — EVERY item draws Cmax columns, whatever its policy, and uses its first C_t.  Two stream ids, one
+    when Cmax == 0 (a draw of no columns takes none), none when n == 0.  The seed is key material."""
+    plan = _forest(trees_or_plan)
+    n = bufs.nbytes(messages) // 384
+    s = rng.scalars(messages, n)
+    coeffs = rng.scalars(messages, n, plan[3]) if plan[3] else None
+    return encrypt_batch_policies(engine, plan[:3], policy_of, h, e_alpha, h1, messages, s, coeffs, tables=tables)
+
+
+def leaf_mask_policies(plan, policy_of, attribute_sets):
+    """[n, Lmax] uint8: 1 where set i holds the attribute of leaf y of policy policy_of[i], 0 in the columns that policy does not have —
+    the `held` of decrypt_batch_policies and of engine.ShareForest.weights.  plan: forest_plan(trees) or the list of trees."""
+    plans, _, index, _ = _forest(plan)
+    out = np.zeros((len(attribute_sets), index.shape[1]), dtype=np.uint8)
+    for i, (t, held) in enumerate(zip(policy_of, attribute_sets)):
+        held = held if isinstance(held, (set, frozenset)) else set(held)
+        attrs = plans[int(t)][1]
+        out[i, :len(attrs)] = [a in held for a in attrs]
+    return out
+
+
+def decrypt_batch_policies(engine, trees_or_plan, policy_of, held, d_key, dj, dj_prime, c_tilde, c, cy, cy_prime):
+    """decrypt_batch_keys with a policy per item: item i is under policy policy_of[i], and every [n, L, ...] argument of decrypt_batch_keys
+    is [n, Lmax, ...] here, an item's first L_t columns in its policy's leaf order — held from leaf_mask_policies, the ciphertexts from
+    encrypt_batch_policies; what lies in the other columns is never used.  Returns (messages [n, 384], ok [n]): ok = 0 and an all-zero
+    row where the item's attributes do not satisfy its policy (or, for ids given as a tensor, the id names no policy).  The weights come
+    from ShareForest.weights, one launch for all policies; everything behind them is decrypt_batch_keys'."""
+    plans, _, index, _ = _forest(trees_or_plan)
+    T, Lmax = index.shape
+    ids = _policy_ids(policy_of, T, c)
+    held, n, one_key = _keys_args(held, Lmax, d_key, dj, dj_prime, c_tilde, c, cy, cy_prime, ids)
+    if bufs.nbytes(ids) != n:
+        raise ValueError("policy_of must hold n = %d entries" % n)
+    if not n:
+        return bufs.zeros((0, 384), c), bufs.zeros((0,), c)
+    with _share_forest(engine, plans, Lmax) as forest:
+        w, ok = forest.weights(ids, bufs.flat(bufs.view(held, n * Lmax)))            # [n, Lmax, 32] canonical with zero padding, [n]
+    return _decrypt_weighted(engine, n, Lmax, one_key, w, ok, d_key, dj, dj_prime, c_tilde, c, cy, cy_prime)

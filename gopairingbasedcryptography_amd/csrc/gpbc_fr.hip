@@ -5,12 +5,14 @@
 // polynomial evaluation and the shares of a threshold tree (include/gpbc_bn254_share.h), and LSSS share generation (csrc/lsss29.hip.hpp,
 // include/gpbc_bn254_indexed.h), and the reconstruction weights of a threshold tree (csrc/recon29.hip.hpp, include/gpbc_bn254_recon.h),
 // and the common attributes of a list and a set (csrc/select29.hip.hpp, include/gpbc_bn254_select.h),
-// and LSSS matrices and 0 / 1 weights from boolean formulas (csrc/formula29.hip.hpp, include/gpbc_bn254_formula.h).
+// and LSSS matrices and 0 / 1 weights from boolean formulas (csrc/formula29.hip.hpp, include/gpbc_bn254_formula.h),
+// and sharing and weights over a forest of threshold trees, a tree per item (csrc/forest29.hip.hpp, include/gpbc_bn254_forest.h).
 // gfx950 only.
 #include "gpbc_common.hpp"
 #include "fr29.hip.hpp"
 #include "share29.hip.hpp"
 #include "recon29.hip.hpp"
+#include "forest29.hip.hpp"
 #include "lsss29.hip.hpp"
 #include "select29.hip.hpp"
 #include "formula29.hip.hpp"
@@ -19,6 +21,7 @@
 #include "../../include/gpbc_bn254_recon.h"
 #include "../../include/gpbc_bn254_select.h"
 #include "../../include/gpbc_bn254_formula.h"
+#include "../../include/gpbc_bn254_forest.h"
 
 // ------------------------------------------------------------------------------------------------ elementwise
 // one element per lane (no __restrict__: out may be a, or b)
@@ -280,6 +283,55 @@ template <int CAP> __device__ __forceinline__ void fr_tree_weights_kernel(const 
                         const uint8_t *__restrict__ held, size_t k, ReconGeom gm, uint8_t *__restrict__ w_out, uint8_t *__restrict__ ok_out
 GPBC_KERNEL_G1 k_fr_tree_weights(GPBC_RECON_ARGS) { fr_tree_weights_kernel<FR_RECON_SMALL>(units, level_off, gates, gate_off, held, k, gm, w_out, ok_out); }
 __global__ void __launch_bounds__(BLOCK) k_fr_tree_weights_large(GPBC_RECON_ARGS) { fr_tree_weights_kernel<FR_RECON_LARGE>(units, level_off, gates, gate_off, held, k, gm, w_out, ok_out); }
+
+// ------------------------------------------------------------------------------------------------ threshold-tree forests
+// A tree per item: forest29.hip.hpp has the block, the geometry, the item mapping and the lane code; here are the LDS blocks (those of the
+// two single-tree kernels above, at the same instance sizes) and the barriers.  Every lane runs every level loop to the forest's depth
+// and arrives at every barrier, whatever the depth of its own item's tree and whether its item exists at all.
+template <int CAP> __device__ __forceinline__ void fr_share_forest_kernel(ForestDev fd, const uint32_t *__restrict__ tree_of, const uint8_t *__restrict__ secrets,
+                                                                           const uint8_t *__restrict__ coeffs, size_t k, ForestGeom gm, uint8_t *__restrict__ out,
+                                                                           uint8_t *__restrict__ ok_out) {
+    __shared__ int32_t ss[CAP * NL + BLOCK];
+    const auto get = [&](uint32_t off) { return lds_get(ss + off); };
+    const auto put = [&](uint32_t off, const Fr &v) { lds_put(ss + off, v); };
+    const ForestItem it = fr_forest_item(gm, fd.trees, tree_of, blockIdx.x, threadIdx.x, k);
+    fr_forest_share_stage(gm, it, secrets, coeffs, put);
+    __syncthreads();
+    for (uint32_t lv = 1; lv <= gm.depth; lv++) {
+        fr_forest_share_level(gm, it, fd, lv, get, put, out);
+        __syncthreads();
+    }
+    fr_forest_share_finish(gm, it, secrets, out, ok_out);
+}
+#define GPBC_FOREST_SHARE_ARGS ForestDev fd, const uint32_t *__restrict__ tree_of, const uint8_t *__restrict__ secrets, const uint8_t *__restrict__ coeffs, size_t k, ForestGeom gm, \
+                               uint8_t *__restrict__ out, uint8_t *__restrict__ ok_out
+GPBC_KERNEL_G1 k_fr_share_forest(GPBC_FOREST_SHARE_ARGS) { fr_share_forest_kernel<FR_TREE_SMALL>(fd, tree_of, secrets, coeffs, k, gm, out, ok_out); }
+__global__ void __launch_bounds__(BLOCK) k_fr_share_forest_large(GPBC_FOREST_SHARE_ARGS) { fr_share_forest_kernel<FR_TREE_LARGE>(fd, tree_of, secrets, coeffs, k, gm, out, ok_out); }
+
+template <int CAP> __device__ __forceinline__ void fr_forest_weights_kernel(ForestDev fd, const uint32_t *__restrict__ tree_of, const uint8_t *__restrict__ held, size_t k, ForestGeom gm,
+                                                                             uint8_t *__restrict__ w_out, uint8_t *__restrict__ ok_out) {
+    __shared__ int32_t ss[CAP + BLOCK];
+    const auto get = [&](uint32_t off) { return lds_get(ss + off); };
+    const auto put = [&](uint32_t off, const Fr &v) { lds_put(ss + off, v); };
+    const auto getw = [&](uint32_t off) { return (uint32_t)ss[off]; };
+    const auto putw = [&](uint32_t off, uint32_t v) { ss[off] = (int32_t)v; };
+    const ForestItem it = fr_forest_item(gm, fd.trees, tree_of, blockIdx.x, threadIdx.x, k);
+    fr_forest_recon_stage(gm, it, fd, held, put, putw);
+    __syncthreads();
+    for (uint32_t lv = gm.depth; lv-- > 0;) {
+        fr_forest_recon_up(gm, it, fd, lv, getw, putw, ok_out);
+        __syncthreads();
+    }
+    for (uint32_t lv = 1; lv <= gm.depth; lv++) {
+        fr_forest_recon_down<FR_RECON_G>(gm, it, fd, lv, get, put, getw, putw, w_out);
+        __syncthreads();
+    }
+    fr_forest_recon_finish(gm, it, held, w_out, ok_out);
+}
+#define GPBC_FOREST_RECON_ARGS ForestDev fd, const uint32_t *__restrict__ tree_of, const uint8_t *__restrict__ held, size_t k, ForestGeom gm, uint8_t *__restrict__ w_out, \
+                               uint8_t *__restrict__ ok_out
+GPBC_KERNEL_G1 k_fr_forest_weights(GPBC_FOREST_RECON_ARGS) { fr_forest_weights_kernel<FR_RECON_SMALL>(fd, tree_of, held, k, gm, w_out, ok_out); }
+__global__ void __launch_bounds__(BLOCK) k_fr_forest_weights_large(GPBC_FOREST_RECON_ARGS) { fr_forest_weights_kernel<FR_RECON_LARGE>(fd, tree_of, held, k, gm, w_out, ok_out); }
 
 // ------------------------------------------------------------------------------------------------ LSSS share generation
 // out[j][x] = M_x . v_j: lsss29.hip.hpp has the arithmetic, the geometry, the staging and the lane mapping; here is the LDS block of the
@@ -707,6 +759,133 @@ int gpbc_fr_tree_weights(const gpbc_share_tree *t, const uint8_t *held, size_t k
     const size_t L = t->rgeom.L;
     return host_call(k, HostCall().input(held, L).output(w_out, L * GPBC_SCALAR_BYTES).output(ok_out, 1), HostRoute{CALL_KINDS, nullptr, 0, LANE_CALL_MAX_UNITS},
                      [=](const DevCols &dc, size_t m, hipStream_t st) { return gpbc_fr_tree_weights_dev(t, (const uint8_t *)dc.in[0], m, dc.out[0], (uint8_t *)dc.out[1], st); });
+}
+
+// ------------------------------------------------------------------------------------------------ threshold-tree forest entries (include/gpbc_bn254_forest.h)
+int gpbc_forest_version(void) { return 1; }
+// the block of forest29.hip.hpp in one device allocation, and what the accessors answer from the host
+struct gpbc_share_forest {
+    int device;
+    ForestGeom sgeom, rgeom;
+    ForestDev dev;
+    void *block;
+    std::vector<uint32_t> tree_L, tree_C;
+};
+int gpbc_share_forest_create(const gpbc_share_node *nodes, const uint32_t *node_off, size_t n_trees, gpbc_share_forest **out) {
+    if (!out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    *out = nullptr;
+    ForestPlan plan;
+    size_t bad = 0;
+    const char *why = fr_forest_plan(reinterpret_cast<const ShareNode *>(nodes), node_off, n_trees, plan, &bad);
+    if (why && bad < n_trees) return fail(GPBC_ERR_INVALID_ARG, "malformed tree %zu: %s", bad, why);
+    if (why) return fail(GPBC_ERR_INVALID_ARG, "malformed forest: %s", why);
+    if (!fr_forest_plan_ok(plan)) return fail(GPBC_ERR_INTERNAL, "the plan of a share forest points outside its tables");
+    // one block: headers, sharing units, reconstruction units, level offsets, gate offsets, gates, each table 16-byte aligned
+    const size_t bytes[6] = {plan.trees.size() * sizeof(ForestTree), plan.sunits.size() * sizeof(ShareUnit), plan.runits.size() * sizeof(ReconUnit),
+                             plan.level_off.size() * sizeof(uint32_t), plan.gate_off.size() * sizeof(uint32_t), plan.gates.size() * sizeof(ReconGate)};
+    const void *src[6] = {plan.trees.data(), plan.sunits.data(), plan.runits.data(), plan.level_off.data(), plan.gate_off.data(), plan.gates.data()};
+    size_t at[7] = {0};
+    for (int i = 0; i < 6; i++) at[i + 1] = (at[i] + bytes[i] + 15) & ~(size_t)15;
+    std::vector<uint8_t> host(at[6] + 16, 0);
+    for (int i = 0; i < 6; i++)
+        if (bytes[i]) memcpy(host.data() + at[i], src[i], bytes[i]);
+    TRY(bind_device());
+    gpbc_share_forest *h = new gpbc_share_forest{current_device(), fr_forest_share_geometry(plan), fr_forest_recon_geometry(plan), ForestDev{}, nullptr, {}, {}};
+    hipError_t e = hipMalloc(&h->block, host.size());
+    if (e == hipSuccess) e = hipMemcpy(h->block, host.data(), host.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (h->block) (void)hipFree(h->block);
+        delete h;
+        return fail(GPBC_ERR_HIP, "uploading a share forest failed: %s", hipGetErrorString(e));
+    }
+    const uint8_t *b = (const uint8_t *)h->block;
+    h->dev = ForestDev{(const ForestTree *)(b + at[0]), (const ShareUnit *)(b + at[1]), (const ReconUnit *)(b + at[2]), (const uint32_t *)(b + at[3]), (const uint32_t *)(b + at[4]),
+                       (const ReconGate *)(b + at[5])};
+    for (const ForestTree &t : plan.trees) { h->tree_L.push_back(t.L); h->tree_C.push_back(t.C); }
+    *out = h;
+    return GPBC_OK;
+}
+int gpbc_share_forest_destroy(gpbc_share_forest *f) {
+    if (!f) return GPBC_OK;
+    (void)hipSetDevice(f->device);
+    (void)hipDeviceSynchronize();
+    (void)hipFree(f->block);
+    delete f;
+    return GPBC_OK;
+}
+size_t gpbc_share_forest_trees(const gpbc_share_forest *f) { return f ? f->sgeom.T : 0; }
+size_t gpbc_share_forest_leaves(const gpbc_share_forest *f) { return f ? f->sgeom.Lmax : 0; }
+size_t gpbc_share_forest_coeffs(const gpbc_share_forest *f) { return f ? f->sgeom.Cmax : 0; }
+size_t gpbc_share_forest_tree_leaves(const gpbc_share_forest *f, size_t t) { return f && t < f->tree_L.size() ? f->tree_L[t] : 0; }
+size_t gpbc_share_forest_tree_coeffs(const gpbc_share_forest *f, size_t t) { return f && t < f->tree_C.size() ? f->tree_C[t] : 0; }
+// the rules both forms of both entries share: p[0 .. n_in) are inputs, the rest outputs; a null output that may be absent has nb = 0
+static int forest_args(const gpbc_share_forest *f, size_t k, const void *const *p, const size_t *nb, int n_in, int n) {
+    if (!f) return fail(GPBC_ERR_INVALID_ARG, "null forest handle");
+    if (k > (size_t)0x7fffffff / 4) return fail(GPBC_ERR_INVALID_ARG, "too many items for one call (%zu)", k);
+    if (!k) return GPBC_OK;
+    for (int i = 0; i < n; i++)
+        if (!p[i] && nb[i]) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    for (int i = n_in; i < n; i++)
+        for (int j = 0; j < i; j++)
+            if (p[i] && p[j] && overlap(p[i], nb[i], p[j], nb[j])) return fail(GPBC_ERR_INVALID_ARG, "an output overlaps an input or another output");
+    return GPBC_OK;
+}
+static int forest_device(const gpbc_share_forest *f) {
+    TRY(bind_device());
+    if (current_device() != f->device) return fail(GPBC_ERR_INVALID_ARG, "forest was created on device %d", f->device);
+    return GPBC_OK;
+}
+static int share_forest_args(const gpbc_share_forest *f, const void *tree_of, const void *secrets, const void *coeffs, size_t k, const void *out, const void *ok_out) {
+    const size_t S = GPBC_SCALAR_BYTES, L = f ? f->sgeom.Lmax : 0, C = f ? f->sgeom.Cmax : 0;
+    const void *p[5] = {tree_of, secrets, C ? coeffs : nullptr, out, ok_out};
+    const size_t nb[5] = {k * sizeof(uint32_t), k * S, k * C * S, k * L * S, ok_out ? k : 0};
+    return forest_args(f, k, p, nb, 3, 5);
+}
+int gpbc_fr_share_forest_dev(const gpbc_share_forest *f, const uint32_t *d_tree_of, const void *d_secrets, const void *d_coeffs, size_t k, void *d_out, uint8_t *d_ok_out, void *stream) {
+    TRY(share_forest_args(f, d_tree_of, d_secrets, d_coeffs, k, d_out, d_ok_out));
+    if (!k) return GPBC_OK;
+    TRY(forest_device(f));
+    const unsigned grid = (unsigned)fr_forest_grid(f->sgeom, k);
+    if (f->sgeom.large)
+        return GPBC_LAUNCH(k_fr_share_forest_large, grid, BLOCK, (hipStream_t)stream, f->dev, d_tree_of, (const uint8_t *)d_secrets, (const uint8_t *)d_coeffs, k, f->sgeom, (uint8_t *)d_out, d_ok_out);
+    return GPBC_LAUNCH(k_fr_share_forest, grid, BLOCK, (hipStream_t)stream, f->dev, d_tree_of, (const uint8_t *)d_secrets, (const uint8_t *)d_coeffs, k, f->sgeom, (uint8_t *)d_out, d_ok_out);
+}
+// Host pointers: as gpbc_fr_share_tree, the shared staging path on the forest's device only.
+int gpbc_fr_share_forest(const gpbc_share_forest *f, const uint32_t *tree_of, const void *secrets, const void *coeffs, size_t k, void *out, uint8_t *ok_out) {
+    TRY(share_forest_args(f, tree_of, secrets, coeffs, k, out, ok_out));
+    if (!k) return GPBC_OK;
+    TRY(forest_device(f));
+    const size_t C = f->sgeom.Cmax;
+    HostCall c = HostCall().input(tree_of, sizeof(uint32_t)).input(secrets, GPBC_SCALAR_BYTES);
+    if (C) c.input(coeffs, C * GPBC_SCALAR_BYTES);
+    return host_call(k, c.output(out, f->sgeom.Lmax * GPBC_SCALAR_BYTES).output(ok_out, 1), HostRoute{CALL_KINDS, nullptr, 0, LANE_CALL_MAX_UNITS},
+                     [=](const DevCols &dc, size_t m, hipStream_t st) {
+                         return gpbc_fr_share_forest_dev(f, (const uint32_t *)dc.in[0], dc.in[1], C ? dc.in[2] : nullptr, m, dc.out[0], dc.out[1], st);
+                     });
+}
+static int forest_weights_args(const gpbc_share_forest *f, const void *tree_of, const void *held, size_t k, const void *w_out, const void *ok_out) {
+    const size_t L = f ? f->rgeom.Lmax : 0;
+    const void *p[4] = {tree_of, held, w_out, ok_out};
+    const size_t nb[4] = {k * sizeof(uint32_t), k * L, k * L * GPBC_SCALAR_BYTES, k};
+    return forest_args(f, k, p, nb, 2, 4);
+}
+int gpbc_fr_forest_weights_dev(const gpbc_share_forest *f, const uint32_t *d_tree_of, const uint8_t *d_held, size_t k, void *d_w_out, uint8_t *d_ok_out, void *stream) {
+    TRY(forest_weights_args(f, d_tree_of, d_held, k, d_w_out, d_ok_out));
+    if (!k) return GPBC_OK;
+    TRY(forest_device(f));
+    const unsigned grid = (unsigned)fr_forest_grid(f->rgeom, k);
+    if (f->rgeom.large) return GPBC_LAUNCH(k_fr_forest_weights_large, grid, BLOCK, (hipStream_t)stream, f->dev, d_tree_of, d_held, k, f->rgeom, (uint8_t *)d_w_out, d_ok_out);
+    return GPBC_LAUNCH(k_fr_forest_weights, grid, BLOCK, (hipStream_t)stream, f->dev, d_tree_of, d_held, k, f->rgeom, (uint8_t *)d_w_out, d_ok_out);
+}
+int gpbc_fr_forest_weights(const gpbc_share_forest *f, const uint32_t *tree_of, const uint8_t *held, size_t k, void *w_out, uint8_t *ok_out) {
+    TRY(forest_weights_args(f, tree_of, held, k, w_out, ok_out));
+    if (!k) return GPBC_OK;
+    TRY(forest_device(f));
+    const size_t L = f->rgeom.Lmax;
+    return host_call(k, HostCall().input(tree_of, sizeof(uint32_t)).input(held, L).output(w_out, L * GPBC_SCALAR_BYTES).output(ok_out, 1), HostRoute{CALL_KINDS, nullptr, 0, LANE_CALL_MAX_UNITS},
+                     [=](const DevCols &dc, size_t m, hipStream_t st) {
+                         return gpbc_fr_forest_weights_dev(f, (const uint32_t *)dc.in[0], (const uint8_t *)dc.in[1], m, dc.out[0], (uint8_t *)dc.out[1], st);
+                     });
 }
 
 // ------------------------------------------------------------------------------------------------ common attribute entries (include/gpbc_bn254_select.h)

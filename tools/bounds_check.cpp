@@ -1317,3 +1317,92 @@ void hc_stats(double *out) {
     out[0] = s.max_col; out[1] = s.max_limb; out[2] = s.max_vb; out[3] = (double)s.muls; out[4] = (double)s.norms; out[5] = (double)s.muls2; out[6] = (double)s.reduces;
 }
 }
+
+// ------------------------------------------------------------------------------------------------ threshold-tree forests
+#include "../gopairingbasedcryptography_amd/csrc/forest29.hip.hpp"
+extern "C" {
+// the plan of a forest alone: sizes_out [T, Lmax, Gmax, Cmax, Umax, depth_max, narrowest level, widest level, Emax, Pmax]; -1, the tree the
+// reason belongs to in *bad_tree (T: the forest itself) and the reason in why (up to 96 bytes) when it is refused
+int hc_fr_forest_plan(const uint32_t *nodes, const uint32_t *node_off, size_t n_trees, uint32_t *sizes_out, size_t *bad_tree, char *why) {
+    ForestPlan f;
+    size_t bad = 0;
+    const char *w = fr_forest_plan(reinterpret_cast<const ShareNode *>(nodes), node_off, n_trees, f, &bad);
+    if (bad_tree) *bad_tree = bad;
+    if (w) { if (why) snprintf(why, 96, "%s", w); return -1; }
+    if (!fr_forest_plan_ok(f)) return -2;
+    if (sizes_out) {
+        const uint32_t v[10] = {f.T, f.Lmax, f.Gmax, f.Cmax, f.Umax, f.depth_max, f.wmin, f.wmax, f.Emax, f.Pmax};
+        memcpy(sizes_out, v, sizeof(v));
+    }
+    return 0;
+}
+// k_fr_share_forest as it is launched: the plan, the block check, the geometry, the item mapping, the staging, every level to the forest's
+// depth and the finish of forest29.hip.hpp, workgroup by workgroup, a barrier = the end of a loop over the lanes.
+// geom_out: [Lmax, Cmax, depth, ipb, lpi, pitch, large, workgroups].  -1: a refused forest or argument; -2: a refusal of the LDS stand-in
+// or a block that fails its check.
+int hc_fr_share_forest(const uint32_t *nodes, const uint32_t *node_off, size_t n_trees, const uint32_t *tree_of, const uint8_t *secrets, const uint8_t *coeffs, size_t k, uint8_t *out,
+                       uint8_t *ok_out, uint32_t *geom_out) {
+    ForestPlan f;
+    size_t bad = 0;
+    if (fr_forest_plan(reinterpret_cast<const ShareNode *>(nodes), node_off, n_trees, f, &bad) || !k || !tree_of || !secrets || !out || (f.Cmax && !coeffs)) return -1;
+    if (!fr_forest_plan_ok(f)) return -2;
+    const ForestGeom g = fr_forest_share_geometry(f);
+    const size_t cap = (size_t)(g.large ? FR_TREE_LARGE : FR_TREE_SMALL) * NL + FR_SHARE_WAVE;
+    if (g.ipb * g.lpi != (uint32_t)FR_SHARE_WAVE || (size_t)g.ipb * g.pitch > cap) return -2;
+    const ForestDev fd{f.trees.data(), f.sunits.data(), f.runits.data(), f.level_off.data(), f.gate_off.data(), f.gates.data()};
+    CheckedLds lds(cap);
+    const size_t grid = fr_forest_grid(g, k);
+    const auto get = [&](uint32_t off) { return lds.get(off); };
+    const auto put = [&](uint32_t off, const Fr &v) { lds.put(off, v); };
+    std::vector<ForestItem> its(FR_SHARE_WAVE);
+    for (size_t block = 0; block < grid; block++) {
+        lds.reset();
+        for (uint32_t lane = 0; lane < FR_SHARE_WAVE; lane++) {
+            its[lane] = fr_forest_item(g, fd.trees, tree_of, (uint32_t)block, lane, k);
+            fr_forest_share_stage(g, its[lane], secrets, coeffs, put);
+        }
+        for (uint32_t lv = 1; lv <= g.depth && !lds.bad; lv++)
+            for (uint32_t lane = 0; lane < FR_SHARE_WAVE; lane++) fr_forest_share_level(g, its[lane], fd, lv, get, put, out);
+        for (uint32_t lane = 0; lane < FR_SHARE_WAVE; lane++) fr_forest_share_finish(g, its[lane], secrets, out, ok_out);
+        if (lds.bad) return -2;
+    }
+    if (geom_out) { const uint32_t v[8] = {g.Lmax, g.Cmax, g.depth, g.ipb, g.lpi, g.pitch, g.large, (uint32_t)grid}; memcpy(geom_out, v, sizeof(v)); }
+    stats_flush();
+    return 0;
+}
+// k_fr_forest_weights as it is launched, in the same way: staging, UP and DOWN to the forest's depth, the finish.  geom_out as above.
+int hc_fr_forest_weights(const uint32_t *nodes, const uint32_t *node_off, size_t n_trees, const uint32_t *tree_of, const uint8_t *held, size_t k, uint8_t *w_out, uint8_t *ok_out,
+                         uint32_t *geom_out) {
+    ForestPlan f;
+    size_t bad = 0;
+    if (fr_forest_plan(reinterpret_cast<const ShareNode *>(nodes), node_off, n_trees, f, &bad) || !k || !tree_of || !held || !w_out || !ok_out) return -1;
+    if (!fr_forest_plan_ok(f)) return -2;
+    const ForestGeom g = fr_forest_recon_geometry(f);
+    const size_t cap = (size_t)(g.large ? FR_RECON_LARGE : FR_RECON_SMALL);
+    if (g.ipb * g.lpi != (uint32_t)FR_RECON_WAVE || (size_t)g.ipb * g.pitch > cap) return -2;
+    const ForestDev fd{f.trees.data(), f.sunits.data(), f.runits.data(), f.level_off.data(), f.gate_off.data(), f.gates.data()};
+    CheckedMixed lds(cap + FR_RECON_WAVE);
+    const size_t grid = fr_forest_grid(g, k);
+    const auto get = [&](uint32_t off) { return lds.get(off); };
+    const auto put = [&](uint32_t off, const Fr &v) { lds.put(off, v); };
+    const auto getw = [&](uint32_t off) { return lds.getw(off); };
+    const auto putw = [&](uint32_t off, uint32_t v) { lds.putw(off, v); };
+    std::vector<ForestItem> its(FR_RECON_WAVE);
+    for (size_t block = 0; block < grid; block++) {
+        lds.reset();
+        for (uint32_t lane = 0; lane < FR_RECON_WAVE; lane++) {
+            its[lane] = fr_forest_item(g, fd.trees, tree_of, (uint32_t)block, lane, k);
+            fr_forest_recon_stage(g, its[lane], fd, held, put, putw);
+        }
+        for (uint32_t lv = g.depth; lv-- > 0 && !lds.bad;)
+            for (uint32_t lane = 0; lane < FR_RECON_WAVE; lane++) fr_forest_recon_up(g, its[lane], fd, lv, getw, putw, ok_out);
+        for (uint32_t lv = 1; lv <= g.depth && !lds.bad; lv++)
+            for (uint32_t lane = 0; lane < FR_RECON_WAVE; lane++) fr_forest_recon_down<FR_RECON_G>(g, its[lane], fd, lv, get, put, getw, putw, w_out);
+        for (uint32_t lane = 0; lane < FR_RECON_WAVE; lane++) fr_forest_recon_finish(g, its[lane], held, w_out, ok_out);
+        if (lds.bad) return -2;
+    }
+    if (geom_out) { const uint32_t v[8] = {g.Lmax, g.Cmax, g.depth, g.ipb, g.lpi, g.pitch, g.large, (uint32_t)grid}; memcpy(geom_out, v, sizeof(v)); }
+    stats_flush();
+    return 0;
+}
+}
