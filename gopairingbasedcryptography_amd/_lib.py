@@ -118,6 +118,11 @@ FOREST_SIGNATURES = {
     "gpbc_share_forest_leaves": "z:p", "gpbc_share_forest_coeffs": "z:p", "gpbc_share_forest_tree_leaves": "z:pz", "gpbc_share_forest_tree_coeffs": "z:pz",
     "gpbc_fr_share_forest": "i:ppppzpp", "gpbc_fr_share_forest_dev": "i:ppppzppp", "gpbc_fr_forest_weights": "i:pppzpp", "gpbc_fr_forest_weights_dev": "i:pppzppp",
 }
+# ... and for include/gpbc_bn254_mask.h, the XOR mask from GT bytes (tests/test_gt_xor_mask.py holds this table against that header).
+# The twelve tables are disjoint.
+MASK_SIGNATURES = {
+    "gpbc_mask_version": "i:", "gpbc_gt_xor_mask": "i:pppzzpp", "gpbc_gt_xor_mask_dev": "i:pppzzzppp",
+}
 # every pointer is a c_void_p: it takes ints, None, c_void_p, ctypes arrays, byref() and ndarray.ctypes.data_as() alike
 _CTYPES = {"p": ctypes.c_void_p, "z": ctypes.c_size_t, "i": ctypes.c_int, "l": ctypes.c_long, "s": ctypes.c_char_p}
 
@@ -143,7 +148,7 @@ def load():
         except ImportError:
             pass
         lib = ctypes.CDLL(LIB_PATH)
-        for name, sig in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(SUBSET_SIGNATURES.items()) + list(HASH_SIGNATURES.items()) + list(SHARE_SIGNATURES.items()) + list(INDEXED_SIGNATURES.items()) + list(RECON_SIGNATURES.items()) + list(SELECT_SIGNATURES.items()) + list(FORMULA_SIGNATURES.items()) + list(RANDOM_SIGNATURES.items()) + list(FOREST_SIGNATURES.items()):
+        for name, sig in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(SUBSET_SIGNATURES.items()) + list(HASH_SIGNATURES.items()) + list(SHARE_SIGNATURES.items()) + list(INDEXED_SIGNATURES.items()) + list(RECON_SIGNATURES.items()) + list(SELECT_SIGNATURES.items()) + list(FORMULA_SIGNATURES.items()) + list(RANDOM_SIGNATURES.items()) + list(FOREST_SIGNATURES.items()) + list(MASK_SIGNATURES.items()):
             ret, params = sig.split(":")
             fn = getattr(lib, name)
             fn.restype = _CTYPES[ret]

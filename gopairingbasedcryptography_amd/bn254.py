@@ -1495,6 +1495,55 @@ def hash_g1_gt_gt_to_fr(u, v, w, out=None):
     return _rowwise("hash_g1_gt_gt_to_fr", SCALAR_BYTES, (u, G1_BYTES, "u"), (v, GT_BYTES, "v"), (w, GT_BYTES, "w"), out=out)
 
 
+# --------------------------------------------------------------------------------------- the XOR mask from GT bytes
+def gt_xor_mask(gt, msgs, msg_off=None, out=None):
+    """(out, out_len): out_i = msg_i XOR GT.Bytes()(gt_i) cut to the shorter of the two — utils.Xor(message, hash.FromGT(gid)), the last
+    step of Boneh-Franklin Encrypt and Decrypt (ibe/bf01_ibe/bf01_ibe.go:170-176,202-208; include/gpbc_bn254_mask.h) — for n items in ONE
+    launch.  gt: [n, 384] GT elements.  The messages as sha256 takes them, plus a row form:
+        a list of bytes (host)                                         out is (flat uint8 array, uint64 offsets [n + 1])
+        a flat buffer plus msg_off (numpy uint64 / an int64 CUDA tensor)    out is a flat buffer of the message buffer's size
+        an [n, width] uint8 array or CUDA tensor, msg_off=None         out is [n, width]
+    out_len [n] = min(len_i, 384), the length of the slice the reference returns (uint32 on the host, the same bits as int32 on the
+    device); out[L_i:len_i] is zero.  The output is of the kind the inputs are.  `out` may be given — it has the layout of the message
+    buffer — and may be the message buffer itself: the call then runs in place.  Bytes of a given `out` that belong to no message are
+    left as they are; in a buffer made here they are undefined."""
+    if bufs.is_torch(gt) != bufs.is_torch(msgs):
+        raise ValueError("the GT elements and the messages must both be host data or both CUDA tensors")
+    if msg_off is None and not isinstance(msgs, (list, tuple)):
+        if not (isinstance(msgs, np.ndarray) or bufs.is_torch(msgs)) or msgs.ndim != 2:
+            raise ValueError("messages without msg_off are a list of bytes or an [n, width] uint8 array / tensor")
+        dev = bufs.device_of(gt, msgs, out)
+        n, width = (int(e) for e in msgs.shape)
+        data, off, shape = bufs.rows(msgs, 1, "messages")[0], None, (n, width)
+        nbytes = () if dev is None else (n * width,)
+    else:
+        dev, data, off, nbytes, n = _messages(msgs, msg_off)
+        bufs.device_of(gt, data, out)
+        # (_messages hands an empty host buffer on as one byte, so that it has an address; the output is of the true size)
+        size = bufs.nbytes(data) if dev is not None else int(off[-1]) if isinstance(msgs, (list, tuple)) else np.asarray(msgs).size
+        width, shape = 0, (size,)
+    gt, ng = bufs.rows(gt, GT_BYTES, "gt")
+    if ng != n:
+        raise ValueError("%d GT elements for %d messages" % (ng, n))
+    given = out
+    out = bufs.output(out, shape, dev)
+    out_len = bufs.output(None, (n, 4), dev)
+    if given is not None and bufs.address(out) != bufs.address(data) and _overlaps(out, data):
+        raise ValueError("out overlaps the messages (only the message buffer itself runs in place)")
+    if given is not None and _overlaps(out, gt):
+        raise ValueError("out overlaps gt")
+    if n:
+        _call("gt_xor_mask", dev, gt, data, off, *nbytes, width, n, out, out_len)
+    if dev is None:
+        out_len = out_len.view(np.uint32).reshape(n)
+    else:
+        import torch
+        out_len = out_len.view(torch.int32).reshape(n)
+    if isinstance(msgs, (list, tuple)):
+        return (out, off), out_len
+    return out, out_len
+
+
 # --------------------------------------------------------------------------------------- randomness addressed by (seed, stream, index)
 RANDOM_SEED_BYTES = 32
 RANDOM_BLOCK_BYTES = 64

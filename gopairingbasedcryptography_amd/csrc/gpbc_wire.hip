@@ -1,10 +1,14 @@
 // libgpbc_bn254.so, one of the units listed in _build.py: gnark wire formats (csrc/wire29.hip.hpp) and hash to curve — hash_to_field
-// (csrc/xmd29.hip.hpp) and the group part (csrc/h2c29.hip.hpp) — with their C-ABI entries (include/gpbc_bn254.h).  gfx950 only.
+// (csrc/xmd29.hip.hpp) and the group part (csrc/h2c29.hip.hpp) — with their C-ABI entries (include/gpbc_bn254.h); and, as the unit
+// that has the GT coefficient order and fe_to_plain_words, the XOR mask from GT bytes (csrc/mask29.hip.hpp) with the entries of
+// include/gpbc_bn254_mask.h.  gfx950 only.
 #include "gpbc_common.hpp"
+#include "../../include/gpbc_bn254_mask.h"
 #include "curve29_oct.hip.hpp"
 #include "wire29.hip.hpp"
 #include "h2c29.hip.hpp"
 #include "xmd29.hip.hpp"
+#include "mask29.hip.hpp"
 
 // ---- wire formats (csrc/wire29.hip.hpp): one element per lane
 GPBC_KERNEL k_g1_encode(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, size_t n, int compressed) {
@@ -278,6 +282,20 @@ GPBC_KERNEL k_g2_hash_quad(const uint8_t *__restrict__ msgs, const uint64_t *__r
     if ((lane & 3) == 0) g2_store_aff(out + i * GPBC_G2_BYTES, r);
 }
 
+// ---- the XOR mask from GT bytes (csrc/mask29.hip.hpp): one lane per (item, 32-byte window).  Rows: wpi lanes per item, an item's lanes
+// side by side.  Offsets: twelve lanes per item, a WAVEFRONT per window of 64 items (mask_ragged_lane), so that the wavefronts of
+// windows no message of the 64 reaches leave after two loads.
+__global__ void __launch_bounds__(MASK_BLOCK) k_gt_xor_mask(const uint8_t *__restrict__ gt, const uint8_t *msgs, const uint64_t *off, size_t total, size_t width, size_t n,
+                                                            int wpi, uint8_t *out, uint32_t *out_len) {
+    const size_t lane = (size_t)blockIdx.x * MASK_BLOCK + threadIdx.x;
+    size_t i;
+    int w;
+    if (off) mask_ragged_lane(lane, i, w);
+    else { i = lane / (unsigned)wpi; w = (int)(lane - i * (unsigned)wpi); }
+    if (i >= n) return;
+    gt_xor_mask_lane(gt, msgs, off, total, width, i, w, out, out_len);
+}
+
 extern "C" {
 
 // ----------------------------------------------------------------------------------------------- wire formats
@@ -453,6 +471,63 @@ int gpbc_hash_to_g2_dev(const void *m, const uint64_t *off, size_t mb, size_t n,
 int gpbc_hash_to_field_dev(const void *m, const uint64_t *off, size_t mb, size_t n, const void *dst, size_t dl, int count, void *o, void *st) {
     if (count != 2 && count != 4) return fail(GPBC_ERR_INVALID_ARG, "count must be 2 or 4");
     return hash_dev(count, m, off, mb, n, dst, dl, o, st);
+}
+
+// ----------------------------------------------------------------------------------------------- the XOR mask from GT bytes
+int gpbc_mask_version(void) { return 1; }
+
+constexpr size_t MASK_MAX_N = (size_t)0x7fffffff * MASK_BLOCK / MASK_WINDOWS;      // the grid's x extent, twelve lanes per item
+static bool ranges_meet(const void *a, size_t na, const void *b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return na && nb && x < y + nb && y < x + na;
+}
+int gpbc_gt_xor_mask_dev(const void *d_gt, const void *d_msgs, const uint64_t *d_msg_off, size_t msgs_bytes, size_t width, size_t n, void *d_out,
+                         uint32_t *d_out_len, void *stream) {
+    if (!n) return GPBC_OK;
+    if (n > MASK_MAX_N) return fail(GPBC_ERR_INVALID_ARG, "too many items for one call (%zu)", n);
+    if (!d_msg_off && width && n > msgs_bytes / width) return fail(GPBC_ERR_INVALID_ARG, "n * width exceeds msgs_bytes (n = %zu, width = %zu, msgs_bytes = %zu)", n, width, msgs_bytes);
+    const size_t span = d_msg_off ? msgs_bytes : n * width;        // what the messages, and the output, can occupy
+    if (!d_gt || (span && (!d_msgs || !d_out))) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    if (ranges_meet(d_gt, n * GPBC_GT_BYTES, d_out, span)) return fail(GPBC_ERR_INVALID_ARG, "out overlaps gt");
+    TRY(bind_device());
+    const int wpi = mask_lanes_per_item(!d_msg_off, width);
+    const size_t lanes = d_msg_off ? (n + MASK_GROUP - 1) / MASK_GROUP * MASK_GROUP * MASK_WINDOWS : n * (size_t)wpi;
+    return GPBC_LAUNCH(k_gt_xor_mask, (unsigned)((lanes + MASK_BLOCK - 1) / MASK_BLOCK), MASK_BLOCK, (hipStream_t)stream, (const uint8_t *)d_gt,
+                       (const uint8_t *)d_msgs, d_msg_off, msgs_bytes, width, n, wpi, (uint8_t *)d_out, d_out_len);
+}
+// Host pointers: the shared staging path (host_call) through device blocks on the calling thread's current device — the GT rows, the
+// bytes the offsets span and the offsets rebased to them travel as whole columns, the kernel runs in place on the device's copy of the
+// messages and that copy comes back into `out`; not combined with other threads' calls, not sharded.
+int gpbc_gt_xor_mask(const void *gt, const void *msgs, const uint64_t *msg_off, size_t width, size_t n, void *out, uint32_t *out_len) {
+    if (!n) return GPBC_OK;
+    if (n > MASK_MAX_N) return fail(GPBC_ERR_INVALID_ARG, "too many items for one call (%zu)", n);
+    if (!gt) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    uint64_t base = 0, bytes = 0;
+    std::vector<uint64_t> rel;
+    if (msg_off) {
+        for (size_t i = 0; i < n; i++) if (msg_off[i + 1] < msg_off[i]) return fail(GPBC_ERR_INVALID_ARG, "message offsets must not decrease");
+        base = msg_off[0]; bytes = msg_off[n] - base;
+        rel.resize(n + 1);
+        for (size_t i = 0; i <= n; i++) rel[i] = msg_off[i] - base;
+    } else {
+        if (width && n > ~(size_t)0 / width) return fail(GPBC_ERR_INVALID_ARG, "n * width overflows (n = %zu, width = %zu)", n, width);
+        bytes = n * width;
+    }
+    if (bytes && (!msgs || !out)) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    const uint8_t *src = bytes ? (const uint8_t *)msgs + base : nullptr;
+    uint8_t *dst = bytes ? (uint8_t *)out + base : nullptr;
+    if (ranges_meet(gt, n * GPBC_GT_BYTES, dst, bytes)) return fail(GPBC_ERR_INVALID_ARG, "out overlaps gt");
+    if (out != msgs && ranges_meet(src, bytes, dst, bytes)) return fail(GPBC_ERR_INVALID_ARG, "out overlaps msgs (only out == msgs runs in place)");
+    if (out_len && (ranges_meet(out_len, n * sizeof(uint32_t), dst, bytes) || ranges_meet(out_len, n * sizeof(uint32_t), gt, n * GPBC_GT_BYTES)))
+        return fail(GPBC_ERR_INVALID_ARG, "out_len overlaps out or gt");
+    // ONE unit of whole columns: column 0 is the message bytes and, in place, the output
+    HostCall c = HostCall().input(src, bytes, true).input(gt, n * GPBC_GT_BYTES, true);
+    if (msg_off) c.input(rel.data(), (n + 1) * sizeof(uint64_t), true);
+    c.output(dst, bytes).output(out_len, n * sizeof(uint32_t));
+    c.in_place = true;
+    return host_call(1, c, HostRoute{}, [&](const DevCols &d, size_t, hipStream_t st) {
+        return gpbc_gt_xor_mask_dev(d.in[1], d.in[0], msg_off ? (const uint64_t *)d.in[2] : nullptr, bytes, width, n, d.out[0], (uint32_t *)d.out[1], st);
+    });
 }
 
 }  // extern "C"

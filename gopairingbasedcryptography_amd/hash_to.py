@@ -107,5 +107,6 @@ def BytesToG2(b):
 
 
 def FromGT(gt):
-    """hash.FromGT: GT.Bytes() (384 big-endian canonical bytes) of one value."""
+    """hash.FromGT: GT.Bytes() (384 big-endian canonical bytes) of one value.  A batch that XORs these bytes with messages, as
+    Boneh-Franklin Encrypt and Decrypt do, stays on the device with bn254.gt_xor_mask."""
     return bn254.gt_marshal(gt)[0].tobytes()
