@@ -20,7 +20,7 @@ SOURCES = ["gpbc_core.hip", "gpbc_pairing.hip", "gpbc_curve.hip", "gpbc_wire.hip
 HASH_SOURCES = ["gpbc_hash.hip"]
 UNITS = SOURCES + HASH_SOURCES
 HEADERS = ["gpbc_common.hpp", "fe29.hip.hpp", "tower29.hip.hpp", "tower29_pair.hip.hpp", "curve29.hip.hpp", "pairing29.hip.hpp", "pairing29_pair.hip.hpp", "wide29.hip.hpp", "curve29_quad.hip.hpp", "curve29_oct.hip.hpp",
-           "wire29.hip.hpp", "h2c29.hip.hpp", "xmd29.hip.hpp", "msm29.hip.hpp", "group29.hip.hpp", "fr29.hip.hpp", "segred29.hip.hpp", "gtmexp29.hip.hpp", "gmsm29.hip.hpp", "subset29.hip.hpp", "transcript29.hip.hpp", "chacha29.hip.hpp", "share29.hip.hpp", "recon29.hip.hpp", "forest29.hip.hpp", "select29.hip.hpp", "formula29.hip.hpp", "fbindex29.hip.hpp", "lsss29.hip.hpp", "mask29.hip.hpp", "bn254_constants.hip.hpp", "bn254_constants29.hip.hpp"]
+           "wire29.hip.hpp", "h2c29.hip.hpp", "xmd29.hip.hpp", "msm29.hip.hpp", "group29.hip.hpp", "fr29.hip.hpp", "segred29.hip.hpp", "gtmexp29.hip.hpp", "gmsm29.hip.hpp", "subset29.hip.hpp", "transcript29.hip.hpp", "chacha29.hip.hpp", "share29.hip.hpp", "recon29.hip.hpp", "forest29.hip.hpp", "select29.hip.hpp", "formula29.hip.hpp", "fbindex29.hip.hpp", "lsss29.hip.hpp", "mask29.hip.hpp", "frdot29.hip.hpp", "bn254_constants.hip.hpp", "bn254_constants29.hip.hpp"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
 # host-only measurement program over the C ABI (bench.py runs it: calls/s of concurrent one-element calls); built next to the library
 CALLS_SRC = os.path.join(HERE, "..", "tools", "concurrent_calls.cpp")
@@ -29,7 +29,7 @@ CALLS_EXE = os.path.join(HERE, "gpbc_concurrent_calls")
 
 def _source_hash():
     h = hashlib.sha256(" ".join(FLAGS).encode())
-    deps = [os.path.join(CSRC, f) for f in UNITS + HEADERS] + [os.path.join(HERE, "..", "include", name) for name in ("gpbc_bn254.h", "gpbc_bn254_ext.h", "gpbc_bn254_subset.h", "gpbc_bn254_hash.h", "gpbc_bn254_share.h", "gpbc_bn254_indexed.h", "gpbc_bn254_recon.h", "gpbc_bn254_select.h", "gpbc_bn254_formula.h", "gpbc_bn254_random.h", "gpbc_bn254_forest.h", "gpbc_bn254_mask.h")] + [CALLS_SRC]
+    deps = [os.path.join(CSRC, f) for f in UNITS + HEADERS] + [os.path.join(HERE, "..", "include", name) for name in ("gpbc_bn254.h", "gpbc_bn254_ext.h", "gpbc_bn254_subset.h", "gpbc_bn254_hash.h", "gpbc_bn254_share.h", "gpbc_bn254_indexed.h", "gpbc_bn254_recon.h", "gpbc_bn254_select.h", "gpbc_bn254_formula.h", "gpbc_bn254_random.h", "gpbc_bn254_forest.h", "gpbc_bn254_mask.h", "gpbc_bn254_verify.h")] + [CALLS_SRC]
     for d in deps:
         with open(d, "rb") as f:
             h.update(f.read())

@@ -1,4 +1,4 @@
-"""What the scheme planners (bsw07, waters11, lw11, sw05, waters05, gentry06, afp25) share besides the array operations of _buffers:
+"""What the scheme planners (bsw07, waters11, lw11, sw05, waters05, gentry06, afp25, and at the end bls01, zss04, bb04sig) share besides the array operations of _buffers:
 Python integers as scalar rows, public values put where the batch lives, uniform segment tables, index tables for FixedBase.indexed,
 the blinding factor of every Encrypt, a handle that is the caller's or made and closed here, and the items of a batch with ok = 1.
 Host-side and engine-agnostic like the planners: an engine is only ever an argument."""
@@ -117,3 +117,48 @@ class Good:
         if self.count:
             out[bufs.put(self.index, self.like)] = bufs.view(msgs, self.count, width)
         return out
+
+
+# ------------------------------------------------------------------------------------------------ batch verification (bls01, zss04, bb04sig)
+P_MODULUS = 21888242871839275222246405745257275088696311157297823662689037894645226208583
+# the one of GT as gnark holds it in memory: coefficient C0.B0.A0 = 1 in Montgomery form (2^256 mod p, little-endian), the other eleven zero
+GT_ONE = np.frombuffer(((1 << 256) % P_MODULUS).to_bytes(32, "little") + bytes(352), dtype=np.uint8)
+
+
+def interleave(parts, width):
+    """[n * len(parts) * width] flat: row i of every part in turn (the points of a multi-pairing segment per item)"""
+    n = bufs.nbytes(parts[0]) // width
+    return bufs.flat(bufs.cat([bufs.view(p, n, 1, width) for p in parts], axis=1))
+
+
+def group_table(n, group):
+    """the offset table of n items cut into groups of `group`, the last one short"""
+    if not isinstance(group, (int, np.integer)) or isinstance(group, bool) or group < 1:
+        raise ValueError("group must be a positive integer")
+    return np.append(np.arange(0, n, group, dtype=np.uint64), np.uint64(n))
+
+
+def weights(rho, like, n):
+    """the n weights of a batch verification as scalar rows of the kind of `like`: ONE draw of an rng.Randomness (one stream, weight i
+    from index i), or the caller's rows.  Caller-supplied host rows are checked to be non-zero modulo r; rows in a tensor are the
+    caller's promise (a zero weight takes its signature out of the equation: a forgery there would pass)."""
+    if hasattr(rho, "scalars") and not is_buffer(rho):
+        return bufs.flat(bufs.view(rho.scalars(like, n), n * 32))
+    rows = scalars(rho, like, n, "rho")
+    if not bufs.is_torch(rows):
+        r = np.asarray(rows).reshape(n, 32)
+        if any(int.from_bytes(x.tobytes(), "little") % R_ORDER == 0 for x in r):
+            raise ValueError("the weights rho must be non-zero modulo r")
+    return rows
+
+
+def settle(ok_groups, n, group, like, each):
+    """The verdict per item [n] from the verdicts per group: every item of a passing group is accepted; the items of the failing groups
+    are gathered — ONE read of the group verdicts — and settled by each(index) -> their verdicts (the per-item Verify)."""
+    host = ok_groups.cpu().numpy() if bufs.is_torch(ok_groups) else np.asarray(ok_groups)
+    of_item = np.arange(n) // group
+    verdict = bufs.copy(bufs.take(bufs.view(ok_groups, -1), of_item))
+    bad = np.nonzero(host.reshape(-1)[of_item] == 0)[0]
+    if bad.size:
+        verdict[bufs.put(bad, like)] = bufs.view(each(bad), -1)
+    return verdict

@@ -535,6 +535,22 @@ def fr_to_mont(a, out=None):
     return _binary("fr_to_mont", SCALAR_BYTES, _fr_in(a), None, out)
 
 
+def fr_dot_segments(a, b, seg_off, out=None, workspace=None):
+    """out[s] = sum_{i in [seg_off[s], seg_off[s+1])} a[i] b[i] mod r (include/gpbc_bn254_verify.h): gt_multi_exp's shape in Fr, with
+    sums for products.  b: one scalar per element, or ONE list of m when every segment has exactly m elements, or None for the plain
+    sum of a.  Scalar rows (any value below 2^256, acting as its residue) or Python ints in [0, 2^256); the sums are canonical.  numpy
+    arrays in, numpy array out; CUDA tensors in (seg_off a host sequence, or an int64 / uint64 CUDA tensor that is then validated on
+    the device), CUDA tensor out, enqueued on the current torch stream.  Arguments are checked before the engine is touched."""
+    op = _SegRed("fr_dot_segments", SCALAR_BYTES, "a", "b", "elements", "one second operand per element", "second operand",
+                 "scalars must be in [0, 2^256) (they act as their residue mod r)", lambda lib, n, n_seg: lib.gpbc_fr_dot_segments_workspace_bytes(n, n_seg), 16)
+    return _segmented_reduce(op, _fr_in(a), b, seg_off, out, workspace)
+
+
+def fr_sum_segments(a, seg_off):
+    """out[s] = sum a[seg_off[s]:seg_off[s+1]] mod r: fr_dot_segments without a second operand."""
+    return fr_dot_segments(a, None, seg_off)
+
+
 def _fr_rows_arg(v, per_row, what):
     """(flat buffer, rows, per_row) of a polynomial / set / node argument: nested Python ints [rows][per_row] (per_row may then be
     None), or scalar rows as a uint8 array / bytes / CUDA tensor together with per_row"""
@@ -1330,6 +1346,20 @@ def gt_div(a, b):
 
 def gt_inverse(a):
     return _rowwise("gt_inverse_batch", GT_BYTES, (a, GT_BYTES, "a"))
+
+
+def gt_equal(a, b, out=None):
+    """ok[i] = 1 where a[i] == b[i] (or == b[0] for a single b), else 0: (*GT).Equal per row, the 384 bytes compared as they are
+    (include/gpbc_bn254_verify.h).  uint8 [n] of the kind the inputs are: the verdicts of a device-resident batch stay in HBM.  An
+    empty batch returns an empty result without touching the engine."""
+    dev = bufs.device_of(a, b)
+    (a, n), (b, nb) = bufs.rows(a, GT_BYTES, "a"), bufs.rows(b, GT_BYTES, "b")
+    if nb not in (1, n):
+        raise ValueError("need one b or one b per a (got %d for %d)" % (nb, n))
+    out = bufs.output(out, (n,), dev)
+    if n:
+        _call("gt_equal", dev, a, b, nb, n, out)
+    return out
 
 
 def fp_mul(a, b):

@@ -319,6 +319,7 @@ struct SegRedOp {
     size_t ws_align;                                   // what the kernels need of the workspace's address (1: nothing)
     const char *elements, *scalars, *scalar, *x_name, *ws_fn;     // the words of the messages
     int (*launch)(const SegRedArgs &g, int32_t *tabws, hipStream_t st);
+    bool host_sharded = true;                          // the host-pointer entry cuts the segments over the bound devices
 };
 size_t segred_workspace_bytes(const SegRedOp &op, size_t n, size_t n_seg);
 // The device entry: the argument rules (everything that needs no look at a table), the plan, the workspace checks, then one level

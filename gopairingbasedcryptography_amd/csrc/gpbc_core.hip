@@ -456,7 +456,7 @@ int segred_host(const SegRedOp &op, const void *x, const void *k, size_t nk, con
             if (seg_off[j + 1] - seg_off[j] != nk)
                 return fail(GPBC_ERR_INVALID_ARG, "a shared %s list of %zu needs segments of %zu %s (segment %zu has %zu)", op.scalar, nk, nk, op.elements, j, (size_t)(seg_off[j + 1] - seg_off[j]));
     constexpr size_t SHARD_MIN_ELEMENTS = 4096;
-    return run_sharded_segments(seg_off, n_seg, SHARD_MIN_ELEMENTS, [&](size_t lo, size_t hi, const uint64_t *seg, size_t base) {
+    const auto body = [&](size_t lo, size_t hi, const uint64_t *seg, size_t base) {
         const size_t segs = hi - lo, ns = (size_t)seg[segs], nks = shared ? nk : k ? ns : 0;
         const void *ks = k && !shared ? (const uint8_t *)k + base * GPBC_SCALAR_BYTES : k;
         HostCall c = HostCall().input((const uint8_t *)x + base * op.elem_bytes, ns * op.elem_bytes, true).input(ks, nks * GPBC_SCALAR_BYTES, true)
@@ -466,7 +466,9 @@ int segred_host(const SegRedOp &op, const void *x, const void *k, size_t nk, con
         return host_call(segs, c, HostRoute{CALL_KINDS, nullptr, 0, SMALL_CALL_MAX_UNITS, 0, wsb}, [&](const DevCols &d, size_t, hipStream_t st) {
             return segred_dev(op, d.in[0], d.in[1], nks, (const uint64_t *)d.in[2], ns, segs, d.out[0], d.tmp, wsb, st);
         });
-    });
+    };
+    if (!op.host_sharded) return body(0, n_seg, seg_off, 0);
+    return run_sharded_segments(seg_off, n_seg, SHARD_MIN_ELEMENTS, body);
 }
 
 // ---- internal workspace, one grow-only buffer per (bound device slot, stream)

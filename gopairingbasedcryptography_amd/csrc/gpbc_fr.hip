@@ -16,12 +16,14 @@
 #include "lsss29.hip.hpp"
 #include "select29.hip.hpp"
 #include "formula29.hip.hpp"
+#include "frdot29.hip.hpp"
 #include "../../include/gpbc_bn254_share.h"
 #include "../../include/gpbc_bn254_indexed.h"
 #include "../../include/gpbc_bn254_recon.h"
 #include "../../include/gpbc_bn254_select.h"
 #include "../../include/gpbc_bn254_formula.h"
 #include "../../include/gpbc_bn254_forest.h"
+#include "../../include/gpbc_bn254_verify.h"
 
 // ------------------------------------------------------------------------------------------------ elementwise
 // one element per lane (no __restrict__: out may be a, or b)
@@ -1059,6 +1061,52 @@ int gpbc_formula_select(const int64_t *nodes, size_t n_formulas, size_t n_nodes,
                      [=](const DevCols &dc, size_t n, hipStream_t st) {
                          return gpbc_formula_select_dev((const int64_t *)dc.in[0], one ? 1 : n, n_nodes, dc.in[1], n, rows, dc.out[0], dc.out[1], st);
                      });
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ segmented inner products (include/gpbc_bn254_verify.h)
+// L lanes per piece, 64 / L pieces per wavefront (= workgroup) (segred_piece: clamped table, uniform folds, a shared list never overrun):
+// the L lanes stride the piece's elements, EVERY lane of the wavefront runs the wavefront's trip count — a piece slot past the last piece
+// is an empty piece, no lane leaves early — and log2(L) butterfly steps fold the L partial sums (csrc/frdot29.hip.hpp).
+__global__ void __launch_bounds__(BLOCK, FR_DOT_WAVES_PER_SIMD) k_fr_dot_segments(SegRedArgs g, uint32_t L, int wide_x, int wide_k) {
+    const uint32_t lane = threadIdx.x % L;
+    size_t lo = 0, a = 0, b = 0, P = 0;
+    const bool have = segred_piece(g, (size_t)blockIdx.x * (FR_DOT_WAVE / L) + threadIdx.x / L, lo, a, b, P);
+    if (!have) lo = a = b = 0;
+    unsigned long long rounds = fr_dot_rounds(b - a, L);
+    for (uint32_t off = FR_DOT_WAVE / 2; off >= L; off >>= 1) {           // the largest of the wavefront's pieces
+        const unsigned long long o = __shfl_xor(rounds, (int)off, FR_DOT_WAVE);
+        rounds = o > rounds ? o : rounds;
+    }
+    Fr v = fr_dot_lane(g.x, g.k, g.k_shared ? lo : 0, a, b, lane, L, (size_t)rounds, wide_x != 0, wide_k != 0);
+    for (uint32_t off = L / 2; off >= 1; off >>= 1) {
+        Fr o;
+#pragma unroll
+        for (int i = 0; i < NL; i++) o.l.v[i] = __shfl_xor(v.l.v[i], (int)off, FR_DOT_WAVE);
+        v = fr_dot_fold(v, o);
+    }
+    if (have && lane == 0) fr_dot_store(g.out + P * GPBC_SCALAR_BYTES, v);
+}
+static int fr_dot_launch(const SegRedArgs &g, int32_t *, hipStream_t st) {
+    const uint32_t L = fr_dot_lanes(g), per_wave = FR_DOT_WAVE / L;
+    return GPBC_LAUNCH(k_fr_dot_segments, (unsigned)((g.n_pieces + per_wave - 1) / per_wave), BLOCK, st, g, L, (int)(((uintptr_t)g.x & 15) == 0), (int)(((uintptr_t)g.k & 15) == 0));
+}
+// no tables; the piece values are read 128 bits at a time; the host form is one call
+static const SegRedOp FR_DOT_OP{FR_DOT_SHAPE, GPBC_SCALAR_BYTES, 0, 16, "elements", "second operands", "second operand", "a", "gpbc_fr_dot_segments_workspace_bytes", fr_dot_launch, false};
+
+extern "C" {
+
+int gpbc_verify_version(void) { return 1; }
+size_t gpbc_fr_dot_segments_workspace_bytes(size_t n, size_t n_seg) { return segred_workspace_bytes(FR_DOT_OP, n, n_seg); }
+int gpbc_fr_dot_segments_dev(const void *d_a, const void *d_b, size_t nb, const uint64_t *d_seg_off, size_t n, size_t n_seg, void *d_out, void *d_workspace,
+                             size_t workspace_bytes, void *stream) {
+    if (!n_seg) return GPBC_OK;
+    return segred_dev(FR_DOT_OP, d_a, d_b, nb, d_seg_off, n, n_seg, d_out, d_workspace, workspace_bytes, stream);
+}
+int gpbc_fr_dot_segments(const void *a, const void *b, size_t nb, const uint64_t *seg_off, size_t n_seg, void *out) {
+    if (!n_seg) return GPBC_OK;
+    return segred_host(FR_DOT_OP, a, b, nb, seg_off, n_seg, out);
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
 #include "wide29.hip.hpp"
 #include "pairing29.hip.hpp"
 #include "pairing29_pair.hip.hpp"
+#include "../../include/gpbc_bn254_verify.h"
 
 static_assert(LINE_BYTES_PER_PAIR == (size_t)MILLER_LINES * LINE_WORDS * sizeof(int32_t), "lines workspace row size");
 
@@ -649,6 +650,26 @@ GPBC_KERNEL k_gt_binary(const uint8_t *__restrict__ a, const uint8_t *__restrict
     }
     f12_store(out + i * GPBC_GT_BYTES, z);
 }
+// ok[i] = 1 iff the 384 bytes of a[i] and b[i] (b_step 0: b[0]) are equal: GT.Equal on the in-memory structs.  Four neighbouring lanes per
+// row, lane q of them takes the words q, q + 4, ... (W = uint4: a quad reads 64 consecutive bytes per load; uint32_t for rows that are
+// only 4-byte aligned), the four verdicts meet through two butterfly steps.  A lane past the last row compares row n - 1 and stores nothing.
+constexpr int GT_EQUAL_LANES = 4;
+template <class W> __global__ void __launch_bounds__(BLOCK) k_gt_equal(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, size_t b_step, size_t n, uint8_t *__restrict__ ok) {
+    const size_t lane = (size_t)blockIdx.x * BLOCK + threadIdx.x, row = lane / GT_EQUAL_LANES, i = row < n ? row : n - 1;
+    const uint32_t q = (uint32_t)(lane % GT_EQUAL_LANES);
+    const W *pa = reinterpret_cast<const W *>(a + i * GPBC_GT_BYTES), *pb = reinterpret_cast<const W *>(b + i * b_step);
+    constexpr int WORDS = GPBC_GT_BYTES / sizeof(W);
+    uint32_t diff = 0;
+#pragma unroll 6
+    for (int w = q; w < WORDS; w += GT_EQUAL_LANES) {
+        const W x = pa[w], y = pb[w];
+        if constexpr (sizeof(W) == 16) diff |= (x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w);
+        else diff |= x ^ y;
+    }
+    diff |= __shfl_xor(diff, 1);
+    diff |= __shfl_xor(diff, 2);
+    if (q == 0 && row < n) ok[row] = diff == 0;
+}
 
 extern "C" {
 
@@ -804,6 +825,26 @@ static int gt_binary_dev(int op, const void *a, const void *b, size_t n, void *o
 int gpbc_gt_mul_batch_dev(const void *a, const void *b, size_t n, void *o, void *s) { return gt_binary_dev(0, a, b, n, o, s); }
 int gpbc_gt_div_batch_dev(const void *a, const void *b, size_t n, void *o, void *s) { return gt_binary_dev(1, a, b, n, o, s); }
 int gpbc_gt_inverse_batch_dev(const void *a, size_t n, void *o, void *s) { return gt_binary_dev(2, a, nullptr, n, o, s); }
+// GT.Equal per row (include/gpbc_bn254_verify.h): the 384 bytes compared as they are.  ONE launch, no workspace.
+static int gt_equal_args(const void *a, const void *b, size_t nb, size_t n, const void *ok_out) {
+    if (!n) return GPBC_OK;
+    if (nb != n && nb != 1) return fail(GPBC_ERR_INVALID_ARG, "nb must be n or 1 (got nb = %zu, n = %zu)", nb, n);
+    if (n > (size_t)0x7fffffff / GT_EQUAL_LANES) return fail(GPBC_ERR_INVALID_ARG, "too many rows for one call (%zu)", n);
+    if (!a || !b || !ok_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    const uint8_t *ab = (const uint8_t *)a, *bb = (const uint8_t *)b, *ob = (const uint8_t *)ok_out;
+    if ((ab < ob + n && ob < ab + n * GPBC_GT_BYTES) || (bb < ob + n && ob < bb + nb * GPBC_GT_BYTES)) return fail(GPBC_ERR_INVALID_ARG, "ok_out overlaps an input");
+    return GPBC_OK;
+}
+int gpbc_gt_equal_dev(const void *d_a, const void *d_b, size_t nb, size_t n, uint8_t *d_ok_out, void *stream) {
+    TRY(gt_equal_args(d_a, d_b, nb, n, d_ok_out));
+    if (!n) return GPBC_OK;
+    TRY(bind_device());
+    const size_t b_step = nb == 1 ? 0 : GPBC_GT_BYTES;
+    if ((((uintptr_t)d_a | (uintptr_t)d_b) & 15) == 0)
+        return GPBC_LAUNCH_AS("k_gt_equal", k_gt_equal<uint4>, grid_for(n * GT_EQUAL_LANES), BLOCK, (hipStream_t)stream, (const uint8_t *)d_a, (const uint8_t *)d_b, b_step, n, d_ok_out);
+    if ((((uintptr_t)d_a | (uintptr_t)d_b) & 3) != 0) return fail(GPBC_ERR_INVALID_ARG, "GT rows must be 4-byte aligned");
+    return GPBC_LAUNCH_AS("k_gt_equal", k_gt_equal<uint32_t>, grid_for(n * GT_EQUAL_LANES), BLOCK, (hipStream_t)stream, (const uint8_t *)d_a, (const uint8_t *)d_b, b_step, n, d_ok_out);
+}
 
 // Host-pointer entries: [0, n) is split over the bound devices (run_sharded, gpbc_core.hip); each shard uploads, computes and
 // downloads on its own device from its own host thread.
@@ -1135,5 +1176,13 @@ static int gt_binary_host(int op, const void *a, const void *b, size_t n, void *
 int gpbc_gt_mul_batch(const void *a, const void *b, size_t n, void *o) { return gt_binary_host(0, a, b, n, o); }
 int gpbc_gt_div_batch(const void *a, const void *b, size_t n, void *o) { return gt_binary_host(1, a, b, n, o); }
 int gpbc_gt_inverse_batch(const void *a, size_t n, void *o) { return gt_binary_host(2, a, nullptr, n, o); }
+// the shared staging path on the current device; a single b travels once
+int gpbc_gt_equal(const void *a, const void *b, size_t nb, size_t n, uint8_t *ok_out) {
+    TRY(gt_equal_args(a, b, nb, n, ok_out));
+    if (!n) return GPBC_OK;
+    const bool one = nb == 1 && n > 1;
+    return host_call(n, HostCall().input(a, GPBC_GT_BYTES).input(b, GPBC_GT_BYTES, one).output(ok_out, 1), HostRoute{},
+                     [=](const DevCols &d, size_t m, hipStream_t st) { return gpbc_gt_equal_dev(d.in[0], d.in[1], one ? 1 : m, m, d.out[0], st); });
+}
 
 }  // extern "C"

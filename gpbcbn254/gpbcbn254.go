@@ -18,6 +18,7 @@ package gpbcbn254
 #include "gpbc_bn254_share.h"
 #include "gpbc_bn254_indexed.h"
 #include "gpbc_bn254_select.h"
+#include "gpbc_bn254_verify.h"
 */
 import "C"
 
@@ -734,6 +735,60 @@ func FrFindCommon(sets []fr.Element, m int, lists []fr.Element, a, d int) (setPo
 	}
 	common = make([]fr.Element, len(kc))
 	return setPos, listPos, common, ok, frElements(kc, common)
+}
+
+// FrDotSegments: out[s] = sum_{i in [segOff[s], segOff[s+1])} a[i] * b[i] (include/gpbc_bn254_verify.h) — the scalar sums of a batch
+// verifier (sum rho_i per group of signatures) and of the planners' checks (sum w_x lambda_x = s).  b holds one element per a, or ONE
+// list for segments of one length, or is nil for the plain sums.  segOff: len(out) + 1 non-decreasing offsets from 0 to len(a).
+func FrDotSegments(a, b []fr.Element, segOff []uint64) ([]fr.Element, error) {
+	defer pin()()
+	if len(segOff) < 1 || segOff[len(segOff)-1] != uint64(len(a)) {
+		return nil, errSizes
+	}
+	nSeg := len(segOff) - 1
+	if nSeg == 0 {
+		return nil, nil
+	}
+	ka, err := frPlain(a)
+	if err != nil {
+		return nil, err
+	}
+	var kb [][32]byte
+	if b != nil {
+		if kb, err = frPlain(b); err != nil {
+			return nil, err
+		}
+	}
+	ko := make([][32]byte, nSeg)
+	rc := C.gpbc_fr_dot_segments(unsafe.Pointer(unsafe.SliceData(ka)), unsafe.Pointer(unsafe.SliceData(kb)), C.size_t(len(kb)), (*C.uint64_t)(unsafe.SliceData(segOff)),
+		C.size_t(nSeg), unsafe.Pointer(unsafe.SliceData(ko)))
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	out := make([]fr.Element, nSeg)
+	return out, frElements(ko, out)
+}
+
+// GTEqual: ok[i] = a[i].Equal(&b[i]), or a[i].Equal(&b[0]) for a single b, for n elements in one launch (include/gpbc_bn254_verify.h):
+// pairLeft.Equal(&pp.eG1G2) of signature/zss04_signature/zss04_signature.go:337 and signature/bb04_signature/bb04_signature.go:292.
+func GTEqual(a, b []bn254.GT) ([]bool, error) {
+	defer pin()()
+	if len(b) != len(a) && len(b) != 1 {
+		return nil, errSizes
+	}
+	if len(a) == 0 {
+		return nil, nil
+	}
+	ok := make([]uint8, len(a))
+	rc := C.gpbc_gt_equal(unsafe.Pointer(unsafe.SliceData(a)), unsafe.Pointer(unsafe.SliceData(b)), C.size_t(len(b)), C.size_t(len(a)), (*C.uint8_t)(unsafe.SliceData(ok)))
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	out := make([]bool, len(a))
+	for i, v := range ok {
+		out[i] = v != 0
+	}
+	return out, nil
 }
 
 // g1GroupOp: Add (sub == false) or Sub over the batch (cgo cannot take a C function as a value, hence the flag)

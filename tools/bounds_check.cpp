@@ -1238,6 +1238,55 @@ int hc_fr_random(const uint8_t *seed, uint64_t stream, uint64_t first, size_t n,
     return 0;
 }
 }  // extern "C"
+// k_fr_dot_segments as gpbc_fr_dot_segments_dev runs it (csrc/gpbc_fr.hip): the plan and the level walk of csrc/segred29.hip.hpp with
+// FR_DOT_SHAPE, fr_dot_lanes(g) lanes per piece and a wavefront of 64 lanes at a time — fr_dot_lane for each of them with the wavefront's
+// trip count (piece slots past the last piece are empty pieces), the butterfly steps of the fold on all 64 values at once, fr_dot_store
+// by the first lane of every piece.  levels_out: [the number of levels the plan took, the OR of the lanes-per-piece values of its
+// launches].  -1: arguments the entry refuses.
+#include "../gopairingbasedcryptography_amd/csrc/frdot29.hip.hpp"
+extern "C" {
+int hc_fr_dot_segments(const uint8_t *A, const uint8_t *B, size_t nb, const uint64_t *seg_off, size_t n, size_t n_seg, uint8_t *out, uint32_t *levels_out) {
+    if (!n_seg || !seg_off || (n && !A) || !out || (!B && nb) || (B && nb != n && (nb > n || nb * n_seg != n))) return -1;
+    const SegRedPlan plan = segred_plan(FR_DOT_SHAPE, 32, 0, n, n_seg, B != nullptr);
+    std::vector<uint8_t> v0(plan.val_bytes[0]), v1(plan.val_bytes[1]);
+    uint8_t *const val[2] = {v0.data(), v1.data()};
+    uint32_t levels = 0, lanes_used = 0;
+    segred_walk(FR_DOT_SHAPE, segred_args(A, B, nb, seg_off, n, n_seg), val, out, [&](SegRedArgs g, size_t pieces) {
+        g.n_pieces = pieces;
+        levels++;
+        const uint32_t L = fr_dot_lanes(g), per_wave = FR_DOT_WAVE / L;
+        lanes_used |= L;
+        for (size_t w = 0; w < (pieces + per_wave - 1) / per_wave; w++) {
+            size_t lo[FR_DOT_WAVE], a[FR_DOT_WAVE], b[FR_DOT_WAVE], P[FR_DOT_WAVE], rounds = 0;
+            bool have[FR_DOT_WAVE];
+            for (uint32_t t = 0; t < FR_DOT_WAVE; t++) {
+                have[t] = segred_piece(g, w * per_wave + t / L, lo[t], a[t], b[t], P[t]);
+                if (!have[t]) lo[t] = a[t] = b[t] = P[t] = 0;
+                const size_t r = fr_dot_rounds(b[t] - a[t], L);
+                rounds = r > rounds ? r : rounds;
+            }
+            Fr v[FR_DOT_WAVE];
+            for (uint32_t t = 0; t < FR_DOT_WAVE; t++) v[t] = fr_dot_lane(g.x, g.k, g.k_shared ? lo[t] : 0, a[t], b[t], t % L, L, rounds, false, false);
+            for (uint32_t off = L / 2; off >= 1; off >>= 1) {
+                Fr nv[FR_DOT_WAVE];
+                for (uint32_t t = 0; t < FR_DOT_WAVE; t++) nv[t] = fr_dot_fold(v[t], v[t ^ off]);
+                for (uint32_t t = 0; t < FR_DOT_WAVE; t++) v[t] = nv[t];
+            }
+            for (uint32_t t = 0; t < FR_DOT_WAVE; t += L)
+                if (have[t]) fr_dot_store(g.out + P[t] * 32, v[t]);
+        }
+        return 0;
+    });
+    if (levels_out) { levels_out[0] = levels; levels_out[1] = lanes_used; }
+    stats_flush();
+    return 0;
+}
+// the shape constants, for the tests' restatement of the plan: [fill, group, plain_min, lanes of a wavefront, FR_DOT_NORM, FR_DOT_RUN_MUL, FR_DOT_RUN_SUM, FR_DOT_LANES_MIN]
+void hc_fr_dot_shape(uint32_t *o) {
+    o[0] = (uint32_t)FR_DOT_SHAPE.fill; o[1] = (uint32_t)FR_DOT_SHAPE.group; o[2] = (uint32_t)FR_DOT_SHAPE.plain_min; o[3] = FR_DOT_WAVE;
+    o[4] = FR_DOT_NORM; o[5] = FR_DOT_RUN_MUL; o[6] = FR_DOT_RUN_SUM; o[7] = FR_DOT_LANES_MIN;
+}
+}  // extern "C"
 // k_g1_fb_indexed / k_g2_fb_indexed as they are launched: the window tables of the bases (only the rows the scalars reach are built, by
 // the scalar multiplication k_g1/g2_fb_build uses), then fb_index_map / fb_index_output / fb_indexed_lane for every lane of every
 // workgroup.  group_min: as GPBC_FBINDEX_GROUP_MIN of the build (0 = its default 64).  geom_out: [grouped, workgroups, lanes with an
