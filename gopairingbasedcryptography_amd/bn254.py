@@ -660,7 +660,58 @@ SHARE_MAX = 1024
 SHARE_ROOT = 0xFFFFFFFF
 
 
-class ShareTree:
+def _share_nodes(nodes, prefix=""):
+    """a node list as a checked uint32 [n, 2] array; prefix ("tree 3: ") names the tree in a forest's messages"""
+    try:
+        arr = np.ascontiguousarray(np.asarray(nodes, dtype=np.int64).reshape(-1, 2))
+    except (ValueError, TypeError):
+        raise ValueError(prefix + "nodes must be a list of (parent, threshold) pairs") from None
+    if arr.size and (arr.min() < 0 or arr.max() > SHARE_ROOT):
+        raise ValueError(prefix + "parents and thresholds are unsigned 32-bit values")
+    why = share_tree_check(arr.tolist())
+    if why:
+        raise ValueError("malformed " + (prefix or "tree: ") + why)
+    return arr.astype(np.uint32)
+
+
+def _share_counts(nodes):
+    """(leaves, coefficients per item) of a checked node array"""
+    return int((nodes[:, 1] == 0).sum()), int((nodes[:, 1].astype(np.int64) - 1)[nodes[:, 1] != 0].sum())
+
+
+def _share_coeffs(coeffs, k, per_item, noun):
+    """the coefficient argument of a share() as a byte buffer of k x per_item scalars, None where the tree / forest (noun) takes none"""
+    if coeffs is not None and not bufs.is_torch(coeffs) and not isinstance(coeffs, (np.ndarray, bytes, bytearray)):
+        coeffs = [v for row in coeffs for v in (row if isinstance(row, (list, tuple)) else [row])]
+    if per_item:
+        if coeffs is None:
+            raise ValueError("the %s needs %d coefficients per item" % (noun, per_item))
+        c, nc = bufs.rows(_fr_in(coeffs), SCALAR_BYTES, "coeffs")
+        if nc != k * per_item:
+            raise ValueError("coeffs holds %d scalars, expected %d x %d" % (nc, k, per_item))
+        return c
+    if coeffs is not None and bufs.nbytes(_fr_in(coeffs)):
+        raise ValueError("the %s takes no coefficients" % noun)
+    return None
+
+
+class _ShareHandle:
+    """what ShareTree and ShareForest do with their library handle: close() destroys it once, and so does the object's end"""
+    _destroy = None
+
+    def close(self):
+        if self._h:
+            getattr(self._lib, self._destroy)(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ShareTree(_ShareHandle):
     """A threshold access tree uploaded once (include/gpbc_bn254_share.h): afterwards the shares of k secrets — AccessTreeNode.ShareSecret,
     the polynomial of every gate evaluated at its children's positions down to the leaves — are one launch.
 
@@ -673,20 +724,12 @@ class ShareTree:
     Scalars are Python ints, uint8 arrays or CUDA tensors; CUDA tensors give a CUDA tensor enqueued on the current stream and not
     synchronised.  A malformed tree and every argument error are ValueError before the device is touched."""
 
+    _destroy = "gpbc_share_tree_destroy"
+
     def __init__(self, nodes):
         self._h = ctypes.c_void_p()
-        try:
-            arr = np.ascontiguousarray(np.asarray(nodes, dtype=np.int64).reshape(-1, 2))
-        except (ValueError, TypeError):
-            raise ValueError("nodes must be a list of (parent, threshold) pairs") from None
-        if arr.size and (arr.min() < 0 or arr.max() > SHARE_ROOT):
-            raise ValueError("parents and thresholds are unsigned 32-bit values")
-        why = share_tree_check(arr.tolist())
-        if why:
-            raise ValueError("malformed tree: " + why)
-        self.nodes = arr.astype(np.uint32)
-        self.leaves = int((self.nodes[:, 1] == 0).sum())
-        self.coeffs = int((self.nodes[:, 1].astype(np.int64) - 1)[self.nodes[:, 1] != 0].sum())
+        self.nodes = _share_nodes(nodes)
+        self.leaves, self.coeffs = _share_counts(self.nodes)
         self._lib = _lib.load()
         _ensure_init()
         _lib.check(self._lib.gpbc_share_tree_create(self.nodes.ctypes.data, len(self.nodes), ctypes.byref(self._h)))
@@ -694,17 +737,7 @@ class ShareTree:
 
     def share(self, secrets, coeffs=None, out=None):
         s, k = bufs.rows(_fr_in(secrets), SCALAR_BYTES, "secrets")
-        if coeffs is not None and not bufs.is_torch(coeffs) and not isinstance(coeffs, (np.ndarray, bytes, bytearray)):
-            coeffs = [v for row in coeffs for v in (row if isinstance(row, (list, tuple)) else [row])]
-        c = None
-        if self.coeffs:
-            if coeffs is None:
-                raise ValueError("the tree needs %d coefficients per item" % self.coeffs)
-            c, nc = bufs.rows(_fr_in(coeffs), SCALAR_BYTES, "coeffs")
-            if nc != k * self.coeffs:
-                raise ValueError("coeffs holds %d scalars, expected %d x %d" % (nc, k, self.coeffs))
-        elif coeffs is not None and bufs.nbytes(_fr_in(coeffs)):
-            raise ValueError("the tree takes no coefficients")
+        c = _share_coeffs(coeffs, k, self.coeffs, "tree")
         dev = bufs.device_of(s, c, out)
         if k > (1 << 29) - 1:
             raise ValueError("too many items for one call (%d)" % k)
@@ -724,16 +757,7 @@ class ShareTree:
         satisfied children; every leaf that is not used gets 0; ok = 0 and a zero row where the root is not satisfied.  For ok = 1,
         sum_y w[y] share[y] is the secret for every output of share().  Outputs are of the kind that went in."""
         L = self.leaves
-        if isinstance(held, np.ndarray):
-            if held.dtype not in (np.uint8, np.bool_):
-                raise ValueError("held must be uint8 or bool (got %s)" % held.dtype)
-            held = held.astype(np.uint8, copy=False)
-        elif not bufs.is_torch(held) and not isinstance(held, (bytes, bytearray)):
-            hrows = [list(h) for h in held]
-            if any(len(h) != L for h in hrows):
-                raise ValueError("held: every item needs %d entries" % L)
-            held = np.array([1 if v else 0 for h in hrows for v in h], dtype=np.uint8)
-        hb, nheld = bufs.rows(held, 1, "held")
+        hb, nheld = bufs.rows(_held_bytes(held, L), 1, "held")
         if nheld % L:
             raise ValueError("held holds %d bytes, not whole items of %d leaves" % (nheld, L))
         k = nheld // L
@@ -749,17 +773,6 @@ class ShareTree:
                 raise ValueError("the tree is closed")
             _call("fr_tree_weights", dev, self._h, hb, k, out, ok_out)
         return out, ok_out
-
-    def close(self):
-        if self._h:
-            self._lib.gpbc_share_tree_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 FOREST_MAX_TREES = 65536
@@ -779,7 +792,7 @@ def _held_bytes(held, width):
     return np.array([1 if v else 0 for h in hrows for v in h], dtype=np.uint8)
 
 
-class ShareForest:
+class ShareForest(_ShareHandle):
     """T threshold access trees uploaded once (include/gpbc_bn254_forest.h): afterwards the shares of k secrets, item i over the tree
     tree_of[i], are one launch, and so are the reconstruction weights of k attribute sets — ShareTree with a policy per item.
 
@@ -795,6 +808,8 @@ class ShareForest:
     bits).  CUDA tensors give CUDA tensors enqueued on the current stream and not synchronised.  A malformed tree and every argument error
     are ValueError before the device is touched."""
 
+    _destroy = "gpbc_share_forest_destroy"
+
     def __init__(self, node_lists):
         self._h = ctypes.c_void_p()
         lists = list(node_lists)
@@ -802,23 +817,11 @@ class ShareForest:
             raise ValueError("a forest needs at least one tree")
         if len(lists) > FOREST_MAX_TREES:
             raise ValueError("more than %d trees" % FOREST_MAX_TREES)
-        arrays = []
-        for t, nodes in enumerate(lists):
-            try:
-                arr = np.ascontiguousarray(np.asarray(nodes, dtype=np.int64).reshape(-1, 2))
-            except (ValueError, TypeError):
-                raise ValueError("tree %d: nodes must be a list of (parent, threshold) pairs" % t) from None
-            if arr.size and (arr.min() < 0 or arr.max() > SHARE_ROOT):
-                raise ValueError("tree %d: parents and thresholds are unsigned 32-bit values" % t)
-            why = share_tree_check(arr.tolist())
-            if why:
-                raise ValueError("malformed tree %d: %s" % (t, why))
-            arrays.append(arr.astype(np.uint32))
+        arrays = [_share_nodes(nodes, "tree %d: " % t) for t, nodes in enumerate(lists)]
         self.nodes = np.ascontiguousarray(np.concatenate(arrays))
         self.node_off = np.cumsum([0] + [len(a) for a in arrays]).astype(np.uint32)
         self.trees = len(arrays)
-        self.tree_leaves = [int((a[:, 1] == 0).sum()) for a in arrays]
-        self.tree_coeffs = [int((a[:, 1].astype(np.int64) - 1)[a[:, 1] != 0].sum()) for a in arrays]
+        self.tree_leaves, self.tree_coeffs = (list(v) for v in zip(*map(_share_counts, arrays)))
         self.leaves, self.coeffs = max(self.tree_leaves), max(self.tree_coeffs)
         self._lib = _lib.load()
         _ensure_init()
@@ -857,17 +860,7 @@ class ShareForest:
         s, ns = bufs.rows(_fr_in(secrets), SCALAR_BYTES, "secrets")
         if ns != k:
             raise ValueError("secrets holds %d scalars for %d tree ids" % (ns, k))
-        if coeffs is not None and not bufs.is_torch(coeffs) and not isinstance(coeffs, (np.ndarray, bytes, bytearray)):
-            coeffs = [v for row in coeffs for v in (row if isinstance(row, (list, tuple)) else [row])]
-        c = None
-        if self.coeffs:
-            if coeffs is None:
-                raise ValueError("the forest needs %d coefficients per item" % self.coeffs)
-            c, nc = bufs.rows(_fr_in(coeffs), SCALAR_BYTES, "coeffs")
-            if nc != k * self.coeffs:
-                raise ValueError("coeffs holds %d scalars, expected %d x %d" % (nc, k, self.coeffs))
-        elif coeffs is not None and bufs.nbytes(_fr_in(coeffs)):
-            raise ValueError("the forest takes no coefficients")
+        c = _share_coeffs(coeffs, k, self.coeffs, "forest")
         dev = bufs.device_of(ids, s, c, out, ok_out)
         if k > (1 << 29) - 1:
             raise ValueError("too many items for one call (%d)" % k)
@@ -901,17 +894,6 @@ class ShareForest:
                 raise ValueError("the forest is closed")
             _call("fr_forest_weights", dev, self._h, ids, hb, k, out, ok_out)
         return out, ok_out
-
-    def close(self):
-        if self._h:
-            self._lib.gpbc_share_forest_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def share_tree_check(nodes):

@@ -7,10 +7,10 @@
 // before it is uploaded, so the kernels (k_fr_share_forest, k_fr_forest_weights in csrc/gpbc_fr.hip) and the host harness
 // (tools/bounds_check.cpp) use the records as they are; the two differ only in where the staged values wait.
 //
-// The arithmetic is the single-tree kernels': fr_share_step / fr_share_out on unconverted coefficients and positions, the small-integer
-// Lagrange products with FR_RECON_G units of a lane sharing one inversion, only what is written made canonical.  What changes is who
-// walks what.  The geometry — pitch, items per workgroup, LDS instance — is a function of the forest's maxima alone; an item owns
-// lpi = 64 / ipb consecutive lanes of its workgroup's one wave, and at a level its lanes walk the units (or gates) its OWN tree has
+// The arithmetic and the LDS offsets are the single-tree kernels' own code: a sharing unit is share29's fr_share_unit, a gate on the way
+// UP recon29's fr_recon_gate_up, the FR_RECON_G units of a lane that share one inversion its fr_recon_down_batch, all of them handed the
+// item as an ItemView; no field operation is written here.  What is written here is who walks what.  The geometry — pitch, items per
+// workgroup, LDS instance — is a function of the forest's maxima alone; an item owns lpi = 64 / ipb consecutive lanes of its workgroup's one wave, and at a level its lanes walk the units (or gates) its OWN tree has
 // there, none if its tree is shallower.  The level loops and their barriers run to the forest's deepest tree in every lane.
 // Per-item arrays are padded to the maxima: coeffs [k, Cmax] (an item reads its first C_t), held [k, Lmax] (columns >= L_t ignored),
 // out and w_out [k, Lmax] (columns >= L_t written as zero).  tree_of[i] >= T: an all-zero row and ok = 0, and no header is read.
@@ -91,19 +91,10 @@ inline bool fr_forest_plan_ok(const ForestPlan &f) {
         if (t.depth && (lo[0] != 0 || lo[t.depth] != t.U || go[0] != 0 || go[t.depth] != t.G)) return false;
         for (uint32_t lv = 0; lv < t.depth; lv++)
             if (lo[lv] > lo[lv + 1] || go[lv] > go[lv + 1]) return false;
-        for (uint32_t u = 0; u < t.U; u++) {
-            const ShareUnit &s = f.sunits[t.units + u];
-            const ReconUnit &r = f.runits[t.units + u];
-            const uint32_t sd = s.dest & ~FR_SHARE_LEAF, x = s.gate_x >> 16, c0 = s.coef_steps & 0xffffu, steps = s.coef_steps >> 16;
-            if ((s.gate_x & 0xffffu) >= t.G || sd >= ((s.dest & FR_SHARE_LEAF) ? t.L : t.G) || x < 1 || x > FR_SHARE_MAX || c0 + steps > t.C) return false;
-            const uint32_t rd = r.dest & ~FR_SHARE_LEAF, sf = r.sib & 0xffffu, nc = r.sib >> 16, rx = r.gate_x >> 16;
-            if ((r.gate_x & 0xffffu) >= t.G || rd >= ((r.dest & FR_SHARE_LEAF) ? t.L : t.G) || sf + nc > t.U || rx < 1 || rx > nc) return false;
-        }
-        for (uint32_t g = 0; g < t.G; g++) {
-            const ReconGate &q = f.gates[t.gates + g];
-            const uint32_t nc = q.n_t & 0xffffu, th = q.n_t >> 16;
-            if (q.slot > t.U || q.number >= t.G || q.first + nc > t.U || th < 1 || th > nc) return false;
-        }
+        for (uint32_t u = 0; u < t.U; u++)
+            if (!fr_share_unit_ok(f.sunits[t.units + u], t.L, t.G, t.C) || !fr_recon_unit_ok(f.runits[t.units + u], t.L, t.G, t.U)) return false;
+        for (uint32_t g = 0; g < t.G; g++)
+            if (!fr_recon_gate_ok(f.gates[t.gates + g], t.G, t.U)) return false;
     }
     return true;
 }
@@ -170,6 +161,8 @@ GPBC_INLINE ForestItem fr_forest_item(const ForestGeom &g, const ForestTree *tre
     }
     return it;
 }
+// the item as the lane code of share29 / recon29 takes it: laid out by its OWN tree's G and U, its rows Lmax columns wide
+GPBC_INLINE ItemView fr_forest_view(const ForestGeom &g, const ForestItem &it) { return ItemView{it.base, it.t.G, it.t.U, it.item * g.Lmax}; }
 
 // ------------------------------------------------------------------------------------------------ sharing
 template <class Put> GPBC_INLINE void fr_forest_share_stage(const ForestGeom &g, const ForestItem &it, const uint8_t *secrets, const uint8_t *coeffs, const Put &put) {
@@ -184,21 +177,8 @@ template <class Get, class Put>
 GPBC_INLINE void fr_forest_share_level(const ForestGeom &g, const ForestItem &it, const ForestDev &fd, uint32_t lv, const Get &get, const Put &put, uint8_t *out) {
     if (!it.valid || lv > it.t.depth) return;
     const uint32_t first = fd.level_off[it.t.levels + lv - 1], W = fd.level_off[it.t.levels + lv] - first;
-    for (uint32_t u = it.sub; u < W; u += g.lpi) {
-        const ShareUnit un = fd.sunits[it.t.units + first + u];
-        const uint32_t gate = un.gate_x & 0xffffu, x = un.gate_x >> 16, c0 = un.coef_steps & 0xffffu, steps = un.coef_steps >> 16;
-        Fr v = get(it.base + gate * NL);
-        if (steps) {
-            const Fr xi = fr_share_position(x);
-            const uint32_t cw = it.base + (it.t.G + c0) * NL;
-            Fr carry = get(cw + (steps - 1) * NL);
-            for (uint32_t i = steps - 1; i-- > 0;) carry = fr_share_step(carry, get(cw + i * NL), xi);
-            v = fr_share_step(carry, v, xi);
-        }
-        v = fr_share_out(v);
-        if (un.dest & FR_SHARE_LEAF) fr_store_canonical(out + 32 * (it.item * g.Lmax + (un.dest & ~FR_SHARE_LEAF)), v);
-        else put(it.base + un.dest * NL, v);
-    }
+    const ItemView view = fr_forest_view(g, it);
+    for (uint32_t u = it.sub; u < W; u += g.lpi) fr_share_unit(view, fd.sunits[it.t.units + first + u], get, put, out);
 }
 // behind the levels: the share of a tree that is one leaf, zeros in the columns the item's tree does not have, the ok byte
 GPBC_INLINE void fr_forest_share_finish(const ForestGeom &g, const ForestItem &it, const uint8_t *secrets, uint8_t *out, uint8_t *ok_out) {
@@ -209,97 +189,41 @@ GPBC_INLINE void fr_forest_share_finish(const ForestGeom &g, const ForestItem &i
 }
 
 // ------------------------------------------------------------------------------------------------ reconstruction weights
-GPBC_INLINE uint32_t fr_forest_state(const ForestItem &it) { return it.base + it.t.G * NL; }                                    // the item's state word 0
-GPBC_INLINE uint32_t fr_forest_used(const ForestItem &it, uint32_t gate) { return it.base + it.t.G * NL + it.t.U + 1 + gate; }
 template <class Put, class PutW>
 GPBC_INLINE void fr_forest_recon_stage(const ForestGeom &g, const ForestItem &it, const ForestDev &fd, const uint8_t *held, const Put &put, const PutW &putw) {
     if (!it.valid || !it.t.G) return;
+    const ItemView view = fr_forest_view(g, it);
     for (uint32_t s = it.sub; s < it.t.U + 1; s += g.lpi) {
         uint32_t v = 0;
         if (s == 0) put(it.base, fr_one());
         else {
             const uint32_t dest = fd.runits[it.t.units + s - 1].dest;
-            if (dest & FR_SHARE_LEAF) v = held[it.item * g.Lmax + (dest & ~FR_SHARE_LEAF)] ? FR_RECON_SAT : 0u;
+            if (dest & FR_SHARE_LEAF) v = held[view.row + (dest & ~FR_SHARE_LEAF)] ? FR_RECON_SAT : 0u;
         }
-        putw(fr_forest_state(it) + s, v);
+        putw(fr_item_state(view) + s, v);
     }
 }
 // UP, a lane's share of its tree's gates at depth lv (the forest's depth - 1 .. 0); a barrier belongs after it, for every lane
 template <class GetW, class PutW>
 GPBC_INLINE void fr_forest_recon_up(const ForestGeom &g, const ForestItem &it, const ForestDev &fd, uint32_t lv, const GetW &getw, const PutW &putw, uint8_t *ok_out) {
     if (!it.valid || lv >= it.t.depth) return;
-    const uint32_t first = fd.gate_off[it.t.gate_offs + lv], W = fd.gate_off[it.t.gate_offs + lv + 1] - first, sb = fr_forest_state(it);
-    for (uint32_t u = it.sub; u < W; u += g.lpi) {
-        const ReconGate gt = fd.gates[it.t.gates + first + u];
-        const uint32_t n = gt.n_t & 0xffffu, t = gt.n_t >> 16;
-        uint32_t cnt = 0;
-        for (uint32_t c = 0; c < n && cnt < t; c++) {
-            const uint32_t w = sb + 1 + gt.first + c, s = getw(w);
-            if (s & FR_RECON_SAT) { putw(w, s | FR_RECON_CHOSEN); cnt++; }
-        }
-        const bool sat = cnt == t;
-        if (sat) putw(sb + gt.slot, FR_RECON_SAT);
-        if (!gt.slot) {                                     // the root: used iff satisfied
-            putw(fr_forest_used(it, gt.number), sat ? 1u : 0u);
-            ok_out[it.item] = sat ? 1 : 0;
-        }
-    }
+    const uint32_t first = fd.gate_off[it.t.gate_offs + lv], W = fd.gate_off[it.t.gate_offs + lv + 1] - first;
+    const ItemView view = fr_forest_view(g, it);
+    for (uint32_t u = it.sub; u < W; u += g.lpi) fr_recon_gate_up(view, fd.gates[it.t.gates + first + u], getw, putw, ok_out + it.item);
 }
 // DOWN, a lane's share of level lv (1 .. the forest's depth) of its item's tree; a barrier belongs after it, for every lane
 template <int GG, class Get, class Put, class GetW, class PutW>
 GPBC_INLINE void fr_forest_recon_down(const ForestGeom &g, const ForestItem &it, const ForestDev &fd, uint32_t lv, const Get &get, const Put &put, const GetW &getw, const PutW &putw,
                                       uint8_t *w_out) {
-    static_assert(GG >= 1 && GG <= 32, "one used bit per unit of a lane");
     if (!it.valid || lv > it.t.depth) return;
-    const uint32_t first = fd.level_off[it.t.levels + lv - 1], W = fd.level_off[it.t.levels + lv] - first, sb = fr_forest_state(it);
-    const ReconUnit *units = fd.runits + it.t.units;
+    const uint32_t first = fd.level_off[it.t.levels + lv - 1], W = fd.level_off[it.t.levels + lv] - first;
+    const ItemView view = fr_forest_view(g, it);
     for (uint32_t b = 0; b < W; b += g.lpi * GG) {
-        Fr Wv[GG], D[GG], P = fr_one();
-        uint32_t used = 0;
-#pragma unroll
-        for (int q = 0; q < GG; q++) {
+        const auto slot = [&](int q) {
             const uint32_t u = b + (uint32_t)q * g.lpi + it.sub;
-            Fr n = fr_one(), d = fr_one();
-            if (u < W) {
-                const uint32_t ui = first + u;
-                const ReconUnit un = units[ui];
-                const uint32_t gate = un.gate_x & 0xffffu, x = un.gate_x >> 16, sfirst = un.sib & 0xffffu, nch = un.sib >> 16;
-                if (getw(fr_forest_used(it, gate)) && (getw(sb + 1 + ui) & FR_RECON_CHOSEN)) {
-                    used |= 1u << q;
-                    n = get(it.base + gate * NL);
-                    // (0 - j) / (i - j) = j / (j - i); two positions a product: j j' and (j - i)(j' - i) are one limb each
-                    int32_t pn = 0, pd = 0;
-                    for (uint32_t c = 0; c < nch; c++) {
-                        if (c + 1 == x || !(getw(sb + 1 + sfirst + c) & FR_RECON_CHOSEN)) continue;
-                        const int32_t j = (int32_t)c + 1, dj = j - (int32_t)x;
-                        if (!pn) { pn = j; pd = dj; continue; }
-                        n = fr_mul(n, fr_recon_small(pn * j));
-                        d = fr_mul(d, fr_recon_small(pd * dj));
-                        pn = 0;
-                    }
-                    if (pn) { n = fr_mul(n, fr_recon_small(pn)); d = fr_mul(d, fr_recon_small(pd)); }
-                }
-            }
-            D[q] = d;
-            Wv[q] = q ? fr_mul(n, P) : n;
-            P = q ? fr_mul(P, d) : d;
-        }
-        Fr inv = fr_mul(fr_inv(P), fr_plain_one());            // 2^522 / P / 2^261; no denominator is 0: |j - i| < r
-#pragma unroll
-        for (int q = GG - 1; q >= 0; q--) {
-            const uint32_t u = b + (uint32_t)q * g.lpi + it.sub;
-            if (u < W) {
-                const uint32_t dest = units[first + u].dest;
-                const bool on = (used >> q) & 1u;
-                const Fr v = on ? fr_mul(Wv[q], inv) : fr_zero();                             // the plain weight
-                if (dest & FR_SHARE_LEAF) fr_store_canonical(w_out + 32 * (it.item * g.Lmax + (dest & ~FR_SHARE_LEAF)), on ? fr_canonical<1, 2>(v) : v);
-                else {
-                    if (on) put(it.base + dest * NL, fr_to_internal(v));
-                    putw(fr_forest_used(it, dest), on ? 1u : 0u);
-                }
-            }
-            if (q) inv = fr_mul(inv, D[q]);
-        }
+            return ReconSlot{u < W, first + u, view};
+        };
+        fr_recon_down_batch<GG>(fd.runits + it.t.units, slot, get, put, getw, putw, w_out);
     }
 }
 // behind the levels: the tree that is one leaf (1 when held), zeros in the columns the item's tree does not have, ok = 0 for a tree id

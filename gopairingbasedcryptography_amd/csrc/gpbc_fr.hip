@@ -638,16 +638,49 @@ int gpbc_fr_poly_eval(const void *coeffs, size_t n_coeff_rows, size_t d, const v
                              [=](const DevCols &dc, size_t rows, hipStream_t st) { return gpbc_fr_poly_eval_dev(dc.in[0], one_c ? 1 : rows, d, dc.in[1], one_p ? 1 : rows, m, rows, dc.out[0], st); });
 }
 
-// the sharing plan and, behind it, the reconstruction plan of the same node list (recon29.hip.hpp; level_off serves both)
+// n host tables in one device allocation, each 16-byte aligned, with one copy; at[i]: where table i starts in *block
+static hipError_t upload_tables(int n, const void *const *src, const size_t *bytes, void **block, size_t *at) {
+    size_t end = 0;
+    for (int i = 0; i < n; i++) { at[i] = end; end = (end + bytes[i] + 15) & ~(size_t)15; }
+    std::vector<uint8_t> host(end + 16, 0);
+    for (int i = 0; i < n; i++)
+        if (bytes[i]) memcpy(host.data() + at[i], src[i], bytes[i]);
+    *block = nullptr;
+    hipError_t e = hipMalloc(block, host.size());
+    if (e == hipSuccess) e = hipMemcpy(*block, host.data(), host.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess && *block) { (void)hipFree(*block); *block = nullptr; }
+    return e;
+}
+// what both forms of the tree and forest entries refuse, in this order: p[0 .. n_in) are inputs, the rest outputs; a null pointer that
+// may be absent has nb = 0
+static int handle_args(const void *h, const char *null_handle, const char *overlaps, size_t k, const void *const *p, const size_t *nb, int n_in, int n) {
+    if (!h) return fail(GPBC_ERR_INVALID_ARG, "%s", null_handle);
+    if (k > (size_t)0x7fffffff / 4) return fail(GPBC_ERR_INVALID_ARG, "too many items for one call (%zu)", k);
+    if (!k) return GPBC_OK;
+    for (int i = 0; i < n; i++)
+        if (!p[i] && nb[i]) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    for (int i = n_in; i < n; i++)
+        for (int j = 0; j < i; j++)
+            if (p[i] && p[j] && overlap(p[i], nb[i], p[j], nb[j])) return fail(GPBC_ERR_INVALID_ARG, "%s", overlaps);
+    return GPBC_OK;
+}
+static int handle_device(int device, const char *what) {
+    TRY(bind_device());
+    if (current_device() != device) return fail(GPBC_ERR_INVALID_ARG, "%s was created on device %d", what, device);
+    return GPBC_OK;
+}
+
+// the sharing plan and, behind it, the reconstruction plan of the same node list (recon29.hip.hpp; level_off serves both), in one block
 struct gpbc_share_tree {
     int device;
     ShareGeom geom;
-    ShareUnit *units;
-    uint32_t *level_off;
     ReconGeom rgeom;
-    ReconUnit *runits;
-    ReconGate *rgates;
-    uint32_t *rgate_off;
+    void *block;
+    const ShareUnit *units;
+    const uint32_t *level_off;
+    const ReconUnit *runits;
+    const ReconGate *rgates;
+    const uint32_t *rgate_off;
 };
 int gpbc_share_tree_create(const gpbc_share_node *nodes, size_t n_nodes, gpbc_share_tree **out) {
     static_assert(sizeof(gpbc_share_node) == sizeof(ShareNode), "the public node is the plan's node");
@@ -659,63 +692,41 @@ int gpbc_share_tree_create(const gpbc_share_node *nodes, size_t n_nodes, gpbc_sh
     ReconPlan rplan;
     why = fr_recon_plan(reinterpret_cast<const ShareNode *>(nodes), n_nodes, rplan);
     if (why) return fail(GPBC_ERR_INVALID_ARG, "malformed tree: %s", why);      // fr_share_plan's reasons: nothing that passed above is refused here
+    if (!fr_share_plan_ok(plan)) return fail(GPBC_ERR_INTERNAL, "the sharing plan of a share tree points outside its tables");
     if (!fr_recon_plan_ok(rplan)) return fail(GPBC_ERR_INTERNAL, "the reconstruction plan of a share tree points outside its tables");
     TRY(bind_device());
-    gpbc_share_tree *h = new gpbc_share_tree{current_device(), fr_share_geometry(plan), nullptr, nullptr, fr_recon_geometry(rplan), nullptr, nullptr, nullptr};
-    const size_t ub = (plan.units.size() ? plan.units.size() : 1) * sizeof(ShareUnit), lb = plan.level_off.size() * sizeof(uint32_t);
-    const size_t rub = (rplan.units.size() ? rplan.units.size() : 1) * sizeof(ReconUnit), rgb = (rplan.gates.size() ? rplan.gates.size() : 1) * sizeof(ReconGate),
-                 rob = rplan.gate_off.size() * sizeof(uint32_t);
-    hipError_t e = hipMalloc((void **)&h->units, ub);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->level_off, lb);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->runits, rub);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->rgates, rgb);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->rgate_off, rob);
-    if (e == hipSuccess && plan.units.size()) e = hipMemcpy(h->units, plan.units.data(), plan.units.size() * sizeof(ShareUnit), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(h->level_off, plan.level_off.data(), lb, hipMemcpyHostToDevice);
-    if (e == hipSuccess && rplan.units.size()) e = hipMemcpy(h->runits, rplan.units.data(), rplan.units.size() * sizeof(ReconUnit), hipMemcpyHostToDevice);
-    if (e == hipSuccess && rplan.gates.size()) e = hipMemcpy(h->rgates, rplan.gates.data(), rplan.gates.size() * sizeof(ReconGate), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(h->rgate_off, rplan.gate_off.data(), rob, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (h->units) (void)hipFree(h->units);
-        if (h->level_off) (void)hipFree(h->level_off);
-        if (h->runits) (void)hipFree(h->runits);
-        if (h->rgates) (void)hipFree(h->rgates);
-        if (h->rgate_off) (void)hipFree(h->rgate_off);
-        delete h;
-        return fail(GPBC_ERR_HIP, "uploading a share tree failed: %s", hipGetErrorString(e));
-    }
-    *out = h;
+    const void *src[5] = {plan.units.data(), plan.level_off.data(), rplan.units.data(), rplan.gates.data(), rplan.gate_off.data()};
+    const size_t bytes[5] = {plan.units.size() * sizeof(ShareUnit), plan.level_off.size() * sizeof(uint32_t), rplan.units.size() * sizeof(ReconUnit),
+                             rplan.gates.size() * sizeof(ReconGate), rplan.gate_off.size() * sizeof(uint32_t)};
+    size_t at[5];
+    void *block;
+    const hipError_t e = upload_tables(5, src, bytes, &block, at);
+    if (e != hipSuccess) return fail(GPBC_ERR_HIP, "uploading a share tree failed: %s", hipGetErrorString(e));
+    const uint8_t *b = (const uint8_t *)block;
+    *out = new gpbc_share_tree{current_device(), fr_share_geometry(plan), fr_recon_geometry(rplan), block, (const ShareUnit *)(b + at[0]), (const uint32_t *)(b + at[1]),
+                               (const ReconUnit *)(b + at[2]), (const ReconGate *)(b + at[3]), (const uint32_t *)(b + at[4])};
     return GPBC_OK;
 }
 int gpbc_share_tree_destroy(gpbc_share_tree *t) {
     if (!t) return GPBC_OK;
     (void)hipSetDevice(t->device);
     (void)hipDeviceSynchronize();
-    (void)hipFree(t->units);
-    (void)hipFree(t->level_off);
-    (void)hipFree(t->runits);
-    (void)hipFree(t->rgates);
-    (void)hipFree(t->rgate_off);
+    (void)hipFree(t->block);
     delete t;
     return GPBC_OK;
 }
 size_t gpbc_share_tree_leaves(const gpbc_share_tree *t) { return t ? t->geom.L : 0; }
 size_t gpbc_share_tree_coeffs(const gpbc_share_tree *t) { return t ? t->geom.C : 0; }
 static int share_tree_args(const gpbc_share_tree *t, const void *secrets, const void *coeffs, size_t k, const void *out) {
-    if (!t) return fail(GPBC_ERR_INVALID_ARG, "null tree handle");
-    if (k > (size_t)0x7fffffff / 4) return fail(GPBC_ERR_INVALID_ARG, "too many items for one call (%zu)", k);
-    if (!k) return GPBC_OK;
-    if (!secrets || !out || (t->geom.C && !coeffs)) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    const size_t out_bytes = k * t->geom.L * GPBC_SCALAR_BYTES;
-    if (overlap(out, out_bytes, secrets, k * GPBC_SCALAR_BYTES) || (t->geom.C && overlap(out, out_bytes, coeffs, k * t->geom.C * GPBC_SCALAR_BYTES)))
-        return fail(GPBC_ERR_INVALID_ARG, "out overlaps an input");
-    return GPBC_OK;
+    const size_t S = GPBC_SCALAR_BYTES, L = t ? t->geom.L : 0, C = t ? t->geom.C : 0;
+    const void *p[3] = {secrets, C ? coeffs : nullptr, out};
+    const size_t nb[3] = {k * S, k * C * S, k * L * S};
+    return handle_args(t, "null tree handle", "out overlaps an input", k, p, nb, 2, 3);
 }
 int gpbc_fr_share_tree_dev(const gpbc_share_tree *t, const void *d_secrets, const void *d_coeffs, size_t k, void *d_out, void *stream) {
     TRY(share_tree_args(t, d_secrets, d_coeffs, k, d_out));
     if (!k) return GPBC_OK;
-    TRY(bind_device());
-    if (current_device() != t->device) return fail(GPBC_ERR_INVALID_ARG, "tree was created on device %d", t->device);
+    TRY(handle_device(t->device, "tree"));
     const unsigned grid = (unsigned)fr_share_grid(t->geom, k);
     if (t->geom.large)
         return GPBC_LAUNCH(k_fr_share_tree_large, grid, BLOCK, (hipStream_t)stream, t->units, t->level_off, (const uint8_t *)d_secrets, (const uint8_t *)d_coeffs, k, t->geom, (uint8_t *)d_out);
@@ -735,20 +746,15 @@ int gpbc_fr_share_tree(const gpbc_share_tree *t, const void *secrets, const void
 // ------------------------------------------------------------------------------------------------ threshold-tree weight entries (include/gpbc_bn254_recon.h)
 int gpbc_recon_version(void) { return 1; }
 static int tree_weights_args(const gpbc_share_tree *t, const uint8_t *held, size_t k, const void *w_out, const uint8_t *ok_out) {
-    if (!t) return fail(GPBC_ERR_INVALID_ARG, "null tree handle");
-    if (k > (size_t)0x7fffffff / 4) return fail(GPBC_ERR_INVALID_ARG, "too many items for one call (%zu)", k);
-    if (!k) return GPBC_OK;
-    if (!held || !w_out || !ok_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    const size_t L = t->rgeom.L, wb = k * L * GPBC_SCALAR_BYTES;
-    if (overlap(w_out, wb, held, k * L) || overlap(ok_out, k, held, k * L) || overlap(w_out, wb, ok_out, k))
-        return fail(GPBC_ERR_INVALID_ARG, "an output overlaps an input or the other output");
-    return GPBC_OK;
+    const size_t L = t ? t->rgeom.L : 0;
+    const void *p[3] = {held, w_out, ok_out};
+    const size_t nb[3] = {k * L, k * L * GPBC_SCALAR_BYTES, k};
+    return handle_args(t, "null tree handle", "an output overlaps an input or the other output", k, p, nb, 1, 3);
 }
 int gpbc_fr_tree_weights_dev(const gpbc_share_tree *t, const uint8_t *d_held, size_t k, void *d_w_out, uint8_t *d_ok_out, void *stream) {
     TRY(tree_weights_args(t, d_held, k, d_w_out, d_ok_out));
     if (!k) return GPBC_OK;
-    TRY(bind_device());
-    if (current_device() != t->device) return fail(GPBC_ERR_INVALID_ARG, "tree was created on device %d", t->device);
+    TRY(handle_device(t->device, "tree"));
     const unsigned grid = (unsigned)fr_recon_grid(t->rgeom, k);
     if (t->rgeom.large)
         return GPBC_LAUNCH(k_fr_tree_weights_large, grid, BLOCK, (hipStream_t)stream, t->runits, t->level_off, t->rgates, t->rgate_off, d_held, k, t->rgeom, (uint8_t *)d_w_out, d_ok_out);
@@ -782,27 +788,20 @@ int gpbc_share_forest_create(const gpbc_share_node *nodes, const uint32_t *node_
     if (why && bad < n_trees) return fail(GPBC_ERR_INVALID_ARG, "malformed tree %zu: %s", bad, why);
     if (why) return fail(GPBC_ERR_INVALID_ARG, "malformed forest: %s", why);
     if (!fr_forest_plan_ok(plan)) return fail(GPBC_ERR_INTERNAL, "the plan of a share forest points outside its tables");
-    // one block: headers, sharing units, reconstruction units, level offsets, gate offsets, gates, each table 16-byte aligned
+    // one block: headers, sharing units, reconstruction units, level offsets, gate offsets, gates
     const size_t bytes[6] = {plan.trees.size() * sizeof(ForestTree), plan.sunits.size() * sizeof(ShareUnit), plan.runits.size() * sizeof(ReconUnit),
                              plan.level_off.size() * sizeof(uint32_t), plan.gate_off.size() * sizeof(uint32_t), plan.gates.size() * sizeof(ReconGate)};
     const void *src[6] = {plan.trees.data(), plan.sunits.data(), plan.runits.data(), plan.level_off.data(), plan.gate_off.data(), plan.gates.data()};
-    size_t at[7] = {0};
-    for (int i = 0; i < 6; i++) at[i + 1] = (at[i] + bytes[i] + 15) & ~(size_t)15;
-    std::vector<uint8_t> host(at[6] + 16, 0);
-    for (int i = 0; i < 6; i++)
-        if (bytes[i]) memcpy(host.data() + at[i], src[i], bytes[i]);
+    size_t at[6];
+    void *block;
     TRY(bind_device());
-    gpbc_share_forest *h = new gpbc_share_forest{current_device(), fr_forest_share_geometry(plan), fr_forest_recon_geometry(plan), ForestDev{}, nullptr, {}, {}};
-    hipError_t e = hipMalloc(&h->block, host.size());
-    if (e == hipSuccess) e = hipMemcpy(h->block, host.data(), host.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (h->block) (void)hipFree(h->block);
-        delete h;
-        return fail(GPBC_ERR_HIP, "uploading a share forest failed: %s", hipGetErrorString(e));
-    }
-    const uint8_t *b = (const uint8_t *)h->block;
-    h->dev = ForestDev{(const ForestTree *)(b + at[0]), (const ShareUnit *)(b + at[1]), (const ReconUnit *)(b + at[2]), (const uint32_t *)(b + at[3]), (const uint32_t *)(b + at[4]),
-                       (const ReconGate *)(b + at[5])};
+    const hipError_t e = upload_tables(6, src, bytes, &block, at);
+    if (e != hipSuccess) return fail(GPBC_ERR_HIP, "uploading a share forest failed: %s", hipGetErrorString(e));
+    const uint8_t *b = (const uint8_t *)block;
+    gpbc_share_forest *h = new gpbc_share_forest{current_device(), fr_forest_share_geometry(plan), fr_forest_recon_geometry(plan),
+                                                 ForestDev{(const ForestTree *)(b + at[0]), (const ShareUnit *)(b + at[1]), (const ReconUnit *)(b + at[2]), (const uint32_t *)(b + at[3]),
+                                                           (const uint32_t *)(b + at[4]), (const ReconGate *)(b + at[5])},
+                                                 block, {}, {}};
     for (const ForestTree &t : plan.trees) { h->tree_L.push_back(t.L); h->tree_C.push_back(t.C); }
     *out = h;
     return GPBC_OK;
@@ -820,23 +819,10 @@ size_t gpbc_share_forest_leaves(const gpbc_share_forest *f) { return f ? f->sgeo
 size_t gpbc_share_forest_coeffs(const gpbc_share_forest *f) { return f ? f->sgeom.Cmax : 0; }
 size_t gpbc_share_forest_tree_leaves(const gpbc_share_forest *f, size_t t) { return f && t < f->tree_L.size() ? f->tree_L[t] : 0; }
 size_t gpbc_share_forest_tree_coeffs(const gpbc_share_forest *f, size_t t) { return f && t < f->tree_C.size() ? f->tree_C[t] : 0; }
-// the rules both forms of both entries share: p[0 .. n_in) are inputs, the rest outputs; a null output that may be absent has nb = 0
 static int forest_args(const gpbc_share_forest *f, size_t k, const void *const *p, const size_t *nb, int n_in, int n) {
-    if (!f) return fail(GPBC_ERR_INVALID_ARG, "null forest handle");
-    if (k > (size_t)0x7fffffff / 4) return fail(GPBC_ERR_INVALID_ARG, "too many items for one call (%zu)", k);
-    if (!k) return GPBC_OK;
-    for (int i = 0; i < n; i++)
-        if (!p[i] && nb[i]) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    for (int i = n_in; i < n; i++)
-        for (int j = 0; j < i; j++)
-            if (p[i] && p[j] && overlap(p[i], nb[i], p[j], nb[j])) return fail(GPBC_ERR_INVALID_ARG, "an output overlaps an input or another output");
-    return GPBC_OK;
+    return handle_args(f, "null forest handle", "an output overlaps an input or another output", k, p, nb, n_in, n);
 }
-static int forest_device(const gpbc_share_forest *f) {
-    TRY(bind_device());
-    if (current_device() != f->device) return fail(GPBC_ERR_INVALID_ARG, "forest was created on device %d", f->device);
-    return GPBC_OK;
-}
+static int forest_device(const gpbc_share_forest *f) { return handle_device(f->device, "forest"); }
 static int share_forest_args(const gpbc_share_forest *f, const void *tree_of, const void *secrets, const void *coeffs, size_t k, const void *out, const void *ok_out) {
     const size_t S = GPBC_SCALAR_BYTES, L = f ? f->sgeom.Lmax : 0, C = f ? f->sgeom.Cmax : 0;
     const void *p[5] = {tree_of, secrets, C ? coeffs : nullptr, out, ok_out};

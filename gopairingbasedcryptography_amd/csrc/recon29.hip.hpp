@@ -83,22 +83,26 @@ inline const char *fr_recon_plan(const ShareNode *nodes, size_t n, ReconPlan &r)
     }
     return nullptr;
 }
-// whether every index of a plan's records lies inside the table it points into: asked once, before the plan is uploaded or walked, so
-// that the kernel can use the records as they are
+// whether a reconstruction unit, resp. a gate, stays inside a tree of L leaves, G gates and U units
+inline bool fr_recon_unit_ok(const ReconUnit &u, uint32_t L, uint32_t G, uint32_t U) {
+    const uint32_t d = u.dest & ~FR_SHARE_LEAF, sf = u.sib & 0xffffu, nc = u.sib >> 16, x = u.gate_x >> 16;
+    return (u.gate_x & 0xffffu) < G && d < ((u.dest & FR_SHARE_LEAF) ? L : G) && sf + nc <= U && x >= 1 && x <= nc;
+}
+inline bool fr_recon_gate_ok(const ReconGate &q, uint32_t G, uint32_t U) {
+    const uint32_t nc = q.n_t & 0xffffu, t = q.n_t >> 16;
+    return q.slot <= U && q.number < G && q.first + nc <= U && t >= 1 && t <= nc;
+}
+// whether every index of a plan's records lies inside the table it points into, as fr_share_plan_ok
 inline bool fr_recon_plan_ok(const ReconPlan &p) {
     if (p.units.size() != p.U || p.gates.size() != p.G || p.level_off.size() != p.depth + 1 || p.gate_off.size() != p.depth + 1) return false;
     if (p.L > FR_SHARE_MAX || p.G > FR_SHARE_MAX || p.U + 1 != p.L + p.G) return false;
     if (p.depth && (p.level_off[p.depth] != p.U || p.gate_off[p.depth] != p.G)) return false;
     for (uint32_t lv = 0; lv < p.depth; lv++)
         if (p.level_off[lv] > p.level_off[lv + 1] || p.gate_off[lv] > p.gate_off[lv + 1]) return false;
-    for (const ReconUnit &u : p.units) {
-        const uint32_t d = u.dest & ~FR_SHARE_LEAF, sf = u.sib & 0xffffu, nc = u.sib >> 16, x = u.gate_x >> 16;
-        if ((u.gate_x & 0xffffu) >= p.G || d >= ((u.dest & FR_SHARE_LEAF) ? p.L : p.G) || sf + nc > p.U || x < 1 || x > nc) return false;
-    }
-    for (const ReconGate &q : p.gates) {
-        const uint32_t nc = q.n_t & 0xffffu, t = q.n_t >> 16;
-        if (q.slot > p.U || q.number >= p.G || q.first + nc > p.U || t < 1 || t > nc) return false;
-    }
+    for (const ReconUnit &u : p.units)
+        if (!fr_recon_unit_ok(u, p.L, p.G, p.U)) return false;
+    for (const ReconGate &q : p.gates)
+        if (!fr_recon_gate_ok(q, p.G, p.U)) return false;
     return true;
 }
 
@@ -127,8 +131,8 @@ GPBC_INLINE uint32_t fr_recon_items(const ReconGeom &g, uint32_t block, size_t k
     const size_t left = k - (size_t)block * g.ipb;
     return left < g.ipb ? (uint32_t)left : g.ipb;
 }
-GPBC_INLINE uint32_t fr_recon_state(const ReconGeom &g, uint32_t li) { return li * g.pitch + g.G * NL; }                 // the item's state word 0
-GPBC_INLINE uint32_t fr_recon_used(const ReconGeom &g, uint32_t li, uint32_t gate) { return li * g.pitch + g.G * NL + g.U + 1 + gate; }
+// item li of the workgroup whose first item is item0, as the shared lane code takes it
+GPBC_INLINE ItemView fr_recon_item(const ReconGeom &g, size_t item0, uint32_t li) { return ItemView{li * g.pitch, g.G, g.U, (item0 + li) * g.L}; }
 // a plain value of one limb: a position, a difference of two, or the product of two of either (|v| <= 1024 x 1024)
 constexpr int32_t FR_RECON_SMALL_MAX = (int32_t)(FR_SHARE_MAX * FR_SHARE_MAX);
 GPBC_INLINE Fr fr_recon_small(int32_t v) {
@@ -143,14 +147,30 @@ GPBC_INLINE void fr_recon_stage(const ReconGeom &g, const ReconUnit *units, uint
     const size_t item0 = (size_t)block * g.ipb;
     const uint32_t items = fr_recon_items(g, block, k), per = g.U + 1;
     for (uint32_t idx = lane; idx < items * per; idx += FR_RECON_WAVE) {
-        const uint32_t li = idx / per, s = idx % per;
+        const uint32_t s = idx % per;
+        const ItemView it = fr_recon_item(g, item0, idx / per);
         uint32_t v = 0;
-        if (s == 0) put(li * g.pitch, fr_one());
+        if (s == 0) put(it.base, fr_one());
         else {
             const uint32_t dest = units[s - 1].dest;
-            if (dest & FR_SHARE_LEAF) v = held[(item0 + li) * g.L + (dest & ~FR_SHARE_LEAF)] ? FR_RECON_SAT : 0u;
+            if (dest & FR_SHARE_LEAF) v = held[it.row + (dest & ~FR_SHARE_LEAF)] ? FR_RECON_SAT : 0u;
         }
-        putw(fr_recon_state(g, li) + s, v);
+        putw(fr_item_state(it) + s, v);
+    }
+}
+// UP, one gate of an item: count its satisfied children, mark the first `threshold` CHOSEN and, with as many, itself SAT; *ok is the item's ok byte
+template <class GetW, class PutW> GPBC_INLINE void fr_recon_gate_up(const ItemView &it, const ReconGate &gt, const GetW &getw, const PutW &putw, uint8_t *ok) {
+    const uint32_t n = gt.n_t & 0xffffu, t = gt.n_t >> 16, sb = fr_item_state(it);
+    uint32_t cnt = 0;
+    for (uint32_t c = 0; c < n && cnt < t; c++) {
+        const uint32_t w = sb + 1 + gt.first + c, s = getw(w);
+        if (s & FR_RECON_SAT) { putw(w, s | FR_RECON_CHOSEN); cnt++; }
+    }
+    const bool sat = cnt == t;
+    if (sat) putw(sb + gt.slot, FR_RECON_SAT);
+    if (!gt.slot) {                                         // the root: used iff satisfied
+        putw(fr_item_used(it, gt.number), sat ? 1u : 0u);
+        *ok = sat ? 1 : 0;
     }
 }
 // UP, a lane's share of the gates at depth lv (depth - 1 .. 0); a barrier belongs after it
@@ -161,75 +181,74 @@ GPBC_INLINE void fr_recon_up(const ReconGeom &g, const ReconGate *gates, const u
     const uint32_t first = gate_off[lv], W = gate_off[lv + 1] - first, total = fr_recon_items(g, block, k) * W;
     for (uint32_t u = lane; u < total; u += FR_RECON_WAVE) {
         const uint32_t li = u / W;
-        const ReconGate gt = gates[first + u % W];
-        const uint32_t n = gt.n_t & 0xffffu, t = gt.n_t >> 16, sb = fr_recon_state(g, li);
-        uint32_t cnt = 0;
-        for (uint32_t c = 0; c < n && cnt < t; c++) {
-            const uint32_t w = sb + 1 + gt.first + c, s = getw(w);
-            if (s & FR_RECON_SAT) { putw(w, s | FR_RECON_CHOSEN); cnt++; }
+        fr_recon_gate_up(fr_recon_item(g, item0, li), gates[first + u % W], getw, putw, ok_out + item0 + li);
+    }
+}
+// DOWN, the GG units of a lane that share one inversion.  slot(q): whether the lane has a q-th unit in this batch, which unit of `units`
+// it is (its state word is 1 + unit) and which item it belongs to.
+struct ReconSlot { bool live; uint32_t unit; ItemView item; };
+template <int GG, class Slot, class Get, class Put, class GetW, class PutW>
+GPBC_INLINE void fr_recon_down_batch(const ReconUnit *units, const Slot &slot, const Get &get, const Put &put, const GetW &getw, const PutW &putw, uint8_t *w_out) {
+    static_assert(GG >= 1 && GG <= 32, "one used bit per unit of a lane");
+    Fr Wv[GG], D[GG], P = fr_one();
+    uint32_t used = 0;
+#pragma unroll
+    for (int q = 0; q < GG; q++) {
+        const ReconSlot sl = slot(q);
+        Fr n = fr_one(), d = fr_one();
+        if (sl.live) {
+            const uint32_t ui = sl.unit, sb = fr_item_state(sl.item);
+            const ReconUnit un = units[ui];
+            const uint32_t gate = un.gate_x & 0xffffu, x = un.gate_x >> 16, sfirst = un.sib & 0xffffu, nch = un.sib >> 16;
+            if (getw(fr_item_used(sl.item, gate)) && (getw(sb + 1 + ui) & FR_RECON_CHOSEN)) {
+                used |= 1u << q;
+                n = get(sl.item.base + gate * NL);
+                // (0 - j) / (i - j) = j / (j - i); two positions a product: j j' and (j - i)(j' - i) are one limb each
+                int32_t pn = 0, pd = 0;
+                for (uint32_t c = 0; c < nch; c++) {
+                    if (c + 1 == x || !(getw(sb + 1 + sfirst + c) & FR_RECON_CHOSEN)) continue;
+                    const int32_t j = (int32_t)c + 1, dj = j - (int32_t)x;
+                    if (!pn) { pn = j; pd = dj; continue; }
+                    n = fr_mul(n, fr_recon_small(pn * j));
+                    d = fr_mul(d, fr_recon_small(pd * dj));
+                    pn = 0;
+                }
+                if (pn) { n = fr_mul(n, fr_recon_small(pn)); d = fr_mul(d, fr_recon_small(pd)); }
+            }
         }
-        const bool sat = cnt == t;
-        if (sat) putw(sb + gt.slot, FR_RECON_SAT);
-        if (!gt.slot) {                                     // the root: used iff satisfied
-            putw(fr_recon_used(g, li, gt.number), sat ? 1u : 0u);
-            ok_out[item0 + li] = sat ? 1 : 0;
+        D[q] = d;
+        Wv[q] = q ? fr_mul(n, P) : n;
+        P = q ? fr_mul(P, d) : d;
+    }
+    Fr inv = fr_mul(fr_inv(P), fr_plain_one());            // 2^522 / P / 2^261; no denominator is 0: |j - i| < r
+#pragma unroll
+    for (int q = GG - 1; q >= 0; q--) {
+        const ReconSlot sl = slot(q);
+        if (sl.live) {
+            const uint32_t dest = units[sl.unit].dest;
+            const bool on = (used >> q) & 1u;
+            const Fr v = on ? fr_mul(Wv[q], inv) : fr_zero();                             // the plain weight
+            if (dest & FR_SHARE_LEAF) fr_store_canonical(w_out + 32 * (sl.item.row + (dest & ~FR_SHARE_LEAF)), on ? fr_canonical<1, 2>(v) : v);
+            else {
+                if (on) put(sl.item.base + dest * NL, fr_to_internal(v));
+                putw(fr_item_used(sl.item, dest), on ? 1u : 0u);
+            }
         }
+        if (q) inv = fr_mul(inv, D[q]);
     }
 }
 // DOWN, a lane's share of level lv (1 .. depth); a barrier belongs after it
 template <int GG, class Get, class Put, class GetW, class PutW>
 GPBC_INLINE void fr_recon_down(const ReconGeom &g, const ReconUnit *units, const uint32_t *level_off, uint32_t lv, uint32_t block, uint32_t lane, size_t k, const Get &get,
                                const Put &put, const GetW &getw, const PutW &putw, uint8_t *w_out) {
-    static_assert(GG >= 1 && GG <= 32, "one used bit per unit of a lane");
     const size_t item0 = (size_t)block * g.ipb;
     const uint32_t first = level_off[lv - 1], W = level_off[lv] - first, total = fr_recon_items(g, block, k) * W;
     for (uint32_t base = 0; base < total; base += FR_RECON_WAVE * GG) {
-        Fr Wv[GG], D[GG], P = fr_one();
-        uint32_t used = 0;
-#pragma unroll
-        for (int q = 0; q < GG; q++) {
+        const auto slot = [&](int q) {
             const uint32_t u = base + (uint32_t)q * FR_RECON_WAVE + lane;
-            Fr n = fr_one(), d = fr_one();
-            if (u < total) {
-                const uint32_t li = u / W, ui = first + u % W, sb = fr_recon_state(g, li);
-                const ReconUnit un = units[ui];
-                const uint32_t gate = un.gate_x & 0xffffu, x = un.gate_x >> 16, sfirst = un.sib & 0xffffu, nch = un.sib >> 16;
-                if (getw(fr_recon_used(g, li, gate)) && (getw(sb + 1 + ui) & FR_RECON_CHOSEN)) {
-                    used |= 1u << q;
-                    n = get(li * g.pitch + gate * NL);
-                    // (0 - j) / (i - j) = j / (j - i); two positions a product: j j' and (j - i)(j' - i) are one limb each
-                    int32_t pn = 0, pd = 0;
-                    for (uint32_t c = 0; c < nch; c++) {
-                        if (c + 1 == x || !(getw(sb + 1 + sfirst + c) & FR_RECON_CHOSEN)) continue;
-                        const int32_t j = (int32_t)c + 1, dj = j - (int32_t)x;
-                        if (!pn) { pn = j; pd = dj; continue; }
-                        n = fr_mul(n, fr_recon_small(pn * j));
-                        d = fr_mul(d, fr_recon_small(pd * dj));
-                        pn = 0;
-                    }
-                    if (pn) { n = fr_mul(n, fr_recon_small(pn)); d = fr_mul(d, fr_recon_small(pd)); }
-                }
-            }
-            D[q] = d;
-            Wv[q] = q ? fr_mul(n, P) : n;
-            P = q ? fr_mul(P, d) : d;
-        }
-        Fr inv = fr_mul(fr_inv(P), fr_plain_one());            // 2^522 / P / 2^261; no denominator is 0: |j - i| < r
-#pragma unroll
-        for (int q = GG - 1; q >= 0; q--) {
-            const uint32_t u = base + (uint32_t)q * FR_RECON_WAVE + lane;
-            if (u < total) {
-                const uint32_t li = u / W, dest = units[first + u % W].dest;
-                const bool on = (used >> q) & 1u;
-                const Fr v = on ? fr_mul(Wv[q], inv) : fr_zero();                             // the plain weight
-                if (dest & FR_SHARE_LEAF) fr_store_canonical(w_out + 32 * ((item0 + li) * g.L + (dest & ~FR_SHARE_LEAF)), on ? fr_canonical<1, 2>(v) : v);
-                else {
-                    if (on) put(li * g.pitch + dest * NL, fr_to_internal(v));
-                    putw(fr_recon_used(g, li, dest), on ? 1u : 0u);
-                }
-            }
-            if (q) inv = fr_mul(inv, D[q]);
-        }
+            return u < total ? ReconSlot{true, first + u % W, fr_recon_item(g, item0, u / W)} : ReconSlot{false, 0, ItemView{0, 0, 0, 0}};
+        };
+        fr_recon_down_batch<GG>(units, slot, get, put, getw, putw, w_out);
     }
 }
 // the tree that is one leaf

@@ -143,6 +143,44 @@ inline const char *fr_share_plan(const ShareNode *nodes, size_t n, SharePlan &p)
     }
     return nullptr;
 }
+// whether a sharing unit stays inside a tree of L leaves, G gates and C coefficients per item
+inline bool fr_share_unit_ok(const ShareUnit &s, uint32_t L, uint32_t G, uint32_t C) {
+    const uint32_t d = s.dest & ~FR_SHARE_LEAF, x = s.gate_x >> 16, c0 = s.coef_steps & 0xffffu, steps = s.coef_steps >> 16;
+    return (s.gate_x & 0xffffu) < G && d < ((s.dest & FR_SHARE_LEAF) ? L : G) && x >= 1 && x <= FR_SHARE_MAX && c0 + steps <= C;
+}
+// whether every index of a plan's records lies inside the table it points into: asked once, before the plan is uploaded or walked, so
+// that the kernel can use the records as they are
+inline bool fr_share_plan_ok(const SharePlan &p) {
+    if (p.level_off.size() != p.depth + 1 || p.units.size() + 1 != (size_t)p.L + p.G) return false;
+    if (p.L > FR_SHARE_MAX || p.G > FR_SHARE_MAX || p.G + p.C > 2 * FR_SHARE_MAX || p.level_off[p.depth] != p.units.size()) return false;
+    for (uint32_t lv = 0; lv < p.depth; lv++)
+        if (p.level_off[lv] > p.level_off[lv + 1]) return false;
+    for (const ShareUnit &u : p.units)
+        if (!fr_share_unit_ok(u, p.L, p.G, p.C)) return false;
+    return true;
+}
+
+// What a lane knows of the item it works on, whichever walk hands it out (the single tree's here and in recon29.hip.hpp, the forest's
+// in forest29.hip.hpp): the item's first LDS word, its tree's gates and units (U only where there are state words: the weights), and
+// item x row width, the item's first column of the per-leaf arrays.  Every LDS offset of an item is formed from it, here.
+struct ItemView { uint32_t base, G, U; size_t row; };
+GPBC_INLINE uint32_t fr_item_state(const ItemView &v) { return v.base + v.G * NL; }                                       // the item's state word 0
+GPBC_INLINE uint32_t fr_item_used(const ItemView &v, uint32_t gate) { return v.base + v.G * NL + v.U + 1 + gate; }
+// one sharing unit of an item: the parent's polynomial at the child's position, Horner from the top coefficient, to the leaf's share or the gate's value
+template <class Get, class Put> GPBC_INLINE void fr_share_unit(const ItemView &it, const ShareUnit &un, const Get &get, const Put &put, uint8_t *out) {
+    const uint32_t gate = un.gate_x & 0xffffu, x = un.gate_x >> 16, c0 = un.coef_steps & 0xffffu, steps = un.coef_steps >> 16;
+    Fr v = get(it.base + gate * NL);
+    if (steps) {
+        const Fr xi = fr_share_position(x);
+        const uint32_t cw = it.base + (it.G + c0) * NL;
+        Fr carry = get(cw + (steps - 1) * NL);
+        for (uint32_t i = steps - 1; i-- > 0;) carry = fr_share_step(carry, get(cw + i * NL), xi);
+        v = fr_share_step(carry, v, xi);
+    }
+    v = fr_share_out(v);
+    if (un.dest & FR_SHARE_LEAF) fr_store_canonical(out + 32 * (it.row + (un.dest & ~FR_SHARE_LEAF)), v);
+    else put(it.base + un.dest * NL, v);
+}
 
 // The launch: one wave per workgroup, ipb items per workgroup.  An item's block in LDS holds its gates' values (gate g at word g x NL;
 // gate 0 is the secret) and behind them its coefficients (c at (G + c) x NL), E = G + C elements at an odd pitch; the values stay there
@@ -186,19 +224,7 @@ GPBC_INLINE void fr_share_level(const ShareGeom &g, const ShareUnit *units, cons
     const uint32_t first = level_off[lv - 1], W = level_off[lv] - first, total = fr_share_items(g, block, k) * W;
     for (uint32_t u = lane; u < total; u += FR_SHARE_WAVE) {
         const uint32_t li = u / W;
-        const ShareUnit un = units[first + u % W];
-        const uint32_t gate = un.gate_x & 0xffffu, x = un.gate_x >> 16, c0 = un.coef_steps & 0xffffu, steps = un.coef_steps >> 16, base = li * g.pitch;
-        Fr v = get(base + gate * NL);
-        if (steps) {
-            const Fr xi = fr_share_position(x);
-            const uint32_t cw = base + (g.G + c0) * NL;
-            Fr carry = get(cw + (steps - 1) * NL);
-            for (uint32_t i = steps - 1; i-- > 0;) carry = fr_share_step(carry, get(cw + i * NL), xi);
-            v = fr_share_step(carry, v, xi);
-        }
-        v = fr_share_out(v);
-        if (un.dest & FR_SHARE_LEAF) fr_store_canonical(out + 32 * ((item0 + li) * g.L + (un.dest & ~FR_SHARE_LEAF)), v);
-        else put(base + un.dest * NL, v);
+        fr_share_unit(ItemView{li * g.pitch, g.G, 0, (item0 + li) * g.L}, units[first + u % W], get, put, out);
     }
 }
 // the tree that is one leaf

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Threshold-tree forests measured on one MI355X, in one process: writes profiles/share_forest.json.
 
-  (1) the cost of generality: ITEMS items over ONE tree — 256-of-256, 128-of-256, 16 x (16-of-16) under 16-of-16 — through ShareTree and
-      through a ShareForest of that one tree, share and weights, on the same HBM-resident inputs; the bytes must be equal; the ratio is
-      reported, not gated;
+  (1) the cost of generality: ITEMS items over ONE tree — 256-of-256, 128-of-256, 16 x (16-of-16) under 16-of-16, and two trees whose
+      levels are no power of two wide, 2-of-3 and 3-of-5 over five 2-of-3 gates — through ShareTree and through a ShareForest of that
+      one tree, share and weights, on the same HBM-resident inputs; the bytes must be equal; the ratio is reported, not gated;
   (2) the mixed call: ITEMS items over 16 and over 256 distinct flat policies t-of-n, n in 16 .. 256, assigned at random.  ShareForest.share
       / .weights against the single-policy route: group by policy on the host, one ShareTree per policy (made beforehand; the time to make
       them is reported beside it), gather, call, scatter back into the padded rows.  The bytes must be equal.  Then
@@ -105,7 +105,9 @@ def main():
 
     # ---- (1) one tree: the forest of it beside ShareTree
     doc["one_tree"] = []
-    for name, tree in (("256-of-256", flat(256, 256)), ("128-of-256", flat(128, 256)), ("16x(16-of-16)", Threshold(16, *[flat(16, 16) for _ in range(16)]))):
+    # the last two have levels that are no power of two (3; 5 and 15): the forest's fixed lanes per item leave part of a wave idle there
+    for name, tree in (("256-of-256", flat(256, 256)), ("128-of-256", flat(128, 256)), ("16x(16-of-16)", Threshold(16, *[flat(16, 16) for _ in range(16)])),
+                       ("2-of-3", flat(2, 3)), ("3-of-5 over 5x(2-of-3)", Threshold(3, *[flat(2, 3) for _ in range(5)]))):
         nodes, _ = bsw07.share_plan(tree)
         t, f = eng.ShareTree(nodes), eng.ShareForest([nodes])
         L, C = t.leaves, t.coeffs

@@ -889,13 +889,15 @@ int hc_fr_lsss_launch(const uint8_t *matrix, size_t n_matrices, size_t rows, siz
     stats_flush();
     return 0;
 }
-// A stand-in for an LDS block of `words` words that refuses a store outside the block or across the boundaries of another element and a
-// load of anything but a whole element stored before (k_fr_poly_eval and k_fr_share_tree as they are LAUNCHED, below)
+// A stand-in for an LDS block of `words` words, elements of NL words and single words side by side (the kernels as they are LAUNCHED,
+// below; the single words are k_fr_tree_weights' and k_fr_forest_weights').  A store outside the block, an element across a word or
+// another element's boundaries, a word inside an element, and a load of anything but what was stored whole at that offset are refused.
 struct CheckedLds {
     std::vector<Fr> v;
-    std::vector<int64_t> owner;
+    std::vector<uint32_t> w;
+    std::vector<int64_t> owner;                 // -1 free, off: a word of the element at off, -2 - off: the single word at off
     bool bad = false;
-    explicit CheckedLds(size_t words) : v(words), owner(words, -1) {}
+    explicit CheckedLds(size_t words) : v(words), w(words, 0), owner(words, -1) {}
     void reset() { std::fill(owner.begin(), owner.end(), -1); }
     Fr get(uint32_t off) {
         if ((size_t)off + NL > v.size() || owner[off] != (int64_t)off) { bad = true; return fr_zero(); }
@@ -905,6 +907,15 @@ struct CheckedLds {
         if ((size_t)off + NL > v.size()) { bad = true; return; }
         for (int i = 0; i < NL; i++) { if (owner[off + i] != -1 && owner[off + i] != (int64_t)off) bad = true; owner[off + i] = off; }
         v[off] = x;
+    }
+    uint32_t getw(uint32_t off) {
+        if ((size_t)off >= w.size() || owner[off] != -2 - (int64_t)off) { bad = true; return 0; }
+        return w[off];
+    }
+    void putw(uint32_t off, uint32_t x) {
+        if ((size_t)off >= w.size() || (owner[off] != -1 && owner[off] != -2 - (int64_t)off)) { bad = true; return; }
+        owner[off] = -2 - (int64_t)off;
+        w[off] = x;
     }
 };
 // k_fr_poly_eval as it is launched: geometry, staging and lane mapping of share29.hip.hpp, workgroup by workgroup.
@@ -945,10 +956,11 @@ int hc_fr_share_plan(const uint32_t *nodes, size_t n_nodes, uint32_t *sizes_out,
     return 0;
 }
 // k_fr_share_tree as it is launched: the plan, the geometry, the staging and every level of share29.hip.hpp, workgroup by workgroup, a
-// barrier = the end of a loop over the lanes.  geom_out: [L, G, C, depth, ipb, large, workgroups].  -1: a refused tree or argument; -2 as above.
+// barrier = the end of a loop over the lanes.  geom_out: [L, G, C, depth, ipb, large, workgroups].  -1: a refused tree or argument; -2 as above, or a plan index outside its table.
 int hc_fr_share_tree(const uint32_t *nodes, size_t n_nodes, const uint8_t *secrets, const uint8_t *coeffs, size_t k, uint8_t *out, uint32_t *geom_out) {
     SharePlan p;
     if (fr_share_plan(reinterpret_cast<const ShareNode *>(nodes), n_nodes, p) || !k || !secrets || !out || (p.C && !coeffs)) return -1;
+    if (!fr_share_plan_ok(p)) return -2;
     const ShareGeom g = fr_share_geometry(p);
     CheckedLds lds((size_t)(g.large ? FR_TREE_LARGE : FR_TREE_SMALL) * NL + FR_SHARE_WAVE);
     const size_t grid = fr_share_grid(g, k);
@@ -969,35 +981,6 @@ int hc_fr_share_tree(const uint32_t *nodes, size_t n_nodes, const uint8_t *secre
     stats_flush();
     return 0;
 }
-// The LDS block of k_fr_tree_weights: elements of NL words and single words side by side.  A store outside the block, an element across
-// a word or another element's boundaries, a word inside an element, and a load of anything but what was stored whole at that offset
-// are refused.
-struct CheckedMixed {
-    std::vector<Fr> v;
-    std::vector<uint32_t> w;
-    std::vector<int64_t> owner;                 // -1 free, off: a word of the element at off, -2 - off: the single word at off
-    bool bad = false;
-    explicit CheckedMixed(size_t words) : v(words), w(words, 0), owner(words, -1) {}
-    void reset() { std::fill(owner.begin(), owner.end(), -1); }
-    Fr get(uint32_t off) {
-        if ((size_t)off + NL > v.size() || owner[off] != (int64_t)off) { bad = true; return fr_zero(); }
-        return v[off];
-    }
-    void put(uint32_t off, const Fr &x) {
-        if ((size_t)off + NL > v.size()) { bad = true; return; }
-        for (int i = 0; i < NL; i++) { if (owner[off + i] != -1 && owner[off + i] != (int64_t)off) bad = true; owner[off + i] = off; }
-        v[off] = x;
-    }
-    uint32_t getw(uint32_t off) {
-        if ((size_t)off >= w.size() || owner[off] != -2 - (int64_t)off) { bad = true; return 0; }
-        return w[off];
-    }
-    void putw(uint32_t off, uint32_t x) {
-        if ((size_t)off >= w.size() || (owner[off] != -1 && owner[off] != -2 - (int64_t)off)) { bad = true; return; }
-        owner[off] = -2 - (int64_t)off;
-        w[off] = x;
-    }
-};
 // k_fr_tree_weights as it is launched: the plan, the geometry, the staging and both passes of recon29.hip.hpp, workgroup by workgroup, a
 // barrier = the end of a loop over the lanes.  geom_out: [L, G, U, depth, ipb, pitch, large, workgroups].  -1: a refused tree or argument;
 // -2: a refusal of the LDS stand-in, a plan index outside its table or an output outside the rows.
@@ -1007,7 +990,7 @@ int hc_fr_tree_weights(const uint32_t *nodes, size_t n_nodes, const uint8_t *hel
     const ReconGeom g = fr_recon_geometry(p);
     if (g.G && (size_t)g.ipb * g.pitch > (size_t)(g.large ? FR_RECON_LARGE : FR_RECON_SMALL)) return -2;
     if (!fr_recon_plan_ok(p)) return -2;
-    CheckedMixed lds((size_t)(g.large ? FR_RECON_LARGE : FR_RECON_SMALL) + FR_RECON_WAVE);
+    CheckedLds lds((size_t)(g.large ? FR_RECON_LARGE : FR_RECON_SMALL) + FR_RECON_WAVE);
     const size_t grid = fr_recon_grid(g, k);
     const auto get = [&](uint32_t off) { return lds.get(off); };
     const auto put = [&](uint32_t off, const Fr &v) { lds.put(off, v); };
@@ -1430,7 +1413,7 @@ int hc_fr_forest_weights(const uint32_t *nodes, const uint32_t *node_off, size_t
     const size_t cap = (size_t)(g.large ? FR_RECON_LARGE : FR_RECON_SMALL);
     if (g.ipb * g.lpi != (uint32_t)FR_RECON_WAVE || (size_t)g.ipb * g.pitch > cap) return -2;
     const ForestDev fd{f.trees.data(), f.sunits.data(), f.runits.data(), f.level_off.data(), f.gate_off.data(), f.gates.data()};
-    CheckedMixed lds(cap + FR_RECON_WAVE);
+    CheckedLds lds(cap + FR_RECON_WAVE);
     const size_t grid = fr_forest_grid(g, k);
     const auto get = [&](uint32_t off) { return lds.get(off); };
     const auto put = [&](uint32_t off, const Fr &v) { lds.put(off, v); };
