@@ -1344,6 +1344,46 @@ def gt_equal(a, b, out=None):
     return out
 
 
+# --------------------------------------------------------------------------------------- membership of in-memory elements
+# (*G1Affine|*G2Affine).IsOnCurve / IsInSubGroup and (*GT).IsInSubGroup for n structs as they are in memory
+# (include/gpbc_bn254_member.h): what guards elements that did not come through g1_unmarshal / g2_unmarshal — the only other places where
+# the engine validates anything.
+def _member(name, width, x, out):
+    """ok[i] = the verdict for row i: uint8 [n] of the kind `x` is.  An empty batch returns an empty result without touching the engine."""
+    dev = bufs.device_of(x, out)
+    x, n = bufs.rows(x, width, "x")
+    out = bufs.output(out, (n,), dev)
+    if n:
+        _call(name, dev, x, n, out)
+    return out
+
+
+def g1_is_on_curve(x, out=None):
+    """ok[i] = 1 where the G1Affine struct x[i] is on the curve (the point at infinity is), else 0; a coordinate whose stored value is not
+    below p gives 0.  Host arrays in, host array out; CUDA tensors in, CUDA tensor out on the current stream."""
+    return _member("g1_is_on_curve", G1_BYTES, x, out)
+
+
+g1_is_in_subgroup = g1_is_on_curve           # the cofactor of G1 is 1: gnark's IsInSubGroup is the same verdict
+
+
+def g2_is_on_curve(x, out=None):
+    """ok[i] = 1 where the G2Affine struct x[i] is on the twist (infinity is), else 0"""
+    return _member("g2_is_on_curve", G2_BYTES, x, out)
+
+
+def g2_is_in_subgroup(x, out=None):
+    """ok[i] = 1 where x[i] is on the twist AND in its subgroup of order r (gnark's endomorphism identity), else 0.  gnark's IsInSubGroup
+    evaluates the identity without a curve test; this entry's 0 for a point off the twist is the project's definition."""
+    return _member("g2_is_in_subgroup", G2_BYTES, x, out)
+
+
+def gt_is_in_subgroup(x, out=None):
+    """ok[i] = 1 where the GT struct x[i] is canonical, not zero and of order dividing r (cyclotomic and x^p == x^(6u^2): gnark's
+    E12.IsInSubGroup, which read literally accepts zero; this entry does not), else 0"""
+    return _member("gt_is_in_subgroup", GT_BYTES, x, out)
+
+
 def fp_mul(a, b):
     """Batched Fp Montgomery product (kernel unit test entry; host buffers only)."""
     a, b = np.asarray(a, dtype=np.uint8), np.asarray(b, dtype=np.uint8)

@@ -1438,3 +1438,35 @@ int hc_fr_forest_weights(const uint32_t *nodes, const uint32_t *node_off, size_t
     return 0;
 }
 }
+
+// ------------------------------------------------------------------------------------------------ membership of in-memory elements
+#include "../gopairingbasedcryptography_amd/csrc/member29.hip.hpp"
+extern "C" {
+// the lane bodies of k_g1_is_on_curve, k_g2_is_on_curve (curve_only = 1) / k_g2_is_in_subgroup and k_gt_is_in_subgroup, a verdict byte per
+// element.  force = 1 runs every GT element through the whole chain, whatever the earlier tests said: what a lane pair does on the device
+// beside a neighbour that is still a candidate — the limb-bound proof for non-cyclotomic values in the Granger-Scott squarings; force = 0
+// is the wavefront skip with the pair as the whole wavefront.
+void hc_g1_is_on_curve(const uint8_t *P, size_t n, uint8_t *ok) {
+    for (size_t i = 0; i < n; i++) ok[i] = g1_member_on_curve(P + 64 * i) ? 1 : 0;
+    stats_flush();
+}
+void hc_g2_is_in_subgroup(const uint8_t *P, size_t n, uint8_t *ok, int curve_only) {
+    for (size_t i = 0; i < n; i++) ok[i] = g2_member(P + 128 * i, !curve_only) ? 1 : 0;
+    stats_flush();
+}
+void hc_gt_is_in_subgroup(const uint8_t *Z, size_t n, uint8_t *ok, int force) {
+    for (size_t i = 0; i < n; i++) {
+        PairRendezvous rv;
+        bool verdict[2];
+        auto lane = [&](bool odd) {
+            PairHost x{odd, &rv};
+            verdict[odd] = gt_member_pair(x, Z + 384 * i + (odd ? 192 : 0), force != 0);
+            stats_flush();
+        };
+        std::thread t1(lane, true);
+        lane(false);
+        t1.join();
+        ok[i] = verdict[0] ? (verdict[1] ? 1 : 2) : (verdict[1] ? 2 : 0);      // 2: the two lanes of a pair disagree (never)
+    }
+}
+}
