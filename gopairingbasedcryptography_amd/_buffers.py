@@ -144,6 +144,15 @@ def rows_nonzero(a):
     return (a != 0).any(1).to(a.dtype) if is_torch(a) else (a != 0).any(1).astype(np.uint8)
 
 
+def unpack_bits(a):
+    """[n, W] bytes as [n, 8 W] bits of 0 / 1, the most significant bit of every byte first (numpy.unpackbits' order), uint8 of the
+    buffer's kind"""
+    if not is_torch(a):
+        return np.unpackbits(np.asarray(a, dtype=np.uint8), axis=1)
+    shifts = put(np.arange(7, -1, -1, dtype=np.uint8), a)
+    return ((a.unsqueeze(-1) >> shifts) & 1).reshape(a.shape[0], -1)
+
+
 def rows_equal(a, b):
     """per row of two uint8 buffers of one shape and kind: 1 where the rows hold the same bytes, else 0"""
     return (a == b).all(1).to(a.dtype) if is_torch(a) else (a == b).all(1).astype(np.uint8)

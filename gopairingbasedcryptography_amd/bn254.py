@@ -1659,6 +1659,55 @@ INDEX_NONE = 0xFFFFFFFF          # GPBC_INDEX_NONE: "no term" in an index row of
 INDEXED_MAX_TERMS = 16
 
 
+def _indexed(name, handle, width, index, scalars, terms, out, ok_out):
+    """The arguments of FixedBase.indexed / GTFixedBase.indexed, checked, and the call gpbc_<name>: (out [n, width], ok [n])"""
+    if not bufs.is_torch(index) and not isinstance(index, np.ndarray):
+        irows = [list(r) if isinstance(r, (list, tuple)) else [r] for r in index]
+        terms = len(irows[0]) if irows and terms is None else terms
+        if any(len(r) != terms for r in irows):
+            raise ValueError("index: every row needs %s entries" % terms)
+        flat = [INDEX_NONE if v is None else int(v) for r in irows for v in r]
+        if any(v < 0 or v > INDEX_NONE for v in flat):
+            raise ValueError("index entries are unsigned 32-bit values")
+        index = np.array(flat, dtype=np.uint32)
+    if not isinstance(terms, (int, np.integer)) or isinstance(terms, bool) or not 1 <= int(terms) <= INDEXED_MAX_TERMS:
+        raise ValueError("terms must be in 1 .. %d (got %s)" % (INDEXED_MAX_TERMS, terms))
+    terms = int(terms)
+    if bufs.is_torch(index):
+        if str(index.dtype) not in ("torch.int32", "torch.uint32") or not index.is_contiguous():
+            raise ValueError("a device index must be a contiguous int32 / uint32 tensor")
+        nidx = index.numel()
+    else:
+        if index.dtype != np.uint32:
+            raise ValueError("index must be uint32 (got %s)" % index.dtype)
+        index = np.ascontiguousarray(index).reshape(-1)
+        nidx = index.size
+    if not bufs.is_torch(scalars) and not isinstance(scalars, (np.ndarray, bytes, bytearray)):
+        srows = [list(r) if isinstance(r, (list, tuple)) else [r] for r in scalars]
+        if any(len(r) != terms for r in srows):
+            raise ValueError("scalars: every output needs %d scalars" % terms)
+        scalars = [v for r in srows for v in r]
+    k, nscalars = bufs.rows(_fr_in(scalars), SCALAR_BYTES, "scalars")
+    dev = bufs.device_of(index, k, out, ok_out)
+    if nscalars % terms or nidx % terms:
+        raise ValueError("scalars and index need whole rows of %d" % terms)
+    n, nrows = nscalars // terms, nidx // terms
+    if n and not 1 <= nrows <= n:
+        raise ValueError("index needs between 1 and n = %d rows (got %d)" % (n, nrows))
+    if n * terms >> 32:
+        raise ValueError("n * terms must stay below 2^32")
+    out = bufs.output(out, (n, width), dev)
+    ok = bufs.output(ok_out, (n,), dev, "ok")
+    if n:
+        if not handle:
+            raise ValueError("the table is closed")
+        idx_bytes = index.view(np.uint8) if dev is None else None
+        if _overlaps(out, idx_bytes, k) or (ok_out is not None and _overlaps(ok, idx_bytes, k, out)):
+            raise ValueError("out overlaps an input")
+        _call(name, dev, handle, index, nrows, terms, k, n, out, ok)
+    return out, ok
+
+
 class FixedBase:
     """8-bit window tables of a fixed set of bases kept in HBM (1 MB per G1 base, 2 MB per G2 base): afterwards a term of
     a sum costs 32 mixed additions and no doublings.  Serves (*G1Affine|*G2Affine).ScalarMultiplicationBase (one base: the
@@ -1718,54 +1767,75 @@ class FixedBase:
         ints or n x terms scalar rows, any value below 2^256, used as they are (so [r] B is infinity).  1 <= terms <= 16.  An index
         >= nbase other than INDEX_NONE gives an all-zero row and ok = 0.  CUDA tensors in give CUDA tensors out, enqueued on the
         current stream and not synchronised."""
-        if not bufs.is_torch(index) and not isinstance(index, np.ndarray):
-            irows = [list(r) if isinstance(r, (list, tuple)) else [r] for r in index]
-            terms = len(irows[0]) if irows and terms is None else terms
-            if any(len(r) != terms for r in irows):
-                raise ValueError("index: every row needs %s entries" % terms)
-            flat = [INDEX_NONE if v is None else int(v) for r in irows for v in r]
-            if any(v < 0 or v > INDEX_NONE for v in flat):
-                raise ValueError("index entries are unsigned 32-bit values")
-            index = np.array(flat, dtype=np.uint32)
-        if not isinstance(terms, (int, np.integer)) or isinstance(terms, bool) or not 1 <= int(terms) <= INDEXED_MAX_TERMS:
-            raise ValueError("terms must be in 1 .. %d (got %s)" % (INDEXED_MAX_TERMS, terms))
-        terms = int(terms)
-        if bufs.is_torch(index):
-            if str(index.dtype) not in ("torch.int32", "torch.uint32") or not index.is_contiguous():
-                raise ValueError("a device index must be a contiguous int32 / uint32 tensor")
-            nidx = index.numel()
-        else:
-            if index.dtype != np.uint32:
-                raise ValueError("index must be uint32 (got %s)" % index.dtype)
-            index = np.ascontiguousarray(index).reshape(-1)
-            nidx = index.size
-        if not bufs.is_torch(scalars) and not isinstance(scalars, (np.ndarray, bytes, bytearray)):
-            srows = [list(r) if isinstance(r, (list, tuple)) else [r] for r in scalars]
-            if any(len(r) != terms for r in srows):
-                raise ValueError("scalars: every output needs %d scalars" % terms)
-            scalars = [v for r in srows for v in r]
-        k, nscalars = bufs.rows(_fr_in(scalars), SCALAR_BYTES, "scalars")
-        dev = bufs.device_of(index, k, out)
-        if nscalars % terms or nidx % terms:
-            raise ValueError("scalars and index need whole rows of %d" % terms)
-        n, nrows = nscalars // terms, nidx // terms
-        if n and not 1 <= nrows <= n:
-            raise ValueError("index needs between 1 and n = %d rows (got %d)" % (n, nrows))
-        if n * terms >> 32:
-            raise ValueError("n * terms must stay below 2^32")
-        out = bufs.output(out, (n, self.width), dev)
-        ok = bufs.output(None, (n,), dev, "ok")
-        if n:
-            if not self._h:
-                raise ValueError("the table is closed")
-            if _overlaps(out, index.view(np.uint8) if dev is None else None, k):
-                raise ValueError("out overlaps an input")
-            _call("fixed_base_indexed", dev, self._h, index, nrows, terms, k, n, out, ok)
-        return out, ok
+        return _indexed("fixed_base_indexed", self._h, self.width, index, scalars, terms, out, None)
 
     def close(self):
         if self._h:
             self._lib.gpbc_fixed_base_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class GTFixedBase:
+    """8-bit window tables of a fixed set of GT elements kept in HBM (include/gpbc_bn254_gtfixed.h, 4 MiB per base): afterwards a power
+    costs 32 Fp12 products and no squarings, where gt_exp on a replicated base does 252 squarings and 77 products.  Serves the blinding
+    factor of every Encrypt — e(g1, g2)^s (ibe/bb04_sibe/bb04_sibe.go:195-200), e(g1^alpha, g2)^t (ibe/bb04_ibe/bb04_ibe.go:181-189,
+    ibe/waters05_ibe/waters05_ibe.go:214), and Gentry06's v, w and y.  A base is any Fp12 element, as for gt_exp.
+
+        fb = GTFixedBase(bases)                  # bases: [nbase, 384] uint8 (numpy or CUDA tensor)
+        out = fb.pow(scalars, base=0)            # out[i] = bases[base] ^ scalars[i]                              -> [n, 384]
+        out, ok = fb.indexed(index, scalars)     # out[i] = prod_t bases[index[i % rows][t]] ^ scalars[i][t]      -> [n, 384], [n]
+
+    A table from a CUDA tensor is built on the current torch stream, and the constructor waits for that build."""
+
+    def __init__(self, bases):
+        self._lib = _lib.load()
+        self._h, self._rows = ctypes.c_void_p(), {}
+        dev = bufs.device_of(bases)
+        bases, self.nbase = bufs.rows(bases, GT_BYTES, "bases")
+        if not self.nbase:
+            raise ValueError("a table needs at least one base")
+        # called directly, as FixedBase does: the device form takes the stream before the handle
+        if dev is None:
+            _ensure_init()
+            _lib.check(self._lib.gpbc_gt_fixed_base_create(bufs.address(bases), self.nbase, ctypes.byref(self._h)))
+        else:
+            _bind(dev)
+            _lib.check(self._lib.gpbc_gt_fixed_base_create_dev(bufs.address(bases), self.nbase, _torch_stream(), ctypes.byref(self._h)))
+            _current_stream().synchronize()                      # `bases` may be released by the caller after this returns
+
+    def table_bytes(self):
+        return int(self._lib.gpbc_gt_fixed_base_table_bytes(self.nbase))
+
+    def pow(self, scalars, base=0, out=None):
+        """[n, 384]: out[i] = bases[base] ^ scalars[i], gnark's GT.Exp with the scalar as the integer it is (below 2^256).  scalars: n
+        ints or scalar rows, host or CUDA; the output is of their kind (the one index row is made here and put where they are)."""
+        if not isinstance(base, (int, np.integer)) or isinstance(base, bool) or not 0 <= int(base) < self.nbase:
+            raise ValueError("base must be in 0 .. %d (got %s)" % (self.nbase - 1, base))
+        key = (int(base), scalars.device if bufs.is_torch(scalars) else None)
+        row = self._rows.get(key)
+        if row is None:                                              # a device row travels once per table, not once per call
+            row = np.array([int(base)], dtype=np.uint32)
+            row = self._rows[key] = bufs.put(row.view(np.int32), scalars) if bufs.is_torch(scalars) else row
+        return self.indexed(row, scalars, terms=1, out=out)[0]
+
+    def indexed(self, index, scalars, terms=None, out=None, ok_out=None):
+        """(out [n, 384], ok [n]): out[i] = prod_{t < terms} bases[index[i % rows][t]] ^ scalars[i][t].  The arguments are those of
+        FixedBase.indexed: index as a uint32 array / CUDA tensor of the int32 or uint32 kind with `terms`, or a list of rows with None
+        (INDEX_NONE) for "no term" — a row of nothing else gives one; rows == n gives every output its own row, fewer rows repeat with that
+        period.  scalars: [n][terms] ints or n x terms scalar rows, any value below 2^256, used as they are.  1 <= terms <= 16.  An index
+        >= nbase other than INDEX_NONE gives an all-zero row and ok = 0.  CUDA tensors in give CUDA tensors out, enqueued on the
+        current stream and not synchronised."""
+        return _indexed("gt_fixed_base_indexed", self._h, GT_BYTES, index, scalars, terms, out, ok_out)
+
+    def close(self):
+        if self._h:
+            self._lib.gpbc_gt_fixed_base_destroy(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):

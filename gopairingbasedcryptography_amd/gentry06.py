@@ -21,6 +21,8 @@ Host orchestration only, engine-agnostic (every function takes the engine: `bn25
 randomness r / s comes in as arguments (scalar rows, or Python integers).  Host arrays in give host arrays out; CUDA tensors in give
 CUDA tensors out, every step takes device rows and leaves device rows, and nothing per item crosses PCIe but what the caller passes
 in and takes out (the shared points and pairings, and integer arguments, travel once)."""
+import numpy as np
+
 from . import _buffers as bufs, _plan
 
 
@@ -65,7 +67,7 @@ def public_pairings(engine, g1, g2, h):
     return e[0], e[1:]
 
 
-def encrypt_batch(engine, g1_alpha, e_gg, e_gh, messages, ids, s):
+def encrypt_batch(engine, g1_alpha, e_gg, e_gh, messages, ids, s, gt_table=None):
     """(u [n, 64], v [n, 384], w [n, 384]) and, for k = 3, y [n, 384], for n messages (GT elements, [n, 384]) to n identities (scalars)
     with the randomness s (n scalars).  g1_alpha: g1^alpha; e_gg, e_gh: public_pairings.  u by g1_scalar_mul of the one shared point,
     g1_scalar_mul_base and g1_add; v and e_gh[0]^(-s) by ONE gt_exp over 2 n rows, w by gt_mul; then beta on the device, s beta by
@@ -74,7 +76,12 @@ def encrypt_batch(engine, g1_alpha, e_gg, e_gh, messages, ids, s):
     y is two exponentiations — one gt_exp over the 2 n rows (e_gh[1], s), (e_gh[2], s beta) — and a gt_mul, not one gt_multi_exp of
     two-factor segments: gt_multi_exp walks a segment table, n + 1 offsets that would have to be copied to the device for every batch
     (or, made there, be validated with a read-back that stops the stream), and this planner lets nothing per item cross PCIe.  The
-    price is the 254 squarings of the second factor, which a shared walk would save."""
+    price is the 254 squarings of the second factor, which a shared walk would save.
+
+    gt_table: an engine.GTFixedBase over the 1 + k public pairings in the order e_gg, e_gh[0], ... (engine.GTFixedBase(cat([e_gg,
+    e_gh]))).  With it v and e_gh[0]^(-s) are gt_table.pow (32 products each, no squarings) and y is ONE gt_table.indexed with two
+    terms per item, the index row (2, 3) shared by all; the bytes are the same.  Without it (the default) the calls are the ones
+    above."""
     k = _k_of(bufs.nbytes(e_gh) // 384 if bufs.nbytes(e_gh) % 384 == 0 else 0, "e_gh")
     n = bufs.nbytes(messages) // 384
     if bufs.nbytes(messages) != n * 384:
@@ -85,14 +92,22 @@ def encrypt_batch(engine, g1_alpha, e_gg, e_gh, messages, ids, s):
     neg_s = engine.fr_neg(s)
     u = engine.g1_add(engine.g1_scalar_mul(bufs.flat(_plan.public(g1_alpha, 1, 64, messages, "g1_alpha")), s),
                       engine.g1_scalar_mul_base(engine.fr_mul(bufs.flat(neg_s), ids)))
-    vw = bufs.view(engine.gt_exp(bufs.cat([_repeat(e_gg, n, 1, 384), _repeat(e_gh[0], n, 1, 384)]), bufs.cat([s, bufs.flat(neg_s)])), 2, n, 384)
-    v = vw[0]
-    w = engine.gt_mul(bufs.flat(vw[1]), bufs.flat(messages))
+    if gt_table is None:
+        vw = bufs.view(engine.gt_exp(bufs.cat([_repeat(e_gg, n, 1, 384), _repeat(e_gh[0], n, 1, 384)]), bufs.cat([s, bufs.flat(neg_s)])), 2, n, 384)
+        v, w_mask = vw[0], vw[1]
+    else:
+        if gt_table.nbase != 1 + k:
+            raise ValueError("gt_table must hold e_gg and the %d e_gh, in that order (it holds %d bases)" % (k, gt_table.nbase))
+        v, w_mask = bufs.view(gt_table.pow(s, base=0), n, 384), gt_table.pow(bufs.flat(neg_s), base=1)
+    w = engine.gt_mul(bufs.flat(w_mask), bufs.flat(messages))
     out = bufs.view(u, n, 64), v, bufs.view(w, n, 384)
     if k == 1:
         return out
     beta = engine.hash_g1_gt_gt_to_fr(bufs.flat(u), bufs.flat(v), bufs.flat(w))
     s_beta = engine.fr_mul(s, bufs.flat(beta))
+    if gt_table is not None:
+        exps = bufs.flat(bufs.cat([bufs.view(s, n, 1, 32), bufs.view(s_beta, n, 1, 32)], 1))            # (s, s beta) per item
+        return out + (bufs.view(gt_table.indexed(_plan.index_rows(np.array([2, 3]), messages), exps, terms=2)[0], n, 384),)
     yy = bufs.view(engine.gt_exp(bufs.cat([_repeat(e_gh[1], n, 1, 384), _repeat(e_gh[2], n, 1, 384)]), bufs.cat([s, bufs.flat(s_beta)])), 2, n, 384)
     return out + (bufs.view(engine.gt_mul(bufs.flat(yy[0]), bufs.flat(yy[1])), n, 384),)
 

@@ -1470,3 +1470,42 @@ void hc_gt_is_in_subgroup(const uint8_t *Z, size_t n, uint8_t *ok, int force) {
     }
 }
 }
+
+// ------------------------------------------------------------------------------------------------ fixed-base exponentiation in GT
+#include "../gopairingbasedcryptography_amd/csrc/gtfixed29.hip.hpp"
+// jobs 0 .. n_jobs - 1, each a lane pair on two threads of its own, a few pairs side by side (the pairs share nothing but the statistics)
+template <class Job> static void gt_fb_pairs(size_t n_jobs, Job job) {
+    const size_t width = std::max<size_t>(1, std::min<size_t>(16, std::thread::hardware_concurrency() / 2));
+    for (size_t lo = 0; lo < n_jobs; lo += width) {
+        std::vector<PairRendezvous> rv(std::min(width, n_jobs - lo));
+        std::vector<std::thread> th;
+        for (size_t q = 0; q < rv.size(); q++)
+            for (int odd = 0; odd < 2; odd++)
+                th.emplace_back([&, q, odd] { job(PairHost{odd != 0, &rv[q]}, lo + q); stats_flush(); });
+        for (auto &t : th) t.join();
+    }
+}
+extern "C" {
+// the lane bodies of k_gt_fb_build and k_gt_fb_indexed (csrc/gpbc_gtfixed.hip) with the kernels' own addressing: table = nbase x 4 MiB of
+// int32 (gpbc_gt_fixed_base_table_bytes), one lane pair per (base, window) and per output.  In the build the pair is the wavefront, so
+// w_max is its own window.  -1: arguments the entry refuses.
+int hc_gt_fb_build(const uint8_t *B, size_t nbase, int32_t *table) {
+    if (!B || !nbase || !table) return -1;
+    gt_fb_pairs(nbase * GTFB_WINDOWS, [&](const PairHost &x, size_t q) {
+        const size_t j = q / GTFB_WINDOWS;
+        const int w = (int)(q % GTFB_WINDOWS);
+        gt_fb_build_lane(x, B + 384 * j + (x.odd ? 192 : 0), w, w, table + j * GTFB_BASE_DWORDS + (size_t)w * GTFB_WINDOW_DWORDS);
+    });
+    return 0;
+}
+int hc_gt_fb_indexed(const int32_t *table, size_t nbase, const uint32_t *index, size_t n_index_rows, size_t terms, const uint8_t *K, size_t n, uint8_t *out, uint8_t *ok_out) {
+    if (!table || !nbase || terms < 1 || terms > FBI_MAX_TERMS || n > (size_t)0xffffffffu / terms) return -1;
+    if (!n) return 0;
+    if (n_index_rows < 1 || n_index_rows > n || !index || !K || !out) return -1;
+    gt_fb_pairs(n, [&](const PairHost &x, size_t i) {
+        gt_fb_indexed_lane(x, table, nbase, index + (i % n_index_rows) * terms, (uint32_t)terms, K + 32 * i * terms, out + 384 * i + (x.odd ? 192 : 0), ok_out ? ok_out + i : nullptr,
+                           [](uint32_t *k, const uint8_t *p) { memcpy(k, p, 32); });
+    });
+    return 0;
+}
+}
