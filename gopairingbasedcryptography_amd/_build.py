@@ -4,7 +4,7 @@ Eleven translation units (csrc/gpbc_core.hip, gpbc_pairing.hip, gpbc_curve.hip, 
 gpbc_gmsm.hip, gpbc_subset.hip, gpbc_hash.hip) are compiled in parallel and
 linked into one shared library; every unit carries its own device code (no relocatable device code is needed: kernels are
 launched from the unit that defines them).  A twelfth, csrc/gpbc_member.hip, is listed beside them (MEMBER_SOURCES), and a thirteenth,
-csrc/gpbc_gtfixed.hip (GTFIXED_SOURCES)."""
+csrc/gpbc_gtfixed.hip (GTFIXED_SOURCES), and a fourteenth, csrc/gpbc_openings.hip (OPENINGS_SOURCES)."""
 import hashlib
 import os
 import shutil
@@ -29,8 +29,12 @@ ALL_UNITS = UNITS + MEMBER_SOURCES
 # the twelve above.  ALL_UNITS + GTFIXED_SOURCES is what is compiled, scanned and hashed.  (Why the kernels are not beside k_gt_exp in
 # gpbc_pairing.hip: the head of csrc/gpbc_gtfixed.hip.)
 GTFIXED_SOURCES = ["gpbc_gtfixed.hip"]
+# The fourteenth unit, the entries of include/gpbc_bn254_openings.h, in a list of its own for the same reason: tests/test_gt_fixed_base.py holds
+# the text ALL_UNITS + GTFIXED_SOURCES in the three functions below.  ALL_UNITS + GTFIXED_SOURCES + OPENINGS_SOURCES is what is compiled, scanned
+# and hashed.  (Why the kernels are not beside fb_msm_lane in gpbc_curve.hip: the head of csrc/gpbc_openings.hip.)
+OPENINGS_SOURCES = ["gpbc_openings.hip"]
 HEADERS = ["gpbc_common.hpp", "fe29.hip.hpp", "tower29.hip.hpp", "tower29_pair.hip.hpp", "curve29.hip.hpp", "pairing29.hip.hpp", "pairing29_pair.hip.hpp", "wide29.hip.hpp", "curve29_quad.hip.hpp", "curve29_oct.hip.hpp",
-           "wire29.hip.hpp", "h2c29.hip.hpp", "xmd29.hip.hpp", "msm29.hip.hpp", "group29.hip.hpp", "fr29.hip.hpp", "segred29.hip.hpp", "gtmexp29.hip.hpp", "gmsm29.hip.hpp", "subset29.hip.hpp", "transcript29.hip.hpp", "chacha29.hip.hpp", "share29.hip.hpp", "recon29.hip.hpp", "forest29.hip.hpp", "select29.hip.hpp", "formula29.hip.hpp", "fbindex29.hip.hpp", "lsss29.hip.hpp", "mask29.hip.hpp", "frdot29.hip.hpp", "member29.hip.hpp", "gtfixed29.hip.hpp", "bn254_constants.hip.hpp", "bn254_constants29.hip.hpp"]
+           "wire29.hip.hpp", "h2c29.hip.hpp", "xmd29.hip.hpp", "msm29.hip.hpp", "group29.hip.hpp", "fr29.hip.hpp", "segred29.hip.hpp", "gtmexp29.hip.hpp", "gmsm29.hip.hpp", "subset29.hip.hpp", "transcript29.hip.hpp", "chacha29.hip.hpp", "share29.hip.hpp", "recon29.hip.hpp", "forest29.hip.hpp", "select29.hip.hpp", "formula29.hip.hpp", "fbindex29.hip.hpp", "lsss29.hip.hpp", "mask29.hip.hpp", "frdot29.hip.hpp", "member29.hip.hpp", "gtfixed29.hip.hpp", "openings29.hip.hpp", "bn254_constants.hip.hpp", "bn254_constants29.hip.hpp"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
 # host-only measurement program over the C ABI (bench.py runs it: calls/s of concurrent one-element calls); built next to the library
 CALLS_SRC = os.path.join(HERE, "..", "tools", "concurrent_calls.cpp")
@@ -39,7 +43,7 @@ CALLS_EXE = os.path.join(HERE, "gpbc_concurrent_calls")
 
 def _source_hash():
     h = hashlib.sha256(" ".join(FLAGS).encode())
-    deps = [os.path.join(CSRC, f) for f in ALL_UNITS + GTFIXED_SOURCES + HEADERS] + [os.path.join(HERE, "..", "include", name) for name in ("gpbc_bn254.h", "gpbc_bn254_ext.h", "gpbc_bn254_subset.h", "gpbc_bn254_hash.h", "gpbc_bn254_share.h", "gpbc_bn254_indexed.h", "gpbc_bn254_recon.h", "gpbc_bn254_select.h", "gpbc_bn254_formula.h", "gpbc_bn254_random.h", "gpbc_bn254_forest.h", "gpbc_bn254_mask.h", "gpbc_bn254_verify.h", "gpbc_bn254_member.h", "gpbc_bn254_gtfixed.h")] + [CALLS_SRC]
+    deps = [os.path.join(CSRC, f) for f in ALL_UNITS + GTFIXED_SOURCES + OPENINGS_SOURCES + HEADERS] + [os.path.join(HERE, "..", "include", name) for name in ("gpbc_bn254.h", "gpbc_bn254_ext.h", "gpbc_bn254_subset.h", "gpbc_bn254_hash.h", "gpbc_bn254_share.h", "gpbc_bn254_indexed.h", "gpbc_bn254_recon.h", "gpbc_bn254_select.h", "gpbc_bn254_formula.h", "gpbc_bn254_random.h", "gpbc_bn254_forest.h", "gpbc_bn254_mask.h", "gpbc_bn254_verify.h", "gpbc_bn254_member.h", "gpbc_bn254_gtfixed.h", "gpbc_bn254_openings.h")] + [CALLS_SRC]
     for d in deps:
         with open(d, "rb") as f:
             h.update(f.read())
@@ -62,7 +66,7 @@ def _check_isa(tmp):
     import glob
     import re
     bad = []
-    for s in ALL_UNITS + GTFIXED_SOURCES:
+    for s in ALL_UNITS + GTFIXED_SOURCES + OPENINGS_SOURCES:
         unit = s.replace(".hip", "")
         files = glob.glob(os.path.join(tmp, unit, "*gfx950*.s"))
         if not files:                                   # a check that scanned nothing has checked nothing
@@ -83,7 +87,7 @@ def build_library(force=False, verbose=False):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     with tempfile.TemporaryDirectory(prefix="gpbc_build_") as tmp:
         procs = []
-        for s in ALL_UNITS + GTFIXED_SOURCES:
+        for s in ALL_UNITS + GTFIXED_SOURCES + OPENINGS_SOURCES:
             unit = os.path.join(tmp, s.replace(".hip", ""))
             os.makedirs(unit)
             obj = os.path.join(unit, s.replace(".hip", ".o"))

@@ -153,11 +153,17 @@ NEWER_TABLES = {
 # the last of its kind: the tests that came with it (tests/test_gt_fixed_base.py) hold their own table against its header and against
 # every other table, and count nothing, so the next header's table goes in here.  every_table() is the full list, and what load() declares.
 #   GTFIXED_SIGNATURES: include/gpbc_bn254_gtfixed.h, window tables of public GT elements and indexed products of their powers
+#   OPENINGS_SIGNATURES: include/gpbc_bn254_openings.h, batch polynomials over segments and opening proofs over fixed-base tables
+#   (tests/test_openings.py holds this table against that header, and disjoint from every other one)
 OPEN_TABLES = {
     "GTFIXED_SIGNATURES": {
         "gpbc_gtfixed_version": "i:", "gpbc_gt_fixed_base_table_bytes": "z:z", "gpbc_gt_fixed_base_create": "i:pzp",
         "gpbc_gt_fixed_base_create_dev": "i:pzpp", "gpbc_gt_fixed_base_destroy": "i:p", "gpbc_gt_fixed_base_indexed": "i:ppzzpzpp",
         "gpbc_gt_fixed_base_indexed_dev": "i:ppzzpzppp",
+    },
+    "OPENINGS_SIGNATURES": {
+        "gpbc_openings_version": "i:", "gpbc_fr_poly_from_roots_segments": "i:ppzzp", "gpbc_fr_poly_from_roots_segments_dev": "i:ppzzpp",
+        "gpbc_fixed_base_openings_workspace_bytes": "z:pz", "gpbc_fixed_base_openings": "i:ppppzpp", "gpbc_fixed_base_openings_dev": "i:ppppzpppzp",
     },
 }
 

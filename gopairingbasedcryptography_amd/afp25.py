@@ -190,3 +190,70 @@ def decrypt_batches(engine, table, ids, sk, C1, C2, D=None):
             raise ValueError("%s must hold one point per batch (%d) or per item (%d)" % (name, k, n))
         return bufs.expand(bufs.view(x, k, 1, 64), k, B, 64).reshape(n, 64)
     return decrypt_batch_arrays(engine, per_item(D, "D"), pi, per_item(sk, "sk"), C1, C2)
+
+
+# ----------------------------------------------------------------------------------------------- ragged batches, fused openings
+# The same again over batches of any length from 1 to B, as the reference's Digest takes them (afp25_bibe.go:293-305), on
+# engine.fr_poly_from_roots_segments and table.openings (include/gpbc_bn254_openings.h): the quotient's coefficients are made in the
+# lane that adds their terms, so there is no scratch buffer, no chunk loop and no flag read back.  The rule "the identity occurs
+# exactly once in its batch" (afp25_bibe.go:371-381) is decided on the device also for tensors: ok = 0 and an all-zero row, where
+# opening_proofs raises.  The functions above keep their behaviour.
+def _ragged(engine, table, ids, counts):
+    """(flat identity rows, counts): counts=None takes whole batches of B = table.nbase - 1 as _identity_rows does (without its host
+    check for duplicates: the device decides); otherwise ids holds sum(counts) identities, integers or scalar rows."""
+    B = table.nbase - 1
+    if B < 1:
+        raise ValueError("the SRS table needs at least two bases (g1 and [tau]_1)")
+    if not (bufs.is_torch(ids) or isinstance(ids, np.ndarray) and ids.dtype == np.uint8):
+        flat = [int(x) for r in ids for x in (r if isinstance(r, (list, tuple)) else (r,))]
+        ids = engine.fr_to_bytes(flat)
+    ids = ids.reshape(-1)
+    n = bufs.nbytes(ids) // 32
+    if bufs.nbytes(ids) != n * 32:
+        raise ValueError("ids must hold 32-byte scalars")
+    if counts is None:
+        if n == 0 or n % B:
+            raise ValueError("ids must hold a whole number of batches of B = %d identities" % B)
+        counts = [B] * (n // B)
+    counts = [int(c) for c in counts]
+    if not counts or any(c == 0 for c in counts):
+        raise ValueError("identities is empty")
+    if any(c < 0 or c > B for c in counts):
+        raise ValueError("too many identities for batch size")
+    if sum(counts) != n:
+        raise ValueError("ids must hold one scalar per identity of every batch (%d)" % sum(counts))
+    return ids, counts
+
+
+def digests_ragged(engine, table, ids, counts):
+    """D_j = [f_j(tau)]_1 for batches of counts[j] identities each: [k, 64] (Digest, afp25_bibe.go:293-305, with its two refusals)."""
+    ids, counts = _ragged(engine, table, ids, counts)
+    return table.msm(engine.fr_poly_from_roots_segments(ids, counts, table.nbase).reshape(-1))
+
+
+def opening_proofs_fused(engine, table, ids, counts=None):
+    """(pi [n, 64], ok [n]): pi[i] = [f_j(tau) / (tau - ids[i])]_1 for every identity i of every batch j, by ONE call of table.openings.
+    counts=None: whole batches of B, and then pi is opening_proofs' byte for byte wherever ok = 1.  ok[i] = 0 and an all-zero row where
+    the identity does not occur exactly once in its batch; nothing is read back here, so the caller decides when to look at ok."""
+    ids, counts = _ragged(engine, table, ids, counts)
+    return table.openings(ids, counts)
+
+
+def decrypt_batches_ragged(engine, table, ids, counts, sk, C1, C2, D=None):
+    """(messages [n, 384], ok [n]): decrypt_batches over batches of any length.  ids, counts: as opening_proofs_fused takes them; sk, D:
+    [k, 64] (one per batch) or [n, 64] (one per item); C1: [n, 3, 128]; C2: [n, 384].  Rows with ok = 0 come back all zero."""
+    ids, counts = _ragged(engine, table, ids, counts)
+    n, k = sum(counts), len(counts)
+    coeffs = engine.fr_poly_from_roots_segments(ids, counts, table.nbase)
+    if D is None:
+        D = table.msm(coeffs.reshape(-1))
+    pi, ok = table.openings(ids, counts, coeffs=coeffs.reshape(-1))
+    of_item = np.repeat(np.arange(k), counts)
+
+    def per_item(x, name):
+        if bufs.nbytes(x) not in (k * 64, n * 64):
+            raise ValueError("%s must hold one point per batch (%d) or per item (%d)" % (name, k, n))
+        x = bufs.view(_plan._placed(x, pi, name), -1, 64)
+        return x if x.shape[0] == n else bufs.take(x, of_item)
+    m = decrypt_batch_arrays(engine, per_item(D, "D"), pi, per_item(sk, "sk"), C1, C2)
+    return bufs.view(m, n, 384) * bufs.view(ok, n, 1), ok

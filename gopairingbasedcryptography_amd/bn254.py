@@ -580,6 +580,58 @@ def fr_poly_from_roots(roots, B=None, out=None):
     return out
 
 
+def _segment_counts(counts, n, longest, what):
+    """(seg_off [k + 1] uint64 on the host, k) of n elements cut into segments: counts a list of segment lengths that sum to n, or an
+    int B for whole batches of B.  No segment may be longer than `longest`."""
+    if isinstance(counts, (int, np.integer)) and not isinstance(counts, bool):
+        B = int(counts)
+        if B < 1 or n % B:
+            raise ValueError("%s: %d elements are not a whole number of batches of %s" % (what, n, counts))
+        lens = np.full(n // B, B, dtype=np.int64)
+    else:
+        try:
+            lens = np.array([int(c) for c in counts], dtype=np.int64).reshape(-1)
+        except (TypeError, ValueError, OverflowError):
+            raise ValueError("%s: counts is a list of segment lengths or one batch size" % what) from None
+    if lens.size >= 1 << 31:
+        raise ValueError("%s: too many segments for one call (%d)" % (what, lens.size))
+    if lens.size and (int(lens.min()) < 0 or int(lens.max()) > longest):
+        raise ValueError("%s: a segment holds between 0 and %d elements (got %d .. %d)" % (what, longest, int(lens.min()), int(lens.max())))
+    if int(lens.sum()) != n:
+        raise ValueError("%s: the segments hold %d elements, the buffer %d" % (what, int(lens.sum()), n))
+    seg = np.zeros(lens.size + 1, dtype=np.uint64)
+    np.cumsum(lens, out=seg[1:])
+    return seg, lens.size
+
+
+def _flat_scalars(v, what):
+    """(flat buffer, n) of a list of scalars: Python ints (flat, or a list of rows of any lengths), scalar rows as a uint8 array / bytes /
+    CUDA tensor"""
+    if not bufs.is_torch(v) and not isinstance(v, (np.ndarray, bytes, bytearray)):
+        v = [v] if isinstance(v, (int, np.integer)) else list(v)
+        v = [s for r in v for s in (r if isinstance(r, (list, tuple)) else (r,))]
+    return bufs.rows(_fr_in(v), SCALAR_BYTES, what)
+
+
+def fr_poly_from_roots_segments(roots, counts, stride, out=None):
+    """k polynomials prod_{i in segment j} (X - roots[i]) over segments of any length up to 1024 (include/gpbc_bn254_openings.h): row j of
+    the result [k, stride, 32] holds the m_j + 1 coefficients, constant term first, then zeros; an empty segment gives the polynomial 1.
+    roots: n Python ints, or n scalar rows as a uint8 array / CUDA tensor; counts: the k segment lengths, or an int B for whole batches of
+    B; stride: scalars per row, at least the longest segment + 1.  On full batches with stride = B + 1 the bytes are fr_poly_from_roots'."""
+    r, n = _flat_scalars(roots, "roots")
+    dev = bufs.device_of(r, out)
+    if not isinstance(stride, (int, np.integer)) or isinstance(stride, bool) or not 1 <= int(stride) <= 1 << 24:
+        raise ValueError("stride must be in 1 .. 2^24 (got %s)" % (stride,))
+    stride = int(stride)
+    seg, k = _segment_counts(counts, n, min(FR_POLY_MAX_B, stride - 1), "roots")
+    out = bufs.output(out, (k, stride, SCALAR_BYTES), dev)
+    if k:
+        if _overlaps(out, r):
+            raise ValueError("out overlaps the roots")
+        _call("fr_poly_from_roots_segments", dev, r, seg, k, stride, out)
+    return out
+
+
 def fr_poly_quotients(coeffs, points, B, stride=None, out=None, ok=None):
     """Row j*B + i of the result: the B coefficients of coeffs[j](X) / (X - points[j][i]) followed by stride - B zeros (stride
     defaults to B); ok[j*B + i] = 1 iff the division is exact, otherwise the row is all zero.  coeffs: k x (B + 1) scalars,
@@ -1768,6 +1820,37 @@ class FixedBase:
         >= nbase other than INDEX_NONE gives an all-zero row and ok = 0.  CUDA tensors in give CUDA tensors out, enqueued on the
         current stream and not synchronised."""
         return _indexed("fixed_base_indexed", self._h, self.width, index, scalars, terms, out, None)
+
+    def openings(self, ids, counts, coeffs=None, out=None, ok_out=None):
+        """(points [n, 64|128], ok [n]): the opening proofs of n identities in k batches against this table, whose base c stands for
+        [tau^c] (include/gpbc_bn254_openings.h): points[i] = [f_j(tau) / (tau - ids[i])] for identity i of batch j, f_j the product of
+        (X - id) over the batch; ok[i] = 1 iff the identity is a root of f_j exactly once (gwww25_bibe.go:214-223, afp25_bibe.go:371-381),
+        otherwise the row is all zero.  ids: n Python ints or scalar rows (uint8 array / CUDA tensor); counts: the k batch sizes, each at
+        most min(nbase - 1, 1024), or an int B for whole batches of B; coeffs: the f_j as fr_poly_from_roots_segments(ids, counts, nbase)
+        gives them (computed here when None).  CUDA tensors in give CUDA tensors out, enqueued on the current stream and not
+        synchronised: the workspace is a tensor of that stream, which the allocator hands on to later work of the same stream only."""
+        i, n = _flat_scalars(ids, "ids")
+        if coeffs is not None:
+            coeffs = _fr_in(coeffs)
+        dev = bufs.device_of(i, coeffs, out, ok_out)
+        seg, k = _segment_counts(counts, n, min(FR_POLY_MAX_B, self.nbase - 1), "ids")
+        if coeffs is not None:
+            coeffs, nc = bufs.rows(coeffs, SCALAR_BYTES, "coeffs")
+            if nc != k * self.nbase:
+                raise ValueError("coeffs holds %d scalars, expected %d rows of nbase = %d" % (nc, k, self.nbase))
+        out = bufs.output(out, (n, self.width), dev)
+        ok = bufs.output(ok_out, (n,), dev, "ok")
+        if not n:
+            return out, ok
+        if not self._h:
+            raise ValueError("the table is closed")
+        if _overlaps(out, i, coeffs) or (ok_out is not None and _overlaps(ok, i, coeffs, out)):
+            raise ValueError("out overlaps an input")
+        if coeffs is None:
+            coeffs = fr_poly_from_roots_segments(i, seg[1:] - seg[:-1], self.nbase).reshape(-1)
+        ws = () if dev is None else _workspace(None, int(self._lib.gpbc_fixed_base_openings_workspace_bytes(self._h, n)), dev)
+        _call("fixed_base_openings", dev, self._h, coeffs, i, seg, k, out, ok, *ws)
+        return out, ok
 
     def close(self):
         if self._h:

@@ -1509,3 +1509,138 @@ int hc_gt_fb_indexed(const int32_t *table, size_t nbase, const uint32_t *index, 
     return 0;
 }
 }
+
+// ------------------------------------------------------------------------------------------------ opening proofs over ragged batches
+#include "../gopairingbasedcryptography_amd/csrc/openings29.hip.hpp"
+// k_g1/g2_fb_openings as gpbc_fixed_base_openings_dev launches them: the blocks of the segment table (opn_blocks), one lane per (identity,
+// chunk of C bases) through fb_openings_lane with f's coefficients canonical as the staging leaves them, the partial sums chunk-major, then
+// the fan-in-16 levels of the strided point sum and the mask.  The window tables hold the rows the quotients reach (found by a first walk
+// of the same steps) and are kept from call to call while the bases stay the same.
+template <class F> struct OpnTables {
+    std::vector<uint8_t> bases;
+    std::vector<int32_t> mem;
+    std::vector<uint8_t> built;
+    int32_t *table = nullptr;
+};
+template <class F, class LoadA, class StoreA> static int fb_openings_host(const uint8_t *B, size_t nbase, const uint8_t *coeffs, const uint8_t *ids, const uint64_t *seg_off, size_t k, size_t C,
+                                                                          uint8_t *out, uint8_t *ok_out, size_t pt, LoadA ld, StoreA st) {
+    constexpr size_t ED = (size_t)TabLayout<F>::ENTRY_DWORDS;
+    static OpnTables<F> T;
+    if (T.bases.size() != nbase * pt || memcmp(T.bases.data(), B, nbase * pt)) {
+        T.bases.assign(B, B + nbase * pt);
+        T.mem.assign(nbase * (size_t)OPN_ENTRIES * ED + 32, 0);
+        T.built.assign(nbase * (size_t)OPN_ENTRIES, 0);
+        T.table = T.mem.data();
+        while ((uintptr_t)T.table & 127) T.table++;                // rows 128-byte aligned like the device's
+    }
+    std::vector<uint8_t> inf(nbase);
+    std::vector<AffP<F>> bases(nbase);
+    for (size_t b = 0; b < nbase; b++) { bases[b] = ld(B + pt * b); inf[b] = bases[b].inf ? 1 : 0; }
+    const size_t n = (size_t)seg_off[k], n_blocks = opn_blocks(seg_off, k, nullptr), n_chunks = (nbase + C - 1) / C;
+    std::vector<OpnBlock> blocks(n_blocks);
+    opn_blocks(seg_off, k, blocks.data());
+    std::vector<Fr> cs(nbase);
+    for (const OpnBlock &b : blocks) {                             // the rows the quotients of this block reach
+        for (uint32_t i = 0; i <= b.m; i++) cs[i] = fr_poly_coeff_in(coeffs + ((size_t)b.seg * nbase + i) * 32);
+        for (uint32_t lane = 0; lane < b.rows; lane++) {
+            const Fr point = fr_poly_point(ids + 32 * ((size_t)b.id0 + lane));
+            Fr carry = fr_zero();
+            for (uint32_t c = b.m; c-- > 0;) {
+                carry = fr_poly_horner_step(carry, cs[c + 1], point);
+                if (inf[c]) continue;
+                uint32_t kw[8]; fr_words(kw, carry);
+                for (int w = 0; w < OPN_WINDOWS; w++) {
+                    const int d = (int)((kw[w >> 2] >> (8 * (w & 3))) & 255u);
+                    const size_t e = ((size_t)c * OPN_WINDOWS + w) * OPN_DIGITS + d - 1;
+                    if (!d || T.built[e]) continue;
+                    uint32_t kk[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+                    kk[w >> 2] = (uint32_t)d << (8 * (w & 3));
+                    alignas(16) int32_t tab[glv_table_dwords<F>()];
+                    JacP<F> r; scalar_mul29_best(r, bases[c], kk, tab);
+                    AffP<F> a; jac_to_affine(a, r);
+                    tab_store(T.table + e * ED, 0, a);
+                    T.built[e] = 1;
+                }
+            }
+        }
+    }
+    std::vector<uint8_t> partial(n_chunks * n * pt + 64, 0xC3), flags(n + 16, 0xC3);
+    std::vector<uint8_t> seen(n_chunks * n, 0);
+    for (size_t wg = 0; wg < n_blocks * n_chunks; wg++) {          // the grid, chunk-major
+        const uint32_t chunk = (uint32_t)(wg / n_blocks);
+        const OpnBlock &b = blocks[wg % n_blocks];
+        const uint32_t c_lo = chunk * (uint32_t)C, c_hi = (size_t)c_lo + C < nbase ? c_lo + (uint32_t)C : (uint32_t)nbase;
+        if (c_lo < b.m)
+            for (uint32_t i = 0; i <= b.m; i++) cs[i] = fr_poly_coeff_in(coeffs + ((size_t)b.seg * nbase + i) * 32);
+        for (uint32_t lane = 0; lane < b.rows; lane++) {
+            const size_t i = (size_t)b.id0 + lane, slot = (size_t)chunk * n + i;
+            if (i >= n || seen[slot]) return -2;
+            seen[slot] = 1;
+            fb_openings_lane<F>(T.table, inf.data(), [&](uint32_t c) { return cs[c]; }, b.m, ids + 32 * i, c_lo, c_hi, C >= nbase, partial.data() + slot * pt, flags.data() + i, st);
+        }
+    }
+    for (size_t s = 0; s < n_chunks * n; s++) if (!seen[s]) return -2;
+    for (size_t g = n_chunks * n * pt; g < partial.size(); g++) if (partial[g] != 0xC3) return -3;
+    for (size_t g = n; g < flags.size(); g++) if (flags[g] != 0xC3) return -3;
+    std::vector<uint8_t> level;
+    for (size_t c = n_chunks; c > 1;) {                            // k_g1/g2_sum_level: out[t] = in[t] + in[t + n_out] + ...
+        const size_t c2 = (c + 15) / 16, n_in = c * n, n_out = c2 * n;
+        level.assign(n_out * pt, 0);
+        for (size_t t = 0; t < n_out; t++) {
+            JacP<F> acc; jac_set_inf(acc);
+            for (size_t i = t; i < n_in; i += n_out) jac_add_mixed(acc, acc, ld(partial.data() + i * pt));
+            AffP<F> r; jac_to_affine(r, acc);
+            st(level.data() + t * pt, r);
+        }
+        partial.swap(level); c = c2;
+    }
+    for (size_t i = 0; i < n; i++) {
+        if (n_chunks > 1 && !flags[i]) memset(out + i * pt, 0, pt); else memcpy(out + i * pt, partial.data() + i * pt, pt);
+        if (ok_out) ok_out[i] = flags[i];
+    }
+    return 0;
+}
+extern "C" {
+// -1: arguments the entries refuse.  k_fr_poly_from_roots_segments: the steps of hc_fr_poly_from_roots per segment, rows of `stride` scalars
+int hc_fr_poly_from_roots_segments(const uint8_t *roots, const uint64_t *seg_off, size_t k, size_t stride, uint8_t *coeffs_out) {
+    if (!seg_off || seg_off[0] != 0 || stride < 1 || stride > ((size_t)1 << 24) || !coeffs_out) return -1;
+    for (size_t j = 0; j < k; j++)
+        if (seg_off[j + 1] < seg_off[j] || seg_off[j + 1] - seg_off[j] > (uint64_t)FR_POLY_MAX_B || seg_off[j + 1] - seg_off[j] + 1 > stride) return -1;
+    if (seg_off[k] && !roots) return -1;
+    std::vector<Fr> cs(FR_POLY_MAX_B + 1), nw(FR_POLY_MAX_B + 1);
+    for (size_t j = 0; j < k; j++) {
+        const size_t lo = (size_t)seg_off[j], B = (size_t)(seg_off[j + 1] - seg_off[j]);
+        for (size_t i = 0; i <= B; i++) cs[i] = i ? fr_zero() : fr_plain_one();
+        for (size_t s = 0; s < B; s++) {
+            const Fr nr = fr_poly_neg_root(roots + (lo + s) * 32);
+            for (size_t i = 0; i <= s + 1; i++) nw[i] = fr_poly_root_step(i ? cs[i - 1] : fr_zero(), cs[i], nr);
+            for (size_t i = 0; i <= s + 1; i++) cs[i] = nw[i];
+        }
+        for (size_t i = 0; i <= B; i++) fr_poly_store(coeffs_out + (j * stride + i) * 32, cs[i]);
+        memset(coeffs_out + (j * stride + B + 1) * 32, 0, (stride - B - 1) * 32);
+    }
+    stats_flush();
+    return 0;
+}
+// C: bases per lane (the entry takes opn_shape's; here 1 .. nbase and beyond are walked); -2: a lane outside the grid's outputs or one
+// owned twice; -3: a write outside the partial sums or the flags
+int hc_fb_openings(int is_g2, const uint8_t *B, size_t nbase, const uint8_t *coeffs, const uint8_t *ids, const uint64_t *seg_off, size_t k, size_t C, uint8_t *out, uint8_t *ok_out) {
+    if (!B || !nbase || !seg_off || seg_off[0] != 0 || C < 1) return -1;
+    for (size_t j = 0; j < k; j++)
+        if (seg_off[j + 1] < seg_off[j] || seg_off[j + 1] - seg_off[j] > (uint64_t)FR_POLY_MAX_B || seg_off[j + 1] - seg_off[j] + 1 > nbase) return -1;
+    if (!k || !seg_off[k]) return 0;
+    if (!coeffs || !ids || !out) return -1;
+    int rc;
+    if (is_g2)
+        rc = fb_openings_host<F2>(B, nbase, coeffs, ids, seg_off, k, C, out, ok_out, 128,
+                                  [](const uint8_t *p) { return AffP<F2>{f2_load(p), f2_load(p + 64), bytes_all_zero(p, 32)}; },
+                                  [](uint8_t *p, const AffP<F2> &r) { f2_store(p, r.x); f2_store(p + 64, r.y); });
+    else
+        rc = fb_openings_host<Fe>(B, nbase, coeffs, ids, seg_off, k, C, out, ok_out, 64,
+                                  [](const uint8_t *p) { return AffP<Fe>{fe_load(p), fe_load(p + 32), bytes_all_zero(p, 16)}; },
+                                  [](uint8_t *p, const AffP<Fe> &r) { fe_store(p, r.x); fe_store(p + 32, r.y); });
+    stats_flush();
+    return rc;
+}
+void hc_opn_shape(size_t nbase, size_t n, size_t *out2) { opn_shape(nbase, n, out2, out2 + 1); }
+}
