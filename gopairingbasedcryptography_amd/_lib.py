@@ -10,8 +10,7 @@ LIB_PATH = os.environ.get("GPBC_LIB_PATH") or os.path.join(HERE, "libgpbc_bn254.
 # The C signatures of include/gpbc_bn254.h, in its order: symbol -> "return kind : one kind per parameter".
 #   p  pointer (any C type with a `*`)    z  size_t    i  int    l  long    s  const char * (a return only)
 # load() declares every restype and argtypes from this table, so a Python int reaches a size_t or pointer parameter at its full
-# width and a value of the wrong kind is an ArgumentError at the call, not a truncated argument.  tests/test_abi.py holds the
-# table against the header's prototypes.
+# width and a value of the wrong kind is an ArgumentError at the call, not a truncated argument.
 SIGNATURES = {
     "gpbc_init": "i:i", "gpbc_init_devices": "i:pi", "gpbc_num_devices": "i:", "gpbc_device_at": "i:i", "gpbc_set_device": "i:i",
     "gpbc_get_device": "i:", "gpbc_set_host_sharding": "i:i", "gpbc_shutdown": "i:", "gpbc_release_workspaces": "i:",
@@ -56,140 +55,94 @@ SIGNATURES = {
     "gpbc_profile_begin": "i:p", "gpbc_profile_end": "i:pppip", "gpbc_valu_probe": "i:p", "gpbc_fp_mul_batch": "i:ppzp",
 }
 EXPORTS = list(SIGNATURES)
-# The same for include/gpbc_bn254_ext.h, the entries added since the main header was frozen (tests/test_multi_scalar_mul.py holds
-# this table against that header).
+# include/gpbc_bn254_ext.h — the entries added since the main header was frozen
 EXT_SIGNATURES = {
     "gpbc_ext_version": "i:", "gpbc_g1_multi_scalar_mul": "i:ppzpzp", "gpbc_g2_multi_scalar_mul": "i:ppzpzp",
     "gpbc_multi_scalar_mul_workspace_bytes": "z:zzi", "gpbc_g1_multi_scalar_mul_dev": "i:ppzpzzppzp",
     "gpbc_g2_multi_scalar_mul_dev": "i:ppzpzzppzp", "gpbc_small_call_stats": "i:pppp",
 }
-# ... and for include/gpbc_bn254_subset.h, the bit-selected sums over a fixed set (tests/test_subset_sum.py holds this table against
-# that header).  The three tables are disjoint.
+# include/gpbc_bn254_subset.h — the bit-selected sums over a fixed set
 SUBSET_SIGNATURES = {
     "gpbc_subset_version": "i:", "gpbc_subset_table_bytes": "z:zi", "gpbc_g1_subset_table_create": "i:pzpp",
     "gpbc_g2_subset_table_create": "i:pzpp", "gpbc_subset_table_create_dev": "i:ipzppp", "gpbc_subset_sum": "i:ppzp",
     "gpbc_subset_sum_workspace_bytes": "z:pz", "gpbc_subset_sum_dev": "i:ppzppzp", "gpbc_subset_table_destroy": "i:p",
 }
-# ... and for include/gpbc_bn254_hash.h, SHA-256 on the device with the digest as bytes or as a scalar (tests/test_transcript_hash.py
-# holds this table against that header).  The four tables are disjoint.
+# include/gpbc_bn254_hash.h — SHA-256 on the device with the digest as bytes or as a scalar
 HASH_SIGNATURES = {
     "gpbc_hash_version": "i:", "gpbc_sha256_batch": "i:ppzip", "gpbc_sha256_batch_dev": "i:ppzzipp",
     "gpbc_hash_g1_gt_gt_to_fr": "i:pppzp", "gpbc_hash_g1_gt_gt_to_fr_dev": "i:pppzpp",
 }
-# ... and for include/gpbc_bn254_share.h, polynomial evaluation and the shares of a threshold tree in Fr (tests/test_fr_share.py holds
-# this table against that header).  The five tables are disjoint.
+# include/gpbc_bn254_share.h — polynomial evaluation and the shares of a threshold tree in Fr
 SHARE_SIGNATURES = {
     "gpbc_share_version": "i:", "gpbc_fr_poly_eval": "i:pzzpzzzp", "gpbc_fr_poly_eval_dev": "i:pzzpzzzpp",
     "gpbc_share_tree_create": "i:pzp", "gpbc_share_tree_destroy": "i:p", "gpbc_share_tree_leaves": "z:p",
     "gpbc_share_tree_coeffs": "z:p", "gpbc_fr_share_tree": "i:pppzp", "gpbc_fr_share_tree_dev": "i:pppzpp",
 }
-# ... and for include/gpbc_bn254_indexed.h, the indexed sums over fixed-base tables and LSSS share generation (tests/test_indexed_abi.py
-# holds this table against that header).  The six tables are disjoint.
+# include/gpbc_bn254_indexed.h — the indexed sums over fixed-base tables and LSSS share generation
 INDEXED_SIGNATURES = {
     "gpbc_indexed_version": "i:", "gpbc_fixed_base_indexed": "i:ppzzpzpp", "gpbc_fixed_base_indexed_dev": "i:ppzzpzppp",
     "gpbc_fr_lsss_shares": "i:pzzzpzp", "gpbc_fr_lsss_shares_dev": "i:pzzzpzpp",
 }
-# ... and for include/gpbc_bn254_recon.h, the reconstruction weights of a threshold tree (tests/test_fr_tree_weights.py holds this table
-# against that header).  The seven tables are disjoint.
+# include/gpbc_bn254_recon.h — the reconstruction weights of a threshold tree
 RECON_SIGNATURES = {
     "gpbc_recon_version": "i:", "gpbc_fr_tree_weights": "i:ppzpp", "gpbc_fr_tree_weights_dev": "i:ppzppp",
 }
-# ... and for include/gpbc_bn254_select.h, the common attributes of a list and a set (tests/test_fr_find_common.py holds this table
-# against that header).  The eight tables are disjoint.
+# include/gpbc_bn254_select.h — the common attributes of a list and a set
 SELECT_SIGNATURES = {
     "gpbc_select_version": "i:", "gpbc_fr_find_common": "i:pzzpzzzpppp", "gpbc_fr_find_common_dev": "i:pzzpzzzppppp",
 }
-# ... and for include/gpbc_bn254_formula.h, LSSS matrices and 0 / 1 weights from boolean formulas (tests/test_formula.py holds this table
-# against that header).  The nine tables are disjoint.
+# include/gpbc_bn254_formula.h — LSSS matrices and 0 / 1 weights from boolean formulas
 FORMULA_SIGNATURES = {
     "gpbc_formula_version": "i:", "gpbc_fr_lsss_from_formula": "i:pzzzzpppp", "gpbc_fr_lsss_from_formula_dev": "i:pzzzzppppp",
     "gpbc_formula_select": "i:pzzpzzpp", "gpbc_formula_select_dev": "i:pzzpzzppp",
 }
-# ... and for include/gpbc_bn254_random.h, ChaCha20 blocks and scalars addressed by (seed, stream, index) and the 64-byte reduction into
-# Fr (tests/test_random_abi.py holds this table against that header).  The ten tables are disjoint.
+# include/gpbc_bn254_random.h — ChaCha20 blocks and scalars addressed by (seed, stream, index) and the 64-byte reduction into Fr
 RANDOM_SIGNATURES = {
     "gpbc_random_version": "i:", "gpbc_random_bytes": "i:pzzzp", "gpbc_random_bytes_dev": "i:pzzzpp", "gpbc_fr_random": "i:pzzzp",
     "gpbc_fr_random_dev": "i:pzzzpp", "gpbc_fr_set_bytes64": "i:pzp", "gpbc_fr_set_bytes64_dev": "i:pzpp",
 }
-# ... and for include/gpbc_bn254_forest.h, sharing and weights over a forest of threshold trees, a tree per item (tests/test_fr_forest.py
-# holds this table against that header).  The eleven tables are disjoint.
+# include/gpbc_bn254_forest.h — sharing and weights over a forest of threshold trees, a tree per item
 FOREST_SIGNATURES = {
     "gpbc_forest_version": "i:", "gpbc_share_forest_create": "i:ppzp", "gpbc_share_forest_destroy": "i:p", "gpbc_share_forest_trees": "z:p",
     "gpbc_share_forest_leaves": "z:p", "gpbc_share_forest_coeffs": "z:p", "gpbc_share_forest_tree_leaves": "z:pz", "gpbc_share_forest_tree_coeffs": "z:pz",
     "gpbc_fr_share_forest": "i:ppppzpp", "gpbc_fr_share_forest_dev": "i:ppppzppp", "gpbc_fr_forest_weights": "i:pppzpp", "gpbc_fr_forest_weights_dev": "i:pppzppp",
 }
-# ... and for include/gpbc_bn254_mask.h, the XOR mask from GT bytes (tests/test_gt_xor_mask.py holds this table against that header).
-# The twelve tables up to here are disjoint.
+# include/gpbc_bn254_mask.h — the XOR mask from GT bytes
 MASK_SIGNATURES = {
     "gpbc_mask_version": "i:", "gpbc_gt_xor_mask": "i:pppzzpp", "gpbc_gt_xor_mask_dev": "i:pppzzzppp",
 }
-# Tables added after the twelfth, by the name they are reached under: _lib.VERIFY_SIGNATURES is LATER_TABLES["VERIFY_SIGNATURES"], through
-# the module's __getattr__ below.  They are kept out of the module's own names because tests/test_gt_xor_mask.py counts the names ending
-# in SIGNATURES at twelve, the state when the mask header came, and that file stays as it is; all_tables() is the full list.
-#   VERIFY_SIGNATURES: include/gpbc_bn254_verify.h, the sums in Fr and the verdicts in GT of batch verification
-#   (tests/test_fr_dot_segments.py holds this table against that header, and all thirteen tables disjoint).
-LATER_TABLES = {
-    "VERIFY_SIGNATURES": {
-        "gpbc_verify_version": "i:", "gpbc_fr_dot_segments": "i:ppzpzp", "gpbc_fr_dot_segments_workspace_bytes": "z:zz", "gpbc_fr_dot_segments_dev": "i:ppzpzzppzp",
-        "gpbc_gt_equal": "i:ppzzp", "gpbc_gt_equal_dev": "i:ppzzpp",
-    },
+# include/gpbc_bn254_verify.h — the sums in Fr and the verdicts in GT of batch verification
+VERIFY_SIGNATURES = {
+    "gpbc_verify_version": "i:", "gpbc_fr_dot_segments": "i:ppzpzp", "gpbc_fr_dot_segments_workspace_bytes": "z:zz", "gpbc_fr_dot_segments_dev": "i:ppzpzzppzp",
+    "gpbc_gt_equal": "i:ppzzp", "gpbc_gt_equal_dev": "i:ppzzpp",
 }
-# ... and the tables after the thirteenth, reached the same way (_lib.MEMBER_SIGNATURES).  They are kept out of LATER_TABLES because
-# tests/test_fr_dot_segments.py counts all_tables() at thirteen, the state when the verify header came, and that file stays as it is:
-# all_tables() is the list up to that header, tables() the full one.
-#   MEMBER_SIGNATURES: include/gpbc_bn254_member.h, IsOnCurve / IsInSubGroup on in-memory G1, G2 and GT elements
-#   (tests/test_membership.py holds this table against that header, and all fourteen tables disjoint).
-NEWER_TABLES = {
-    "MEMBER_SIGNATURES": {
-        "gpbc_member_version": "i:", "gpbc_g1_is_on_curve": "i:pzp", "gpbc_g1_is_on_curve_dev": "i:pzpp", "gpbc_g2_is_on_curve": "i:pzp",
-        "gpbc_g2_is_on_curve_dev": "i:pzpp", "gpbc_g2_is_in_subgroup": "i:pzp", "gpbc_g2_is_in_subgroup_dev": "i:pzpp",
-        "gpbc_gt_is_in_subgroup": "i:pzp", "gpbc_gt_is_in_subgroup_dev": "i:pzpp",
-    },
+# include/gpbc_bn254_member.h — IsOnCurve / IsInSubGroup on in-memory G1, G2 and GT elements
+MEMBER_SIGNATURES = {
+    "gpbc_member_version": "i:", "gpbc_g1_is_on_curve": "i:pzp", "gpbc_g1_is_on_curve_dev": "i:pzpp", "gpbc_g2_is_on_curve": "i:pzp",
+    "gpbc_g2_is_on_curve_dev": "i:pzpp", "gpbc_g2_is_in_subgroup": "i:pzp", "gpbc_g2_is_in_subgroup_dev": "i:pzpp",
+    "gpbc_gt_is_in_subgroup": "i:pzp", "gpbc_gt_is_in_subgroup_dev": "i:pzpp",
 }
-
-
-# ... and every table after the fourteenth, reached the same way (_lib.GTFIXED_SIGNATURES).  Kept out of NEWER_TABLES because
-# tests/test_membership.py counts tables() at fourteen, the state when the member header came, and that file stays as it is.  This dict is
-# the last of its kind: the tests that came with it (tests/test_gt_fixed_base.py) hold their own table against its header and against
-# every other table, and count nothing, so the next header's table goes in here.  every_table() is the full list, and what load() declares.
-#   GTFIXED_SIGNATURES: include/gpbc_bn254_gtfixed.h, window tables of public GT elements and indexed products of their powers
-#   OPENINGS_SIGNATURES: include/gpbc_bn254_openings.h, batch polynomials over segments and opening proofs over fixed-base tables
-#   (tests/test_openings.py holds this table against that header, and disjoint from every other one)
-OPEN_TABLES = {
-    "GTFIXED_SIGNATURES": {
-        "gpbc_gtfixed_version": "i:", "gpbc_gt_fixed_base_table_bytes": "z:z", "gpbc_gt_fixed_base_create": "i:pzp",
-        "gpbc_gt_fixed_base_create_dev": "i:pzpp", "gpbc_gt_fixed_base_destroy": "i:p", "gpbc_gt_fixed_base_indexed": "i:ppzzpzpp",
-        "gpbc_gt_fixed_base_indexed_dev": "i:ppzzpzppp",
-    },
-    "OPENINGS_SIGNATURES": {
-        "gpbc_openings_version": "i:", "gpbc_fr_poly_from_roots_segments": "i:ppzzp", "gpbc_fr_poly_from_roots_segments_dev": "i:ppzzpp",
-        "gpbc_fixed_base_openings_workspace_bytes": "z:pz", "gpbc_fixed_base_openings": "i:ppppzpp", "gpbc_fixed_base_openings_dev": "i:ppppzpppzp",
-    },
+# include/gpbc_bn254_gtfixed.h — window tables of public GT elements and indexed products of their powers
+GTFIXED_SIGNATURES = {
+    "gpbc_gtfixed_version": "i:", "gpbc_gt_fixed_base_table_bytes": "z:z", "gpbc_gt_fixed_base_create": "i:pzp",
+    "gpbc_gt_fixed_base_create_dev": "i:pzpp", "gpbc_gt_fixed_base_destroy": "i:p", "gpbc_gt_fixed_base_indexed": "i:ppzzpzpp",
+    "gpbc_gt_fixed_base_indexed_dev": "i:ppzzpzppp",
 }
-
-
-def __getattr__(name):
-    for later in (LATER_TABLES, NEWER_TABLES, OPEN_TABLES):
-        if name in later:
-            return later[name]
-    raise AttributeError("module %r has no attribute %r" % (__name__, name))
-
-
-def all_tables():
-    """{name: table} of the signature tables up to the verify header: the module's own names ending in SIGNATURES and LATER_TABLES"""
-    own = {k: v for k, v in globals().items() if k.endswith("SIGNATURES") and isinstance(v, dict)}
-    return {**own, **LATER_TABLES}
-
-
-def tables():
-    """{name: table} of the signature tables up to the member header: all_tables() and NEWER_TABLES"""
-    return {**all_tables(), **NEWER_TABLES}
-
-
-def every_table():
-    """{name: table} of every signature table: tables() and OPEN_TABLES"""
-    return {**tables(), **OPEN_TABLES}
-
+# include/gpbc_bn254_openings.h — batch polynomials over segments and opening proofs over fixed-base tables
+OPENINGS_SIGNATURES = {
+    "gpbc_openings_version": "i:", "gpbc_fr_poly_from_roots_segments": "i:ppzzp", "gpbc_fr_poly_from_roots_segments_dev": "i:ppzzpp",
+    "gpbc_fixed_base_openings_workspace_bytes": "z:pz", "gpbc_fixed_base_openings": "i:ppppzpp", "gpbc_fixed_base_openings_dev": "i:ppppzpppzp",
+}
+# Public header -> its table, in the order the headers were added.  load() declares every table here; a new header is one table above
+# and one line here.  tests/test_abi_tables.py holds each table against its header and their union against the library's exports.
+HEADERS = {
+    "gpbc_bn254.h": SIGNATURES, "gpbc_bn254_ext.h": EXT_SIGNATURES, "gpbc_bn254_subset.h": SUBSET_SIGNATURES,
+    "gpbc_bn254_hash.h": HASH_SIGNATURES, "gpbc_bn254_share.h": SHARE_SIGNATURES, "gpbc_bn254_indexed.h": INDEXED_SIGNATURES,
+    "gpbc_bn254_recon.h": RECON_SIGNATURES, "gpbc_bn254_select.h": SELECT_SIGNATURES, "gpbc_bn254_formula.h": FORMULA_SIGNATURES,
+    "gpbc_bn254_random.h": RANDOM_SIGNATURES, "gpbc_bn254_forest.h": FOREST_SIGNATURES, "gpbc_bn254_mask.h": MASK_SIGNATURES,
+    "gpbc_bn254_verify.h": VERIFY_SIGNATURES, "gpbc_bn254_member.h": MEMBER_SIGNATURES, "gpbc_bn254_gtfixed.h": GTFIXED_SIGNATURES,
+    "gpbc_bn254_openings.h": OPENINGS_SIGNATURES,
+}
 
 # every pointer is a c_void_p: it takes ints, None, c_void_p, ctypes arrays, byref() and ndarray.ctypes.data_as() alike
 _CTYPES = {"p": ctypes.c_void_p, "z": ctypes.c_size_t, "i": ctypes.c_int, "l": ctypes.c_long, "s": ctypes.c_char_p}
@@ -216,7 +169,7 @@ def load():
         except ImportError:
             pass
         lib = ctypes.CDLL(LIB_PATH)
-        for name, sig in [item for table in every_table().values() for item in table.items()]:
+        for name, sig in [item for table in HEADERS.values() for item in table.items()]:
             ret, params = sig.split(":")
             fn = getattr(lib, name)
             fn.restype = _CTYPES[ret]

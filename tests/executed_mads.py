@@ -5,25 +5,18 @@ what actually issues.  usage: python tests/executed_mads.py   (CPU only; lives u
 import ctypes
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 
+import bounds_harness
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))   # tests/ -> repo root
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
-SO = os.path.join(ROOT, "tools", "libgpbc_bounds.so")
 
 
 def harness():
-    src = os.path.join(ROOT, "tools", "bounds_check.cpp")
-    csrc = os.path.join(ROOT, "gopairingbasedcryptography_amd", "csrc")
-    deps = [src] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".hpp")]
-    if not os.path.exists(SO) or any(os.path.getmtime(f) > os.path.getmtime(SO) for f in deps):
-        subprocess.check_call(["g++", "-O2", "-pthread", "-std=c++17", "-DGPBC_BOUNDS", "-shared", "-fPIC", "-o", SO, src])
-    hc = ctypes.CDLL(SO)
-    hc.hc_mads_take.restype = ctypes.c_double
-    return hc
+    return bounds_harness.load()
 
 
 def count(hc=None, n=4):

@@ -16,10 +16,7 @@ at both ends.
 
 Run as a script it sends the cases and the ragged calls through the host-pointer entry in a process of its own bound to the device
 list given on the command line (a device may be listed twice, so one GPU still crosses the shard split, which cuts by whole segments)."""
-import ctypes
-import glob
 import os
-import subprocess
 import sys
 
 if __name__ == "__main__":
@@ -29,30 +26,17 @@ if __name__ == "__main__":
 import numpy as np  # noqa: E402
 
 import bn254_py as o  # noqa: E402
+import bounds_harness  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 R = o.R
 BYTES = {False: 64, True: 128}
 SUM_MIN, FILL = 8, 131072
-_HC = []
 
 
 def harness():
-    """tools/libgpbc_bounds.so (the device arithmetic as a host build with -DGPBC_BOUNDS), built when it is older than its sources"""
-    if not _HC:
-        so = os.path.join(ROOT, "tools", "libgpbc_bounds.so")
-        src = os.path.join(ROOT, "tools", "bounds_check.cpp")
-        hdrs = glob.glob(os.path.join(ROOT, "gopairingbasedcryptography_amd", "csrc", "*.hpp"))
-        if not os.path.exists(so) or any(os.path.getmtime(f) > os.path.getmtime(so) for f in [src] + hdrs):
-            subprocess.check_call(["g++", "-O2", "-pthread", "-std=c++17", "-DGPBC_BOUNDS", "-shared", "-fPIC", "-o", so, src])
-        lib = ctypes.CDLL(so)
-        VP, SZ = ctypes.c_void_p, ctypes.c_size_t
-        lib.hc_multi_scalar_mul.restype = None
-        lib.hc_multi_scalar_mul.argtypes = [ctypes.c_int, VP, VP, SZ, VP, SZ, SZ, VP]
-        lib.hc_gmsm_group.restype = ctypes.c_int
-        lib.hc_gmsm_group.argtypes = [ctypes.c_int]
-        _HC.append(lib)
-    return _HC[0]
+    """tools/libgpbc_bounds.so (the device arithmetic as a host build with -DGPBC_BOUNDS), through the one loader"""
+    return bounds_harness.load()
 
 
 def group(g2):

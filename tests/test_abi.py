@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+import abi_headers
 
 
 @pytest.fixture(scope="module")
@@ -17,9 +18,7 @@ def lib():
 
 
 def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "gpbc_bn254.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(gpbc_[a-z0-9_]+)\s*\(", text)))
+    return abi_headers.declared_symbols("gpbc_bn254.h")
 
 
 def test_header_symbols_exported(lib):
@@ -34,35 +33,12 @@ def test_python_binding_covers_header(lib):
     assert sorted(_lib.EXPORTS) == declared_symbols()
 
 
-def header_prototypes():
-    """{symbol: (return kind, [parameter kinds])} parsed from the header, in the kinds of _lib.SIGNATURES: p for any type with a `*`,
-    z size_t, l long, i int; s for the one `const char *` return"""
-    text = open(os.path.join(ROOT, "include", "gpbc_bn254.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-
-    def kind(decl, ret=False):
-        if "*" in decl:
-            assert not ret or re.fullmatch(r"\s*const\s+char\s*\*\s*", decl), decl
-            return "s" if ret else "p"
-        words = set(re.findall(r"[A-Za-z_]\w*", decl))
-        hits = [k for k, w in (("z", "size_t"), ("l", "long"), ("i", "int")) if w in words]
-        assert len(hits) == 1, decl
-        return hits[0]
-    protos = {}
-    for ret, name, params in re.findall(r"([A-Za-z_][\w \t\n\*]*?)\b(gpbc_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
-        assert name not in protos, name
-        params = " ".join(params.split())
-        protos[name] = (kind(ret, ret=True), [] if params in ("", "void") else [kind(p) for p in params.split(",")])
-    return protos
-
-
 def test_signature_table_is_the_header(lib):
     """Every prototype of the header, return and parameter by parameter, is what _lib.SIGNATURES declares, and load() has given
     every symbol its restype and argtypes from it: no call relies on ctypes' default of a 32-bit int."""
     import ctypes
     from gopairingbasedcryptography_amd import _lib
-    protos = header_prototypes()
+    protos = abi_headers.prototypes("gpbc_bn254.h")
     assert sorted(protos) == declared_symbols() == sorted(_lib.SIGNATURES) and len(protos) == 131
     ctype = {"p": ctypes.c_void_p, "z": ctypes.c_size_t, "i": ctypes.c_int, "l": ctypes.c_long, "s": ctypes.c_char_p}
     for name, (ret, params) in protos.items():

@@ -6,25 +6,13 @@ computes are the exact values the GPU computes, and are compared with the oracle
 (Verification harness only: the product has no CPU fallback and never loads this library.)"""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
-import pytest
 
 import bn254_py as o
 from conftest import ROOT, cat, load_golden
+from bounds_harness import hc  # noqa: F401  (the fixture)
 
-SO = os.path.join(ROOT, "tools", "libgpbc_bounds.so")
-
-
-@pytest.fixture(scope="module")
-def hc():
-    src = os.path.join(ROOT, "tools", "bounds_check.cpp")
-    import glob
-    hdrs = glob.glob(os.path.join(ROOT, "gopairingbasedcryptography_amd", "csrc", "*.hpp"))      # every header the harness can include
-    if not os.path.exists(SO) or any(os.path.getmtime(f) > os.path.getmtime(SO) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-pthread", "-std=c++17", "-DGPBC_BOUNDS", "-shared", "-fPIC", "-o", SO, src])
-    return ctypes.CDLL(SO)
 
 
 def vp(a):
@@ -309,7 +297,6 @@ def test_executed_mad_counts_file_is_current(hc):
     MADs the device code issues per pairing / scalar multiplication (tests/executed_mads.py regenerates it)."""
     import json
     import executed_mads
-    hc.hc_mads_take.restype = ctypes.c_double
     got = executed_mads.count(hc, n=4)                                       # the same four inputs the file was made from
     doc = json.load(open(os.path.join(ROOT, "profiles", "executed_mads.json")))
     for unit, want in doc["mads_per_unit"].items():

@@ -7,35 +7,18 @@ recursive restatement of tests/formula_cases.py on every case, exactly, with a g
 the two entries and FindLinearCombinationWeight (lw11.reconstruction_weights), formula.py against the same restatement, the new header
 against _lib.FORMULA_SIGNATURES, the build's dependency lists, and the argument checks that need no device."""
 import ctypes
-import glob
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+from bounds_harness import hc  # noqa: F401  (the fixture)
+import abi_headers
 import formula_cases as fc
 
-SO = os.path.join(ROOT, "tools", "libgpbc_bounds.so")
-VP, SZ = ctypes.c_void_p, ctypes.c_size_t
 GUARD = 0xA5
 BUILD, SELECT = fc.build_cases(), fc.select_cases()
-
-
-@pytest.fixture(scope="module")
-def hc():
-    src = os.path.join(ROOT, "tools", "bounds_check.cpp")
-    hdrs = glob.glob(os.path.join(ROOT, "gopairingbasedcryptography_amd", "csrc", "*.hpp"))
-    if not os.path.exists(SO) or any(os.path.getmtime(f) > os.path.getmtime(SO) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-pthread", "-std=c++17", "-DGPBC_BOUNDS", "-shared", "-fPIC", "-o", SO, src])
-    lib = ctypes.CDLL(SO)
-    lib.hc_fr_lsss_from_formula.restype = ctypes.c_int
-    lib.hc_fr_lsss_from_formula.argtypes = [VP, SZ, SZ, SZ, SZ, VP, VP, VP, VP, ctypes.c_int, VP]
-    lib.hc_formula_select.restype = ctypes.c_int
-    lib.hc_formula_select.argtypes = [VP, SZ, SZ, VP, SZ, SZ, VP, VP, VP]
-    return lib
 
 
 def aligned(n, shift=0):
@@ -264,26 +247,6 @@ def test_lsss_matrix_feeds_reconstruction_weights():
 
 
 # ------------------------------------------------------------------------------------------------ the header, the table, the build
-def formula_prototypes():
-    """{symbol: (return kind, [parameter kinds])} of include/gpbc_bn254_formula.h in the kinds of _lib.SIGNATURES"""
-    text = open(os.path.join(ROOT, "include", "gpbc_bn254_formula.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-
-    def kind(decl):
-        if "*" in decl:
-            return "p"
-        words = set(re.findall(r"[A-Za-z_]\w*", decl))
-        hits = [k for k, w in (("z", "size_t"), ("i", "int")) if w in words]
-        assert len(hits) == 1, decl
-        return hits[0]
-    protos = {}
-    for ret, name, params in re.findall(r"([A-Za-z_][\w \t\n\*]*?)\b(gpbc_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
-        assert name not in protos, name
-        params = " ".join(params.split())
-        protos[name] = (kind(ret), [] if params in ("", "void") else [kind(q) for q in params.split(",")])
-    return protos
-
-
 @pytest.fixture(scope="module")
 def lib():
     from gopairingbasedcryptography_amd import _build, _lib
@@ -293,12 +256,9 @@ def lib():
 
 def test_formula_signature_table_is_the_formula_header(lib):
     from gopairingbasedcryptography_amd import _lib
-    protos = formula_prototypes()
+    protos = abi_headers.prototypes("gpbc_bn254_formula.h")
     names = ["gpbc_formula_select", "gpbc_formula_select_dev", "gpbc_formula_version", "gpbc_fr_lsss_from_formula", "gpbc_fr_lsss_from_formula_dev"]
     assert sorted(protos) == sorted(_lib.FORMULA_SIGNATURES) == names
-    others = [_lib.SIGNATURES, _lib.EXT_SIGNATURES, _lib.SUBSET_SIGNATURES, _lib.HASH_SIGNATURES, _lib.SHARE_SIGNATURES, _lib.INDEXED_SIGNATURES, _lib.RECON_SIGNATURES,
-              _lib.SELECT_SIGNATURES]
-    assert not set(_lib.FORMULA_SIGNATURES) & (set().union(*others) | set(_lib.EXPORTS))
     ctype = {"p": ctypes.c_void_p, "z": ctypes.c_size_t, "i": ctypes.c_int}
     for name, (ret, params) in protos.items():
         assert _lib.FORMULA_SIGNATURES[name] == ret + ":" + "".join(params), name
@@ -312,10 +272,8 @@ def test_formula_signature_table_is_the_formula_header(lib):
 
 
 def test_build_lists_cover_the_new_header_and_lane_functions():
-    import inspect
     from gopairingbasedcryptography_amd import _build
-    assert "formula29.hip.hpp" in _build.HEADERS and "gpbc_bn254_formula.h" in inspect.getsource(_build._source_hash)
-    assert len(_build.UNITS) == 11 and not os.path.exists(os.path.join(_build.CSRC, "gpbc_formula.hip"))
+    assert "formula29.hip.hpp" in _build.HEADERS and not os.path.exists(os.path.join(_build.CSRC, "gpbc_formula.hip"))
     fr = open(os.path.join(_build.CSRC, "gpbc_fr.hip")).read()
     assert 'include "formula29.hip.hpp"' in fr and "k_fr_lsss_from_formula" in fr and "k_formula_select" in fr
     lane = open(os.path.join(_build.CSRC, "formula29.hip.hpp")).read()

@@ -12,35 +12,16 @@ makes afp25.quotient_by_root a valid stand-in for the reference's multiplied-out
 per root, so it runs for every root up to B = 257 and for every 64th root at B = 1024, while the device rows are compared with
 quotient_by_root for every root of every B."""
 import ctypes
-import glob
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from bounds_harness import hc  # noqa: F401  (the fixture)
 import fr_cases as fc
 from gopairingbasedcryptography_amd import afp25
 
-SO = os.path.join(ROOT, "tools", "libgpbc_bounds.so")
 VP, SZ = ctypes.c_void_p, ctypes.c_size_t
-
-
-@pytest.fixture(scope="module")
-def hc():
-    src = os.path.join(ROOT, "tools", "bounds_check.cpp")
-    hdrs = glob.glob(os.path.join(ROOT, "gopairingbasedcryptography_amd", "csrc", "*.hpp"))
-    if not os.path.exists(SO) or any(os.path.getmtime(f) > os.path.getmtime(SO) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-pthread", "-std=c++17", "-DGPBC_BOUNDS", "-shared", "-fPIC", "-o", SO, src])
-    lib = ctypes.CDLL(SO)
-    lib.hc_fr_op.restype = ctypes.c_int
-    lib.hc_fr_op.argtypes = [ctypes.c_int, VP, VP, SZ, SZ, VP, ctypes.c_int]
-    lib.hc_fr_poly_from_roots.restype = ctypes.c_int
-    lib.hc_fr_poly_from_roots.argtypes = [VP, SZ, SZ, VP]
-    lib.hc_fr_poly_quotients.restype = ctypes.c_int
-    lib.hc_fr_poly_quotients.argtypes = [VP, VP, SZ, SZ, SZ, VP, VP]
-    return lib
 
 
 def hc_op(hc, op, A, B=None, k=0, out=None):

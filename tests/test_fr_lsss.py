@@ -6,34 +6,16 @@ as it is made — geometry, staging into a checked stand-in for the LDS block, l
 Every product in that build asserts its int64 columns and every canonical form its input range, so a run that finishes is the
 overflow proof.  Then the wrapper's argument checks, the C entries' and the missing CPU fallback."""
 import ctypes
-import glob
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from bounds_harness import hc  # noqa: F401  (the fixture)
 import fr_cases as fc
 import fr_lsss_cases as lc
 
-SO = os.path.join(ROOT, "tools", "libgpbc_bounds.so")
 VP, SZ = ctypes.c_void_p, ctypes.c_size_t
 R = fc.R
-
-
-@pytest.fixture(scope="module")
-def hc():
-    src = os.path.join(ROOT, "tools", "bounds_check.cpp")
-    hdrs = glob.glob(os.path.join(ROOT, "gopairingbasedcryptography_amd", "csrc", "*.hpp"))
-    if not os.path.exists(SO) or any(os.path.getmtime(f) > os.path.getmtime(SO) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-pthread", "-std=c++17", "-DGPBC_BOUNDS", "-shared", "-fPIC", "-o", SO, src])
-    lib = ctypes.CDLL(SO)
-    lib.hc_fr_lsss_weights.restype = ctypes.c_int
-    lib.hc_fr_lsss_weights.argtypes = [VP, SZ, SZ, SZ, VP, SZ, VP, VP]
-    lib.hc_fr_lsss_launch.restype = ctypes.c_int
-    lib.hc_fr_lsss_launch.argtypes = [VP, SZ, SZ, SZ, VP, SZ, VP, VP, VP]
-    return lib
 
 
 def guarded(k, rows):

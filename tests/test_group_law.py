@@ -8,30 +8,14 @@ that finishes is also the overflow proof of the formulas.  Argument checks and t
 GPU: the same cases through the host and the device entries, in place included; a 2^20 algebraic check against the engine's
 scalar multiplication (independent of the new kernels); a ZSS04 verification and BSW07 key components kept in HBM."""
 import ctypes
-import glob
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import bn254_py as o  # noqa: F401
-from conftest import ROOT
+from bounds_harness import hc  # noqa: F401  (the fixture)
 from group_law_cases import ADD, DBL, GROUPS, OPS, SPECIALS, SUB, group_k, make_special, run_hc, special_batch
 
-SO = os.path.join(ROOT, "tools", "libgpbc_bounds.so")
-
-
-@pytest.fixture(scope="module")
-def hc():
-    src = os.path.join(ROOT, "tools", "bounds_check.cpp")
-    hdrs = glob.glob(os.path.join(ROOT, "gopairingbasedcryptography_amd", "csrc", "*.hpp"))
-    if not os.path.exists(SO) or any(os.path.getmtime(f) > os.path.getmtime(SO) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-pthread", "-std=c++17", "-DGPBC_BOUNDS", "-shared", "-fPIC", "-o", SO, src])
-    lib = ctypes.CDLL(SO)
-    lib.hc_group_op.restype = ctypes.c_int
-    lib.hc_group_op.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int]
-    return lib
 
 
 # ------------------------------------------------------------------------------------------------ CPU: the harness

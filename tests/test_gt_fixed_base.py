@@ -5,44 +5,28 @@
     columns and every normalisation its limbs, for the interval classes of the operands, and a violation aborts: a run that finishes is the
     limb-bound proof for the chain f12p_mul(output of f12p_mul, normalised table entry), for bases outside the cyclotomic subgroup and zero
     included;
-  * the header's prototypes against _lib.GTFIXED_SIGNATURES, that table loaded and disjoint from every other one (no totals are counted),
-    the version entries, the build lists;
+  * the header's prototypes against _lib.GTFIXED_SIGNATURES and that table loaded, the version entries, the build lists;
   * the argument errors of the C entries (decided before any device is touched, nothing written) and of the Python class."""
 import ctypes
-import glob
 import inspect
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+from bounds_harness import hc  # noqa: F401  (the fixture)
+import abi_headers
 import gt_fixed_cases as gc
 
-SO = os.path.join(ROOT, "tools", "libgpbc_bounds.so")
 HEADER = os.path.join(ROOT, "include", "gpbc_bn254_gtfixed.h")
-VP, SZ = ctypes.c_void_p, ctypes.c_size_t
+VP = ctypes.c_void_p
 GUARD = 0xA5
 NBASE = 4
 TABLE_DWORDS = 1 << 20                                                 # 4 MiB of int32 per base
 
 
 # ------------------------------------------------------------------------------------------------ the lane bodies
-@pytest.fixture(scope="module")
-def hc():
-    src = os.path.join(ROOT, "tools", "bounds_check.cpp")
-    hdrs = glob.glob(os.path.join(ROOT, "gopairingbasedcryptography_amd", "csrc", "*.hpp"))
-    if not os.path.exists(SO) or any(os.path.getmtime(f) > os.path.getmtime(SO) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-pthread", "-std=c++17", "-DGPBC_BOUNDS", "-shared", "-fPIC", "-o", SO, src])
-    lib = ctypes.CDLL(SO)
-    lib.hc_gt_fb_build.restype = lib.hc_gt_fb_indexed.restype = ctypes.c_int
-    lib.hc_gt_fb_build.argtypes = [VP, SZ, VP]
-    lib.hc_gt_fb_indexed.argtypes = [VP, SZ, VP, SZ, SZ, VP, SZ, VP, VP]
-    return lib
-
-
 @pytest.fixture(scope="module")
 def table(hc):
     """the tables of one, e(g1, g2), a Miller value and zero, built once by the build kernel's lane body, with guards behind them"""
@@ -122,45 +106,14 @@ def lib():
     return _lib.load()
 
 
-def prototypes():
-    """{symbol: (return kind, [parameter kinds])} of include/gpbc_bn254_gtfixed.h in the kinds of _lib.SIGNATURES"""
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-
-    def kind(decl, ret=False):
-        if "*" in decl:
-            assert not ret, decl
-            return "p"
-        words = set(re.findall(r"[A-Za-z_]\w*", decl))
-        hits = [k for k, w in (("z", "size_t"), ("l", "long"), ("i", "int")) if w in words]
-        assert len(hits) == 1, decl
-        return hits[0]
-    protos = {}
-    for ret, name, params in re.findall(r"([A-Za-z_][\w \t\n\*]*?)\b(gpbc_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
-        assert name not in protos, name
-        params = " ".join(params.split())
-        protos[name] = (kind(ret, ret=True), [] if params in ("", "void") else [kind(p) for p in params.split(",")])
-    return protos
-
-
 def test_signature_table_is_the_header_loaded_and_disjoint(lib):
-    """no totals: the new table is what the header declares, load() has declared it, and it shares no symbol with any other table"""
+    """the new table is what the header declares, and load() has declared it"""
     from gopairingbasedcryptography_amd import _lib
-    protos = prototypes()
+    protos = abi_headers.prototypes("gpbc_bn254_gtfixed.h")
     mine = _lib.GTFIXED_SIGNATURES
     assert sorted(protos) == sorted(mine) == sorted(
         ["gpbc_gtfixed_version", "gpbc_gt_fixed_base_table_bytes", "gpbc_gt_fixed_base_create", "gpbc_gt_fixed_base_create_dev", "gpbc_gt_fixed_base_destroy",
          "gpbc_gt_fixed_base_indexed", "gpbc_gt_fixed_base_indexed_dev"])
-    every = _lib.every_table()
-    assert every["GTFIXED_SIGNATURES"] is mine and "GTFIXED_SIGNATURES" not in _lib.tables()
-    assert set(_lib.tables()) < set(every) and all(every[name] is t for name, t in _lib.tables().items())
-    assert "every_table()" in inspect.getsource(_lib.load)
-    others = set()
-    for name, t in every.items():
-        if name != "GTFIXED_SIGNATURES":
-            others |= set(t)
-    assert others and not set(mine) & others
     ctype = {"p": ctypes.c_void_p, "z": ctypes.c_size_t, "i": ctypes.c_int}
     for name, (ret, params) in protos.items():
         assert mine[name] == ret + ":" + "".join(params), name
@@ -177,13 +130,9 @@ def test_signature_table_is_the_header_loaded_and_disjoint(lib):
 
 def test_build_lists_name_the_new_unit_and_headers():
     from gopairingbasedcryptography_amd import _build
-    assert _build.GTFIXED_SOURCES == ["gpbc_gtfixed.hip"] and "gpbc_gtfixed.hip" not in _build.ALL_UNITS
-    assert "gtfixed29.hip.hpp" in _build.HEADERS
-    for f in _build.GTFIXED_SOURCES + ["gtfixed29.hip.hpp"]:
+    assert "gpbc_gtfixed.hip" in _build.UNITS and "gtfixed29.hip.hpp" in _build.HEADERS
+    for f in ("gpbc_gtfixed.hip", "gtfixed29.hip.hpp"):
         assert os.path.exists(os.path.join(_build.CSRC, f))
-    for fn in (_build._source_hash, _build._check_isa, _build.build_library):
-        assert "ALL_UNITS + GTFIXED_SOURCES" in inspect.getsource(fn), fn.__name__
-    assert "gpbc_bn254_gtfixed.h" in inspect.getsource(_build._source_hash)
     unit = open(os.path.join(_build.CSRC, "gpbc_gtfixed.hip")).read()
     assert all(k in unit for k in ("k_gt_fb_build", "k_gt_fb_indexed", '#include "gtfixed29.hip.hpp"'))
     for older in ("gpbc_pairing.hip", "gpbc_gtmexp.hip"):

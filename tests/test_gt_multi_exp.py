@@ -7,30 +7,14 @@ to four times in a row with no squaring between, and folds products of products:
 columns and every table row its limb range, so a run that finishes is the overflow proof.  Then the wrapper's and the C entries'
 argument checks, which need no device."""
 import ctypes
-import glob
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from bounds_harness import hc  # noqa: F401  (the fixture)
 import gt_multi_exp_cases as gc
 
-SO = os.path.join(ROOT, "tools", "libgpbc_bounds.so")
 VP, SZ = ctypes.c_void_p, ctypes.c_size_t
-
-
-@pytest.fixture(scope="module")
-def hc():
-    src = os.path.join(ROOT, "tools", "bounds_check.cpp")
-    hdrs = glob.glob(os.path.join(ROOT, "gopairingbasedcryptography_amd", "csrc", "*.hpp"))
-    if not os.path.exists(SO) or any(os.path.getmtime(f) > os.path.getmtime(SO) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-pthread", "-std=c++17", "-DGPBC_BOUNDS", "-shared", "-fPIC", "-o", SO, src])
-    lib = ctypes.CDLL(SO)
-    lib.hc_gt_multi_exp_pair.restype = None
-    lib.hc_gt_multi_exp_pair.argtypes = [VP, VP, SZ, VP, SZ, SZ, VP]
-    return lib
 
 
 def hc_run(hc, x, k, seg):

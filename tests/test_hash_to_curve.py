@@ -2,26 +2,14 @@
 committed fixture, the host-side hashing of the product mirror (hash_to.py — plain hashlib, no GPU needed) against the
 oracle, and the DEVICE code of csrc/h2c29.hip.hpp compiled for the host under the bounds harness against the fixture and the map corpus of tests/wire_cases.py."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import bn254_py as o
-from conftest import ROOT, load_golden
+from conftest import load_golden
+from bounds_harness import hc  # noqa: F401  (the fixture)
 
-SO = os.path.join(ROOT, "tools", "libgpbc_bounds.so")
-
-
-@pytest.fixture(scope="module")
-def hc():
-    src = os.path.join(ROOT, "tools", "bounds_check.cpp")
-    hdrs = [os.path.join(ROOT, "gopairingbasedcryptography_amd", "csrc", f)
-            for f in ("fe29.hip.hpp", "tower29.hip.hpp", "curve29.hip.hpp", "wire29.hip.hpp", "h2c29.hip.hpp")]
-    if not os.path.exists(SO) or any(os.path.getmtime(f) > os.path.getmtime(SO) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-pthread", "-std=c++17", "-DGPBC_BOUNDS", "-shared", "-fPIC", "-o", SO, src])
-    return ctypes.CDLL(SO)
 
 
 def vp(a):

@@ -5,33 +5,15 @@ tests/indexed_cases.py: shares against Python integers, points against the oracl
 bases, exactly.  Every product in that build asserts its int64 columns for ANY input of its interval class and every canonical form
 its input range, so a run that finishes is the overflow proof of the accumulator's bound (the header comment of lsss29.hip.hpp)."""
 import ctypes
-import glob
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from bounds_harness import hc  # noqa: F401  (the fixture)
 import indexed_cases as ic
 
-SO = os.path.join(ROOT, "tools", "libgpbc_bounds.so")
-VP, SZ = ctypes.c_void_p, ctypes.c_size_t
+VP = ctypes.c_void_p
 R = ic.R
-
-
-@pytest.fixture(scope="module")
-def hc():
-    src = os.path.join(ROOT, "tools", "bounds_check.cpp")
-    hdrs = glob.glob(os.path.join(ROOT, "gopairingbasedcryptography_amd", "csrc", "*.hpp"))
-    if not os.path.exists(SO) or any(os.path.getmtime(f) > os.path.getmtime(SO) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-pthread", "-std=c++17", "-DGPBC_BOUNDS", "-shared", "-fPIC", "-o", SO, src])
-    lib = ctypes.CDLL(SO)
-    lib.hc_fr_lsss_shares.restype = ctypes.c_int
-    lib.hc_fr_lsss_shares.argtypes = [VP, SZ, SZ, SZ, VP, SZ, VP, VP]
-    lib.hc_fb_indexed.restype = ctypes.c_int
-    lib.hc_fb_indexed.argtypes = [ctypes.c_int, VP, SZ, VP, SZ, SZ, VP, SZ, SZ, VP, VP, VP]
-    return lib
 
 
 def run_shares(hc, case, geoms=None):

@@ -12,16 +12,15 @@
     gka/agka09/asbb.go:21-30 with three members, validation (masks, zero rows, ok = 0, a rejected element replaced by the neutral
     element before the sum), the empty group, verify_batch == verify_each."""
 import ctypes
-import glob
 import inspect
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+from bounds_harness import hc  # noqa: F401  (the fixture)
+import abi_headers
 import bn254_py as o
 import member_cases as mc
 from standin_engine import TensorEngine, recorded, tensors
@@ -29,29 +28,12 @@ from standin_member import MemberStandIn
 from gopairingbasedcryptography_amd import _plan, agka09
 from gopairingbasedcryptography_amd.rng import Randomness
 
-SO = os.path.join(ROOT, "tools", "libgpbc_bounds.so")
 HEADER = os.path.join(ROOT, "include", "gpbc_bn254_member.h")
-VP, SZ = ctypes.c_void_p, ctypes.c_size_t
 GUARD = 0xA5
 SEED = bytes(range(32))
 
 
 # ------------------------------------------------------------------------------------------------ the lane bodies
-@pytest.fixture(scope="module")
-def hc():
-    src = os.path.join(ROOT, "tools", "bounds_check.cpp")
-    hdrs = glob.glob(os.path.join(ROOT, "gopairingbasedcryptography_amd", "csrc", "*.hpp"))
-    if not os.path.exists(SO) or any(os.path.getmtime(f) > os.path.getmtime(SO) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-pthread", "-std=c++17", "-DGPBC_BOUNDS", "-shared", "-fPIC", "-o", SO, src])
-    lib = ctypes.CDLL(SO)
-    lib.hc_g1_is_on_curve.restype = None
-    lib.hc_g1_is_on_curve.argtypes = [VP, SZ, VP]
-    for fn in (lib.hc_g2_is_in_subgroup, lib.hc_gt_is_in_subgroup):
-        fn.restype = None
-        fn.argtypes = [VP, SZ, VP, ctypes.c_int]
-    return lib
-
-
 def verdicts(fn, corpus, *flag):
     ok = np.full(len(corpus) + 16, GUARD, dtype=np.uint8)
     fn(corpus.data.ctypes.data, len(corpus), ok.ctypes.data, *flag)
@@ -110,41 +92,11 @@ def lib():
     return _lib.load()
 
 
-def member_prototypes():
-    """{symbol: (return kind, [parameter kinds])} of include/gpbc_bn254_member.h in the kinds of _lib.SIGNATURES"""
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-
-    def kind(decl, ret=False):
-        if "*" in decl:
-            assert not ret, decl
-            return "p"
-        words = set(re.findall(r"[A-Za-z_]\w*", decl))
-        hits = [k for k, w in (("z", "size_t"), ("l", "long"), ("i", "int")) if w in words]
-        assert len(hits) == 1, decl
-        return hits[0]
-    protos = {}
-    for ret, name, params in re.findall(r"([A-Za-z_][\w \t\n\*]*?)\b(gpbc_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
-        assert name not in protos, name
-        params = " ".join(params.split())
-        protos[name] = (kind(ret, ret=True), [] if params in ("", "void") else [kind(p) for p in params.split(",")])
-    return protos
-
-
 def test_member_signature_table_is_the_member_header(lib):
     from gopairingbasedcryptography_amd import _lib
-    protos = member_prototypes()
+    protos = abi_headers.prototypes("gpbc_bn254_member.h")
     entries = ["gpbc_g1_is_on_curve", "gpbc_g2_is_on_curve", "gpbc_g2_is_in_subgroup", "gpbc_gt_is_in_subgroup"]
     assert sorted(protos) == sorted(_lib.MEMBER_SIGNATURES) == sorted(entries + [e + "_dev" for e in entries] + ["gpbc_member_version"])
-    tables = _lib.tables()
-    assert len(tables) == 14 and tables["MEMBER_SIGNATURES"] is _lib.MEMBER_SIGNATURES and len(_lib.all_tables()) == 13
-    others = set()
-    for name, table in tables.items():
-        if name != "MEMBER_SIGNATURES":
-            assert not others & set(table), name
-            others |= set(table)
-    assert others and not set(_lib.MEMBER_SIGNATURES) & others
     ctype = {"p": ctypes.c_void_p, "z": ctypes.c_size_t, "i": ctypes.c_int}
     for name, (ret, params) in protos.items():
         assert _lib.MEMBER_SIGNATURES[name] == ret + ":" + "".join(params), name
@@ -158,13 +110,11 @@ def test_member_signature_table_is_the_member_header(lib):
 
 
 def test_build_lists_cover_the_new_files_and_the_twelfth_unit():
-    """the membership kernels have a unit of their own, listed beside the eleven that the earlier tests hold; the pairing and the wire
-    unit, whose headers the lane bodies come from, do not know of them (csrc/gpbc_member.hip says why)"""
+    """the membership kernels have a unit of their own; the pairing and the wire unit, whose headers the lane bodies come from, do not
+    know of them (csrc/gpbc_member.hip says why)"""
     from gopairingbasedcryptography_amd import _build
     assert "member29.hip.hpp" in _build.HEADERS and os.path.exists(os.path.join(_build.CSRC, "member29.hip.hpp"))
-    assert "gpbc_bn254_member.h" in inspect.getsource(_build._source_hash) and "ALL_UNITS" in inspect.getsource(_build._source_hash)
-    assert len(_build.UNITS) == 11 and len(_build.SOURCES) == 10 and _build.ALL_UNITS == _build.UNITS + ["gpbc_member.hip"]
-    assert "ALL_UNITS" in inspect.getsource(_build._check_isa) and "ALL_UNITS" in inspect.getsource(_build.build_library)
+    assert "gpbc_member.hip" in _build.UNITS
     unit = open(os.path.join(_build.CSRC, "gpbc_member.hip")).read()
     assert all(k in unit for k in ("k_g1_is_on_curve", "k_g2_is_on_curve", "k_g2_is_in_subgroup", "k_gt_is_in_subgroup", '#include "member29.hip.hpp"'))
     for older in ("gpbc_pairing.hip", "gpbc_wire.hip"):

@@ -14,22 +14,13 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from bounds_harness import hc  # noqa: F401  (the fixture)
+import abi_headers
 import gmsm_cases as gc
 
-VP, SZ = ctypes.c_void_p, ctypes.c_size_t
+VP = ctypes.c_void_p
 GROUPS = [False, True]
 IDS = ["g1", "g2"]
-
-
-@pytest.fixture(scope="module")
-def hc():
-    lib = gc.harness()
-    for name in ("hc_g1_mul", "hc_g2_mul"):
-        getattr(lib, name).restype = None
-        getattr(lib, name).argtypes = [VP, VP, SZ, VP]
-    lib.hc_glv_split.restype = lib.hc_gls_split.restype = None
-    lib.hc_glv_split.argtypes = lib.hc_gls_split.argtypes = [VP, SZ, VP]
-    return lib
 
 
 def hc_run(hc, g2, x, k, seg):
@@ -121,7 +112,6 @@ def test_bound_margins_after_multi_scalar_mul(hc):
     G = gc.group(False)
     hc_run(hc, False, gc.take(p["pt"], 2 * G + 1), gc.rand_scalars("bm", 2 * G + 1), [0, 2 * G + 1])
     st = np.zeros(7)
-    hc.hc_stats.restype = None
     hc.hc_stats(st.ctypes.data_as(VP))
     assert 0 < st[0] < 2.0**63 and st[1] < 2.0**31
 
@@ -134,36 +124,12 @@ def lib():
     return _lib.load()
 
 
-def ext_prototypes():
-    """{symbol: (return kind, [parameter kinds])} of include/gpbc_bn254_ext.h in the kinds of _lib.SIGNATURES, parsed the way
-    test_abi.py parses the main header"""
-    text = open(os.path.join(ROOT, "include", "gpbc_bn254_ext.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-
-    def kind(decl, ret=False):
-        if "*" in decl:
-            assert not ret, decl
-            return "p"
-        words = set(re.findall(r"[A-Za-z_]\w*", decl))
-        hits = [k for k, w in (("z", "size_t"), ("l", "long"), ("i", "int")) if w in words]
-        assert len(hits) == 1, decl
-        return hits[0]
-    protos = {}
-    for ret, name, params in re.findall(r"([A-Za-z_][\w \t\n\*]*?)\b(gpbc_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
-        assert name not in protos, name
-        params = " ".join(params.split())
-        protos[name] = (kind(ret, ret=True), [] if params in ("", "void") else [kind(p) for p in params.split(",")])
-    return protos
-
-
 def test_ext_signature_table_is_the_extension_header(lib):
     """every prototype of the extension header is what _lib.EXT_SIGNATURES declares, load() has set restype and argtypes from it,
     and the main table does not hold the new names (it mirrors the main header alone)"""
     from gopairingbasedcryptography_amd import _lib
-    protos = ext_prototypes()
+    protos = abi_headers.prototypes("gpbc_bn254_ext.h")
     assert sorted(protos) == sorted(_lib.EXT_SIGNATURES) and len(protos) == 7
-    assert not set(_lib.EXT_SIGNATURES) & set(_lib.SIGNATURES) and not set(_lib.EXT_SIGNATURES) & set(_lib.EXPORTS)
     ctype = {"p": ctypes.c_void_p, "z": ctypes.c_size_t, "i": ctypes.c_int}
     for name, (ret, params) in protos.items():
         assert _lib.EXT_SIGNATURES[name] == ret + ":" + "".join(params), name
@@ -180,7 +146,7 @@ def test_small_call_stats_symbol_and_signature(lib):
     text = re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "gpbc_bn254_ext.h")).read())
     assert ("int gpbc_small_call_stats(uint64_t *batches_out, uint64_t *calls_out, uint64_t *largest_batch_out, "
             "uint64_t *failed_in_shared_batches_out);") in text
-    assert _lib.EXT_SIGNATURES["gpbc_small_call_stats"] == "i:pppp" and ext_prototypes()["gpbc_small_call_stats"] == ("i", ["p"] * 4)
+    assert _lib.EXT_SIGNATURES["gpbc_small_call_stats"] == "i:pppp" and abi_headers.prototypes("gpbc_bn254_ext.h")["gpbc_small_call_stats"] == ("i", ["p"] * 4)
     fn = lib.gpbc_small_call_stats
     assert fn.restype is ctypes.c_int and list(fn.argtypes) == [ctypes.c_void_p] * 4
     v = [ctypes.c_uint64(1 << 63) for _ in range(4)]

