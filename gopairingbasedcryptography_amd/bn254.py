@@ -330,19 +330,36 @@ def _scalar_mul(group, width, bases, scalars, out):
     scalars = scalars_to_bytes(scalars)
     dev = bufs.device_of(bases, scalars)
     (bases, nbase), (scalars, n) = bufs.rows(bases, width, "bases"), bufs.rows(scalars, SCALAR_BYTES, "scalars")
-    if nbase not in (1, n):
-        raise ValueError("need one base or one base per scalar")
+    if nbase not in (1, n) and (nbase < 1 or nbase > n or n % nbase):
+        raise ValueError("need one base, one base per scalar, or one base per row of n / nbase scalars (got %d bases for %d scalars)" % (nbase, n))
     out = bufs.output(out, (n, width), dev)
     _call(group + "_scalar_mul_batch", dev, bases, nbase, scalars, n, out)
     return out
 
 
+# The row form of g1 / g2_scalar_mul as csrc/rows29.hip.hpp lays it out (tests and tools/scalar_mul_rows_bench.py derive their shapes
+# from these; tests/test_scalar_mul_rows.py holds them against the header): G1 rows of ROWS_TABLE_MIN .. ROWS_TABLE_MAX - 1 scalars get
+# a window table of ROWS_TABLE_BYTES per base, built for a pass of at most rows_pass_bases(nbase, m) bases at a time; the window bases
+# the tables grow from are made for up to ROWS_GROUP_BASES bases ahead of their passes.
+ROWS_TABLE_MIN, ROWS_TABLE_MAX, ROWS_TABLE_BYTES, ROWS_PASS_OUTPUTS, ROWS_TABLE_CAP, ROWS_GROUP_BASES = 32, 16384, 61440, 1 << 18, 1 << 30, 1 << 16
+
+
+def rows_pass_bases(nbase, m):
+    """bases per pass of the G1 row tables for nbase bases of m scalars each (csrc/rows29.hip.hpp: rows_pass_bases)"""
+    return min(nbase, max(1, min(ROWS_PASS_OUTPUTS // m, ROWS_TABLE_CAP // ROWS_TABLE_BYTES)))
+
+
 def g1_scalar_mul(bases, scalars, out=None):
-    """out[i] = new(G1Affine).ScalarMultiplication(&bases[i], scalars[i]) (one shared base allowed)."""
+    """out[i] = new(G1Affine).ScalarMultiplication(&bases[i], scalars[i]): one base per scalar, ONE shared base, or — the row form —
+    nbase bases for n = nbase * m scalars, row-major: out[j * m + i] = [scalars[j * m + i]] bases[j], a base with its own row of m
+    scalars (the authority secrets against one user's H(GID)).  The bytes are those of the call on the bases repeated m times.  Any
+    other count of bases is a ValueError.  numpy arrays in, numpy array out; CUDA tensors in, CUDA tensor out, enqueued on the
+    current torch stream."""
     return _scalar_mul("g1", G1_BYTES, bases, scalars, out)
 
 
 def g2_scalar_mul(bases, scalars, out=None):
+    """g1_scalar_mul in G2, the row form (out[j * m + i] = [scalars[j * m + i]] bases[j]) included."""
     return _scalar_mul("g2", G2_BYTES, bases, scalars, out)
 
 

@@ -125,6 +125,9 @@ int msm_dev(bool g2, const void *d_bases, const void *d_scalars, size_t n, void 
 // One level of the point-sum tree (gpbc_curve.hip): out[t] = in[t] + in[t + n_out] + ... over n_in affine points, t < n_out; asynchronous
 // on `st`.  Folds chunk-major partial sums (partial[c * n + m], n_out = n) in one launch.
 int point_sum_strided_dev(bool g2, const void *d_in, size_t n_in, void *d_out, size_t n_out, hipStream_t st);
+// The row form of the scalar multiplications (gpbc_rows.hip): out[j m + i] = [scalars[j m + i]] bases[j] for nbase bases and m scalars a
+// base; asynchronous on `st`.  G1 rows of fewer than table_max scalars may take the per-base row tables of csrc/rows29.hip.hpp.
+int scalar_mul_rows_dev(bool g2, const void *d_bases, size_t nbase, const void *d_scalars, size_t m, void *d_out, size_t table_max, hipStream_t st);
 // RCCL communicator of the current device (gpbc_core.hip): number of ranks (0 = none), this device's rank, all-gather
 int comm_ranks();
 int comm_rank();

@@ -262,9 +262,21 @@ static int shared_base_mul_dev(bool g2, const void *d_base, const void *d_scalar
 static int scalar_mul_dev(bool g2, const void *d_bases, size_t nbase, const void *d_scalars, size_t n, void *d_out, void *stream) {
     if (!n) return GPBC_OK;
     if (!d_bases || !d_scalars || !d_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    if (nbase != 1 && nbase != n) return fail(GPBC_ERR_INVALID_ARG, "nbase must be 1 or n");
+    if (!nbase || nbase > n || n % nbase) return fail(GPBC_ERR_INVALID_ARG, "nbase must be 1, n or a divisor of n (one base per row of n / nbase scalars)");
     TRY(bind_device());
     static_assert(SMUL_K == 1, "the table workspace is laid out for one point per lane");
+    if (nbase != 1 && nbase != n) {
+        // One base per ROW of m scalars.  Long rows go row by row through the transient 8-bit table below; the other rows, and what is
+        // left when that table's memory cannot be had, through gpbc_rows.hip.  Same canonical affine results on every route.
+        const size_t m = n / nbase, pt = g2 ? GPBC_G2_BYTES : GPBC_G1_BYTES;
+        size_t j = 0;
+        for (; m >= FB_AUTO_MIN && j < nbase; j++) {
+            const int rc = shared_base_mul_dev(g2, (const uint8_t *)d_bases + j * pt, (const uint8_t *)d_scalars + j * m * GPBC_SCALAR_BYTES, m, (uint8_t *)d_out + j * m * pt, (hipStream_t)stream);
+            if (rc == GPBC_ERR_WORKSPACE) break;
+            TRY(rc);
+        }
+        return scalar_mul_rows_dev(g2, (const uint8_t *)d_bases + j * pt, nbase - j, (const uint8_t *)d_scalars + j * m * GPBC_SCALAR_BYTES, m, (uint8_t *)d_out + j * m * pt, FB_AUTO_MIN, (hipStream_t)stream);
+    }
     if (nbase == 1 && n >= FB_AUTO_MIN) {
         // One base for a large batch (ScalarMultiplicationBase-style calls): a transient fixed-base window table (8 160 rows,
         // ~0.1 ms to build) turns every multiplication into 32 mixed additions.  Same canonical affine results.
@@ -342,8 +354,13 @@ constexpr size_t SMUL_SHARD_MIN = 4096;
 static int scalar_mul_host(bool g2, const void *bases, size_t nbase, const void *scalars, size_t n, void *out) {
     if (!n) return GPBC_OK;
     if (!bases || !scalars || !out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    if (nbase != 1 && nbase != n) return fail(GPBC_ERR_INVALID_ARG, "nbase must be 1 or n");
+    if (!nbase || nbase > n || n % nbase) return fail(GPBC_ERR_INVALID_ARG, "nbase must be 1, n or a divisor of n (one base per row of n / nbase scalars)");
     const size_t pt = g2 ? GPBC_G2_BYTES : GPBC_G1_BYTES;
+    if (nbase != 1 && nbase != n)
+        // the row form: ONE call of one unit, the three arrays whole columns, staged through the device blocks on the calling thread's
+        // current device — not sharded over the bound devices (a row's base and its scalars belong together) and not combined
+        return host_call(1, HostCall().input(bases, nbase * pt, true).input(scalars, n * GPBC_SCALAR_BYTES, true).output(out, n * pt), HostRoute{},
+                         [=](const DevCols &d, size_t, hipStream_t st) { return scalar_mul_dev(g2, d.in[0], nbase, d.in[1], n, d.out[0], st); });
     const bool shared = nbase == 1 && n != 1;
     return host_call_sharded(n, SMUL_SHARD_MIN, HostCall().input(bases, pt, shared).input(scalars, GPBC_SCALAR_BYTES).output(out, pt),
                              HostRoute{g2 ? CALL_G2_MUL : CALL_G1_MUL, small_mul_run, SMALL_CALL_MAX_UNITS, 0, shared ? 0 : SMUL_PIPE_CHUNK},

@@ -25,6 +25,10 @@ and it indexes the compacted weight slice by the matrix row number (lw11_dabe.go
 record both).  The two agree when every weight is 1 — the solution that Lewko-Waters matrices of AND / OR formulas have — and this
 planner follows the scheme, not the loop, just as bsw07.py drops the reference's debug pairing.
 
+The other end of the scheme is here too: authority_setup (the public keys of an authority's attributes), keygen_batch (the keys of U
+users over A attributes: one H(GID) per user raised to the row of the authority's y_i, the row form of engine.g1_scalar_mul) and
+encrypt_batch, each with a *_seeded form where it draws randomness.
+
 Host orchestration only, engine-agnostic (every function takes the engine: `bn254`, or a stand-in with the same function names):
 the elimination is per policy, microseconds in Python integers, and stays on the host."""
 import numpy as np
@@ -128,6 +132,82 @@ def decrypt_batch_msm(engine, folded, h_gid, c0, c1, c2, c3):
     E = engine.multi_pair(bufs.flat(P), bufs.flat(Q), _plan.segments(n, k + 1))
     F = engine.gt_multi_exp(bufs.flat(used(c1, 384)), weights, table)
     return engine.gt_div(bufs.flat(c0).reshape(n, 384), engine.gt_mul(E, F))
+
+
+# ------------------------------------------------------------------------------------------------ AuthoritySetup, KeyGenerate
+def _secrets(alpha, y):
+    """(alpha, y, A): an authority's secrets as flat scalar buffers of one kind — that of whichever is a buffer, host arrays otherwise"""
+    like = next((x for x in (alpha, y) if _plan.is_buffer(x)), np.zeros(0, dtype=np.uint8))
+    alpha, y = _plan.scalars(alpha, like), _plan.scalars(y, like)
+    bufs.device_of(alpha, y)
+    A = bufs.nbytes(alpha) // 32
+    if bufs.nbytes(alpha) != A * 32 or bufs.nbytes(y) != A * 32:
+        raise ValueError("alpha and y must hold one 32-byte scalar per attribute each (got %d and %d bytes)" % (bufs.nbytes(alpha), bufs.nbytes(y)))
+    return bufs.flat(alpha), bufs.flat(y), A
+
+
+def authority_setup(engine, e, alpha, y, gt_table=None):
+    """The public keys of A attributes from their secrets (AuthoritySetup, dabe/lw11_dabe.go:63-88): (egg_alpha [A, 384], g2_y [A, 128])
+    with egg_alpha_i = e(g1, g2)^alpha_i and g2_y_i = [y_i] g2.  e = e(g1, g2) (384 B); alpha, y: A scalars each, Python ints, uint8
+    arrays or CUDA tensors (the outputs are of their kind).  gt_table: an engine.GTFixedBase whose base 0 is e, built once by the
+    caller; the powers then come from its indexed products and are the same bytes.  Engine calls: gt_exp on e repeated (or
+    gt_table.indexed, one term) and g2_scalar_mul_base.  Rows i of the two results are the values of encrypt_batch's dictionaries."""
+    alpha, y, A = _secrets(alpha, y)
+    if not A:
+        return bufs.zeros((0, 384), alpha), bufs.zeros((0, 128), alpha)
+    if gt_table is None:
+        base = _plan.public(e, 1, 384, alpha, "e")
+        egg = engine.gt_exp(bufs.flat(bufs.expand(base, A, 384)), alpha)
+    else:
+        egg, _ = gt_table.indexed(_plan.index_rows(np.array([[0]]), alpha), alpha, terms=1)
+    return bufs.view(egg, A, 384), bufs.view(engine.g2_scalar_mul_base(y), A, 128)
+
+
+def authority_setup_seeded(engine, e, n_attrs, rng, like=None, gt_table=None):
+    """(alpha [A, 32], y [A, 32], egg_alpha, g2_y): authority_setup with the secrets of A = n_attrs attributes drawn on the device; rng is
+    an rng.Randomness over the engine.  The draws, in this order (the order is part of the interface: it is what makes the keys
+    reproducible from the seed): alpha [A], then y [A] — two stream ids, none when A == 0.  like: a buffer of the kind the secrets and
+    the keys are to be (None: host arrays).  The seed is key material: whoever holds it holds the authority's secret key."""
+    like = np.zeros(0, dtype=np.uint8) if like is None else like
+    alpha = rng.scalars(like, n_attrs)
+    y = rng.scalars(like, n_attrs)
+    return (alpha, y) + authority_setup(engine, e, alpha, y, gt_table=gt_table)
+
+
+def keygen_batch(engine, gids, alpha, y, mask=None, h_gid=None):
+    """The keys of U users over A attributes (KeyGenerate, dabe/lw11_dabe.go:90-107): K [U, A, 64] with
+    K[u, i] = [alpha_i] g1 + [y_i] H(GID_u).  gids: the U global identifiers, str (hashed as UTF-8, hash.ToG1) or bytes, hashed by
+    engine.hash_to_g1 with the reference's tag; or None with h_gid [U, 64], the rows H(GID_u) ready (numpy, or CUDA tensors: everything
+    then stays on the device).  alpha, y: the authority's A secrets each (Python ints, uint8 arrays or tensors of h_gid's kind).
+    mask [U, A] bytes: non-zero = user u is granted attribute i; the other rows of K come out all zero (None: every attribute to every
+    user).  Engine calls: hash_to_g1, g1_scalar_mul in its ROW form — U bases, U * A scalars, y repeated per user, row-major: one
+    base per user and a row of A scalars per base —, g1_scalar_mul_base of the A alphas, g1_add.  K[u] indexed by the matrix rows'
+    attributes is the k_by_rho of fold_key."""
+    if h_gid is None:
+        if gids is None:
+            raise ValueError("need the identifiers gids, or their hashes h_gid")
+        from .hash_to import DST_STRING_G1
+        h_gid = engine.hash_to_g1([g.encode("utf-8") if isinstance(g, str) else bytes(g) for g in gids], DST_STRING_G1)
+        h_gid = bufs.put(h_gid, next((x for x in (alpha, y) if bufs.is_torch(x)), h_gid))      # the hashes go where the secrets live
+    U = bufs.nbytes(h_gid) // 64
+    if bufs.nbytes(h_gid) != U * 64:
+        raise ValueError("h_gid must hold whole G1 points")
+    h = bufs.view(h_gid, U, 64)
+    alpha, y = (_plan.scalars(x, h) for x in (alpha, y))
+    bufs.device_of(h, alpha, y)
+    A = bufs.nbytes(alpha) // 32
+    if bufs.nbytes(alpha) != A * 32 or bufs.nbytes(y) != A * 32:
+        raise ValueError("alpha and y must hold one 32-byte scalar per attribute each")
+    if mask is not None:
+        mask = _plan.public(mask, U * A, 1, h, "mask")
+    if not U or not A:
+        return bufs.zeros((U, A, 64), h)
+    T = engine.g1_scalar_mul(bufs.flat(h), bufs.flat(bufs.expand(bufs.view(y, 1, A, 32), U, A, 32)))
+    ga = engine.g1_scalar_mul_base(bufs.flat(alpha))
+    K = bufs.view(engine.g1_add(bufs.flat(T), bufs.flat(bufs.expand(bufs.view(ga, 1, A, 64), U, A, 64))), U * A, 64)
+    if mask is not None:
+        K = K * bufs.view(bufs.rows_nonzero(mask), U * A, 1)
+    return bufs.view(K, U, A, 64)
 
 
 # ------------------------------------------------------------------------------------------------ Encrypt

@@ -200,11 +200,24 @@ int gpbc_final_exp(const void *f, size_t n, void *gt_out);
  * (*G1Affine).ScalarMultiplication(a, s) / ScalarMultiplicationBase(s), n times
  *   (signature/bls01_signature/bls_signature.go:45; cpabe/bsw07/bsw07_cpabe.go:69,149,157,160;
  *    bibe/afp25_bibe/afp25_bibe_utils.go:48,51).  nbase == n: one base per scalar; nbase == 1: shared base (from 16 384
- *    scalars on, served by a transient fixed-base window table: 5x the variable-base rate, same results). */
+ *    scalars on, served by a transient fixed-base window table: 5x the variable-base rate, same results).
+ *   1 < nbase < n with nbase dividing n, the ROW form: one base per row of m = n / nbase scalars,
+ *      out[j m + i] = [scalars[j m + i]] bases[j]
+ *    (K_(i,GID) = g1^alpha_i H(GID)^y_i, dabe/lw11_dabe.go:90-107: one H(GID) per user, a row of y_i).  The same canonical affine
+ *    bytes as the nbase == n call on the bases repeated m times, infinity bases (zero rows) and scalars of 0, >= r and up to
+ *    2^256 - 1 included.  Rows of 16 384 scalars and more go row by row through the transient table above; shorter G1 rows of at
+ *    least ROWS_TABLE_MIN scalars (csrc/rows29.hip.hpp) through a 60 KiB window table per base that is built by a chain of
+ *    doublings and additions, used for the row and dropped; every other row through the variable-base kernel with lane i on base
+ *    i / m.  The _dev form is ordered on `stream` only and not synchronised; it takes the tables from the library's per-stream
+ *    scratch and falls back to the variable-base kernel when that cannot be had.  The host form of a row call stages through the
+ *    library's device blocks on the calling thread's current device: it is neither sharded over the bound devices nor combined with
+ *    other threads' calls.
+ *   Any other nbase (0, above n, not a divisor of n) is GPBC_ERR_INVALID_ARG before anything is launched or written. */
 int gpbc_g1_scalar_mul_batch(const void *bases, size_t nbase, const void *scalars, size_t n, void *out);
 int gpbc_g1_scalar_mul_batch_dev(const void *d_bases, size_t nbase, const void *d_scalars, size_t n, void *d_out, void *stream);
 /* (*G2Affine).ScalarMultiplication(a, s) (signature/bls01_signature/bls_signature.go:63;
- *  cpabe/bsw07/bsw07_cpabe.go:73,83,103-121; bibe/afp25_bibe/afp25_bibe.go:215,250,251) */
+ *  cpabe/bsw07/bsw07_cpabe.go:73,83,103-121; bibe/afp25_bibe/afp25_bibe.go:215,250,251); nbase as above, the row form without
+ *  per-base tables (rows below 16 384 scalars take the variable-base kernel) */
 int gpbc_g2_scalar_mul_batch(const void *bases, size_t nbase, const void *scalars, size_t n, void *out);
 int gpbc_g2_scalar_mul_batch_dev(const void *d_bases, size_t nbase, const void *d_scalars, size_t n, void *d_out, void *stream);
 
