@@ -349,6 +349,18 @@ def rows_pass_bases(nbase, m):
     return min(nbase, max(1, min(ROWS_PASS_OUTPUTS // m, ROWS_TABLE_CAP // ROWS_TABLE_BYTES)))
 
 
+# The G2 row tables as csrc/rows29_g2.hip.hpp lays them out (tests/test_scalar_mul_rows_g2.py holds these against the header): G2 rows of
+# ROWS_G2_TABLE_MIN .. ROWS_TABLE_MAX - 1 scalars get a window table of ROWS_G2_TABLE_BYTES per base over the four GLS quarters (17 windows
+# of 15 rows of 256 bytes), built for a pass of at most rows_g2_pass_bases(nbase, m) bases at a time from window bases made for up to
+# ROWS_G2_GROUP_BASES bases ahead of their passes.  ROWS_G2_TABLE_MIN is measured (profiles/shared_base_rows_g2.json).
+ROWS_G2_TABLE_MIN, ROWS_G2_TABLE_BYTES, ROWS_G2_PASS_OUTPUTS, ROWS_G2_TABLE_CAP, ROWS_G2_GROUP_BASES = 16, 65280, 1 << 18, 1 << 30, 1 << 16
+
+
+def rows_g2_pass_bases(nbase, m):
+    """bases per pass of the G2 row tables for nbase bases of m scalars each (csrc/rows29_g2.hip.hpp: rows_g2_pass_bases)"""
+    return min(nbase, max(1, min(ROWS_G2_PASS_OUTPUTS // m, ROWS_G2_TABLE_CAP // ROWS_G2_TABLE_BYTES)))
+
+
 def g1_scalar_mul(bases, scalars, out=None):
     """out[i] = new(G1Affine).ScalarMultiplication(&bases[i], scalars[i]): one base per scalar, ONE shared base, or — the row form —
     nbase bases for n = nbase * m scalars, row-major: out[j * m + i] = [scalars[j * m + i]] bases[j], a base with its own row of m

@@ -468,3 +468,136 @@ def decrypt_batch_policies(engine, trees_or_plan, policy_of, held, d_key, dj, dj
     with _share_forest(engine, plans, Lmax) as forest:
         w, ok = forest.weights(ids, bufs.flat(bufs.view(held, n * Lmax)))            # [n, Lmax, 32] canonical with zero padding, [n]
     return _decrypt_weighted(engine, n, Lmax, one_key, w, ok, d_key, dj, dj_prime, c_tilde, c, cy, cy_prime)
+
+
+# ------------------------------------------------------------------------------------------------ SetUp, KeyGenerate
+# cpabe/bsw07/bsw07_cpabe.go:56-131.  SetUp is a handful of generator multiplications; KeyGenerate for U users over a list of A attributes
+# is generator multiplications and elementwise additions except for [rj_ua] H2(a), U A variable-base multiplications in G2 with one base
+# per ATTRIBUTE: the row form of g2_scalar_mul with A bases and a row of U scalars each, which from ROWS_G2_TABLE_MIN users on runs from
+# a window table per attribute (csrc/rows29_g2.hip.hpp).
+def _host_like(*values):
+    """the first buffer among the values (its kind is the call's), or an empty host array"""
+    return next((x for x in values if _plan.is_buffer(x)), np.zeros(0, dtype=np.uint8))
+
+
+def setup(engine, alpha, beta, gt_table=None):
+    """(pp, msk) from the two secrets (SetUp, cpabe/bsw07/bsw07_cpabe.go:56-95).  pp = {"h": [beta] g1 (64 B), "f": [1/beta] g2 (128 B),
+    "e_alpha": e(g1, g2)^alpha (384 B)} and msk = {"beta": beta (32 B), "g2_alpha": [alpha] g2 (128 B)}.  alpha, beta: a scalar each, a
+    Python int, 32 bytes or a CUDA tensor (the values are of their kind).  beta = 0 gives f = the point at infinity, as the reference's
+    Inverse does (0 -> 0): nothing is refused that the reference accepts.  gt_table: an engine.GTFixedBase whose base 0 is e(g1, g2),
+    built once by the caller; e_alpha then comes from its indexed products and is the same bytes.  Engine calls: g1_scalar_mul_base,
+    fr_inverse, g2_scalar_mul_base (1/beta and alpha in one call), pair_batch on the generators and gt_exp (or gt_table.indexed, one
+    term)."""
+    like = _host_like(alpha, beta)
+    alpha, beta = _plan.scalars(alpha, like, 1, "alpha"), _plan.scalars(beta, like, 1, "beta")
+    bufs.device_of(alpha, beta)
+    g2s = bufs.view(engine.g2_scalar_mul_base(bufs.flat(bufs.cat([bufs.view(engine.fr_inverse(beta), 1, 32), bufs.view(alpha, 1, 32)]))), 2, 128)
+    if gt_table is None:
+        g1, g2 = engine.generators()
+        e = _plan.public(np.asarray(engine.pair_batch(np.asarray(g1, dtype=np.uint8).reshape(-1), np.asarray(g2, dtype=np.uint8).reshape(-1))), 1, 384, like, "e")
+        e_alpha = engine.gt_exp(bufs.flat(e), alpha)
+    else:
+        e_alpha, _ = gt_table.indexed(_plan.index_rows(np.array([[0]]), like), alpha, terms=1)
+    pp = {"h": bufs.view(engine.g1_scalar_mul_base(beta), 64), "f": g2s[0], "e_alpha": bufs.view(e_alpha, 384)}
+    return pp, {"beta": bufs.view(beta, 32), "g2_alpha": g2s[1]}
+
+
+def setup_seeded(engine, rng, like=None, gt_table=None):
+    """setup with the secrets drawn on the device: rng is an rng.Randomness over the engine.  The draws, in this order (the order is part
+    of the interface: it is what makes the keys reproducible from the seed): alpha, then beta — two stream ids.  like: a buffer of the
+    kind the keys are to be (None: host arrays).  The seed is key material: whoever holds it holds the master secret key."""
+    like = np.zeros(0, dtype=np.uint8) if like is None else like
+    alpha = rng.scalars(like, 1)
+    beta = rng.scalars(like, 1)
+    return setup(engine, alpha, beta, gt_table=gt_table)
+
+
+def keygen_batch(engine, msk, h2, r, rj, held=None):
+    """The keys of U users over a list of A attributes (KeyGenerate, cpabe/bsw07/bsw07_cpabe.go:97-131): (D [U, 128], dj [U, A, 128],
+    dj_prime [U, A, 128]) with D_u = [1/beta]([alpha] g2 + [r_u] g2), dj[u, a] = [r_u] g2 + [rj_ua] H2(a), dj_prime[u, a] = [rj_ua] g2.
+    msk: setup's; h2 [A, 128]: H2 of the A attributes; r: U scalars; rj [U, A] scalars, user-major as the reference draws them (Python
+    ints, uint8 arrays or CUDA tensors; numpy in gives numpy out, tensors give tensors).  held [U, A] bytes: non-zero = user u gets
+    attribute a; the other rows of dj and dj_prime come out all zero (None: every attribute to every user).
+
+    h2=None reproduces the reference, whose Hash2BSw07 returns the generator for every attribute: dj = [r + rj] g2 by fr_add and one
+    generator multiplication — the bytes the row route gives with h2 = the generator repeated.
+
+    Engine calls: g2_scalar_mul_base (R = [r] g2), g2_add with g2_alpha and g2_scalar_mul by fr_inverse(beta) with a base per scalar (D),
+    g2_scalar_mul_base (dj_prime), ONE g2_scalar_mul in its row form — A bases, A U scalars, rj permuted to attribute-major: one base
+    per attribute and a row of U scalars per base — and g2_add of its result permuted back with R expanded over A (dj)."""
+    like = _host_like(r, rj, h2)
+    r, rj = _plan.scalars(r, like), _plan.scalars(rj, like)
+    U = bufs.nbytes(r) // 32
+    if bufs.nbytes(r) != U * 32:
+        raise ValueError("r must hold whole 32-byte scalars")
+    if h2 is None:
+        A = bufs.nbytes(rj) // (32 * U) if U else 0
+    else:
+        A = bufs.nbytes(h2) // 128
+        if bufs.nbytes(h2) != A * 128:
+            raise ValueError("h2 must hold whole G2 points")
+        h2 = _plan.public(h2, A, 128, like, "h2")
+    if bufs.nbytes(rj) != U * A * 32:
+        raise ValueError("rj must hold U x A = %d x %d scalars" % (U, A))
+    bufs.device_of(r, rj, *([] if h2 is None else [h2]))
+    if held is not None:
+        held = _plan.public(held, U * A, 1, like, "held")
+    g2_alpha = _plan.public(msk["g2_alpha"], 1, 128, like, "msk g2_alpha")
+    beta = bufs.flat(_plan.public(msk["beta"], 1, 32, like, "msk beta"))
+    if not U:
+        return bufs.zeros((0, 128), like), bufs.zeros((0, A, 128), like), bufs.zeros((0, A, 128), like)
+    R = bufs.view(engine.g2_scalar_mul_base(bufs.flat(r)), U, 128)
+    inv = bufs.view(engine.fr_inverse(beta), 1, 32)
+    D = engine.g2_scalar_mul(engine.g2_add(bufs.flat(R), bufs.flat(bufs.expand(g2_alpha, U, 128))), bufs.flat(bufs.expand(inv, U, 32)))
+    if not A:
+        return bufs.view(D, U, 128), bufs.zeros((U, 0, 128), like), bufs.zeros((U, 0, 128), like)
+    rj = bufs.view(rj, U, A, 32)
+    dj_prime = bufs.view(engine.g2_scalar_mul_base(bufs.flat(rj)), U * A, 128)
+    if h2 is None:
+        dj = engine.g2_scalar_mul_base(engine.fr_add(bufs.flat(bufs.expand(bufs.view(r, U, 1, 32), U, A, 32)), bufs.flat(rj)))
+    else:
+        T = bufs.view(engine.g2_scalar_mul(bufs.flat(h2), bufs.flat(rj.swapaxes(0, 1))), A, U, 128)
+        dj = engine.g2_add(bufs.flat(T.swapaxes(0, 1)), bufs.flat(bufs.expand(bufs.view(R, U, 1, 128), U, A, 128)))
+    dj = bufs.view(dj, U * A, 128)
+    if held is not None:
+        keep = bufs.view(bufs.rows_nonzero(held), U * A, 1)
+        dj, dj_prime = dj * keep, dj_prime * keep
+    return bufs.view(D, U, 128), bufs.view(dj, U, A, 128), bufs.view(dj_prime, U, A, 128)
+
+
+def keygen_batch_seeded(engine, msk, h2, n_users, rng, n_attrs=None, held=None, like=None):
+    """keygen_batch with its randomness drawn on the device: rng is an rng.Randomness over the engine, everything else as there, and the
+    return value is exactly keygen_batch's on the scalars drawn.  The draws, in this order (the order is part of the interface: it is
+    what makes the keys reproducible from the seed): r [U], then rj [U, A] — two stream ids, one when A == 0, none when U == 0.  A is
+    h2's, or n_attrs with h2=None.  like: a buffer of the kind the keys are to be (None: h2's kind, host arrays without it).  The seed
+    is key material: whoever holds it can recompute every user's r."""
+    like = _host_like(h2) if like is None else like
+    A = int(n_attrs) if h2 is None else bufs.nbytes(h2) // 128
+    r = rng.scalars(like, int(n_users))
+    rj = rng.scalars(like, int(n_users), A)
+    return keygen_batch(engine, msk, h2, r, rj, held=held)
+
+
+def key_for_leaves(tree_or_plan, attrs, held, dj, dj_prime):
+    """keygen_batch's keys over the attribute list `attrs` as decrypt_batch_keys takes them: (held [U, L], dj [U, L, 128],
+    dj_prime [U, L, 128]) with the columns in leaf order.  tree_or_plan: a Leaf / Threshold tree or share_plan(tree); attrs: the A
+    attributes of the columns of dj and dj_prime [U, A, 128]; held [U, A] as keygen_batch took it (None: every attribute to every user).
+    An attribute that sits on several leaves goes to all of them; a leaf whose attribute is not in attrs has held = 0 and zero rows."""
+    _, attributes = share_plan(tree_or_plan) if isinstance(tree_or_plan, (Leaf, Threshold)) else tree_or_plan
+    attrs = list(attrs)
+    A, L = len(attrs), len(attributes)
+    if len(set(attrs)) != A:
+        raise ValueError("attrs names an attribute twice")
+    U = bufs.nbytes(dj) // (128 * A) if A else 0
+    if not A or bufs.nbytes(dj) != U * A * 128 or bufs.nbytes(dj_prime) != U * A * 128:
+        raise ValueError("need dj and dj_prime [U, A, 128] over A = %d >= 1 attributes" % A)
+    bufs.device_of(dj, dj_prime)
+    where = {a: i for i, a in enumerate(attrs)}
+    column = np.array([where.get(a, A) for a in attributes], dtype=np.int64)         # column A: the padding, all zero
+    held = bufs.zeros((U, A), dj) + 1 if held is None else bufs.view(bufs.rows_nonzero(_plan.public(held, U * A, 1, dj, "held")), U, A)
+
+    def leaves(a, width):
+        padded = bufs.cat([bufs.view(a, U, A, width), bufs.zeros((U, 1, width), dj)], 1)
+        return bufs.take(padded, column, axis=1)
+    h = leaves(held, 1)
+    return bufs.view(h, U, L), leaves(dj, 128) * h, leaves(dj_prime, 128) * h

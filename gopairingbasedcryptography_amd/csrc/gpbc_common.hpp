@@ -126,8 +126,14 @@ int msm_dev(bool g2, const void *d_bases, const void *d_scalars, size_t n, void 
 // on `st`.  Folds chunk-major partial sums (partial[c * n + m], n_out = n) in one launch.
 int point_sum_strided_dev(bool g2, const void *d_in, size_t n_in, void *d_out, size_t n_out, hipStream_t st);
 // The row form of the scalar multiplications (gpbc_rows.hip): out[j m + i] = [scalars[j m + i]] bases[j] for nbase bases and m scalars a
-// base; asynchronous on `st`.  G1 rows of fewer than table_max scalars may take the per-base row tables of csrc/rows29.hip.hpp.
+// base; asynchronous on `st`.  Rows of fewer than table_max scalars may take the per-base row tables of csrc/rows29.hip.hpp (G1) and
+// csrc/rows29_g2.hip.hpp (G2).
 int scalar_mul_rows_dev(bool g2, const void *d_bases, size_t nbase, const void *d_scalars, size_t m, void *d_out, size_t table_max, hipStream_t st);
+// The G2 row tables (gpbc_rows_g2.hip), called by scalar_mul_rows_dev: the same outputs through a window table per base over the GLS
+// quarters; GPBC_ERR_WORKSPACE when the tables' memory cannot be had (nothing was enqueued).  rows_g2_table_min(): the row length from
+// which they are taken, ROWS_G2_TABLE_MIN or what GPBC_ROWS_G2_TABLE_MIN in the environment says (the measurement's A/B).
+int rows_g2_table_dev(const void *d_bases, size_t nbase, size_t m, const void *d_scalars, void *d_out, hipStream_t st);
+size_t rows_g2_table_min();
 // RCCL communicator of the current device (gpbc_core.hip): number of ranks (0 = none), this device's rank, all-gather
 int comm_ranks();
 int comm_rank();

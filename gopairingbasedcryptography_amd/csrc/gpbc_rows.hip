@@ -100,12 +100,13 @@ static size_t rows_table_min() {
 }
 
 // out[j m + i] = [scalars[j m + i]] bases[j], j < nbase, i < m; the caller has checked the arguments and bound the device.  G1 rows of
-// ROWS_TABLE_MIN .. table_max - 1 scalars take the row tables (and the table-free kernel when their memory cannot be had), every other
-// row the table-free kernel.  Asynchronous on `st`.
+// ROWS_TABLE_MIN .. table_max - 1 scalars and G2 rows of ROWS_G2_TABLE_MIN .. table_max - 1 (gpbc_rows_g2.hip) take their group's row
+// tables (and the table-free kernel when their memory cannot be had), every other row the table-free kernel.  Asynchronous on `st`.
 int scalar_mul_rows_dev(bool g2, const void *d_bases, size_t nbase, const void *d_scalars, size_t m, void *d_out, size_t table_max, hipStream_t st) {
     if (!nbase || !m) return GPBC_OK;
-    if (!g2 && m >= rows_table_min() && m < table_max) {
-        const int rc = rows_table_dev((const uint8_t *)d_bases, nbase, m, (const uint8_t *)d_scalars, (uint8_t *)d_out, st);
+    if (m >= (g2 ? rows_g2_table_min() : rows_table_min()) && m < table_max) {
+        const int rc = g2 ? rows_g2_table_dev(d_bases, nbase, m, d_scalars, d_out, st)
+                          : rows_table_dev((const uint8_t *)d_bases, nbase, m, (const uint8_t *)d_scalars, (uint8_t *)d_out, st);
         if (rc != GPBC_ERR_WORKSPACE) return rc;
     }
     return rows_free_dev(g2, (const uint8_t *)d_bases, m, (const uint8_t *)d_scalars, nbase * m, (uint8_t *)d_out, st);

@@ -16,8 +16,10 @@
 //   evaluation one lane per output: glv_split, then 32 + 32 look-ups and mixed additions, no doublings; digit 0 is skipped.
 // jac_add_mixed is the complete law, so the doubling inside a chain, a cancellation and the restart after it are its exceptional branches
 // (the contract of fbindex29.hip.hpp), and every scalar up to 2^256 - 1 comes out as [k mod r] P.
-// Everything else (G1 rows below the crossover, G2 rows) takes rows_free_lane: scalar_mul29_best as k_g1 / g2_scalar_mul use it, lane i
-// on base i / m.  A G2 table form would need the four-dimensional GLS split (17 windows per quarter) and has no consumer yet.
+// Everything else (G1 and G2 rows below their crossovers) takes rows_free_lane: scalar_mul29_best as k_g1 / g2_scalar_mul use it, lane i
+// on base i / m.  The G2 table form — the four-dimensional GLS split, 17 windows per quarter, psi on the accumulator — is
+// csrc/rows29_g2.hip.hpp with kernels of its own in csrc/gpbc_rows_g2.hip; scalar_mul_rows_dev sends G2 rows of ROWS_G2_TABLE_MIN
+// scalars and more there.  The ROWS_* constants below are G1's; G2 has ROWS_G2_*.
 // The lane functions are shared with the host harness (tools/rows_check.cpp); none of them uses blockIdx.
 #ifndef GPBC_ROWS29_HIP_HPP
 #define GPBC_ROWS29_HIP_HPP

@@ -216,8 +216,12 @@ int gpbc_final_exp(const void *f, size_t n, void *gt_out);
 int gpbc_g1_scalar_mul_batch(const void *bases, size_t nbase, const void *scalars, size_t n, void *out);
 int gpbc_g1_scalar_mul_batch_dev(const void *d_bases, size_t nbase, const void *d_scalars, size_t n, void *d_out, void *stream);
 /* (*G2Affine).ScalarMultiplication(a, s) (signature/bls01_signature/bls_signature.go:63;
- *  cpabe/bsw07/bsw07_cpabe.go:73,83,103-121; bibe/afp25_bibe/afp25_bibe.go:215,250,251); nbase as above, the row form without
- *  per-base tables (rows below 16 384 scalars take the variable-base kernel) */
+ *  cpabe/bsw07/bsw07_cpabe.go:73,83,103-121; bibe/afp25_bibe/afp25_bibe.go:215,250,251); nbase as above.  The row form
+ *  (Dj = g2^r H2(j)^rj, cpabe/bsw07/bsw07_cpabe.go:111-122: one H2(j) per attribute, a row of rj per user): rows of at least
+ *  ROWS_G2_TABLE_MIN and fewer than 16 384 scalars (csrc/rows29_g2.hip.hpp) go through a 65 280-byte window table per base over the
+ *  four GLS quarters, built, used for the row and dropped like the G1 tables and with the same fall-back; shorter rows take the
+ *  variable-base kernel with lane i on base i / m.  The same canonical affine bytes on every route, for bases in the order-r
+ *  subgroup (which the variable-base kernel presumes as well). */
 int gpbc_g2_scalar_mul_batch(const void *bases, size_t nbase, const void *scalars, size_t n, void *out);
 int gpbc_g2_scalar_mul_batch_dev(const void *d_bases, size_t nbase, const void *d_scalars, size_t n, void *d_out, void *stream);
 

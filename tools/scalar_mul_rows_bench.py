@@ -5,7 +5,8 @@ against route to the same bytes, and the planner built on it:
     every row length they serve), the table-free row kernel (GPBC_ROWS_TABLE_MIN=0 never takes them) and the route the engine had before —
     g1_scalar_mul with one base per scalar on the bases expanded by repeat_interleave, the expansion included;
   * the m = 16 comparison a second time: the difference between the two runs is the run-to-run spread the others are read against;
-  * G2 at m = 16 (table-free rows only) against its expanded route;
+  * G2 at m = 16, the table-free rows against the expanded route (GPBC_ROWS_G2_TABLE_MIN=0 beside the G1 knob: the G2 row tables
+    have a tool of their own, tools/scalar_mul_rows_g2_bench.py);
   * lw11.keygen_batch at 2^16 users x 16 attributes and 2^14 x 64, H(GID) given as rows, against the same planner on an engine whose
     g1_scalar_mul expands the rows first.
 Seeded inputs; the legs of a comparison alternate inside one repetition loop; the output bytes of the legs are compared before any time
@@ -30,6 +31,7 @@ import torch  # noqa: E402
 from gopairingbasedcryptography_amd import _lib, bn254, lw11  # noqa: E402
 
 KNOB = "GPBC_ROWS_TABLE_MIN"
+KNOB_G2 = "GPBC_ROWS_G2_TABLE_MIN"           # the G2 tables' own override (csrc/gpbc_rows_g2.hip); this tool's G2 leg is the table-free one
 ROW_LENGTHS = (4, 8, 16, 32, 64, 256, 4096)
 
 
@@ -74,20 +76,22 @@ def points(g2, n, tag):
 
 
 def with_knob(value, fn):
-    """fn under GPBC_ROWS_TABLE_MIN=value (None: as built); the library reads it at every call"""
+    """fn under GPBC_ROWS_TABLE_MIN=value and GPBC_ROWS_G2_TABLE_MIN=value (None: as built); the library reads them at every call"""
     def run():
-        old = os.environ.get(KNOB)
-        if value is None:
-            os.environ.pop(KNOB, None)
-        else:
-            os.environ[KNOB] = value
+        old = {k: os.environ.get(k) for k in (KNOB, KNOB_G2)}
+        for k in old:
+            if value is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = value
         try:
             return fn()
         finally:
-            if old is None:
-                os.environ.pop(KNOB, None)
-            else:
-                os.environ[KNOB] = old
+            for k, v in old.items():
+                if v is None:
+                    os.environ.pop(k, None)
+                else:
+                    os.environ[k] = v
     return run
 
 
@@ -95,7 +99,7 @@ def dispatched(g2, m):
     """the route the library as built takes for a row length"""
     if m >= 16384:
         return "transient_8bit_table"
-    return "table" if not g2 and m >= bn254.ROWS_TABLE_MIN else "table_free"
+    return "table" if m >= (bn254.ROWS_G2_TABLE_MIN if g2 else bn254.ROWS_TABLE_MIN) else "table_free"
 
 
 def rows_section(g2, m, n, reps, rng):
