@@ -153,6 +153,46 @@ def unpack_bits(a):
     return ((a.unsqueeze(-1) >> shifts) & 1).reshape(a.shape[0], -1)
 
 
+def group_rows(a):
+    """(distinct [g, W], inverse [n] int64) of the n >= 1 rows of a two-dimensional uint8 buffer: the distinct rows, in an order of the
+    library's choosing, and for every row the position of its value among them — numpy.unique / torch.unique along axis 0 with
+    return_inverse, on the rows read as 64-bit words where W allows it (the grouping is the same, a comparison eight times shorter).
+    On a CUDA tensor the count g comes back to the host: the call waits for the stream."""
+    width = a.shape[1]
+    if is_torch(a):
+        import torch
+        words = a.contiguous().view(torch.int64) if width % 8 == 0 else a
+        distinct, inverse = torch.unique(words, dim=0, return_inverse=True)
+        return distinct.view(torch.uint8).reshape(-1, width), inverse.reshape(-1)
+    a = np.ascontiguousarray(a, dtype=np.uint8)
+    distinct, inverse = np.unique(a.view(np.uint64) if width % 8 == 0 else a, axis=0, return_inverse=True)
+    return distinct.view(np.uint8).reshape(-1, width), inverse.reshape(-1).astype(np.int64, copy=False)
+
+
+def range_positions(rows, start, end):
+    """[n] int64: for canonical scalar rows [n, 32] the value minus start where it lies in [start, end), else -1, for
+    0 <= start <= end < 2^63 — arithmetic on the low 8 bytes once the upper 24 are seen to be zero"""
+    if is_torch(rows):
+        import torch
+        low = rows[:, :8].contiguous().view(torch.int64).reshape(-1)                    # a value of 2^63 or more reads negative: outside
+        inside = ~(rows[:, 8:] != 0).any(1) & (low >= start) & (low < end)
+        return torch.where(inside, low - start, torch.full_like(low, -1))
+    rows = np.asarray(rows, dtype=np.uint8)
+    low = np.ascontiguousarray(rows[:, :8]).view("<i8").reshape(-1)
+    inside = ~(rows[:, 8:] != 0).any(1) & (low >= start) & (low < end)
+    return np.where(inside, low - start, -1).astype(np.int64)
+
+
+def index_rows_ok(pos, k, a):
+    """(index [k, a], ok [k] uint8) of k * a positions with -1 for "none": the positions as FixedBase.indexed takes an index table —
+    uint32 on the host, the same bits as int32 on the device, "none" as 0xFFFFFFFF — and ok = 1 where a row holds no "none\""""
+    pos = pos.reshape(k, a)
+    if is_torch(pos):
+        import torch
+        return pos.to(torch.int32), (pos >= 0).all(1).to(torch.uint8)
+    return np.where(pos < 0, 0xFFFFFFFF, pos).astype(np.uint32), (pos >= 0).all(1).astype(np.uint8)
+
+
 def rows_equal(a, b):
     """per row of two uint8 buffers of one shape and kind: 1 where the rows hold the same bytes, else 0"""
     return (a == b).all(1).to(a.dtype) if is_torch(a) else (a == b).all(1).astype(np.uint8)

@@ -17,6 +17,16 @@ def is_buffer(x):
     return bufs.is_torch(x) or isinstance(x, np.ndarray)
 
 
+def like_of(*values):
+    """the first buffer among the values (its kind is the call's), or an empty host array"""
+    return next((x for x in values if is_buffer(x)), np.zeros(0, dtype=np.uint8))
+
+
+def host(a):
+    """a buffer's bytes on the host (a CUDA tensor: the copy waits for its stream)"""
+    return a.cpu().numpy() if bufs.is_torch(a) else np.asarray(a)
+
+
 def scalar_rows(values):
     """Python integers — one, a flat list or generator, or a list of rows — as scalar rows modulo r: a writable [k, 32] uint8 array
     (it may become a tensor).  The values of a batch repeat: each distinct one is converted once."""

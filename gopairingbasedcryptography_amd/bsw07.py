@@ -475,9 +475,7 @@ def decrypt_batch_policies(engine, trees_or_plan, policy_of, held, d_key, dj, dj
 # is generator multiplications and elementwise additions except for [rj_ua] H2(a), U A variable-base multiplications in G2 with one base
 # per ATTRIBUTE: the row form of g2_scalar_mul with A bases and a row of U scalars each, which from ROWS_G2_TABLE_MIN users on runs from
 # a window table per attribute (csrc/rows29_g2.hip.hpp).
-def _host_like(*values):
-    """the first buffer among the values (its kind is the call's), or an empty host array"""
-    return next((x for x in values if _plan.is_buffer(x)), np.zeros(0, dtype=np.uint8))
+_host_like = _plan.like_of
 
 
 def setup(engine, alpha, beta, gt_table=None):
