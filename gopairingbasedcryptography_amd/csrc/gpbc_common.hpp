@@ -48,6 +48,27 @@ __device__ __forceinline__ void g2_store_aff(uint8_t *p, const AffP<F2> &r) { f2
 // ---- host side
 extern thread_local char g_err[512];
 int fail(int code, const char *fmt, ...);
+// Three argument rules that many entries state, each with its message written once: a count given once or per item ("<name> must be 1 or k
+// (got <n>, k = <k>)"; nb_one_or_n: the elementwise entries' wording), the items one call may hold ("too many <noun> for one call (<n>)";
+// the default limit leaves the grid four workgroups per item), and the units a shard of a host-pointer call needs to pay for its thread
+// and transfers: about 2^16 steps of `work` steps each, at least one unit.
+int one_or_k(const char *name, size_t n, size_t k);
+int nb_one_or_n(size_t nb, size_t n);
+int call_limit(const char *noun, size_t n, size_t max = (size_t)0x7fffffff / 4);
+static inline size_t shard_min_units(size_t work) { const size_t m = ((size_t)1 << 16) / work; return m ? m : 1; }
+// Argument ranges as (pointer, bytes).  ranges_overlap: a null pointer or an empty range overlaps nothing.  outputs_overlap: r[0 .. n_in)
+// are the inputs of a call and r[n_in .. n) its outputs; true when an output meets an input or another output.
+struct ByteRange { const void *p; size_t bytes; };
+static inline bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return a && b && na && nb && pa < pb + nb && pb < pa + na;
+}
+static inline bool outputs_overlap(const ByteRange *r, int n_in, int n) {
+    for (int i = n_in; i < n; i++)
+        for (int j = 0; j < i; j++)
+            if (ranges_overlap(r[i].p, r[i].bytes, r[j].p, r[j].bytes)) return true;
+    return false;
+}
 #define HIP_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(GPBC_ERR_HIP, "%s failed: %s", #x, hipGetErrorString(e_)); } while (0)
 #define TRY(x) do { int rc_ = (x); if (rc_ != GPBC_OK) return rc_; } while (0)
 // Devices: gpbc_init_devices() binds the process to a LIST of HIP devices.  Every host thread has a current device
@@ -253,13 +274,16 @@ struct CallLane {
     bool busy = false;
     int reserve(size_t pin_need, size_t dev_need);  // grow-only; called by the batch runner before it writes anything
 };
-// A host-pointer call of n units: its columns and, for the combined route, what the combiner needs besides.
+// A host-pointer call of n units: its columns and, for the combined route, what the combiner needs besides.  Up to MAX_IN input and
+// MAX_OUT output columns; every route of the staging path loops over these two counts, and a column that is not used (0 bytes per unit,
+// a null pointer) costs nothing: no bytes of a lane's pinned block, no device block.
 struct HostCall {
-    const void *in[3] = {nullptr, nullptr, nullptr};   // input columns (meaning per entry); null = none
-    size_t in_bytes[3] = {0, 0, 0};                    // bytes per unit, or of the whole column with in_one
-    bool in_one[3] = {false, false, false};            // column holds ONE element for all units (a shared base, the fixed-Q list)
-    void *out[2] = {nullptr, nullptr};                 // output columns; null = not wanted
-    size_t out_bytes[2] = {0, 0};                      // bytes per unit
+    static constexpr int MAX_IN = 3, MAX_OUT = 4;
+    const void *in[MAX_IN] = {};                       // input columns (meaning per entry); null = none
+    size_t in_bytes[MAX_IN] = {};                      // bytes per unit, or of the whole column with in_one
+    bool in_one[MAX_IN] = {};                          // column holds ONE element for all units (a shared base, the fixed-Q list)
+    void *out[MAX_OUT] = {};                           // output columns; null = not wanted
+    size_t out_bytes[MAX_OUT] = {};                    // bytes per unit
     int n_in = 0, n_out = 0;
     static constexpr size_t UNITS_N = ~(size_t)0;
     size_t units = UNITS_N;                            // what the combiner's cap counts: pairs / points / terms (UNITS_N: the n of the call)
@@ -305,7 +329,7 @@ struct HostRoute {
     SmallBatchFn run = nullptr;
     size_t small_max = 0, lane_max = 0, pipe_chunk = 0, tmp_bytes = 0;
 };
-struct DevCols { const uint8_t *in[3]; uint8_t *out[2]; uint8_t *tmp; };
+struct DevCols { const uint8_t *in[HostCall::MAX_IN]; uint8_t *out[HostCall::MAX_OUT]; uint8_t *tmp; };
 using HostCallBody = std::function<int(const DevCols &d, size_t n, hipStream_t st)>;
 int host_call(size_t n, const HostCall &c, const HostRoute &r, const HostCallBody &body);
 int host_call_sharded(size_t n, size_t min_units, const HostCall &c, const HostRoute &r, const HostCallBody &body);

@@ -20,6 +20,9 @@ int fail(int code, const char *fmt, ...) {
     va_end(ap);
     return code;
 }
+int one_or_k(const char *name, size_t n, size_t k) { return n == 1 || n == k ? GPBC_OK : fail(GPBC_ERR_INVALID_ARG, "%s must be 1 or k (got %zu, k = %zu)", name, n, k); }
+int nb_one_or_n(size_t nb, size_t n) { return nb == 1 || nb == n ? GPBC_OK : fail(GPBC_ERR_INVALID_ARG, "nb must be 1 or n (got nb = %zu, n = %zu)", nb, n); }
+int call_limit(const char *noun, size_t n, size_t max) { return n <= max ? GPBC_OK : fail(GPBC_ERR_INVALID_ARG, "too many %s for one call (%zu)", noun, n); }
 
 // ---- devices.  Slots are written under g_dev_mu by init / shutdown and read lock-free afterwards (g_ndev is published
 // last); a slot's mutex and communicator live as long as the process.
@@ -261,31 +264,34 @@ int with_call_lane(const std::function<int(CallLane &)> &body) {
     }
     return rc;
 }
+constexpr int MAX_IN = HostCall::MAX_IN, MAX_OUT = HostCall::MAX_OUT;     // the staging path's column counts, here and in host_call below
 int small_rows_run(CallLane &lane, SmallCall *const *calls, size_t nc, const RowsLaunch &launch) {
     const HostCall &h = *calls[0];                               // (the calls of a batch share one kind and key: their column widths agree)
-    size_t N = 0, off[5], total = 0;
+    size_t N = 0, in_off[MAX_IN], out_off[MAX_OUT], total = 0;
     for (size_t c = 0; c < nc; c++) N += calls[c]->segs;
-    for (int i = 0; i < 5; i++) { off[i] = total; total += Scratch::padded(N * (i < 3 ? h.in_bytes[i] : h.out_bytes[i - 3])); }
+    for (int i = 0; i < MAX_IN; i++) { in_off[i] = total; total += Scratch::padded(N * h.in_bytes[i]); }
+    for (int i = 0; i < MAX_OUT; i++) { out_off[i] = total; total += Scratch::padded(N * h.out_bytes[i]); }
     TRY(lane.reserve(total, 0));
     size_t n0 = 0;
     for (size_t c = 0; c < nc; c++) {
         const SmallCall &r = *calls[c];
-        for (int i = 0; i < 3; i++) {
+        for (int i = 0; i < MAX_IN; i++) {
             const size_t w = h.in_bytes[i];
-            if (r.in_one[i]) for (size_t j = 0; j < r.segs; j++) memcpy(lane.pin + off[i] + (n0 + j) * w, r.in[i], w);
-            else if (w) memcpy(lane.pin + off[i] + n0 * w, r.in[i], r.segs * w);
+            if (r.in_one[i]) for (size_t j = 0; j < r.segs; j++) memcpy(lane.pin + in_off[i] + (n0 + j) * w, r.in[i], w);
+            else if (w) memcpy(lane.pin + in_off[i] + n0 * w, r.in[i], r.segs * w);
         }
         n0 += r.segs;
     }
-    const uint8_t *in[3] = {lane.d_pin + off[0], lane.d_pin + off[1], lane.d_pin + off[2]};
-    const uint8_t *in_host[3] = {lane.pin + off[0], lane.pin + off[1], lane.pin + off[2]};
-    uint8_t *out[2] = {lane.d_pin + off[3], lane.d_pin + off[4]};
+    const uint8_t *in[MAX_IN], *in_host[MAX_IN];
+    uint8_t *out[MAX_OUT];
+    for (int i = 0; i < MAX_IN; i++) { in[i] = lane.d_pin + in_off[i]; in_host[i] = lane.pin + in_off[i]; }
+    for (int i = 0; i < MAX_OUT; i++) out[i] = lane.d_pin + out_off[i];
     TRY(launch(in, in_host, out, N));
     HIP_TRY(hipStreamSynchronize(lane.stream));
     n0 = 0;
     for (size_t c = 0; c < nc; c++) {
-        for (int i = 0; i < 2; i++)
-            if (calls[c]->out[i]) memcpy(calls[c]->out[i], lane.pin + off[3 + i] + n0 * h.out_bytes[i], calls[c]->segs * h.out_bytes[i]);
+        for (int i = 0; i < MAX_OUT; i++)
+            if (calls[c]->out[i]) memcpy(calls[c]->out[i], lane.pin + out_off[i] + n0 * h.out_bytes[i], calls[c]->segs * h.out_bytes[i]);
         n0 += calls[c]->segs;
     }
     return GPBC_OK;
@@ -320,28 +326,29 @@ int host_call(size_t n, const HostCall &c, const HostRoute &r, const HostCallBod
     }
     if (units && units <= r.lane_max)
         return with_call_lane([&](CallLane &l) {
-            size_t off[5], total = 0;
-            for (int i = 0; i < 5; i++) { off[i] = total; total += Scratch::padded(i < 3 ? in_col_bytes(c, i, n) : n * c.out_bytes[i - 3]); }
+            size_t in_off[MAX_IN], out_off[MAX_OUT], total = 0;
+            for (int i = 0; i < MAX_IN; i++) { in_off[i] = total; total += Scratch::padded(in_col_bytes(c, i, n)); }
+            for (int i = 0; i < MAX_OUT; i++) { out_off[i] = total; total += Scratch::padded(n * c.out_bytes[i]); }
             TRY(l.reserve(total, r.tmp_bytes));
-            if (c.in_place) off[3] = off[0];
+            if (c.in_place) out_off[0] = in_off[0];
             DevCols d{};
-            for (int i = 0; i < 3; i++) if (c.in[i]) { if (in_col_bytes(c, i, n)) memcpy(l.pin + off[i], c.in[i], in_col_bytes(c, i, n)); d.in[i] = l.d_pin + off[i]; }
-            for (int i = 0; i < 2; i++) if (c.out[i]) d.out[i] = l.d_pin + off[3 + i];
+            for (int i = 0; i < MAX_IN; i++) if (c.in[i]) { if (in_col_bytes(c, i, n)) memcpy(l.pin + in_off[i], c.in[i], in_col_bytes(c, i, n)); d.in[i] = l.d_pin + in_off[i]; }
+            for (int i = 0; i < MAX_OUT; i++) if (c.out[i]) d.out[i] = l.d_pin + out_off[i];
             d.tmp = l.dev;
             TRY(body(d, n, l.stream));
             HIP_TRY(hipStreamSynchronize(l.stream));
-            for (int i = 0; i < 2; i++) if (c.out[i]) memcpy(c.out[i], l.pin + off[3 + i], n * c.out_bytes[i]);
+            for (int i = 0; i < MAX_OUT; i++) if (c.out[i]) memcpy(c.out[i], l.pin + out_off[i], n * c.out_bytes[i]);
             return (int)GPBC_OK;
         });
     const bool pipe = r.pipe_chunk && n >= 2 * r.pipe_chunk;
-    DevBuf din[3], dout[2], dtmp;
+    DevBuf din[MAX_IN], dout[MAX_OUT], dtmp;
     DevCols d{};
-    for (int i = 0; i < 3; i++) {
+    for (int i = 0; i < MAX_IN; i++) {
         if (!c.in[i]) continue;
         TRY(pipe && !c.in_one[i] ? din[i].alloc(n * c.in_bytes[i]) : din[i].upload(c.in[i], in_col_bytes(c, i, n)));
         d.in[i] = din[i].u8();
     }
-    for (int i = 0; i < 2; i++) {
+    for (int i = 0; i < MAX_OUT; i++) {
         if (!c.out[i]) continue;
         if (i == 0 && c.in_place) { d.out[0] = din[0].u8(); continue; }
         TRY(dout[i].alloc(n * c.out_bytes[i]));
@@ -351,20 +358,20 @@ int host_call(size_t n, const HostCall &c, const HostRoute &r, const HostCallBod
     if (!pipe) {
         TRY(body(d, n, nullptr));
         TRY(sync_default());
-        for (int i = 0; i < 2; i++) if (c.out[i]) TRY((i == 0 && c.in_place ? din[0] : dout[i]).download(c.out[i], n * c.out_bytes[i]));
+        for (int i = 0; i < MAX_OUT; i++) if (c.out[i]) TRY((i == 0 && c.in_place ? din[0] : dout[i]).download(c.out[i], n * c.out_bytes[i]));
         return GPBC_OK;
     }
     // upload / kernels / download of neighbouring chunks overlap on the slot's two streams (pipelined_chunks)
     auto at = [&](size_t off) {
         DevCols s = d;
-        for (int i = 0; i < 3; i++) if (s.in[i] && !c.in_one[i]) s.in[i] += off * c.in_bytes[i];
-        for (int i = 0; i < 2; i++) if (s.out[i]) s.out[i] += off * c.out_bytes[i];
+        for (int i = 0; i < MAX_IN; i++) if (s.in[i] && !c.in_one[i]) s.in[i] += off * c.in_bytes[i];
+        for (int i = 0; i < MAX_OUT; i++) if (s.out[i]) s.out[i] += off * c.out_bytes[i];
         return s;
     };
     const int rc = pipelined_chunks(n, r.pipe_chunk,
         [&](size_t off, size_t m, hipStream_t st) {
             const DevCols s = at(off);
-            for (int i = 0; i < 3; i++)
+            for (int i = 0; i < MAX_IN; i++)
                 if (c.in[i] && !c.in_one[i])
                     HIP_TRY(hipMemcpyAsync((void *)s.in[i], (const uint8_t *)c.in[i] + off * c.in_bytes[i], m * c.in_bytes[i], hipMemcpyHostToDevice, st));
             return (int)GPBC_OK;
@@ -372,7 +379,7 @@ int host_call(size_t n, const HostCall &c, const HostRoute &r, const HostCallBod
         [&](size_t off, size_t m, hipStream_t st) { return body(at(off), m, st); },
         [&](size_t off, size_t m, hipStream_t st) {
             const DevCols s = at(off);
-            for (int i = 0; i < 2; i++)
+            for (int i = 0; i < MAX_OUT; i++)
                 if (c.out[i]) HIP_TRY(hipMemcpyAsync((uint8_t *)c.out[i] + off * c.out_bytes[i], s.out[i], m * c.out_bytes[i], hipMemcpyDeviceToHost, st));
             return (int)GPBC_OK;
         });
@@ -382,8 +389,8 @@ int host_call(size_t n, const HostCall &c, const HostRoute &r, const HostCallBod
 int host_call_sharded(size_t n, size_t min_units, const HostCall &c, const HostRoute &r, const HostCallBody &body) {
     return run_sharded(n, min_units, [&](size_t lo, size_t hi) {
         HostCall s = c;
-        for (int i = 0; i < 3; i++) if (s.in[i] && !s.in_one[i]) s.in[i] = (const uint8_t *)s.in[i] + lo * s.in_bytes[i];
-        for (int i = 0; i < 2; i++) if (s.out[i]) s.out[i] = (uint8_t *)s.out[i] + lo * s.out_bytes[i];
+        for (int i = 0; i < MAX_IN; i++) if (s.in[i] && !s.in_one[i]) s.in[i] = (const uint8_t *)s.in[i] + lo * s.in_bytes[i];
+        for (int i = 0; i < MAX_OUT; i++) if (s.out[i]) s.out[i] = (uint8_t *)s.out[i] + lo * s.out_bytes[i];
         return host_call(hi - lo, s, r, body);
     });
 }
@@ -420,9 +427,8 @@ static int segred_check_args(const SegRedOp &op, const void *x, const void *k, s
     if (!k && nk) return fail(GPBC_ERR_INVALID_ARG, "nk must be 0 without %s (got nk = %zu)", op.scalars, nk);
     if (k && nk != n && (nk > n || nk * n_seg != n))
         return fail(GPBC_ERR_INVALID_ARG, "nk must be n, or n / n_seg when every segment has that many %s (got nk = %zu, n = %zu, n_seg = %zu)", op.elements, nk, n, n_seg);
-    const uint8_t *xb = (const uint8_t *)x, *kb = (const uint8_t *)k, *ob = (const uint8_t *)out;
-    if (n && xb < ob + n_seg * op.elem_bytes && ob < xb + n * op.elem_bytes) return fail(GPBC_ERR_INVALID_ARG, "out must not overlap %s", op.x_name);
-    if (k && nk && kb < ob + n_seg * op.elem_bytes && ob < kb + nk * GPBC_SCALAR_BYTES) return fail(GPBC_ERR_INVALID_ARG, "out must not overlap the %s", op.scalars);
+    if (ranges_overlap(out, n_seg * op.elem_bytes, x, n * op.elem_bytes)) return fail(GPBC_ERR_INVALID_ARG, "out must not overlap %s", op.x_name);
+    if (ranges_overlap(out, n_seg * op.elem_bytes, k, nk * GPBC_SCALAR_BYTES)) return fail(GPBC_ERR_INVALID_ARG, "out must not overlap the %s", op.scalars);
     return GPBC_OK;
 }
 int segred_dev(const SegRedOp &op, const void *d_x, const void *d_k, size_t nk, const uint64_t *d_seg_off, size_t n, size_t n_seg, void *d_out,

@@ -606,10 +606,6 @@ int gpbc_fixed_base_msm(const gpbc_fixed_base *h, const void *scalars, size_t n_
 
 // ----------------------------------------------------------------------------------------------- indexed sums (include/gpbc_bn254_indexed.h)
 int gpbc_indexed_version(void) { return 1; }
-static bool fbi_overlap(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return a && b && pa < pb + nb && pb < pa + na;
-}
 // everything that can be said without the device; *todo = whether there is anything to launch
 static int fb_indexed_args(const gpbc_fixed_base *h, const uint32_t *index, size_t n_index_rows, size_t terms, const void *scalars, size_t n, const void *out, const uint8_t *ok_out) {
     if (terms < 1 || terms > FBI_MAX_TERMS) return fail(GPBC_ERR_INVALID_ARG, "terms must be in 1 .. %zu (got %zu)", FBI_MAX_TERMS, terms);
@@ -618,8 +614,8 @@ static int fb_indexed_args(const gpbc_fixed_base *h, const uint32_t *index, size
     if (!n) return GPBC_OK;
     if (n_index_rows < 1 || n_index_rows > n) return fail(GPBC_ERR_INVALID_ARG, "n_index_rows must be in 1 .. n (got %zu, n = %zu)", n_index_rows, n);
     if (!index || !scalars || !out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    const size_t ib = n_index_rows * terms * sizeof(uint32_t), sb = n * terms * GPBC_SCALAR_BYTES, ob = n * (h->is_g2 ? GPBC_G2_BYTES : GPBC_G1_BYTES);
-    if (fbi_overlap(out, ob, index, ib) || fbi_overlap(out, ob, scalars, sb) || fbi_overlap(ok_out, n, index, ib) || fbi_overlap(ok_out, n, scalars, sb) || fbi_overlap(out, ob, ok_out, n))
+    const ByteRange r[4] = {{index, n_index_rows * terms * sizeof(uint32_t)}, {scalars, n * terms * GPBC_SCALAR_BYTES}, {out, n * (h->is_g2 ? GPBC_G2_BYTES : GPBC_G1_BYTES)}, {ok_out, n}};
+    if (outputs_overlap(r, 2, 4))
         return fail(GPBC_ERR_INVALID_ARG, "an output overlaps an input or the other output");
     return GPBC_OK;
 }

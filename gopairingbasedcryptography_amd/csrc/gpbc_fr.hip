@@ -421,7 +421,7 @@ static int fr_dev(int op, const void *d_a, const void *d_b, size_t nb, size_t n,
     const bool binary = op == FR_ADD || op == FR_SUB || op == FR_MUL;
     if (!n) return GPBC_OK;
     if (!d_a || !d_out || (binary && !d_b)) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    if (binary && nb != 1 && nb != n) return fail(GPBC_ERR_INVALID_ARG, "nb must be 1 or n (got nb = %zu, n = %zu)", nb, n);
+    if (binary) TRY(nb_one_or_n(nb, n));
     TRY(bind_device());
     const hipStream_t st = (hipStream_t)stream;
     const uint8_t *a = (const uint8_t *)d_a, *b = binary ? (const uint8_t *)d_b : a;
@@ -446,7 +446,7 @@ static int fr_host(int op, const void *a, const void *b, size_t nb, size_t n, vo
     const bool binary = op == FR_ADD || op == FR_SUB || op == FR_MUL;
     if (!n) return GPBC_OK;
     if (!a || !out || (binary && !b)) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    if (binary && nb != 1 && nb != n) return fail(GPBC_ERR_INVALID_ARG, "nb must be 1 or n (got nb = %zu, n = %zu)", nb, n);
+    if (binary) TRY(nb_one_or_n(nb, n));
     const bool one = binary && nb == 1;
     HostCall c = HostCall().input(a, GPBC_SCALAR_BYTES);
     if (binary) c.input(b, GPBC_SCALAR_BYTES, one);
@@ -474,8 +474,7 @@ static int poly_args(size_t B, size_t k, size_t stride, bool quotients) {
     if (quotients && stride < B) return fail(GPBC_ERR_INVALID_ARG, "stride must be at least B (got stride = %zu, B = %zu)", stride, B);
     if (quotients && stride > ((size_t)1 << 24)) return fail(GPBC_ERR_INVALID_ARG, "stride too large (%zu)", stride);
     const size_t blocks = quotients ? (B + BLOCK - 1) / BLOCK : 1;
-    if (k > (size_t)0x7fffffff / blocks) return fail(GPBC_ERR_INVALID_ARG, "too many polynomials for one call (%zu)", k);
-    return GPBC_OK;
+    return call_limit("polynomials", k, (size_t)0x7fffffff / blocks);
 }
 int gpbc_fr_poly_from_roots_dev(const void *d_roots, size_t B, size_t k, void *d_coeffs_out, void *stream) {
     TRY(poly_args(B, k, 0, false));
@@ -497,7 +496,7 @@ int gpbc_fr_poly_quotients_dev(const void *d_coeffs, const void *d_points, size_
                        stride, (uint8_t *)d_q_out, d_ok_out);
 }
 // Host-pointer forms: the unit is a polynomial; a shard needs about 2^16 coefficient steps to pay for its thread and transfers.
-static size_t poly_shard_min(size_t B) { const size_t m = ((size_t)1 << 16) / (B * B); return m ? m : 1; }
+static size_t poly_shard_min(size_t B) { return shard_min_units(B * B); }
 int gpbc_fr_poly_from_roots(const void *roots, size_t B, size_t k, void *coeffs_out) {
     TRY(poly_args(B, k, 0, false));
     if (!k) return GPBC_OK;
@@ -516,24 +515,18 @@ int gpbc_fr_poly_quotients(const void *coeffs, const void *points, size_t B, siz
 }
 
 // ------------------------------------------------------------------------------------------------ Lagrange basis entries
-static bool overlap(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return a && b && pa < pb + nb && pb < pa + na;
-}
 static int lagrange_args(const void *set, size_t n_set_rows, size_t B, const void *nodes, size_t n_node_rows, size_t m, const void *x, size_t nx, size_t k, const void *out) {
     if (B < 1 || B > (size_t)FR_POLY_MAX_B || m < 1 || m > (size_t)FR_POLY_MAX_B)
         return fail(GPBC_ERR_INVALID_ARG, "B and m must be in 1 .. %d (got B = %zu, m = %zu)", FR_POLY_MAX_B, B, m);
-    if (k > (size_t)0x7fffffff / 4) return fail(GPBC_ERR_INVALID_ARG, "too many rows for one call (%zu)", k);
+    TRY(call_limit("rows", k));
     if (!k) return GPBC_OK;
-    if (n_set_rows != 1 && n_set_rows != k) return fail(GPBC_ERR_INVALID_ARG, "n_set_rows must be 1 or k (got %zu, k = %zu)", n_set_rows, k);
-    if (nodes && n_node_rows != 1 && n_node_rows != k) return fail(GPBC_ERR_INVALID_ARG, "n_node_rows must be 1 or k (got %zu, k = %zu)", n_node_rows, k);
+    TRY(one_or_k("n_set_rows", n_set_rows, k));
+    if (nodes) TRY(one_or_k("n_node_rows", n_node_rows, k));
     if (!nodes && m != B) return fail(GPBC_ERR_INVALID_ARG, "without nodes m must equal B (got m = %zu, B = %zu)", m, B);
     if (x ? nx != 1 && nx != k : nx != 0) return fail(GPBC_ERR_INVALID_ARG, "nx must be 1 or k, or 0 with x == NULL (got nx = %zu, k = %zu)", nx, k);
     if (!set || !out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    const size_t out_bytes = k * m * GPBC_SCALAR_BYTES;
-    if (overlap(out, out_bytes, set, n_set_rows * B * GPBC_SCALAR_BYTES) || overlap(out, out_bytes, nodes, n_node_rows * m * GPBC_SCALAR_BYTES) ||
-        overlap(out, out_bytes, x, nx * GPBC_SCALAR_BYTES))
-        return fail(GPBC_ERR_INVALID_ARG, "out overlaps an input");
+    const ByteRange r[4] = {{set, n_set_rows * B * GPBC_SCALAR_BYTES}, {nodes, n_node_rows * m * GPBC_SCALAR_BYTES}, {x, nx * GPBC_SCALAR_BYTES}, {out, k * m * GPBC_SCALAR_BYTES}};
+    if (outputs_overlap(r, 3, 4)) return fail(GPBC_ERR_INVALID_ARG, "out overlaps an input");
     return GPBC_OK;
 }
 int gpbc_fr_lagrange_basis_dev(const void *d_set, size_t n_set_rows, size_t B, const void *d_nodes, size_t n_node_rows, size_t m, const void *d_x, size_t nx, size_t k,
@@ -556,9 +549,8 @@ int gpbc_fr_lagrange_basis(const void *set, size_t n_set_rows, size_t B, const v
     TRY(lagrange_args(set, n_set_rows, B, nodes, n_node_rows, m, x, nx, k, out));
     if (!k) return GPBC_OK;
     const bool one_set = n_set_rows == 1, one_nodes = nodes && n_node_rows == 1, one_x = x && nx == 1;
-    const size_t per_row = B * m, shard_min = ((size_t)1 << 16) / per_row;
     HostCall c = HostCall().input(set, B * GPBC_SCALAR_BYTES, one_set).input(nodes, m * GPBC_SCALAR_BYTES, one_nodes).input(x, GPBC_SCALAR_BYTES, one_x);
-    return host_call_sharded(k, shard_min ? shard_min : 1, c.output(out, m * GPBC_SCALAR_BYTES), HostRoute{},
+    return host_call_sharded(k, shard_min_units(B * m), c.output(out, m * GPBC_SCALAR_BYTES), HostRoute{},
                              [=](const DevCols &d, size_t rows, hipStream_t st) {
                                  return gpbc_fr_lagrange_basis_dev(d.in[0], one_set ? 1 : rows, B, d.in[1], one_nodes ? 1 : rows, m, d.in[2], d.in[2] ? (one_x ? 1 : rows) : 0, rows, d.out[0], st);
                              });
@@ -568,12 +560,12 @@ int gpbc_fr_lagrange_basis(const void *set, size_t n_set_rows, size_t B, const v
 static int lsss_args(const void *matrix, size_t n_matrices, size_t rows, size_t cols, const void *held, size_t k, const void *w_out, const void *ok_out) {
     if (rows < 1 || rows > (size_t)FR_LSSS_MAX || cols < 1 || cols > (size_t)FR_LSSS_MAX)
         return fail(GPBC_ERR_INVALID_ARG, "rows and cols must be in 1 .. %d (got rows = %zu, cols = %zu)", FR_LSSS_MAX, rows, cols);
-    if (k > (size_t)0x7fffffff / 4) return fail(GPBC_ERR_INVALID_ARG, "too many systems for one call (%zu)", k);
+    TRY(call_limit("systems", k));
     if (!k) return GPBC_OK;
-    if (n_matrices != 1 && n_matrices != k) return fail(GPBC_ERR_INVALID_ARG, "n_matrices must be 1 or k (got %zu, k = %zu)", n_matrices, k);
+    TRY(one_or_k("n_matrices", n_matrices, k));
     if (!matrix || !held || !w_out || !ok_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    const size_t mb = n_matrices * rows * cols * GPBC_SCALAR_BYTES, hb = k * rows, wb = k * rows * GPBC_SCALAR_BYTES;
-    if (overlap(w_out, wb, matrix, mb) || overlap(w_out, wb, held, hb) || overlap(ok_out, k, matrix, mb) || overlap(ok_out, k, held, hb) || overlap(w_out, wb, ok_out, k))
+    const ByteRange r[4] = {{matrix, n_matrices * rows * cols * GPBC_SCALAR_BYTES}, {held, k * rows}, {w_out, k * rows * GPBC_SCALAR_BYTES}, {ok_out, k}};
+    if (outputs_overlap(r, 2, 4))
         return fail(GPBC_ERR_INVALID_ARG, "an output overlaps an input or the other output");
     return GPBC_OK;
 }
@@ -594,9 +586,8 @@ int gpbc_fr_lsss_weights(const void *matrix, size_t n_matrices, size_t rows, siz
     TRY(lsss_args(matrix, n_matrices, rows, cols, held, k, w_out, ok_out));
     if (!k) return GPBC_OK;
     const bool one = n_matrices == 1;
-    const size_t shard_min = ((size_t)1 << 16) / (rows * cols);
     HostCall c = HostCall().input(matrix, rows * cols * GPBC_SCALAR_BYTES, one).input(held, rows);
-    return host_call_sharded(k, shard_min ? shard_min : 1, c.output(w_out, rows * GPBC_SCALAR_BYTES).output(ok_out, 1), HostRoute{},
+    return host_call_sharded(k, shard_min_units(rows * cols), c.output(w_out, rows * GPBC_SCALAR_BYTES).output(ok_out, 1), HostRoute{},
                              [=](const DevCols &d, size_t m, hipStream_t st) { return gpbc_fr_lsss_weights_dev(d.in[0], one ? 1 : m, rows, cols, d.in[1], m, d.out[0], d.out[1], st); });
 }
 
@@ -605,14 +596,13 @@ int gpbc_share_version(void) { return 1; }
 static int poly_eval_args(const void *coeffs, size_t n_coeff_rows, size_t d, const void *points, size_t n_point_rows, size_t m, size_t k, const void *out) {
     if (d < 1 || d > (size_t)FR_POLY_MAX_B || m < 1 || m > (size_t)FR_POLY_MAX_B)
         return fail(GPBC_ERR_INVALID_ARG, "d and m must be in 1 .. %d (got d = %zu, m = %zu)", FR_POLY_MAX_B, d, m);
-    if (k > (size_t)0x7fffffff / 4) return fail(GPBC_ERR_INVALID_ARG, "too many rows for one call (%zu)", k);
+    TRY(call_limit("rows", k));
     if (!k) return GPBC_OK;
-    if (n_coeff_rows != 1 && n_coeff_rows != k) return fail(GPBC_ERR_INVALID_ARG, "n_coeff_rows must be 1 or k (got %zu, k = %zu)", n_coeff_rows, k);
-    if (n_point_rows != 1 && n_point_rows != k) return fail(GPBC_ERR_INVALID_ARG, "n_point_rows must be 1 or k (got %zu, k = %zu)", n_point_rows, k);
+    TRY(one_or_k("n_coeff_rows", n_coeff_rows, k));
+    TRY(one_or_k("n_point_rows", n_point_rows, k));
     if (!coeffs || !points || !out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    const size_t out_bytes = k * m * GPBC_SCALAR_BYTES;
-    if (overlap(out, out_bytes, coeffs, n_coeff_rows * d * GPBC_SCALAR_BYTES) || overlap(out, out_bytes, points, n_point_rows * m * GPBC_SCALAR_BYTES))
-        return fail(GPBC_ERR_INVALID_ARG, "out overlaps an input");
+    const ByteRange r[3] = {{coeffs, n_coeff_rows * d * GPBC_SCALAR_BYTES}, {points, n_point_rows * m * GPBC_SCALAR_BYTES}, {out, k * m * GPBC_SCALAR_BYTES}};
+    if (outputs_overlap(r, 2, 3)) return fail(GPBC_ERR_INVALID_ARG, "out overlaps an input");
     return GPBC_OK;
 }
 int gpbc_fr_poly_eval_dev(const void *d_coeffs, size_t n_coeff_rows, size_t d, const void *d_points, size_t n_point_rows, size_t m, size_t k, void *d_out, void *stream) {
@@ -632,9 +622,8 @@ int gpbc_fr_poly_eval(const void *coeffs, size_t n_coeff_rows, size_t d, const v
     TRY(poly_eval_args(coeffs, n_coeff_rows, d, points, n_point_rows, m, k, out));
     if (!k) return GPBC_OK;
     const bool one_c = n_coeff_rows == 1, one_p = n_point_rows == 1;
-    const size_t shard_min = ((size_t)1 << 16) / (d * m);
     HostCall c = HostCall().input(coeffs, d * GPBC_SCALAR_BYTES, one_c).input(points, m * GPBC_SCALAR_BYTES, one_p);
-    return host_call_sharded(k, shard_min ? shard_min : 1, c.output(out, m * GPBC_SCALAR_BYTES), HostRoute{},
+    return host_call_sharded(k, shard_min_units(d * m), c.output(out, m * GPBC_SCALAR_BYTES), HostRoute{},
                              [=](const DevCols &dc, size_t rows, hipStream_t st) { return gpbc_fr_poly_eval_dev(dc.in[0], one_c ? 1 : rows, d, dc.in[1], one_p ? 1 : rows, m, rows, dc.out[0], st); });
 }
 
@@ -651,17 +640,15 @@ static hipError_t upload_tables(int n, const void *const *src, const size_t *byt
     if (e != hipSuccess && *block) { (void)hipFree(*block); *block = nullptr; }
     return e;
 }
-// what both forms of the tree and forest entries refuse, in this order: p[0 .. n_in) are inputs, the rest outputs; a null pointer that
-// may be absent has nb = 0
-static int handle_args(const void *h, const char *null_handle, const char *overlaps, size_t k, const void *const *p, const size_t *nb, int n_in, int n) {
+// what both forms of the tree and forest entries refuse, in this order: r[0 .. n_in) are inputs, the rest outputs; a null pointer that
+// may be absent has 0 bytes
+static int handle_args(const void *h, const char *null_handle, const char *overlaps, size_t k, const ByteRange *r, int n_in, int n) {
     if (!h) return fail(GPBC_ERR_INVALID_ARG, "%s", null_handle);
-    if (k > (size_t)0x7fffffff / 4) return fail(GPBC_ERR_INVALID_ARG, "too many items for one call (%zu)", k);
+    TRY(call_limit("items", k));
     if (!k) return GPBC_OK;
     for (int i = 0; i < n; i++)
-        if (!p[i] && nb[i]) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    for (int i = n_in; i < n; i++)
-        for (int j = 0; j < i; j++)
-            if (p[i] && p[j] && overlap(p[i], nb[i], p[j], nb[j])) return fail(GPBC_ERR_INVALID_ARG, "%s", overlaps);
+        if (!r[i].p && r[i].bytes) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
+    if (outputs_overlap(r, n_in, n)) return fail(GPBC_ERR_INVALID_ARG, "%s", overlaps);
     return GPBC_OK;
 }
 static int handle_device(int device, const char *what) {
@@ -719,9 +706,8 @@ size_t gpbc_share_tree_leaves(const gpbc_share_tree *t) { return t ? t->geom.L :
 size_t gpbc_share_tree_coeffs(const gpbc_share_tree *t) { return t ? t->geom.C : 0; }
 static int share_tree_args(const gpbc_share_tree *t, const void *secrets, const void *coeffs, size_t k, const void *out) {
     const size_t S = GPBC_SCALAR_BYTES, L = t ? t->geom.L : 0, C = t ? t->geom.C : 0;
-    const void *p[3] = {secrets, C ? coeffs : nullptr, out};
-    const size_t nb[3] = {k * S, k * C * S, k * L * S};
-    return handle_args(t, "null tree handle", "out overlaps an input", k, p, nb, 2, 3);
+    const ByteRange r[3] = {{secrets, k * S}, {C ? coeffs : nullptr, k * C * S}, {out, k * L * S}};
+    return handle_args(t, "null tree handle", "out overlaps an input", k, r, 2, 3);
 }
 int gpbc_fr_share_tree_dev(const gpbc_share_tree *t, const void *d_secrets, const void *d_coeffs, size_t k, void *d_out, void *stream) {
     TRY(share_tree_args(t, d_secrets, d_coeffs, k, d_out));
@@ -747,9 +733,8 @@ int gpbc_fr_share_tree(const gpbc_share_tree *t, const void *secrets, const void
 int gpbc_recon_version(void) { return 1; }
 static int tree_weights_args(const gpbc_share_tree *t, const uint8_t *held, size_t k, const void *w_out, const uint8_t *ok_out) {
     const size_t L = t ? t->rgeom.L : 0;
-    const void *p[3] = {held, w_out, ok_out};
-    const size_t nb[3] = {k * L, k * L * GPBC_SCALAR_BYTES, k};
-    return handle_args(t, "null tree handle", "an output overlaps an input or the other output", k, p, nb, 1, 3);
+    const ByteRange r[3] = {{held, k * L}, {w_out, k * L * GPBC_SCALAR_BYTES}, {ok_out, k}};
+    return handle_args(t, "null tree handle", "an output overlaps an input or the other output", k, r, 1, 3);
 }
 int gpbc_fr_tree_weights_dev(const gpbc_share_tree *t, const uint8_t *d_held, size_t k, void *d_w_out, uint8_t *d_ok_out, void *stream) {
     TRY(tree_weights_args(t, d_held, k, d_w_out, d_ok_out));
@@ -819,15 +804,14 @@ size_t gpbc_share_forest_leaves(const gpbc_share_forest *f) { return f ? f->sgeo
 size_t gpbc_share_forest_coeffs(const gpbc_share_forest *f) { return f ? f->sgeom.Cmax : 0; }
 size_t gpbc_share_forest_tree_leaves(const gpbc_share_forest *f, size_t t) { return f && t < f->tree_L.size() ? f->tree_L[t] : 0; }
 size_t gpbc_share_forest_tree_coeffs(const gpbc_share_forest *f, size_t t) { return f && t < f->tree_C.size() ? f->tree_C[t] : 0; }
-static int forest_args(const gpbc_share_forest *f, size_t k, const void *const *p, const size_t *nb, int n_in, int n) {
-    return handle_args(f, "null forest handle", "an output overlaps an input or another output", k, p, nb, n_in, n);
+static int forest_args(const gpbc_share_forest *f, size_t k, const ByteRange *r, int n_in, int n) {
+    return handle_args(f, "null forest handle", "an output overlaps an input or another output", k, r, n_in, n);
 }
 static int forest_device(const gpbc_share_forest *f) { return handle_device(f->device, "forest"); }
 static int share_forest_args(const gpbc_share_forest *f, const void *tree_of, const void *secrets, const void *coeffs, size_t k, const void *out, const void *ok_out) {
     const size_t S = GPBC_SCALAR_BYTES, L = f ? f->sgeom.Lmax : 0, C = f ? f->sgeom.Cmax : 0;
-    const void *p[5] = {tree_of, secrets, C ? coeffs : nullptr, out, ok_out};
-    const size_t nb[5] = {k * sizeof(uint32_t), k * S, k * C * S, k * L * S, ok_out ? k : 0};
-    return forest_args(f, k, p, nb, 3, 5);
+    const ByteRange r[5] = {{tree_of, k * sizeof(uint32_t)}, {secrets, k * S}, {C ? coeffs : nullptr, k * C * S}, {out, k * L * S}, {ok_out, ok_out ? k : 0}};
+    return forest_args(f, k, r, 3, 5);
 }
 int gpbc_fr_share_forest_dev(const gpbc_share_forest *f, const uint32_t *d_tree_of, const void *d_secrets, const void *d_coeffs, size_t k, void *d_out, uint8_t *d_ok_out, void *stream) {
     TRY(share_forest_args(f, d_tree_of, d_secrets, d_coeffs, k, d_out, d_ok_out));
@@ -853,9 +837,8 @@ int gpbc_fr_share_forest(const gpbc_share_forest *f, const uint32_t *tree_of, co
 }
 static int forest_weights_args(const gpbc_share_forest *f, const void *tree_of, const void *held, size_t k, const void *w_out, const void *ok_out) {
     const size_t L = f ? f->rgeom.Lmax : 0;
-    const void *p[4] = {tree_of, held, w_out, ok_out};
-    const size_t nb[4] = {k * sizeof(uint32_t), k * L, k * L * GPBC_SCALAR_BYTES, k};
-    return forest_args(f, k, p, nb, 2, 4);
+    const ByteRange r[4] = {{tree_of, k * sizeof(uint32_t)}, {held, k * L}, {w_out, k * L * GPBC_SCALAR_BYTES}, {ok_out, k}};
+    return forest_args(f, k, r, 2, 4);
 }
 int gpbc_fr_forest_weights_dev(const gpbc_share_forest *f, const uint32_t *d_tree_of, const uint8_t *d_held, size_t k, void *d_w_out, uint8_t *d_ok_out, void *stream) {
     TRY(forest_weights_args(f, d_tree_of, d_held, k, d_w_out, d_ok_out));
@@ -882,68 +865,50 @@ static int find_common_args(const void *sets, size_t n_sets, size_t m, const voi
                             const void *common_out, const void *ok_out) {
     const size_t lim = (size_t)FR_SELECT_MAX;
     if (m < 1 || m > lim || a < 1 || a > lim || d < 1 || d > lim) return fail(GPBC_ERR_INVALID_ARG, "m, a and d must be in 1 .. %d (got m = %zu, a = %zu, d = %zu)", FR_SELECT_MAX, m, a, d);
-    if (k > (size_t)0x7fffffff / 4) return fail(GPBC_ERR_INVALID_ARG, "too many items for one call (%zu)", k);
+    TRY(call_limit("items", k));
     if (!k) return GPBC_OK;
-    if (n_sets != 1 && n_sets != k) return fail(GPBC_ERR_INVALID_ARG, "n_sets must be 1 or k (got %zu, k = %zu)", n_sets, k);
+    TRY(one_or_k("n_sets", n_sets, k));
     if (!sets || !lists || !set_pos_out || !list_pos_out || !common_out || !ok_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    const void *p[6] = {sets, lists, set_pos_out, list_pos_out, common_out, ok_out};
-    const size_t nb[6] = {n_sets * m * GPBC_SCALAR_BYTES, k * a * GPBC_SCALAR_BYTES, k * d * sizeof(uint32_t), k * d * sizeof(uint32_t), k * d * GPBC_SCALAR_BYTES, k};
-    for (int i = 2; i < 6; i++)
-        for (int j = 0; j < i; j++)
-            if (overlap(p[i], nb[i], p[j], nb[j])) return fail(GPBC_ERR_INVALID_ARG, "an output overlaps an input or another output");
+    const ByteRange r[6] = {{sets, n_sets * m * GPBC_SCALAR_BYTES}, {lists, k * a * GPBC_SCALAR_BYTES}, {set_pos_out, k * d * sizeof(uint32_t)}, {list_pos_out, k * d * sizeof(uint32_t)},
+                            {common_out, k * d * GPBC_SCALAR_BYTES}, {ok_out, k}};
+    if (outputs_overlap(r, 2, 6)) return fail(GPBC_ERR_INVALID_ARG, "an output overlaps an input or another output");
     return GPBC_OK;
-}
-static int find_common_launch(const void *d_sets, size_t n_sets, size_t m, const void *d_lists, size_t a, size_t d, size_t k, const SelectOut &o, void *stream) {
-    TRY(bind_device());
-    const SelectGeom g = fr_select_geometry(m, a, d, n_sets == 1);
-    const unsigned grid = (unsigned)fr_select_grid(g, k);
-    if (g.large) return GPBC_LAUNCH(k_fr_find_common_large, grid, BLOCK, (hipStream_t)stream, (const uint8_t *)d_sets, (const uint8_t *)d_lists, k, g, o);
-    return GPBC_LAUNCH(k_fr_find_common, grid, BLOCK, (hipStream_t)stream, (const uint8_t *)d_sets, (const uint8_t *)d_lists, k, g, o);
 }
 int gpbc_fr_find_common_dev(const void *d_sets, size_t n_sets, size_t m, const void *d_lists, size_t a, size_t d, size_t k, uint32_t *d_set_pos_out, uint32_t *d_list_pos_out,
                             void *d_common_out, uint8_t *d_ok_out, void *stream) {
     TRY(find_common_args(d_sets, n_sets, m, d_lists, a, d, k, d_set_pos_out, d_list_pos_out, d_common_out, d_ok_out));
     if (!k) return GPBC_OK;
-    return find_common_launch(d_sets, n_sets, m, d_lists, a, d, k,
-                              SelectOut{(uint8_t *)d_set_pos_out, (uint8_t *)d_list_pos_out, (uint8_t *)d_common_out, d_ok_out, d * sizeof(uint32_t), d * GPBC_SCALAR_BYTES}, stream);
+    TRY(bind_device());
+    const SelectGeom g = fr_select_geometry(m, a, d, n_sets == 1);
+    const SelectOut o{(uint8_t *)d_set_pos_out, (uint8_t *)d_list_pos_out, (uint8_t *)d_common_out, d_ok_out, d * sizeof(uint32_t), d * GPBC_SCALAR_BYTES};
+    const unsigned grid = (unsigned)fr_select_grid(g, k);
+    if (g.large) return GPBC_LAUNCH(k_fr_find_common_large, grid, BLOCK, (hipStream_t)stream, (const uint8_t *)d_sets, (const uint8_t *)d_lists, k, g, o);
+    return GPBC_LAUNCH(k_fr_find_common, grid, BLOCK, (hipStream_t)stream, (const uint8_t *)d_sets, (const uint8_t *)d_lists, k, g, o);
 }
 // Host-pointer form: the unit is an item; a shard needs about 2^16 comparisons to pay for its thread and transfers.  A set given once
-// travels whole to every shard.  The staging path carries two output columns, so an item's three rows travel as one record of 40 d bytes
-// (set positions, list positions, values; the kernel writes the record's parts at the record's pitch) and are dealt out here.
+// travels whole to every shard; the four outputs are the staging path's four output columns.
 int gpbc_fr_find_common(const void *sets, size_t n_sets, size_t m, const void *lists, size_t a, size_t d, size_t k, uint32_t *set_pos_out, uint32_t *list_pos_out, void *common_out,
                         uint8_t *ok_out) {
     TRY(find_common_args(sets, n_sets, m, lists, a, d, k, set_pos_out, list_pos_out, common_out, ok_out));
     if (!k) return GPBC_OK;
     const bool one = n_sets == 1;
-    const size_t shard_min = ((size_t)1 << 16) / (m * a), pb = d * sizeof(uint32_t), cb = d * GPBC_SCALAR_BYTES, rec = 2 * pb + cb;
-    std::vector<uint8_t> records, oks;
-    try { records.resize(k * rec); oks.resize(k); } catch (const std::bad_alloc &) { return fail(GPBC_ERR_INTERNAL, "out of host memory for %zu records", k); }
     HostCall c = HostCall().input(sets, m * GPBC_SCALAR_BYTES, one).input(lists, a * GPBC_SCALAR_BYTES);
-    TRY(host_call_sharded(k, shard_min ? shard_min : 1, c.output(records.data(), rec).output(oks.data(), 1), HostRoute{},
-                          [=](const DevCols &dc, size_t n, hipStream_t st) {
-                              return find_common_launch(dc.in[0], one ? 1 : n, m, dc.in[1], a, d, n, SelectOut{dc.out[0], dc.out[0] + pb, dc.out[0] + 2 * pb, dc.out[1], rec, rec}, st);
-                          }));
-    for (size_t j = 0; j < k; j++) {
-        const uint8_t *r = records.data() + j * rec;
-        memcpy((uint8_t *)set_pos_out + j * pb, r, pb);
-        memcpy((uint8_t *)list_pos_out + j * pb, r + pb, pb);
-        memcpy((uint8_t *)common_out + j * cb, r + 2 * pb, cb);
-    }
-    memcpy(ok_out, oks.data(), k);
-    return GPBC_OK;
+    c.output(set_pos_out, d * sizeof(uint32_t)).output(list_pos_out, d * sizeof(uint32_t)).output(common_out, d * GPBC_SCALAR_BYTES).output(ok_out, 1);
+    return host_call_sharded(k, shard_min_units(m * a), c, HostRoute{}, [=](const DevCols &dc, size_t n, hipStream_t st) {
+        return gpbc_fr_find_common_dev(dc.in[0], one ? 1 : n, m, dc.in[1], a, d, n, (uint32_t *)dc.out[0], (uint32_t *)dc.out[1], dc.out[2], dc.out[3], st);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ LSSS share entries (include/gpbc_bn254_indexed.h)
 static int lsss_shares_args(const void *matrix, size_t n_matrices, size_t rows, size_t cols, const void *vectors, size_t k, const void *out) {
     if (rows < 1 || rows > (size_t)FR_LSSS_MAX || cols < 1 || cols > (size_t)FR_LSSS_MAX)
         return fail(GPBC_ERR_INVALID_ARG, "rows and cols must be in 1 .. %d (got rows = %zu, cols = %zu)", FR_LSSS_MAX, rows, cols);
-    if (k > (size_t)0x7fffffff / 4) return fail(GPBC_ERR_INVALID_ARG, "too many vectors for one call (%zu)", k);
+    TRY(call_limit("vectors", k));
     if (!k) return GPBC_OK;
-    if (n_matrices != 1 && n_matrices != k) return fail(GPBC_ERR_INVALID_ARG, "n_matrices must be 1 or k (got %zu, k = %zu)", n_matrices, k);
+    TRY(one_or_k("n_matrices", n_matrices, k));
     if (!matrix || !vectors || !out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    const size_t ob = k * rows * GPBC_SCALAR_BYTES;
-    if (overlap(out, ob, matrix, n_matrices * rows * cols * GPBC_SCALAR_BYTES) || overlap(out, ob, vectors, k * cols * GPBC_SCALAR_BYTES))
-        return fail(GPBC_ERR_INVALID_ARG, "out overlaps an input");
+    const ByteRange r[3] = {{matrix, n_matrices * rows * cols * GPBC_SCALAR_BYTES}, {vectors, k * cols * GPBC_SCALAR_BYTES}, {out, k * rows * GPBC_SCALAR_BYTES}};
+    if (outputs_overlap(r, 2, 3)) return fail(GPBC_ERR_INVALID_ARG, "out overlaps an input");
     return GPBC_OK;
 }
 int gpbc_fr_lsss_shares_dev(const void *d_matrix, size_t n_matrices, size_t rows, size_t cols, const void *d_vectors, size_t k, void *d_out, void *stream) {
@@ -961,9 +926,8 @@ int gpbc_fr_lsss_shares(const void *matrix, size_t n_matrices, size_t rows, size
     TRY(lsss_shares_args(matrix, n_matrices, rows, cols, vectors, k, out));
     if (!k) return GPBC_OK;
     const bool one = n_matrices == 1;
-    const size_t shard_min = ((size_t)1 << 16) / (rows * cols);
     HostCall c = HostCall().input(matrix, rows * cols * GPBC_SCALAR_BYTES, one).input(vectors, cols * GPBC_SCALAR_BYTES);
-    return host_call_sharded(k, shard_min ? shard_min : 1, c.output(out, rows * GPBC_SCALAR_BYTES), HostRoute{},
+    return host_call_sharded(k, shard_min_units(rows * cols), c.output(out, rows * GPBC_SCALAR_BYTES), HostRoute{},
                              [=](const DevCols &d, size_t m, hipStream_t st) { return gpbc_fr_lsss_shares_dev(d.in[0], one ? 1 : m, rows, cols, d.in[1], m, d.out[0], st); });
 }
 
@@ -973,60 +937,47 @@ static int formula_sizes(size_t n_nodes, size_t rows, size_t cols, size_t k) {
     if (n_nodes < 1 || n_nodes > (size_t)FORMULA_MAX_NODES) return fail(GPBC_ERR_INVALID_ARG, "n_nodes must be in 1 .. %d (got %zu)", FORMULA_MAX_NODES, n_nodes);
     if (rows < 1 || rows > (size_t)FORMULA_MAX || cols < 1 || cols > (size_t)FORMULA_MAX)
         return fail(GPBC_ERR_INVALID_ARG, "rows and cols must be in 1 .. %d (got rows = %zu, cols = %zu)", FORMULA_MAX, rows, cols);
-    if (k > (size_t)0x7fffffff / 4) return fail(GPBC_ERR_INVALID_ARG, "too many items for one call (%zu)", k);
-    return GPBC_OK;
+    return call_limit("items", k);
 }
 static int from_formula_args(const void *nodes, size_t n_nodes, size_t k, size_t rows, size_t cols, const void *matrix_out, const void *rho_out, const void *dims_out, const void *ok_out) {
     TRY(formula_sizes(n_nodes, rows, cols, k));
     if (!k) return GPBC_OK;
     if (!nodes || !matrix_out || !rho_out || !ok_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    const void *p[5] = {nodes, matrix_out, rho_out, ok_out, dims_out};
-    const size_t nb[5] = {k * n_nodes * sizeof(int64_t), k * rows * cols * GPBC_SCALAR_BYTES, k * rows * sizeof(int64_t), k, k * 2 * sizeof(uint32_t)};
-    for (int i = 1; i < (dims_out ? 5 : 4); i++)
-        for (int j = 0; j < i; j++)
-            if (overlap(p[i], nb[i], p[j], nb[j])) return fail(GPBC_ERR_INVALID_ARG, "an output overlaps the input or another output");
+    const ByteRange r[5] = {{nodes, k * n_nodes * sizeof(int64_t)}, {matrix_out, k * rows * cols * GPBC_SCALAR_BYTES}, {rho_out, k * rows * sizeof(int64_t)}, {ok_out, k},
+                            {dims_out, k * 2 * sizeof(uint32_t)}};
+    if (outputs_overlap(r, 1, 5)) return fail(GPBC_ERR_INVALID_ARG, "an output overlaps the input or another output");
     return GPBC_OK;
 }
-static int from_formula_launch(const void *d_nodes, size_t n_nodes, size_t k, size_t rows, size_t cols, const FormulaOut &o, void *stream) {
-    TRY(bind_device());
-    const FormulaGeom g = formula_build_geometry(n_nodes, rows, cols, (((uintptr_t)o.matrix | o.mat_step) & 15) == 0);
-    return GPBC_LAUNCH(k_fr_lsss_from_formula, (unsigned)formula_grid(g, k), BLOCK, (hipStream_t)stream, (const int64_t *)d_nodes, k, g, o);
-}
+// The kernel stores a matrix 128 bits at a time when its address and pitch allow it.  From the host form they always do: every staging route
+// starts a column at a 256-byte aligned device address (a lane's pinned block, a device block) and the matrix pitch, rows x cols x 32 bytes,
+// is a multiple of 32 — so is the step of a pipelined chunk.
 int gpbc_fr_lsss_from_formula_dev(const int64_t *d_nodes, size_t n_nodes, size_t k, size_t rows, size_t cols, void *d_matrix_out, int64_t *d_rho_out, uint32_t *d_dims_out,
                                   uint8_t *d_ok_out, void *stream) {
     TRY(from_formula_args(d_nodes, n_nodes, k, rows, cols, d_matrix_out, d_rho_out, d_dims_out, d_ok_out));
     if (!k) return GPBC_OK;
-    return from_formula_launch(d_nodes, n_nodes, k, rows, cols,
-                               FormulaOut{(uint8_t *)d_matrix_out, (uint8_t *)d_rho_out, (uint8_t *)d_dims_out, d_ok_out, rows * cols * GPBC_SCALAR_BYTES, rows * sizeof(int64_t), 2 * sizeof(uint32_t)}, stream);
+    TRY(bind_device());
+    const FormulaOut o{(uint8_t *)d_matrix_out, (uint8_t *)d_rho_out, (uint8_t *)d_dims_out, d_ok_out, rows * cols * GPBC_SCALAR_BYTES, rows * sizeof(int64_t), 2 * sizeof(uint32_t)};
+    const FormulaGeom g = formula_build_geometry(n_nodes, rows, cols, (((uintptr_t)o.matrix | o.mat_step) & 15) == 0);
+    return GPBC_LAUNCH(k_fr_lsss_from_formula, (unsigned)formula_grid(g, k), BLOCK, (hipStream_t)stream, d_nodes, k, g, o);
 }
-// Host-pointer form: the shared staging path on the current device.  It carries two output columns, so an item's matrix, rho and dims travel
-// as one record (the kernel writes the record's parts at the record's pitch, a multiple of 16) and are dealt out here.
+// Host-pointer form: the shared staging path on the current device, the four outputs as its four output columns (dims_out == NULL: that
+// column is not wanted, and the device form is told so).
 int gpbc_fr_lsss_from_formula(const int64_t *nodes, size_t n_nodes, size_t k, size_t rows, size_t cols, void *matrix_out, int64_t *rho_out, uint32_t *dims_out, uint8_t *ok_out) {
     TRY(from_formula_args(nodes, n_nodes, k, rows, cols, matrix_out, rho_out, dims_out, ok_out));
     if (!k) return GPBC_OK;
-    const size_t mb = rows * cols * GPBC_SCALAR_BYTES, rb = rows * sizeof(int64_t), db = 2 * sizeof(uint32_t), rec = (mb + rb + db + 15) / 16 * 16;
-    std::vector<uint8_t> records, oks;
-    try { records.resize(k * rec); oks.resize(k); } catch (const std::bad_alloc &) { return fail(GPBC_ERR_INTERNAL, "out of host memory for %zu records", k); }
-    TRY(host_call(k, HostCall().input(nodes, n_nodes * sizeof(int64_t)).output(records.data(), rec).output(oks.data(), 1), HostRoute{},
-                  [=](const DevCols &dc, size_t n, hipStream_t st) {
-                      return from_formula_launch(dc.in[0], n_nodes, n, rows, cols, FormulaOut{dc.out[0], dc.out[0] + mb, dc.out[0] + mb + rb, dc.out[1], rec, rec, rec}, st);
-                  }));
-    for (size_t j = 0; j < k; j++) {
-        const uint8_t *r = records.data() + j * rec;
-        memcpy((uint8_t *)matrix_out + j * mb, r, mb);
-        memcpy((uint8_t *)rho_out + j * rb, r + mb, rb);
-        if (dims_out) memcpy((uint8_t *)dims_out + j * db, r + mb + rb, db);
-    }
-    memcpy(ok_out, oks.data(), k);
-    return GPBC_OK;
+    HostCall c = HostCall().input(nodes, n_nodes * sizeof(int64_t));
+    c.output(matrix_out, rows * cols * GPBC_SCALAR_BYTES).output(rho_out, rows * sizeof(int64_t)).output(dims_out, 2 * sizeof(uint32_t)).output(ok_out, 1);
+    return host_call(k, c, HostRoute{}, [=](const DevCols &dc, size_t n, hipStream_t st) {
+        return gpbc_fr_lsss_from_formula_dev((const int64_t *)dc.in[0], n_nodes, n, rows, cols, dc.out[0], (int64_t *)dc.out[1], (uint32_t *)dc.out[2], dc.out[3], st);
+    });
 }
 static int formula_select_args(const void *nodes, size_t n_formulas, size_t n_nodes, const void *held, size_t k, size_t rows, const void *chosen_out, const void *ok_out) {
     TRY(formula_sizes(n_nodes, rows, 1, k));
     if (!k) return GPBC_OK;
-    if (n_formulas != 1 && n_formulas != k) return fail(GPBC_ERR_INVALID_ARG, "n_formulas must be 1 or k (got %zu, k = %zu)", n_formulas, k);
+    TRY(one_or_k("n_formulas", n_formulas, k));
     if (!nodes || !held || !chosen_out || !ok_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    const size_t fb = n_formulas * n_nodes * sizeof(int64_t), hb = k * rows;
-    if (overlap(chosen_out, hb, nodes, fb) || overlap(chosen_out, hb, held, hb) || overlap(ok_out, k, nodes, fb) || overlap(ok_out, k, held, hb) || overlap(chosen_out, hb, ok_out, k))
+    const ByteRange r[4] = {{nodes, n_formulas * n_nodes * sizeof(int64_t)}, {held, k * rows}, {chosen_out, k * rows}, {ok_out, k}};
+    if (outputs_overlap(r, 2, 4))
         return fail(GPBC_ERR_INVALID_ARG, "an output overlaps an input or the other output");
     return GPBC_OK;
 }

@@ -22,7 +22,7 @@ extern "C" {
 static int group_dev(bool g2, int op, const void *d_a, const void *d_b, size_t nb, size_t n, void *d_out, void *stream) {
     if (!n) return GPBC_OK;
     if (!d_a || !d_out || (op != GROUP_DBL && !d_b)) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    if (op != GROUP_DBL && nb != 1 && nb != n) return fail(GPBC_ERR_INVALID_ARG, "nb must be 1 or n (got nb = %zu, n = %zu)", nb, n);
+    if (op != GROUP_DBL) TRY(nb_one_or_n(nb, n));
     TRY(bind_device());
     const hipStream_t st = (hipStream_t)stream;
     const uint8_t *a = (const uint8_t *)d_a, *b = op == GROUP_DBL ? a : (const uint8_t *)d_b;
@@ -47,7 +47,7 @@ constexpr size_t GROUP_SHARD_MIN = 4 * 4096;
 static int group_host(bool g2, int op, const void *a, const void *b, size_t nb, size_t n, void *out) {
     if (!n) return GPBC_OK;
     if (!a || !out || (op != GROUP_DBL && !b)) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    if (op != GROUP_DBL && nb != 1 && nb != n) return fail(GPBC_ERR_INVALID_ARG, "nb must be 1 or n (got nb = %zu, n = %zu)", nb, n);
+    if (op != GROUP_DBL) TRY(nb_one_or_n(nb, n));
     const size_t pt = g2 ? GPBC_G2_BYTES : GPBC_G1_BYTES;
     const bool one = op != GROUP_DBL && nb == 1;
     HostCall c = HostCall().input(a, pt);

@@ -79,10 +79,6 @@ int gpbc_gt_fixed_base_destroy(gpbc_gt_fixed_base *h) {
     return GPBC_OK;
 }
 
-static bool gtfb_overlap(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return a && b && pa < pb + nb && pb < pa + na;
-}
 // Everything that can be said without the device: the limits, then the pointers and their ranges (an output row is 384 bytes whatever
 // the table), then the handle — a null handle is refused also where there is nothing to do, as gpbc_fixed_base_indexed refuses it.
 static int gtfb_indexed_args(const gpbc_gt_fixed_base *h, const uint32_t *index, size_t n_index_rows, size_t terms, const void *scalars, size_t n, const void *out, const uint8_t *ok_out) {
@@ -91,8 +87,8 @@ static int gtfb_indexed_args(const gpbc_gt_fixed_base *h, const uint32_t *index,
     if (n) {
         if (n_index_rows < 1 || n_index_rows > n) return fail(GPBC_ERR_INVALID_ARG, "n_index_rows must be in 1 .. n (got %zu, n = %zu)", n_index_rows, n);
         if (!index || !scalars || !out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-        const size_t ib = n_index_rows * terms * sizeof(uint32_t), sb = n * terms * GPBC_SCALAR_BYTES, ob = n * GPBC_GT_BYTES;
-        if (gtfb_overlap(out, ob, index, ib) || gtfb_overlap(out, ob, scalars, sb) || gtfb_overlap(ok_out, n, index, ib) || gtfb_overlap(ok_out, n, scalars, sb) || gtfb_overlap(out, ob, ok_out, n))
+        const ByteRange r[4] = {{index, n_index_rows * terms * sizeof(uint32_t)}, {scalars, n * terms * GPBC_SCALAR_BYTES}, {out, n * GPBC_GT_BYTES}, {ok_out, n}};
+        if (outputs_overlap(r, 2, 4))
             return fail(GPBC_ERR_INVALID_ARG, "an output overlaps an input or the other output");
     }
     if (!h) return fail(GPBC_ERR_INVALID_ARG, "null table handle");

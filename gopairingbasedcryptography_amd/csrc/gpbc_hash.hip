@@ -54,8 +54,7 @@ constexpr size_t RANDOM_MAX_N = (size_t)0x7fffffff * BLOCK;                  // 
 static int random_args(const void *seed, size_t first, size_t n, const void *out) {
     if (!seed || !out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
     if (first && n > (size_t)0 - first) return fail(GPBC_ERR_INVALID_ARG, "first + n exceeds 2^64 (first = %zu, n = %zu)", first, n);
-    if (n > RANDOM_MAX_N) return fail(GPBC_ERR_INVALID_ARG, "too many elements for one call (%zu)", n);
-    return GPBC_OK;
+    return call_limit("elements", n, RANDOM_MAX_N);
 }
 static bool wide_at(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
@@ -94,9 +93,8 @@ int gpbc_fr_random(const void *seed, size_t stream, size_t first, size_t n, void
 }
 static int set_bytes64_args(const void *in, size_t n, const void *out) {
     if (!in || !out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    if (n > RANDOM_MAX_N) return fail(GPBC_ERR_INVALID_ARG, "too many elements for one call (%zu)", n);
-    const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
-    if (a < b + n * GPBC_SCALAR_BYTES && b < a + n * GPBC_RANDOM_BLOCK_BYTES) return fail(GPBC_ERR_INVALID_ARG, "out overlaps in");
+    TRY(call_limit("elements", n, RANDOM_MAX_N));
+    if (ranges_overlap(in, n * GPBC_RANDOM_BLOCK_BYTES, out, n * GPBC_SCALAR_BYTES)) return fail(GPBC_ERR_INVALID_ARG, "out overlaps in");
     return GPBC_OK;
 }
 int gpbc_fr_set_bytes64_dev(const void *d_in, size_t n, void *d_out, void *hip_stream) {

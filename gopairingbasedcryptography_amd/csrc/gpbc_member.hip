@@ -43,11 +43,10 @@ int gpbc_member_version(void) { return 1; }
 static size_t member_row_bytes(int kind) { return kind == 0 ? GPBC_G1_BYTES : kind == 3 ? GPBC_GT_BYTES : GPBC_G2_BYTES; }
 static int member_args(int kind, const void *in, size_t n, const void *ok_out) {
     if (!n) return GPBC_OK;
-    if (n > (size_t)0x7fffffff) return fail(GPBC_ERR_INVALID_ARG, "too many rows for one call (%zu)", n);
+    TRY(call_limit("rows", n, 0x7fffffff));
     if (!in || !ok_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
     if ((uintptr_t)in & 3) return fail(GPBC_ERR_INVALID_ARG, "rows must be 4-byte aligned");
-    const uintptr_t a = (uintptr_t)in, o = (uintptr_t)ok_out;
-    if (a < o + n && o < a + n * member_row_bytes(kind)) return fail(GPBC_ERR_INVALID_ARG, "ok_out overlaps the input");
+    if (ranges_overlap(in, n * member_row_bytes(kind), ok_out, n)) return fail(GPBC_ERR_INVALID_ARG, "ok_out overlaps the input");
     return GPBC_OK;
 }
 static int member_dev(int kind, const void *d_in, size_t n, uint8_t *d_ok_out, void *stream) {

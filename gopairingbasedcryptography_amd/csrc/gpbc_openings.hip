@@ -126,13 +126,9 @@ int upload_table_async(const void *src, size_t bytes, void *d_dst, hipStream_t s
     HIP_TRY(hipEventRecord(s.ev, st));
     return GPBC_OK;
 }
-bool opn_overlap(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return a && b && na && nb && pa < pb + nb && pb < pa + na;
-}
 // the segment table and what it implies: *n = identities, *m_max = the longest segment; limit = the longest segment allowed
 int opn_segments(const uint64_t *seg_off, size_t k, size_t limit, const char *limit_text, size_t *n, size_t *m_max) {
-    if (k > (size_t)0x7fffffff) return fail(GPBC_ERR_INVALID_ARG, "too many segments for one call (%zu)", k);
+    TRY(call_limit("segments", k, 0x7fffffff));
     TRY(check_segment_table(seg_off, k, n));
     *m_max = 0;
     for (size_t j = 0; j < k; j++) {
@@ -148,17 +144,17 @@ int roots_segments_args(const void *roots, const uint64_t *seg_off, size_t k, si
     const size_t limit = stride - 1 < (size_t)FR_POLY_MAX_B ? stride - 1 : (size_t)FR_POLY_MAX_B;
     TRY(opn_segments(seg_off, k, limit, stride - 1 < (size_t)FR_POLY_MAX_B ? "stride - 1" : "FR_POLY_MAX_B", n, &m_max));
     if ((*n && !roots) || !coeffs_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    if (opn_overlap(coeffs_out, k * stride * GPBC_SCALAR_BYTES, roots, *n * GPBC_SCALAR_BYTES)) return fail(GPBC_ERR_INVALID_ARG, "coeffs_out overlaps the roots");
+    if (ranges_overlap(coeffs_out, k * stride * GPBC_SCALAR_BYTES, roots, *n * GPBC_SCALAR_BYTES)) return fail(GPBC_ERR_INVALID_ARG, "coeffs_out overlaps the roots");
     return GPBC_OK;
 }
 int openings_args(const gpbc_fixed_base *h, const void *coeffs, const void *ids, const uint64_t *seg_off, size_t k, const void *out, const uint8_t *ok_out, size_t *n, size_t *m_max) {
     if (!h) return fail(GPBC_ERR_INVALID_ARG, "null table handle");
     TRY(opn_segments(seg_off, k, h->nbase - 1 < (size_t)FR_POLY_MAX_B ? h->nbase - 1 : (size_t)FR_POLY_MAX_B, h->nbase - 1 < (size_t)FR_POLY_MAX_B ? "nbase - 1" : "FR_POLY_MAX_B", n, m_max));
-    if (*n > (size_t)0x7fffffff) return fail(GPBC_ERR_INVALID_ARG, "too many identities for one call (%zu)", *n);
+    TRY(call_limit("identities", *n, 0x7fffffff));
     if (!*n) return GPBC_OK;
     if (!coeffs || !ids || !out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    const size_t cb = k * h->nbase * GPBC_SCALAR_BYTES, ib = *n * GPBC_SCALAR_BYTES, ob = *n * (h->is_g2 ? GPBC_G2_BYTES : GPBC_G1_BYTES);
-    if (opn_overlap(out, ob, coeffs, cb) || opn_overlap(out, ob, ids, ib) || opn_overlap(ok_out, *n, coeffs, cb) || opn_overlap(ok_out, *n, ids, ib) || opn_overlap(out, ob, ok_out, *n))
+    const ByteRange r[4] = {{coeffs, k * h->nbase * GPBC_SCALAR_BYTES}, {ids, *n * GPBC_SCALAR_BYTES}, {out, *n * (h->is_g2 ? GPBC_G2_BYTES : GPBC_G1_BYTES)}, {ok_out, *n}};
+    if (outputs_overlap(r, 2, 4))
         return fail(GPBC_ERR_INVALID_ARG, "an output overlaps an input or the other output");
     return GPBC_OK;
 }

@@ -829,10 +829,10 @@ int gpbc_gt_inverse_batch_dev(const void *a, size_t n, void *o, void *s) { retur
 static int gt_equal_args(const void *a, const void *b, size_t nb, size_t n, const void *ok_out) {
     if (!n) return GPBC_OK;
     if (nb != n && nb != 1) return fail(GPBC_ERR_INVALID_ARG, "nb must be n or 1 (got nb = %zu, n = %zu)", nb, n);
-    if (n > (size_t)0x7fffffff / GT_EQUAL_LANES) return fail(GPBC_ERR_INVALID_ARG, "too many rows for one call (%zu)", n);
+    TRY(call_limit("rows", n, (size_t)0x7fffffff / GT_EQUAL_LANES));
     if (!a || !b || !ok_out) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    const uint8_t *ab = (const uint8_t *)a, *bb = (const uint8_t *)b, *ob = (const uint8_t *)ok_out;
-    if ((ab < ob + n && ob < ab + n * GPBC_GT_BYTES) || (bb < ob + n && ob < bb + nb * GPBC_GT_BYTES)) return fail(GPBC_ERR_INVALID_ARG, "ok_out overlaps an input");
+    const ByteRange r[3] = {{a, n * GPBC_GT_BYTES}, {b, nb * GPBC_GT_BYTES}, {ok_out, n}};
+    if (outputs_overlap(r, 2, 3)) return fail(GPBC_ERR_INVALID_ARG, "ok_out overlaps an input");
     return GPBC_OK;
 }
 int gpbc_gt_equal_dev(const void *d_a, const void *d_b, size_t nb, size_t n, uint8_t *d_ok_out, void *stream) {

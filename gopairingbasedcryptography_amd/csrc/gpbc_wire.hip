@@ -477,18 +477,14 @@ int gpbc_hash_to_field_dev(const void *m, const uint64_t *off, size_t mb, size_t
 int gpbc_mask_version(void) { return 1; }
 
 constexpr size_t MASK_MAX_N = (size_t)0x7fffffff * MASK_BLOCK / MASK_WINDOWS;      // the grid's x extent, twelve lanes per item
-static bool ranges_meet(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return na && nb && x < y + nb && y < x + na;
-}
 int gpbc_gt_xor_mask_dev(const void *d_gt, const void *d_msgs, const uint64_t *d_msg_off, size_t msgs_bytes, size_t width, size_t n, void *d_out,
                          uint32_t *d_out_len, void *stream) {
     if (!n) return GPBC_OK;
-    if (n > MASK_MAX_N) return fail(GPBC_ERR_INVALID_ARG, "too many items for one call (%zu)", n);
+    TRY(call_limit("items", n, MASK_MAX_N));
     if (!d_msg_off && width && n > msgs_bytes / width) return fail(GPBC_ERR_INVALID_ARG, "n * width exceeds msgs_bytes (n = %zu, width = %zu, msgs_bytes = %zu)", n, width, msgs_bytes);
     const size_t span = d_msg_off ? msgs_bytes : n * width;        // what the messages, and the output, can occupy
     if (!d_gt || (span && (!d_msgs || !d_out))) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
-    if (ranges_meet(d_gt, n * GPBC_GT_BYTES, d_out, span)) return fail(GPBC_ERR_INVALID_ARG, "out overlaps gt");
+    if (ranges_overlap(d_gt, n * GPBC_GT_BYTES, d_out, span)) return fail(GPBC_ERR_INVALID_ARG, "out overlaps gt");
     TRY(bind_device());
     const int wpi = mask_lanes_per_item(!d_msg_off, width);
     const size_t lanes = d_msg_off ? (n + MASK_GROUP - 1) / MASK_GROUP * MASK_GROUP * MASK_WINDOWS : n * (size_t)wpi;
@@ -500,7 +496,7 @@ int gpbc_gt_xor_mask_dev(const void *d_gt, const void *d_msgs, const uint64_t *d
 // messages and that copy comes back into `out`; not combined with other threads' calls, not sharded.
 int gpbc_gt_xor_mask(const void *gt, const void *msgs, const uint64_t *msg_off, size_t width, size_t n, void *out, uint32_t *out_len) {
     if (!n) return GPBC_OK;
-    if (n > MASK_MAX_N) return fail(GPBC_ERR_INVALID_ARG, "too many items for one call (%zu)", n);
+    TRY(call_limit("items", n, MASK_MAX_N));
     if (!gt) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
     uint64_t base = 0, bytes = 0;
     std::vector<uint64_t> rel;
@@ -516,9 +512,9 @@ int gpbc_gt_xor_mask(const void *gt, const void *msgs, const uint64_t *msg_off, 
     if (bytes && (!msgs || !out)) return fail(GPBC_ERR_INVALID_ARG, "null pointer");
     const uint8_t *src = bytes ? (const uint8_t *)msgs + base : nullptr;
     uint8_t *dst = bytes ? (uint8_t *)out + base : nullptr;
-    if (ranges_meet(gt, n * GPBC_GT_BYTES, dst, bytes)) return fail(GPBC_ERR_INVALID_ARG, "out overlaps gt");
-    if (out != msgs && ranges_meet(src, bytes, dst, bytes)) return fail(GPBC_ERR_INVALID_ARG, "out overlaps msgs (only out == msgs runs in place)");
-    if (out_len && (ranges_meet(out_len, n * sizeof(uint32_t), dst, bytes) || ranges_meet(out_len, n * sizeof(uint32_t), gt, n * GPBC_GT_BYTES)))
+    if (ranges_overlap(gt, n * GPBC_GT_BYTES, dst, bytes)) return fail(GPBC_ERR_INVALID_ARG, "out overlaps gt");
+    if (out != msgs && ranges_overlap(src, bytes, dst, bytes)) return fail(GPBC_ERR_INVALID_ARG, "out overlaps msgs (only out == msgs runs in place)");
+    if (out_len && (ranges_overlap(out_len, n * sizeof(uint32_t), dst, bytes) || ranges_overlap(out_len, n * sizeof(uint32_t), gt, n * GPBC_GT_BYTES)))
         return fail(GPBC_ERR_INVALID_ARG, "out_len overlaps out or gt");
     // ONE unit of whole columns: column 0 is the message bytes and, in place, the output
     HostCall c = HostCall().input(src, bytes, true).input(gt, n * GPBC_GT_BYTES, true);

@@ -45,9 +45,7 @@ int gpbc_formula_version(void);             /* 1 */
  *   dims 0, 0.  That is a verdict on the data, not an argument error.
  * 1 <= n_nodes <= 127; 1 <= rows, cols <= 64; k < 2^29; k == 0 is a no-op.  A null pointer other than dims_out, a size out of range, or
  * an output that overlaps the input or another output is GPBC_ERR_INVALID_ARG before any launch, with nothing written.  The host form
- * runs on the calling thread's current device.  Its staging path carries two output columns, so an item's matrix, rho and dims come back
- * as one record and are copied out to the caller's arrays on the host: it needs a second host copy of the outputs (rows x cols x 32 +
- * rows x 8 + 8 bytes per item, 128 KiB at 64 x 64) for the length of the call.  The _dev form writes the caller's buffers directly. */
+ * runs on the calling thread's current device and copies each output straight into the caller's array. */
 int gpbc_fr_lsss_from_formula(const int64_t *nodes, size_t n_nodes, size_t k, size_t rows, size_t cols, void *matrix_out, int64_t *rho_out,
                               uint32_t *dims_out, uint8_t *ok_out);
 int gpbc_fr_lsss_from_formula_dev(const int64_t *d_nodes, size_t n_nodes, size_t k, size_t rows, size_t cols, void *d_matrix_out,

@@ -145,6 +145,45 @@ int main() {
         EXPECT(S7.Equal(want7));
     }
     printf("sharded host entries identical to one device: %zu pairings, %zu ragged segments, scalar mults, GT, wire, sums\n", N, k);
+    {   // a host call with FOUR output columns cut into shards: the common attributes of kc (set, list) items, m = 32, a = 24, d = 8; a shard
+        // needs 2^16 / (m a) = 85 items and kc = 256 is three times that.  Each output has a guard row behind it; ONE _dev call over the whole
+        // batch is the reference.  A shared set travels whole to every shard, per-item sets are sliced.
+        const size_t m = 32, al = 24, d = 8, kc = 256;
+        std::vector<Scalar> sets(kc * m), lists(kc * al);
+        for (size_t j = 0; j < kc; j++) {
+            for (size_t u = 0; u < m; u++) sets[j * m + u] = Scalar(3 * u + j % 5 + 1);
+            for (size_t t = 0; t < al; t++) lists[j * al + t] = Scalar(j % 9 == 0 ? 1000 + t : 2 * t + j % 7 + 1);      // every ninth item has nothing in common
+        }
+        const size_t pos_bytes = kc * d * sizeof(uint32_t), val_bytes = kc * d * sizeof(Scalar);
+        void *dS, *dL, *dSp, *dLp, *dC, *dOk;
+        HIP_OK(hipSetDevice(gpbc_device_at(0)));
+        HIP_OK(hipMalloc(&dS, sets.size() * sizeof(Scalar))); HIP_OK(hipMalloc(&dL, lists.size() * sizeof(Scalar)));
+        HIP_OK(hipMalloc(&dSp, pos_bytes)); HIP_OK(hipMalloc(&dLp, pos_bytes)); HIP_OK(hipMalloc(&dC, val_bytes)); HIP_OK(hipMalloc(&dOk, kc));
+        HIP_OK(hipMemcpy(dS, sets.data(), sets.size() * sizeof(Scalar), hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(dL, lists.data(), lists.size() * sizeof(Scalar), hipMemcpyHostToDevice));
+        const auto guarded = [](const std::vector<uint8_t> &v, size_t used) {
+            for (size_t i = used; i < v.size(); i++) if (v[i] != 0xA5) return false;
+            return v.size() > used;
+        };
+        for (int shared = 0; shared < 2; shared++) {
+            const size_t n_sets = shared ? 1 : kc;
+            std::vector<uint8_t> sp(pos_bytes + d * sizeof(uint32_t), 0xA5), lp(sp), cm(val_bytes + d * sizeof(Scalar), 0xA5), okc(kc + 1, 0xA5);
+            check(gpbc_fr_find_common(sets.data(), n_sets, m, lists.data(), al, d, kc, (uint32_t *)sp.data(), (uint32_t *)lp.data(), cm.data(), okc.data()));
+            EXPECT(guarded(sp, pos_bytes) && guarded(lp, pos_bytes) && guarded(cm, val_bytes) && guarded(okc, kc));
+            std::vector<uint8_t> sp1(pos_bytes), lp1(pos_bytes), cm1(val_bytes), ok1(kc);
+            check(gpbc_fr_find_common_dev(dS, n_sets, m, dL, al, d, kc, (uint32_t *)dSp, (uint32_t *)dLp, dC, (uint8_t *)dOk, nullptr));
+            HIP_OK(hipDeviceSynchronize());
+            HIP_OK(hipMemcpy(sp1.data(), dSp, pos_bytes, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(lp1.data(), dLp, pos_bytes, hipMemcpyDeviceToHost));
+            HIP_OK(hipMemcpy(cm1.data(), dC, val_bytes, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(ok1.data(), dOk, kc, hipMemcpyDeviceToHost));
+            EXPECT(std::memcmp(sp.data(), sp1.data(), pos_bytes) == 0 && std::memcmp(lp.data(), lp1.data(), pos_bytes) == 0);
+            EXPECT(std::memcmp(cm.data(), cm1.data(), val_bytes) == 0 && std::memcmp(okc.data(), ok1.data(), kc) == 0);
+            size_t kept = 0;
+            for (size_t j = 0; j < kc; j++) kept += ok1[j];
+            EXPECT(kept > 0 && kept < kc);                               // both verdicts occur
+        }
+        hipFree(dS); hipFree(dL); hipFree(dSp); hipFree(dLp); hipFree(dC); hipFree(dOk);
+        printf("sharded four-output host call identical to one _dev call: common attributes of %zu items, shared and per-item sets\n", kc);
+    }
     {   // a batch large enough for every shard to run PIPELINED (>= 2 x 131072 units per device: chunks on two streams, results
         // drained by a helper thread) against the same batch in slices small enough for the plain upload -> compute -> download
         const size_t NB = (size_t)(nd < 4 ? nd : 4) * 270000 + 17;     // (with more slots only the first ones get a pipelined share: the point is made with four)
