@@ -10,6 +10,9 @@ Batched form used here, bit-identical in its GT result:
   * pi_i = sum_j coef_j * [tau^j]_1 through the engine's G1 scalar-multiplication kernel and point-sum tree;
   * all items of the batch go through ONE multi_pair call (3 Miller loops + 1 final exponentiation per item) and one gt_div.
 Host orchestration only; all group arithmetic goes through the engine (`bn254`).
+
+Below the Decrypt forms: KeyGen, Encrypt and ComputeKey (afp25_bibe.go:146-173, 211-269, 327-334) for many identities, labels and
+messages at once, whose outputs are the operands of decrypt_batch_arrays / decrypt_batches_ragged.
 """
 import numpy as np
 
@@ -257,3 +260,216 @@ def decrypt_batches_ragged(engine, table, ids, counts, sk, C1, C2, D=None):
         return x if x.shape[0] == n else bufs.take(x, of_item)
     m = decrypt_batch_arrays(engine, per_item(D, "D"), pi, per_item(sk, "sk"), C1, C2)
     return bufs.view(m, n, 384) * bufs.view(ok, n, 1), ok
+
+
+# ----------------------------------------------------------------------------------------------- KeyGen, Encrypt, ComputeKey
+# bibe/afp25_bibe/afp25_bibe.go:146-173, 211-269, 327-334 — the rest of the scheme, for many identities, labels and messages at once.  With the
+# master key msk, the SRS secret tau, an identity id, a batch label t and randomness r1, r2 in Zr:
+#
+#     KeyGen       [tau^i]_1, i = 1 .. B     [tau]_2     [msk]_2
+#     Encrypt      C1 = ([r1]g2 + [r2][msk]_2,  [r1]([id]_2 - [tau]_2),  [-r2]g2)     C2 = M e(h(t), [msk]_2)^(-r2)
+#     ComputeKey   sk = [msk](D + h(t))
+#
+# Planners only: every stage is an engine entry that exists (fr_mul, g1 / g2_scalar_mul(_base), hash_to_g1, multi_pair_fixed_q, gt_inverse,
+# gt_exp, gt_mul, FixedBase.indexed, GTFixedBase.indexed).  Scalars are Python ints, 32-byte rows or tensors; with CUDA tensors nothing but
+# the inputs going in and the outputs coming out crosses PCIe.  The master PUBLIC key is a dict of host arrays under the reference struct's
+# field names — it is public, B * 64 + 256 bytes, and what srs_table above takes; the public values are put where a batch lives by the
+# functions that use them.  Secrets (msk, and tau inside keygen_seeded) stay of the kind they came in.
+MAX_B = 1024          # FR_POLY_MAX_B: the longest batch the polynomial kernels behind Digest and Decrypt take
+DST_BYTES_G1 = b"Hash Bytes To Element In G1"            # hash_to.DST_BYTES_G1, the tag of hash.BytesToG1 (afp25_bibe_utils.go:10-12)
+ROUTES = ("labels", "items")
+
+
+def _batch_size(B):
+    if not isinstance(B, (int, np.integer)) or isinstance(B, bool) or not 1 <= B <= MAX_B:
+        raise ValueError("invalid B")                                          # Setup, :114-117, and the polynomial kernels' limit
+    return int(B)
+
+
+def tau_powers(engine, tau, B):
+    """[B, 32]: tau^1 .. tau^B modulo r as canonical scalar rows, of the kind of tau (the tauPower chain of KeyGen, :157-162).  By doubling
+    where the scalar lives: P[0] = fr_mul(tau, 1), then P[m : 2m] = fr_mul(P[0 : m], P[m - 1]) with the second operand ONE row, broadcast
+    (P[m - 1] = tau^m), the last round cut to B — ceil(log2 B) + 1 fr_mul calls in all, and no Python integer when tau is a buffer."""
+    B = _batch_size(B)
+    tau = _plan.scalars(tau, _plan.like_of(tau), 1, "tau")
+    P = bufs.view(engine.fr_mul(tau, bufs.flat(bufs.put(_plan.scalar_rows([1]), tau))), 1, 32)
+    while P.shape[0] < B:
+        m = P.shape[0]
+        more = engine.fr_mul(bufs.flat(P[:min(m, B - m)]), bufs.flat(P[m - 1]))
+        P = bufs.cat([P, bufs.view(more, -1, 32)])
+    return P
+
+
+def keygen(engine, B, tau, msk):
+    """mpk (KeyGen, :146-173) as a dict of host arrays: G1ExpTauPowers [B, 64] = [tau]_1 .. [tau^B]_1, G2ExpTau [128] = [tau]_2, G2ExpMsk
+    [128] = [msk]_2.  The master secret key is the caller's msk.  tau, msk: one scalar each, of one kind.  B < 1 raises
+    ValueError("invalid B") as the reference's Setup does (:114-117), and so does B > 1024: the polynomial kernels behind Digest and
+    Decrypt take batches of at most 1024, the rule gwww25.keygen has.  Engine calls: tau_powers (fr_mul), ONE g1_scalar_mul_base over the
+    B powers, ONE g2_scalar_mul_base over (tau, msk).  The powers of tau are made where tau lives; only the public points come back."""
+    B = _batch_size(B)
+    like = _plan.like_of(tau, msk)
+    tau, msk = _plan.scalars(tau, like, 1, "tau"), _plan.scalars(msk, like, 1, "msk")
+    bufs.device_of(tau, msk)
+    powers = tau_powers(engine, tau, B)
+    in_g1 = engine.g1_scalar_mul_base(bufs.flat(powers))
+    in_g2 = bufs.view(engine.g2_scalar_mul_base(bufs.flat(bufs.cat([powers[:1], bufs.view(msk, 1, 32)]))), 2, 128)
+    host = lambda x, *shape: np.array(_plan.host(x), dtype=np.uint8, copy=True).reshape(*shape)
+    return {"G1ExpTauPowers": host(in_g1, B, 64), "G2ExpTau": host(in_g2[0], 128), "G2ExpMsk": host(in_g2[1], 128)}
+
+
+def keygen_seeded(engine, B, rng, like=None):
+    """(mpk, msk): keygen with the secrets drawn on the device.  ONE draw of two scalars in the reference's order, msk then tau (:147-154)
+    — one stream id; the order and the count are part of the interface: they make the key reproducible from the seed.  like: a buffer of
+    the kind msk is to be (None: a host array); msk comes back as its 32-byte row.  tau is used and dropped: with a CUDA `like` it is
+    drawn, raised to its powers and multiplied into the generators on the device and never becomes a host value.  A refused B draws
+    nothing.  The seed is key material: whoever holds it holds the master secret key and the trapdoor."""
+    B = _batch_size(B)
+    drawn = bufs.view(rng.scalars(np.zeros(0, dtype=np.uint8) if like is None else like, 2), 2, 32)
+    return keygen(engine, B, drawn[1], drawn[0]), bufs.copy(bufs.view(drawn[0], 32))          # a copy: msk does not keep the buffer tau sits in alive
+
+
+def encrypt_tables(engine, mpk):
+    """engine.FixedBase(g2=True) over (g2, [msk]_2, [tau]_2): with it every component of C1 is one indexed sum (encrypt_batch, tables=).
+    Built once per master public key (6 MiB of device memory); the caller closes it."""
+    _, g2 = engine.generators()
+    rows = [np.asarray(x, dtype=np.uint8).reshape(1, 128) for x in (g2, mpk["G2ExpMsk"], mpk["G2ExpTau"])]
+    return engine.FixedBase(np.concatenate(rows), g2=True)
+
+
+def label_points(engine, labels, msg_off=None):
+    """[L, 64]: h(t) = hash.BytesToG1(t) for every batch label (afp25_bibe_utils.go:10-12) — engine.hash_to_g1 under DST_BYTES_G1.
+    labels: a list of byte strings, or the concatenated bytes with msg_off (a device byte buffer with an int64 offset tensor gives a
+    tensor), exactly as bn254.hash_to_g1 takes them."""
+    return bufs.view(engine.hash_to_g1(labels, DST_BYTES_G1, msg_off), -1, 64)
+
+
+def label_bases(engine, mpk, points):
+    """[L, 384]: b_l = e(h(t_l), [msk]_2)^-1, the reference's b[1] (:227-234), for every label point.  ONE multi_pair_fixed_q over the
+    single shared Q = [msk]_2 with one-pair segments (its lines are computed once for all labels), then gt_inverse."""
+    if not _plan.is_buffer(points):
+        raise ValueError("points must be a uint8 array or a CUDA tensor")
+    L = bufs.nbytes(points) // 64
+    if bufs.nbytes(points) != L * 64:
+        raise ValueError("points are G1 points, rows of 64 bytes")
+    if not L:
+        return bufs.empty((0, 384), points)
+    q = _plan.public(mpk["G2ExpMsk"], 1, 128, points, "G2ExpMsk")
+    return bufs.view(engine.gt_inverse(bufs.flat(engine.multi_pair_fixed_q(bufs.flat(points), bufs.flat(q)))), L, 384)
+
+
+def _pairs_of(a, b, n):
+    """[n * 2 * 32] flat: the scalars (a[i], b[i]) of n two-term sums"""
+    return bufs.flat(bufs.cat([bufs.view(a, n, 1, 32), bufs.view(b, n, 1, 32)], 1))
+
+
+def encrypt_batch(engine, mpk, messages, ids, r1, r2, points, label_of=None, bases=None, tables=None, gt_table=None, route="labels"):
+    """(C1 [n, 3, 128], C2 [n, 384]) for n messages (GT elements) to n identities with the randomness r1, r2 (Encrypt, :211-269) — the
+    operands of decrypt_batch_arrays / decrypt_batches_ragged.  points: label_points' [L, 64]; label_of: a host integer array [n], the
+    label of every item as a row of points (None: one label for all, and then L must be 1; an entry outside 0 .. L - 1 is a ValueError
+    before any engine call).  ids, r1, r2: n scalars each.  n = 0 gives empty outputs.
+
+    C1 and C2 each by two routes, every combination the same bytes (affine points and GT elements are canonical, and e(P, Q)^k and
+    e([k] P, Q) are the same Fp12 element, as bf01.py relies on):
+
+      C1, tables=None   the reference's operations in its order: g2_scalar_mul_base(id) and g2_sub of [tau]_2; g2_scalar_mul of g2 by r1 and
+                        of [msk]_2 by r2, g2_add; g2_scalar_mul of [id]_2 - [tau]_2 by r1; g2_scalar_mul of -g2 by r2.  The reference's
+                        products with the two infinity entries of A (:218-220) and its power of b[0] = 1 (:258) have fixed bytes — the
+                        point at infinity, the one of GT — and are not computed.  With tensors this route also puts four public
+                        constants on the device per call — g2, -g2, [tau]_2, [msk]_2, 512 bytes from host arrays (generators, g2_neg,
+                        mpk) — besides the inputs; the tables route uploads [msk]_2 for C2 and its index rows, a few bytes.
+      C1, tables=       encrypt_tables(engine, mpk): three FixedBase.indexed calls with ONE periodic index row each,
+                        C1[0] = indexed([0, 1]; r1, r2), C1[1] = indexed([0, 2]; r1 id, -r1), C1[2] = indexed([0]; -r2), the scalars from
+                        fr_mul / fr_neg: no doubling and no variable base.
+      C2, "labels"      bases (label_bases' [L, 384]; computed here when None) gathered by label_of, gt_exp by r2, gt_mul with M; or with
+                        gt_table — an engine.GTFixedBase over the L bases, built by the caller — gt_table.indexed(label_of; r2, terms=1)
+                        and gt_mul: 32 Fp12 products per item and no squaring.  The table costs about 8 ms (for 1 base as for 256) and 4 MiB a
+                        base to build: it pays where a label serves thousands of items, not where every batch of B has a label of its own.
+      C2, "items"       no pairing per label and no power in GT: P_i = g1_scalar_mul(points[label_of[i]], -r2_i), ONE multi_pair_fixed_q
+                        against [msk]_2, gt_mul with M.  For batches whose labels are mostly distinct; bases and gt_table do not apply."""
+    if route not in ROUTES:
+        raise ValueError('route is "labels" or "items" (got %r)' % (route,))
+    if not _plan.is_buffer(messages) or not _plan.is_buffer(points):
+        raise ValueError("messages and points must be uint8 arrays or CUDA tensors")
+    n, L = bufs.nbytes(messages) // 384, bufs.nbytes(points) // 64
+    if bufs.nbytes(messages) != n * 384 or bufs.nbytes(points) != L * 64:
+        raise ValueError("messages are GT elements, rows of 384 bytes, and points G1 points, rows of 64")
+    if label_of is None:
+        if L != 1:
+            raise ValueError("label_of=None is one label for all: points must hold one point (got %d)" % L)
+    else:
+        label_of = np.asarray(label_of)
+        if label_of.dtype.kind not in "iu" or label_of.shape != (n,):
+            raise ValueError("label_of must be a host integer array of n = %d entries" % n)
+        label_of = label_of.astype(np.int64)
+        if n and (label_of.min() < 0 or label_of.max() >= L):
+            raise ValueError("label_of: every entry must be in 0 .. %d" % (L - 1))
+    if route == "items" and (bases is not None or gt_table is not None):
+        raise ValueError('bases and gt_table belong to route "labels"')
+    if tables is not None and (tables.nbase != 3 or not tables.g2):
+        raise ValueError("tables is encrypt_tables(engine, mpk): three G2 bases")
+    if gt_table is not None and gt_table.nbase != L:
+        raise ValueError("gt_table holds %d bases, the labels need %d" % (gt_table.nbase, L))
+    bufs.device_of(messages, points)
+    messages, points = bufs.view(messages, n, 384), bufs.view(points, L, 64)
+    ids, r1, r2 = (_plan.scalars(x, messages, n, name) for x, name in ((ids, "ids"), (r1, "r1"), (r2, "r2")))
+    if bases is not None:
+        bases = _plan.public(bases, L, 384, messages, "bases")
+    if not n:
+        return bufs.empty((0, 3, 128), messages), bufs.empty((0, 384), messages)
+    msk2 = bufs.flat(_plan.public(mpk["G2ExpMsk"], 1, 128, messages, "G2ExpMsk"))
+    if tables is None:
+        g2 = np.asarray(engine.generators()[1], dtype=np.uint8).reshape(128)
+        tau2 = bufs.flat(_plan.public(mpk["G2ExpTau"], 1, 128, messages, "G2ExpTau"))
+        gen, neg_gen = (bufs.flat(_plan.public(x, 1, 128, messages, "g2")) for x in (g2, engine.g2_neg(g2)))
+        a01 = engine.g2_sub(engine.g2_scalar_mul_base(ids), tau2)                                  # [id]_2 - [tau]_2
+        c10 = engine.g2_add(engine.g2_scalar_mul(gen, r1), engine.g2_scalar_mul(msk2, r2))
+        c11 = engine.g2_scalar_mul(bufs.flat(a01), r1)
+        c12 = engine.g2_scalar_mul(neg_gen, r2)
+    else:
+        row = lambda *index: _plan.index_rows(np.array([index]), messages)
+        r1id, nr1, nr2 = engine.fr_mul(r1, ids), engine.fr_neg(r1), engine.fr_neg(r2)
+        c10 = tables.indexed(row(0, 1), _pairs_of(r1, r2, n), terms=2)[0]
+        c11 = tables.indexed(row(0, 2), _pairs_of(r1id, nr1, n), terms=2)[0]
+        c12 = tables.indexed(row(0), bufs.flat(nr2), terms=1)[0]
+    C1 = bufs.cat([bufs.view(c, n, 1, 128) for c in (c10, c11, c12)], 1)
+    if route == "items":
+        mine = bufs.flat(points) if label_of is None else bufs.flat(bufs.take(points, label_of))   # one shared base, or one per scalar
+        P = engine.g1_scalar_mul(mine, bufs.flat(engine.fr_neg(r2)))
+        blind = engine.multi_pair_fixed_q(bufs.flat(P), msk2)
+    elif gt_table is not None:
+        index = np.zeros((1, 1), dtype=np.int64) if label_of is None else label_of.reshape(n, 1)        # one periodic row, or a row per item
+        blind = gt_table.indexed(_plan.index_rows(index, messages), r2, terms=1)[0]
+    else:
+        if bases is None:
+            bases = label_bases(engine, mpk, points)
+        mine = bufs.expand(bufs.view(bases, 1, 384), n, 384) if label_of is None else bufs.take(bufs.view(bases, L, 384), label_of)
+        blind = engine.gt_exp(bufs.flat(mine), r2)
+    return C1, bufs.view(engine.gt_mul(bufs.flat(blind), bufs.flat(messages)), n, 384)
+
+
+def encrypt_batch_seeded(engine, mpk, messages, ids, rng, points, label_of=None, bases=None, tables=None, gt_table=None, route="labels"):
+    """encrypt_batch with its randomness drawn on the device: TWO draws, r1 [n] then r2 [n], the reference's order (:237-244) — two stream
+    ids, none when n == 0 — of the kind the messages are; the order is part of the interface.  The return value is exactly
+    encrypt_batch's on the scalars drawn.  The seed is key material: whoever holds it can recompute r2 and with it every message."""
+    n = bufs.nbytes(messages) // 384
+    r1 = rng.scalars(messages, n)
+    return encrypt_batch(engine, mpk, messages, ids, r1, rng.scalars(messages, n), points, label_of=label_of, bases=bases, tables=tables,
+                         gt_table=gt_table, route=route)
+
+
+def compute_key_batch(engine, msk, D, points):
+    """sk [k, 64], sk_j = [msk](D_j + h(t_j)) for k (digest, label) pairs (ComputeKey, :327-334): g1_add, then g1_scalar_mul with msk
+    expanded to k rows.  D: [k, 64] as digests_ragged gives them; points: label_points' [k, 64], or one point for all; msk: one scalar."""
+    if not _plan.is_buffer(D) or not _plan.is_buffer(points):
+        raise ValueError("D and points must be uint8 arrays or CUDA tensors")
+    k = bufs.nbytes(D) // 64
+    if bufs.nbytes(D) != k * 64:
+        raise ValueError("D holds G1 points, rows of 64 bytes")
+    if bufs.nbytes(points) not in (64, k * 64):
+        raise ValueError("points must hold one point per digest (%d), or one for all" % k)
+    msk = _plan.scalars(msk, D, 1, "msk")
+    points = _plan._placed(points, D, "points")
+    if not k:
+        return bufs.empty((0, 64), D)
+    s = engine.g1_add(bufs.flat(D), bufs.flat(points))
+    return bufs.view(engine.g1_scalar_mul(bufs.flat(s), bufs.flat(bufs.expand(bufs.view(msk, 1, 32), k, 32))), k, 64)

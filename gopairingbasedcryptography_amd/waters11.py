@@ -31,7 +31,10 @@ unchanged and takes formula.padded(...) like any other block).
 
 Host orchestration only, engine-agnostic (every function takes the engine: `bn254`, or a stand-in with the same function names).
 Host arrays in give host arrays out; CUDA tensors in give CUDA tensors out, with only the key, the padded matrices, the mask and
-an index table going to the device."""
+an index table going to the device.
+
+Below Decrypt: Encrypt and KeyGenerate (:130-237), and at the end SetUp (:82-118) with the universe constructor of
+waters11_cpabe_utils.go:29-41."""
 import collections
 
 import numpy as np
@@ -39,6 +42,7 @@ import numpy as np
 from . import _buffers as bufs, _plan
 from ._plan import INDEX_NONE, NO_ATTRIBUTE      # noqa: F401 (INDEX_NONE: for callers that build index rows themselves)
 from .lw11 import reconstruction_weights
+from .sw05 import _power_of_pairing
 
 Padded = collections.namedtuple("Padded", "matrix rho rows cols")      # matrix [n, R, C, 32] uint8 scalars; rho [n, R] int64, -1 = padding
 
@@ -352,3 +356,71 @@ def keygen_batch(engine, g1_alpha, g1a, h, user_attrs, t, table=None):
     K = engine.g1_add(bufs.flat(bufs.expand(_plan.public(g1_alpha, 1, 64, t, "g1_alpha"), n, 64)), bufs.flat(pts[:, 0]))
     L = engine.g2_scalar_mul_base(bufs.flat(t))
     return bufs.view(K, n, 64), bufs.view(L, n, 128), pts[:, 1:], held
+
+
+# ------------------------------------------------------------------------------------------------ SetUp
+# cpabe/waters11/waters11_cpabe.go:82-118 and waters11_cpabe_utils.go:29-41.  The universe is a list of distinct integers in [0, 2^63), as
+# every function above takes attributes; the public parameters come back as host arrays — they are public, h is a dict of host rows in
+# encrypt_table's and keygen_batch's form, and every function above puts them where its batch lives — and g1^alpha of the kind the
+# secrets are.
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def universe_range(start, end):
+    """the attributes start .. end - 1 (NewWaters11CPABEInstanceByInt64Pair, waters11_cpabe_utils.go:29-41): end < start is a ValueError,
+    as there; end == start is the empty universe, which setup accepts.  Attributes here are integers in [0, 2^63), so a negative start
+    is refused where the reference would read it as r - |start|."""
+    if not _is_int(start) or not _is_int(end):
+        raise ValueError("start and end must be integers")
+    start, end = int(start), int(end)
+    if end < start:
+        raise ValueError("end must be greater than start")
+    if start < 0 or end > 1 << 63:
+        raise ValueError("attributes must be integers in [0, 2^63)")
+    return list(range(start, end))
+
+
+def _setup_universe(universe):
+    universe = list(universe)
+    if not all(_is_int(u) for u in universe):                                  # no int(): 3.7 is not attribute 3, True not attribute 1
+        raise ValueError("the universe must hold distinct integers in [0, 2^63)")
+    attrs = sorted(int(u) for u in universe)
+    if any(not 0 <= u < 1 << 63 for u in attrs) or len(set(attrs)) != len(attrs):
+        raise ValueError("the universe must hold distinct integers in [0, 2^63)")
+    return attrs
+
+
+def setup(engine, universe, alpha, a, tau, gt_table=None):
+    """(pp, msk) from the secrets (SetUp, waters11_cpabe.go:82-118): pp = {"g1a": [a] g1 (64 B), "e_alpha": e(g1, g2)^alpha (384 B),
+    "h": {u: [tau_u] g1 (64 B)}} as host arrays — exactly the (g1a, e_alpha, h) arguments of encrypt_batch, keygen_batch and encrypt_table
+    — and msk = {"g1_alpha": [alpha] g1 (64 B)}, keygen_batch's g1_alpha, of the kind the secrets are.  universe: distinct integers in
+    [0, 2^63), in any order (universe_range makes one); alpha, a: one scalar each; tau: one scalar per attribute, tau[i] belonging to the
+    i-th attribute in ASCENDING order, whatever order the universe was given in (Python ints, 32-byte rows or CUDA tensors, all of one
+    kind).  The empty universe gives h = {}.  gt_table: an engine.GTFixedBase whose base 0 is e(g1, g2), built once by the caller;
+    e_alpha then comes from its indexed products and is the same bytes.  Engine calls: ONE g1_scalar_mul_base over (a, alpha, tau ...);
+    pair_batch on the generators and gt_exp, or gt_table.indexed with one term."""
+    attrs = _setup_universe(universe)                                          # before anything touches the engine
+    U = len(attrs)
+    like = _plan.like_of(alpha, a, tau)
+    alpha, a, tau = _plan.scalars(alpha, like, 1, "alpha"), _plan.scalars(a, like, 1, "a"), _plan.scalars(tau, like, U, "tau")
+    bufs.device_of(alpha, a, tau)
+    pts = bufs.view(engine.g1_scalar_mul_base(bufs.flat(bufs.cat([a, alpha, tau]))), 2 + U, 64)
+    e_alpha = _power_of_pairing(engine, alpha, like, gt_table)
+    host = np.array(_plan.host(pts), dtype=np.uint8, copy=True)
+    pp = {"g1a": host[0], "e_alpha": np.array(_plan.host(e_alpha), dtype=np.uint8, copy=True).reshape(384), "h": {u: host[2 + i] for i, u in enumerate(attrs)}}
+    return pp, {"g1_alpha": bufs.view(pts[1], 64)}
+
+
+def setup_seeded(engine, universe, rng, like=None, gt_table=None):
+    """setup with the secrets drawn on the device: rng is an rng.Randomness over the engine.  The draws, in this order (the order is part
+    of the interface: it is what makes the keys reproducible from the seed): alpha, then a, then tau [U] — the reference's order
+    (:84-107), three stream ids, two for an empty universe.  The reference draws tau_u while it ranges over a Go map, in an order that
+    differs from run to run; here tau_u belongs to the u-th attribute in ascending order.  A refused universe draws nothing.  like: a
+    buffer of the kind the master key is to be (None: a host array).  The seed is key material: whoever holds it holds the master key."""
+    attrs = _setup_universe(universe)
+    like = np.zeros(0, dtype=np.uint8) if like is None else like
+    alpha = rng.scalars(like, 1)
+    a = rng.scalars(like, 1)
+    tau = rng.scalars(like, len(attrs))
+    return setup(engine, attrs, alpha, a, tau, gt_table=gt_table)
