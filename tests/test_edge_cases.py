@@ -129,8 +129,16 @@ def test_point_sums_of_repeated_and_opposite_points(eng, oracle):
 def test_fixed_base_and_bucket_sums_with_repeated_bases(eng, oracle):
     """Sums of multiples whose TERMS coincide or cancel: the same base listed twice with equal scalars (the accumulator meets its own
     addend), with opposite scalars (infinity mid-sum), the negated base with the same scalar, bases at infinity, all scalars zero —
-    through the fixed-base tables (few bases) and the bucket method (>= 16 384 terms)."""
+    through the fixed-base tables (few bases) and a 16 500-term call.  That call does NOT run the bucket method: its scalars come from a pool
+    of 8 values, so every window has about 2 000 terms per bucket, far above the 288 msm_run accepts, and the call takes the per-term
+    path (asserted below through gpbc_msm_stats).  The bucket method itself meets such runs in tests/test_bucket_msm_structured_gpu.py."""
+    import ctypes
     import torch
+    from gopairingbasedcryptography_amd import _lib
+    def paths():                     # (bucket runs, skew fallbacks) so far
+        x, y = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _lib.check(_lib.load().gpbc_msm_stats(ctypes.byref(x), ctypes.byref(y)))
+        return x.value, y.value
     g1, g2 = eng.generators()
     for gen, mul, summ, msm, w, is_g2 in ((g1, eng.g1_scalar_mul, eng.g1_sum, eng.g1_scalar_mul_sum, 64, False), (g2, eng.g2_scalar_mul, eng.g2_sum, eng.g2_scalar_mul_sum, 128, True)):
         A = np.asarray(mul(gen, _kb([o.bench_scalar("fbr", 0)]))).reshape(w)
@@ -151,8 +159,8 @@ def test_fixed_base_and_bucket_sums_with_repeated_bases(eng, oracle):
             assert (got[i] == want).all(), (w, i, "fixed base")
             assert (np.asarray(msm(bases.reshape(-1), _kb(r))).reshape(w) == want).all(), (w, i, "small sum of multiples")
         fb.close()
-        # the bucket method: 16 500 terms over FOUR distinct points and their negatives, scalars drawn from a handful of values, so that
-        # buckets hold runs of equal and of opposite points (each bucket's running sum meets doublings and infinities)
+        # 16 500 terms over FOUR distinct points and their negatives, scalars drawn from a handful of values: the histogram of the
+        # bucket method sees buckets of about 2 000 terms and hands the call to the per-term path (scalar multiplications + sum tree)
         rng = np.random.default_rng(2024)
         n = 16500
         pool_pts = np.stack([A, nA, B, _neg(eng, B, w), inf])
@@ -161,7 +169,10 @@ def test_fixed_base_and_bucket_sums_with_repeated_bases(eng, oracle):
         ks = pool_k[rng.integers(0, 8, size=n)]
         dp, dk = torch.from_numpy(np.ascontiguousarray(pts)).cuda(), torch.from_numpy(np.ascontiguousarray(ks)).cuda()
         want = summ(mul(dp.reshape(-1), dk.reshape(-1))).cpu().numpy().reshape(w)
-        assert (msm(dp.reshape(-1), dk.reshape(-1)).cpu().numpy().reshape(w) == want).all(), (w, "bucket / per-term path")
+        before = paths()
+        got = msm(dp.reshape(-1), dk.reshape(-1)).cpu().numpy().reshape(w)
+        assert paths() == (before[0], before[1] + 1), (w, "scalars from a pool of 8 values must take the per-term path, not the bucket method", before, paths())
+        assert (got == want).all(), (w, "per-term path of the 16 500-term call")
         # ... and against the restatement on a 600-term slice
         sl = slice(0, 600)
         o_terms = (oracle.g2_scalar_mul if is_g2 else oracle.g1_scalar_mul)(pts[sl].reshape(-1), ks[sl].reshape(-1), threads=16)
