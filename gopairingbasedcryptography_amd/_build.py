@@ -18,7 +18,7 @@ STAMP = os.path.join(HERE, "libgpbc_bn254.buildhash")
 # their own and not beside the code they call: the head of each file.)
 UNITS = ["gpbc_core.hip", "gpbc_pairing.hip", "gpbc_curve.hip", "gpbc_wire.hip", "gpbc_msm.hip", "gpbc_group.hip", "gpbc_fr.hip", "gpbc_gtmexp.hip", "gpbc_gmsm.hip", "gpbc_subset.hip",
          "gpbc_hash.hip", "gpbc_member.hip", "gpbc_gtfixed.hip", "gpbc_openings.hip", "gpbc_rows.hip", "gpbc_rows_g2.hip"]
-HEADERS = ["gpbc_common.hpp", "fe29.hip.hpp", "tower29.hip.hpp", "tower29_pair.hip.hpp", "curve29.hip.hpp", "pairing29.hip.hpp", "pairing29_pair.hip.hpp", "wide29.hip.hpp", "curve29_quad.hip.hpp", "curve29_oct.hip.hpp",
+HEADERS = ["gpbc_common.hpp", "fe29.hip.hpp", "tower29.hip.hpp", "tower29_pair.hip.hpp", "curve29.hip.hpp", "pairing29.hip.hpp", "pairing29_pair.hip.hpp", "wide29.hip.hpp", "wide_lds29.hip.hpp", "curve29_quad.hip.hpp", "curve29_oct.hip.hpp",
            "wire29.hip.hpp", "h2c29.hip.hpp", "xmd29.hip.hpp", "msm29.hip.hpp", "group29.hip.hpp", "fr29.hip.hpp", "segred29.hip.hpp", "gtmexp29.hip.hpp", "gmsm29.hip.hpp", "subset29.hip.hpp", "transcript29.hip.hpp", "chacha29.hip.hpp", "share29.hip.hpp", "recon29.hip.hpp", "forest29.hip.hpp", "select29.hip.hpp", "formula29.hip.hpp", "fbindex29.hip.hpp", "lsss29.hip.hpp", "mask29.hip.hpp", "frdot29.hip.hpp", "member29.hip.hpp", "gtfixed29.hip.hpp", "openings29.hip.hpp", "rows29.hip.hpp", "rows29_g2.hip.hpp", "bn254_constants.hip.hpp", "bn254_constants29.hip.hpp"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
 # host-only measurement program over the C ABI (bench.py runs it: calls/s of concurrent one-element calls); built next to the library

@@ -491,7 +491,9 @@ GPBC_INLINE Fe fe_halve(const Fe &a) {
 }
 
 // Value reduction without a multiplication: subtract the table row k*p with k = round(top limb / p_8).  Input: weakly normalised,
-// |value| < 256p.  Output: |value| < 0.51p, limbs 0..7 within +-(2^29 + 2^9).  Used where a small-constant multiple
+// |value| < 256p.  Output: |value| < 0.51p; a limb 0..7 is the input limb minus a row limb in [0, 2^29): within +-(2^29 + 2^9) for input
+// limbs within [-2^9, 2^29 + 2^9], down to -2^30 - 2^10 for the signed limbs the input class also admits (tests/test_field_primitives.py
+// runs both, over every row of the table).  Used where a small-constant multiple
 // (the non-residue 9+i) would otherwise let the worst-case magnitude compound through the tower.
 // k * p for k in [-256, 256] (row k + 256): limbs 0..7 in [0, 2^29), top limb signed (tools/gen_constants.py).  21 KB,
 // resident in the caches: k is almost always within a few units of zero.
@@ -581,8 +583,9 @@ GPBC_INLINE Fe fe_reduce_arith(const Fe &a) {
 }
 
 // norm(a - k p) with k p formed arithmetically: the value reduction IN FRONT of the normalisation, so that the result comes out of
-// fe_norm (limbs 0..7 non-negative, "positive-normalised": what the subtractive Karatsuba forms of the towers need) instead of out
-// of a subtraction (signed limbs).  a: any limbs for which a_i - 2^29 - carry stays inside int32 (the interval harness checks);
+// fe_norm ("positive-normalised": limb 0 in [0, 2^29), limbs 1..7 a masked limb plus the carry of the limb below, which for input limbs
+// within +-(2^29 + 2^10) is -3 .. 1 — what the subtractive Karatsuba forms of the towers need) instead of out of a subtraction (limbs
+// down to -2^30).  a: any limbs for which a_i - 2^29 - carry stays inside int32 (the interval harness checks);
 // k from the un-normalised top limb — what still sits in the lower limbs as carries is worth less than 2^-20 p.
 GPBC_INLINE Fe fe_reduce_arith_norm(const Fe &a) {
     constexpr int32_t P8 = f29_p(NL - 1);
@@ -637,7 +640,8 @@ GPBC_INLINE Fe fe_canonical(const Fe &a) {
     return r;
 }
 // x == 0 (mod p) for a weakly normalised x with |value| < 128p.  If x = k p then its top limb lies within |k| + 2
-// of k * p_8, so one float quotient and one integer remainder rule out all but ~2^-13 of the non-zero values; the
+// of k * p_8 (closer: p mod 2^232 is 0.449 * 2^232, so within 0.449 |k| + 2 — at most 59 for |k| <= 127, and the window of 136 below
+// has room to spare), so one float quotient and one integer remainder rule out all but ~2^-13 of the non-zero values; the
 // survivors take the exact (slow, divergent) path: one Montgomery product by R' mod p, canonical form, compare.
 GPBC_INLINE bool fe_is_zero(const Fe &a) {
 #ifdef GPBC_BOUNDS

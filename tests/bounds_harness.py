@@ -36,6 +36,7 @@ HC_SIGNATURES = {
     "hc_stats": "v:p", "hc_fr_forest_plan": "i:ppzppp", "hc_fr_share_forest": "i:ppzpppzppp", "hc_fr_forest_weights": "i:ppzppzppp",
     "hc_g1_is_on_curve": "v:pzp", "hc_g2_is_in_subgroup": "v:pzpi", "hc_gt_is_in_subgroup": "v:pzpi", "hc_gt_fb_build": "i:pzp",
     "hc_gt_fb_indexed": "i:pzpzzpzpp", "hc_fr_poly_from_roots_segments": "i:ppzzp", "hc_fb_openings": "i:ipzpppzzpp", "hc_opn_shape": "v:zzp",
+    "hc_fe_primitive": "i:ippzippp",
 }
 # every pointer is a c_void_p: it takes ints, None, ctypes arrays and string buffers, byref() and ndarray.ctypes.data_as() alike
 CTYPES = {"p": ctypes.c_void_p, "z": ctypes.c_size_t, "i": ctypes.c_int, "q": ctypes.c_uint64, "d": ctypes.c_double, "v": None}

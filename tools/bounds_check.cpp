@@ -1643,4 +1643,43 @@ int hc_fb_openings(int is_g2, const uint8_t *B, size_t nbase, const uint8_t *coe
     return rc;
 }
 void hc_opn_shape(size_t nbase, size_t n, size_t *out2) { opn_shape(nbase, n, out2, out2 + 1); }
+// The data-dependent routines of fe29.hip.hpp on RAW limbs (tests/limb_cases.py, tests/test_field_primitives.py): n rows of nine int32,
+// given the interval class the caller names — limbs 0..7 within +-(2^29 + slack) (fe_cyclo_out, op 6: within [-slack, 2^29 + slack], the
+// class its comment states for t and x), the top limb as it stands, |value| <= vb p with vb[2 i] for row i of a and vb[2 i + 1] for
+// row i of b (only op 6 reads b).  op: 0 fe_norm, 1 fe_mul8_norm, 2 fe_halve, 3 fe_reduce, 4 fe_reduce_arith, 5 fe_reduce_arith_norm,
+// 6 fe_cyclo_out(a, b), 7 fe_canonical, 8 fe_is_zero (flags_out[i]; its out row is zero).  Every routine checks its own input class and
+// that its tracked intervals hold the actual output (check_limbs).  -1: no such op.
+static Fe fe_raw_class(const int32_t *w, double lo, double hi, double vb) {
+    Fe r;
+    for (int i = 0; i < NL; i++) { r.v[i] = w[i]; r.lo[i] = lo; r.hi[i] = hi; }
+    r.lo[NL - 1] = r.hi[NL - 1] = (double)w[NL - 1];
+    r.vb = vb;
+    check_limbs(r, "raw limb outside the class the caller named");
+    return r;
+}
+int hc_fe_primitive(int op, const int32_t *a_limbs, const int32_t *b_limbs, size_t n, int slack, const double *vb, int32_t *out_limbs, int32_t *flags_out) {
+    if (op < 0 || op > 8) return -1;
+    const double hi = 536870912.0 + (double)slack, lo = op == 6 ? -(double)slack : -hi;
+    for (size_t i = 0; i < n; i++) {
+        const Fe a = fe_raw_class(a_limbs + NL * i, lo, hi, vb[2 * i]);
+        Fe r = fe_zero();
+        int flag = 0;
+        switch (op) {
+        case 0: r = fe_norm(a); break;
+        case 1: r = fe_mul8_norm(a); break;
+        case 2: r = fe_halve(a); break;
+        case 3: r = fe_reduce(a); break;
+        case 4: r = fe_reduce_arith(a); break;
+        case 5: r = fe_reduce_arith_norm(a); break;
+        case 6: r = fe_cyclo_out(a, fe_raw_class(b_limbs + NL * i, lo, hi, vb[2 * i + 1])); break;
+        case 7: r = fe_canonical(a); break;
+        default: flag = fe_is_zero(a) ? 1 : 0; break;
+        }
+        check_limbs(r, "fe primitive output");
+        for (int j = 0; j < NL; j++) out_limbs[NL * i + j] = r.v[j];
+        flags_out[i] = flag;
+    }
+    stats_flush();
+    return 0;
+}
 }
