@@ -24,7 +24,7 @@ HC_SIGNATURES = {
     "hc_g1_mul": "v:ppzp", "hc_g2_mul": "v:ppzp", "hc_glv_split": "v:pzp", "hc_g2_mul_glv": "v:ppzp", "hc_gls_split": "v:pzp", "hc_fp_mul": "v:ppzp",
     "hc_fp_inv": "v:pzpp", "hc_fp_legendre": "v:pzp", "hc_gt_mul": "v:ppzp", "hc_gt_div": "v:ppzp", "hc_gt_inv": "v:pzp", "hc_gt_sqr": "v:pzpi",
     "hc_pair_lanes": "v:ppzpi", "hc_sparse_products": "v:ppzipp", "hc_pair_lanes_multi": "v:ppzp", "hc_pair_fixed_q": "v:ppzpi",
-    "hc_gt_pair_ops": "v:ppzppppp", "hc_gt_exp_pair": "v:ppzp", "hc_gt_multi_exp_pair": "v:ppzpzzp", "hc_wire_encode": "v:ipzip",
+    "hc_gt_pair_ops": "v:ppzppppp", "hc_gt_exp_pair": "v:ppzp", "hc_final_exp_forms": "v:pzpi", "hc_gt_is_cyclotomic": "v:pzp", "hc_gt_multi_exp_pair": "v:ppzpzzp", "hc_wire_encode": "v:ipzip",
     "hc_wire_decode": "v:ipizpp", "hc_hash_g1_gt_gt_to_fr": "v:pppzp", "hc_sha256": "v:ppzzip", "hc_fe_sqrt": "v:pzpp", "hc_f2_sqrt": "v:pzpp",
     "hc_map_fields": "v:ipzp", "hc_g1_fb_msm": "v:pzpzp", "hc_group_op": "i:iippzzpi", "hc_group_k": "i:i", "hc_msm": "v:ippzip",
     "hc_fr_op": "i:ippzzpi", "hc_fr_inv_k": "i:", "hc_fr_poly_from_roots": "i:pzzp", "hc_fr_poly_quotients": "i:ppzzzpp",

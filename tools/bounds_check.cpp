@@ -575,6 +575,50 @@ void hc_gt_exp_pair(const uint8_t *A, const uint8_t *K, size_t n, uint8_t *out) 
         t1.join();
     }
 }
+// The final exponentiation of the lane-pair form (k_final_exp: final_exp_pair) and of the latency form (k_final_exp_wide:
+// wide_final_exp) on ANY Fp12 value, as gpbc_final_exp hands it over: zero, one, subfield elements and elements already in GT
+// included, which no Miller loop produces (hc_pair_lanes / hc_pair_wide reach these functions only behind one).
+void hc_final_exp_forms(const uint8_t *F, size_t n, uint8_t *out, int wide) {
+    for (size_t i = 0; i < n; i++) {
+        if (wide) {
+            WideHost m;
+            for (int c = 0; c < 6; c++) m.s[wv(0) + c] = f2_load(F + 384 * i + 64 * c);
+            wide_final_exp(m);
+            for (int c = 0; c < 6; c++) f2_store(out + 384 * i + 64 * c, m.s[c]);
+            stats_flush();
+            continue;
+        }
+        PairRendezvous rv;
+        auto lane = [&](bool odd) {
+            PairHost x{odd, &rv};
+            size_t o = 384 * i + (odd ? 192 : 0);
+            f6_store(out + o, final_exp_pair(x, f6_load(F + o)));
+            stats_flush();
+        };
+        std::thread t1(lane, true);
+        lane(false);
+        t1.join();
+    }
+}
+// The predicate that chooses the squarings of GT.Exp, as each form answers it: out[3 i] the even lane's and out[3 i + 1] the odd
+// lane's f12p_is_cyclotomic (documented to be the same on both), out[3 i + 2] wide_is_cyclotomic with the scratch values wide_exp256 gives it
+void hc_gt_is_cyclotomic(const uint8_t *A, size_t n, uint8_t *out) {
+    for (size_t i = 0; i < n; i++) {
+        PairRendezvous rv;
+        auto lane = [&](bool odd) {
+            PairHost x{odd, &rv};
+            out[3 * i + (odd ? 1 : 0)] = f12p_is_cyclotomic(x, f6_load(A + 384 * i + (odd ? 192 : 0))) ? 1 : 0;
+            stats_flush();
+        };
+        std::thread t1(lane, true);
+        lane(false);
+        t1.join();
+        WideHost m;
+        for (int c = 0; c < 6; c++) m.s[wv(1) + c] = f2_load(A + 384 * i + 64 * c);
+        out[3 * i + 2] = wide_is_cyclotomic(m, wv(1), wv(8), wv(9)) ? 1 : 0;
+        stats_flush();
+    }
+}
 // segmented GT multi-exponentiation exactly as gpbc_gt_multi_exp_dev (csrc/gpbc_gtmexp.hip) runs it: the plan and the level walk of
 // csrc/segred29.hip.hpp with GT_MEXP_SHAPE (segred_piece per piece, the function the kernel calls, so a table is clamped as on the
 // device; the value buffers sized by segred_plan), the same lane functions (f12p_multi_exp, f12p_product for K = null and for the
